@@ -10,12 +10,19 @@ collective; the voice table is broadcast once (RCCL ncclBroadcast inside the C A
 the timed region.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--utts U] [--voices V] [--mode exact|fast]
+                    [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 `--gpus N` with N > 1 and no launcher (WORLD_SIZE unset): this process starts N rank processes
 itself (before it touches the GPU or loads the library), waits for them and relays rank 0's
 line; any failing rank makes the whole run fail.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what is
+measured beside the headline, after the timed region: the same batch in fast mode (`fast_mode`),
+BASELINE configs 4 and 2 and the speech-like corpus (`other_configs`), and the oracle on the CPU
+(`cpu_baseline`, `cpu_all_cores`).  `--dump-outputs DIR` writes what the last timed step computed
+(see dump_outputs) before anything else runs on the device.
 """
 import argparse
 import hashlib
@@ -37,6 +44,34 @@ HBM_PEAK_GBS = 8000.0        # MI355X HBM3E spec peak (/opt/skills/guides/MI355X
 ALG_BYTES_PER_SAMPLE = 4.01  # 4 B f32 written + <= 0.01 B of segment/voice input
 TRAFFIC_FILE = os.path.join(ROOT, "profiles", "traffic.json")
 RCCL_TIMEOUT_S = float(os.environ.get("GRAIL_BENCH_RCCL_TIMEOUT", "240"))
+DUMP_ROW_BYTES = 48 << 20    # --dump-outputs: sampled PCM rows of all ranks together (the whole dump stays under 64 MB)
+DUMP_SEED = 20261016         # --dump-outputs: which rows are sampled; fixed, so that two builds dump the same rows
+
+
+def dump_outputs(out_dir, ctx, d_out, stride, out_len, first, rank, world, pcm16):
+    """`--dump-outputs DIR`: what the timed path handed its caller in the last timed step, as .npy files.
+    lengths.npy   every utterance's sample count (float64, one per utterance of this rank's shard);
+    pcm.npy       a fixed, seeded sample of the PCM rows (float32, rows x out_stride, zero past each row's
+                  length; i16 rows under --pcm16 as their integer values), at most DUMP_ROW_BYTES over all ranks;
+    pcm_utterances.npy  the global utterance index of each sampled row (float64).
+    With more than one rank every rank writes its own files, prefixed rank<r>_."""
+    n_utt = len(out_len)
+    n_rows = max(1, min(n_utt, DUMP_ROW_BYTES // world // (stride * 4)))
+    pick = np.sort(np.random.default_rng(DUMP_SEED).choice(n_utt, n_rows, replace=False))
+    itemsize = 2 if pcm16 else 4
+    row = np.empty(stride, dtype=np.int16 if pcm16 else np.float32)
+    rows = np.zeros((n_rows, stride), dtype=np.float32)
+    for i, u in enumerate(pick):
+        ctx.d2h(row, d_out, stride * itemsize, offset=int(u) * stride * itemsize)
+        n = int(out_len[u])
+        rows[i, :n] = row[:n]
+    prefix = f"rank{rank}_" if world > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, prefix + "lengths.npy"), out_len.astype(np.float64))
+    np.save(os.path.join(out_dir, prefix + "pcm.npy"), rows)
+    np.save(os.path.join(out_dir, prefix + "pcm_utterances.npy"), (pick + first).astype(np.float64))
+
+
 def kernel_sources():
     """Every device-side source of the library: the kernel template and its instantiation units
     (csrc/*.hip) and the headers they include (csrc/*.h), sorted by name.  (Host-only code is
@@ -253,13 +288,18 @@ def main():
     ap.add_argument("--mode", choices=["exact", "fast", "mid"], default="exact",
                     help="arithmetic of the timed region: exact (bit-identical to the reference, the "
                          "headline) or fast (stated tolerance, DESIGN.md §Fast mode)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the fast leg, the other configs and the CPU baselines "
+                         "(each where its own option's default turns it on)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps: write the last step's rows (a fixed sample) and lengths as DIR/*.npy")
     ap.add_argument("--fast-leg", type=int, default=-1, choices=[-1, 0, 1],
                     help="with --mode exact: also time the same batch in fast mode after the timed "
-                         "region and report it as `fast_mode` (default: on at N=1)")
+                         "region and report it as `fast_mode` (default: on at N=1 with --full)")
     ap.add_argument("--other-configs", type=int, default=-1, choices=[-1, 0, 1],
                     help="after the timed region and the fast leg: BASELINE configs 4 (65 536 utterances x 8 presets) and 2 "
                          "(4 096 utterances) and the speech-like corpus (65 536), exact and fast, a few steps each, reported as `other_configs` (default: "
-                         "on for the default config-3 run at N=1)")
+                         "on for the default config-3 run at N=1 with --full)")
     ap.add_argument("--corpus", default="aligned", choices=["aligned", "speech"],
                     help="aligned: the BASELINE corpus (four segments of 0.5 s per utterance, the headline); speech: the "
                          "speech-like corpus of grail_hip/workload.py (8 - 32 phonemes of 40 - 160 ms, 0.5 - 3.8 s) as the timed "
@@ -287,9 +327,11 @@ def main():
                          "(counter passes: only the measured kernel should appear)")
     ap.add_argument("--rccl-diagnose", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-utts", type=int, default=1536,
-                    help="utterances for the CPU baseline (0 = skip); 1536 is ~11 s of CPU on one "
+                    help="utterances for the CPU baseline of a --full run (0 = skip); 1536 is ~11 s of CPU on one "
                          "thread of the GPU box's host (samples/s does not depend on it)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.config == 2:
         args.utts, args.voices = 4096, 1
     elif args.config == 3:
@@ -499,6 +541,8 @@ def main():
     out_len = np.zeros(n_utt, dtype=np.uint32)
     ctx.d2h(out_len, d_len, n_utt * 4)
     samples_per_step = int(out_len.astype(np.uint64).sum())
+    if args.dump_outputs:     # before --verify and the --full legs, which render into the same rows
+        dump_outputs(args.dump_outputs, ctx, d_out, stride, out_len, first, rank, world, args.pcm16)
     slow = ctx.get_option("slow_division_wave_steps")
     kernel_symbol = ctx.last_kernel_name()
     launch_info = {"formants_laid_out": ctx.get_option("last_launch_formants"),
@@ -617,7 +661,7 @@ def main():
 
     # Outside the timed region: the same batch in fast mode (stated tolerance), its own roofline.
     fast_leg = None
-    want_fast_leg = (args.fast_leg == 1) or (args.fast_leg == -1 and world == 1)
+    want_fast_leg = (args.fast_leg == 1) or (args.fast_leg == -1 and args.full and world == 1)
     if args.mode == "exact" and want_fast_leg and rank == 0 and not args.pcm16:
         ctx.set_option("arithmetic", 1)
         step()
@@ -649,7 +693,7 @@ def main():
     # of their own (the voice table of the timed context stays what it is), exact and fast — the numbers the headline is
     # quoted beside (config 4: all eight formants live; config 2: a batch that leaves most lanes of the device idle).
     other_configs = None
-    want_other = (args.other_configs == 1) or (args.other_configs == -1 and world == 1 and args.mode == "exact" and
+    want_other = (args.other_configs == 1) or (args.other_configs == -1 and args.full and world == 1 and args.mode == "exact" and
                                                  n_utt == 65536 and n_voices == 1 and not args.pcm16 and args.lanes == 0)
     if want_other and rank == 0 and world == 1 and args.corpus == "aligned":
         other_configs = {}
@@ -821,7 +865,7 @@ def main():
             line["fast_mode"] = fast_leg
         if other_configs is not None:
             line["other_configs"] = other_configs
-        if world == 1 and args.cpu_utts > 0:
+        if args.full and world == 1 and args.cpu_utts > 0:
             line["cpu_baseline"] = cpu_baseline(args.cpu_utts, voices, W)
             line["speedup_vs_cpu_1thread"] = value / line["cpu_baseline"]["value"]
             # like for like: the CPU baseline evaluates all eight formants; so does config 4 (the headline skips four dead ones)

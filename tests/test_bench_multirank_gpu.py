@@ -77,7 +77,7 @@ def test_require_rccl_fails_loudly_when_the_ranks_cannot_meet(built):
 
 def test_single_gpu_verify_and_fast_leg(built):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--utts", "4096",
-           "--verify", "--cpu-utts", "0"]
+           "--verify", "--cpu-utts", "0", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     d = _one_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600))
     assert d["n_gpus"] == 1 and d["verify"]["mismatches"] == 0
@@ -86,6 +86,38 @@ def test_single_gpu_verify_and_fast_leg(built):
     assert d["config"]["arithmetic"] == "exact"
     assert d["fast_mode"]["value"] > 0 and "FAST" in d["fast_mode"]["kernel"]
     assert d["rccl"]["ranks"] == 0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_its_last_step(built, tmp_path):
+    """Without --full the line carries no fast leg, other configs or CPU baselines.  --dump-outputs writes the last
+    timed step's lengths and a seeded sample of its rows, under 64 MB; in exact mode those rows are the oracle's bits."""
+    import numpy as np
+
+    import oracle_lib as O
+    from grail_hip import workload as W
+    n_utt = 4096
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--utts", str(n_utt),
+           "--dump-outputs", str(tmp_path)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    d = _one_line(subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["dtype"] == "f32"
+    assert not {"fast_mode", "other_configs", "cpu_baseline", "cpu_all_cores"} & set(d)
+    assert sorted(os.listdir(tmp_path)) == ["lengths.npy", "pcm.npy", "pcm_utterances.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in os.listdir(tmp_path)) <= 64 << 20
+    lengths, rows = np.load(tmp_path / "lengths.npy"), np.load(tmp_path / "pcm.npy")
+    pick = np.load(tmp_path / "pcm_utterances.npy").astype(np.int64)
+    assert lengths.dtype == np.float64 and rows.dtype == np.float32 and lengths.shape == (n_utt,)
+    assert int(lengths.sum()) == d["config"]["samples_per_step_per_gpu"]
+    assert len(pick) == len(rows) > 1 and np.all(np.diff(pick) > 0)
+    stride = d["config"]["out_stride"]
+    segs, offs, vids, seeds = W.make_batch(n_utt)
+    voices = [O.Voice.from_buffer_copy(bytes(v)) for v in W.single_voice()]
+    ref, ref_len = O.synthesize_batch(voices, segs.reshape(n_utt, -1)[pick].reshape(-1),
+                                      offs[: len(pick) + 1], vids[pick], seeds[pick], stride)
+    assert np.array_equal(ref_len, lengths[pick])
+    for i, n in enumerate(ref_len):
+        assert np.array_equal(rows[i, :n].view(np.uint32), ref[i, :n].view(np.uint32)), f"utterance {pick[i]}"
+        assert not rows[i, n:].any()
 
 
 @pytest.mark.parametrize("utts", [4096, 65536])

@@ -7,22 +7,22 @@ root=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}; export TMPDIR=/tmp; 
 out=gpurun_out/$tag; mkdir -p $out
 python3 tools/collect_counters.py $out/traffic.json > $out/collect_counters.log 2>&1
 cp $out/traffic.json profiles/traffic.json            # so that the bench lines below carry the counters
-python3 bench.py > $out/bench_n1.json 2> $out/bench_n1.err
-python3 bench.py --config 4 --cpu-utts 0 > $out/bench_n1_config4.json 2>/dev/null
-python3 bench.py --config 2 --cpu-utts 0 > $out/bench_n1_config2.json 2>/dev/null
+python3 bench.py --full > $out/bench_n1.json 2> $out/bench_n1.err
+python3 bench.py --full --config 4 --cpu-utts 0 > $out/bench_n1_config4.json 2>/dev/null
+python3 bench.py --full --config 2 --cpu-utts 0 > $out/bench_n1_config2.json 2>/dev/null
 python3 bench.py --mode fast --cpu-utts 0 > $out/bench_n1_fast.json 2>/dev/null
 python3 bench.py --pcm16 --cpu-utts 0 > $out/bench_n1_pcm16.json 2>/dev/null
-python3 bench.py --verify --cpu-utts 0 --fast-leg 0 > $out/bench_n1_verify.json 2>/dev/null
-rm -rf gpurun_out/prof/stats
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/stats -- python3 bench.py --cpu-utts 0 > $out/stats.log 2>&1
-cp gpurun_out/prof/stats/*/*kernel_stats.csv $out/kernel_stats.csv
-rm -rf gpurun_out/prof/stats2
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/stats2 -- python3 bench.py --config 2 --cpu-utts 0 > $out/stats2.log 2>&1
-cp gpurun_out/prof/stats2/*/*kernel_stats.csv $out/kernel_stats_config2.csv
-# config 4 (all eight formants live), exact (with the fast leg of the default line) and the second tolerance tier
-rm -rf gpurun_out/prof/stats4
-rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/stats4 -- python3 bench.py --config 4 --cpu-utts 0 > $out/stats4.log 2>&1
-cp gpurun_out/prof/stats4/*/*kernel_stats.csv $out/kernel_stats_config4.csv
+python3 bench.py --full --verify --cpu-utts 0 --fast-leg 0 > $out/bench_n1_verify.json 2>/dev/null
+rm -rf $out/prof/stats
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof/stats -- python3 bench.py --full --cpu-utts 0 > $out/stats.log 2>&1
+cp $out/prof/stats/*/*kernel_stats.csv $out/kernel_stats.csv
+rm -rf $out/prof/stats2
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof/stats2 -- python3 bench.py --full --config 2 --cpu-utts 0 > $out/stats2.log 2>&1
+cp $out/prof/stats2/*/*kernel_stats.csv $out/kernel_stats_config2.csv
+# config 4 (all eight formants live), exact (with the fast leg of the --full line) and the second tolerance tier
+rm -rf $out/prof/stats4
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof/stats4 -- python3 bench.py --full --config 4 --cpu-utts 0 > $out/stats4.log 2>&1
+cp $out/prof/stats4/*/*kernel_stats.csv $out/kernel_stats_config4.csv
 rm -rf gpurun_out/prof/stats5
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof/stats5 -- python3 bench.py --mode mid --cpu-utts 0 --fast-leg 0 > $out/stats5.log 2>&1
 cp gpurun_out/prof/stats5/*/*kernel_stats.csv $out/kernel_stats_mid.csv
