@@ -1,0 +1,49 @@
+// grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
+// the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
+//   usage: grail_dialogue [-o out.wav] "first line" "second line"
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "grail.hpp"
+
+int main(int argc, char **argv)
+{
+    std::string out_path = "dialogue.wav";
+    std::vector<std::string> lines;
+    for (int i = 1; i < argc; ++i) {
+        if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
+        else lines.push_back(argv[i]);
+    }
+    if (lines.size() != 2) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] \"first line\" \"second line\"\n");
+        return 2;
+    }
+    try {
+        const grail::Voice first = grail::voices::generic();        // 44.1 kHz, as the CLI
+        grail::Voice second = first;
+        second.center_frequency = first.center_frequency * 1.5f;    // a higher voice
+        grail::Gpu gpu(0, {first, second});
+        const std::vector<grail::Utterance> utts = {grail::Utterance{grail::phoneme_elems(first, lines[0]), 0, 0},
+                                                    grail::Utterance{grail::phoneme_elems(second, lines[1]), 1, 0}};
+        const std::vector<uint32_t> lens = gpu.lengths(utts);
+        // one timeline: the second line starts 0.3 s after the first has ended
+        const uint32_t rows[2] = {0, 1};
+        const int64_t gaps[2] = {0, (int64_t)(first.sample_rate * 3.0f / 10.0f)};
+        uint64_t at[2] = {0, 0}, end = 0;
+        grail::check(grail_mix_place_sequential(lens.data(), 2, rows, nullptr, gaps, 2, 1, at, &end));
+        // the first voice left, the second right
+        const std::vector<grail::Placement> placements = {
+            {0, 0, at[0], 0.8f}, {0, 1, at[0], 0.2f}, {1, 0, at[1], 0.2f}, {1, 1, at[1], 0.8f}};
+        const auto tracks = gpu.mix(utts, placements, 2, end);
+        std::printf("%.2f seconds of stereo audio: \"%s\" (left), \"%s\" (right)\n", end / first.sample_rate,
+                    lines[0].c_str(), lines[1].c_str());
+        std::printf("Writing the dialogue to %s\n", out_path.c_str());
+        gpu.save_wav_frames(out_path, tracks, (uint32_t)first.sample_rate);
+    } catch (const grail::Error &e) {
+        std::fprintf(stderr, "grail_dialogue: %s (status %d)\n", e.what(), e.status);
+        return 1;
+    }
+    return 0;
+}

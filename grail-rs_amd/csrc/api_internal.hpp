@@ -111,6 +111,7 @@ struct grail_ctx {
     ncclComm_t comm = nullptr;
     uint32_t comm_rank = 0, comm_world = 1;
     void *host_pipe = nullptr;        // HostPipe: streams, events and buffers of the host-output path
+    void *mix_state = nullptr;        // MixState (mix.cpp): the last mix's plan and the device buffers it was uploaded to
 };
 
 struct grail_stream {
@@ -315,6 +316,7 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev, in
 // host_output.cpp / comm.cpp: what grail_destroy releases
 void pipe_destroy_opaque(void *p);
 void comm_release(grail_ctx *ctx);
+void mix_release(grail_ctx *ctx);     // mix.cpp
 // host_output.cpp: texts -> PhonemeElems (grail_say_batch, grail_node_say_batch)
 int say_segments(const std::vector<grail_voice> &voices, const char *const *texts_utf8, uint32_t n_texts,
                  const uint32_t *voice_ids, std::vector<grail_phoneme_elem> &segs, std::vector<uint32_t> &offs);

@@ -141,4 +141,22 @@ hipError_t launch_compare(const float *a, const float *b, uint64_t stride, const
 uint32_t state_words(int lanes_per_utt);
 uint64_t state_lanes(uint32_t n_utt, int lanes_per_utt);
 
+// mixing (mix_kernels.hip): one launch of a plan of mix_plan.cpp — a workgroup per (track, span), n_workgroups of them
+namespace mix { struct MixItem; }
+struct MixArgs {
+    const float *rows;
+    const mix::MixItem *items;
+    const uint32_t *tile_start;
+    const uint32_t *tile_items;
+    float *tracks;
+    uint64_t track_stride, track_len, wg_samples;
+    uint32_t wgs_per_track, wgs_per_tile, tiles_per_track, n_workgroups;
+    uint32_t samples_per_lane;   // 1 or 8
+    uint32_t accumulate;         // GRAIL_MIX_ACCUMULATE
+};
+hipError_t launch_mix(const MixArgs &args, hipStream_t stream);
+// tracks [n_tracks][track_stride] -> interleaved i16 frames[f * n_tracks + t] (examples/cli.rs:49)
+hipError_t launch_pcm16_frames(const float *tracks, uint64_t track_stride, uint32_t n_tracks, uint64_t n_frames,
+                               int16_t *frames, hipStream_t stream);
+
 }  // namespace grail

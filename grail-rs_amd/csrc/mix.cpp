@@ -1,0 +1,243 @@
+// mix.cpp — rendered rows -> tracks on the device: grail_mix_async (checks, the plan's upload, one launch), grail_batch_mix
+// (a batch rendered in blocks of rows into scratch, each block mixed before the next one renders) and
+// grail_pcm16_frames_async.  The plan is mix_plan.cpp (pure host), the kernels are mix_kernels.hip.  DESIGN.md §4.8.
+#include "api_internal.hpp"
+#include "mix_plan.h"
+
+using namespace grail;
+using namespace grail::host;
+
+// Per context (grail_ctx::mix_state): the plan of the last mix and the device buffers it went to, and grail_batch_mix's
+// scratch (one block of rows and their lengths) — all grown, never shrunk, freed by grail_destroy, so that a mix in steady
+// state costs no hipMalloc / hipFree (those of a 25 GB block cost a third of a render, and vary from call to call).  The
+// host vectors of the plan are rebuilt only once the upload from them has completed.
+struct MixState {
+    mix::Plan plan;
+    mix::MixItem *d_items = nullptr;
+    uint32_t *d_tile_start = nullptr, *d_tile_items = nullptr;
+    size_t cap_items = 0, cap_tile_start = 0, cap_tile_items = 0;
+    float *d_rows = nullptr;          // grail_batch_mix: rows of one block
+    uint32_t *d_len = nullptr;        // ... and their lengths
+    size_t cap_rows = 0, cap_len = 0;
+    hipEvent_t uploaded = nullptr;
+    bool pending = false;
+};
+
+namespace grail {
+namespace host {
+
+void mix_release(grail_ctx *ctx)
+{
+    MixState *st = (MixState *)ctx->mix_state;
+    if (!st) return;
+    if (st->d_items) (void)hipFree(st->d_items);
+    if (st->d_tile_start) (void)hipFree(st->d_tile_start);
+    if (st->d_tile_items) (void)hipFree(st->d_tile_items);
+    if (st->d_rows) (void)hipFree(st->d_rows);
+    if (st->d_len) (void)hipFree(st->d_len);
+    if (st->uploaded) (void)hipEventDestroy(st->uploaded);
+    delete st;
+    ctx->mix_state = nullptr;
+}
+
+}  // namespace host
+}  // namespace grail
+
+namespace {
+
+// a buffer of at least n elements (headroom: a quarter more, so that slowly growing plans do not reallocate every call)
+template <typename T>
+int reserve(grail_ctx *ctx, T **p, size_t *cap, size_t n, bool headroom = true)
+{
+    n = std::max<size_t>(n, 1);
+    if (*cap >= n) return GRAIL_OK;
+    if (*p) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));    // (a queued mix may still read the old buffer)
+        HIP_TRY(hipFree(*p));
+        *p = nullptr;
+        *cap = 0;
+    }
+    const size_t want = headroom ? n + n / 4 : n;
+    HIP_TRY(hipMalloc((void **)p, want * sizeof(T)));
+    *cap = want;
+    return GRAIL_OK;
+}
+
+// grail_mix_async after bind(): the checks, the plan, its upload, the launch
+int mix_rows(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *row_len,
+             uint32_t n_rows, const uint32_t *item_rows, const uint32_t *item_tracks, const uint64_t *item_offsets,
+             const float *item_gains, uint32_t n_items, float *tracks_dev, uint64_t track_stride, uint32_t n_tracks,
+             uint64_t track_len, uint32_t flags)
+{
+    if (flags & ~GRAIL_MIX_ACCUMULATE) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": unknown flags");
+    if (n_items && !rows_dev) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": rows_dev is NULL");
+    if (n_tracks && !tracks_dev) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": tracks_dev is NULL");
+    if (!ctx->mix_state) ctx->mix_state = new (std::nothrow) MixState();
+    MixState *st = (MixState *)ctx->mix_state;
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "mix state");
+    if (!st->uploaded) HIP_TRY(hipEventCreateWithFlags(&st->uploaded, hipEventDisableTiming));
+    if (st->pending) {
+        HIP_TRY(hipEventSynchronize(st->uploaded));
+        st->pending = false;
+    }
+    std::string why;
+    const int rc = mix::build_plan(row_len, n_rows, row_stride, item_rows, item_tracks, item_offsets, item_gains, n_items,
+                                   n_tracks, track_len, track_stride, (uint32_t)ctx->cus, st->plan, &why);
+    if (rc) return fail(rc, std::string(who) + ": " + why);
+    const mix::Plan &p = st->plan;
+    const uint64_t wgs = (uint64_t)n_tracks * p.wgs_per_track;
+    if (wgs == 0) return GRAIL_OK;
+    int r;
+    if ((r = reserve(ctx, &st->d_items, &st->cap_items, p.items.size()))) return r;
+    if ((r = reserve(ctx, &st->d_tile_start, &st->cap_tile_start, p.tile_start.size()))) return r;
+    if ((r = reserve(ctx, &st->d_tile_items, &st->cap_tile_items, p.tile_items.size()))) return r;
+    if (!p.items.empty())
+        HIP_TRY(hipMemcpyAsync(st->d_items, p.items.data(), p.items.size() * sizeof(mix::MixItem), hipMemcpyHostToDevice,
+                               ctx->stream));
+    HIP_TRY(hipMemcpyAsync(st->d_tile_start, p.tile_start.data(), p.tile_start.size() * sizeof(uint32_t),
+                           hipMemcpyHostToDevice, ctx->stream));
+    if (!p.tile_items.empty())
+        HIP_TRY(hipMemcpyAsync(st->d_tile_items, p.tile_items.data(), p.tile_items.size() * sizeof(uint32_t),
+                               hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(st->uploaded, ctx->stream));
+    st->pending = true;
+    MixArgs a{};
+    a.rows = rows_dev;
+    a.items = st->d_items;
+    a.tile_start = st->d_tile_start;
+    a.tile_items = st->d_tile_items;
+    a.tracks = tracks_dev;
+    a.track_stride = track_stride;
+    a.track_len = track_len;
+    a.wg_samples = p.wg_samples;
+    a.wgs_per_track = (uint32_t)p.wgs_per_track;
+    a.wgs_per_tile = (uint32_t)(p.tile_samples / p.wg_samples);
+    a.tiles_per_track = (uint32_t)p.tiles_per_track;
+    a.n_workgroups = (uint32_t)wgs;
+    a.samples_per_lane = p.samples_per_lane;
+    a.accumulate = flags & GRAIL_MIX_ACCUMULATE;
+    const hipError_t e = launch_mix(a, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "mix kernel launch");
+    return GRAIL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int grail_mix_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *row_len,
+                    uint32_t n_rows, const uint32_t *item_rows, const uint32_t *item_tracks,
+                    const uint64_t *item_offsets, const float *item_gains, uint32_t n_items,
+                    float *tracks_dev, uint64_t track_stride, uint32_t n_tracks, uint64_t track_len,
+                    uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    return mix_rows(ctx, "grail_mix_async", rows_dev, row_stride, row_len, n_rows, item_rows, item_tracks, item_offsets,
+                    item_gains, n_items, tracks_dev, track_stride, n_tracks, track_len, flags);
+}
+
+int grail_batch_mix(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                    const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_gains,
+                    uint32_t n_items, float *tracks_dev, uint64_t track_stride, uint32_t n_tracks,
+                    uint64_t track_len, uint32_t *out_len, uint32_t flags)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if ((rc = check_ready(ctx, batch))) return rc;
+    const uint32_t n = batch->n_utt;
+    // the items' checks before anything is rendered (the plan repeats them per block, with the rows' lengths)
+    if (n_items && (!item_rows || !item_offsets)) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: item_rows or item_offsets is NULL");
+    if (n_tracks && !tracks_dev) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: tracks_dev is NULL");
+    if (track_len > track_stride) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: track_len > track_stride");
+    if (flags & ~GRAIL_MIX_ACCUMULATE) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: unknown flags");
+    for (uint32_t i = 0; i < n_items; ++i) {
+        if (item_rows[i] >= n) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: an item's row is >= the batch size");
+        if ((item_tracks ? item_tracks[i] : 0u) >= n_tracks)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: an item's track is >= n_tracks");
+    }
+    if (n == 0) {           // nothing to render: the tracks as an empty mix leaves them (+0.0, or untouched)
+        rc = mix_rows(ctx, "grail_batch_mix", nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, tracks_dev,
+                      track_stride, n_tracks, track_len, flags);
+        const int sync_rc = grail_sync(ctx);
+        return rc ? rc : sync_rc;
+    }
+    std::vector<uint32_t> lens(n);
+    if ((rc = grail_batch_lengths(ctx, batch, 0xFFFFFFFFu, lens.data()))) return rc;
+    const uint64_t longest = *std::max_element(lens.begin(), lens.end());
+    const uint64_t stride = std::max<uint64_t>(64, (longest + 63) / 64 * 64);
+    if (!ctx->mix_state) ctx->mix_state = new (std::nothrow) MixState();
+    MixState *st = (MixState *)ctx->mix_state;
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "mix state");
+    // the block rule of the header: 2 x 256 x CUs rows, as many as half of the free HBM holds (the context's scratch from an
+    // earlier call counts as free: it is this call's to reuse)
+    uint64_t block = 2ull * 256ull * (uint64_t)std::max(ctx->cus, 1);
+    size_t free_bytes = 0, total_bytes = 0;
+    HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes));
+    const uint64_t fit = (uint64_t)((free_bytes + st->cap_rows * sizeof(float)) / 2) / (stride * sizeof(float));
+    if (fit == 0) return fail(GRAIL_ERR_OUT_OF_MEMORY, "grail_batch_mix: not one row fits in half of the free HBM");
+    block = std::min(block, fit);
+    const bool one_piece = n <= block;
+    const uint64_t rows_alloc = one_piece ? n : block;
+    const uint64_t n_blocks = one_piece ? 1 : (n + block - 1) / block;
+    // the items of each block, in the order given (the plan orders them by row; blocks follow each other in row order)
+    std::vector<std::vector<uint32_t>> of_block(n_blocks);
+    if (!one_piece)
+        for (uint32_t i = 0; i < n_items; ++i) of_block[item_rows[i] / block].push_back(i);
+    if ((rc = reserve(ctx, &st->d_rows, &st->cap_rows, rows_alloc * stride, false))) return rc;
+    if ((rc = reserve(ctx, &st->d_len, &st->cap_len, rows_alloc, false))) return rc;
+    float *const d_rows = st->d_rows;
+    uint32_t *const d_len = st->d_len;
+    std::vector<uint32_t> sub_rows, sub_tracks;
+    std::vector<uint64_t> sub_offs;
+    std::vector<float> sub_gains;
+    for (uint64_t b = 0; !rc && b < n_blocks; ++b) {
+        const uint32_t first = (uint32_t)(b * block), count = (uint32_t)std::min<uint64_t>(block, n - first);
+        const uint32_t fl = b ? flags | GRAIL_MIX_ACCUMULATE : flags;
+        if (one_piece) {
+            rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len);      // = grail_batch_synthesize_async
+            if (!rc)
+                rc = mix_rows(ctx, "grail_batch_mix", d_rows, stride, lens.data(), n, item_rows, item_tracks, item_offsets,
+                              item_gains, n_items, tracks_dev, track_stride, n_tracks, track_len, fl);
+            break;
+        }
+        if (b && of_block[b].empty()) continue;      // no item reads these rows: not rendered at all
+        rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len, first, count, (uint32_t)block);
+        if (rc) break;
+        sub_rows.clear();
+        sub_tracks.clear();
+        sub_offs.clear();
+        sub_gains.clear();
+        for (const uint32_t i : of_block[b]) {
+            sub_rows.push_back(item_rows[i] - first);
+            if (item_tracks) sub_tracks.push_back(item_tracks[i]);
+            sub_offs.push_back(item_offsets[i]);
+            if (item_gains) sub_gains.push_back(item_gains[i]);
+        }
+        rc = mix_rows(ctx, "grail_batch_mix", d_rows, stride, lens.data() + first, count, sub_rows.data(),
+                      item_tracks ? sub_tracks.data() : nullptr, sub_offs.data(), item_gains ? sub_gains.data() : nullptr,
+                      (uint32_t)sub_rows.size(), tracks_dev, track_stride, n_tracks, track_len, fl);
+    }
+    const int sync_rc = grail_sync(ctx);      // (every block queued; a cut row cannot happen: the stride holds the longest)
+    if (rc) return rc;
+    if (sync_rc) return sync_rc;
+    if (out_len) std::memcpy(out_len, lens.data(), (size_t)n * sizeof(uint32_t));
+    return GRAIL_OK;
+}
+
+int grail_pcm16_frames_async(grail_ctx *ctx, const float *tracks_dev, uint64_t track_stride,
+                             uint32_t n_tracks, uint64_t n_frames, int16_t *frames_dev)
+{
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (n_frames == 0) return GRAIL_OK;
+    if (n_tracks == 0) return fail(GRAIL_ERR_INVALID_ARG, "grail_pcm16_frames_async: no tracks");
+    if (!tracks_dev || !frames_dev) return fail(GRAIL_ERR_INVALID_ARG, "grail_pcm16_frames_async: NULL buffer");
+    if (n_frames > track_stride) return fail(GRAIL_ERR_INVALID_ARG, "grail_pcm16_frames_async: n_frames > track_stride");
+    if (n_frames > UINT64_MAX / n_tracks) return fail(GRAIL_ERR_INVALID_ARG, "grail_pcm16_frames_async: too many frames");
+    const hipError_t e = launch_pcm16_frames(tracks_dev, track_stride, n_tracks, n_frames, frames_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "pcm16 frames kernel launch");
+    return GRAIL_OK;
+}
+
+}  // extern "C"

@@ -225,4 +225,38 @@ int grail_wav_write_i16(const char *path, const int16_t *pcm, uint32_t n, uint32
     return ok ? GRAIL_OK : GRAIL_ERR_INVALID_ARG;
 }
 
+// the same for n_channels interleaved channels (frames[f * n_channels + c]): channel count, byte rate and block align
+// follow it; one channel IS grail_wav_write_i16
+int grail_wav_write_i16_frames(const char *path, const int16_t *frames, uint32_t n_frames, uint32_t n_channels,
+                               uint32_t sample_rate)
+{
+    if (n_channels == 1) return grail_wav_write_i16(path, frames, n_frames, sample_rate);
+    if (!path || n_channels == 0 || n_channels > 65535u / 2u || (!frames && n_frames)) return GRAIL_ERR_INVALID_ARG;
+    const uint64_t data = (uint64_t)n_frames * n_channels * 2u;
+    if (data > 0xFFFFFFFFull - 36u) return GRAIL_ERR_INVALID_ARG;
+    FILE *f = std::fopen(path, "wb");
+    if (!f) return GRAIL_ERR_INVALID_ARG;
+    unsigned char h[44];
+    auto le32 = [](unsigned char *p, uint32_t v) { p[0] = v; p[1] = v >> 8; p[2] = v >> 16; p[3] = v >> 24; };
+    auto le16 = [](unsigned char *p, uint16_t v) { p[0] = (unsigned char)v; p[1] = (unsigned char)(v >> 8); };
+    std::memcpy(h, "RIFF", 4);
+    le32(h + 4, 36u + (uint32_t)data);
+    std::memcpy(h + 8, "WAVEfmt ", 8);
+    le32(h + 16, 16);
+    le16(h + 20, 1);                                     // PCM
+    le16(h + 22, (uint16_t)n_channels);
+    le32(h + 24, sample_rate);
+    le32(h + 28, sample_rate * 2u * n_channels);         // byte rate
+    le16(h + 32, (uint16_t)(2u * n_channels));           // block align
+    le16(h + 34, 16);
+    std::memcpy(h + 36, "data", 4);
+    le32(h + 40, (uint32_t)data);
+    bool ok = std::fwrite(h, 1, 44, f) == 44;
+    std::vector<unsigned char> body((size_t)data);
+    for (size_t i = 0; i < (size_t)n_frames * n_channels; ++i) le16(&body[i * 2], (uint16_t)frames[i]);
+    ok = ok && std::fwrite(body.data(), 1, body.size(), f) == body.size();
+    ok = (std::fclose(f) == 0) && ok;
+    return ok ? GRAIL_OK : GRAIL_ERR_INVALID_ARG;
+}
+
 }  // extern "C"

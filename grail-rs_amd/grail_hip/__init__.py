@@ -72,7 +72,10 @@ EXPORTS = [
     "grail_node_synthesize_batch_elems", "grail_node_synthesize_batch_pcm16", "grail_node_synthesize_batch_device",
     "grail_node_say_batch",
     "grail_node_lengths", "grail_node_last_shard_ms", "grail_node_host_alloc", "grail_node_host_free",
+    "grail_mix_async", "grail_batch_mix", "grail_mix_place_sequential", "grail_pcm16_frames_async",
+    "grail_wav_write_i16_frames",
 ]
+MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 
 
 class GrailError(RuntimeError):
@@ -312,6 +315,12 @@ def load():
     L.grail_node_last_shard_ms.argtypes = [vp, C.POINTER(C.c_float), C.c_uint32]
     L.grail_node_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     L.grail_node_host_free.argtypes = [vp, vp]
+    L.grail_mix_async.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, vp, u64, C.c_uint32, u64,
+                                  C.c_uint32]
+    L.grail_batch_mix.argtypes = [vp, vp, vp, vp, vp, vp, C.c_uint32, vp, u64, C.c_uint32, u64, vp, C.c_uint32]
+    L.grail_mix_place_sequential.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
+    L.grail_pcm16_frames_async.argtypes = [vp, vp, u64, C.c_uint32, u64, vp]
+    L.grail_wav_write_i16_frames.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_uint32]
     _lib = L
     return L
 
@@ -456,6 +465,39 @@ def wav_write_i16(path, pcm, sample_rate):
     _check(load().grail_wav_write_i16(path.encode(), pcm.ctypes.data, len(pcm), int(sample_rate)))
 
 
+def wav_write_i16_frames(path, frames, sample_rate):
+    """A multichannel WAV: frames[n_frames, n_channels] int16 (1-D: mono), grail_wav_write_i16_frames."""
+    frames = np.ascontiguousarray(frames, dtype=np.int16)
+    if frames.ndim == 1:
+        frames = frames.reshape(-1, 1)
+    _check(load().grail_wav_write_i16_frames(path.encode(), frames.ctypes.data, frames.shape[0], frames.shape[1],
+                                             int(sample_rate)))
+
+
+def _mix_items(item_rows, item_offsets, item_tracks, item_gains):
+    """The parallel item arrays of the mixing calls (None: all on track 0 / gain 1.0)."""
+    rows = np.ascontiguousarray(item_rows, dtype=np.uint32)
+    offs = np.ascontiguousarray(item_offsets, dtype=np.uint64)
+    tracks = None if item_tracks is None else np.ascontiguousarray(item_tracks, dtype=np.uint32)
+    gains = None if item_gains is None else np.ascontiguousarray(item_gains, dtype=np.float32)
+    assert len(offs) == len(rows) and (tracks is None or len(tracks) == len(rows)) and (gains is None or len(gains) == len(rows))
+    return rows, offs, tracks, gains
+
+
+def mix_place_sequential(row_len, item_rows, item_tracks=None, gaps=None, n_tracks=1):
+    """Items laid end to end per track in accumulation order, gaps[i] samples after the previous item on its track
+    (grail_mix_place_sequential; pure host).  Returns (item_offsets uint64[n_items], track_len uint64[n_tracks])."""
+    row_len = np.ascontiguousarray(row_len, dtype=np.uint32)
+    rows = np.ascontiguousarray(item_rows, dtype=np.uint32)
+    tracks = None if item_tracks is None else np.ascontiguousarray(item_tracks, dtype=np.uint32)
+    gaps = None if gaps is None else np.ascontiguousarray(gaps, dtype=np.int64)
+    offs = np.zeros(max(len(rows), 1), dtype=np.uint64)
+    track_len = np.zeros(max(n_tracks, 1), dtype=np.uint64)
+    _check(load().grail_mix_place_sequential(row_len.ctypes.data, len(row_len), rows.ctypes.data, _ptr(tracks), _ptr(gaps),
+                                             len(rows), n_tracks, offs.ctypes.data, track_len.ctypes.data))
+    return offs[:len(rows)], track_len[:n_tracks]
+
+
 def length_bound(segment_lengths, sample_rate):
     """An upper bound of an utterance's length in samples (grail_length_bound); None: no bound."""
     a = np.ascontiguousarray(segment_lengths, dtype=np.float32)
@@ -552,6 +594,17 @@ class Batch:
         """Rows of i16 PCM: the WAV sink's conversion fused into the kernel's store."""
         _check(load().grail_batch_synthesize_pcm16_async(self.ctx.handle, self.handle, out_dev,
                                                          out_stride, out_len_dev))
+
+    def mix(self, item_rows, item_offsets, tracks_dev, track_stride, n_tracks, track_len, item_tracks=None,
+            item_gains=None, accumulate=False):
+        """grail_batch_mix: the batch rendered in blocks of rows and mixed into tracks_dev [n_tracks][track_stride]
+        (synchronous).  Returns the rows' lengths."""
+        rows, offs, tracks, gains = _mix_items(item_rows, item_offsets, item_tracks, item_gains)
+        out_len = np.zeros(max(self.n_utt, 1), dtype=np.uint32)
+        _check(load().grail_batch_mix(self.ctx.handle, self.handle, rows.ctypes.data, _ptr(tracks), offs.ctypes.data,
+                                      _ptr(gains), len(rows), tracks_dev, track_stride, n_tracks, track_len,
+                                      out_len.ctypes.data, MIX_ACCUMULATE if accumulate else 0))
+        return out_len[:self.n_utt]
 
     def free(self):
         if self.handle:
@@ -765,6 +818,21 @@ class Context:
     def pcm16(self, in_dev, in_stride, len_dev, n_utt, max_len, out_dev, out_stride):
         _check(load().grail_pcm16_async(self.handle, in_dev, in_stride, len_dev, n_utt, max_len,
                                         out_dev, out_stride))
+
+    def mix_async(self, rows_dev, row_stride, row_len, item_rows, item_offsets, tracks_dev, track_stride, n_tracks,
+                  track_len, item_tracks=None, item_gains=None, accumulate=False):
+        """grail_mix_async: rows_dev [n_rows][row_stride] (row_len: host, one per row) mixed into tracks_dev
+        [n_tracks][track_stride], queued on the context's stream."""
+        row_len = np.ascontiguousarray(row_len, dtype=np.uint32)
+        rows, offs, tracks, gains = _mix_items(item_rows, item_offsets, item_tracks, item_gains)
+        _check(load().grail_mix_async(self.handle, rows_dev, row_stride, row_len.ctypes.data, len(row_len),
+                                      rows.ctypes.data, _ptr(tracks), offs.ctypes.data, _ptr(gains), len(rows),
+                                      tracks_dev, track_stride, n_tracks, track_len,
+                                      MIX_ACCUMULATE if accumulate else 0))
+
+    def pcm16_frames_async(self, tracks_dev, track_stride, n_tracks, n_frames, frames_dev):
+        """grail_pcm16_frames_async: tracks -> interleaved i16 frames (frames_dev[f * n_tracks + t])."""
+        _check(load().grail_pcm16_frames_async(self.handle, tracks_dev, track_stride, n_tracks, n_frames, frames_dev))
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max |x|, non-finite counts) per row, computed on the device."""

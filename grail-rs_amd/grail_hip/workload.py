@@ -80,6 +80,33 @@ def speech_like_batch(n_utt, rng, n_voices=1, scale=1.0, blend_is_length=False, 
     return segs, offs, vids, seeds, stride
 
 
+def mix_case(name, row_len, seed=0, sample_rate=SAMPLE_RATE):
+    """The three mixes of tools/mix_bench.py over the rendered rows row_len[n] (items only; no arithmetic):
+    'concat'  (a): every row end to end on 64 tracks, rows in order, gain 1 (grail_mix_place_sequential);
+    'babble'  (b): n / 16 tracks of 16 rows each at random offsets in [0, 0.5 s), random gains +-[0.1, 1);
+    'stacked' (c): every row on ONE track at random offsets in [0, 1 s), random gains.
+    Returns (item_rows, item_tracks, item_offsets, item_gains, n_tracks, track_len)."""
+    from . import mix_place_sequential
+    row_len = np.asarray(row_len, dtype=np.uint32)
+    n = len(row_len)
+    rng = np.random.default_rng(seed)
+    rows = np.arange(n, dtype=np.uint32)
+    gains = (rng.uniform(0.1, 1.0, n) * rng.choice([-1.0, 1.0], n)).astype(np.float32)
+    if name == "concat":
+        n_tracks = 64
+        tracks = (rows // np.uint32(-(-n // n_tracks))).astype(np.uint32)
+        offs, track_len = mix_place_sequential(row_len, rows, tracks, None, n_tracks)
+        return rows, tracks, offs, None, n_tracks, int(track_len.max())
+    if name == "babble":
+        n_tracks = max(1, n // 16)
+        tracks = (rows // np.uint32(16)).astype(np.uint32) % np.uint32(n_tracks)
+        offs = rng.integers(0, int(0.5 * sample_rate), n).astype(np.uint64)
+        return rows, tracks, offs, gains, n_tracks, int(0.5 * sample_rate) + int(row_len.max())
+    assert name == "stacked", name
+    offs = rng.integers(0, int(sample_rate), n).astype(np.uint64)
+    return rows, np.zeros(n, np.uint32), offs, gains, 1, int(sample_rate) + int(row_len.max())
+
+
 def shard_inputs(utts_per_rank, rank, world, n_voices, **kw):
     """This rank's slice of the global synthetic corpus of utts_per_rank*world utterances
     (contiguous shards, no data-path collective)."""

@@ -21,6 +21,7 @@ pub const GRAIL_ERR_RCCL: c_int = -6;
 pub const GRAIL_ERR_NO_VOICES: c_int = -7;
 pub const GRAIL_OUT_HOST: u32 = 0;
 pub const GRAIL_OUT_DEVICE: u32 = 1;
+pub const GRAIL_MIX_ACCUMULATE: u32 = 1;
 
 #[repr(C)]
 #[derive(Copy, Clone, Debug, PartialEq)]
@@ -223,6 +224,22 @@ extern "C" {
                                len_a_dev: *const u32, len_b_dev: *const u32, n_utt: u32,
                                maxdiff: *mut f32, sumsq: *mut f64, mismatches: *mut u32) -> c_int;
     pub fn grail_wav_write_i16(path: *const c_char, pcm: *const i16, n: u32, sample_rate: u32) -> c_int;
+
+    pub fn grail_mix_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, row_len: *const u32,
+        n_rows: u32, item_rows: *const u32, item_tracks: *const u32, item_offsets: *const u64,
+        item_gains: *const f32, n_items: u32, tracks_dev: *mut f32, track_stride: u64, n_tracks: u32,
+        track_len: u64, flags: u32) -> c_int;
+    pub fn grail_batch_mix(ctx: *mut grail_ctx, batch: *const grail_batch, item_rows: *const u32,
+        item_tracks: *const u32, item_offsets: *const u64, item_gains: *const f32, n_items: u32,
+        tracks_dev: *mut f32, track_stride: u64, n_tracks: u32, track_len: u64, out_len: *mut u32,
+        flags: u32) -> c_int;
+    pub fn grail_mix_place_sequential(row_len: *const u32, n_rows: u32, item_rows: *const u32,
+        item_tracks: *const u32, gaps: *const i64, n_items: u32, n_tracks: u32, item_offsets: *mut u64,
+        track_len: *mut u64) -> c_int;
+    pub fn grail_pcm16_frames_async(ctx: *mut grail_ctx, tracks_dev: *const f32, track_stride: u64,
+        n_tracks: u32, n_frames: u64, frames_dev: *mut i16) -> c_int;
+    pub fn grail_wav_write_i16_frames(path: *const c_char, frames: *const i16, n_frames: u32,
+        n_channels: u32, sample_rate: u32) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

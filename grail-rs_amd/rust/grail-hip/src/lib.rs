@@ -278,6 +278,55 @@ impl Gpu {
     }
 }
 
+/// Where an utterance goes in a mix ([`Gpu::mix`]): utterance `utterance` of the call, added into track `track` from
+/// track sample `offset` on, scaled by `gain`.
+#[derive(Copy, Clone, Debug)]
+pub struct Placement {
+    pub utterance: u32,
+    pub track: u32,
+    pub offset: u64,
+    pub gain: f32,
+}
+
+impl Gpu {
+    /// Renders `utterances` and mixes them into `n_tracks` tracks of `track_len` samples on the device
+    /// (`grail_batch_mix`: every track sample is the left fold, in utterance order, of gain * sample over the placements
+    /// that cover it — the bits of that CPU loop over the rows of `synthesize_batch`, `Arithmetic::Exact`); only the
+    /// finished tracks cross PCIe.
+    pub fn mix<I: IntoIterator<Item = Utterance>>(&self, utterances: I, placements: &[Placement], n_tracks: u32,
+                                                 track_len: u64) -> Result<Vec<Vec<f32>>, Error> {
+        let b = FlatBatch::new(utterances);
+        let rows: Vec<u32> = placements.iter().map(|p| p.utterance).collect();
+        let tracks: Vec<u32> = placements.iter().map(|p| p.track).collect();
+        let offsets: Vec<u64> = placements.iter().map(|p| p.offset).collect();
+        let gains: Vec<f32> = placements.iter().map(|p| p.gain).collect();
+        let stride = ((track_len + 63) / 64 * 64).max(64);
+        let floats = n_tracks as usize * stride as usize;
+        let mut host = vec![0f32; floats];
+        unsafe {
+            let mut h = std::ptr::null_mut();
+            check(sys::grail_batch_upload(self.ctx, b.segs.as_ptr(), b.offs.as_ptr(), b.vids.as_ptr(), b.seeds.as_ptr(),
+                                          b.len(), &mut h))?;
+            let mut d: *mut std::ffi::c_void = std::ptr::null_mut();
+            let mut r = check(sys::grail_device_alloc(self.ctx, floats * 4 + 4, &mut d));
+            if r.is_ok() {
+                r = check(sys::grail_batch_mix(self.ctx, h, rows.as_ptr(), tracks.as_ptr(), offsets.as_ptr(), gains.as_ptr(),
+                                               rows.len() as u32, d as *mut f32, stride, n_tracks, track_len,
+                                               std::ptr::null_mut(), 0));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, host.as_mut_ptr() as *mut std::ffi::c_void, d, floats * 4));
+            }
+            if !d.is_null() {
+                sys::grail_device_free(self.ctx, d);
+            }
+            sys::grail_batch_free(self.ctx, h);
+            r?;
+        }
+        Ok(host.chunks(stride as usize).map(|t| t[..track_len as usize].to_vec()).collect())
+    }
+}
+
 /// Predicted |fast - reference| of `voice` in units of 2^-23 of max(1, peak) (grail_fast_sharpness): narrow and
 /// high formants amplify rounding-level differences of the filter coefficients.  Fast arithmetic is served up to
 /// GRAIL_FAST_SHARPNESS_LIMIT = 28 (`voices::generic()`: 24).  Pure host function, no GPU.

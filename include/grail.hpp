@@ -70,6 +70,29 @@ struct Utterance {
     uint32_t jitter_seed = 0;   // examples/cli.rs:182 uses 0
 };
 
+// Where an utterance goes in a mix (Gpu::mix): utterance `utterance` of the call, added into track `track` from track
+// sample `offset` on, scaled by `gain`.  The C ABI takes the same as parallel arrays (grail_batch_mix).
+struct Placement {
+    uint32_t utterance = 0;
+    uint32_t track = 0;
+    uint64_t offset = 0;
+    float gain = 1.0f;
+};
+
+namespace detail {
+inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
+                    std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
+{
+    offs.assign(1, 0u);
+    for (const Utterance &u : utts) {
+        segs.insert(segs.end(), u.phonemes.begin(), u.phonemes.end());
+        offs.push_back((uint32_t)segs.size());
+        vids.push_back(u.voice);
+        seeds.push_back(u.jitter_seed);
+    }
+}
+}  // namespace detail
+
 // One GPU and its voice table.
 class Gpu {
 public:
@@ -160,6 +183,81 @@ public:
         grail_device_free(ctx_, d_len);
         check(rc);
         check(grail_wav_write_i16(path.c_str(), i16.data(), n, sample_rate));
+    }
+
+    // every utterance's length in samples (the Sequencer clock alone, src/lib.rs:861-888): what a timeline is laid out with
+    std::vector<uint32_t> lengths(const std::vector<Utterance> &utts) const
+    {
+        std::vector<PhonemeElem> segs;
+        std::vector<uint32_t> offs, vids, seeds;
+        detail::flatten(utts, segs, offs, vids, seeds);
+        const uint32_t n = (uint32_t)utts.size();
+        std::vector<uint32_t> lens(n ? n : 1);
+        grail_batch *b = nullptr;
+        check(grail_batch_upload(ctx_, segs.data(), offs.data(), vids.data(), seeds.data(), n, &b));
+        const int rc = grail_batch_lengths(ctx_, b, 0xFFFFFFFFu, lens.data());
+        grail_batch_free(ctx_, b);
+        check(rc);
+        lens.resize(n);
+        return lens;
+    }
+
+    // Renders the utterances and mixes them into n_tracks tracks of track_len samples on the device (grail_batch_mix: every
+    // track sample is the left fold, in utterance order, of gain * sample over the placements that cover it; bit-identical
+    // to that CPU loop over Gpu::synthesize's rows, Exact), then copies the tracks back.
+    std::vector<std::vector<float>> mix(const std::vector<Utterance> &utts, const std::vector<Placement> &placements,
+                                        uint32_t n_tracks, uint64_t track_len) const
+    {
+        std::vector<PhonemeElem> segs;
+        std::vector<uint32_t> offs, vids, seeds, rows, tracks;
+        std::vector<uint64_t> at;
+        std::vector<float> gains;
+        detail::flatten(utts, segs, offs, vids, seeds);
+        for (const Placement &p : placements) {
+            rows.push_back(p.utterance);
+            tracks.push_back(p.track);
+            at.push_back(p.offset);
+            gains.push_back(p.gain);
+        }
+        const uint64_t stride = track_len ? (track_len + 63) / 64 * 64 : 64;
+        grail_batch *b = nullptr;
+        check(grail_batch_upload(ctx_, segs.data(), offs.data(), vids.data(), seeds.data(), (uint32_t)utts.size(), &b));
+        void *d = nullptr;
+        std::vector<float> flat((size_t)n_tracks * stride);
+        int rc = grail_device_alloc(ctx_, flat.size() * sizeof(float) + 4, &d);
+        if (!rc) rc = grail_batch_mix(ctx_, b, rows.data(), tracks.data(), at.data(), gains.data(), (uint32_t)rows.size(),
+                                      (float *)d, stride, n_tracks, track_len, nullptr, 0u);
+        if (!rc && !flat.empty()) rc = grail_memcpy_d2h(ctx_, flat.data(), d, flat.size() * sizeof(float));
+        if (d) grail_device_free(ctx_, d);
+        grail_batch_free(ctx_, b);
+        check(rc);
+        std::vector<std::vector<float>> out(n_tracks);
+        for (uint32_t t = 0; t < n_tracks; ++t)
+            out[t].assign(flat.begin() + (size_t)t * stride, flat.begin() + (size_t)t * stride + track_len);
+        return out;
+    }
+
+    // Tracks of equal length as one multichannel WAV: interleaved i16 frames made on the device (grail_pcm16_frames_async,
+    // the examples/cli.rs:49 conversion), then save_wav for as many channels (grail_wav_write_i16_frames).
+    void save_wav_frames(const std::string &path, const std::vector<std::vector<float>> &tracks, uint32_t sample_rate) const
+    {
+        const uint32_t ch = (uint32_t)tracks.size();
+        const uint64_t n = ch ? tracks[0].size() : 0;
+        for (const auto &t : tracks)
+            if (t.size() != n) throw Error(GRAIL_ERR_INVALID_ARG, "save_wav_frames: tracks of different lengths");
+        void *d_in = nullptr, *d_out = nullptr;
+        std::vector<int16_t> frames((size_t)n * ch);
+        check(grail_device_alloc(ctx_, (size_t)n * ch * 4 + 4, &d_in));
+        int rc = grail_device_alloc(ctx_, frames.size() * 2 + 4, &d_out);
+        for (uint32_t t = 0; !rc && t < ch && n; ++t)
+            rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)t * n, tracks[t].data(), (size_t)n * 4);
+        if (!rc) rc = grail_pcm16_frames_async(ctx_, (const float *)d_in, n, ch, n, (int16_t *)d_out);
+        if (!rc) rc = grail_sync(ctx_);
+        if (!rc && !frames.empty()) rc = grail_memcpy_d2h(ctx_, frames.data(), d_out, frames.size() * 2);
+        grail_device_free(ctx_, d_in);
+        if (d_out) grail_device_free(ctx_, d_out);
+        check(rc);
+        check(grail_wav_write_i16_frames(path.c_str(), frames.data(), (uint32_t)n, ch, sample_rate));
     }
 
 private:

@@ -81,7 +81,9 @@ extern "C" {
  *   development builds only; "arithmetic" = 1 is served up to a sharpness of the voice table.
  *   3: round 5 — grail_length_bound; options "two_waves_per_simd", "pipeline_spread", "pipeline_round32" = 2; "ragged_plan" also weighs the scan and
  *   time-split kernels by the rows.
- *   4: round 6 — grail_node_* (one call, every GPU of the node); option "packed_launch_order". */
+ *   4: round 6 — grail_node_* (one call, every GPU of the node); option "packed_launch_order".  Additions since, which
+ *   change nothing that was there: grail_mix_async, grail_batch_mix, grail_mix_place_sequential,
+ *   grail_pcm16_frames_async, grail_wav_write_i16_frames. */
 #define GRAIL_ABI_VERSION 4
 /* fast mode ("arithmetic" = 1): bound on |fast - exact| per sample, full scale = 1.0; k * 2^-23 */
 #define GRAIL_FAST_TOLERANCE_ULPS 64
@@ -537,6 +539,74 @@ int grail_batch_compare(grail_ctx *ctx, const float *a_dev, const float *b_dev, 
                         float *maxdiff, double *sumsq, uint32_t *mismatches);
 /* save_wav  examples/cli.rs:28-67: 44-byte RIFF header (PCM, mono, 16 bit) + samples. */
 int grail_wav_write_i16(const char *path, const int16_t *pcm, uint32_t n, uint32_t sample_rate);
+
+/* ---- mixing: rendered rows -> tracks, on the device ---------------------------------------------------------------
+ * An ITEM i adds one rendered row, item_rows[i], using its first row_len[row] samples, scaled by item_gains[i], into
+ * track item_tracks[i], starting at track sample item_offsets[i].  Samples at or past track_len are dropped; an item
+ * that starts at or past track_len adds nothing.  For every track sample s of track t:
+ *
+ *     acc = +0.0f                         (GRAIL_MIX_ACCUMULATE: acc = the track's current value)
+ *     for each item i covering (t, s), in ascending item_rows[i], ties in the order the items were given:
+ *         acc = acc + gain_i * x           (binary32; the product rounded, then the sum rounded; never a fused multiply-add)
+ *
+ * Samples that no item covers are +0.0, or left untouched with GRAIL_MIX_ACCUMULATE.  Track memory between track_len
+ * and track_stride is never written.  An uncovered lane skips the add rather than adding zero (adding +0.0 would turn
+ * a -0.0 into +0.0).  The order is by row, not by item index: that lets grail_batch_mix render a batch in blocks of
+ * rows and still produce the same bits.  No atomics: every sample is one left fold in a fixed order, so the result is
+ * bit-identical across devices, block sizes and kernel tilings, and a three-line CPU loop reproduces it.
+ * GRAIL_ERR_INVALID_ARG, tracks unwritten: an item's row >= n_rows, an item's track >= n_tracks, track_len >
+ * track_stride, a row_len > row_stride, or a pointer the call needs is NULL (also: more than 4 194 304 tracks). */
+#define GRAIL_MIX_ACCUMULATE 1u   /* add into the tracks' contents instead of starting from +0.0 */
+
+/* rows_dev: device [n_rows][row_stride]; row_len: HOST [n_rows] (grail_batch_lengths / out_len);
+ * items: HOST arrays [n_items], copied before the call returns; item_tracks NULL = track 0, item_gains NULL = 1.0f;
+ * tracks_dev: device [n_tracks][track_stride], track_len <= track_stride.  Queued on ctx's stream behind earlier
+ * work (a grail_batch_synthesize_async before it needs no sync).  Rows and tracks must not overlap.
+ * The host side of a call is not free of waiting: it builds the plan into host memory of the context that the
+ * previous mix of the context was uploaded from, and first waits until that upload has completed — which is queued
+ * behind everything submitted before that previous mix.  So in render, mix, render, mix the second mix returns once
+ * the first render has finished (the device never idles: the work queued after it is already there). */
+int grail_mix_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *row_len,
+                    uint32_t n_rows, const uint32_t *item_rows, const uint32_t *item_tracks,
+                    const uint64_t *item_offsets, const float *item_gains, uint32_t n_items,
+                    float *tracks_dev, uint64_t track_stride, uint32_t n_tracks, uint64_t track_len,
+                    uint32_t flags);
+
+/* Render an uploaded batch and mix it, without ever holding all of its rows: contiguous row ranges are rendered
+ * into scratch and mixed before the next range (same bits as rendering everything and calling grail_mix_async,
+ * "arithmetic" = 0).  out_len: HOST [n_utt] or NULL.  Synchronous.
+ * Block rule: 2 x 256 x CUs rows, CUs = what the planner plans for (the device's compute units, or option
+ * "assume_compute_units"), fewer where half of the free HBM does not hold that many rows at the batch's stride (its
+ * longest utterance rounded up to 64 samples).  A batch that fits in one block renders in one piece, exactly as
+ * grail_batch_synthesize_async would; otherwise every block, the short last one included, is rendered with the kernel
+ * family of a full block (as the host-output calls do), and blocks after the first are mixed with
+ * GRAIL_MIX_ACCUMULATE, in block order; a block after the first that no item reads is not rendered.  The scratch (one
+ * block of rows and their lengths) stays with the context for its next call, grown and never shrunk, until
+ * grail_destroy: what an earlier call left counts as free HBM for the rule above.  In fast arithmetic ("arithmetic" = 1) the rows follow each block's kernel
+ * family, as every fast-mode rendering does: within GRAIL_FAST_TOLERANCE of the exact rows, per row. */
+int grail_batch_mix(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                    const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_gains,
+                    uint32_t n_items, float *tracks_dev, uint64_t track_stride, uint32_t n_tracks,
+                    uint64_t track_len, uint32_t *out_len, uint32_t flags);
+
+/* Pure host (no GPU): lay items end to end per track, in the accumulation order above.  Item i starts gaps[i]
+ * samples after the end of the previous item on its track (the first at gaps[i]); a negative gap overlaps
+ * (cross-fade); a start below 0 is GRAIL_ERR_INVALID_ARG.  gaps NULL = 0.  track_len: HOST [n_tracks], end of the
+ * last item per track (the furthest end of any of its items, where a negative gap lets an item end before the one
+ * before it; 0 for a track without items).  item_tracks NULL = track 0. */
+int grail_mix_place_sequential(const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows,
+                               const uint32_t *item_tracks, const int64_t *gaps, uint32_t n_items,
+                               uint32_t n_tracks, uint64_t *item_offsets, uint64_t *track_len);
+
+/* Tracks -> interleaved i16 frames (frames_dev[f * n_tracks + t]) with the examples/cli.rs:49 conversion of
+ * pcm16.h: what a multichannel WAV's data chunk and a sound card's callback hold.  n_frames <= track_stride.
+ * Asynchronous. */
+int grail_pcm16_frames_async(grail_ctx *ctx, const float *tracks_dev, uint64_t track_stride,
+                             uint32_t n_tracks, uint64_t n_frames, int16_t *frames_dev);
+
+/* save_wav for n_channels interleaved channels; n_channels = 1 is byte-identical to grail_wav_write_i16. */
+int grail_wav_write_i16_frames(const char *path, const int16_t *frames, uint32_t n_frames,
+                               uint32_t n_channels, uint32_t sample_rate);
 
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
