@@ -1,7 +1,11 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB] "first line" "second line"
+// --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
+// measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -12,12 +16,19 @@ int main(int argc, char **argv)
 {
     std::string out_path = "dialogue.wav";
     std::vector<std::string> lines;
+    bool leveled = false, bad_level = false;
+    float level_db = 0.0f;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
-        else lines.push_back(argv[i]);
+        else if (!std::strcmp(argv[i], "--level") && i + 1 < argc) {
+            char *rest = nullptr;
+            level_db = std::strtof(argv[++i], &rest);
+            leveled = true;
+            bad_level = rest == argv[i] || *rest || !std::isfinite(level_db);
+        } else lines.push_back(argv[i]);
     }
-    if (lines.size() != 2) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] \"first line\" \"second line\"\n");
+    if (lines.size() != 2 || bad_level) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB] \"first line\" \"second line\"\n");
         return 2;
     }
     try {
@@ -36,7 +47,17 @@ int main(int argc, char **argv)
         // the first voice left, the second right
         const std::vector<grail::Placement> placements = {
             {0, 0, at[0], 0.8f}, {0, 1, at[0], 0.2f}, {1, 0, at[1], 0.2f}, {1, 1, at[1], 0.8f}};
-        const auto tracks = gpu.mix(utts, placements, 2, end);
+        std::vector<std::vector<float>> tracks;
+        if (leveled) {          // the same pan as a level: 0.8 and 0.2 of the line at level_db
+            std::vector<float> levels, gains;
+            for (const grail::Placement &p : placements) levels.push_back(level_db + 20.0f * std::log10(p.gain));
+            uint32_t unleveled = 0;
+            tracks = gpu.mix_leveled(utts, placements, levels, 2, end, GRAIL_LEVEL_RMS, &gains, &unleveled);
+            std::printf("Lines brought to %.1f dB RMS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
+                        unleveled ? " (a silent line was left out)" : "");
+        } else {
+            tracks = gpu.mix(utts, placements, 2, end);
+        }
         std::printf("%.2f seconds of stereo audio: \"%s\" (left), \"%s\" (right)\n", end / first.sample_rate,
                     lines[0].c_str(), lines[1].c_str());
         std::printf("Writing the dialogue to %s\n", out_path.c_str());

@@ -112,6 +112,7 @@ struct grail_ctx {
     uint32_t comm_rank = 0, comm_world = 1;
     void *host_pipe = nullptr;        // HostPipe: streams, events and buffers of the host-output path
     void *mix_state = nullptr;        // MixState (mix.cpp): the last mix's plan and the device buffers it was uploaded to
+    void *level_state = nullptr;      // LevelState (levels.cpp): the frame scratch of grail_levels_async, a block's numbers
 };
 
 struct grail_stream {
@@ -317,6 +318,12 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev, in
 void pipe_destroy_opaque(void *p);
 void comm_release(grail_ctx *ctx);
 void mix_release(grail_ctx *ctx);     // mix.cpp
+void levels_release(grail_ctx *ctx);  // levels.cpp
+// levels.cpp, for grail_batch_mix_leveled: the rows of one rendered block measured on ctx's stream and their numbers
+// brought to the host (one wait), then the items' gains by grail_level_gains; gains[n_items], *n_unleveled is added to
+int level_block_gains(grail_ctx *ctx, int mode, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                      const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows, const float *item_level_db,
+                      uint32_t n_items, float *gains, uint32_t *n_unleveled);
 // host_output.cpp: texts -> PhonemeElems (grail_say_batch, grail_node_say_batch)
 int say_segments(const std::vector<grail_voice> &voices, const char *const *texts_utf8, uint32_t n_texts,
                  const uint32_t *voice_ids, std::vector<grail_phoneme_elem> &segs, std::vector<uint32_t> &offs);

@@ -440,6 +440,7 @@ int grail_destroy(grail_ctx *ctx)
     comm_release(ctx);
     pipe_destroy_opaque(ctx->host_pipe);
     mix_release(ctx);
+    levels_release(ctx);
     if (ctx->d_voices) (void)hipFree(ctx->d_voices);
     if (ctx->d_voice_elems) (void)hipFree(ctx->d_voice_elems);
     if (ctx->d_truncated) (void)hipFree(ctx->d_truncated);

@@ -159,4 +159,15 @@ hipError_t launch_mix(const MixArgs &args, hipStream_t stream);
 hipError_t launch_pcm16_frames(const float *tracks, uint64_t track_stride, uint32_t n_tracks, uint64_t n_frames,
                                int16_t *frames, hipStream_t stream);
 
+// levels (level_kernels.hip): one wave per (row, frame of `frame` samples), grid_frames = ceil(row_stride / frame) of them
+// per row; per frame the binary64 sum of squares, the largest finite |x| and the count of non-finite samples, at
+// [row * frames_stride + f] (any of the three may be NULL; frames past a row's last are left unwritten)
+hipError_t launch_level_frames(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows,
+                               uint32_t frame, uint32_t grid_frames, double *fsum, float *fpeak, uint32_t *fbad,
+                               uint64_t frames_stride, hipStream_t stream);
+// ... and a row's totals from them: the sums folded in ascending frame order (outputs may be NULL)
+hipError_t launch_level_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t frame,
+                               const double *fsum, const float *fpeak, const uint32_t *fbad, uint64_t frames_stride,
+                               double *sumsq, float *peak, uint32_t *nonfinite, hipStream_t stream);
+
 }  // namespace grail

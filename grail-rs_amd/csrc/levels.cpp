@@ -1,0 +1,191 @@
+// levels.cpp — rendered rows measured on the device: grail_levels_async and grail_frame_levels_async (checks, the frame
+// scratch, the launches) and what grail_batch_mix_leveled (mix.cpp) needs per block.  The kernels are level_kernels.hip,
+// the gains are level_gains.cpp (pure host).  DESIGN.md §4.9.
+#include "api_internal.hpp"
+
+using namespace grail;
+using namespace grail::host;
+
+// Per context (grail_ctx::level_state), grown and never shrunk, freed by grail_destroy: the per-frame numbers that a
+// totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), and one block's totals for the leveled mix.
+struct LevelState {
+    double *d_fsum = nullptr;
+    float *d_fpeak = nullptr;
+    uint32_t *d_fbad = nullptr;
+    size_t cap_fsum = 0, cap_fpeak = 0, cap_fbad = 0;
+    double *d_sumsq = nullptr;
+    float *d_peak = nullptr;
+    uint32_t *d_bad = nullptr;
+    size_t cap_sumsq = 0, cap_peak = 0, cap_bad = 0;
+};
+
+namespace grail {
+namespace host {
+
+void levels_release(grail_ctx *ctx)
+{
+    LevelState *st = (LevelState *)ctx->level_state;
+    if (!st) return;
+    for (void *p : {(void *)st->d_fsum, (void *)st->d_fpeak, (void *)st->d_fbad, (void *)st->d_sumsq, (void *)st->d_peak,
+                    (void *)st->d_bad})
+        if (p) (void)hipFree(p);
+    delete st;
+    ctx->level_state = nullptr;
+}
+
+}  // namespace host
+}  // namespace grail
+
+namespace {
+
+template <typename T>
+int reserve(grail_ctx *ctx, T **p, size_t *cap, size_t n)
+{
+    n = std::max<size_t>(n, 1);
+    if (*cap >= n) return GRAIL_OK;
+    if (*p) {
+        HIP_TRY(hipStreamSynchronize(ctx->stream));    // (a queued measurement may still use the old buffer)
+        HIP_TRY(hipFree(*p));
+        *p = nullptr;
+        *cap = 0;
+    }
+    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
+    *cap = n;
+    return GRAIL_OK;
+}
+
+// a context, or why there is none: the device entry points say GRAIL_ERR_NO_DEVICE on a machine without a GPU
+int bind_device(grail_ctx *ctx, const char *who)
+{
+    if (ctx) return bind(ctx);
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+        return fail(GRAIL_ERR_NO_DEVICE, std::string(who) + ": no usable HIP device (there is no CPU fallback)");
+    return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": ctx is NULL");
+}
+
+LevelState *state(grail_ctx *ctx)
+{
+    if (!ctx->level_state) ctx->level_state = new (std::nothrow) LevelState();
+    return (LevelState *)ctx->level_state;
+}
+
+uint64_t ceil_div(uint64_t a, uint64_t b) { return a / b + (a % b != 0); }
+
+// the rows' totals with frames of GRAIL_LEVEL_FRAME through the context's frame scratch (which then holds the frames'
+// numbers at stride ceil(row_stride / GRAIL_LEVEL_FRAME) until the context's next measurement)
+int totals(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+           uint32_t n_rows, double *sumsq_dev, float *peak_dev, uint32_t *nonfinite_dev)
+{
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    const uint64_t frames = ceil_div(row_stride, GRAIL_LEVEL_FRAME);
+    if (frames == 0) {          // rows of no samples: +0.0, +0.0f, 0
+        const hipError_t e = launch_level_totals(len_dev, 0, n_rows, GRAIL_LEVEL_FRAME, nullptr, nullptr, nullptr, 0,
+                                                 sumsq_dev, peak_dev, nonfinite_dev, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "level totals kernel launch");
+        return GRAIL_OK;
+    }
+    if (frames > 0xFFFFFFFFull || (uint64_t)n_rows * frames > (1ull << 32))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^32 frames");
+    const size_t cells = (size_t)n_rows * (size_t)frames;
+    int rc;
+    if ((rc = reserve(ctx, &st->d_fsum, &st->cap_fsum, cells))) return rc;
+    if ((rc = reserve(ctx, &st->d_fpeak, &st->cap_fpeak, cells))) return rc;
+    if ((rc = reserve(ctx, &st->d_fbad, &st->cap_fbad, cells))) return rc;
+    hipError_t e = launch_level_frames(rows_dev, row_stride, len_dev, n_rows, GRAIL_LEVEL_FRAME, (uint32_t)frames, st->d_fsum,
+                                       st->d_fpeak, st->d_fbad, frames, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "level frames kernel launch");
+    e = launch_level_totals(len_dev, row_stride, n_rows, GRAIL_LEVEL_FRAME, st->d_fsum, st->d_fpeak, st->d_fbad, frames,
+                            sumsq_dev, peak_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "level totals kernel launch");
+    return GRAIL_OK;
+}
+
+}  // namespace
+
+namespace grail {
+namespace host {
+
+int level_block_gains(grail_ctx *ctx, int mode, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                      const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows, const float *item_level_db,
+                      uint32_t n_items, float *gains, uint32_t *n_unleveled)
+{
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    if (n_rows == 0 || n_items == 0) return GRAIL_OK;
+    int rc;
+    if ((rc = reserve(ctx, &st->d_sumsq, &st->cap_sumsq, n_rows))) return rc;
+    if ((rc = reserve(ctx, &st->d_peak, &st->cap_peak, n_rows))) return rc;
+    if ((rc = reserve(ctx, &st->d_bad, &st->cap_bad, n_rows))) return rc;
+    if ((rc = totals(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, st->d_sumsq, st->d_peak, st->d_bad)))
+        return rc;
+    std::vector<double> sumsq(n_rows), active;
+    std::vector<float> peak(n_rows);
+    std::vector<uint32_t> bad(n_rows);
+    if (mode == GRAIL_LEVEL_RMS)
+        HIP_TRY(hipMemcpyAsync(sumsq.data(), st->d_sumsq, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (mode == GRAIL_LEVEL_PEAK)
+        HIP_TRY(hipMemcpyAsync(peak.data(), st->d_peak, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(bad.data(), st->d_bad, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+    std::vector<double> frames;
+    const uint64_t fs = ceil_div(row_stride, GRAIL_LEVEL_FRAME);
+    if (mode == GRAIL_LEVEL_ACTIVE && fs) {
+        frames.resize((size_t)n_rows * fs);
+        HIP_TRY(hipMemcpyAsync(frames.data(), st->d_fsum, frames.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (mode == GRAIL_LEVEL_ACTIVE) {
+        active.assign(n_rows, 0.0);
+        // (frames past a row's last were never written: grail_active_level reads ceil(len / frame) of them)
+        for (uint32_t r = 0; r < n_rows && fs; ++r)
+            active[r] = grail_active_level(frames.data() + (size_t)r * fs, row_len[r], GRAIL_LEVEL_FRAME,
+                                           GRAIL_LEVEL_ACTIVE_FLOOR_DB);
+    }
+    uint32_t unleveled = 0;
+    rc = grail_level_gains(mode, sumsq.data(), peak.data(), bad.data(), row_len, active.data(), n_rows, item_rows,
+                           item_level_db, n_items, gains, &unleveled);
+    if (rc) return fail(rc, "grail_batch_mix_leveled: grail_level_gains refused the block");
+    *n_unleveled += unleveled;
+    return GRAIL_OK;
+}
+
+}  // namespace host
+}  // namespace grail
+
+extern "C" {
+
+int grail_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                       uint32_t n_rows, double *sumsq_dev, float *peak_dev, uint32_t *nonfinite_dev)
+{
+    int rc = bind_device(ctx, "grail_levels_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_levels_async: NULL buffer");
+    if (!sumsq_dev && !peak_dev && !nonfinite_dev) return GRAIL_OK;
+    return totals(ctx, "grail_levels_async", rows_dev, row_stride, len_dev, n_rows, sumsq_dev, peak_dev, nonfinite_dev);
+}
+
+int grail_frame_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                             uint32_t n_rows, uint32_t frame, double *frame_sumsq_dev, float *frame_peak_dev,
+                             uint64_t frames_stride)
+{
+    int rc = bind_device(ctx, "grail_frame_levels_async");
+    if (rc) return rc;
+    if (frame < GRAIL_LEVEL_FRAME_MIN || frame > GRAIL_LEVEL_FRAME_MAX)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_frame_levels_async: frame is outside 256 .. 1 048 576");
+    const uint64_t frames = ceil_div(row_stride, frame);
+    if (frames_stride < frames)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_frame_levels_async: frames_stride < ceil(row_stride / frame)");
+    if (n_rows == 0 || frames == 0) return GRAIL_OK;
+    if (!len_dev || !rows_dev) return fail(GRAIL_ERR_INVALID_ARG, "grail_frame_levels_async: NULL buffer");
+    if (!frame_sumsq_dev && !frame_peak_dev) return GRAIL_OK;
+    if (frames > 0xFFFFFFFFull || (uint64_t)n_rows * frames > (1ull << 32))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_frame_levels_async: more than 2^32 frames");
+    const hipError_t e = launch_level_frames(rows_dev, row_stride, len_dev, n_rows, frame, (uint32_t)frames, frame_sumsq_dev,
+                                             frame_peak_dev, nullptr, frames_stride, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "level frames kernel launch");
+    return GRAIL_OK;
+}
+
+}  // extern "C"

@@ -121,6 +121,118 @@ int mix_rows(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t ro
     return GRAIL_OK;
 }
 
+// grail_batch_mix after bind(), and grail_batch_mix_leveled: with item_level_db the gains are not given but derived per
+// block, between its rendering and its mix, from the block's measured rows (levels.cpp: one small copy and one wait per
+// block); they are returned through gains_out / n_unleveled once everything has succeeded
+int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const uint32_t *item_rows,
+              const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_gains,
+              const float *item_level_db, int mode, uint32_t n_items, float *tracks_dev, uint64_t track_stride,
+              uint32_t n_tracks, uint64_t track_len, uint32_t *out_len, float *gains_out, uint32_t *n_unleveled,
+              uint32_t flags)
+{
+    int rc;
+    if ((rc = check_ready(ctx, batch))) return rc;
+    const bool leveled = item_level_db != nullptr;
+    std::vector<float> level_gains(leveled ? n_items : 0);
+    uint32_t unleveled = 0;
+    const uint32_t n = batch->n_utt;
+    // the items' checks before anything is rendered (the plan repeats them per block, with the rows' lengths)
+    if (n_items && (!item_rows || !item_offsets)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": item_rows or item_offsets is NULL");
+    if (n_tracks && !tracks_dev) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": tracks_dev is NULL");
+    if (track_len > track_stride) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": track_len > track_stride");
+    if (flags & ~GRAIL_MIX_ACCUMULATE) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": unknown flags");
+    for (uint32_t i = 0; i < n_items; ++i) {
+        if (item_rows[i] >= n) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": an item's row is >= the batch size");
+        if ((item_tracks ? item_tracks[i] : 0u) >= n_tracks)
+            return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": an item's track is >= n_tracks");
+    }
+    if (n == 0) {           // nothing to render: the tracks as an empty mix leaves them (+0.0, or untouched)
+        rc = mix_rows(ctx, who, nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, tracks_dev,
+                      track_stride, n_tracks, track_len, flags);
+        const int sync_rc = grail_sync(ctx);
+        if (!rc && !sync_rc && leveled && n_unleveled) *n_unleveled = 0;
+        return rc ? rc : sync_rc;
+    }
+    std::vector<uint32_t> lens(n);
+    if ((rc = grail_batch_lengths(ctx, batch, 0xFFFFFFFFu, lens.data()))) return rc;
+    const uint64_t longest = *std::max_element(lens.begin(), lens.end());
+    const uint64_t stride = std::max<uint64_t>(64, (longest + 63) / 64 * 64);
+    if (!ctx->mix_state) ctx->mix_state = new (std::nothrow) MixState();
+    MixState *st = (MixState *)ctx->mix_state;
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "mix state");
+    // the block rule of the header: 2 x 256 x CUs rows, as many as half of the free HBM holds (the context's scratch from an
+    // earlier call counts as free: it is this call's to reuse)
+    uint64_t block = 2ull * 256ull * (uint64_t)std::max(ctx->cus, 1);
+    size_t free_bytes = 0, total_bytes = 0;
+    HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes));
+    const uint64_t fit = (uint64_t)((free_bytes + st->cap_rows * sizeof(float)) / 2) / (stride * sizeof(float));
+    if (fit == 0) return fail(GRAIL_ERR_OUT_OF_MEMORY, std::string(who) + ": not one row fits in half of the free HBM");
+    block = std::min(block, fit);
+    const bool one_piece = n <= block;
+    const uint64_t rows_alloc = one_piece ? n : block;
+    const uint64_t n_blocks = one_piece ? 1 : (n + block - 1) / block;
+    // the items of each block, in the order given (the plan orders them by row; blocks follow each other in row order)
+    std::vector<std::vector<uint32_t>> of_block(n_blocks);
+    if (!one_piece)
+        for (uint32_t i = 0; i < n_items; ++i) of_block[item_rows[i] / block].push_back(i);
+    if ((rc = reserve(ctx, &st->d_rows, &st->cap_rows, rows_alloc * stride, false))) return rc;
+    if ((rc = reserve(ctx, &st->d_len, &st->cap_len, rows_alloc, false))) return rc;
+    float *const d_rows = st->d_rows;
+    uint32_t *const d_len = st->d_len;
+    std::vector<uint32_t> sub_rows, sub_tracks;
+    std::vector<uint64_t> sub_offs;
+    std::vector<float> sub_gains, sub_levels;
+    for (uint64_t b = 0; !rc && b < n_blocks; ++b) {
+        const uint32_t first = (uint32_t)(b * block), count = (uint32_t)std::min<uint64_t>(block, n - first);
+        const uint32_t fl = b ? flags | GRAIL_MIX_ACCUMULATE : flags;
+        if (one_piece) {
+            rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len);      // = grail_batch_synthesize_async
+            if (!rc && leveled) {
+                rc = level_block_gains(ctx, mode, d_rows, stride, d_len, lens.data(), n, item_rows, item_level_db, n_items,
+                                       level_gains.data(), &unleveled);
+                item_gains = level_gains.data();
+            }
+            if (!rc)
+                rc = mix_rows(ctx, who, d_rows, stride, lens.data(), n, item_rows, item_tracks, item_offsets,
+                              item_gains, n_items, tracks_dev, track_stride, n_tracks, track_len, fl);
+            break;
+        }
+        if (b && of_block[b].empty()) continue;      // no item reads these rows: not rendered at all
+        rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len, first, count, (uint32_t)block);
+        if (rc) break;
+        sub_rows.clear();
+        sub_tracks.clear();
+        sub_offs.clear();
+        sub_gains.clear();
+        sub_levels.clear();
+        for (const uint32_t i : of_block[b]) {
+            sub_rows.push_back(item_rows[i] - first);
+            if (item_tracks) sub_tracks.push_back(item_tracks[i]);
+            sub_offs.push_back(item_offsets[i]);
+            if (item_gains) sub_gains.push_back(item_gains[i]);
+            if (leveled) sub_levels.push_back(item_level_db[i]);
+        }
+        if (leveled) {
+            sub_gains.assign(sub_rows.size(), 0.0f);
+            rc = level_block_gains(ctx, mode, d_rows, stride, d_len, lens.data() + first, count, sub_rows.data(),
+                                   sub_levels.data(), (uint32_t)sub_rows.size(), sub_gains.data(), &unleveled);
+            if (rc) break;
+            for (size_t k = 0; k < of_block[b].size(); ++k) level_gains[of_block[b][k]] = sub_gains[k];
+        }
+        rc = mix_rows(ctx, who, d_rows, stride, lens.data() + first, count, sub_rows.data(),
+                      item_tracks ? sub_tracks.data() : nullptr, sub_offs.data(),
+                      item_gains || leveled ? sub_gains.data() : nullptr,
+                      (uint32_t)sub_rows.size(), tracks_dev, track_stride, n_tracks, track_len, fl);
+    }
+    const int sync_rc = grail_sync(ctx);      // (every block queued; a cut row cannot happen: the stride holds the longest)
+    if (rc) return rc;
+    if (sync_rc) return sync_rc;
+    if (out_len) std::memcpy(out_len, lens.data(), (size_t)n * sizeof(uint32_t));
+    if (leveled && gains_out && n_items) std::memcpy(gains_out, level_gains.data(), (size_t)n_items * sizeof(float));
+    if (leveled && n_unleveled) *n_unleveled = unleveled;
+    return GRAIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -144,85 +256,30 @@ int grail_batch_mix(grail_ctx *ctx, const grail_batch *batch, const uint32_t *it
 {
     int rc = bind(ctx);
     if (rc) return rc;
-    if ((rc = check_ready(ctx, batch))) return rc;
-    const uint32_t n = batch->n_utt;
-    // the items' checks before anything is rendered (the plan repeats them per block, with the rows' lengths)
-    if (n_items && (!item_rows || !item_offsets)) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: item_rows or item_offsets is NULL");
-    if (n_tracks && !tracks_dev) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: tracks_dev is NULL");
-    if (track_len > track_stride) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: track_len > track_stride");
-    if (flags & ~GRAIL_MIX_ACCUMULATE) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: unknown flags");
-    for (uint32_t i = 0; i < n_items; ++i) {
-        if (item_rows[i] >= n) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: an item's row is >= the batch size");
-        if ((item_tracks ? item_tracks[i] : 0u) >= n_tracks)
-            return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix: an item's track is >= n_tracks");
+    return batch_mix(ctx, "grail_batch_mix", batch, item_rows, item_tracks, item_offsets, item_gains, nullptr, 0, n_items,
+                     tracks_dev, track_stride, n_tracks, track_len, out_len, nullptr, nullptr, flags);
+}
+
+int grail_batch_mix_leveled(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                            const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_level_db,
+                            int mode, uint32_t n_items, float *tracks_dev, uint64_t track_stride, uint32_t n_tracks,
+                            uint64_t track_len, uint32_t *out_len, float *item_gains_out, uint32_t *n_unleveled,
+                            uint32_t flags)
+{
+    if (!ctx) {                 // (no context can exist without a device: say which of the two it is)
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+            return fail(GRAIL_ERR_NO_DEVICE, "grail_batch_mix_leveled: no usable HIP device (there is no CPU fallback)");
     }
-    if (n == 0) {           // nothing to render: the tracks as an empty mix leaves them (+0.0, or untouched)
-        rc = mix_rows(ctx, "grail_batch_mix", nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, tracks_dev,
-                      track_stride, n_tracks, track_len, flags);
-        const int sync_rc = grail_sync(ctx);
-        return rc ? rc : sync_rc;
-    }
-    std::vector<uint32_t> lens(n);
-    if ((rc = grail_batch_lengths(ctx, batch, 0xFFFFFFFFu, lens.data()))) return rc;
-    const uint64_t longest = *std::max_element(lens.begin(), lens.end());
-    const uint64_t stride = std::max<uint64_t>(64, (longest + 63) / 64 * 64);
-    if (!ctx->mix_state) ctx->mix_state = new (std::nothrow) MixState();
-    MixState *st = (MixState *)ctx->mix_state;
-    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "mix state");
-    // the block rule of the header: 2 x 256 x CUs rows, as many as half of the free HBM holds (the context's scratch from an
-    // earlier call counts as free: it is this call's to reuse)
-    uint64_t block = 2ull * 256ull * (uint64_t)std::max(ctx->cus, 1);
-    size_t free_bytes = 0, total_bytes = 0;
-    HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes));
-    const uint64_t fit = (uint64_t)((free_bytes + st->cap_rows * sizeof(float)) / 2) / (stride * sizeof(float));
-    if (fit == 0) return fail(GRAIL_ERR_OUT_OF_MEMORY, "grail_batch_mix: not one row fits in half of the free HBM");
-    block = std::min(block, fit);
-    const bool one_piece = n <= block;
-    const uint64_t rows_alloc = one_piece ? n : block;
-    const uint64_t n_blocks = one_piece ? 1 : (n + block - 1) / block;
-    // the items of each block, in the order given (the plan orders them by row; blocks follow each other in row order)
-    std::vector<std::vector<uint32_t>> of_block(n_blocks);
-    if (!one_piece)
-        for (uint32_t i = 0; i < n_items; ++i) of_block[item_rows[i] / block].push_back(i);
-    if ((rc = reserve(ctx, &st->d_rows, &st->cap_rows, rows_alloc * stride, false))) return rc;
-    if ((rc = reserve(ctx, &st->d_len, &st->cap_len, rows_alloc, false))) return rc;
-    float *const d_rows = st->d_rows;
-    uint32_t *const d_len = st->d_len;
-    std::vector<uint32_t> sub_rows, sub_tracks;
-    std::vector<uint64_t> sub_offs;
-    std::vector<float> sub_gains;
-    for (uint64_t b = 0; !rc && b < n_blocks; ++b) {
-        const uint32_t first = (uint32_t)(b * block), count = (uint32_t)std::min<uint64_t>(block, n - first);
-        const uint32_t fl = b ? flags | GRAIL_MIX_ACCUMULATE : flags;
-        if (one_piece) {
-            rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len);      // = grail_batch_synthesize_async
-            if (!rc)
-                rc = mix_rows(ctx, "grail_batch_mix", d_rows, stride, lens.data(), n, item_rows, item_tracks, item_offsets,
-                              item_gains, n_items, tracks_dev, track_stride, n_tracks, track_len, fl);
-            break;
-        }
-        if (b && of_block[b].empty()) continue;      // no item reads these rows: not rendered at all
-        rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len, first, count, (uint32_t)block);
-        if (rc) break;
-        sub_rows.clear();
-        sub_tracks.clear();
-        sub_offs.clear();
-        sub_gains.clear();
-        for (const uint32_t i : of_block[b]) {
-            sub_rows.push_back(item_rows[i] - first);
-            if (item_tracks) sub_tracks.push_back(item_tracks[i]);
-            sub_offs.push_back(item_offsets[i]);
-            if (item_gains) sub_gains.push_back(item_gains[i]);
-        }
-        rc = mix_rows(ctx, "grail_batch_mix", d_rows, stride, lens.data() + first, count, sub_rows.data(),
-                      item_tracks ? sub_tracks.data() : nullptr, sub_offs.data(), item_gains ? sub_gains.data() : nullptr,
-                      (uint32_t)sub_rows.size(), tracks_dev, track_stride, n_tracks, track_len, fl);
-    }
-    const int sync_rc = grail_sync(ctx);      // (every block queued; a cut row cannot happen: the stride holds the longest)
+    int rc = bind(ctx);
     if (rc) return rc;
-    if (sync_rc) return sync_rc;
-    if (out_len) std::memcpy(out_len, lens.data(), (size_t)n * sizeof(uint32_t));
-    return GRAIL_OK;
+    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix_leveled: unknown mode");
+    static const float none = 0.0f;
+    if (n_items && !item_level_db) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix_leveled: item_level_db is NULL");
+    return batch_mix(ctx, "grail_batch_mix_leveled", batch, item_rows, item_tracks, item_offsets, nullptr,
+                     item_level_db ? item_level_db : &none, mode, n_items, tracks_dev, track_stride, n_tracks, track_len,
+                     out_len, item_gains_out, n_unleveled, flags);
 }
 
 int grail_pcm16_frames_async(grail_ctx *ctx, const float *tracks_dev, uint64_t track_stride,

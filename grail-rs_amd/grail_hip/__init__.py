@@ -74,8 +74,12 @@ EXPORTS = [
     "grail_node_lengths", "grail_node_last_shard_ms", "grail_node_host_alloc", "grail_node_host_free",
     "grail_mix_async", "grail_batch_mix", "grail_mix_place_sequential", "grail_pcm16_frames_async",
     "grail_wav_write_i16_frames",
+    "grail_levels_async", "grail_frame_levels_async", "grail_level_gains", "grail_active_level", "grail_batch_mix_leveled",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
+LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
+LEVEL_FRAME = 4096               # GRAIL_LEVEL_FRAME: the frame length of the row totals
+LEVEL_ACTIVE_FLOOR_DB = 40.0     # GRAIL_LEVEL_ACTIVE_FLOOR_DB
 
 
 class GrailError(RuntimeError):
@@ -321,6 +325,13 @@ def load():
     L.grail_mix_place_sequential.argtypes = [vp, C.c_uint32, vp, vp, vp, C.c_uint32, C.c_uint32, vp, vp]
     L.grail_pcm16_frames_async.argtypes = [vp, vp, u64, C.c_uint32, u64, vp]
     L.grail_wav_write_i16_frames.argtypes = [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.grail_levels_async.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp, vp]
+    L.grail_frame_levels_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, u64]
+    L.grail_level_gains.argtypes = [C.c_int, vp, vp, vp, vp, vp, C.c_uint32, vp, vp, C.c_uint32, vp, vp]
+    L.grail_active_level.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_float]
+    L.grail_active_level.restype = C.c_double
+    L.grail_batch_mix_leveled.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp, vp,
+                                          vp, C.c_uint32]
     _lib = L
     return L
 
@@ -577,6 +588,36 @@ def _ptr(a):
     return None if a is None else a.ctypes.data
 
 
+def level_gains(mode, item_rows, item_level_db, sumsq=None, peak=None, nonfinite=None, row_len=None, active_level=None,
+                n_rows=None):
+    """grail_level_gains (pure host): the gain that brings each item's row to item_level_db[i] dB, from the rows' numbers
+    (LEVEL_PEAK: peak; LEVEL_RMS: sumsq and row_len; LEVEL_ACTIVE: active_level).  Returns (gains float32[n_items],
+    n_unleveled: the items that got gain 0 because their row's level is 0 or it holds a non-finite sample)."""
+    arr = lambda a, t: None if a is None else np.ascontiguousarray(a, dtype=t)
+    sumsq, peak, nonfinite = arr(sumsq, np.float64), arr(peak, np.float32), arr(nonfinite, np.uint32)
+    row_len, active_level = arr(row_len, np.uint32), arr(active_level, np.float64)
+    given = [len(a) for a in (sumsq, peak, nonfinite, row_len, active_level) if a is not None]
+    if n_rows is None:
+        n_rows = min(given) if given else 0
+    assert all(g >= n_rows for g in given)
+    rows = np.ascontiguousarray(item_rows, dtype=np.uint32)
+    db = np.ascontiguousarray(item_level_db, dtype=np.float32)
+    assert len(db) == len(rows)
+    gains = np.full(max(len(rows), 1), np.nan, dtype=np.float32)
+    n_unleveled = C.c_uint32(0xFFFFFFFF)
+    _check(load().grail_level_gains(int(mode), _ptr(sumsq), _ptr(peak), _ptr(nonfinite), _ptr(row_len), _ptr(active_level),
+                                    n_rows, rows.ctypes.data, db.ctypes.data, len(rows), gains.ctypes.data,
+                                    C.addressof(n_unleveled)))
+    return gains[:len(rows)], n_unleveled.value
+
+
+def active_level(frame_sumsq, row_len, frame=LEVEL_FRAME, floor_db=LEVEL_ACTIVE_FLOOR_DB):
+    """grail_active_level (pure host): sqrt(mean square) over the frames within floor_db of the loudest frame."""
+    fs = np.ascontiguousarray(frame_sumsq, dtype=np.float64)
+    assert len(fs) >= -(-int(row_len) // int(frame))
+    return float(load().grail_active_level(fs.ctypes.data, int(row_len), int(frame), float(floor_db)))
+
+
 class Batch:
     def __init__(self, ctx, handle, n_utt):
         self.ctx, self.handle, self.n_utt = ctx, handle, n_utt
@@ -605,6 +646,22 @@ class Batch:
                                       _ptr(gains), len(rows), tracks_dev, track_stride, n_tracks, track_len,
                                       out_len.ctypes.data, MIX_ACCUMULATE if accumulate else 0))
         return out_len[:self.n_utt]
+
+    def mix_leveled(self, item_rows, item_offsets, item_level_db, tracks_dev, track_stride, n_tracks, track_len,
+                    item_tracks=None, mode=LEVEL_RMS, accumulate=False):
+        """grail_batch_mix_leveled: mix() with a level in dB per item instead of a gain; every block's rows are measured on
+        the device between rendering and mixing.  Returns (the rows' lengths, the gains used, n_unleveled)."""
+        rows, offs, tracks, _ = _mix_items(item_rows, item_offsets, item_tracks, None)
+        db = np.ascontiguousarray(item_level_db, dtype=np.float32)
+        assert len(db) == len(rows)
+        out_len = np.zeros(max(self.n_utt, 1), dtype=np.uint32)
+        gains = np.zeros(max(len(rows), 1), dtype=np.float32)
+        n_unleveled = C.c_uint32(0)
+        _check(load().grail_batch_mix_leveled(self.ctx.handle, self.handle, rows.ctypes.data, _ptr(tracks), offs.ctypes.data,
+                                              db.ctypes.data, int(mode), len(rows), tracks_dev, track_stride, n_tracks,
+                                              track_len, out_len.ctypes.data, gains.ctypes.data, C.addressof(n_unleveled),
+                                              MIX_ACCUMULATE if accumulate else 0))
+        return out_len[:self.n_utt], gains[:len(rows)], n_unleveled.value
 
     def free(self):
         if self.handle:
@@ -833,6 +890,54 @@ class Context:
     def pcm16_frames_async(self, tracks_dev, track_stride, n_tracks, n_frames, frames_dev):
         """grail_pcm16_frames_async: tracks -> interleaved i16 frames (frames_dev[f * n_tracks + t])."""
         _check(load().grail_pcm16_frames_async(self.handle, tracks_dev, track_stride, n_tracks, n_frames, frames_dev))
+
+    def levels_async(self, rows_dev, row_stride, len_dev, n_rows, sumsq_dev=None, peak_dev=None, nonfinite_dev=None):
+        """grail_levels_async: per row the binary64 sum of squares, the largest finite |x| and the count of non-finite
+        samples, into DEVICE arrays [n_rows] (any may be None), queued on the context's stream."""
+        _check(load().grail_levels_async(self.handle, rows_dev, row_stride, len_dev, n_rows, sumsq_dev, peak_dev,
+                                         nonfinite_dev))
+
+    def levels(self, rows_dev, row_stride, len_dev, n_rows):
+        """levels_async, waited for and copied back: (sumsq float64, peak float32, nonfinite uint32), one per row."""
+        sumsq = np.zeros(max(n_rows, 1), dtype=np.float64)
+        peak = np.zeros(max(n_rows, 1), dtype=np.float32)
+        bad = np.zeros(max(n_rows, 1), dtype=np.uint32)
+        d = [self.device_alloc(max(n_rows, 1) * k) for k in (8, 4, 4)]
+        try:
+            self.levels_async(rows_dev, row_stride, len_dev, n_rows, *d)
+            for dst, src in zip((sumsq, peak, bad), d):
+                self.d2h(dst, src, n_rows * dst.itemsize)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return sumsq[:n_rows], peak[:n_rows], bad[:n_rows]
+
+    def frame_levels_async(self, rows_dev, row_stride, len_dev, n_rows, frame, frame_sumsq_dev, frame_peak_dev,
+                           frames_stride):
+        """grail_frame_levels_async: per frame of `frame` samples, into DEVICE arrays [n_rows][frames_stride]."""
+        _check(load().grail_frame_levels_async(self.handle, rows_dev, row_stride, len_dev, n_rows, frame, frame_sumsq_dev,
+                                               frame_peak_dev, frames_stride))
+
+    def frame_levels(self, rows_dev, row_stride, len_dev, n_rows, frame, fill=None):
+        """frame_levels_async, waited for and copied back: (sumsq float64 [n_rows, frames], peak float32 [n_rows, frames])
+        with frames = ceil(row_stride / frame).  Frames past a row's end hold `fill` (default NaN): the call leaves them
+        unwritten."""
+        frames = max(-(-int(row_stride) // int(frame)), 1)
+        sumsq = np.full((max(n_rows, 1), frames), np.nan if fill is None else fill, dtype=np.float64)
+        peak = np.full((max(n_rows, 1), frames), np.nan if fill is None else fill, dtype=np.float32)
+        d = [self.device_alloc(sumsq.nbytes), self.device_alloc(peak.nbytes)]
+        try:
+            self.h2d(d[0], sumsq, sumsq.nbytes)
+            self.h2d(d[1], peak, peak.nbytes)
+            self.frame_levels_async(rows_dev, row_stride, len_dev, n_rows, frame, d[0], d[1], frames)
+            self.d2h(sumsq, d[0], sumsq.nbytes)
+            self.d2h(peak, d[1], peak.nbytes)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return sumsq[:n_rows], peak[:n_rows]
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max |x|, non-finite counts) per row, computed on the device."""

@@ -240,6 +240,18 @@ extern "C" {
         n_tracks: u32, n_frames: u64, frames_dev: *mut i16) -> c_int;
     pub fn grail_wav_write_i16_frames(path: *const c_char, frames: *const i16, n_frames: u32,
         n_channels: u32, sample_rate: u32) -> c_int;
+    pub fn grail_levels_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, sumsq_dev: *mut f64, peak_dev: *mut f32, nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_frame_levels_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, frame: u32, frame_sumsq_dev: *mut f64, frame_peak_dev: *mut f32, frames_stride: u64) -> c_int;
+    pub fn grail_level_gains(mode: c_int, sumsq: *const f64, peak: *const f32, nonfinite: *const u32,
+        row_len: *const u32, active_level: *const f64, n_rows: u32, item_rows: *const u32,
+        item_level_db: *const f32, n_items: u32, item_gains: *mut f32, n_unleveled: *mut u32) -> c_int;
+    pub fn grail_active_level(frame_sumsq: *const f64, row_len: u32, frame: u32, floor_db: f32) -> f64;
+    pub fn grail_batch_mix_leveled(ctx: *mut grail_ctx, batch: *const grail_batch, item_rows: *const u32,
+        item_tracks: *const u32, item_offsets: *const u64, item_level_db: *const f32, mode: c_int, n_items: u32,
+        tracks_dev: *mut f32, track_stride: u64, n_tracks: u32, track_len: u64, out_len: *mut u32,
+        item_gains_out: *mut f32, n_unleveled: *mut u32, flags: u32) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

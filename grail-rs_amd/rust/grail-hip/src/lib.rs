@@ -325,6 +325,63 @@ impl Gpu {
         }
         Ok(host.chunks(stride as usize).map(|t| t[..track_len as usize].to_vec()).collect())
     }
+
+    /// [`Gpu::mix`] with a level per placement instead of a gain (`grail_batch_mix_leveled`): placement `i`'s utterance is
+    /// brought to `level_db[i]` decibels (0 dB = level 1.0) of `mode`; `Placement::gain` is not read.  The rows are
+    /// measured on the device between rendering and mixing.  Returns the tracks, the gains that were used and the number
+    /// of placements that got gain 0 (an empty or silent utterance, or one holding a non-finite sample).
+    pub fn mix_leveled<I: IntoIterator<Item = Utterance>>(&self, utterances: I, placements: &[Placement], level_db: &[f32],
+                                                         mode: LevelMode, n_tracks: u32, track_len: u64)
+                                                         -> Result<(Vec<Vec<f32>>, Vec<f32>, u32), Error> {
+        assert_eq!(level_db.len(), placements.len());
+        let b = FlatBatch::new(utterances);
+        let rows: Vec<u32> = placements.iter().map(|p| p.utterance).collect();
+        let tracks: Vec<u32> = placements.iter().map(|p| p.track).collect();
+        let offsets: Vec<u64> = placements.iter().map(|p| p.offset).collect();
+        let stride = ((track_len + 63) / 64 * 64).max(64);
+        let floats = n_tracks as usize * stride as usize;
+        let mut host = vec![0f32; floats];
+        let mut gains = vec![0f32; rows.len().max(1)];
+        let mut unleveled = 0u32;
+        unsafe {
+            let mut h = std::ptr::null_mut();
+            check(sys::grail_batch_upload(self.ctx, b.segs.as_ptr(), b.offs.as_ptr(), b.vids.as_ptr(), b.seeds.as_ptr(),
+                                          b.len(), &mut h))?;
+            let mut d: *mut std::ffi::c_void = std::ptr::null_mut();
+            let mut r = check(sys::grail_device_alloc(self.ctx, floats * 4 + 4, &mut d));
+            if r.is_ok() {
+                r = check(sys::grail_batch_mix_leveled(self.ctx, h, rows.as_ptr(), tracks.as_ptr(), offsets.as_ptr(),
+                                                       level_db.as_ptr(), mode as std::os::raw::c_int, rows.len() as u32,
+                                                       d as *mut f32, stride, n_tracks, track_len, std::ptr::null_mut(),
+                                                       gains.as_mut_ptr(), &mut unleveled, 0));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, host.as_mut_ptr() as *mut std::ffi::c_void, d, floats * 4));
+            }
+            if !d.is_null() {
+                sys::grail_device_free(self.ctx, d);
+            }
+            sys::grail_batch_free(self.ctx, h);
+            r?;
+        }
+        gains.truncate(rows.len());
+        Ok((host.chunks(stride as usize).map(|t| t[..track_len as usize].to_vec()).collect(), gains, unleveled))
+    }
+}
+
+/// What "level" means to [`Gpu::mix_leveled`] (GRAIL_LEVEL_PEAK / _RMS / _ACTIVE).
+#[derive(Copy, Clone, Debug, PartialEq, Eq)]
+#[repr(i32)]
+pub enum LevelMode {
+    Peak = 0,
+    Rms = 1,
+    Active = 2,
+}
+
+/// The "active" level of one row from its frames' sums of squares (`grail_active_level`; pure host, no GPU).
+pub fn active_level(frame_sumsq: &[f64], row_len: u32, frame: u32, floor_db: f32) -> f64 {
+    assert!(frame > 0 && frame_sumsq.len() as u64 >= (row_len as u64 + frame as u64 - 1) / frame as u64);
+    unsafe { sys::grail_active_level(frame_sumsq.as_ptr(), row_len, frame, floor_db) }
 }
 
 /// Predicted |fast - reference| of `voice` in units of 2^-23 of max(1, peak) (grail_fast_sharpness): narrow and

@@ -79,6 +79,13 @@ struct Placement {
     float gain = 1.0f;
 };
 
+// What Gpu::levels measures, one entry per row (grail_levels_async)
+struct Levels {
+    std::vector<double> sumsq;         // binary64 sum of squares of the finite samples
+    std::vector<float> peak;           // largest finite |x|
+    std::vector<uint32_t> nonfinite;   // NaN and Inf samples
+};
+
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
                     std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
@@ -234,6 +241,84 @@ public:
         std::vector<std::vector<float>> out(n_tracks);
         for (uint32_t t = 0; t < n_tracks; ++t)
             out[t].assign(flat.begin() + (size_t)t * stride, flat.begin() + (size_t)t * stride + track_len);
+        return out;
+    }
+
+    // Gpu::mix with a level instead of a gain: placement i's utterance is brought to level_db[i] decibels (0 dB = level
+    // 1.0; mode GRAIL_LEVEL_RMS, GRAIL_LEVEL_PEAK or GRAIL_LEVEL_ACTIVE) and Placement::gain is not read.  The rows are
+    // measured on the device between rendering and mixing (grail_batch_mix_leveled).  gains_used, unleveled: the gains the
+    // mix applied, and how many placements got gain 0 because their utterance is empty, silent or holds a non-finite sample.
+    std::vector<std::vector<float>> mix_leveled(const std::vector<Utterance> &utts, const std::vector<Placement> &placements,
+                                                const std::vector<float> &level_db, uint32_t n_tracks, uint64_t track_len,
+                                                int mode = GRAIL_LEVEL_RMS, std::vector<float> *gains_used = nullptr,
+                                                uint32_t *unleveled = nullptr) const
+    {
+        if (level_db.size() != placements.size())
+            throw Error(GRAIL_ERR_INVALID_ARG, "mix_leveled: one level per placement");
+        std::vector<PhonemeElem> segs;
+        std::vector<uint32_t> offs, vids, seeds, rows, tracks;
+        std::vector<uint64_t> at;
+        detail::flatten(utts, segs, offs, vids, seeds);
+        for (const Placement &p : placements) {
+            rows.push_back(p.utterance);
+            tracks.push_back(p.track);
+            at.push_back(p.offset);
+        }
+        const uint64_t stride = track_len ? (track_len + 63) / 64 * 64 : 64;
+        grail_batch *b = nullptr;
+        check(grail_batch_upload(ctx_, segs.data(), offs.data(), vids.data(), seeds.data(), (uint32_t)utts.size(), &b));
+        void *d = nullptr;
+        std::vector<float> flat((size_t)n_tracks * stride), gains(rows.size() ? rows.size() : 1);
+        uint32_t left_out = 0;
+        int rc = grail_device_alloc(ctx_, flat.size() * sizeof(float) + 4, &d);
+        if (!rc) rc = grail_batch_mix_leveled(ctx_, b, rows.data(), tracks.data(), at.data(), level_db.data(), mode,
+                                              (uint32_t)rows.size(), (float *)d, stride, n_tracks, track_len, nullptr,
+                                              gains.data(), &left_out, 0u);
+        if (!rc && !flat.empty()) rc = grail_memcpy_d2h(ctx_, flat.data(), d, flat.size() * sizeof(float));
+        if (d) grail_device_free(ctx_, d);
+        grail_batch_free(ctx_, b);
+        check(rc);
+        gains.resize(rows.size());
+        if (gains_used) *gains_used = gains;
+        if (unleveled) *unleveled = left_out;
+        std::vector<std::vector<float>> out(n_tracks);
+        for (uint32_t t = 0; t < n_tracks; ++t)
+            out[t].assign(flat.begin() + (size_t)t * stride, flat.begin() + (size_t)t * stride + track_len);
+        return out;
+    }
+
+    // How loud rows of samples are, measured on the device (grail_levels_async; the contract is the header's section
+    // "levels"): per row the binary64 sum of squares, the largest finite |x| and the count of non-finite samples.
+    Levels levels(const std::vector<std::vector<float>> &rows) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64;
+        Levels out;
+        out.sumsq.resize(n);
+        out.peak.resize(n);
+        out.nonfinite.resize(n);
+        if (!n) return out;
+        std::vector<uint32_t> lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        void *d_rows = nullptr, *d_len = nullptr, *d_sumsq = nullptr, *d_peak = nullptr, *d_bad = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 8, &d_sumsq);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_peak);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_bad);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc) rc = grail_levels_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, (double *)d_sumsq,
+                                         (float *)d_peak, (uint32_t *)d_bad);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.sumsq.data(), d_sumsq, (size_t)n * 8);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.peak.data(), d_peak, (size_t)n * 4);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
+        for (void *p : {d_rows, d_len, d_sumsq, d_peak, d_bad})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
         return out;
     }
 

@@ -608,6 +608,79 @@ int grail_pcm16_frames_async(grail_ctx *ctx, const float *tracks_dev, uint64_t t
 int grail_wav_write_i16_frames(const char *path, const int16_t *frames, uint32_t n_frames,
                                uint32_t n_channels, uint32_t sample_rate);
 
+/* ---- levels: how loud rendered rows are, measured on the device -----------------------------------------------------
+ * For a row of n = len[u] samples and a frame length F (samples, 256 <= F <= 1 048 576):
+ *   - Frame f holds the samples t in [f*F, min((f+1)*F, n)), t counted from the row's first sample.  A row has
+ *     ceil(n / F) frames; an empty row has none.
+ *   - A sample is FINITE when |x| <= FLT_MAX.  A sample that is not is counted and otherwise skipped.
+ *   - PEAK of a frame: the largest |x| of its finite samples, +0.0 if there are none.
+ *   - SUM OF SQUARES of a frame, binary64: 256 partial sums p[j], j = t mod 256; each starts at +0.0 and is the left
+ *     fold, in ascending t, of p[j] + (double)x * (double)x over the frame's finite samples with that j (the product of
+ *     two binary32 values is exact in binary64, so a fused multiply-add gives the same bits).  Then the halving tree
+ *         for w = 128, 64, ..., 1:  p[j] = p[j] + p[j + w]  for j < w
+ *     and the frame's value is p[0].
+ *   - ROW TOTALS: peak = the largest frame peak; sumsq = the left fold from +0.0, in ascending f, of the frames' sums
+ *     with F = GRAIL_LEVEL_FRAME; nonfinite = the count.
+ * No float atomics anywhere: a row's numbers are a pure function of its samples and F, not of row_stride, the row's
+ * index, the number of rows, the alignment of rows_dev, the device or the launch.  A len[u] above row_stride is read
+ * as row_stride.  -0.0 and denormals are finite samples like any other. */
+#define GRAIL_LEVEL_FRAME      4096u      /* the frame length of the row totals (and of GRAIL_LEVEL_ACTIVE in the leveled mix) */
+#define GRAIL_LEVEL_FRAME_MIN  256u
+#define GRAIL_LEVEL_FRAME_MAX  1048576u
+#define GRAIL_LEVEL_PEAK       0          /* level = peak */
+#define GRAIL_LEVEL_RMS        1          /* level = sqrt(sumsq / len) */
+#define GRAIL_LEVEL_ACTIVE     2          /* level = grail_active_level of the row */
+#define GRAIL_LEVEL_ACTIVE_FLOOR_DB 40.0f /* the floor grail_batch_mix_leveled uses in GRAIL_LEVEL_ACTIVE */
+
+/* Row totals.  Queued on ctx's stream behind earlier work (a grail_batch_synthesize_async before it needs no sync);
+ * rows_dev: device [n_rows][row_stride]; len_dev: device [n_rows], the out_len a rendering wrote; results are DEVICE
+ * arrays [n_rows], any of them may be NULL.  16-byte loads where rows_dev is 16-byte aligned and row_stride a multiple
+ * of 4, 4-byte loads otherwise: same bits.  The per-frame numbers go through scratch that stays with the context
+ * (16 bytes per GRAIL_LEVEL_FRAME samples of n_rows x row_stride), grown and never shrunk, until grail_destroy.
+ * Without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                       uint32_t n_rows, double *sumsq_dev, float *peak_dev, uint32_t *nonfinite_dev);
+
+/* Per frame of `frame` samples: DEVICE arrays [n_rows][frames_stride], either may be NULL; frames past a row's last
+ * are left unwritten.  The lengths live on the device, so the bound the host can check is on row_stride:
+ * frames_stride >= ceil(row_stride / frame), else GRAIL_ERR_INVALID_ARG (as for a frame outside 256 .. 1 048 576).
+ * One wavefront folds one frame, so frames much longer than GRAIL_LEVEL_FRAME need many rows to fill the device. */
+int grail_frame_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                             uint32_t n_rows, uint32_t frame, double *frame_sumsq_dev, float *frame_peak_dev,
+                             uint64_t frames_stride);
+
+/* Pure host (no GPU): the gain that brings item i's row to item_level_db[i] decibels (0 dB = level 1.0),
+ *     gain_i = (float)(pow(10.0, item_level_db[i] / 20.0) / level(row_i))     computed in binary64, rounded once.
+ * mode: GRAIL_LEVEL_PEAK (needs peak), GRAIL_LEVEL_RMS (needs sumsq and row_len), GRAIL_LEVEL_ACTIVE (needs
+ * active_level: one grail_active_level per row); the arrays a mode does not need may be NULL, as may nonfinite (no row
+ * holds a non-finite sample) and n_unleveled.  A row whose level is 0 or that holds a non-finite sample gets gain 0 and
+ * its ITEMS are counted in *n_unleveled: not an error, a batch may hold an empty utterance.
+ * GRAIL_ERR_INVALID_ARG, outputs unwritten: an unknown mode, an item's row >= n_rows, a NULL array the mode needs. */
+int grail_level_gains(int mode, const double *sumsq, const float *peak, const uint32_t *nonfinite,
+                      const uint32_t *row_len, const double *active_level, uint32_t n_rows,
+                      const uint32_t *item_rows, const float *item_level_db, uint32_t n_items, float *item_gains,
+                      uint32_t *n_unleveled);
+
+/* Pure host: the "active" level of one row from its frames' sums of squares [ceil(row_len / frame)] (speech has
+ * pauses; the RMS of a whole row under-reads it).  A frame's mean square is its sum over its own sample count (the
+ * last frame may be short); frames whose mean square is at least 10^(-floor_db / 10) of the loudest frame's are
+ * active; returns sqrt(sum of their sums / sum of their sample counts), both folded in ascending frame order in
+ * binary64.  0.0 for an empty or all-silent row. */
+double grail_active_level(const double *frame_sumsq, uint32_t row_len, uint32_t frame, float floor_db);
+
+/* grail_batch_mix with a level per item instead of a gain: same arguments, block rule, scratch and skipping of blocks
+ * no item reads.  Per block: render, measure (grail_levels_async's kernels), copy the block's numbers to the host (at
+ * most 16 bytes a row, or the frame sums in GRAIL_LEVEL_ACTIVE: frames of GRAIL_LEVEL_FRAME, floor
+ * GRAIL_LEVEL_ACTIVE_FLOOR_DB), grail_level_gains, mix: one small copy and one wait per block more than
+ * grail_batch_mix.  The tracks are the bits grail_batch_mix gives with the gains that were used.
+ * item_gains_out: HOST [n_items] or NULL, those gains; n_unleveled: the items that got gain 0, or NULL; both are
+ * written only when the call succeeds.  Invalid arguments follow the mixing section's rules. */
+int grail_batch_mix_leveled(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                            const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_level_db,
+                            int mode, uint32_t n_items, float *tracks_dev, uint64_t track_stride, uint32_t n_tracks,
+                            uint64_t track_len, uint32_t *out_len, float *item_gains_out, uint32_t *n_unleveled,
+                            uint32_t flags);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
