@@ -1,8 +1,9 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
-// measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).
+// measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
+// K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -16,11 +17,12 @@ int main(int argc, char **argv)
 {
     std::string out_path = "dialogue.wav";
     std::vector<std::string> lines;
-    bool leveled = false, bad_level = false;
+    bool leveled = false, bad_level = false, lufs = false;
     float level_db = 0.0f;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
-        else if (!std::strcmp(argv[i], "--level") && i + 1 < argc) {
+        else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
+            lufs = !std::strcmp(argv[i], "--lufs");
             char *rest = nullptr;
             level_db = std::strtof(argv[++i], &rest);
             leveled = true;
@@ -28,7 +30,7 @@ int main(int argc, char **argv)
         } else lines.push_back(argv[i]);
     }
     if (lines.size() != 2 || bad_level) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB] \"first line\" \"second line\"\n");
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] \"first line\" \"second line\"\n");
         return 2;
     }
     try {
@@ -52,9 +54,14 @@ int main(int argc, char **argv)
             std::vector<float> levels, gains;
             for (const grail::Placement &p : placements) levels.push_back(level_db + 20.0f * std::log10(p.gain));
             uint32_t unleveled = 0;
-            tracks = gpu.mix_leveled(utts, placements, levels, 2, end, GRAIL_LEVEL_RMS, &gains, &unleveled);
-            std::printf("Lines brought to %.1f dB RMS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
-                        unleveled ? " (a silent line was left out)" : "");
+            tracks = gpu.mix_leveled(utts, placements, levels, 2, end, lufs ? GRAIL_LEVEL_LOUDNESS : GRAIL_LEVEL_RMS, &gains,
+                                     &unleveled);
+            if (lufs)
+                std::printf("Lines brought to %.1f LUFS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
+                            unleveled ? " (a silent line or one shorter than 400 ms was left out)" : "");
+            else
+                std::printf("Lines brought to %.1f dB RMS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f,
+                            gains[3] / 0.8f, unleveled ? " (a silent line was left out)" : "");
         } else {
             tracks = gpu.mix(utts, placements, 2, end);
         }

@@ -170,4 +170,14 @@ hipError_t launch_level_totals(const uint32_t *len, uint64_t row_stride, uint32_
                                const double *fsum, const float *fpeak, const uint32_t *fbad, uint64_t frames_stride,
                                double *sumsq, float *peak, uint32_t *nonfinite, hipStream_t stream);
 
+// loudness (loudness_kernels.hip): one lane per row through the two K-weighting sections (coef: HOST [10]), the sum of
+// z*z per hop of `hop` samples at hops[row * hops_stride + h] for the row's floor(n / hop) whole hops, and the count of
+// non-finite samples (may be NULL); hops_stride >= row_stride / hop
+hipError_t launch_loudness_hops(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, uint32_t hop,
+                                const double *coef, double *hops, uint64_t hops_stride, uint32_t *nonfinite,
+                                hipStream_t stream);
+// ... and a row's gated mean square from its hops, one lane per row
+hipError_t launch_loudness_gate(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t hop, const double *hops,
+                                uint64_t hops_stride, double *gated, hipStream_t stream);
+
 }  // namespace grail

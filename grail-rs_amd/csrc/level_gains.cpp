@@ -1,6 +1,8 @@
 // level_gains.cpp — the host side of levels that needs no device: grail_level_gains (a row's numbers and a target level
-// per item -> the item's gain) and grail_active_level (a row's level over its active frames).  No HIP call, so it builds
-// with g++ under AddressSanitizer and UBSan (tests/test_levels_host.py), as mix_plan.cpp does.  DESIGN.md §4.9.
+// per item -> the item's gain), grail_active_level (a row's level over its active frames) and the host side of the
+// K-weighted loudness: grail_kweighting, grail_gated_mean_square, grail_loudness_lufs, grail_loudness_level.  No HIP call,
+// so it builds with g++ under AddressSanitizer and UBSan (tests/test_levels_host.py, tests/test_loudness_host.py), as
+// mix_plan.cpp does.  DESIGN.md §4.9, §4.10.
 #include <cmath>
 
 #include "../../include/grail_hip.h"
@@ -12,11 +14,12 @@ int grail_level_gains(int mode, const double *sumsq, const float *peak, const ui
                       const uint32_t *item_rows, const float *item_level_db, uint32_t n_items, float *item_gains,
                       uint32_t *n_unleveled)
 {
-    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE) return GRAIL_ERR_INVALID_ARG;
+    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE && mode != GRAIL_LEVEL_LOUDNESS)
+        return GRAIL_ERR_INVALID_ARG;
     if (n_items && (!item_rows || !item_level_db || !item_gains)) return GRAIL_ERR_INVALID_ARG;
     if (n_items && mode == GRAIL_LEVEL_PEAK && !peak) return GRAIL_ERR_INVALID_ARG;
     if (n_items && mode == GRAIL_LEVEL_RMS && (!sumsq || !row_len)) return GRAIL_ERR_INVALID_ARG;
-    if (n_items && mode == GRAIL_LEVEL_ACTIVE && !active_level) return GRAIL_ERR_INVALID_ARG;
+    if (n_items && (mode == GRAIL_LEVEL_ACTIVE || mode == GRAIL_LEVEL_LOUDNESS) && !active_level) return GRAIL_ERR_INVALID_ARG;
     for (uint32_t i = 0; i < n_items; ++i)
         if (item_rows[i] >= n_rows) return GRAIL_ERR_INVALID_ARG;          // (before the first gain is written)
     uint32_t unleveled = 0;
@@ -59,5 +62,70 @@ double grail_active_level(const double *frame_sumsq, uint32_t row_len, uint32_t 
     }
     return samples > 0.0 ? std::sqrt(sum / samples) : 0.0;
 }
+
+int grail_kweighting(uint32_t sample_rate, double coef[10])
+{
+    if (!coef || sample_rate < GRAIL_LOUDNESS_RATE_MIN || sample_rate > GRAIL_LOUDNESS_RATE_MAX) return GRAIL_ERR_INVALID_ARG;
+    const double pi = 3.141592653589793, rate = (double)sample_rate;
+    {       // the shelf
+        const double K = std::tan(pi * 1681.974450955533 / rate), Q = 0.7071752369554196;
+        const double Vh = std::pow(10.0, 3.999843853973347 / 20.0), Vb = std::pow(Vh, 0.4996667741545416);
+        const double a0 = 1.0 + K / Q + K * K;
+        coef[0] = (Vh + Vb * K / Q + K * K) / a0;
+        coef[1] = 2.0 * (K * K - Vh) / a0;
+        coef[2] = (Vh - Vb * K / Q + K * K) / a0;
+        coef[3] = 2.0 * (K * K - 1.0) / a0;
+        coef[4] = (1.0 - K / Q + K * K) / a0;
+    }
+    {       // the high-pass
+        const double K = std::tan(pi * 38.13547087602444 / rate), Q = 0.5003270373238773;
+        const double a0 = 1.0 + K / Q + K * K;
+        coef[5] = 1.0;
+        coef[6] = -2.0;
+        coef[7] = 1.0;
+        coef[8] = 2.0 * (K * K - 1.0) / a0;
+        coef[9] = (1.0 - K / Q + K * K) / a0;
+    }
+    return GRAIL_OK;
+}
+
+double grail_gated_mean_square(const double *hop_sumsq, uint32_t n_hops, uint32_t hop)
+{
+    if (!hop_sumsq || hop == 0 || n_hops < 4) return 0.0;
+    const uint32_t blocks = n_hops - 3u;
+    const double per = 4.0 * (double)hop;
+    const auto block = [&](uint32_t j) {
+        return (((hop_sumsq[j] + hop_sumsq[j + 1]) + hop_sumsq[j + 2]) + hop_sumsq[j + 3]) / per;
+    };
+    double sum = 0.0;
+    uint32_t count = 0;
+    for (uint32_t j = 0; j < blocks; ++j) {
+        const double z = block(j);
+        if (z > GRAIL_LOUDNESS_ABS_GATE) {
+            sum = sum + z;
+            ++count;
+        }
+    }
+    if (count == 0) return 0.0;
+    const double r = 0.1 * (sum / (double)count);
+    sum = 0.0;
+    count = 0;
+    for (uint32_t j = 0; j < blocks; ++j) {
+        const double z = block(j);
+        if (z > GRAIL_LOUDNESS_ABS_GATE && z > r) {
+            sum = sum + z;
+            ++count;
+        }
+    }
+    return count ? sum / (double)count : 0.0;
+}
+
+double grail_loudness_lufs(double gated_ms)
+{
+    if (!(gated_ms > 0.0)) return gated_ms == 0.0 ? -HUGE_VAL : gated_ms;      // (a NaN or a negative stays what it is)
+    return -0.691 + 10.0 * std::log10(gated_ms);
+}
+
+double grail_loudness_level(double gated_ms) { return std::sqrt(gated_ms * GRAIL_LOUDNESS_LEVEL_SCALE); }
 
 }  // extern "C"

@@ -1,13 +1,14 @@
-// levels.cpp — rendered rows measured on the device: grail_levels_async and grail_frame_levels_async (checks, the frame
-// scratch, the launches) and what grail_batch_mix_leveled (mix.cpp) needs per block.  The kernels are level_kernels.hip,
-// the gains are level_gains.cpp (pure host).  DESIGN.md §4.9.
+// levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async and grail_loudness_async
+// (checks, the scratch, the launches) and what grail_batch_mix_leveled (mix.cpp) needs per block.  The kernels are
+// level_kernels.hip and loudness_kernels.hip, the gains are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10.
 #include "api_internal.hpp"
 
 using namespace grail;
 using namespace grail::host;
 
 // Per context (grail_ctx::level_state), grown and never shrunk, freed by grail_destroy: the per-frame numbers that a
-// totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), and one block's totals for the leveled mix.
+// totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), one block's totals for the leveled mix, and the
+// hop sums of a loudness call that does not ask for them (8 B per hop of 100 ms).
 struct LevelState {
     double *d_fsum = nullptr;
     float *d_fpeak = nullptr;
@@ -17,6 +18,8 @@ struct LevelState {
     float *d_peak = nullptr;
     uint32_t *d_bad = nullptr;
     size_t cap_sumsq = 0, cap_peak = 0, cap_bad = 0;
+    double *d_hops = nullptr;
+    size_t cap_hops = 0;
 };
 
 namespace grail {
@@ -27,7 +30,7 @@ void levels_release(grail_ctx *ctx)
     LevelState *st = (LevelState *)ctx->level_state;
     if (!st) return;
     for (void *p : {(void *)st->d_fsum, (void *)st->d_fpeak, (void *)st->d_fbad, (void *)st->d_sumsq, (void *)st->d_peak,
-                    (void *)st->d_bad})
+                    (void *)st->d_bad, (void *)st->d_hops})
         if (p) (void)hipFree(p);
     delete st;
     ctx->level_state = nullptr;
@@ -102,14 +105,58 @@ int totals(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_
     return GRAIL_OK;
 }
 
+// hop sums, gated mean squares and non-finite counts (any output may be NULL; hops_dev NULL = the context's scratch)
+int loudness(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+             uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_dev, double *hops_dev,
+             uint64_t hops_stride, uint32_t *nonfinite_dev)
+{
+    double own[10];
+    if (!coef) {
+        if (grail_kweighting(sample_rate, own)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": sample rate out of range");
+        coef = own;
+    }
+    const uint32_t hop = sample_rate / 10u;
+    if (!hops_dev) {
+        LevelState *st = state(ctx);
+        if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+        hops_stride = row_stride / hop;
+        if (hops_stride && (uint64_t)n_rows > (1ull << 40) / hops_stride)
+            return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^40 hops");
+        int rc;
+        if ((rc = reserve(ctx, &st->d_hops, &st->cap_hops, (size_t)n_rows * (size_t)hops_stride))) return rc;
+        hops_dev = st->d_hops;
+    }
+    hipError_t e = launch_loudness_hops(rows_dev, row_stride, len_dev, n_rows, hop, coef, hops_dev, hops_stride,
+                                        nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "loudness hops kernel launch");
+    if (gated_dev) {
+        e = launch_loudness_gate(len_dev, row_stride, n_rows, hop, hops_dev, hops_stride, gated_dev, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "loudness gate kernel launch");
+    }
+    return GRAIL_OK;
+}
+
 }  // namespace
 
 namespace grail {
 namespace host {
 
-int level_block_gains(grail_ctx *ctx, int mode, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
-                      const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows, const float *item_level_db,
-                      uint32_t n_items, float *gains, uint32_t *n_unleveled)
+uint32_t level_table_rate(const grail_ctx *ctx)
+{
+    uint32_t rate = 0;
+    for (const grail_voice &v : ctx->voices) {
+        const float r = v.sample_rate;
+        if (!(r >= (float)GRAIL_LOUDNESS_RATE_MIN) || !(r <= (float)GRAIL_LOUDNESS_RATE_MAX)) return 0;
+        const uint32_t whole = (uint32_t)r;
+        if ((float)whole != r || (rate && whole != rate)) return 0;
+        rate = whole;
+    }
+    return rate;
+}
+
+int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const float *rows_dev, uint64_t row_stride,
+                      const uint32_t *len_dev, const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows,
+                      const float *item_level_db, uint32_t n_items, float *gains, uint32_t *n_unleveled)
 {
     LevelState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
@@ -118,6 +165,23 @@ int level_block_gains(grail_ctx *ctx, int mode, const float *rows_dev, uint64_t 
     if ((rc = reserve(ctx, &st->d_sumsq, &st->cap_sumsq, n_rows))) return rc;
     if ((rc = reserve(ctx, &st->d_peak, &st->cap_peak, n_rows))) return rc;
     if ((rc = reserve(ctx, &st->d_bad, &st->cap_bad, n_rows))) return rc;
+    if (mode == GRAIL_LEVEL_LOUDNESS) {     // the gated mean squares in place of the totals: 12 bytes a row come back
+        if ((rc = loudness(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, sample_rate, nullptr,
+                           st->d_sumsq, nullptr, 0, st->d_bad)))
+            return rc;
+        std::vector<double> gated(n_rows), level(n_rows);
+        std::vector<uint32_t> bad(n_rows);
+        HIP_TRY(hipMemcpyAsync(gated.data(), st->d_sumsq, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(bad.data(), st->d_bad, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (uint32_t r = 0; r < n_rows; ++r) level[r] = grail_loudness_level(gated[r]);
+        uint32_t unleveled = 0;
+        rc = grail_level_gains(mode, nullptr, nullptr, bad.data(), row_len, level.data(), n_rows, item_rows, item_level_db,
+                               n_items, gains, &unleveled);
+        if (rc) return fail(rc, "grail_batch_mix_leveled: grail_level_gains refused the block");
+        *n_unleveled += unleveled;
+        return GRAIL_OK;
+    }
     if ((rc = totals(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, st->d_sumsq, st->d_peak, st->d_bad)))
         return rc;
     std::vector<double> sumsq(n_rows), active;
@@ -164,6 +228,23 @@ int grail_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_strid
     if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_levels_async: NULL buffer");
     if (!sumsq_dev && !peak_dev && !nonfinite_dev) return GRAIL_OK;
     return totals(ctx, "grail_levels_async", rows_dev, row_stride, len_dev, n_rows, sumsq_dev, peak_dev, nonfinite_dev);
+}
+
+int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                         uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
+                         double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
+{
+    int rc = bind_device(ctx, "grail_loudness_async");
+    if (rc) return rc;
+    if (sample_rate < GRAIL_LOUDNESS_RATE_MIN || sample_rate > GRAIL_LOUDNESS_RATE_MAX)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_loudness_async: sample_rate is outside 2 560 .. 1 048 576");
+    if (hop_sumsq_dev && hops_stride < row_stride / (sample_rate / 10u))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_loudness_async: hops_stride < row_stride / (sample_rate / 10)");
+    if (n_rows == 0) return GRAIL_OK;
+    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_loudness_async: NULL buffer");
+    if (!gated_ms_dev && !hop_sumsq_dev && !nonfinite_dev) return GRAIL_OK;
+    return loudness(ctx, "grail_loudness_async", rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, gated_ms_dev,
+                    hop_sumsq_dev, hops_stride, nonfinite_dev);
 }
 
 int grail_frame_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,

@@ -133,6 +133,10 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
     int rc;
     if ((rc = check_ready(ctx, batch))) return rc;
     const bool leveled = item_level_db != nullptr;
+    uint32_t level_rate = 0;
+    if (leveled && mode == GRAIL_LEVEL_LOUDNESS && !(level_rate = level_table_rate(ctx)))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": GRAIL_LEVEL_LOUDNESS needs voices of one whole-numbered "
+                                                              "sample rate within 2 560 .. 1 048 576");
     std::vector<float> level_gains(leveled ? n_items : 0);
     uint32_t unleveled = 0;
     const uint32_t n = batch->n_utt;
@@ -188,8 +192,8 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
         if (one_piece) {
             rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len);      // = grail_batch_synthesize_async
             if (!rc && leveled) {
-                rc = level_block_gains(ctx, mode, d_rows, stride, d_len, lens.data(), n, item_rows, item_level_db, n_items,
-                                       level_gains.data(), &unleveled);
+                rc = level_block_gains(ctx, mode, level_rate, d_rows, stride, d_len, lens.data(), n, item_rows, item_level_db,
+                                       n_items, level_gains.data(), &unleveled);
                 item_gains = level_gains.data();
             }
             if (!rc)
@@ -214,7 +218,7 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
         }
         if (leveled) {
             sub_gains.assign(sub_rows.size(), 0.0f);
-            rc = level_block_gains(ctx, mode, d_rows, stride, d_len, lens.data() + first, count, sub_rows.data(),
+            rc = level_block_gains(ctx, mode, level_rate, d_rows, stride, d_len, lens.data() + first, count, sub_rows.data(),
                                    sub_levels.data(), (uint32_t)sub_rows.size(), sub_gains.data(), &unleveled);
             if (rc) break;
             for (size_t k = 0; k < of_block[b].size(); ++k) level_gains[of_block[b][k]] = sub_gains[k];
@@ -273,7 +277,7 @@ int grail_batch_mix_leveled(grail_ctx *ctx, const grail_batch *batch, const uint
     }
     int rc = bind(ctx);
     if (rc) return rc;
-    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE)
+    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE && mode != GRAIL_LEVEL_LOUDNESS)
         return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix_leveled: unknown mode");
     static const float none = 0.0f;
     if (n_items && !item_level_db) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix_leveled: item_level_db is NULL");

@@ -75,11 +75,16 @@ EXPORTS = [
     "grail_mix_async", "grail_batch_mix", "grail_mix_place_sequential", "grail_pcm16_frames_async",
     "grail_wav_write_i16_frames",
     "grail_levels_async", "grail_frame_levels_async", "grail_level_gains", "grail_active_level", "grail_batch_mix_leveled",
+    "grail_kweighting", "grail_loudness_async", "grail_gated_mean_square", "grail_loudness_lufs", "grail_loudness_level",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
 LEVEL_FRAME = 4096               # GRAIL_LEVEL_FRAME: the frame length of the row totals
 LEVEL_ACTIVE_FLOOR_DB = 40.0     # GRAIL_LEVEL_ACTIVE_FLOOR_DB
+LEVEL_LOUDNESS = 4               # GRAIL_LEVEL_LOUDNESS: level = loudness_level(gated mean square), targets in LUFS
+LOUDNESS_ABS_GATE = 1.1724653045822981e-07      # GRAIL_LOUDNESS_ABS_GATE: the mean square of -70 LUFS
+LOUDNESS_LEVEL_SCALE = 0.8529037030705663       # GRAIL_LOUDNESS_LEVEL_SCALE: 10^(-0.691 / 10)
+LOUDNESS_RATE_MIN, LOUDNESS_RATE_MAX = 2560, 1048576
 
 
 class GrailError(RuntimeError):
@@ -332,6 +337,14 @@ def load():
     L.grail_active_level.restype = C.c_double
     L.grail_batch_mix_leveled.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp, vp,
                                           vp, C.c_uint32]
+    L.grail_kweighting.argtypes = [C.c_uint32, vp]
+    L.grail_loudness_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64, vp]
+    L.grail_gated_mean_square.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.grail_gated_mean_square.restype = C.c_double
+    L.grail_loudness_lufs.argtypes = [C.c_double]
+    L.grail_loudness_lufs.restype = C.c_double
+    L.grail_loudness_level.argtypes = [C.c_double]
+    L.grail_loudness_level.restype = C.c_double
     _lib = L
     return L
 
@@ -616,6 +629,30 @@ def active_level(frame_sumsq, row_len, frame=LEVEL_FRAME, floor_db=LEVEL_ACTIVE_
     fs = np.ascontiguousarray(frame_sumsq, dtype=np.float64)
     assert len(fs) >= -(-int(row_len) // int(frame))
     return float(load().grail_active_level(fs.ctypes.data, int(row_len), int(frame), float(floor_db)))
+
+
+def kweighting(sample_rate):
+    """grail_kweighting (pure host): the ten K-weighting coefficients for a sample rate, float64[10]: b0 b1 b2 a1 a2 of the
+    shelf, then of the high-pass."""
+    coef = np.full(10, np.nan, dtype=np.float64)
+    _check(load().grail_kweighting(int(sample_rate), coef.ctypes.data))
+    return coef
+
+
+def gated_mean_square(hop_sumsq, hop):
+    """grail_gated_mean_square (pure host): the BS.1770 gate over one row's hop sums; hop = sample_rate // 10."""
+    hs = np.ascontiguousarray(hop_sumsq, dtype=np.float64)
+    return float(load().grail_gated_mean_square(hs.ctypes.data if len(hs) else None, len(hs), int(hop)))
+
+
+def loudness_lufs(gated_ms):
+    """grail_loudness_lufs: -0.691 + 10 log10(gated mean square); -inf for 0."""
+    return float(load().grail_loudness_lufs(float(gated_ms)))
+
+
+def loudness_level(gated_ms):
+    """grail_loudness_level: the level whose 20 log10 is the loudness in LUFS."""
+    return float(load().grail_loudness_level(float(gated_ms)))
 
 
 class Batch:
@@ -938,6 +975,43 @@ class Context:
             for p in d:
                 self.device_free(p)
         return sumsq[:n_rows], peak[:n_rows]
+
+    def loudness_async(self, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef=None, gated_ms_dev=None,
+                       hop_sumsq_dev=None, hops_stride=0, nonfinite_dev=None):
+        """grail_loudness_async: per row the K-weighted gated mean square, the hop sums [n_rows][hops_stride] and the count
+        of non-finite samples, into DEVICE arrays (any may be None), queued on the context's stream.  coef: ten float64 or
+        None = kweighting(sample_rate)."""
+        c = None if coef is None else np.ascontiguousarray(coef, dtype=np.float64)
+        assert c is None or c.shape == (10,)
+        _check(load().grail_loudness_async(self.handle, rows_dev, row_stride, len_dev, n_rows, int(sample_rate), _ptr(c),
+                                           gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev))
+
+    def loudness(self, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef=None, hops=True, fill=None):
+        """loudness_async, waited for and copied back: (gated_ms float64 [n_rows], hop_sumsq float64 [n_rows, row_stride //
+        hop] or None, nonfinite uint32 [n_rows]).  Hops past a row's last hold `fill` (default NaN): the call leaves them
+        unwritten."""
+        hop = int(sample_rate) // 10
+        hs = max(int(row_stride) // hop, 1) if hop else 1
+        gated = np.zeros(max(n_rows, 1), dtype=np.float64)
+        bad = np.zeros(max(n_rows, 1), dtype=np.uint32)
+        hop_sumsq = np.full((max(n_rows, 1), hs), np.nan if fill is None else fill, dtype=np.float64) if hops else None
+        d = [self.device_alloc(gated.nbytes), self.device_alloc(bad.nbytes)]
+        if hops:
+            d.append(self.device_alloc(hop_sumsq.nbytes))
+        try:
+            if hops:
+                self.h2d(d[2], hop_sumsq, hop_sumsq.nbytes)
+            self.loudness_async(rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, d[0], d[2] if hops else None,
+                                hs if hops else 0, d[1])
+            self.d2h(gated, d[0], gated.nbytes)
+            self.d2h(bad, d[1], bad.nbytes)
+            if hops:
+                self.d2h(hop_sumsq, d[2], hop_sumsq.nbytes)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return gated[:n_rows], (hop_sumsq[:n_rows] if hops else None), bad[:n_rows]
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max |x|, non-finite counts) per row, computed on the device."""

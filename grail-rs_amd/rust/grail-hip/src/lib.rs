@@ -367,15 +367,90 @@ impl Gpu {
         gains.truncate(rows.len());
         Ok((host.chunks(stride as usize).map(|t| t[..track_len as usize].to_vec()).collect(), gains, unleveled))
     }
+
+    /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
+    /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
+    /// non-finite samples.  One lane filters one row: many rows fill the device.
+    pub fn loudness(&self, rows: &[Vec<f32>], sample_rate: u32) -> Result<(Vec<f64>, Vec<u32>), Error> {
+        let n = rows.len();
+        let mut gated = vec![0f64; n];
+        let mut bad = vec![0u32; n];
+        if n == 0 {
+            return Ok((gated, bad));
+        }
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 4] = [std::ptr::null_mut(); 4];
+            let sizes = [n * stride * 4, n * 4, n * 8, n * 4];
+            let mut r = Ok(());
+            for k in 0..4 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[1], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_loudness_async(self.ctx, d[0] as *const f32, stride as u64, d[1] as *const u32, n as u32,
+                                                    sample_rate, std::ptr::null(), d[2] as *mut f64, std::ptr::null_mut(), 0,
+                                                    d[3] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, gated.as_mut_ptr() as *mut std::ffi::c_void, d[2], n * 8));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((gated, bad))
+    }
 }
 
-/// What "level" means to [`Gpu::mix_leveled`] (GRAIL_LEVEL_PEAK / _RMS / _ACTIVE).
+/// The ten K-weighting coefficients for a sample rate (`grail_kweighting`; pure host, no GPU).
+pub fn kweighting(sample_rate: u32) -> Result<[f64; 10], Error> {
+    let mut coef = [0f64; 10];
+    check(unsafe { sys::grail_kweighting(sample_rate, coef.as_mut_ptr()) })?;
+    Ok(coef)
+}
+
+/// The BS.1770 gate over one row's hop sums, `hop` = sample rate / 10 (`grail_gated_mean_square`; pure host).
+pub fn gated_mean_square(hop_sumsq: &[f64], hop: u32) -> f64 {
+    unsafe { sys::grail_gated_mean_square(hop_sumsq.as_ptr(), hop_sumsq.len() as u32, hop) }
+}
+
+/// Loudness in LUFS of a gated mean square (`grail_loudness_lufs`): negative infinity for 0.
+pub fn loudness_lufs(gated_ms: f64) -> f64 {
+    unsafe { sys::grail_loudness_lufs(gated_ms) }
+}
+
+/// The level whose 20 log10 is the loudness in LUFS (`grail_loudness_level`).
+pub fn loudness_level(gated_ms: f64) -> f64 {
+    unsafe { sys::grail_loudness_level(gated_ms) }
+}
+
+/// What "level" means to [`Gpu::mix_leveled`] (GRAIL_LEVEL_PEAK / _RMS / _ACTIVE / _LOUDNESS: targets then in LUFS).
 #[derive(Copy, Clone, Debug, PartialEq, Eq)]
 #[repr(i32)]
 pub enum LevelMode {
     Peak = 0,
     Rms = 1,
     Active = 2,
+    Loudness = 4,
 }
 
 /// The "active" level of one row from its frames' sums of squares (`grail_active_level`; pure host, no GPU).

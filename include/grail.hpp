@@ -86,6 +86,13 @@ struct Levels {
     std::vector<uint32_t> nonfinite;   // NaN and Inf samples
 };
 
+// What Gpu::loudness measures, one entry per row (grail_loudness_async)
+struct Loudness {
+    std::vector<double> gated_ms;      // K-weighted gated mean square (BS.1770-4); 0 for a row shorter than 400 ms
+    std::vector<uint32_t> nonfinite;   // NaN and Inf samples (they enter the filter as 0)
+    double lufs(size_t row) const { return grail_loudness_lufs(gated_ms[row]); }
+};
+
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
                     std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
@@ -245,7 +252,8 @@ public:
     }
 
     // Gpu::mix with a level instead of a gain: placement i's utterance is brought to level_db[i] decibels (0 dB = level
-    // 1.0; mode GRAIL_LEVEL_RMS, GRAIL_LEVEL_PEAK or GRAIL_LEVEL_ACTIVE) and Placement::gain is not read.  The rows are
+    // 1.0; mode GRAIL_LEVEL_RMS, GRAIL_LEVEL_PEAK or GRAIL_LEVEL_ACTIVE; with GRAIL_LEVEL_LOUDNESS level_db[i] is a target
+    // in LUFS and an utterance shorter than 400 ms cannot be leveled) and Placement::gain is not read.  The rows are
     // measured on the device between rendering and mixing (grail_batch_mix_leveled).  gains_used, unleveled: the gains the
     // mix applied, and how many placements got gain 0 because their utterance is empty, silent or holds a non-finite sample.
     std::vector<std::vector<float>> mix_leveled(const std::vector<Utterance> &utts, const std::vector<Placement> &placements,
@@ -317,6 +325,38 @@ public:
         if (!rc) rc = grail_memcpy_d2h(ctx_, out.peak.data(), d_peak, (size_t)n * 4);
         if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
         for (void *p : {d_rows, d_len, d_sumsq, d_peak, d_bad})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
+    // K-weighted gated loudness of rows of samples at sample_rate, measured on the device (grail_loudness_async; the
+    // contract is the header's section "levels, continued").  One lane filters one row: many rows fill the device.
+    Loudness loudness(const std::vector<std::vector<float>> &rows, uint32_t sample_rate) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64;
+        Loudness out;
+        out.gated_ms.resize(n);
+        out.nonfinite.resize(n);
+        if (!n) return out;
+        std::vector<uint32_t> lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        void *d_rows = nullptr, *d_len = nullptr, *d_ms = nullptr, *d_bad = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 8, &d_ms);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_bad);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc) rc = grail_loudness_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, sample_rate, nullptr,
+                                           (double *)d_ms, nullptr, 0, (uint32_t *)d_bad);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.gated_ms.data(), d_ms, (size_t)n * 8);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
+        for (void *p : {d_rows, d_len, d_ms, d_bad})
             if (p) grail_device_free(ctx_, p);
         check(rc);
         return out;
