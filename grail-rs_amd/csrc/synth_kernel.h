@@ -107,6 +107,15 @@
                                   // config 2, 24: 7.49, 64: 7.41; a run ends at the next event anyway, ~40 tiles)
 #endif
 
+// the one-lane four-formant exact kernels render runs of consecutive calm tiles behind one tile head (CALM_RUNS in the
+// tile loop): 1 on, 0 every tile decides for itself
+#ifndef GRAIL_CALM_RUNS
+#define GRAIL_CALM_RUNS 1
+#endif
+#ifndef CALM_RUN_MAX_TILES
+#define CALM_RUN_MAX_TILES PIPE_MAX_TILES
+#endif
+
 // GRAIL_FAST_PROF (debug builds only, `make EXTRA=-DGRAIL_FAST_PROF`): cycle and event counters of the tolerance-mode
 // tile loop, summed over the waves of a launch into 32 u64 words behind A.truncated[8] (tools/fast_prof.py reads them)
 #ifdef GRAIL_FAST_PROF

@@ -29,6 +29,21 @@
         // The pipelined workgroups take it too: their four waves render the run redundantly, as they do the single steps)
         constexpr bool MIXED_RUNS = GRAIL_MIXED_RUNS && !FAST && (!PIPE || GRAIL_MIXED_RUNS_PIPE) && GRAIL_SCALAR_PACK && (L > 1 || GRAIL_MIXED_RUNS_L1);
         bool mixed_shared = false, mixed_stale = false;
+        // CALM_RUNS (one lane per utterance, four formants, one-shot): what the head of a calm tile decides — calm or not,
+        // one smoothness for all formants, the pair's constants — can only change at an event, and between two events lie
+        // some 80 calm tiles.  The head therefore finds, as the pipelined workgroups do, how many tiles in a row are calm
+        // and renders them all in one go: per tile only the noise redraw, the row counts and the flush.  A lone wave pays
+        // every ballot, every look-up of the skip-ahead constants and every branch of the head in full: 1 260 cycles a
+        // tile, 240 with runs (profiles/r10_exact_tile_split.txt).
+        // (Not the eight-formant one-lane kernels, which hold 428 - 511 registers and have lost to every extra path, and not
+        // the resumable ones: both compile to what they were.  Not the kernel for blend lengths that are not powers of two
+        // either: with the runs the compiler lays its calm loop out with three times as many 8-byte instructions across
+        // 16-byte boundaries, which costs a lone wave more than the head gives back — 42.5 against 41.3 ms, same-box A/B.
+        // The lanes still stage their samples: storing them to their own rows from registers takes the flush away but
+        // needs a second copy of the calm loop, and no form of it tried kept both copies at the pace of the one —
+        // NOTEBOOK "Runs of calm tiles".)
+        constexpr bool CALM_RUNS = GRAIL_CALM_RUNS && GRAIL_SCALAR_PACK && L == 1 && NFA == 4 && !FAST && !PIPE && !STREAM && !SPLIT && !ANYBL;
+        bool run_full = false;                     // CALM_RUNS: every row of the wave takes whole tiles as 16-byte stores
         uint32_t mixed_seed = 0u, mixed_sk = 0u;
         float mixed_noise = 0.0f;
         if constexpr (!FAST) PROF_ADD(8);
@@ -65,14 +80,17 @@
                             mixed_noise = (__uint_as_float((mixed_sk >> 9) | 0x3F800000u) - 1.5f) * 2.0f;
                         }
                     }
-                    if constexpr (PIPE) {
+                    if constexpr (PIPE || CALM_RUNS) {
                         // how many calm tiles in a row (every wave of the workgroup finds the same number): the
                         // pipeline then runs through them without draining.  The margins of the single tile
                         // for N = k T steps: each step lowers the bound on the clock by at most 1.01 dt.
                         pipe_tiles = 1;
-                        if (calm_tile) {
+                        // (CALM_RUNS: rows of i16 samples and rows without 16-byte alignment keep a head per tile and with it
+                        // the main loop's flushes written for them; inside a run they would take the general one — i16 rows
+                        // 45.2 instead of 41.7 ms)
+                        if (calm_tile && (PIPE || (vec_ok && !A.out_pcm16))) {
 #pragma unroll 1
-                            for (int k = 2; k <= PIPE_MAX_TILES; ++k) {
+                            for (int k = 2; k <= (PIPE ? PIPE_MAX_TILES : CALM_RUN_MAX_TILES); ++k) {
                                 const float nsteps = (float)(k * T);
                                 const bool ok = (clk > (nsteps * 1.0125f + 8.0f) * dt) &
                                                 (jphase + (nsteps + 1.0f) * jinc < 0.999f) &
@@ -81,6 +99,11 @@
                                 pipe_tiles = k;
                             }
                         }
+                    }
+                    if constexpr (CALM_RUNS) {
+                        // nobody starts or stops rendering inside a run (both are events), so which flush the run's tiles
+                        // take is decided here: with idle lanes they go through flush_rows
+                        if (pipe_tiles > 1) run_full = __builtin_amdgcn_ballot_w64(idle | (n_out != base)) == 0;
                     }
                 }
             }
@@ -159,6 +182,31 @@
                             float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, noise_of_lane), tc + 1));
                         scalar_packed_steps(nlive_tag, su_tag, tc, nz0, nz1);
                     }
+                }
+            };
+            // CALM_RUNS: a tile inside a run in which every row of the wave received all T samples, as 16-byte stores (the
+            // main loop's full-tile flush below: the LDS reads of all rows in flight together, the stores back to back)
+            auto flush_full_tile = [&](const uint32_t base_) __attribute__((always_inline)) {
+                if constexpr (CALM_RUNS) {
+                    constexpr int ROW_LANES = T / 4;
+                    constexpr int ROWS_PER_IT = 64 / ROW_LANES;
+                    const int rl = lane % ROW_LANES;
+                    const int rr = lane / ROW_LANES;
+                    wave_lds_sync();
+                    float4 v[S / ROWS_PER_IT];
+#pragma unroll
+                    for (int i = 0; i < S / ROWS_PER_IT; ++i) {
+                        const int r = i * ROWS_PER_IT + rr;
+                        const int t0 = rl * 4;
+                        v[i] = make_float4(stage[(t0 + 0) * SP + r], stage[(t0 + 1) * SP + r], stage[(t0 + 2) * SP + r],
+                                           stage[(t0 + 3) * SP + r]);
+                    }
+#pragma unroll
+                    for (int i = 0; i < S / ROWS_PER_IT; ++i) {
+                        const uint64_t row = A.perm ? rowid[i * ROWS_PER_IT + rr] : u0 + i * ROWS_PER_IT + rr;
+                        *reinterpret_cast<float4 *>(A.out + row * A.out_stride + base_ + rl * 4) = v[i];
+                    }
+                    wave_lds_sync();
                 }
             };
             auto quiet_run = [&](auto nlive_tag, auto su_tag) __attribute__((always_inline)) {
@@ -261,6 +309,33 @@
                     } else if constexpr (GRAIL_SCALAR_PACK && STEPS_PER_TRIP == 2 && L >= 4 && T % 8 == 0) {
 #pragma unroll 1
                         for (int tc = 0; tc < T; tc += 8) scalar_packed_block(nlive_tag, su_tag, tc, noise_of_lane);
+                    } else if constexpr (GRAIL_SCALAR_PACK && STEPS_PER_TRIP == 2 && CALM_RUNS) {
+                        // pipe_tiles calm tiles behind this one head.  The skip-ahead constants stay in registers for the
+                        // run (not across the kernel); between two tiles: what the main loop does after a calm tile, and
+                        // the tile's flush — the last tile of the run leaves both to the main loop.
+                        const uint32_t skip_mul = LCG_SKIP.mul[ahead], skip_add = LCG_SKIP.add[ahead];
+                        float noise_run = noise_of_lane;
+#pragma unroll 1
+                        for (int left = pipe_tiles;;) {
+#pragma unroll 1
+                            for (int tc = 0; tc < T; tc += 2) {
+                                const float nz0 = __builtin_bit_cast(
+                                    float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, noise_run), tc));
+                                const float nz1 = __builtin_bit_cast(
+                                    float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, noise_run), tc + 1));
+                                scalar_packed_steps(nlive_tag, su_tag, tc, nz0, nz1);
+                            }
+                            if (--left == 0) break;
+                            PROF_ADD(2); PROF_CNT(15, 1); PROF_CNT(16, decltype(su_tag)::value ? 1 : 0);
+                            n_out += idle ? 0u : (uint32_t)T;
+                            noise_seed = (uint32_t)__builtin_amdgcn_readlane((int)sk, T - 1);
+                            sk = noise_seed * skip_mul + skip_add;
+                            noise_run = (__uint_as_float((sk >> 9) | 0x3F800000u) - 1.5f) * 2.0f;
+                            if (run_full) flush_full_tile(base);
+                            else flush_rows(base, n_out > base ? n_out - base : 0u);
+                            PROF_ADD(22);
+                            base += T;
+                        }
                     } else if constexpr (GRAIL_SCALAR_PACK && STEPS_PER_TRIP == 2) {
 #pragma unroll 1
                         for (int tc = 0; tc < T; tc += 2) {
@@ -390,6 +465,7 @@
             }
         }
 
+        if constexpr (!FAST) PROF_ADD(21);
         // ---- flush the staged tile: row `slot` holds samples [base, base+T)
         // PIPE: the rendering wave parked the tile; all four waves (identical state, same decisions) flush a
         // share of its rows each instead of waiting for wave 0 to do it alone, between two workgroup barriers
@@ -440,6 +516,7 @@
                     }
                 }
                 wave_lds_sync();
+                if constexpr (!FAST) PROF_ADD(22);
                 if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
                 continue;
             }
@@ -476,10 +553,12 @@
                                                     rl * 4) = v[i];
                 }
                 wave_lds_sync();
+                if constexpr (!FAST) PROF_ADD(22);
                 if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
                 continue;
             }
         }
         flush_rows(base, mine);
+        if constexpr (!FAST) PROF_ADD(22);
         if (__builtin_amdgcn_ballot_w64(!done) == 0) break;
     }

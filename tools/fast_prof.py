@@ -49,7 +49,7 @@ CNT = {10: "plain pairs", 11: "slow samples", 12: "slope-refresh executions (wav
 
 if exact:
     NAMES = {0: "total", 2: "calm tiles", 3: "runs of tiles with an event (pairs + single steps)", 7: "general steps",
-             8: "flush + between tiles", 9: "tile head"}
+             8: "top of the tile loop", 9: "tile head", 21: "leaving the tile's steps", 22: "flush"}
     CNT = {15: "calm tiles", 16: "  of them: one smoothness for all formants", 17: "  of them: upper half silent",
            20: "runs in tiles with an event", 18: "  of them: one smoothness", 19: "  of them: upper half silent",
            10: "packed pairs in those tiles", 12: "single quiet steps in those tiles", 11: "general steps"}
@@ -77,6 +77,12 @@ for k, name in NAMES.items():
         print(f"  {name:32s} {d[k] / waves:12.0f} cycles  {100.0 * d[k] / max(d[0], 1):5.1f} %")
 for k, name in CNT.items():
     print(f"  {name:44s} {d[k] / waves:10.1f} per wave")
+if exact and d[15] + d[20]:
+    # head = everything between the end of one tile's flush and the first sample of the next tile; every bucket's
+    # closing clock64() (an s_memtime and its wait) is part of the bucket
+    tiles = d[15] + d[20]
+    print(f"  per tile ({tiles / waves:.0f} tiles per wave): head {(d[8] + d[9] + d[21]) / tiles:7.0f}  flush {d[22] / tiles:7.0f}  "
+          f"calm loop {d[2] / max(d[15], 1):7.0f}  tile with an event {(d[3] + d[7]) / max(d[20], 1):7.0f} cycles")
 for a, b, what in (((2, 15, "calm tile"), (7, 11, "general step")) if exact else
                    ((2, 10, "plain pair (incl. refreshes)"), (5, 13, "new-beginning execution"), (7, 11, "slow sample: chain"), (6, 11, "slow sample: formants"))):
     if d[b]:
