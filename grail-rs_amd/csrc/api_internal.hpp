@@ -1,6 +1,7 @@
 // api_internal.hpp — what the host translation units of the library share (internal; host code only: the kernel
-// units include kernels.h, never this).  grail_api.cpp: contexts, options, batches, voices; voice_analysis.cpp: what a
-// voice table qualifies for; launch_plan.cpp: kernel families, cost model, block planner; synthesize.cpp: launches;
+// units include kernels.h, never this).  grail_api.cpp: contexts, batches, voices; options.cpp: the option table,
+// grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
+// families, cost model, block planner; synthesize.cpp: launches;
 // streams.cpp: resumable and live streams; host_output.cpp: the one-call forms with a host destination; comm.cpp: RCCL.
 #pragma once
 
@@ -38,6 +39,75 @@ constexpr size_t TRUNCATED_WORDS = 8 + 64;
 constexpr size_t TRUNCATED_WORDS = 4;
 #endif
 
+// What grail_set_option writes (options.cpp holds the table of names and checks), with every default.  All int64, as
+// the ABI passes them.
+struct Options {
+    int64_t fast_option = 0;          // "arithmetic": 0 exact (bit-identical), 1 fast (stated tolerance: the tier the voices'
+                                      // sharpness allows), 2 fast with the reference's own coefficients (MID) whatever the voices
+    int64_t fast_limit = (int64_t)GRAIL_FAST_SHARPNESS_LIMIT;   // "fast_sharpness_limit": fast kernels up to this
+    int64_t mid_option = 1;           // "fast_exact_coefficients": sharper voices get the second tolerance tier (MID)
+    int64_t mid_limit = (int64_t)GRAIL_FAST_SHARPNESS_LIMIT_EXACT_COEFFICIENTS;   // ... up to this sharpness
+    int64_t lanes_option = 0;         // 0 = auto
+    int64_t skip_silent_option = 1;   // skip band-pass filters of provably silent formants
+    int64_t pipeline_option = 1;      // small qualifying batches: producer/consumer workgroups
+    int64_t pipe_round32 = 1;         // ... with rounds of 32 samples while one workgroup per CU suffices (8.20 -> 7.86 ms for config 2)
+    int64_t pipe_spread = 1;          // pipelined workgroups on rows that differ in length: few utterances per workgroup (pipe_fill_for)
+    int64_t pipe4_max_groups = -1;    // four-formant pipelined workgroups (16 utterances each): up to so many (-1: two per CU)
+    int64_t pipe8_max_groups = -1;    // eight-formant pipelined workgroups: up to so many (-1: two per CU)
+    int64_t scan_option = 1;          // fast arithmetic: small batches go to the time-parallel scan kernel
+    int64_t scan_max_utts = -1;       // ... up to this many utterances (x 4/7 with eight live formants; -1: 34 per CU = 8704)
+    int64_t scan_split_max = -1;      // ... and up to this many with the carrier phase on a wave of its own (-1: 6 per CU = 1536)
+    int64_t scan_debug = 0;           // development builds only (-DGRAIL_SCAN_DEBUG): see scan_kernels.hip
+    int64_t split_option = 1;         // fast arithmetic: mid-size batches split every utterance's time axis over lanes
+    int64_t split_chunks = 0;         // ... into this many chunks (0: as many as fill the machine)
+    int64_t split_span = 0;           // ... laid out over this many samples (0: the batch's longest utterance)
+    int64_t split_ff_permille = 165;  // ... cost of a fast-forwarded sample against a rendered one
+    int64_t split_min_utts = -1;      // ... -1: the cost model picks between the scan kernel, the time-split kernels and the lane
+                                      // kernels (family_cost; 2 s utterances: 1 024 of them 2.00 (scan) against 3.13 ms (split),
+                                      // 1 536: 3.22 / 3.14, 2 048: 3.33 / 3.13, profiles/r03_small_batch.txt); >= 0: batches smaller
+                                      // than this (x 5/6 with eight live formants) stay with the scan kernel, whatever their length
+    int64_t composite_option = 1;     // a batch may be cut into blocks with a kernel family each (plan_blocks)
+    int64_t row_groups_option = 1;    // rows the lean families cannot take are planned apart: 1 where the cost model says so, 2 always, 0 never
+    int64_t ragged_option = 1;        // length-sorted batches: lane mappings weighed by the rows' lengths (ragged_plan)
+    int64_t two_waves_option = 1;     // tolerance-mode lane kernels on 2 / 4 / 8 lanes: two waves per SIMD where a launch has more waves than SIMDs
+    int64_t packed_option = 1;        // launches of more one-wave-per-SIMD workgroups than the device has room for: launch slots in packed order
+    int64_t sort_option = 1;          // ragged batches: fill launch slots in order of decreasing length
+};
+
+// what a voice of the table qualifies for (a batch is judged by the voices IT names: used_voices)
+struct VoiceInfo {
+    bool upper_silent = false, live4_ok = false, scan_ok = false, split_ok = false;
+    uint32_t warmup = 0;
+};
+
+// What install_voices derives from the voice table; the defaults are "no voice table set".  The table-wide flags are what
+// a context without per-voice records (grail_plan_blocks) goes by.
+struct VoiceFacts {
+    std::vector<VoiceInfo> voice_info;
+    bool voices_upper_silent = false; // every voice: formants 5-8 have amplitude +0 in every phoneme
+    bool voices_live4_ok = false;     // ... and parameters that keep their output at exactly +0 (live4_ok)
+    bool voices_scan_ok = false;      // every formant of every voice inside the safe window (scan_voice_ok)
+    bool voices_split_ok = false;     // every voice has a warm-up length (voice_warmup): time-split fast kernels
+    uint32_t max_warmup = 0;          // ... the longest of them
+    float max_rate = 0.0f;            // highest sample rate of the table
+    float max_dt = 0.0f;              // largest 1/sample_rate of the table
+    float max_pitch_jitter = 0.0f;    // largest |jitter_delta_frequency| of the table
+    double voices_sharpness = INFINITY;   // the largest predicted fast-mode deviation of the table, units of 2^-23
+    std::vector<double> voice_sharpness;  // ... per voice (a batch is judged by the voices it uses)
+};
+
+// What the read-only options tell of the last synthesis launch (its largest block) and of the kernels synced so far
+struct LaunchStats {
+    std::string last_kernel = "none"; // instantiation of the last synthesis launch
+    int last_formants = 8, last_lanes = 0, last_pipe = 0;
+    int last_split = 0;               // chunks of the last launch (0: not time-split)
+    int last_fast = 0;                // the last launch ran tolerance arithmetic in some block
+    int last_blocks = 0;              // kernel launches the last synthesis call was cut into
+    int last_packed = 0;              // ... blocks of it launched in packed order
+    uint64_t slow_steps = 0;          // of the kernels synced so far
+    uint64_t fast_tiles = 0, general_steps = 0;
+};
+
 struct grail_ctx {
     int device = 0;
     int cus = 256;                    // compute units the launch policy plans for (hipDeviceProp_t::multiProcessorCount;
@@ -46,68 +116,16 @@ struct grail_ctx {
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool have_timing = false;
+    Options opt;
+    uint64_t options_epoch = 0;       // bumped by every grail_set_option (a batch caches its launch plan against both)
     std::vector<grail_voice> voices;  // host copy of the table
     grail::DevVoice *d_voices = nullptr;
     float *d_voice_elems = nullptr;   // [n_voices * NUM_VOICED][49]
-    // what each voice of the table qualifies for (a batch is judged by the voices IT names: used_voices); the table-wide
-    // flags below are what a context without per-voice records (grail_plan_blocks) goes by
-    struct VoiceInfo {
-        bool upper_silent = false, live4_ok = false, scan_ok = false, split_ok = false;
-        uint32_t warmup = 0;
-    };
-    std::vector<VoiceInfo> voice_info;
-    bool voices_upper_silent = false; // every voice: formants 5-8 have amplitude +0 in every phoneme
-    bool voices_live4_ok = false;     // ... and parameters that keep their output at exactly +0 (live4_ok)
-    bool voices_scan_ok = false;      // every formant of every voice inside the safe window (scan_voice_ok)
-    int scan_debug = 0;
-    int sort_option = 1;              // ragged batches: fill launch slots in order of decreasing length
-    int64_t pipe8_max_groups = -1;    // eight-formant pipelined workgroups: up to so many (-1: two per CU)
-    int64_t pipe4_max_groups = -1;    // four-formant pipelined workgroups (16 utterances each): up to so many (-1: two per CU)
-    int scan_option = 1;              // fast arithmetic: small batches go to the time-parallel scan kernel
-    int64_t scan_max_utts = -1;       // ... up to this many utterances (x 4/7 with eight live formants; -1: 34 per CU = 8704)
-    int64_t scan_split_max = -1;      // ... and up to this many with the carrier phase on a wave of its own (-1: 6 per CU = 1536)
-    int ragged_option = 1;            // length-sorted batches: lane mappings weighed by the rows' lengths (ragged_plan)
-    int pipe_spread = 1;              // pipelined workgroups on rows that differ in length: few utterances per workgroup (pipe_fill_for)
-    int two_waves_option = 1;         // tolerance-mode lane kernels on 2 / 4 / 8 lanes: two waves per SIMD where a launch has more waves than SIMDs
-    int packed_option = 1;            // launches of more one-wave-per-SIMD workgroups than the device has room for: launch slots in packed order
-    int composite_option = 1;         // a batch may be cut into blocks with a kernel family each (plan_blocks)
-    int row_groups_option = 1;        // rows the lean families cannot take are planned apart: 1 where the cost model says so, 2 always, 0 never
-    double voices_sharpness = INFINITY;   // the largest predicted fast-mode deviation of the table, units of 2^-23
-    std::vector<double> voice_sharpness;  // ... per voice (a batch is judged by the voices it uses)
-    int64_t fast_limit = (int64_t)GRAIL_FAST_SHARPNESS_LIMIT;   // "fast_sharpness_limit": fast kernels up to this
-    int mid_option = 1;               // "fast_exact_coefficients": sharper voices get the second tolerance tier (MID)
-    int64_t mid_limit = (int64_t)GRAIL_FAST_SHARPNESS_LIMIT_EXACT_COEFFICIENTS;   // ... up to this sharpness
-    bool voices_split_ok = false;     // every voice has a warm-up length (voice_warmup): time-split fast kernels
-    uint32_t max_warmup = 0;          // ... the longest of them
-    float max_rate = 0.0f;            // highest sample rate of the table
-    int split_option = 1;             // fast arithmetic: mid-size batches split every utterance's time axis over lanes
-    int64_t split_chunks = 0;         // ... into this many chunks (0: as many as fill the machine)
-    int64_t split_span = 0;           // ... laid out over this many samples (0: the batch's longest utterance)
-    int64_t split_ff_permille = 165;  // ... cost of a fast-forwarded sample against a rendered one
-    int64_t split_min_utts = -1;      // ... -1: the cost model picks between the scan kernel, the time-split kernels and the lane
-                                      // kernels (family_cost; 2 s utterances: 1 024 of them 2.00 (scan) against 3.13 ms (split),
-                                      // 1 536: 3.22 / 3.14, 2 048: 3.33 / 3.13, profiles/r03_small_batch.txt); >= 0: batches smaller
-                                      // than this (x 5/6 with eight live formants) stay with the scan kernel, whatever their length
-    int last_split = 0;               // chunks of the last launch (statistics; 0: not time-split)
-    int last_fast = 0;                // the last launch ran tolerance arithmetic in some block
-    int last_blocks = 0;              // kernel launches the last synthesis call was cut into
-    float max_dt = 0.0f;              // largest 1/sample_rate of the table
-    float max_pitch_jitter = 0.0f;    // largest |jitter_delta_frequency| of the table
-    int last_formants = 8, last_lanes = 0, last_pipe = 0;   // what the last synthesis launch used (statistics)
-    int last_packed = 0;              // ... blocks of it launched in packed order
-    uint32_t *d_truncated = nullptr;  // [0] truncation flag, [1] slow-path wave-steps, [2] fast wave-tiles, [3] general wave-steps
-    uint64_t slow_steps = 0;          // of the kernels synced so far
-    uint64_t fast_tiles = 0, general_steps = 0;
-    uint32_t seen_counters[4] = {0, 0, 0, 0};   // d_truncated[1..3] as last read: the device counters only ever grow
-    int lanes_option = 0;             // 0 = auto
-    int skip_silent_option = 1;       // skip band-pass filters of provably silent formants
-    int pipeline_option = 1;          // small qualifying batches: producer/consumer workgroups
-    int pipe_round32 = 1;             // ... with rounds of 32 samples while one workgroup per CU suffices (8.20 -> 7.86 ms for config 2)
+    VoiceFacts facts;
     uint64_t voices_epoch = 0;        // set by every install_voices: unique in the process, not per context
-    uint64_t options_epoch = 0;       // bumped by every grail_set_option (a batch caches its launch plan against both)
-    int fast_option = 0;              // "arithmetic": 0 exact (bit-identical), 1 fast (stated tolerance: the tier the voices'
-                                      // sharpness allows), 2 fast with the reference's own coefficients (MID) whatever the voices
-    std::string last_kernel = "none"; // instantiation of the last synthesis launch
+    LaunchStats stats;
+    uint32_t *d_truncated = nullptr;  // [0] truncation flag, [1] slow-path wave-steps, [2] fast wave-tiles, [3] general wave-steps
+    uint32_t seen_counters[4] = {0, 0, 0, 0};   // d_truncated[1..3] as last read: the device counters only ever grow
     ncclComm_t comm = nullptr;
     uint32_t comm_rank = 0, comm_world = 1;
     void *host_pipe = nullptr;        // HostPipe: streams, events and buffers of the host-output path
@@ -227,10 +245,10 @@ std::string &last_error();
 // CPX, 32 CUs — plans for 32, not 256); "assume_compute_units" overrides it for tests.
 inline uint64_t ctx_simds(const grail_ctx *ctx) { return 4ull * (uint64_t)ctx->cus; }
 inline uint64_t ctx_lanes(const grail_ctx *ctx) { return 256ull * (uint64_t)ctx->cus; }
-inline int64_t pipe4_groups(const grail_ctx *ctx) { return ctx->pipe4_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->pipe4_max_groups; }
-inline int64_t pipe8_groups(const grail_ctx *ctx) { return ctx->pipe8_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->pipe8_max_groups; }
-inline int64_t scan_max_utts(const grail_ctx *ctx) { return ctx->scan_max_utts < 0 ? 34 * (int64_t)ctx->cus : ctx->scan_max_utts; }
-inline int64_t scan_split_max(const grail_ctx *ctx) { return ctx->scan_split_max < 0 ? 6 * (int64_t)ctx->cus : ctx->scan_split_max; }
+inline int64_t pipe4_groups(const grail_ctx *ctx) { return ctx->opt.pipe4_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe4_max_groups; }
+inline int64_t pipe8_groups(const grail_ctx *ctx) { return ctx->opt.pipe8_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe8_max_groups; }
+inline int64_t scan_max_utts(const grail_ctx *ctx) { return ctx->opt.scan_max_utts < 0 ? 34 * (int64_t)ctx->cus : ctx->opt.scan_max_utts; }
+inline int64_t scan_split_max(const grail_ctx *ctx) { return ctx->opt.scan_split_max < 0 ? 6 * (int64_t)ctx->cus : ctx->opt.scan_split_max; }
 
 int bind(grail_ctx *ctx);
 

@@ -1,6 +1,6 @@
-// grail_api.cpp — the C ABI (include/grail_hip.h) over the HIP kernels: contexts, voice tables, options, HBM-resident
-// batches, synchronisation and the device utilities.  Host orchestration only (with voice_analysis.cpp, launch_plan.cpp,
-// synthesize.cpp, streams.cpp, host_output.cpp, comm.cpp): no arithmetic of the hot path happens here and
+// grail_api.cpp — the C ABI (include/grail_hip.h) over the HIP kernels: contexts, voice tables, HBM-resident
+// batches, synchronisation and the device utilities.  Host orchestration only (with options.cpp, voice_analysis.cpp,
+// launch_plan.cpp, synthesize.cpp, streams.cpp, host_output.cpp, comm.cpp): no arithmetic of the hot path happens here and
 // there is no CPU fallback: without a HIP device every compute call fails.
 #include "api_internal.hpp"
 
@@ -143,14 +143,14 @@ int upload_len_bound(grail_ctx *ctx, grail_batch *b, const std::vector<RowStats>
 // pitch jitter; a batch uploaded before any table, or rendered with another one, is planned as one.)
 int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowStats> &rows, uint32_t n_utt)
 {
-    if (n_utt < 2 || !ctx->sort_option) return GRAIL_OK;
+    if (n_utt < 2 || !ctx->opt.sort_option) return GRAIL_OK;
     std::vector<uint8_t> outlier(n_utt, 0);
     uint32_t n_out = 0;
     if (!ctx->voices.empty()) {
         for (uint32_t u = 0; u < n_utt; ++u) {
             const RowStats &r = rows[u];
-            const bool lean = r.plain && r.min_length >= 2.0f * ctx->max_dt &&
-                              r.min_pitch * 0.999f - 1.002f * ctx->max_pitch_jitter >= 9.5367431640625e-07f;
+            const bool lean = r.plain && r.min_length >= 2.0f * ctx->facts.max_dt &&
+                              r.min_pitch * 0.999f - 1.002f * ctx->facts.max_pitch_jitter >= 9.5367431640625e-07f;
             outlier[u] = lean ? 0 : 1;
             n_out += outlier[u];
         }
@@ -211,7 +211,7 @@ int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowSta
         t.granule_kinks.assign(n_gran, 0u);
         for (uint32_t s = 0; s < n_rows; ++s) {
             const RowStats &r = rows[perm[s]];
-            const float samples = key(perm[s]) * ctx->max_rate;
+            const float samples = key(perm[s]) * ctx->facts.max_rate;
             if (samples > t.granule_samples[s / 8]) t.granule_samples[s / 8] = samples;
             t.granule_segs[s / 8] += r.segs;
             t.granule_kinks[s / 8] += r.kinks;
@@ -291,34 +291,15 @@ int install_voices(grail_ctx *ctx, const grail_voice *voices, uint32_t n_voices)
     HIP_TRY(hipMemcpyAsync(ctx->d_voice_elems, elems.data(), elems.size() * sizeof(float),
                            hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // dv / elems are locals
-    ctx->voices.assign(voices, voices + n_voices);
-    ctx->voices_epoch = ++g_epoch;
-    bool silent = true;
-    for (uint32_t v = 0; v < n_voices; ++v)
-        for (int p = 0; p < NUM_VOICED; ++p)
-            for (int i = NF / 2; i < NF; ++i) {
-                uint32_t bits;
-                std::memcpy(&bits, &voices[v].phonemes[p].formant_amp[i], sizeof bits);
-                silent = silent && bits == 0u;
-            }
-    ctx->voices_upper_silent = silent;
-    ctx->voices_live4_ok = true;
-    ctx->voices_scan_ok = true;
-    for (uint32_t v = 0; v < n_voices; ++v) ctx->voices_scan_ok = ctx->voices_scan_ok && scan_voice_ok(voices[v]);
-    ctx->max_dt = 0.0f;
-    ctx->max_pitch_jitter = 0.0f;
-    ctx->max_rate = 0.0f;
-    ctx->max_warmup = 0;
-    ctx->voices_split_ok = true;
-    ctx->voices_sharpness = 0.0;
-    ctx->voice_sharpness.assign(n_voices, 0.0);
+    // what the table qualifies for, voice by voice and folded over the table; assigned whole, so that no fact of the
+    // table before survives
+    VoiceFacts facts;
+    facts.voices_upper_silent = facts.voices_live4_ok = facts.voices_scan_ok = facts.voices_split_ok = true;
+    facts.voices_sharpness = 0.0;
+    facts.voice_info.resize(n_voices);
+    facts.voice_sharpness.resize(n_voices);
     for (uint32_t v = 0; v < n_voices; ++v) {
-        ctx->voice_sharpness[v] = elems_sharpness(voices[v].phonemes, NUM_VOICED);
-        ctx->voices_sharpness = std::fmax(ctx->voices_sharpness, ctx->voice_sharpness[v]);
-    }
-    ctx->voice_info.assign(n_voices, grail_ctx::VoiceInfo());
-    for (uint32_t v = 0; v < n_voices; ++v) {
-        grail_ctx::VoiceInfo &vi = ctx->voice_info[v];
+        VoiceInfo &vi = facts.voice_info[v];
         vi.upper_silent = true;
         for (int p = 0; p < NUM_VOICED; ++p)
             for (int i = NF / 2; i < NF; ++i) {
@@ -330,15 +311,22 @@ int install_voices(grail_ctx *ctx, const grail_voice *voices, uint32_t n_voices)
         vi.scan_ok = scan_voice_ok(voices[v]);
         vi.warmup = dv[v].warmup;
         vi.split_ok = dv[v].warmup != 0u && voices[v].sample_rate > 0.0f && std::isfinite(voices[v].sample_rate);
-        ctx->voices_live4_ok = ctx->voices_live4_ok && vi.live4_ok;
-        ctx->voices_split_ok = ctx->voices_split_ok && vi.split_ok;
-        if (dv[v].warmup > ctx->max_warmup) ctx->max_warmup = dv[v].warmup;
-        if (voices[v].sample_rate > ctx->max_rate) ctx->max_rate = voices[v].sample_rate;
+        facts.voices_upper_silent = facts.voices_upper_silent && vi.upper_silent;
+        facts.voices_live4_ok = facts.voices_live4_ok && vi.live4_ok;
+        facts.voices_scan_ok = facts.voices_scan_ok && vi.scan_ok;
+        facts.voices_split_ok = facts.voices_split_ok && vi.split_ok;
+        if (vi.warmup > facts.max_warmup) facts.max_warmup = vi.warmup;
+        if (voices[v].sample_rate > facts.max_rate) facts.max_rate = voices[v].sample_rate;
         const float dt = 1.0f / voices[v].sample_rate;
-        if (!(dt <= ctx->max_dt)) ctx->max_dt = dt;       // NaN-proof max
+        if (!(dt <= facts.max_dt)) facts.max_dt = dt;       // NaN-proof max
         const float pj = std::fabs(voices[v].jitter_delta_frequency);
-        if (!(pj <= ctx->max_pitch_jitter)) ctx->max_pitch_jitter = pj;
+        if (!(pj <= facts.max_pitch_jitter)) facts.max_pitch_jitter = pj;
+        facts.voice_sharpness[v] = elems_sharpness(voices[v].phonemes, NUM_VOICED);
+        facts.voices_sharpness = std::fmax(facts.voices_sharpness, facts.voice_sharpness[v]);
     }
+    ctx->voices.assign(voices, voices + n_voices);
+    ctx->voices_epoch = ++g_epoch;
+    ctx->facts = std::move(facts);
     return GRAIL_OK;
 }
 
@@ -479,307 +467,6 @@ uint64_t grail_length_bound(const float *segment_lengths, uint32_t n_segments, f
     return samples < 1.8e19 ? (uint64_t)samples : UINT64_MAX;
 }
 
-int grail_set_option(grail_ctx *ctx, const char *name, int64_t value)
-{
-    if (!ctx || !name) return fail(GRAIL_ERR_INVALID_ARG, "NULL argument");
-    ++ctx->options_epoch;
-    if (std::strcmp(name, "lanes_per_utterance") == 0) {
-        if (value != 0 && value != 1 && value != 2 && value != 4 && value != 8)
-            return fail(GRAIL_ERR_INVALID_ARG, "lanes_per_utterance must be 0, 1, 2, 4 or 8");
-        ctx->lanes_option = (int)value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "skip_silent_formants") == 0) {
-        ctx->skip_silent_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "small_batch_pipeline") == 0) {
-        ctx->pipeline_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "arithmetic") == 0) {
-        if (value != 0 && value != 1 && value != 2)
-            return fail(GRAIL_ERR_INVALID_ARG, "arithmetic must be 0 (exact), 1 (fast) or 2 (fast, exact coefficients)");
-        ctx->fast_option = (int)value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_exact_coefficients") == 0) {
-        ctx->mid_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_sharpness_limit_exact_coefficients") == 0) {
-        if (value < 0) return fail(GRAIL_ERR_INVALID_ARG, "negative limit");
-        ctx->mid_limit = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_parallel_scan") == 0) {
-        ctx->scan_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "packed_launch_order") == 0) {
-        ctx->packed_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "sort_by_length") == 0) {    // applies to batches uploaded afterwards
-        ctx->sort_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split") == 0) {
-        ctx->split_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_chunks") == 0) {
-        if (value < 0 || value > SPLIT_MAX_CHUNKS) return fail(GRAIL_ERR_INVALID_ARG, "time_split_chunks must be 0 (auto) .. 64");
-        ctx->split_chunks = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_span_samples") == 0) {
-        if (value < 0 || value > 0x7fffffff) return fail(GRAIL_ERR_INVALID_ARG, "time_split_span_samples out of range");
-        ctx->split_span = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_ff_cost_permille") == 0) {
-        if (value < 0 || value > 1000) return fail(GRAIL_ERR_INVALID_ARG, "time_split_ff_cost_permille must be 0 .. 1000");
-        ctx->split_ff_permille = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_min_utterances") == 0) {   // -1: the cost model decides
-        if (value < -1) return fail(GRAIL_ERR_INVALID_ARG, "negative limit");
-        ctx->split_min_utts = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_sharpness_limit") == 0) {
-        if (value < 0) return fail(GRAIL_ERR_INVALID_ARG, "negative limit");
-        ctx->fast_limit = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline4_max_groups") == 0) {   // tuning: four-formant batches, 16 utterances per workgroup
-        ctx->pipe4_max_groups = value;                       // (-1: two per compute unit)
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "assume_compute_units") == 0) {   // plan for so many compute units (0: what the device reports)
-        if (value < 0 || value > 4096) return fail(GRAIL_ERR_INVALID_ARG, "assume_compute_units must be 0 (the device's) .. 4096");
-        ctx->cus = value ? (int)value : ctx->device_cus;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "composite_launches") == 0) {
-        ctx->composite_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "ragged_plan") == 0) {
-        ctx->ragged_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "two_waves_per_simd") == 0) {
-        ctx->two_waves_option = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline_spread") == 0) {
-        ctx->pipe_spread = value ? 1 : 0;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "row_groups") == 0) {
-        if (value < 0 || value > 2) return fail(GRAIL_ERR_INVALID_ARG, "row_groups must be 0 (off), 1 (by cost) or 2 (always)");
-        ctx->row_groups_option = (int)value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline8_max_groups") == 0) {   // tuning: 0 keeps eight-formant batches off the pipeline
-        ctx->pipe8_max_groups = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline_round32") == 0) {       // tuning (A/B)
-        if (value < 0 || value > 2) return fail(GRAIL_ERR_INVALID_ARG, "pipeline_round32 must be 0 (never), 1 (aligned batches) or 2 (any batch)");
-        ctx->pipe_round32 = (int)value;
-        return GRAIL_OK;
-    }
-#ifdef GRAIL_SCAN_DEBUG
-    if (std::strcmp(name, "scan_debug") == 0) {       // development builds only (-DGRAIL_SCAN_DEBUG): see scan_kernels.hip
-        ctx->scan_debug = (int)value;
-        return GRAIL_OK;
-    }
-#endif
-    if (std::strcmp(name, "time_parallel_scan_split_max_utterances") == 0) {   // -1: 6 per compute unit
-        if (value < -1) return fail(GRAIL_ERR_INVALID_ARG, "negative limit");
-        ctx->scan_split_max = value;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_parallel_scan_max_utterances") == 0) {         // -1: 34 per compute unit
-        if (value < -1) return fail(GRAIL_ERR_INVALID_ARG, "negative limit");
-        ctx->scan_max_utts = value;
-        return GRAIL_OK;
-    }
-    return fail(GRAIL_ERR_INVALID_ARG, std::string("unknown option ") + name);
-}
-
-int grail_get_option(grail_ctx *ctx, const char *name, int64_t *value)
-{
-    if (!ctx || !name || !value) return fail(GRAIL_ERR_INVALID_ARG, "NULL argument");
-    if (std::strcmp(name, "lanes_per_utterance") == 0) {
-        *value = ctx->lanes_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "skip_silent_formants") == 0) {
-        *value = ctx->skip_silent_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "arithmetic") == 0) {
-        *value = ctx->fast_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_parallel_scan") == 0) {
-        *value = ctx->scan_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_parallel_scan_max_utterances") == 0) {   // as set (-1: 34 per compute unit), so that
-        *value = ctx->scan_max_utts;                                       // get / set restores exactly
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "compute_units") == 0) {             // read-only: what the launch policy plans for
-        *value = ctx->cus;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "assume_compute_units") == 0) {      // 0: the device's own count is in force
-        *value = ctx->cus == ctx->device_cus ? 0 : ctx->cus;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "composite_launches") == 0) {
-        *value = ctx->composite_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "row_groups") == 0) {
-        *value = ctx->row_groups_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "ragged_plan") == 0) {
-        *value = ctx->ragged_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "two_waves_per_simd") == 0) {
-        *value = ctx->two_waves_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline_spread") == 0) {
-        *value = ctx->pipe_spread;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline4_max_groups") == 0) {
-        *value = ctx->pipe4_max_groups;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline8_max_groups") == 0) {
-        *value = ctx->pipe8_max_groups;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "pipeline_round32") == 0) {
-        *value = ctx->pipe_round32;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "packed_launch_order") == 0) {
-        *value = ctx->packed_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_packed") == 0) {
-        *value = ctx->last_packed;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "sort_by_length") == 0) {
-        *value = ctx->sort_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_fast") == 0) {          // read-only: some block of the last launch ran tolerance arithmetic
-        *value = ctx->last_fast;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_blocks") == 0) {        // read-only: kernel launches the last synthesis call was cut into
-        *value = ctx->last_blocks;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split") == 0) {
-        *value = ctx->split_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_chunks") == 0) {
-        *value = ctx->split_chunks;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_span_samples") == 0) {
-        *value = ctx->split_span;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_ff_cost_permille") == 0) {
-        *value = ctx->split_ff_permille;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_split_min_utterances") == 0) {
-        *value = ctx->split_min_utts;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_sharpness_limit") == 0) {
-        *value = ctx->fast_limit;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_arithmetic_served") == 0) {    // read-only: the tier "arithmetic" = 1 gets for the voice table
-        *value = fast_tier_for(ctx, nullptr, 1);                // as a whole: 1 interpolating, 2 exact coefficients, 0 exact kernels
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_exact_coefficients") == 0) {
-        *value = ctx->mid_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_sharpness_limit_exact_coefficients") == 0) {
-        *value = ctx->mid_limit;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_chunks") == 0) {        // read-only: chunks per utterance (0: not time-split)
-        *value = ctx->last_split;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "time_parallel_scan_split_max_utterances") == 0) {
-        *value = ctx->scan_split_max;
-        return GRAIL_OK;
-    }
-#ifdef GRAIL_FAST_PROF
-    if (std::strncmp(name, "debug_prof_", 11) == 0) {          // debug builds: counter k of the tolerance-mode tile loop
-        const int k = std::atoi(name + 11);
-        if (k < 0 || k >= 32) return fail(GRAIL_ERR_INVALID_ARG, "debug_prof_<k>: k in 0 .. 31");
-        unsigned long long v = 0;
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipMemcpy(&v, reinterpret_cast<unsigned long long *>(ctx->d_truncated + 8) + k, sizeof v, hipMemcpyDeviceToHost));
-        *value = (int64_t)v;
-        return GRAIL_OK;
-    }
-#endif
-    if (std::strcmp(name, "slow_division_wave_steps") == 0) {  // read-only statistic
-        *value = (int64_t)ctx->slow_steps;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "fast_wave_tiles") == 0) {           // read-only: wave-tiles rendered in fast arithmetic
-        *value = (int64_t)ctx->fast_tiles;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "general_wave_steps") == 0) {        // read-only: wave-steps through the general step
-        *value = (int64_t)ctx->general_steps;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_formants") == 0) {      // read-only: 4 or 8 laid out over the lanes
-        *value = ctx->last_formants;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_lanes") == 0) {         // read-only: lanes per utterance chosen
-        *value = ctx->last_lanes;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "small_batch_pipeline") == 0) {
-        *value = ctx->pipeline_option;
-        return GRAIL_OK;
-    }
-    if (std::strcmp(name, "last_launch_pipelined") == 0) {     // read-only
-        *value = ctx->last_pipe;
-        return GRAIL_OK;
-    }
-    return fail(GRAIL_ERR_INVALID_ARG, std::string("unknown option ") + name);
-}
-
 int grail_batch_upload(grail_ctx *ctx, const grail_phoneme_elem *segs, const uint32_t *seg_offsets,
                        const uint32_t *voice_ids, const uint32_t *jitter_seeds, uint32_t n_utt,
                        grail_batch **out)
@@ -797,7 +484,7 @@ int grail_batch_upload(grail_ctx *ctx, const grail_phoneme_elem *segs, const uin
     // per utterance, then over the batch: what the launch policy asks of the segments
     std::vector<RowStats> rows(n_utt);
     // (the device's dt of the table's highest sample rate, as the kernels have it: an f32 reciprocal)
-    const double min_dt = ctx->max_rate > 0.0f ? (double)(1.0f / ctx->max_rate) : 0.0;
+    const double min_dt = ctx->facts.max_rate > 0.0f ? (double)(1.0f / ctx->facts.max_rate) : 0.0;
     for (uint32_t u = 0; u < n_utt; ++u) {
         RowStats &r = rows[u];
         for (uint32_t i = seg_offsets[u]; i < seg_offsets[u + 1]; ++i) {
@@ -863,7 +550,7 @@ int grail_batch_upload_elems(grail_ctx *ctx, const grail_sequence_elem *segs,
     // caller-built elem keeps its frequency as it is, copy_with_frequency's min(f, 0.5) :445-450 belongs to the Selector)
     std::vector<RowStats> rows(n_utt);
     // (the device's dt of the table's highest sample rate, as the kernels have it: an f32 reciprocal)
-    const double min_dt = ctx->max_rate > 0.0f ? (double)(1.0f / ctx->max_rate) : 0.0;
+    const double min_dt = ctx->facts.max_rate > 0.0f ? (double)(1.0f / ctx->facts.max_rate) : 0.0;
     for (uint32_t u = 0; u < n_utt; ++u) {
         RowStats &r = rows[u];
         for (uint32_t i = seg_offsets[u]; i < seg_offsets[u + 1]; ++i) {
@@ -1034,9 +721,9 @@ int grail_sync(grail_ctx *ctx)
     const uint32_t flag = flags[0];
     // the statistics counters are cumulative on the device (u32, wrapping): the host takes differences, so the usual
     // call costs one copy and one synchronisation; only a truncation flag has to be cleared
-    ctx->slow_steps += (uint32_t)(flags[1] - ctx->seen_counters[1]);
-    ctx->fast_tiles += (uint32_t)(flags[2] - ctx->seen_counters[2]);
-    ctx->general_steps += (uint32_t)(flags[3] - ctx->seen_counters[3]);
+    ctx->stats.slow_steps += (uint32_t)(flags[1] - ctx->seen_counters[1]);
+    ctx->stats.fast_tiles += (uint32_t)(flags[2] - ctx->seen_counters[2]);
+    ctx->stats.general_steps += (uint32_t)(flags[3] - ctx->seen_counters[3]);
     for (int i = 1; i < 4; ++i) ctx->seen_counters[i] = flags[i];
     if (flag) {
         HIP_TRY(hipMemsetAsync(ctx->d_truncated, 0, sizeof(uint32_t), ctx->stream));
@@ -1049,7 +736,7 @@ int grail_sync(grail_ctx *ctx)
     return GRAIL_OK;
 }
 
-const char *grail_last_kernel_name(grail_ctx *ctx) { return ctx ? ctx->last_kernel.c_str() : "none"; }
+const char *grail_last_kernel_name(grail_ctx *ctx) { return ctx ? ctx->stats.last_kernel.c_str() : "none"; }
 
 int grail_last_kernel_ms(grail_ctx *ctx, float *ms)
 {

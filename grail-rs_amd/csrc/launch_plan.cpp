@@ -27,7 +27,7 @@ int auto_lanes_per_utt(uint32_t n_utt, uint64_t simds)
 // the longest utterance of the batch in samples, as far as the host knows it (the f32 clock adds a few per segment)
 double batch_span(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride)
 {
-    double span = std::ceil((double)batch->max_seconds * ctx->max_rate) + 64.0;
+    double span = std::ceil((double)batch->max_seconds * ctx->facts.max_rate) + 64.0;
     if (!(span >= 64.0)) span = 64.0;                         // NaN / negative lengths
     return std::fmin(span, (double)(out_stride ? out_stride : 1));
 }
@@ -55,7 +55,7 @@ static double mid_ms_per_sample(bool live4) { return (live4 ? MID_MS_4 : MID_MS_
 // puts their waves cannot matter.
 bool family_cohabits(const grail_ctx *ctx, const Family &f, uint32_t rows)
 {
-    if (!ctx->two_waves_option || f.scan || f.pipe || f.split_k || f.fast > 1u) return false;
+    if (!ctx->opt.two_waves_option || f.scan || f.pipe || f.split_k || f.fast > 1u) return false;
     // (tolerance mode: 2 lanes with four formants laid out, 4 and 8 lanes; exact: 2 lanes with four formants, 4 lanes —
     // the instantiations that hold their state in 256 registers without a scratch segment)
     const bool built = f.fast ? (f.L == 4 || f.L == 8 || (f.L == 2 && f.live4)) : (f.L == 4 || (f.L == 2 && f.live4));
@@ -85,7 +85,7 @@ static double cohabit_gain(const Family &f, double density = 0.0)
 // utterances, one per workgroup, hold no event but their own (profiles/r05_mixed_runs.txt).
 uint32_t pipe_fill_for(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t rows)
 {
-    if (!f.pipe || !ctx->pipe_spread || batch == nullptr || batch->granule_samples.size() < 2 ||
+    if (!f.pipe || !ctx->opt.pipe_spread || batch == nullptr || batch->granule_samples.size() < 2 ||
         batch->granule_samples.front() == batch->granule_samples.back())
         return 0u;
     const uint32_t slots = f.live4 ? 16u : 8u;
@@ -146,18 +146,18 @@ double family_cost(const grail_ctx *ctx, const Family &f, uint32_t rows, double 
 template <typename Pred>
 static bool used_voices_all(const grail_ctx *ctx, const grail_batch *batch, bool table_wide, Pred pred)
 {
-    if (ctx->voice_info.empty() || batch->used_voices.empty()) return table_wide;
+    if (ctx->facts.voice_info.empty() || batch->used_voices.empty()) return table_wide;
     for (const uint32_t v : batch->used_voices)
-        if (v >= ctx->voice_info.size() || !pred(ctx->voice_info[v])) return false;
+        if (v >= ctx->facts.voice_info.size() || !pred(ctx->facts.voice_info[v])) return false;
     return true;
 }
 bool batch_half_capable(const grail_ctx *ctx, const grail_batch *batch)
 {
     // (caller-built elems: judged at upload over the batch's distinct elems, against the voice table of that moment)
     if (!batch->phoneme_mode)
-        return ctx->skip_silent_option && batch->elems_live4_ok && batch->elems_warmup_epoch == ctx->voices_epoch;
-    return ctx->skip_silent_option &&
-           used_voices_all(ctx, batch, ctx->voices_upper_silent, [](const grail_ctx::VoiceInfo &v) { return v.upper_silent; });
+        return ctx->opt.skip_silent_option && batch->elems_live4_ok && batch->elems_warmup_epoch == ctx->voices_epoch;
+    return ctx->opt.skip_silent_option &&
+           used_voices_all(ctx, batch, ctx->facts.voices_upper_silent, [](const VoiceInfo &v) { return v.upper_silent; });
 }
 
 // formants 5-8 left out altogether: the table qualifies (live4_ok); every segment is at least
@@ -168,10 +168,10 @@ bool batch_live4_any_blend(const grail_ctx *ctx, const grail_batch *batch)
 {
     return batch_half_capable(ctx, batch) &&
            (!batch->phoneme_mode ||
-            used_voices_all(ctx, batch, ctx->voices_live4_ok, [](const grail_ctx::VoiceInfo &v) { return v.live4_ok; })) &&
+            used_voices_all(ctx, batch, ctx->facts.voices_live4_ok, [](const VoiceInfo &v) { return v.live4_ok; })) &&
            batch->plain &&
-           batch->min_length >= 2.0f * ctx->max_dt &&
-           batch->min_pitch * 0.999f - 1.002f * ctx->max_pitch_jitter >= 9.5367431640625e-07f;
+           batch->min_length >= 2.0f * ctx->facts.max_dt &&
+           batch->min_pitch * 0.999f - 1.002f * ctx->facts.max_pitch_jitter >= 9.5367431640625e-07f;
 }
 // ... and (the lane kernels' four-formant instantiations) every blend length a power of two
 bool batch_live4(const grail_ctx *ctx, const grail_batch *batch)
@@ -188,7 +188,7 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
                    bool exact_only, int pin_lanes)
 {
     const uint64_t simds = ctx_simds(ctx), cus = (uint64_t)ctx->cus;
-    const int lanes_option = pin_lanes ? pin_lanes : ctx->lanes_option;   // (pin_lanes: as if the option named it)
+    const int lanes_option = pin_lanes ? pin_lanes : ctx->opt.lanes_option;   // (pin_lanes: as if the option named it)
     f = Family();
     // (the lane kernels and the pipelined workgroups have four-formant instantiations for every blend length; the lean
     // stream kernels for power-of-two blend lengths only: batch_live4)
@@ -203,9 +203,9 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
     // small batches leave SIMDs idle: four-wave workgroups (one wave renders 16 utterances, one carries
     // the per-utterance chain, two prepare the filter coefficients), up to two per CU (tools/pipe4_range.py:
     // 11.5 ms up to 4 096 utterances, 15.7 up to 8 192 where the lane kernels take 18.0; three per CU lose)
-    const bool want_pipe4 = batch_live4_any_blend(ctx, batch) && !lanes_option && ctx->pipeline_option &&
+    const bool want_pipe4 = batch_live4_any_blend(ctx, batch) && !lanes_option && ctx->opt.pipeline_option &&
                             (int64_t)(((uint64_t)fam + 15) / 16) <= pipe4_groups(ctx);
-    const bool want_pipe8 = !batch_live4_any_blend(ctx, batch) && !lanes_option && ctx->pipeline_option &&
+    const bool want_pipe8 = !batch_live4_any_blend(ctx, batch) && !lanes_option && ctx->opt.pipeline_option &&
                             (int64_t)(((uint64_t)fam + 7) / 8) <= pipe8_groups(ctx);
     // one workgroup per CU suffices: rounds of 32 samples instead of 16 (pipe = 2) — for batches whose rows are aligned.
     // Rows that differ in length (the upload kept their summary) have their events at times of their own, and a tile with an
@@ -214,7 +214,7 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
     // 4 - 16 ms 4.6 / 5.3; profiles/r05_mixed_runs.txt)
     const bool rows_differ = batch != nullptr && !batch->granule_samples.empty() &&
                              batch->granule_samples.front() != batch->granule_samples.back();
-    const bool round32 = ctx->pipe_round32 == 2 || (ctx->pipe_round32 == 1 && !rows_differ);      // (2: tests, A/B)
+    const bool round32 = ctx->opt.pipe_round32 == 2 || (ctx->opt.pipe_round32 == 1 && !rows_differ);      // (2: tests, A/B)
     const uint32_t pipe4_kind = round32 && ((uint64_t)fam + 15) / 16 <= cus ? 2u : 1u;
     const uint32_t pipe8_kind = round32 && ((uint64_t)fam + 7) / 8 <= cus ? 2u : 1u;
     if (want_pipe4 && !f.fast) {
@@ -247,18 +247,18 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
     Family split = f;
     // (which voices / elems qualify: voice_warmup.  A phoneme batch is covered by its voice table; caller-built elems
     // by the warm-up computed over them at upload, against the voice table of that moment)
-    const bool split_ok = batch->phoneme_mode ? used_voices_all(ctx, batch, ctx->voices_split_ok,
-                                                                [](const grail_ctx::VoiceInfo &v) { return v.split_ok; })
+    const bool split_ok = batch->phoneme_mode ? used_voices_all(ctx, batch, ctx->facts.voices_split_ok,
+                                                                [](const VoiceInfo &v) { return v.split_ok; })
                                               : (batch->elems_warmup != 0u && batch->elems_warmup_epoch == ctx->voices_epoch);
     // (the grid is laid out for the longest warm-up of the TABLE, not of the voices the batch names: for a pinned grid an
     // utterance's samples may not depend on what else is in the batch; each lane still warms up for its own voice's length)
-    const uint32_t warmup = batch->phoneme_mode ? ctx->max_warmup : batch->elems_warmup;
-    if (ctx->split_option && !lanes_option && split_ok && batch->plain &&
-        out_stride <= 0xFFFFFFFFull && (ctx->split_chunks >= 2 || ctx->split_chunks == 0)) {
-        const double sp = ctx->split_span ? std::fmin((double)ctx->split_span, (double)out_stride) : span;
+    const uint32_t warmup = batch->phoneme_mode ? ctx->facts.max_warmup : batch->elems_warmup;
+    if (ctx->opt.split_option && !lanes_option && split_ok && batch->plain &&
+        out_stride <= 0xFFFFFFFFull && (ctx->opt.split_chunks >= 2 || ctx->opt.split_chunks == 0)) {
+        const double sp = ctx->opt.split_span ? std::fmin((double)ctx->opt.split_span, (double)out_stride) : span;
         // as many chunks as give every SIMD one wave: ceil(fam / 64) waves per chunk index (5 000 utterances are 79 waves
         // per chunk: 12 chunks, not 65 536 / 5 000 = 13, which would be 1 027 waves and a second round for three of them)
-        int K = ctx->split_chunks ? (int)ctx->split_chunks
+        int K = ctx->opt.split_chunks ? (int)ctx->opt.split_chunks
                                   : (int)std::min<uint64_t>(simds / (((uint64_t)fam + 63u) / 64u), SPLIT_MAX_CHUNKS);
         // Rows that differ in length (whole batch, launched longest first, the upload's length bounds on the device): a
         // chunk's wave whose utterances all end before the chunk begins is gone at once (synth_kernel.h, SPLIT), so the
@@ -274,12 +274,12 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
             }
             return pairs;
         };
-        const bool by_length = !ctx->split_chunks && !ctx->split_span && rows_differ && fam == batch->n_utt &&
+        const bool by_length = !ctx->opt.split_chunks && !ctx->opt.split_span && rows_differ && fam == batch->n_utt &&
                                batch->len_bound_known && batch->len_bound_epoch == ctx->voices_epoch;
         K = (int)std::fmin((double)K, sp / 512.0);
         // (a fast-forwarded sample costs the same whatever is rendered afterwards; a rendered sample of eight live
         // formants costs 1.5 x one of four; 0.8 from a sweep, profiles/r03_small_batch.txt)
-        const double ff_cost = 1e-3 * (double)ctx->split_ff_permille * (l4ab ? 1.0 : 0.8) * (f.fast == 2u ? 0.6 : 1.0);
+        const double ff_cost = 1e-3 * (double)ctx->opt.split_ff_permille * (l4ab ? 1.0 : 0.8) * (f.fast == 2u ? 0.6 : 1.0);
         // the largest K <= K whose chunks fit (a chunk must render at least a tile): fitting is monotone in K
         if (K >= 2 && !split_grid((uint32_t)sp, warmup, K, ff_cost, split.split_bounds)) {
             int lo = 1, hi = K;                  // lo fits (or is 1), hi does not
@@ -320,13 +320,13 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
     Family scan = f;
     // (rows that differ in length, option "ragged_plan": up to 64 workgroups per compute unit — there the cost model decides,
     // by the rows: 10 000 speech-like utterances 15.3 ms against 19.1 time-split, with phonemes of 16 - 64 ms 7.0 / 13.5)
-    const int64_t scan_limit = ctx->scan_max_utts < 0 && ctx->ragged_option && rows_differ && fam == batch->n_utt
+    const int64_t scan_limit = ctx->opt.scan_max_utts < 0 && ctx->opt.ragged_option && rows_differ && fam == batch->n_utt
                                    ? 64 * (int64_t)ctx->cus : scan_max_utts(ctx);
-    if (f.fast == 1u && ctx->scan_option && !lanes_option && (int64_t)fam * (l4ab ? 4 : 7) <= 4 * scan_limit &&
-        used_voices_all(ctx, batch, ctx->voices_scan_ok, [](const grail_ctx::VoiceInfo &v) { return v.scan_ok; }) &&
+    if (f.fast == 1u && ctx->opt.scan_option && !lanes_option && (int64_t)fam * (l4ab ? 4 : 7) <= 4 * scan_limit &&
+        used_voices_all(ctx, batch, ctx->facts.voices_scan_ok, [](const VoiceInfo &v) { return v.scan_ok; }) &&
         (batch->phoneme_mode || (batch->elems_scan_ok && batch->elems_warmup_epoch == ctx->voices_epoch)) &&
-        batch->plain && batch->min_length >= 2.0f * ctx->max_dt &&
-        batch->min_pitch * 0.999f - 1.002f * ctx->max_pitch_jitter >= 9.5367431640625e-07f) {
+        batch->plain && batch->min_length >= 2.0f * ctx->facts.max_dt &&
+        batch->min_pitch * 0.999f - 1.002f * ctx->facts.max_pitch_jitter >= 9.5367431640625e-07f) {
         scan.scan = true;
         scan.live4 = l4ab ? 1u : 0u;                          // (the scan kernel takes any blend length)
         // three-stage workgroups for few utterances (tools/scan_split_crossover.py: up to ~1500 with four
@@ -339,16 +339,16 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
     // machine's lanes, the lane kernels beyond; shorter utterances move the first crossover up — a chunk's warm-up
     // does not shrink with the utterance)
     bool take_split = false, take_scan = false;
-    if (split.split_k && ctx->split_chunks >= 2) {
+    if (split.split_k && ctx->opt.split_chunks >= 2) {
         take_split = true;
-    } else if (ctx->split_min_utts >= 0) {
-        take_split = split.split_k && (int64_t)fam * 6 >= ctx->split_min_utts * (l4ab ? 6 : 5);
+    } else if (ctx->opt.split_min_utts >= 0) {
+        take_split = split.split_k && (int64_t)fam * 6 >= ctx->opt.split_min_utts * (l4ab ? 6 : 5);
         take_scan = !take_split && scan.scan;
     } else {
         double c_lane = family_cost(ctx, f, fam, span);
         double c_split = split.split_k ? family_cost(ctx, split, fam, span) : INFINITY;
         double c_scan = scan.scan ? family_cost(ctx, scan, fam, span) : INFINITY;
-        if (ctx->ragged_option && rows_differ && fam == batch->n_utt) {
+        if (ctx->opt.ragged_option && rows_differ && fam == batch->n_utt) {
             // Rows that differ in length (the whole batch, its summary from the upload; part of option "ragged_plan"): the three
             // families part ways.  The
             // scan kernel gives every utterance a workgroup of its own — what a compute unit works off is the SUM of its
@@ -369,7 +369,7 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
     }
     if (take_split) f = split;
     else if (take_scan) f = scan;
-    if (f.fast == 2u && !lanes_option && ctx->split_chunks < 2) {
+    if (f.fast == 2u && !lanes_option && ctx->opt.split_chunks < 2) {
         // The second tier costs 0.8 of the exact one-lane kernel (0.64 - 0.8 time-split): where the exact kernels have a
         // wider mapping to fill the machine with — mid-size batches of voices that do not qualify for time-splitting —
         // they are the faster way to the same tolerance (their bits satisfy it trivially).
@@ -823,7 +823,7 @@ bool packed_launch_order(const grail_ctx *ctx, const grail_batch *batch, const F
     // more workgroups than the device holds at once, each alone on its SIMDs (two waves per SIMD: the fold of synth_kernel.h),
     // and only whole workgroups are moved: a last one with fewer rows keeps the last position
     const size_t n_full = rows / per_block;
-    if (!ctx->packed_option || family_cohabits(ctx, f, rows) || cost.size() <= (size_t)d.pools() * d.slots || n_full < 2) return false;
+    if (!ctx->opt.packed_option || family_cohabits(ctx, f, rows) || cost.size() <= (size_t)d.pools() * d.slots || n_full < 2) return false;
     std::vector<uint32_t> o;
     pack_order(d, cost, n_full, o);
     for (size_t b = n_full; b < cost.size(); ++b) o.push_back((uint32_t)b);
@@ -836,7 +836,7 @@ bool packed_launch_order(const grail_ctx *ctx, const grail_batch *batch, const F
 
 void ragged_plan(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t rows, std::vector<Block> &plan)
 {
-    if (!ctx->ragged_option || batch->granule_samples.empty() || rows != batch->n_utt || plan.empty()) return;
+    if (!ctx->opt.ragged_option || batch->granule_samples.empty() || rows != batch->n_utt || plan.empty()) return;
     if (plan.size() == 1 && plan[0].f.scan) return;   // (a few utterances in fast arithmetic: the scan kernel's)
     const double span = batch_span(ctx, batch, out_stride);
     auto cost_of = [&](const std::vector<Block> &blocks) {
@@ -852,10 +852,10 @@ void ragged_plan(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_st
     static const bool debug = [] { const char *e = getenv("GRAIL_PLAN_DEBUG"); return e && *e && *e != '0'; }();
     // (a candidate has to be worth the change: in tolerance arithmetic a row's bits follow its family, and grail_plan_blocks
     // predicts the cut by size; exact bits follow nothing, and one launch in packed order beats the same mapping cut in two)
-    const double worth = ctx->fast_option ? 0.95 : 0.98;
+    const double worth = ctx->opt.fast_option ? 0.95 : 0.98;
     double best = worth * cost_of(plan);
     if (debug) std::fprintf(stderr, "[ragged_plan] %u rows: the cut by size (%zu block(s)) %.2f ms\n", rows, plan.size(), best / worth);
-    if (ctx->fast_option) {
+    if (ctx->opt.fast_option) {
         // fast arithmetic asked for: the cut exact arithmetic would get stands too (small batches: the pipelined
         // workgroups) — events this dense cost the fast kernels more than they save, and exact bits satisfy the tolerance
         // trivially.  Phonemes of 16 - 64 ms, 65 536 utterances: 32 ms exact against 57 fast.
@@ -870,7 +870,7 @@ void ragged_plan(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_st
     // ... the ONE launch the batch as a whole would get (choose_family weighs scan, time-split and lane kernels by the rows
     // when it is asked about the whole batch; the cut above was made block by block, by the aligned model: 6 000 speech-like
     // utterances as 4 096 + 1 904 time-split rows took 26.9 ms, the scan kernel takes 10.9)
-    if (ctx->fast_option) {       // (exact arithmetic: that launch is one of the lane mappings below)
+    if (ctx->opt.fast_option) {       // (exact arithmetic: that launch is one of the lane mappings below)
         Family whole;
         choose_family(ctx, batch, out_stride, rows, whole, false);
         const double c = ragged_cost(ctx, batch, whole, 0, rows, span) + Planner::LAUNCH_MS;
@@ -880,7 +880,7 @@ void ragged_plan(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_st
         }
     }
     // ... and ONE launch of each lane mapping in as many rounds as it takes
-    for (int exact_only = 0; exact_only <= (ctx->fast_option ? 1 : 0); ++exact_only)
+    for (int exact_only = 0; exact_only <= (ctx->opt.fast_option ? 1 : 0); ++exact_only)
         for (int L = 1; L <= 8; L *= 2) {
             Family f;
             choose_family(ctx, batch, out_stride, rows, f, exact_only != 0, L);
@@ -950,14 +950,15 @@ static int plan_preview(uint32_t compute_units, int arithmetic, int live_formant
     // family (four or eight live formants), a plain phoneme batch with power-of-two blend lengths
     grail_ctx ctx;
     ctx.cus = ctx.device_cus = (int)compute_units;
-    ctx.fast_option = arithmetic;
-    ctx.voices_sharpness = 0.0;
-    ctx.voices_upper_silent = ctx.voices_live4_ok = live_formants == 4;
-    ctx.voices_scan_ok = true;
-    ctx.voices_split_ok = warmup != 0u;
-    ctx.max_warmup = warmup;
-    ctx.max_rate = 1.0f;                  // max_seconds below is in samples
-    ctx.max_dt = 1.0f;
+    ctx.opt.fast_option = arithmetic;
+    VoiceFacts &facts = ctx.facts;
+    facts.voices_sharpness = 0.0;
+    facts.voices_upper_silent = facts.voices_live4_ok = live_formants == 4;
+    facts.voices_scan_ok = true;
+    facts.voices_split_ok = warmup != 0u;
+    facts.max_warmup = warmup;
+    facts.max_rate = 1.0f;                // max_seconds below is in samples
+    facts.max_dt = 1.0f;
     grail_batch batch;
     batch.n_utt = rows;
     batch.phoneme_mode = true;

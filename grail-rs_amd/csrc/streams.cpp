@@ -21,13 +21,13 @@ int grail_stream_open(grail_ctx *ctx, const grail_batch *batch, grail_stream **o
     s->any_blend = batch->any_blend;
     s->live4 = batch_live4_any_blend(ctx, batch);      // (the lean resumable kernels exist for every blend length)
     s->voices_epoch = ctx->voices_epoch;
-    s->L = ctx->lanes_option ? ctx->lanes_option : auto_lanes_per_utt(batch->n_utt, ctx_simds(ctx));
-    if (s->live4 && !ctx->lanes_option && ctx->pipeline_option &&
+    s->L = ctx->opt.lanes_option ? ctx->opt.lanes_option : auto_lanes_per_utt(batch->n_utt, ctx_simds(ctx));
+    if (s->live4 && !ctx->opt.lanes_option && ctx->opt.pipeline_option &&
         (int64_t)(((uint64_t)batch->n_utt + 15) / 16) <= pipe4_groups(ctx)) {
         s->L = 4;                            // the pipelined workgroups of four formants (stream_next), 16 utterances each
     } else if (s->live4) {
         if (s->L == 8) s->live4 = false;     // eight lanes per utterance need eight formants to lay out
-        else if (!ctx->lanes_option)         // same rule over four formants: the widest one-wave-per-SIMD mapping
+        else if (!ctx->opt.lanes_option)         // same rule over four formants: the widest one-wave-per-SIMD mapping
             s->L = ((uint64_t)batch->n_utt * 4 + 63) / 64 <= ctx_simds(ctx) ? 4 : ((uint64_t)batch->n_utt * 2 + 63) / 64 <= ctx_simds(ctx) ? 2 : 1;
     }
     s->lanes = state_lanes(batch->n_utt, s->L);
@@ -39,6 +39,18 @@ int grail_stream_open(grail_ctx *ctx, const grail_batch *batch, grail_stream **o
     }
     *out = s;
     return GRAIL_OK;
+}
+
+// the statistics of a pull: one launch of the stream's mapping
+static void record_pull(LaunchStats &st, const SynthArgs &a, int lanes)
+{
+    st.last_kernel = last_kernel_name();
+    st.last_formants = a.live4 ? 4 : 8;
+    st.last_lanes = lanes;
+    st.last_pipe = a.pipe ? 1 : 0;
+    st.last_fast = (int)a.fast;
+    st.last_blocks = 1;
+    // (last_split and last_packed stay what the last one-shot launch left: "last_launch_chunks" / "_packed" tell of those)
 }
 
 static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_samples, float *out_dev,
@@ -73,7 +85,7 @@ static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_sample
     a.n_utt = batch->n_utt;
     a.n_voices = (uint32_t)ctx->voices.size();
     a.phoneme_mode = batch->phoneme_mode ? 1u : 0u;
-    a.skip_silent = ctx->skip_silent_option ? 1u : 0u;
+    a.skip_silent = ctx->opt.skip_silent_option ? 1u : 0u;
     if (stream->voices_epoch != ctx->voices_epoch)
         return fail(GRAIL_ERR_INVALID_ARG, "the voice table changed since the stream was opened");
     a.half_capable = stream->half_capable ? 1u : 0u;
@@ -88,11 +100,11 @@ static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_sample
     // would — same state block as the lane kernels of the stream's mapping, exact arithmetic (a tolerance request is
     // served by them too: their bits are the reference's, and at these sizes they are the faster kernels)
     const uint64_t cus = (uint64_t)ctx->cus;
-    if (ctx->pipeline_option && !ctx->lanes_option) {
+    if (ctx->opt.pipeline_option && !ctx->opt.lanes_option) {
         if (stream->live4 && stream->L == 4 && (int64_t)(((uint64_t)batch->n_utt + 15) / 16) <= pipe4_groups(ctx))
-            a.pipe = ctx->pipe_round32 && ((uint64_t)batch->n_utt + 15) / 16 <= cus ? 2u : 1u;
+            a.pipe = ctx->opt.pipe_round32 && ((uint64_t)batch->n_utt + 15) / 16 <= cus ? 2u : 1u;
         else if (!stream->live4 && stream->L == 8 && (int64_t)(((uint64_t)batch->n_utt + 7) / 8) <= pipe8_groups(ctx))
-            a.pipe = ctx->pipe_round32 && ((uint64_t)batch->n_utt + 7) / 8 <= cus ? 2u : 1u;
+            a.pipe = ctx->opt.pipe_round32 && ((uint64_t)batch->n_utt + 7) / 8 <= cus ? 2u : 1u;
         if (a.pipe) a.fast = 0u;
     }
     a.state = stream->d_state;
@@ -101,12 +113,7 @@ static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_sample
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
     hipError_t e = launch_synth(a, stream->L, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "synth kernel launch");
-    ctx->last_kernel = last_kernel_name();
-    ctx->last_formants = a.live4 ? 4 : 8;
-    ctx->last_lanes = stream->L;
-    ctx->last_pipe = a.pipe ? 1 : 0;
-    ctx->last_fast = (int)a.fast;
-    ctx->last_blocks = 1;
+    record_pull(ctx->stats, a, stream->L);
     HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->have_timing = true;
     stream->started = true;
@@ -210,7 +217,7 @@ int grail_stream_open_live(grail_ctx *ctx, uint32_t n_utt, const uint32_t *voice
     s->any_blend = true;
     s->live4 = false;
     s->voices_epoch = ctx->voices_epoch;
-    s->L = ctx->lanes_option ? ctx->lanes_option : auto_lanes_per_utt(n_utt, ctx_simds(ctx));
+    s->L = ctx->opt.lanes_option ? ctx->opt.lanes_option : auto_lanes_per_utt(n_utt, ctx_simds(ctx));
     s->lanes = state_lanes(n_utt, s->L);
     const size_t bytes = (size_t)state_words(s->L) * s->lanes * sizeof(uint32_t);
     if (e == hipSuccess) e = hipMalloc((void **)&s->d_state, bytes ? bytes : 4);

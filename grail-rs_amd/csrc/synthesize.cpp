@@ -25,7 +25,7 @@ static const uint32_t *packed_perm_of(grail_ctx *ctx, const grail_batch *root, c
                                       uint64_t out_stride, uint32_t slot0, uint32_t count, int *rc)
 {
     *rc = GRAIL_OK;
-    if (!ctx->packed_option || root->perm_host.size() < (size_t)slot0 + count) return nullptr;
+    if (!ctx->opt.packed_option || root->perm_host.size() < (size_t)slot0 + count) return nullptr;
     const uint32_t family = (uint32_t)f.L | f.fast << 8 | f.live4 << 16;
     static std::mutex lock;                    // (one batch may be rendered by several contexts, each on a thread of its own)
     std::lock_guard<std::mutex> hold(lock);
@@ -83,7 +83,7 @@ static int launch_block(grail_ctx *ctx, const grail_batch *root, const grail_bat
         if (rc) return rc;
         if (packed) {
             a.perm = packed;
-            ++ctx->last_packed;
+            ++ctx->stats.last_packed;
         }
     }
     a.elems = batch->phoneme_mode ? ctx->d_voice_elems : batch->d_elems;
@@ -96,7 +96,7 @@ static int launch_block(grail_ctx *ctx, const grail_batch *root, const grail_bat
     a.n_utt = count;
     a.n_voices = (uint32_t)ctx->voices.size();
     a.phoneme_mode = batch->phoneme_mode ? 1u : 0u;
-    a.skip_silent = ctx->skip_silent_option ? 1u : 0u;
+    a.skip_silent = ctx->opt.skip_silent_option ? 1u : 0u;
     a.half_capable = batch_half_capable(ctx, batch) ? 1u : 0u;
     a.any_blend = batch->any_blend ? 1u : 0u;
     a.live4 = f.live4;
@@ -114,10 +114,10 @@ static int launch_block(grail_ctx *ctx, const grail_batch *root, const grail_bat
     a.pipe = f.pipe;
     hipError_t e;
     if (f.scan) {
-        a.resume = (uint32_t)ctx->scan_debug;
+        a.resume = (uint32_t)ctx->opt.scan_debug;
         a.pipe = f.scan_pipe;
         e = launch_scan(a, ctx->stream);
-        ctx->last_kernel = a.live4 ? (a.pipe ? "scan_kernel<pairs=2,SPLIT,FAST>" : "scan_kernel<pairs=2,FAST>")
+        ctx->stats.last_kernel = a.live4 ? (a.pipe ? "scan_kernel<pairs=2,SPLIT,FAST>" : "scan_kernel<pairs=2,FAST>")
                                    : (a.pipe ? "scan_kernel<pairs=4,SPLIT,FAST>" : "scan_kernel<pairs=4,FAST>");
     } else {
         if (f.split_k) {
@@ -126,13 +126,26 @@ static int launch_block(grail_ctx *ctx, const grail_batch *root, const grail_bat
             std::memcpy(a.split_bounds, f.split_bounds, sizeof a.split_bounds);
         }
         e = launch_synth(a, f.L, ctx->stream);
-        ctx->last_kernel = last_kernel_name();
+        ctx->stats.last_kernel = last_kernel_name();
     }
     if (e != hipSuccess) return hip_fail(e, "synth kernel launch");
     return GRAIL_OK;
 }
 
 void free_plan_cache(PlanCache *p) { delete p; }
+
+// the statistics of a synthesis call before its launches: f0 is the family of its largest block; the launches add the
+// kernel's name, the packed blocks and the highest tier that ran
+static void record_plan(LaunchStats &st, const Family &f0, size_t n_blocks)
+{
+    st.last_split = f0.split_k;
+    st.last_formants = f0.live4 ? 4 : 8;
+    st.last_lanes = f0.scan ? 0 : f0.L;
+    st.last_pipe = f0.pipe && !f0.scan ? 1 : 0;
+    st.last_packed = 0;
+    st.last_fast = 0;
+    st.last_blocks = (int)n_blocks;
+}
 
 // Rows [first, first + count) of the batch (count = 0: all of it).  out_dev / out_len_dev point at the
 // first row RENDERED, i.e. the caller has already applied the row offset to them.
@@ -167,7 +180,7 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev,
             if (view->plan_cache && std::memcmp(view->plan_cache->key, key, sizeof key) == 0) return view->plan_cache->plan;
         }
         // one launch when the caller fixes the family (row blocks, a pinned lane mapping or chunk grid) or asks for it
-        const bool single = family_rows != 0 || !ctx->composite_option || ctx->lanes_option || ctx->split_chunks >= 2;
+        const bool single = family_rows != 0 || !ctx->opt.composite_option || ctx->opt.lanes_option || ctx->opt.split_chunks >= 2;
         if (single) {
             Family f;
             choose_family(ctx, view, out_stride, family_rows > rows ? family_rows : rows, f);
@@ -199,7 +212,7 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev,
     };
     std::vector<Part> plan;
     for (const Block &b : plan_of(batch, count)) plan.push_back(Part{batch, b});
-    if (use_perm && family_rows == 0 && ctx->row_groups_option && batch->groups.size() == 2 && batch->groups_epoch == ctx->voices_epoch) {
+    if (use_perm && family_rows == 0 && ctx->opt.row_groups_option && batch->groups.size() == 2 && batch->groups_epoch == ctx->voices_epoch) {
         // ... where that is cheaper by the cost model: a separate launch for four odd rows behind a full round of the
         // one-lane kernel costs more than it saves (53.7 against 46.7 ms), behind 20 000 rows it does not
         // (by the rows' own lengths and events where the view has them — a ragged corpus: ragged_cost falls back to the
@@ -219,19 +232,13 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev,
         std::vector<Part> grouped;
         for (const grail_batch &g : batch->groups)
             for (const Block &b : plan_of(&g, g.n_utt)) grouped.push_back(Part{&g, b});
-        if (ctx->row_groups_option == 2 || cost_of(grouped) < cost_of(plan)) plan.swap(grouped);
+        if (ctx->opt.row_groups_option == 2 || cost_of(grouped) < cost_of(plan)) plan.swap(grouped);
     }
     size_t main_block = 0;                     // the block with the most rows: the one the statistics describe
     for (size_t i = 1; i < plan.size(); ++i)
         if (plan[i].block.rows > plan[main_block].block.rows) main_block = i;
     const Family f0 = plan[main_block].block.f;
-    ctx->last_split = f0.split_k;
-    ctx->last_formants = f0.live4 ? 4 : 8;
-    ctx->last_lanes = f0.scan ? 0 : f0.L;
-    ctx->last_pipe = f0.pipe && !f0.scan ? 1 : 0;
-    ctx->last_packed = 0;
-    ctx->last_fast = 0;
-    ctx->last_blocks = (int)plan.size();
+    record_plan(ctx->stats, f0, plan.size());
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
     uint32_t slot0 = 0;
     std::string first_kernel;
@@ -239,11 +246,11 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev,
         const Block &b = plan[i].block;
         rc = launch_block(ctx, batch, plan[i].view, b.f, out_dev, out_pcm16_dev, out_stride, out_len_dev, first, slot0, b.rows, use_perm);
         if (rc) return rc;
-        if (i == main_block) first_kernel = ctx->last_kernel;
-        if ((int)b.f.fast > ctx->last_fast) ctx->last_fast = (int)b.f.fast;
+        if (i == main_block) first_kernel = ctx->stats.last_kernel;
+        if ((int)b.f.fast > ctx->stats.last_fast) ctx->stats.last_fast = (int)b.f.fast;
         slot0 += b.rows;
     }
-    ctx->last_kernel = first_kernel;            // the largest block's instantiation names the launch
+    ctx->stats.last_kernel = first_kernel;            // the largest block's instantiation names the launch
     HIP_TRY(hipEventRecord(ctx->ev_stop, ctx->stream));
     ctx->have_timing = true;
     return GRAIL_OK;

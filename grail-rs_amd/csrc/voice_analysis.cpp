@@ -205,10 +205,10 @@ double elems_sharpness(const grail_synthesis_elem *elems, size_t n)
 // without a batch: by the whole table.
 double batch_sharpness(const grail_ctx *ctx, const grail_batch *batch)
 {
-    if (!batch) return ctx->voices_sharpness;
+    if (!batch) return ctx->facts.voices_sharpness;
     if (!batch->phoneme_mode) return batch->elems_sharpness;
     double s = 0.0;
-    for (const uint32_t v : batch->used_voices) s = std::fmax(s, v < ctx->voice_sharpness.size() ? ctx->voice_sharpness[v] : INFINITY);
+    for (const uint32_t v : batch->used_voices) s = std::fmax(s, v < ctx->facts.voice_sharpness.size() ? ctx->facts.voice_sharpness[v] : INFINITY);
     return s;
 }
 // Which arithmetic a batch is rendered in when "arithmetic" asks for a tolerance mode: 1 = the interpolating tier (up
@@ -218,11 +218,11 @@ int fast_tier_for(const grail_ctx *ctx, const grail_batch *batch, int arithmetic
 {
     if (!arithmetic) return 0;
     const double s = batch_sharpness(ctx, batch);
-    if (arithmetic == 1 && s <= (double)ctx->fast_limit) return 1;
-    if ((ctx->mid_option || arithmetic == 2) && s <= (double)ctx->mid_limit) return 2;
+    if (arithmetic == 1 && s <= (double)ctx->opt.fast_limit) return 1;
+    if ((ctx->opt.mid_option || arithmetic == 2) && s <= (double)ctx->opt.mid_limit) return 2;
     return 0;
 }
-int fast_tier(const grail_ctx *ctx, const grail_batch *batch) { return fast_tier_for(ctx, batch, ctx->fast_option); }
+int fast_tier(const grail_ctx *ctx, const grail_batch *batch) { return fast_tier_for(ctx, batch, ctx->opt.fast_option); }
 // The chunk grid of a time-split launch: K chunks over `span` samples.  Chunk k's lane fast-forwards the chain over
 // b[k] - W samples (cost r per sample, in units of a rendered sample), warms up over W and renders b[k+1] - b[k]:
 // the bounds are spaced so that all lanes take the same time (T below, by bisection).  Bounds are multiples

@@ -3,6 +3,8 @@
 Integer/bit-exact bar: the kernel is IEEE binary32 without FMA contraction, so every
 sample must equal the oracle's as a 32-bit pattern (tolerance 0 ULP)."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 import pytest
@@ -973,3 +975,63 @@ def test_pipelined_rounds_between_the_events_of_a_tile(gpu_ctx, n_voices, round3
         ctx.set_option("ragged_plan", 1)
         ctx.set_option("pipeline_round32", 1)
         ctx.set_option("pipeline_spread", 1)
+
+
+# name: (documented default, another accepted value, a refused value or None where every value is accepted) — from the
+# option block of include/grail_hip.h
+OPTION_CASES = {
+    "arithmetic": (0, 1, 3),
+    "fast_sharpness_limit": (int(G.FAST_SHARPNESS_LIMIT), 5, -1),
+    "fast_exact_coefficients": (1, 0, None),
+    "fast_sharpness_limit_exact_coefficients": (1024, 7, -1),
+    "lanes_per_utterance": (0, 4, 3),
+    "skip_silent_formants": (1, 0, None),
+    "small_batch_pipeline": (1, 0, None),
+    "pipeline_round32": (1, 2, 3),
+    "pipeline_spread": (1, 0, None),
+    "pipeline4_max_groups": (-1, 5, None),
+    "pipeline8_max_groups": (-1, 0, None),
+    "time_parallel_scan": (1, 0, None),
+    "time_parallel_scan_max_utterances": (-1, 100, -2),
+    "time_parallel_scan_split_max_utterances": (-1, 100, -2),
+    "time_split": (1, 0, None),
+    "time_split_min_utterances": (-1, 10, -2),
+    "time_split_chunks": (0, 8, 65),
+    "time_split_span_samples": (0, 4096, 2 ** 31),
+    "time_split_ff_cost_permille": (165, 200, 1001),
+    "composite_launches": (1, 0, None),
+    "row_groups": (1, 2, 3),
+    "ragged_plan": (1, 0, None),
+    "two_waves_per_simd": (1, 0, None),
+    "packed_launch_order": (1, 0, None),
+    "sort_by_length": (1, 0, None),
+    "assume_compute_units": (0, 64, 4097),
+}
+
+
+def test_every_settable_option_defaults_round_trips_and_refuses(gpu_ctx):
+    """Every settable option of the header's block on a real context: it reads its documented default, another value is
+    read back as set and the default restores, and a value outside its domain is refused with GRAIL_ERR_INVALID_ARG and
+    leaves the option as it was."""
+    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "grail_hip.h")).read()
+    start = header.index("/* Options (grail_set_option / grail_get_option")
+    settable = header[start:header.index("*/", start)].split("Read-only (grail_get_option)")[0]
+    assert set(OPTION_CASES) == set(re.findall(r'"([a-z0-9_]+)"', settable)) - {"last_launch_fast", "scan_debug"}
+    ctx = gpu_ctx
+    for name, (default, other, refused) in OPTION_CASES.items():
+        assert ctx.get_option(name) == default, name
+        try:
+            ctx.set_option(name, other)
+            assert ctx.get_option(name) == other, name
+            if refused is not None:
+                with pytest.raises(G.GrailError) as ei:
+                    ctx.set_option(name, refused)
+                assert ei.value.status == G.ERR_INVALID_ARG, name
+                assert ctx.get_option(name) == other, name
+        finally:
+            ctx.set_option(name, default)
+        assert ctx.get_option(name) == default, name
+    assert ctx.get_option("compute_units") > 0
+    with pytest.raises(G.GrailError) as ei:
+        ctx.set_option("compute_units", 64)                # read-only: not a name grail_set_option knows
+    assert ei.value.status == G.ERR_INVALID_ARG and "unknown option compute_units" in str(ei.value)

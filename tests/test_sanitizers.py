@@ -1,7 +1,8 @@
 """AddressSanitizer + UBSan over the CPU oracle and the product's pure-host sources
 (voice algebra, text front half, RIFF writer; the launch policy: voice analysis, time-split grids,
-block planner).  GPU ASan is not available on the pool."""
+block planner; the option table).  GPU ASan is not available on the pool."""
 import os
+import re
 import subprocess
 
 import pytest
@@ -53,3 +54,34 @@ def test_launch_policy_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     assert "sanitize plan driver: ok" in r.stdout
     assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+
+
+@pytest.mark.timeout(300)
+def test_options_under_asan_ubsan_repeat_the_recorded_transcript(tmp_path):
+    """options.cpp makes no HIP call either: built with g++ and the sanitizers, then every name of the header's option
+    block (and a few it does not list) is set to each of 17 probe values and read back on a context without a device
+    (tests/sanitize_options_driver.cpp).  Return codes, error texts, values read and options_epoch must equal, byte for
+    byte, what the two hand-written ladders this table replaced gave (tests/golden/options_transcript.txt)."""
+    san = ["-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=undefined", "-g", "-O1",
+           "-ffp-contract=off", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+    csrc = os.path.join(ROOT, "grail-rs_amd", "csrc")
+    objs = []
+    for name in (os.path.join(csrc, "options.cpp"), os.path.join(csrc, "voice_analysis.cpp"),
+                 os.path.join(csrc, "voice_host.cpp"), os.path.join(csrc, "launch_plan.cpp"),
+                 os.path.join(ROOT, "tests", "sanitize_options_driver.cpp")):
+        o = str(tmp_path / (os.path.basename(name) + ".o"))
+        subprocess.check_call(["g++", *san, "-c", name, "-o", o])
+        objs.append(o)
+    exe = str(tmp_path / "sanitize_options_driver")
+    subprocess.check_call(["g++", "-fsanitize=address,undefined", *objs, "-o", exe, "-lm"])
+    header = open(os.path.join(ROOT, "include", "grail_hip.h")).read()
+    start = header.index("/* Options (grail_set_option / grail_get_option")
+    names = list(dict.fromkeys(re.findall(r'"([a-z0-9_]+)"', header[start:header.index("*/", start)])))   # in the header's order
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe, *names], capture_output=True, text=True, env=env, timeout=250)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr
+    assert r.stdout.endswith("sanitize options driver: ok\n")
+    recorded = open(os.path.join(ROOT, "tests", "golden", "options_transcript.txt")).read()
+    assert len(names) == 39 and recorded.count("\n[") == len(names) + 6
+    assert r.stdout == recorded
