@@ -1,9 +1,12 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
+// --ceiling DBTP (with --level or --lufs) holds every placement under that true peak as well: the rows' true peaks are
+// measured on the device and cap the gains (grail_batch_mix_leveled_limited), and the two finished tracks are measured
+// the same way (grail::Gpu::true_peak); "--lufs -23 --ceiling -1" is the delivery rule of EBU R 128.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -18,7 +21,8 @@ int main(int argc, char **argv)
     std::string out_path = "dialogue.wav";
     std::vector<std::string> lines;
     bool leveled = false, bad_level = false, lufs = false;
-    float level_db = 0.0f;
+    bool capped = false, bad_ceiling = false;
+    float level_db = 0.0f, ceiling_db = 0.0f;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
         else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
@@ -27,10 +31,16 @@ int main(int argc, char **argv)
             level_db = std::strtof(argv[++i], &rest);
             leveled = true;
             bad_level = rest == argv[i] || *rest || !std::isfinite(level_db);
+        } else if (!std::strcmp(argv[i], "--ceiling") && i + 1 < argc) {
+            char *rest = nullptr;
+            ceiling_db = std::strtof(argv[++i], &rest);
+            capped = true;
+            bad_ceiling = rest == argv[i] || *rest || !std::isfinite(ceiling_db);
         } else lines.push_back(argv[i]);
     }
-    if (lines.size() != 2 || bad_level) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] \"first line\" \"second line\"\n");
+    if (lines.size() != 2 || bad_level || bad_ceiling || (capped && !leveled)) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP] \"first line\" "
+                             "\"second line\"\n       (--ceiling needs --level or --lufs)\n");
         return 2;
     }
     try {
@@ -53,15 +63,21 @@ int main(int argc, char **argv)
         if (leveled) {          // the same pan as a level: 0.8 and 0.2 of the line at level_db
             std::vector<float> levels, gains;
             for (const grail::Placement &p : placements) levels.push_back(level_db + 20.0f * std::log10(p.gain));
-            uint32_t unleveled = 0;
-            tracks = gpu.mix_leveled(utts, placements, levels, 2, end, lufs ? GRAIL_LEVEL_LOUDNESS : GRAIL_LEVEL_RMS, &gains,
-                                     &unleveled);
+            uint32_t unleveled = 0, limited = 0;
+            const int mode = lufs ? GRAIL_LEVEL_LOUDNESS : GRAIL_LEVEL_RMS;
+            tracks = capped ? gpu.mix_leveled_limited(utts, placements, levels, ceiling_db, 2, end, mode, &gains, &unleveled, &limited)
+                            : gpu.mix_leveled(utts, placements, levels, 2, end, mode, &gains, &unleveled);
             if (lufs)
                 std::printf("Lines brought to %.1f LUFS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
                             unleveled ? " (a silent line or one shorter than 400 ms was left out)" : "");
             else
                 std::printf("Lines brought to %.1f dB RMS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f,
                             gains[3] / 0.8f, unleveled ? " (a silent line was left out)" : "");
+            if (capped) {
+                const grail::TruePeak tp = gpu.true_peak(tracks);
+                std::printf("Ceiling %.1f dBTP: %u of 4 placements limited; track true peaks %.6f and %.6f dBTP\n", ceiling_db,
+                            limited, tp.db(0), tp.db(1));
+            }
         } else {
             tracks = gpu.mix(utts, placements, 2, end);
         }

@@ -339,10 +339,13 @@ void mix_release(grail_ctx *ctx);     // mix.cpp
 void levels_release(grail_ctx *ctx);  // levels.cpp
 // levels.cpp, for grail_batch_mix_leveled: the rows of one rendered block measured on ctx's stream and their numbers
 // brought to the host (one wait), then the items' gains by grail_level_gains; gains[n_items], *n_unleveled is added to.
-// sample_rate is read in GRAIL_LEVEL_LOUDNESS only (level_table_rate).
+// sample_rate is read in GRAIL_LEVEL_LOUDNESS only (level_table_rate).  ceiling_db (NULL: none) is
+// grail_batch_mix_leveled_limited's: the rows' true peaks are measured too and grail_true_peak_limit_gains caps the gains;
+// *n_limited is added to.
 int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const float *rows_dev, uint64_t row_stride,
                       const uint32_t *len_dev, const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows,
-                      const float *item_level_db, uint32_t n_items, float *gains, uint32_t *n_unleveled);
+                      const float *item_level_db, uint32_t n_items, float *gains, uint32_t *n_unleveled,
+                      const float *ceiling_db, uint32_t *n_limited);
 // the one whole-numbered sample rate of ctx's voice table within GRAIL_LOUDNESS_RATE_MIN .. _MAX, or 0 if it has none
 uint32_t level_table_rate(const grail_ctx *ctx);
 // host_output.cpp: texts -> PhonemeElems (grail_say_batch, grail_node_say_batch)

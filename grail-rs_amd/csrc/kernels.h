@@ -180,4 +180,15 @@ hipError_t launch_loudness_hops(const float *rows, uint64_t row_stride, const ui
 hipError_t launch_loudness_gate(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t hop, const double *hops,
                                 uint64_t hops_stride, double *gated, hipStream_t stream);
 
+// true peak (true_peak_kernels.hip): one wave per (row, chunk of output times), grid_chunks =
+// true_peak_grid_chunks(row_stride) of them per row; per chunk the largest |y| of the 4x oversampling filter and the
+// count of non-finite samples at [row * grid_chunks + c] (chunks past a row's last are left unwritten)
+uint64_t true_peak_grid_chunks(uint64_t row_stride);
+hipError_t launch_true_peak_frames(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows,
+                                   uint32_t grid_chunks, double *cmax, uint32_t *cbad, hipStream_t stream);
+// ... and a row's true peak and count from them, one lane per row (outputs may be NULL)
+hipError_t launch_true_peak_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, const double *cmax,
+                                   const uint32_t *cbad, uint32_t grid_chunks, double *true_peak, uint32_t *nonfinite,
+                                   hipStream_t stream);
+
 }  // namespace grail

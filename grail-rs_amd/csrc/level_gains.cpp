@@ -1,11 +1,13 @@
 // level_gains.cpp — the host side of levels that needs no device: grail_level_gains (a row's numbers and a target level
 // per item -> the item's gain), grail_active_level (a row's level over its active frames) and the host side of the
-// K-weighted loudness: grail_kweighting, grail_gated_mean_square, grail_loudness_lufs, grail_loudness_level.  No HIP call,
-// so it builds with g++ under AddressSanitizer and UBSan (tests/test_levels_host.py, tests/test_loudness_host.py), as
-// mix_plan.cpp does.  DESIGN.md §4.9, §4.10.
+// K-weighted loudness: grail_kweighting, grail_gated_mean_square, grail_loudness_lufs, grail_loudness_level; and of the
+// true peak: grail_true_peak_coefficients, grail_true_peak_db, grail_true_peak_limit_gains.  No HIP call, so it builds
+// with g++ under AddressSanitizer and UBSan (tests/test_levels_host.py, tests/test_loudness_host.py,
+// tests/test_true_peak_host.py), as mix_plan.cpp does.  DESIGN.md §4.9, §4.10, §4.11.
 #include <cmath>
 
 #include "../../include/grail_hip.h"
+#include "true_peak_taps.h"
 
 extern "C" {
 
@@ -127,5 +129,42 @@ double grail_loudness_lufs(double gated_ms)
 }
 
 double grail_loudness_level(double gated_ms) { return std::sqrt(gated_ms * GRAIL_LOUDNESS_LEVEL_SCALE); }
+
+int grail_true_peak_coefficients(double coef[GRAIL_TRUE_PEAK_PHASES * GRAIL_TRUE_PEAK_TAPS])
+{
+    if (!coef) return GRAIL_ERR_INVALID_ARG;
+    for (int p = 0; p < GRAIL_TRUE_PEAK_PHASES; ++p)
+        for (int k = 0; k < GRAIL_TRUE_PEAK_TAPS; ++k) coef[p * GRAIL_TRUE_PEAK_TAPS + k] = grail::true_peak_tap(p, k);
+    return GRAIL_OK;
+}
+
+double grail_true_peak_db(double true_peak)
+{
+    if (true_peak == 0.0) return -HUGE_VAL;
+    if (!(true_peak > 0.0)) return std::nan("");        // (no true peak is negative; a NaN stays one)
+    return 20.0 * std::log10(true_peak);
+}
+
+int grail_true_peak_limit_gains(const double *true_peak, uint32_t n_rows, const uint32_t *item_rows, uint32_t n_items,
+                                float ceiling_db, float *item_gains, uint32_t *n_limited)
+{
+    if (!std::isfinite(ceiling_db)) return GRAIL_ERR_INVALID_ARG;
+    if (n_items && (!true_peak || !item_rows || !item_gains)) return GRAIL_ERR_INVALID_ARG;
+    for (uint32_t i = 0; i < n_items; ++i)
+        if (item_rows[i] >= n_rows) return GRAIL_ERR_INVALID_ARG;          // (before the first gain is written)
+    const double c = std::pow(10.0, (double)ceiling_db / 20.0);
+    uint32_t limited = 0;
+    for (uint32_t i = 0; i < n_items; ++i) {
+        const double tp = true_peak[item_rows[i]];
+        const float g = item_gains[i];
+        if (!(tp > 0.0) || !((double)std::fabs(g) * tp > c)) continue;
+        float q = (float)(c / tp);
+        if ((double)q * tp > c) q = std::nextafterf(q, 0.0f);      // rounded up past the ceiling: one step back is under it
+        item_gains[i] = std::signbit(g) ? -q : q;
+        ++limited;
+    }
+    if (n_limited) *n_limited = limited;
+    return GRAIL_OK;
+}
 
 }  // extern "C"

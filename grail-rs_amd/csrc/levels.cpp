@@ -1,6 +1,7 @@
-// levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async and grail_loudness_async
-// (checks, the scratch, the launches) and what grail_batch_mix_leveled (mix.cpp) needs per block.  The kernels are
-// level_kernels.hip and loudness_kernels.hip, the gains are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10.
+// levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async and
+// grail_true_peak_async (checks, the scratch, the launches) and what grail_batch_mix_leveled and its _limited form
+// (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip and true_peak_kernels.hip, the gains
+// are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -8,7 +9,8 @@ using namespace grail::host;
 
 // Per context (grail_ctx::level_state), grown and never shrunk, freed by grail_destroy: the per-frame numbers that a
 // totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), one block's totals for the leveled mix, and the
-// hop sums of a loudness call that does not ask for them (8 B per hop of 100 ms).
+// hop sums of a loudness call that does not ask for them (8 B per hop of 100 ms), and the chunk maxima and counts that a
+// true-peak call folds (12 B per chunk of 4096 output times) with one block's true peaks for the limited mix.
 struct LevelState {
     double *d_fsum = nullptr;
     float *d_fpeak = nullptr;
@@ -20,6 +22,11 @@ struct LevelState {
     size_t cap_sumsq = 0, cap_peak = 0, cap_bad = 0;
     double *d_hops = nullptr;
     size_t cap_hops = 0;
+    double *d_cmax = nullptr;
+    uint32_t *d_cbad = nullptr;
+    size_t cap_cmax = 0, cap_cbad = 0;
+    double *d_tp = nullptr;
+    size_t cap_tp = 0;
 };
 
 namespace grail {
@@ -30,7 +37,7 @@ void levels_release(grail_ctx *ctx)
     LevelState *st = (LevelState *)ctx->level_state;
     if (!st) return;
     for (void *p : {(void *)st->d_fsum, (void *)st->d_fpeak, (void *)st->d_fbad, (void *)st->d_sumsq, (void *)st->d_peak,
-                    (void *)st->d_bad, (void *)st->d_hops})
+                    (void *)st->d_bad, (void *)st->d_hops, (void *)st->d_cmax, (void *)st->d_cbad, (void *)st->d_tp})
         if (p) (void)hipFree(p);
     delete st;
     ctx->level_state = nullptr;
@@ -136,6 +143,54 @@ int loudness(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t ro
     return GRAIL_OK;
 }
 
+// true peaks and non-finite counts (either output may be NULL) through the context's chunk scratch
+int true_peak(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+              uint32_t n_rows, double *true_peak_dev, uint32_t *nonfinite_dev)
+{
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    const uint64_t chunks = true_peak_grid_chunks(row_stride);
+    if (chunks > 0xFFFFFFFFull || (uint64_t)n_rows * chunks > (1ull << 32))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^32 chunks");
+    if (chunks) {               // (rows of no samples: +0.0, 0 from the totals alone)
+        const size_t cells = (size_t)n_rows * (size_t)chunks;
+        int rc;
+        if ((rc = reserve(ctx, &st->d_cmax, &st->cap_cmax, cells))) return rc;
+        if ((rc = reserve(ctx, &st->d_cbad, &st->cap_cbad, cells))) return rc;
+        const hipError_t e = launch_true_peak_frames(rows_dev, row_stride, len_dev, n_rows, (uint32_t)chunks, st->d_cmax,
+                                                     st->d_cbad, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "true peak frames kernel launch");
+    }
+    const hipError_t e = launch_true_peak_totals(len_dev, row_stride, n_rows, st->d_cmax, st->d_cbad, (uint32_t)chunks,
+                                                 true_peak_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "true peak totals kernel launch");
+    return GRAIL_OK;
+}
+
+// grail_batch_mix_leveled_limited's part of a block, first half: the rows' true peaks queued behind the level's kernels
+// and their copy to tp[n_rows] on the host, complete once the caller has waited for the stream (8 bytes a row more)
+int queue_block_true_peaks(grail_ctx *ctx, LevelState *st, const float *rows_dev, uint64_t row_stride,
+                           const uint32_t *len_dev, uint32_t n_rows, double *tp)
+{
+    int rc;
+    if ((rc = reserve(ctx, &st->d_tp, &st->cap_tp, n_rows))) return rc;
+    if ((rc = true_peak(ctx, "grail_batch_mix_leveled_limited", rows_dev, row_stride, len_dev, n_rows, st->d_tp, nullptr)))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(tp, st->d_tp, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    return GRAIL_OK;
+}
+
+// ... second half: the ceiling applied to the gains that grail_level_gains gave; *n_limited is added to
+int limit_block_gains(const double *tp, uint32_t n_rows, const uint32_t *item_rows, uint32_t n_items, float ceiling_db,
+                      float *gains, uint32_t *n_limited)
+{
+    uint32_t limited = 0;
+    const int rc = grail_true_peak_limit_gains(tp, n_rows, item_rows, n_items, ceiling_db, gains, &limited);
+    if (rc) return fail(rc, "grail_batch_mix_leveled_limited: grail_true_peak_limit_gains refused the block");
+    *n_limited += limited;
+    return GRAIL_OK;
+}
+
 }  // namespace
 
 namespace grail {
@@ -156,12 +211,14 @@ uint32_t level_table_rate(const grail_ctx *ctx)
 
 int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const float *rows_dev, uint64_t row_stride,
                       const uint32_t *len_dev, const uint32_t *row_len, uint32_t n_rows, const uint32_t *item_rows,
-                      const float *item_level_db, uint32_t n_items, float *gains, uint32_t *n_unleveled)
+                      const float *item_level_db, uint32_t n_items, float *gains, uint32_t *n_unleveled,
+                      const float *ceiling_db, uint32_t *n_limited)
 {
     LevelState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
     if (n_rows == 0 || n_items == 0) return GRAIL_OK;
     int rc;
+    std::vector<double> tp(ceiling_db ? n_rows : 0);      // with a ceiling: the rows' true peaks, brought back in the same wait
     if ((rc = reserve(ctx, &st->d_sumsq, &st->cap_sumsq, n_rows))) return rc;
     if ((rc = reserve(ctx, &st->d_peak, &st->cap_peak, n_rows))) return rc;
     if ((rc = reserve(ctx, &st->d_bad, &st->cap_bad, n_rows))) return rc;
@@ -169,6 +226,7 @@ int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const floa
         if ((rc = loudness(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, sample_rate, nullptr,
                            st->d_sumsq, nullptr, 0, st->d_bad)))
             return rc;
+        if (ceiling_db && (rc = queue_block_true_peaks(ctx, st, rows_dev, row_stride, len_dev, n_rows, tp.data()))) return rc;
         std::vector<double> gated(n_rows), level(n_rows);
         std::vector<uint32_t> bad(n_rows);
         HIP_TRY(hipMemcpyAsync(gated.data(), st->d_sumsq, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -180,10 +238,11 @@ int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const floa
                                n_items, gains, &unleveled);
         if (rc) return fail(rc, "grail_batch_mix_leveled: grail_level_gains refused the block");
         *n_unleveled += unleveled;
-        return GRAIL_OK;
+        return ceiling_db ? limit_block_gains(tp.data(), n_rows, item_rows, n_items, *ceiling_db, gains, n_limited) : GRAIL_OK;
     }
     if ((rc = totals(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, st->d_sumsq, st->d_peak, st->d_bad)))
         return rc;
+    if (ceiling_db && (rc = queue_block_true_peaks(ctx, st, rows_dev, row_stride, len_dev, n_rows, tp.data()))) return rc;
     std::vector<double> sumsq(n_rows), active;
     std::vector<float> peak(n_rows);
     std::vector<uint32_t> bad(n_rows);
@@ -211,7 +270,7 @@ int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const floa
                            item_level_db, n_items, gains, &unleveled);
     if (rc) return fail(rc, "grail_batch_mix_leveled: grail_level_gains refused the block");
     *n_unleveled += unleveled;
-    return GRAIL_OK;
+    return ceiling_db ? limit_block_gains(tp.data(), n_rows, item_rows, n_items, *ceiling_db, gains, n_limited) : GRAIL_OK;
 }
 
 }  // namespace host
@@ -228,6 +287,17 @@ int grail_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_strid
     if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_levels_async: NULL buffer");
     if (!sumsq_dev && !peak_dev && !nonfinite_dev) return GRAIL_OK;
     return totals(ctx, "grail_levels_async", rows_dev, row_stride, len_dev, n_rows, sumsq_dev, peak_dev, nonfinite_dev);
+}
+
+int grail_true_peak_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                          uint32_t n_rows, double *true_peak_dev, uint32_t *nonfinite_dev)
+{
+    int rc = bind_device(ctx, "grail_true_peak_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_true_peak_async: NULL buffer");
+    if (!true_peak_dev && !nonfinite_dev) return GRAIL_OK;
+    return true_peak(ctx, "grail_true_peak_async", rows_dev, row_stride, len_dev, n_rows, true_peak_dev, nonfinite_dev);
 }
 
 int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,

@@ -123,12 +123,13 @@ int mix_rows(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t ro
 
 // grail_batch_mix after bind(), and grail_batch_mix_leveled: with item_level_db the gains are not given but derived per
 // block, between its rendering and its mix, from the block's measured rows (levels.cpp: one small copy and one wait per
-// block); they are returned through gains_out / n_unleveled once everything has succeeded
+// block); they are returned through gains_out / n_unleveled once everything has succeeded.  With ceiling_db
+// (grail_batch_mix_leveled_limited) each block's true peaks are measured too and cap its gains; n_limited as n_unleveled.
 int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const uint32_t *item_rows,
               const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_gains,
               const float *item_level_db, int mode, uint32_t n_items, float *tracks_dev, uint64_t track_stride,
               uint32_t n_tracks, uint64_t track_len, uint32_t *out_len, float *gains_out, uint32_t *n_unleveled,
-              uint32_t flags)
+              const float *ceiling_db, uint32_t *n_limited, uint32_t flags)
 {
     int rc;
     if ((rc = check_ready(ctx, batch))) return rc;
@@ -138,7 +139,7 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
         return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": GRAIL_LEVEL_LOUDNESS needs voices of one whole-numbered "
                                                               "sample rate within 2 560 .. 1 048 576");
     std::vector<float> level_gains(leveled ? n_items : 0);
-    uint32_t unleveled = 0;
+    uint32_t unleveled = 0, limited = 0;
     const uint32_t n = batch->n_utt;
     // the items' checks before anything is rendered (the plan repeats them per block, with the rows' lengths)
     if (n_items && (!item_rows || !item_offsets)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": item_rows or item_offsets is NULL");
@@ -155,6 +156,7 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
                       track_stride, n_tracks, track_len, flags);
         const int sync_rc = grail_sync(ctx);
         if (!rc && !sync_rc && leveled && n_unleveled) *n_unleveled = 0;
+        if (!rc && !sync_rc && ceiling_db && n_limited) *n_limited = 0;
         return rc ? rc : sync_rc;
     }
     std::vector<uint32_t> lens(n);
@@ -193,7 +195,7 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
             rc = synthesize_rows(ctx, batch, d_rows, nullptr, stride, d_len);      // = grail_batch_synthesize_async
             if (!rc && leveled) {
                 rc = level_block_gains(ctx, mode, level_rate, d_rows, stride, d_len, lens.data(), n, item_rows, item_level_db,
-                                       n_items, level_gains.data(), &unleveled);
+                                       n_items, level_gains.data(), &unleveled, ceiling_db, &limited);
                 item_gains = level_gains.data();
             }
             if (!rc)
@@ -219,7 +221,8 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
         if (leveled) {
             sub_gains.assign(sub_rows.size(), 0.0f);
             rc = level_block_gains(ctx, mode, level_rate, d_rows, stride, d_len, lens.data() + first, count, sub_rows.data(),
-                                   sub_levels.data(), (uint32_t)sub_rows.size(), sub_gains.data(), &unleveled);
+                                   sub_levels.data(), (uint32_t)sub_rows.size(), sub_gains.data(), &unleveled, ceiling_db,
+                                   &limited);
             if (rc) break;
             for (size_t k = 0; k < of_block[b].size(); ++k) level_gains[of_block[b][k]] = sub_gains[k];
         }
@@ -234,7 +237,32 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
     if (out_len) std::memcpy(out_len, lens.data(), (size_t)n * sizeof(uint32_t));
     if (leveled && gains_out && n_items) std::memcpy(gains_out, level_gains.data(), (size_t)n_items * sizeof(float));
     if (leveled && n_unleveled) *n_unleveled = unleveled;
+    if (ceiling_db && n_limited) *n_limited = limited;
     return GRAIL_OK;
+}
+
+// grail_batch_mix_leveled and grail_batch_mix_leveled_limited (ceiling_db: NULL = no ceiling)
+int mix_leveled(const char *who, grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_level_db, int mode,
+                uint32_t n_items, float *tracks_dev, uint64_t track_stride, uint32_t n_tracks, uint64_t track_len,
+                uint32_t *out_len, float *item_gains_out, uint32_t *n_unleveled, const float *ceiling_db,
+                uint32_t *n_limited, uint32_t flags)
+{
+    if (!ctx) {                 // (no context can exist without a device: say which of the two it is)
+        int n = 0;
+        if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+            return fail(GRAIL_ERR_NO_DEVICE, std::string(who) + ": no usable HIP device (there is no CPU fallback)");
+    }
+    int rc = bind(ctx);
+    if (rc) return rc;
+    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE && mode != GRAIL_LEVEL_LOUDNESS)
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": unknown mode");
+    if (ceiling_db && !std::isfinite(*ceiling_db)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": ceiling_db is not finite");
+    static const float none = 0.0f;
+    if (n_items && !item_level_db) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": item_level_db is NULL");
+    return batch_mix(ctx, who, batch, item_rows, item_tracks, item_offsets, nullptr, item_level_db ? item_level_db : &none,
+                     mode, n_items, tracks_dev, track_stride, n_tracks, track_len, out_len, item_gains_out, n_unleveled,
+                     ceiling_db, n_limited, flags);
 }
 
 }  // namespace
@@ -261,7 +289,7 @@ int grail_batch_mix(grail_ctx *ctx, const grail_batch *batch, const uint32_t *it
     int rc = bind(ctx);
     if (rc) return rc;
     return batch_mix(ctx, "grail_batch_mix", batch, item_rows, item_tracks, item_offsets, item_gains, nullptr, 0, n_items,
-                     tracks_dev, track_stride, n_tracks, track_len, out_len, nullptr, nullptr, flags);
+                     tracks_dev, track_stride, n_tracks, track_len, out_len, nullptr, nullptr, nullptr, nullptr, flags);
 }
 
 int grail_batch_mix_leveled(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
@@ -270,20 +298,20 @@ int grail_batch_mix_leveled(grail_ctx *ctx, const grail_batch *batch, const uint
                             uint64_t track_len, uint32_t *out_len, float *item_gains_out, uint32_t *n_unleveled,
                             uint32_t flags)
 {
-    if (!ctx) {                 // (no context can exist without a device: say which of the two it is)
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
-            return fail(GRAIL_ERR_NO_DEVICE, "grail_batch_mix_leveled: no usable HIP device (there is no CPU fallback)");
-    }
-    int rc = bind(ctx);
-    if (rc) return rc;
-    if (mode != GRAIL_LEVEL_PEAK && mode != GRAIL_LEVEL_RMS && mode != GRAIL_LEVEL_ACTIVE && mode != GRAIL_LEVEL_LOUDNESS)
-        return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix_leveled: unknown mode");
-    static const float none = 0.0f;
-    if (n_items && !item_level_db) return fail(GRAIL_ERR_INVALID_ARG, "grail_batch_mix_leveled: item_level_db is NULL");
-    return batch_mix(ctx, "grail_batch_mix_leveled", batch, item_rows, item_tracks, item_offsets, nullptr,
-                     item_level_db ? item_level_db : &none, mode, n_items, tracks_dev, track_stride, n_tracks, track_len,
-                     out_len, item_gains_out, n_unleveled, flags);
+    return mix_leveled("grail_batch_mix_leveled", ctx, batch, item_rows, item_tracks, item_offsets, item_level_db, mode,
+                       n_items, tracks_dev, track_stride, n_tracks, track_len, out_len, item_gains_out, n_unleveled, nullptr,
+                       nullptr, flags);
+}
+
+int grail_batch_mix_leveled_limited(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                                    const uint32_t *item_tracks, const uint64_t *item_offsets, const float *item_level_db,
+                                    int mode, uint32_t n_items, float *tracks_dev, uint64_t track_stride,
+                                    uint32_t n_tracks, uint64_t track_len, uint32_t *out_len, float *item_gains_out,
+                                    uint32_t *n_unleveled, float ceiling_db, uint32_t *n_limited, uint32_t flags)
+{
+    return mix_leveled("grail_batch_mix_leveled_limited", ctx, batch, item_rows, item_tracks, item_offsets, item_level_db,
+                       mode, n_items, tracks_dev, track_stride, n_tracks, track_len, out_len, item_gains_out, n_unleveled,
+                       &ceiling_db, n_limited, flags);
 }
 
 int grail_pcm16_frames_async(grail_ctx *ctx, const float *tracks_dev, uint64_t track_stride,

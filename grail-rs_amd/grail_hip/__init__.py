@@ -76,6 +76,8 @@ EXPORTS = [
     "grail_wav_write_i16_frames",
     "grail_levels_async", "grail_frame_levels_async", "grail_level_gains", "grail_active_level", "grail_batch_mix_leveled",
     "grail_kweighting", "grail_loudness_async", "grail_gated_mean_square", "grail_loudness_lufs", "grail_loudness_level",
+    "grail_true_peak_coefficients", "grail_true_peak_async", "grail_true_peak_db", "grail_true_peak_limit_gains",
+    "grail_batch_mix_leveled_limited",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -85,6 +87,7 @@ LEVEL_LOUDNESS = 4               # GRAIL_LEVEL_LOUDNESS: level = loudness_level(
 LOUDNESS_ABS_GATE = 1.1724653045822981e-07      # GRAIL_LOUDNESS_ABS_GATE: the mean square of -70 LUFS
 LOUDNESS_LEVEL_SCALE = 0.8529037030705663       # GRAIL_LOUDNESS_LEVEL_SCALE: 10^(-0.691 / 10)
 LOUDNESS_RATE_MIN, LOUDNESS_RATE_MAX = 2560, 1048576
+TRUE_PEAK_PHASES, TRUE_PEAK_TAPS = 4, 12        # GRAIL_TRUE_PEAK_*: the 4x oversampling filter of BS.1770-4 Annex 2
 
 
 class GrailError(RuntimeError):
@@ -345,6 +348,13 @@ def load():
     L.grail_loudness_lufs.restype = C.c_double
     L.grail_loudness_level.argtypes = [C.c_double]
     L.grail_loudness_level.restype = C.c_double
+    L.grail_true_peak_coefficients.argtypes = [vp]
+    L.grail_true_peak_async.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp]
+    L.grail_true_peak_db.argtypes = [C.c_double]
+    L.grail_true_peak_db.restype = C.c_double
+    L.grail_true_peak_limit_gains.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_float, vp, vp]
+    L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
+                                                  vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
     return L
 
@@ -655,6 +665,31 @@ def loudness_level(gated_ms):
     return float(load().grail_loudness_level(float(gated_ms)))
 
 
+def true_peak_coefficients():
+    """grail_true_peak_coefficients (pure host): the 4 x 12 taps of the BS.1770-4 Annex 2 filter, float64[4, 12]."""
+    coef = np.full((TRUE_PEAK_PHASES, TRUE_PEAK_TAPS), np.nan, dtype=np.float64)
+    _check(load().grail_true_peak_coefficients(coef.ctypes.data))
+    return coef
+
+
+def true_peak_db(true_peak):
+    """grail_true_peak_db: 20 log10(true peak) in dBTP; -inf for 0."""
+    return float(load().grail_true_peak_db(float(true_peak)))
+
+
+def true_peak_limit_gains(true_peak, item_rows, item_gains, ceiling_db, n_rows=None):
+    """grail_true_peak_limit_gains (pure host): the gains capped so that |gain| * true_peak[row] <= 10^(ceiling_db / 20).
+    Returns (gains float32[n_items], a copy; n_limited: the items that were changed)."""
+    tp = np.ascontiguousarray(true_peak, dtype=np.float64)
+    rows = np.ascontiguousarray(item_rows, dtype=np.uint32)
+    gains = np.array(item_gains, dtype=np.float32, ndmin=1)
+    assert len(gains) == len(rows)
+    n_limited = C.c_uint32(0xFFFFFFFF)
+    _check(load().grail_true_peak_limit_gains(tp.ctypes.data, len(tp) if n_rows is None else n_rows, rows.ctypes.data,
+                                              len(rows), float(ceiling_db), gains.ctypes.data, C.addressof(n_limited)))
+    return gains, n_limited.value
+
+
 class Batch:
     def __init__(self, ctx, handle, n_utt):
         self.ctx, self.handle, self.n_utt = ctx, handle, n_utt
@@ -688,17 +723,36 @@ class Batch:
                     item_tracks=None, mode=LEVEL_RMS, accumulate=False):
         """grail_batch_mix_leveled: mix() with a level in dB per item instead of a gain; every block's rows are measured on
         the device between rendering and mixing.  Returns (the rows' lengths, the gains used, n_unleveled)."""
+        return self._mix_leveled(item_rows, item_offsets, item_level_db, tracks_dev, track_stride, n_tracks, track_len,
+                                 item_tracks, mode, accumulate, None)[:3]
+
+    def mix_leveled_limited(self, item_rows, item_offsets, item_level_db, tracks_dev, track_stride, n_tracks, track_len,
+                            ceiling_db, item_tracks=None, mode=LEVEL_RMS, accumulate=False):
+        """grail_batch_mix_leveled_limited: mix_leveled() under a true-peak ceiling in dBTP; the rows' true peaks are
+        measured too and cap the gains.  Returns (the rows' lengths, the gains used, n_unleveled, n_limited)."""
+        return self._mix_leveled(item_rows, item_offsets, item_level_db, tracks_dev, track_stride, n_tracks, track_len,
+                                 item_tracks, mode, accumulate, float(ceiling_db))
+
+    def _mix_leveled(self, item_rows, item_offsets, item_level_db, tracks_dev, track_stride, n_tracks, track_len, item_tracks,
+                     mode, accumulate, ceiling_db):
         rows, offs, tracks, _ = _mix_items(item_rows, item_offsets, item_tracks, None)
         db = np.ascontiguousarray(item_level_db, dtype=np.float32)
         assert len(db) == len(rows)
         out_len = np.zeros(max(self.n_utt, 1), dtype=np.uint32)
         gains = np.zeros(max(len(rows), 1), dtype=np.float32)
-        n_unleveled = C.c_uint32(0)
-        _check(load().grail_batch_mix_leveled(self.ctx.handle, self.handle, rows.ctypes.data, _ptr(tracks), offs.ctypes.data,
-                                              db.ctypes.data, int(mode), len(rows), tracks_dev, track_stride, n_tracks,
-                                              track_len, out_len.ctypes.data, gains.ctypes.data, C.addressof(n_unleveled),
-                                              MIX_ACCUMULATE if accumulate else 0))
-        return out_len[:self.n_utt], gains[:len(rows)], n_unleveled.value
+        n_unleveled, n_limited = C.c_uint32(0), C.c_uint32(0)
+        flags = MIX_ACCUMULATE if accumulate else 0
+        if ceiling_db is None:
+            _check(load().grail_batch_mix_leveled(self.ctx.handle, self.handle, rows.ctypes.data, _ptr(tracks), offs.ctypes.data,
+                                                  db.ctypes.data, int(mode), len(rows), tracks_dev, track_stride, n_tracks,
+                                                  track_len, out_len.ctypes.data, gains.ctypes.data, C.addressof(n_unleveled),
+                                                  flags))
+        else:
+            _check(load().grail_batch_mix_leveled_limited(
+                self.ctx.handle, self.handle, rows.ctypes.data, _ptr(tracks), offs.ctypes.data, db.ctypes.data, int(mode),
+                len(rows), tracks_dev, track_stride, n_tracks, track_len, out_len.ctypes.data, gains.ctypes.data,
+                C.addressof(n_unleveled), ceiling_db, C.addressof(n_limited), flags))
+        return out_len[:self.n_utt], gains[:len(rows)], n_unleveled.value, n_limited.value
 
     def free(self):
         if self.handle:
@@ -1012,6 +1066,27 @@ class Context:
             for p in d:
                 self.device_free(p)
         return gated[:n_rows], (hop_sumsq[:n_rows] if hops else None), bad[:n_rows]
+
+    def true_peak_async(self, rows_dev, row_stride, len_dev, n_rows, true_peak_dev=None, nonfinite_dev=None):
+        """grail_true_peak_async: per row the true peak (4x oversampled, BS.1770-4 Annex 2) and the count of non-finite
+        samples, into DEVICE arrays [n_rows] (either may be None), queued on the context's stream."""
+        _check(load().grail_true_peak_async(self.handle, rows_dev, row_stride, len_dev, n_rows, true_peak_dev,
+                                            nonfinite_dev))
+
+    def true_peak(self, rows_dev, row_stride, len_dev, n_rows):
+        """true_peak_async, waited for and copied back: (true_peak float64, nonfinite uint32), one per row."""
+        tp = np.zeros(max(n_rows, 1), dtype=np.float64)
+        bad = np.zeros(max(n_rows, 1), dtype=np.uint32)
+        d = [self.device_alloc(max(n_rows, 1) * k) for k in (8, 4)]
+        try:
+            self.true_peak_async(rows_dev, row_stride, len_dev, n_rows, *d)
+            for dst, src in zip((tp, bad), d):
+                self.d2h(dst, src, n_rows * dst.itemsize)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return tp[:n_rows], bad[:n_rows]
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max |x|, non-finite counts) per row, computed on the device."""

@@ -259,6 +259,16 @@ extern "C" {
     pub fn grail_gated_mean_square(hop_sumsq: *const f64, n_hops: u32, hop: u32) -> f64;
     pub fn grail_loudness_lufs(gated_ms: f64) -> f64;
     pub fn grail_loudness_level(gated_ms: f64) -> f64;
+    pub fn grail_true_peak_coefficients(coef: *mut f64) -> c_int;
+    pub fn grail_true_peak_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, true_peak_dev: *mut f64, nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_true_peak_db(true_peak: f64) -> f64;
+    pub fn grail_true_peak_limit_gains(true_peak: *const f64, n_rows: u32, item_rows: *const u32, n_items: u32,
+        ceiling_db: f32, item_gains: *mut f32, n_limited: *mut u32) -> c_int;
+    pub fn grail_batch_mix_leveled_limited(ctx: *mut grail_ctx, batch: *const grail_batch, item_rows: *const u32,
+        item_tracks: *const u32, item_offsets: *const u64, item_level_db: *const f32, mode: c_int, n_items: u32,
+        tracks_dev: *mut f32, track_stride: u64, n_tracks: u32, track_len: u64, out_len: *mut u32,
+        item_gains_out: *mut f32, n_unleveled: *mut u32, ceiling_db: f32, n_limited: *mut u32, flags: u32) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

@@ -333,6 +333,27 @@ impl Gpu {
     pub fn mix_leveled<I: IntoIterator<Item = Utterance>>(&self, utterances: I, placements: &[Placement], level_db: &[f32],
                                                          mode: LevelMode, n_tracks: u32, track_len: u64)
                                                          -> Result<(Vec<Vec<f32>>, Vec<f32>, u32), Error> {
+        let (tracks, gains, unleveled, _) = self.mix_leveled_with(utterances, placements, level_db, mode, None, n_tracks,
+                                                                  track_len)?;
+        Ok((tracks, gains, unleveled))
+    }
+
+    /// [`Gpu::mix_leveled`] under a true-peak ceiling in dBTP (`grail_batch_mix_leveled_limited`): every utterance's true
+    /// peak is measured on the device as well, and a gain that would bring it above the ceiling is cut back to it.  The
+    /// ceiling binds each placement; placements that overlap on a track can still sum above it ([`Gpu::true_peak`] of the
+    /// finished tracks tells).  Returns the tracks, the gains that were used, the placements that got gain 0 and the
+    /// placements that the ceiling changed.
+    pub fn mix_leveled_limited<I: IntoIterator<Item = Utterance>>(&self, utterances: I, placements: &[Placement],
+                                                                 level_db: &[f32], mode: LevelMode, ceiling_db: f32,
+                                                                 n_tracks: u32, track_len: u64)
+                                                                 -> Result<(Vec<Vec<f32>>, Vec<f32>, u32, u32), Error> {
+        self.mix_leveled_with(utterances, placements, level_db, mode, Some(ceiling_db), n_tracks, track_len)
+    }
+
+    fn mix_leveled_with<I: IntoIterator<Item = Utterance>>(&self, utterances: I, placements: &[Placement], level_db: &[f32],
+                                                          mode: LevelMode, ceiling_db: Option<f32>, n_tracks: u32,
+                                                          track_len: u64)
+                                                          -> Result<(Vec<Vec<f32>>, Vec<f32>, u32, u32), Error> {
         assert_eq!(level_db.len(), placements.len());
         let b = FlatBatch::new(utterances);
         let rows: Vec<u32> = placements.iter().map(|p| p.utterance).collect();
@@ -343,6 +364,7 @@ impl Gpu {
         let mut host = vec![0f32; floats];
         let mut gains = vec![0f32; rows.len().max(1)];
         let mut unleveled = 0u32;
+        let mut limited = 0u32;
         unsafe {
             let mut h = std::ptr::null_mut();
             check(sys::grail_batch_upload(self.ctx, b.segs.as_ptr(), b.offs.as_ptr(), b.vids.as_ptr(), b.seeds.as_ptr(),
@@ -350,10 +372,18 @@ impl Gpu {
             let mut d: *mut std::ffi::c_void = std::ptr::null_mut();
             let mut r = check(sys::grail_device_alloc(self.ctx, floats * 4 + 4, &mut d));
             if r.is_ok() {
-                r = check(sys::grail_batch_mix_leveled(self.ctx, h, rows.as_ptr(), tracks.as_ptr(), offsets.as_ptr(),
-                                                       level_db.as_ptr(), mode as std::os::raw::c_int, rows.len() as u32,
-                                                       d as *mut f32, stride, n_tracks, track_len, std::ptr::null_mut(),
-                                                       gains.as_mut_ptr(), &mut unleveled, 0));
+                r = check(match ceiling_db {
+                    None => sys::grail_batch_mix_leveled(self.ctx, h, rows.as_ptr(), tracks.as_ptr(), offsets.as_ptr(),
+                                                         level_db.as_ptr(), mode as std::os::raw::c_int, rows.len() as u32,
+                                                         d as *mut f32, stride, n_tracks, track_len, std::ptr::null_mut(),
+                                                         gains.as_mut_ptr(), &mut unleveled, 0),
+                    Some(c) => sys::grail_batch_mix_leveled_limited(self.ctx, h, rows.as_ptr(), tracks.as_ptr(),
+                                                                    offsets.as_ptr(), level_db.as_ptr(),
+                                                                    mode as std::os::raw::c_int, rows.len() as u32,
+                                                                    d as *mut f32, stride, n_tracks, track_len,
+                                                                    std::ptr::null_mut(), gains.as_mut_ptr(), &mut unleveled,
+                                                                    c, &mut limited, 0),
+                });
             }
             if r.is_ok() {
                 r = check(sys::grail_memcpy_d2h(self.ctx, host.as_mut_ptr() as *mut std::ffi::c_void, d, floats * 4));
@@ -365,7 +395,59 @@ impl Gpu {
             r?;
         }
         gains.truncate(rows.len());
-        Ok((host.chunks(stride as usize).map(|t| t[..track_len as usize].to_vec()).collect(), gains, unleveled))
+        Ok((host.chunks(stride as usize).map(|t| t[..track_len as usize].to_vec()).collect(), gains, unleveled, limited))
+    }
+
+    /// True peak of rows of samples, measured on the device (`grail_true_peak_async`; the contract is the header's section
+    /// "levels, continued: true peak"): per row the largest magnitude of the row oversampled four times by the filter of
+    /// BS.1770-4 Annex 2 (see [`true_peak_db`]) and the count of non-finite samples.  Time is parallel: one long row fills
+    /// the device.
+    pub fn true_peak(&self, rows: &[Vec<f32>]) -> Result<(Vec<f64>, Vec<u32>), Error> {
+        let n = rows.len();
+        let mut peaks = vec![0f64; n];
+        let mut bad = vec![0u32; n];
+        if n == 0 {
+            return Ok((peaks, bad));
+        }
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 4] = [std::ptr::null_mut(); 4];
+            let sizes = [n * stride * 4, n * 4, n * 8, n * 4];
+            let mut r = Ok(());
+            for k in 0..4 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[1], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_true_peak_async(self.ctx, d[0] as *const f32, stride as u64, d[1] as *const u32, n as u32,
+                                                     d[2] as *mut f64, d[3] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, peaks.as_mut_ptr() as *mut std::ffi::c_void, d[2], n * 8));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((peaks, bad))
     }
 
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
@@ -441,6 +523,30 @@ pub fn loudness_lufs(gated_ms: f64) -> f64 {
 /// The level whose 20 log10 is the loudness in LUFS (`grail_loudness_level`).
 pub fn loudness_level(gated_ms: f64) -> f64 {
     unsafe { sys::grail_loudness_level(gated_ms) }
+}
+
+/// The 4 x 12 taps of the true-peak filter, `[phase][tap]` (`grail_true_peak_coefficients`; pure host, no GPU).
+pub fn true_peak_coefficients() -> Result<[[f64; 12]; 4], Error> {
+    let mut coef = [[0f64; 12]; 4];
+    check(unsafe { sys::grail_true_peak_coefficients(coef.as_mut_ptr() as *mut f64) })?;
+    Ok(coef)
+}
+
+/// A true peak in dBTP (`grail_true_peak_db`): 20 log10, negative infinity for 0.
+pub fn true_peak_db(true_peak: f64) -> f64 {
+    unsafe { sys::grail_true_peak_db(true_peak) }
+}
+
+/// Caps `gains` so that no item's row exceeds `ceiling_db` dBTP (`grail_true_peak_limit_gains`; pure host): item `i`
+/// plays row `item_rows[i]`.  Returns the number of gains that were changed.
+pub fn true_peak_limit_gains(true_peak: &[f64], item_rows: &[u32], ceiling_db: f32, gains: &mut [f32]) -> Result<u32, Error> {
+    assert_eq!(item_rows.len(), gains.len());
+    let mut limited = 0u32;
+    check(unsafe {
+        sys::grail_true_peak_limit_gains(true_peak.as_ptr(), true_peak.len() as u32, item_rows.as_ptr(),
+                                         item_rows.len() as u32, ceiling_db, gains.as_mut_ptr(), &mut limited)
+    })?;
+    Ok(limited)
 }
 
 /// What "level" means to [`Gpu::mix_leveled`] (GRAIL_LEVEL_PEAK / _RMS / _ACTIVE / _LOUDNESS: targets then in LUFS).

@@ -93,6 +93,13 @@ struct Loudness {
     double lufs(size_t row) const { return grail_loudness_lufs(gated_ms[row]); }
 };
 
+// What Gpu::true_peak measures, one entry per row (grail_true_peak_async)
+struct TruePeak {
+    std::vector<double> true_peak;     // largest |y| of the row oversampled four times (BS.1770-4 Annex 2); 0 for an empty row
+    std::vector<uint32_t> nonfinite;   // NaN and Inf samples (they enter the filter as 0)
+    double db(size_t row) const { return grail_true_peak_db(true_peak[row]); }
+};
+
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
                     std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
@@ -261,38 +268,22 @@ public:
                                                 int mode = GRAIL_LEVEL_RMS, std::vector<float> *gains_used = nullptr,
                                                 uint32_t *unleveled = nullptr) const
     {
-        if (level_db.size() != placements.size())
-            throw Error(GRAIL_ERR_INVALID_ARG, "mix_leveled: one level per placement");
-        std::vector<PhonemeElem> segs;
-        std::vector<uint32_t> offs, vids, seeds, rows, tracks;
-        std::vector<uint64_t> at;
-        detail::flatten(utts, segs, offs, vids, seeds);
-        for (const Placement &p : placements) {
-            rows.push_back(p.utterance);
-            tracks.push_back(p.track);
-            at.push_back(p.offset);
-        }
-        const uint64_t stride = track_len ? (track_len + 63) / 64 * 64 : 64;
-        grail_batch *b = nullptr;
-        check(grail_batch_upload(ctx_, segs.data(), offs.data(), vids.data(), seeds.data(), (uint32_t)utts.size(), &b));
-        void *d = nullptr;
-        std::vector<float> flat((size_t)n_tracks * stride), gains(rows.size() ? rows.size() : 1);
-        uint32_t left_out = 0;
-        int rc = grail_device_alloc(ctx_, flat.size() * sizeof(float) + 4, &d);
-        if (!rc) rc = grail_batch_mix_leveled(ctx_, b, rows.data(), tracks.data(), at.data(), level_db.data(), mode,
-                                              (uint32_t)rows.size(), (float *)d, stride, n_tracks, track_len, nullptr,
-                                              gains.data(), &left_out, 0u);
-        if (!rc && !flat.empty()) rc = grail_memcpy_d2h(ctx_, flat.data(), d, flat.size() * sizeof(float));
-        if (d) grail_device_free(ctx_, d);
-        grail_batch_free(ctx_, b);
-        check(rc);
-        gains.resize(rows.size());
-        if (gains_used) *gains_used = gains;
-        if (unleveled) *unleveled = left_out;
-        std::vector<std::vector<float>> out(n_tracks);
-        for (uint32_t t = 0; t < n_tracks; ++t)
-            out[t].assign(flat.begin() + (size_t)t * stride, flat.begin() + (size_t)t * stride + track_len);
-        return out;
+        return mix_leveled_with(utts, placements, level_db, nullptr, n_tracks, track_len, mode, gains_used, unleveled, nullptr);
+    }
+
+    // Gpu::mix_leveled under a true-peak ceiling in dBTP (grail_batch_mix_leveled_limited): every utterance's true peak is
+    // measured too and a gain that would bring it above the ceiling is cut back to it; limited: how many placements that
+    // changed.  The ceiling binds each placement: placements that overlap on a track can still sum above it (Gpu::true_peak
+    // of the finished tracks tells).
+    std::vector<std::vector<float>> mix_leveled_limited(const std::vector<Utterance> &utts,
+                                                        const std::vector<Placement> &placements,
+                                                        const std::vector<float> &level_db, float ceiling_db,
+                                                        uint32_t n_tracks, uint64_t track_len, int mode = GRAIL_LEVEL_RMS,
+                                                        std::vector<float> *gains_used = nullptr,
+                                                        uint32_t *unleveled = nullptr, uint32_t *limited = nullptr) const
+    {
+        return mix_leveled_with(utts, placements, level_db, &ceiling_db, n_tracks, track_len, mode, gains_used, unleveled,
+                                limited);
     }
 
     // How loud rows of samples are, measured on the device (grail_levels_async; the contract is the header's section
@@ -362,6 +353,38 @@ public:
         return out;
     }
 
+    // True peak of rows of samples (rendered rows or finished tracks), measured on the device (grail_true_peak_async; the
+    // contract is the header's section "levels, continued: true peak").  Time is parallel: one long row fills the device.
+    TruePeak true_peak(const std::vector<std::vector<float>> &rows) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64;
+        TruePeak out;
+        out.true_peak.resize(n);
+        out.nonfinite.resize(n);
+        if (!n) return out;
+        std::vector<uint32_t> lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        void *d_rows = nullptr, *d_len = nullptr, *d_tp = nullptr, *d_bad = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 8, &d_tp);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_bad);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc) rc = grail_true_peak_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, (double *)d_tp,
+                                            (uint32_t *)d_bad);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.true_peak.data(), d_tp, (size_t)n * 8);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
+        for (void *p : {d_rows, d_len, d_tp, d_bad})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
     // Tracks of equal length as one multichannel WAV: interleaved i16 frames made on the device (grail_pcm16_frames_async,
     // the examples/cli.rs:49 conversion), then save_wav for as many channels (grail_wav_write_i16_frames).
     void save_wav_frames(const std::string &path, const std::vector<std::vector<float>> &tracks, uint32_t sample_rate) const
@@ -386,6 +409,53 @@ public:
     }
 
 private:
+    // mix_leveled (ceiling_db NULL) and mix_leveled_limited
+    std::vector<std::vector<float>> mix_leveled_with(const std::vector<Utterance> &utts, const std::vector<Placement> &placements,
+                                                     const std::vector<float> &level_db, const float *ceiling_db,
+                                                     uint32_t n_tracks, uint64_t track_len, int mode,
+                                                     std::vector<float> *gains_used, uint32_t *unleveled,
+                                                     uint32_t *limited) const
+    {
+        if (level_db.size() != placements.size())
+            throw Error(GRAIL_ERR_INVALID_ARG, "mix_leveled: one level per placement");
+        std::vector<PhonemeElem> segs;
+        std::vector<uint32_t> offs, vids, seeds, rows, tracks;
+        std::vector<uint64_t> at;
+        detail::flatten(utts, segs, offs, vids, seeds);
+        for (const Placement &p : placements) {
+            rows.push_back(p.utterance);
+            tracks.push_back(p.track);
+            at.push_back(p.offset);
+        }
+        const uint64_t stride = track_len ? (track_len + 63) / 64 * 64 : 64;
+        grail_batch *b = nullptr;
+        check(grail_batch_upload(ctx_, segs.data(), offs.data(), vids.data(), seeds.data(), (uint32_t)utts.size(), &b));
+        void *d = nullptr;
+        std::vector<float> flat((size_t)n_tracks * stride), gains(rows.size() ? rows.size() : 1);
+        uint32_t left_out = 0, cut = 0;
+        int rc = grail_device_alloc(ctx_, flat.size() * sizeof(float) + 4, &d);
+        if (!rc && ceiling_db)
+            rc = grail_batch_mix_leveled_limited(ctx_, b, rows.data(), tracks.data(), at.data(), level_db.data(), mode,
+                                                 (uint32_t)rows.size(), (float *)d, stride, n_tracks, track_len, nullptr,
+                                                 gains.data(), &left_out, *ceiling_db, &cut, 0u);
+        else if (!rc)
+            rc = grail_batch_mix_leveled(ctx_, b, rows.data(), tracks.data(), at.data(), level_db.data(), mode,
+                                         (uint32_t)rows.size(), (float *)d, stride, n_tracks, track_len, nullptr,
+                                         gains.data(), &left_out, 0u);
+        if (!rc && !flat.empty()) rc = grail_memcpy_d2h(ctx_, flat.data(), d, flat.size() * sizeof(float));
+        if (d) grail_device_free(ctx_, d);
+        grail_batch_free(ctx_, b);
+        check(rc);
+        gains.resize(rows.size());
+        if (gains_used) *gains_used = gains;
+        if (unleveled) *unleveled = left_out;
+        if (limited) *limited = cut;
+        std::vector<std::vector<float>> out(n_tracks);
+        for (uint32_t t = 0; t < n_tracks; ++t)
+            out[t].assign(flat.begin() + (size_t)t * stride, flat.begin() + (size_t)t * stride + track_len);
+        return out;
+    }
+
     grail_ctx *ctx_ = nullptr;
     std::vector<Voice> voices_;
 };

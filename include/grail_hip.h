@@ -749,6 +749,70 @@ double grail_loudness_level(double gated_ms);
  * grail_loudness_async's kernels and 12 bytes a row are copied.  A row whose gated mean square is 0 gets gain 0 and is
  * counted in *n_unleveled: that includes every row shorter than 400 ms. */
 
+/* ---- levels, continued: true peak (ITU-R BS.1770-4 Annex 2) ---------------------------------------------------------------
+ * The sample peak of grail_levels_async under-reads what a converter reconstructs between the samples (by 3 dB for a
+ * tone at a quarter of the rate, sampled 45 degrees off its crests).  The true peak is the largest magnitude of the row
+ * oversampled four times by the Annex's 48-tap filter, taken as four phases of twelve taps, C[p][k] = N[p][k] / 8192:
+ *     N[0] =   14,  90, -161, 272,  -487, 1125, 7964,  -838, 390, -218, 122,  -68
+ *     N[1] = -239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155
+ *     N[2] = N[1] reversed,  N[3] = N[0] reversed
+ * (the Annex's 48 coefficients as multiples of 2^-13; this table is the library's contract, at any sample rate: at 96 or
+ * 192 kHz the filter only looks closer than the standard asks).  All arithmetic is IEEE binary64.  For a row of
+ * n = min(len[u], row_stride) samples:
+ *   - v[t] = (double)x[t] for 0 <= t < n and +0.0 for t < 0 and t >= n; memory between n and row_stride is never looked
+ *     at, whatever it holds.  A sample that is not finite (|x| > FLT_MAX or NaN) is counted and enters as +0.0.
+ *   - For every output time t = 0 .. n + 10 and phase p = 0 .. 3: acc = +0.0; for k = 0 .. 11 ascending
+ *     acc = acc + C[p][k] * v[t - k]; y[p][t] = acc.  Every C[p][k] * v is exact in binary64 (a 13-bit numerator times a
+ *     24-bit significand), so a fused multiply-add and a multiply followed by an add give the same bits.
+ *   - The row's TRUE PEAK is the largest |y[p][t]| over all p and t, a double; +0.0 for an empty row.
+ *     dBTP = 20 log10(true peak).
+ * The eleven outputs after the row's last sample belong to the row: the filter rings on, and a mix places the row in front
+ * of silence (a row [0, ..., 0, 1.0] reads 7964 / 8192 with them and 239 / 8192 without).  A maximum is associative and
+ * commutative and no NaN is left to order, so the number is a pure function of the row's samples: not of row_stride, the
+ * alignment of rows_dev, the row's index, the number of rows, the device or the launch.  No float atomics.
+ * The Annex's phase 0 is no pass-through (its centre tap is 7964 / 8192 = 0.972), so a row's true peak can read up to
+ * about 0.25 dB BELOW its sample peak; a caller who wants the larger of the two has grail_levels_async. */
+#define GRAIL_TRUE_PEAK_PHASES 4
+#define GRAIL_TRUE_PEAK_TAPS   12
+/* Pure host: coef[p * 12 + k] = C[p][k].  GRAIL_ERR_INVALID_ARG for NULL. */
+int grail_true_peak_coefficients(double coef[48]);
+
+/* True peaks and non-finite counts of rows, queued on ctx's stream like grail_levels_async: rows_dev: device
+ * [n_rows][row_stride] (rendered rows or finished tracks alike); len_dev: device [n_rows]; results are DEVICE arrays
+ * [n_rows], either may be NULL.  16-byte loads where rows_dev is 16-byte aligned and row_stride a multiple of 4, 4-byte
+ * loads otherwise: same bits.  The filter is FIR, so time is parallel: one wavefront takes a stretch of one row, and a
+ * lone long row fills the device.  The stretches' maxima go through scratch that stays with the context (12 bytes per
+ * 4096 samples of n_rows x row_stride), grown and never shrunk, until grail_destroy.
+ * Without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_true_peak_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                          uint32_t n_rows, double *true_peak_dev, uint32_t *nonfinite_dev);
+
+/* Pure host: 20 log10(true_peak), -HUGE_VAL for 0; NaN for a negative number (no true peak is one) and for NaN. */
+double grail_true_peak_db(double true_peak);
+
+/* Pure host: caps gains so that no item's row exceeds a ceiling.  c = pow(10.0, (double)ceiling_db / 20.0).  Item i with
+ * row r and gain g = item_gains[i] (in and out) is limited when true_peak[r] > 0 and (double)fabsf(g) * true_peak[r] > c:
+ * its new magnitude is q = (float)(c / true_peak[r]), rounded to nearest, and one float towards 0 from there if
+ * (double)q * true_peak[r] > c, so that (double)q * true_peak[r] <= c holds exactly; the sign of g is kept.  *n_limited
+ * (may be NULL) counts the items changed.  GRAIL_ERR_INVALID_ARG with nothing written: an item's row >= n_rows, a NULL
+ * array with n_items > 0, a ceiling_db that is not finite. */
+int grail_true_peak_limit_gains(const double *true_peak, uint32_t n_rows, const uint32_t *item_rows,
+                                uint32_t n_items, float ceiling_db, float *item_gains, uint32_t *n_limited);
+
+/* grail_batch_mix_leveled with a true-peak ceiling in dBTP: per block render, measure the level, measure the true peak
+ * (grail_true_peak_async's kernels), copy 8 bytes a row more in the same wait, grail_level_gains,
+ * grail_true_peak_limit_gains, mix.  The tracks are the bits grail_batch_mix gives with the gains that were used;
+ * item_gains_out reports them, *n_limited (may be NULL) the items the ceiling changed; both as n_unleveled only when the
+ * call succeeds.  The ceiling binds each ITEM: items that overlap on a track can still sum above it, and the mix rounds
+ * each product once more; a caller measures the finished tracks with grail_true_peak_async.  A ceiling_db that is not
+ * finite: GRAIL_ERR_INVALID_ARG.  (No new GRAIL_LEVEL_* mode: the ceiling works with every one of them.) */
+int grail_batch_mix_leveled_limited(grail_ctx *ctx, const grail_batch *batch, const uint32_t *item_rows,
+                                    const uint32_t *item_tracks, const uint64_t *item_offsets,
+                                    const float *item_level_db, int mode, uint32_t n_items, float *tracks_dev,
+                                    uint64_t track_stride, uint32_t n_tracks, uint64_t track_len, uint32_t *out_len,
+                                    float *item_gains_out, uint32_t *n_unleveled, float ceiling_db,
+                                    uint32_t *n_limited, uint32_t flags);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
