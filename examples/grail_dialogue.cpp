@@ -1,17 +1,21 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
 // --ceiling DBTP (with --level or --lufs) holds every placement under that true peak as well: the rows' true peaks are
 // measured on the device and cap the gains (grail_batch_mix_leveled_limited), and the two finished tracks are measured
 // the same way (grail::Gpu::true_peak); "--lufs -23 --ceiling -1" is the delivery rule of EBU R 128.
+// --limit (with --ceiling) then passes the two finished tracks, as one linked pair, through the look-ahead limiter
+// (grail::Gpu::limit) with the largest power of two of samples within 5 ms as look-ahead, and prints the tracks' true
+// peaks before and after: what placements that overlap, or the mix's own rounding, left above the ceiling gives way there.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "grail.hpp"
@@ -21,7 +25,7 @@ int main(int argc, char **argv)
     std::string out_path = "dialogue.wav";
     std::vector<std::string> lines;
     bool leveled = false, bad_level = false, lufs = false;
-    bool capped = false, bad_ceiling = false;
+    bool capped = false, bad_ceiling = false, limit = false;
     float level_db = 0.0f, ceiling_db = 0.0f;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
@@ -36,11 +40,12 @@ int main(int argc, char **argv)
             ceiling_db = std::strtof(argv[++i], &rest);
             capped = true;
             bad_ceiling = rest == argv[i] || *rest || !std::isfinite(ceiling_db);
-        } else lines.push_back(argv[i]);
+        } else if (!std::strcmp(argv[i], "--limit")) limit = true;
+        else lines.push_back(argv[i]);
     }
-    if (lines.size() != 2 || bad_level || bad_ceiling || (capped && !leveled)) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP] \"first line\" "
-                             "\"second line\"\n       (--ceiling needs --level or --lufs)\n");
+    if (lines.size() != 2 || bad_level || bad_ceiling || (capped && !leveled) || (limit && !capped)) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] \"first line\" "
+                             "\"second line\"\n       (--ceiling needs --level or --lufs, --limit needs --ceiling)\n");
         return 2;
     }
     try {
@@ -77,6 +82,17 @@ int main(int argc, char **argv)
                 const grail::TruePeak tp = gpu.true_peak(tracks);
                 std::printf("Ceiling %.1f dBTP: %u of 4 placements limited; track true peaks %.6f and %.6f dBTP\n", ceiling_db,
                             limited, tp.db(0), tp.db(1));
+                if (limit) {    // the finished tracks as one linked pair; the largest power of two within rate / 200
+                    uint32_t lookahead_log2 = 0;
+                    while (lookahead_log2 < GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX && (2u << lookahead_log2) <= (uint32_t)first.sample_rate / 200u)
+                        ++lookahead_log2;
+                    grail::Limited held = gpu.limit(tracks, grail::limit_ceiling(ceiling_db), lookahead_log2, 2);
+                    const grail::TruePeak after = gpu.true_peak(held.rows);
+                    std::printf("Limiter, %u samples of look-ahead: %u samples limited, smallest gain %.6f; track true peaks %.6f and "
+                                "%.6f dBTP before, %.6f and %.6f dBTP after\n", 1u << lookahead_log2, held.n_limited[0],
+                                held.min_gain[0], tp.db(0), tp.db(1), after.db(0), after.db(1));
+                    tracks = std::move(held.rows);
+                }
             }
         } else {
             tracks = gpu.mix(utts, placements, 2, end);

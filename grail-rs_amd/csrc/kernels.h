@@ -191,4 +191,20 @@ hipError_t launch_true_peak_totals(const uint32_t *len, uint64_t row_stride, uin
                                    const uint32_t *cbad, uint32_t grid_chunks, double *true_peak, uint32_t *nonfinite,
                                    hipStream_t stream);
 
+// limiter (limiter_kernels.hip): one workgroup per (group of `group` consecutive rows, chunk of LIMIT_CHUNK samples),
+// grid_chunks = limit_grid_chunks(row_stride) of them per group; the limited rows go to out, the chunk's numbers
+// (limit_chunk_bytes() each) to cstat[group * grid_chunks + c] (chunks past a group's last and the chunks of a group whose
+// members differ in length are left unwritten, as is out there).  ceiling finite and > 0, lookahead_log2 <= 10.
+constexpr uint32_t LIMIT_CHUNK = 4096;      // == GRAIL_LIMIT_CHUNK (not part of the contract: no number depends on it)
+uint64_t limit_grid_chunks(uint64_t row_stride);
+size_t limit_chunk_bytes();
+hipError_t launch_limit_frames(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_groups, uint32_t group,
+                               float ceiling, uint32_t lookahead_log2, uint32_t grid_chunks, float *out, uint64_t out_stride,
+                               void *cstat, hipStream_t stream);
+// ... and a group's smallest gain, its count of limited samples and of non-finite ones, one lane per group (outputs may
+// be NULL); a refused group reads NaN, 0xFFFFFFFF, 0
+hipError_t launch_limit_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_groups, uint32_t group,
+                               uint32_t lookahead_log2, const void *cstat, uint32_t grid_chunks, float *min_gain,
+                               uint32_t *n_limited, uint32_t *nonfinite, hipStream_t stream);
+
 }  // namespace grail

@@ -1,7 +1,7 @@
 // level_gains.cpp — the host side of levels that needs no device: grail_level_gains (a row's numbers and a target level
 // per item -> the item's gain), grail_active_level (a row's level over its active frames) and the host side of the
 // K-weighted loudness: grail_kweighting, grail_gated_mean_square, grail_loudness_lufs, grail_loudness_level; and of the
-// true peak: grail_true_peak_coefficients, grail_true_peak_db, grail_true_peak_limit_gains.  No HIP call, so it builds
+// true peak: grail_true_peak_coefficients, grail_true_peak_db, grail_true_peak_limit_gains, grail_limit_ceiling.  No HIP call, so it builds
 // with g++ under AddressSanitizer and UBSan (tests/test_levels_host.py, tests/test_loudness_host.py,
 // tests/test_true_peak_host.py), as mix_plan.cpp does.  DESIGN.md §4.9, §4.10, §4.11.
 #include <cmath>
@@ -144,6 +144,8 @@ double grail_true_peak_db(double true_peak)
     if (!(true_peak > 0.0)) return std::nan("");        // (no true peak is negative; a NaN stays one)
     return 20.0 * std::log10(true_peak);
 }
+
+float grail_limit_ceiling(float ceiling_db) { return (float)std::pow(10.0, (double)ceiling_db / 20.0); }
 
 int grail_true_peak_limit_gains(const double *true_peak, uint32_t n_rows, const uint32_t *item_rows, uint32_t n_items,
                                 float ceiling_db, float *item_gains, uint32_t *n_limited)

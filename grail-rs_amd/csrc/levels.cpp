@@ -1,7 +1,7 @@
 // levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async and
-// grail_true_peak_async (checks, the scratch, the launches) and what grail_batch_mix_leveled and its _limited form
-// (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip and true_peak_kernels.hip, the gains
-// are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11.
+// grail_true_peak_async, grail_limit_async (checks, the scratch, the launches) and what grail_batch_mix_leveled and its
+// _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip, true_peak_kernels.hip
+// and limiter_kernels.hip, the gains are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11, §4.12.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -10,7 +10,8 @@ using namespace grail::host;
 // Per context (grail_ctx::level_state), grown and never shrunk, freed by grail_destroy: the per-frame numbers that a
 // totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), one block's totals for the leveled mix, and the
 // hop sums of a loudness call that does not ask for them (8 B per hop of 100 ms), and the chunk maxima and counts that a
-// true-peak call folds (12 B per chunk of 4096 output times) with one block's true peaks for the limited mix.
+// true-peak call folds (12 B per chunk of 4096 output times) with one block's true peaks for the limited mix, and the
+// chunk numbers that a limiter call folds (16 B per group and chunk of 4096 samples).
 struct LevelState {
     double *d_fsum = nullptr;
     float *d_fpeak = nullptr;
@@ -27,6 +28,8 @@ struct LevelState {
     size_t cap_cmax = 0, cap_cbad = 0;
     double *d_tp = nullptr;
     size_t cap_tp = 0;
+    unsigned char *d_lstat = nullptr;
+    size_t cap_lstat = 0;
 };
 
 namespace grail {
@@ -37,7 +40,7 @@ void levels_release(grail_ctx *ctx)
     LevelState *st = (LevelState *)ctx->level_state;
     if (!st) return;
     for (void *p : {(void *)st->d_fsum, (void *)st->d_fpeak, (void *)st->d_fbad, (void *)st->d_sumsq, (void *)st->d_peak,
-                    (void *)st->d_bad, (void *)st->d_hops, (void *)st->d_cmax, (void *)st->d_cbad, (void *)st->d_tp})
+                    (void *)st->d_bad, (void *)st->d_hops, (void *)st->d_cmax, (void *)st->d_cbad, (void *)st->d_tp, (void *)st->d_lstat})
         if (p) (void)hipFree(p);
     delete st;
     ctx->level_state = nullptr;
@@ -298,6 +301,49 @@ int grail_true_peak_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_st
     if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_true_peak_async: NULL buffer");
     if (!true_peak_dev && !nonfinite_dev) return GRAIL_OK;
     return true_peak(ctx, "grail_true_peak_async", rows_dev, row_stride, len_dev, n_rows, true_peak_dev, nonfinite_dev);
+}
+
+int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev, uint32_t n_rows,
+                      uint32_t group, float ceiling, uint32_t lookahead_log2, float *out_dev, uint64_t out_stride,
+                      float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev)
+{
+    // (what is wrong with the arguments is said before what is wrong with the machine)
+    if (lookahead_log2 > GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: lookahead_log2 is above 10");
+    if (group == 0 || n_rows % group != 0)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: n_rows is no multiple of group");
+    if (!(ceiling > 0.0f) || !(ceiling <= 3.4028234663852886e38f))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: the ceiling is not a finite number above 0");
+    if (out_stride < row_stride) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: out_stride < row_stride");
+    if (n_rows && (!len_dev || (row_stride && (!rows_dev || !out_dev))))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: NULL buffer");
+    if (n_rows && row_stride) {
+        if (row_stride > (1ull << 60) / n_rows || out_stride > (1ull << 60) / n_rows)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: the rows span more than 2^60 samples");
+        const uintptr_t in0 = (uintptr_t)rows_dev, in1 = in0 + (uintptr_t)(n_rows * row_stride * 4u);
+        const uintptr_t out0 = (uintptr_t)out_dev, out1 = out0 + (uintptr_t)(n_rows * out_stride * 4u);
+        if (in0 < out1 && out0 < in1)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: out_dev overlaps rows_dev (the look-ahead reads ahead of the stores)");
+    }
+    int rc = bind_device(ctx, "grail_limit_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    const uint32_t n_groups = n_rows / group;
+    const uint64_t chunks = limit_grid_chunks(row_stride);
+    if ((uint64_t)n_groups * chunks > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: more than 2^31 chunks");
+    if (chunks) {               // (rows of no samples: 1.0f, 0, 0 from the totals alone)
+        if ((rc = reserve(ctx, &st->d_lstat, &st->cap_lstat, (size_t)n_groups * (size_t)chunks * limit_chunk_bytes()))) return rc;
+        const hipError_t e = launch_limit_frames(rows_dev, row_stride, len_dev, n_groups, group, ceiling, lookahead_log2,
+                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "limiter frames kernel launch");
+    }
+    if (!min_gain_dev && !n_limited_dev && !nonfinite_dev) return GRAIL_OK;
+    const hipError_t e = launch_limit_totals(len_dev, row_stride, n_groups, group, lookahead_log2, st->d_lstat, (uint32_t)chunks,
+                                             min_gain_dev, n_limited_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "limiter totals kernel launch");
+    return GRAIL_OK;
 }
 
 int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,

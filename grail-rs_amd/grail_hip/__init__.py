@@ -78,6 +78,7 @@ EXPORTS = [
     "grail_kweighting", "grail_loudness_async", "grail_gated_mean_square", "grail_loudness_lufs", "grail_loudness_level",
     "grail_true_peak_coefficients", "grail_true_peak_async", "grail_true_peak_db", "grail_true_peak_limit_gains",
     "grail_batch_mix_leveled_limited",
+    "grail_limit_ceiling", "grail_limit_async",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -88,6 +89,9 @@ LOUDNESS_ABS_GATE = 1.1724653045822981e-07      # GRAIL_LOUDNESS_ABS_GATE: the m
 LOUDNESS_LEVEL_SCALE = 0.8529037030705663       # GRAIL_LOUDNESS_LEVEL_SCALE: 10^(-0.691 / 10)
 LOUDNESS_RATE_MIN, LOUDNESS_RATE_MAX = 2560, 1048576
 TRUE_PEAK_PHASES, TRUE_PEAK_TAPS = 4, 12        # GRAIL_TRUE_PEAK_*: the 4x oversampling filter of BS.1770-4 Annex 2
+LIMIT_LOOKAHEAD_LOG2_MAX = 10                   # GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX: the look-ahead is 2^0 .. 2^10 samples
+LIMIT_REFUSED = 0xFFFFFFFF                      # GRAIL_LIMIT_REFUSED: n_limited of a group whose members differ in length
+LIMIT_CHUNK = 4096                              # GRAIL_LIMIT_CHUNK: one workgroup's samples (no number depends on it)
 
 
 class GrailError(RuntimeError):
@@ -353,6 +357,9 @@ def load():
     L.grail_true_peak_db.argtypes = [C.c_double]
     L.grail_true_peak_db.restype = C.c_double
     L.grail_true_peak_limit_gains.argtypes = [vp, C.c_uint32, vp, C.c_uint32, C.c_float, vp, vp]
+    L.grail_limit_ceiling.argtypes = [C.c_float]
+    L.grail_limit_ceiling.restype = C.c_float
+    L.grail_limit_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, u64, vp, vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -675,6 +682,11 @@ def true_peak_coefficients():
 def true_peak_db(true_peak):
     """grail_true_peak_db: 20 log10(true peak) in dBTP; -inf for 0."""
     return float(load().grail_true_peak_db(float(true_peak)))
+
+
+def limit_ceiling(ceiling_db):
+    """grail_limit_ceiling (pure host): the float32 that a ceiling in dBTP is to grail_limit_async."""
+    return np.float32(load().grail_limit_ceiling(float(np.float32(ceiling_db))))
 
 
 def true_peak_limit_gains(true_peak, item_rows, item_gains, ceiling_db, n_rows=None):
@@ -1087,6 +1099,31 @@ class Context:
             for p in d:
                 self.device_free(p)
         return tp[:n_rows], bad[:n_rows]
+
+    def limit_async(self, rows_dev, row_stride, len_dev, n_rows, ceiling, lookahead_log2, out_dev, out_stride=None, group=1,
+                    min_gain_dev=None, n_limited_dev=None, nonfinite_dev=None):
+        """grail_limit_async: the look-ahead limiter over groups of `group` consecutive rows, into out_dev (must not overlap
+        rows_dev); ceiling is linear (limit_ceiling gives it from dBTP), the look-ahead 2^lookahead_log2 samples.  Results
+        are DEVICE arrays [n_rows // group] (any may be None), queued on the context's stream."""
+        _check(load().grail_limit_async(self.handle, rows_dev, row_stride, len_dev, n_rows, group, float(np.float32(ceiling)),
+                                        lookahead_log2, out_dev, row_stride if out_stride is None else out_stride,
+                                        min_gain_dev, n_limited_dev, nonfinite_dev))
+
+    def limit(self, rows_dev, row_stride, len_dev, n_rows, ceiling, lookahead_log2, out_dev, out_stride=None, group=1):
+        """limit_async, waited for, the results copied back: (min_gain float32, n_limited uint32, nonfinite uint32), one per
+        group; a refused group reads (NaN, LIMIT_REFUSED, 0)."""
+        n_groups = n_rows // group if group else 0
+        res = [np.zeros(max(n_groups, 1), dtype=t) for t in (np.float32, np.uint32, np.uint32)]
+        d = [self.device_alloc(max(n_groups, 1) * 4) for _ in res]
+        try:
+            self.limit_async(rows_dev, row_stride, len_dev, n_rows, ceiling, lookahead_log2, out_dev, out_stride, group, *d)
+            for dst, src in zip(res, d):
+                self.d2h(dst, src, n_groups * 4)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return tuple(r[:n_groups] for r in res)
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max |x|, non-finite counts) per row, computed on the device."""

@@ -269,6 +269,10 @@ extern "C" {
         item_tracks: *const u32, item_offsets: *const u64, item_level_db: *const f32, mode: c_int, n_items: u32,
         tracks_dev: *mut f32, track_stride: u64, n_tracks: u32, track_len: u64, out_len: *mut u32,
         item_gains_out: *mut f32, n_unleveled: *mut u32, ceiling_db: f32, n_limited: *mut u32, flags: u32) -> c_int;
+    pub fn grail_limit_ceiling(ceiling_db: f32) -> f32;
+    pub fn grail_limit_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32, n_rows: u32,
+        group: u32, ceiling: f32, lookahead_log2: u32, out_dev: *mut f32, out_stride: u64, min_gain_dev: *mut f32,
+        n_limited_dev: *mut u32, nonfinite_dev: *mut u32) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

@@ -450,6 +450,79 @@ impl Gpu {
         Ok((peaks, bad))
     }
 
+    /// The look-ahead limiter over rows of samples, `group` consecutive rows sharing one gain curve (finished tracks as one
+    /// linked group: `group = rows.len()`), on the device (`grail_limit_async`; the contract is the header's section "levels,
+    /// continued: limiter").  `ceiling` is linear (see [`limit_ceiling`]), the look-ahead `2^lookahead_log2` samples.
+    /// Returns the limited rows and, per group, the smallest gain, the count of limited samples and the count of
+    /// non-finite ones; a group whose rows differ in length is refused: its rows come back empty, its numbers are NaN,
+    /// [`LIMIT_REFUSED`] and 0.  Afterwards `|sample| <= ceiling` holds exactly; the true peak follows to within the header's
+    /// bound: measure it with [`Gpu::true_peak`].
+    pub fn limit(&self, rows: &[Vec<f32>], ceiling: f32, lookahead_log2: u32, group: u32)
+                 -> Result<(Vec<Vec<f32>>, Vec<f32>, Vec<u32>, Vec<u32>), Error> {
+        let n = rows.len();
+        if group == 0 || n % group as usize != 0 {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "limit: the number of rows is no multiple of group".into() });
+        }
+        let groups = n / group as usize;
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut min_gain = vec![0f32; groups];
+        let mut limited = vec![0u32; groups];
+        let mut bad = vec![0u32; groups];
+        if n == 0 {
+            return Ok((out, min_gain, limited, bad));
+        }
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 6] = [std::ptr::null_mut(); 6];
+            let sizes = [n * stride * 4, n * stride * 4, n * 4, groups * 4, groups * 4, groups * 4];
+            let mut r = Ok(());
+            for k in 0..6 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_limit_async(self.ctx, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32, group,
+                                                 ceiling, lookahead_log2, d[1] as *mut f32, stride as u64, d[3] as *mut f32,
+                                                 d[4] as *mut u32, d[5] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, min_gain.as_mut_ptr() as *mut std::ffi::c_void, d[3], groups * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, limited.as_mut_ptr() as *mut std::ffi::c_void, d[4], groups * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[5], groups * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && lens[i] != 0 && limited[i / group as usize] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(self.ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * stride) as *const std::ffi::c_void, lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, min_gain, limited, bad))
+    }
+
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
     /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
     /// non-finite samples.  One lane filters one row: many rows fill the device.
@@ -535,6 +608,16 @@ pub fn true_peak_coefficients() -> Result<[[f64; 12]; 4], Error> {
 /// A true peak in dBTP (`grail_true_peak_db`): 20 log10, negative infinity for 0.
 pub fn true_peak_db(true_peak: f64) -> f64 {
     unsafe { sys::grail_true_peak_db(true_peak) }
+}
+
+/// `n_limited` of a group that [`Gpu::limit`] refused (`GRAIL_LIMIT_REFUSED`).
+pub const LIMIT_REFUSED: u32 = 0xFFFF_FFFF;
+/// The largest `lookahead_log2` of [`Gpu::limit`] (`GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX`).
+pub const LIMIT_LOOKAHEAD_LOG2_MAX: u32 = 10;
+
+/// The `f32` that a ceiling in dBTP is to [`Gpu::limit`] (`grail_limit_ceiling`; pure host).
+pub fn limit_ceiling(ceiling_db: f32) -> f32 {
+    unsafe { sys::grail_limit_ceiling(ceiling_db) }
 }
 
 /// Caps `gains` so that no item's row exceeds `ceiling_db` dBTP (`grail_true_peak_limit_gains`; pure host): item `i`

@@ -100,6 +100,18 @@ struct TruePeak {
     double db(size_t row) const { return grail_true_peak_db(true_peak[row]); }
 };
 
+// What Gpu::limit gives: the limited rows, and one entry per group of rows (grail_limit_async)
+struct Limited {
+    std::vector<std::vector<float>> rows;   // as long as they came; the rows of a refused group come back empty
+    std::vector<float> min_gain;            // the smallest gain of the group; NaN for a refused group
+    std::vector<uint32_t> n_limited;        // samples whose gain is below 1; GRAIL_LIMIT_REFUSED for a refused group
+    std::vector<uint32_t> nonfinite;        // NaN and Inf samples of the group's rows (they are written as 0)
+    bool refused(size_t group) const { return n_limited[group] == GRAIL_LIMIT_REFUSED; }
+};
+
+// The float that a ceiling in dBTP is to Gpu::limit (grail_limit_ceiling)
+inline float limit_ceiling(float ceiling_db) { return grail_limit_ceiling(ceiling_db); }
+
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
                     std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
@@ -380,6 +392,53 @@ public:
         if (!rc) rc = grail_memcpy_d2h(ctx_, out.true_peak.data(), d_tp, (size_t)n * 8);
         if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
         for (void *p : {d_rows, d_len, d_tp, d_bad})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
+    // The look-ahead limiter over rows of samples, `group` consecutive rows sharing one gain curve (finished tracks as one
+    // linked group: group = rows.size()), on the device (grail_limit_async; the contract is the header's section "levels,
+    // continued: limiter").  ceiling is linear (limit_ceiling), the look-ahead 2^lookahead_log2 samples.  |sample| <= ceiling
+    // holds exactly afterwards; the true peak follows to within the header's bound: measure it with true_peak.
+    Limited limit(const std::vector<std::vector<float>> &rows, float ceiling, uint32_t lookahead_log2, uint32_t group = 1) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        if (group == 0 || n % group) throw Error(GRAIL_ERR_INVALID_ARG, "limit: the number of rows is no multiple of group");
+        const uint32_t n_groups = n / group;
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64;
+        Limited out;
+        out.rows.resize(n);
+        out.min_gain.resize(n_groups);
+        out.n_limited.resize(n_groups);
+        out.nonfinite.resize(n_groups);
+        if (!n) return out;
+        std::vector<uint32_t> lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        void *d_rows = nullptr, *d_out = nullptr, *d_len = nullptr, *d_gain = nullptr, *d_lim = nullptr, *d_bad = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n_groups * 4, &d_gain);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n_groups * 4, &d_lim);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n_groups * 4, &d_bad);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc) rc = grail_limit_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, group, ceiling,
+                                        lookahead_log2, (float *)d_out, stride, (float *)d_gain, (uint32_t *)d_lim,
+                                        (uint32_t *)d_bad);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.min_gain.data(), d_gain, (size_t)n_groups * 4);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.n_limited.data(), d_lim, (size_t)n_groups * 4);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n_groups * 4);
+        for (uint32_t i = 0; !rc && i < n; ++i) {
+            if (out.refused(i / group) || !lens[i]) continue;
+            out.rows[i].resize(lens[i]);
+            rc = grail_memcpy_d2h(ctx_, out.rows[i].data(), (const float *)d_out + (size_t)i * stride, (size_t)lens[i] * 4);
+        }
+        for (void *p : {d_rows, d_out, d_len, d_gain, d_lim, d_bad})
             if (p) grail_device_free(ctx_, p);
         check(rc);
         return out;

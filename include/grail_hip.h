@@ -813,6 +813,61 @@ int grail_batch_mix_leveled_limited(grail_ctx *ctx, const grail_batch *batch, co
                                     float *item_gains_out, uint32_t *n_unleveled, float ceiling_db,
                                     uint32_t *n_limited, uint32_t flags);
 
+/* ---- levels, continued: limiter ----------------------------------------------------------------------------------------------
+ * grail_batch_mix_leveled_limited caps each item by one gain: items that overlap on a track can still sum above the
+ * ceiling, and one loud syllable pulls its whole utterance down.  The limiter is the stage after the mix: a gain curve
+ * computed from a look-ahead window and applied sample by sample, so that a finished track keeps its loudness and
+ * gives way only where it is too high.  c = ceiling (linear, a finite float > 0), L = 2^l = 2^lookahead_log2 samples of
+ * look-ahead, l = 0 .. GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX (a power of two, so that the smoothing divides exactly; 256 samples
+ * are 5.3 ms at 48 kHz; l = 0 is a hard limiter).  Rows come in GROUPS of `group` consecutive rows that share one gain
+ * curve (1: every row alone; 2: a linked stereo pair); n_rows is a multiple of group.  The members of a group must have
+ * equal n = min(len, row_stride); a group whose members differ is REFUSED: its out rows are left unwritten and its
+ * results read min_gain = NaN, n_limited = GRAIL_LIMIT_REFUSED, nonfinite = 0.  For a group of n samples, Q = 2^24:
+ *   1. Detection, per member row: v[t] and the outputs y[p][u], u = 0 .. n + 10, are those of the true-peak section above
+ *      (binary64, the same fold, a non-finite sample counted and entering as +0.0).  e[u] = max over p of |y[p][u]|;
+ *      d[t] = max(|v[t]|, e[t], ..., e[t + 11]): the sample and every oversampled output it feeds.  The group's d[t] is
+ *      the maximum over its members.
+ *   2. The required gain as an integer: q[t] = Q if d[t] <= (double)c, else min(Q, floor((double)c * Q / d[t])), one
+ *      correctly rounded binary64 division (c * Q is exact).  q[s] = Q for s < 0 and s >= n.
+ *   3. Look-ahead: m[s] = min(q[s], ..., q[s + L - 1]) for s = -(L - 1) .. n - 1.
+ *   4. Smoothing: S[t] = m[t - L + 1] + ... + m[t], an integer of at most 2^34, so every summation order gives it;
+ *      g[t] = (float)((double)S[t] * 2^-(24 + l)): the product is exact, the conversion rounds once.
+ *   5. Apply, per member row: z[t] = g[t] * x[t] in binary32, then clamped: z < -c gives -c, z > c gives c, anything else
+ *      (-0.0 included) stays.  A non-finite x[t] writes +0.0.  out between n and out_stride is never written.
+ * Nothing above depends on chunking, layout, alignment, the rows around or the launch: out and the results are a pure
+ * function of the group's samples, c, l.  No float atomics.
+ * GUARANTEED: every m[s] under S[t] has q[t] in its window, so g[t] <= q[t] / Q <= c / d[t], and after the clamp
+ * |z[t]| <= c holds exactly.  A group whose d never exceeds c has g = 1.0f throughout: z equals x bit for bit.
+ * NOT guaranteed: the true peak of z exactly under c, because g varies across the filter's twelve taps.  g moves by at
+ * most 1 / L per sample, which gives the BOUND
+ *     true peak(z) <= c + (11 / L) * TAP_SUM * max|x| + TAP_SUM * 2^-24 * c,   TAP_SUM = 16571 / 8192
+ * (the largest sum of |C[p][k]| of a phase).  The bound is loose (DESIGN.md §4.12 has overshoots of the model: thousandths of
+ * a dB at L >= 16).  Measure the result with grail_true_peak_async; for delivery ask for a hair less than the rule's
+ * ceiling.  Attack and release are both L samples: there are no separate times. */
+#define GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX 10
+#define GRAIL_LIMIT_REFUSED 0xFFFFFFFFu
+/* The samples of one workgroup's stretch of a group.  Not part of the contract (no number depends on it): it is here so
+ * that tests can aim at the seams. */
+#define GRAIL_LIMIT_CHUNK 4096
+
+/* Pure host: the one float that a ceiling in dBTP is: (float)pow(10.0, (double)ceiling_db / 20.0). */
+float grail_limit_ceiling(float ceiling_db);
+
+/* The limiter above, queued on ctx's stream like grail_true_peak_async: rows_dev: device [n_rows][row_stride] (finished
+ * tracks or rendered rows alike); len_dev: device [n_rows]; out_dev: device [n_rows][out_stride], out_stride >=
+ * row_stride.  Results are DEVICE arrays [n_rows / group], any may be NULL: min_gain (the smallest g of the group; 1.0f
+ * for a group of no samples), n_limited (the samples t with S[t] < L * Q), nonfinite (summed over the members).
+ * out_dev must not overlap rows_dev: the look-ahead reads ahead of what other workgroups write.  16-byte loads and stores
+ * where both bases are 16-byte aligned and both strides multiples of 4, 4-byte ones otherwise: same bits.  One workgroup
+ * takes a stretch of one group, so a lone long track fills the device.  Scratch stays with the context (16 bytes per
+ * group and 4096 samples), grown and never shrunk, until grail_destroy.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: lookahead_log2 > 10; group 0 or no divisor of n_rows; a ceiling that is not a
+ * finite number above 0; out_stride < row_stride; a NULL buffer with samples to read; overlapping ranges.  These come
+ * first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev, uint32_t n_rows,
+                      uint32_t group, float ceiling, uint32_t lookahead_log2, float *out_dev, uint64_t out_stride,
+                      float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
