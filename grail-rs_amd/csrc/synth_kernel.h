@@ -112,6 +112,9 @@
 #ifndef GRAIL_CALM_RUNS
 #define GRAIL_CALM_RUNS 1
 #endif
+#ifndef GRAIL_ROW_STEP_FLUSH
+#define GRAIL_ROW_STEP_FLUSH 1
+#endif
 #ifndef CALM_RUN_MAX_TILES
 #define CALM_RUN_MAX_TILES PIPE_MAX_TILES
 #endif

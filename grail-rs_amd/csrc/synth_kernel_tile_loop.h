@@ -43,6 +43,11 @@
         // needs a second copy of the calm loop, and no form of it tried kept both copies at the pace of the one —
         // NOTEBOOK "Runs of calm tiles".)
         constexpr bool CALM_RUNS = GRAIL_CALM_RUNS && GRAIL_SCALAR_PACK && L == 1 && NFA == 4 && !FAST && !PIPE && !STREAM && !SPLIT && !ANYBL;
+        // ROW_STEP_FLUSH: the main loop's full-tile flush of f32 rows in slot order addresses a lane's row once and steps from
+        // one group of rows to the next (as flush_full_tile does for the runs) — only the fast one-lane four-formant one-shot
+        // kernel: its headline leg is 0.3 % faster in every run of an alternating A/B (profiles/r12_flush_ab.txt); every other
+        // instantiation shares this text and compiles to what it was
+        constexpr bool ROW_STEP_FLUSH = GRAIL_ROW_STEP_FLUSH && FAST && L == 1 && T == 64 && NFA == 4 && !STREAM && !SPLIT && !MID;
         bool run_full = false;                     // CALM_RUNS: every row of the wave takes whole tiles as 16-byte stores
         uint32_t mixed_seed = 0u, mixed_sk = 0u;
         float mixed_noise = 0.0f;
@@ -185,7 +190,13 @@
                 }
             };
             // CALM_RUNS: a tile inside a run in which every row of the wave received all T samples, as 16-byte stores (the
-            // main loop's full-tile flush below: the LDS reads of all rows in flight together, the stores back to back)
+            // main loop's full-tile flush below: the LDS reads of all rows in flight together, the stores back to back).
+            // Rows in slot order are addressed once: the lane's pointer into row u0 + rr, which the compiler keeps for the
+            // run, plus the tile's base, then one 64-bit step of ROWS_PER_IT rows per group — no multiply per row group and
+            // tile, no branch between the stores.  All of it in 64 bits: no stride is too long for it.  The barrier between
+            // two groups' reads keeps each lane's (t0, t0 + 1) and (t0 + 2, t0 + 3) paired as ds_read2_b32, so that they land in
+            // the four registers the store takes (across groups the compiler pairs r with r + 8 and shuffles: 22 v_mov).
+            // 1 170 -> 460 cycles a tile (profiles/r12_flush_split.txt).  Rows under A.perm keep a look-up per group.
             auto flush_full_tile = [&](const uint32_t base_) __attribute__((always_inline)) {
                 if constexpr (CALM_RUNS) {
                     constexpr int ROW_LANES = T / 4;
@@ -200,11 +211,20 @@
                         const int t0 = rl * 4;
                         v[i] = make_float4(stage[(t0 + 0) * SP + r], stage[(t0 + 1) * SP + r], stage[(t0 + 2) * SP + r],
                                            stage[(t0 + 3) * SP + r]);
+                        asm volatile("" ::: "memory");
                     }
+                    if (A.perm) {
 #pragma unroll
-                    for (int i = 0; i < S / ROWS_PER_IT; ++i) {
-                        const uint64_t row = A.perm ? rowid[i * ROWS_PER_IT + rr] : u0 + i * ROWS_PER_IT + rr;
-                        *reinterpret_cast<float4 *>(A.out + row * A.out_stride + base_ + rl * 4) = v[i];
+                        for (int i = 0; i < S / ROWS_PER_IT; ++i)
+                            *reinterpret_cast<float4 *>(A.out + (uint64_t)rowid[i * ROWS_PER_IT + rr] * A.out_stride + base_ +
+                                                        rl * 4) = v[i];
+                    } else {
+                        float *p = A.out + (uint64_t)(u0 + rr) * A.out_stride + base_ + rl * 4;
+#pragma unroll
+                        for (int i = 0; i < S / ROWS_PER_IT; ++i) {
+                            *reinterpret_cast<float4 *>(p) = v[i];
+                            p += (uint64_t)ROWS_PER_IT * A.out_stride;
+                        }
                     }
                     wave_lds_sync();
                 }
@@ -529,6 +549,7 @@
                     const int t0 = rl * 4;
                     v[i] = make_float4(stage[(t0 + 0) * SP + r], stage[(t0 + 1) * SP + r], stage[(t0 + 2) * SP + r],
                                        stage[(t0 + 3) * SP + r]);
+                    if constexpr (ROW_STEP_FLUSH) asm volatile("" ::: "memory");
                 }
                 if (PCM_FULL_TILE && A.out_pcm16) {
                     // the WAV sink's `(x * i16::MAX as f32) as i16` (examples/cli.rs:49) on the way out: 8-byte stores
@@ -546,6 +567,13 @@
                     for (int i = 0; i < S / ROWS_PER_IT; ++i)
                         *reinterpret_cast<float4 *>(A.out + (uint64_t)rowid[i * ROWS_PER_IT + rr] * A.out_stride + base +
                                                     rl * 4) = v[i];
+                } else if constexpr (ROW_STEP_FLUSH) {
+                    float *p = A.out + (uint64_t)(u0 + rr) * A.out_stride + base + rl * 4;
+#pragma unroll
+                    for (int i = 0; i < S / ROWS_PER_IT; ++i) {
+                        *reinterpret_cast<float4 *>(p) = v[i];
+                        p += (uint64_t)ROWS_PER_IT * A.out_stride;
+                    }
                 } else {
 #pragma unroll
                     for (int i = 0; i < S / ROWS_PER_IT; ++i)
