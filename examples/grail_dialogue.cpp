@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -10,6 +10,9 @@
 // --limit (with --ceiling) then passes the two finished tracks, as one linked pair, through the look-ahead limiter
 // (grail::Gpu::limit) with the largest power of two of samples within 5 ms as look-ahead, and prints the tracks' true
 // peaks before and after: what placements that overlap, or the mix's own rounding, left above the ceiling gives way there.
+// --report measures the two finished tracks, after the last stage that ran, as a meter would (grail::Gpu::track_loudness,
+// parallel in time, and grail::Gpu::true_peak) and prints one line per track: integrated loudness, loudness range, largest
+// momentary and short-term loudness, true peak; "-" where a track is too short (or too quiet) for a number.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -25,7 +28,7 @@ int main(int argc, char **argv)
     std::string out_path = "dialogue.wav";
     std::vector<std::string> lines;
     bool leveled = false, bad_level = false, lufs = false;
-    bool capped = false, bad_ceiling = false, limit = false;
+    bool capped = false, bad_ceiling = false, limit = false, report = false, bad_report = false;
     float level_db = 0.0f, ceiling_db = 0.0f;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
@@ -41,11 +44,16 @@ int main(int argc, char **argv)
             capped = true;
             bad_ceiling = rest == argv[i] || *rest || !std::isfinite(ceiling_db);
         } else if (!std::strcmp(argv[i], "--limit")) limit = true;
+        else if (!std::strcmp(argv[i], "--report")) {
+            bad_report = report;        // (named twice)
+            report = true;
+        } else if (!std::strncmp(argv[i], "--report", 8)) bad_report = true;        // (it takes no value)
         else lines.push_back(argv[i]);
     }
-    if (lines.size() != 2 || bad_level || bad_ceiling || (capped && !leveled) || (limit && !capped)) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] \"first line\" "
-                             "\"second line\"\n       (--ceiling needs --level or --lufs, --limit needs --ceiling)\n");
+    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || (capped && !leveled) || (limit && !capped)) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--report] "
+                             "\"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit needs --ceiling, "
+                             "--report takes no value)\n");
         return 2;
     }
     try {
@@ -96,6 +104,25 @@ int main(int argc, char **argv)
             }
         } else {
             tracks = gpu.mix(utts, placements, 2, end);
+        }
+        if (report) {           // the finished tracks as a meter reads them; "-" where there is no number
+            const grail::TrackLoudness loud = gpu.track_loudness(tracks, (uint32_t)first.sample_rate);
+            const grail::TruePeak peak = gpu.true_peak(tracks);
+            const auto field = [](bool has, double value, const char *unit) {
+                char text[48];
+                if (has && std::isfinite(value)) std::snprintf(text, sizeof text, "%.2f %s", value, unit);
+                else std::snprintf(text, sizeof text, "-");
+                return std::string(text);
+            };
+            for (size_t t = 0; t < tracks.size(); ++t) {
+                const size_t hops = loud.hop_sumsq[t].size();
+                std::printf("Track %zu: integrated %s, range %s, max momentary %s, max short-term %s, true peak %s\n", t + 1,
+                            field(loud.gated_ms[t] > 0.0, loud.lufs(t), "LUFS").c_str(),
+                            field(hops >= 30 && loud.short_term_max(t) > -70.0, loud.range(t), "LU").c_str(),
+                            field(hops >= 4, loud.momentary_max(t), "LUFS").c_str(),
+                            field(hops >= 30, loud.short_term_max(t), "LUFS").c_str(),
+                            field(peak.true_peak[t] > 0.0, peak.db(t), "dBTP").c_str());
+            }
         }
         std::printf("%.2f seconds of stereo audio: \"%s\" (left), \"%s\" (right)\n", end / first.sample_rate,
                     lines[0].c_str(), lines[1].c_str());

@@ -179,6 +179,18 @@ hipError_t launch_loudness_hops(const float *rows, uint64_t row_stride, const ui
 // ... and a row's gated mean square from its hops, one lane per row
 hipError_t launch_loudness_gate(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t hop, const double *hops,
                                 uint64_t hops_stride, double *gated, hipStream_t stream);
+// the segmented form (loudness_segment_kernels.hip): one lane per (row, hop), each hop filtered from a zero state
+// GRAIL_LOUDNESS_WARMUP_HOPS hops before its first sample; the same hop layout as launch_loudness_hops, so that
+// launch_loudness_gate follows unchanged.  hop_bad: DEVICE [n_rows][loudness_segment_lanes(row_stride, hop)], the hops'
+// own non-finite counts (the lane after a row's last whole hop counts the row's tail), folded into nonfinite[n_rows] by
+// one lane per row; both NULL where the counts are not asked for.  One launch of n_rows * loudness_segment_waves blocks of
+// 64 lanes: a grid holds fewer than 2^32 threads, so more than LOUD_SEGMENT_WAVES_MAX of them is hipErrorInvalidValue.
+constexpr uint64_t LOUD_SEGMENT_WAVES_MAX = (1ull << 26) - 1u;
+uint64_t loudness_segment_lanes(uint64_t row_stride, uint32_t hop);
+uint64_t loudness_segment_waves(uint64_t row_stride, uint32_t hop);
+hipError_t launch_loudness_segments(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, uint32_t hop,
+                                    const double *coef, double *hops, uint64_t hops_stride, uint32_t *hop_bad,
+                                    uint32_t *nonfinite, hipStream_t stream);
 
 // true peak (true_peak_kernels.hip): one wave per (row, chunk of output times), grid_chunks =
 // true_peak_grid_chunks(row_stride) of them per row; per chunk the largest |y| of the 4x oversampling filter and the

@@ -1,10 +1,13 @@
 // level_gains.cpp — the host side of levels that needs no device: grail_level_gains (a row's numbers and a target level
 // per item -> the item's gain), grail_active_level (a row's level over its active frames) and the host side of the
-// K-weighted loudness: grail_kweighting, grail_gated_mean_square, grail_loudness_lufs, grail_loudness_level; and of the
+// K-weighted loudness: grail_kweighting, grail_gated_mean_square, grail_loudness_lufs, grail_loudness_level, grail_loudness_window_max,
+// grail_loudness_range; and of the
 // true peak: grail_true_peak_coefficients, grail_true_peak_db, grail_true_peak_limit_gains, grail_limit_ceiling.  No HIP call, so it builds
 // with g++ under AddressSanitizer and UBSan (tests/test_levels_host.py, tests/test_loudness_host.py,
 // tests/test_true_peak_host.py), as mix_plan.cpp does.  DESIGN.md §4.9, §4.10, §4.11.
+#include <algorithm>
 #include <cmath>
+#include <vector>
 
 #include "../../include/grail_hip.h"
 #include "true_peak_taps.h"
@@ -129,6 +132,59 @@ double grail_loudness_lufs(double gated_ms)
 }
 
 double grail_loudness_level(double gated_ms) { return std::sqrt(gated_ms * GRAIL_LOUDNESS_LEVEL_SCALE); }
+
+namespace {
+
+// the mean square of the window of `window` hops that starts at hop j: a left fold from h[j]
+double window_block(const double *h, uint32_t j, uint32_t window, double per)
+{
+    double sum = h[j];
+    for (uint32_t i = 1; i < window; ++i) sum = sum + h[j + i];
+    return sum / per;
+}
+
+}  // namespace
+
+double grail_loudness_window_max(const double *hop_sumsq, uint32_t n_hops, uint32_t hop, uint32_t window_hops)
+{
+    if (!hop_sumsq || hop == 0 || window_hops == 0 || n_hops < window_hops) return 0.0;
+    const double per = (double)window_hops * (double)hop;
+    double largest = 0.0;
+    for (uint32_t j = 0; j <= n_hops - window_hops; ++j) {
+        const double z = window_block(hop_sumsq, j, window_hops, per);
+        if (z > largest) largest = z;
+    }
+    return largest;
+}
+
+double grail_loudness_range(const double *hop_sumsq, uint32_t n_hops, uint32_t hop)
+{
+    const uint32_t window = 30;
+    if (!hop_sumsq || hop == 0 || n_hops < window) return 0.0;
+    const uint32_t blocks = n_hops - window + 1u;
+    const double per = (double)window * (double)hop;
+    std::vector<double> kept;
+    kept.reserve(blocks);
+    double sum = 0.0;
+    for (uint32_t j = 0; j < blocks; ++j) {
+        const double z = window_block(hop_sumsq, j, window, per);
+        if (z > GRAIL_LOUDNESS_ABS_GATE) {
+            sum = sum + z;
+            kept.push_back(z);
+        }
+    }
+    if (kept.empty()) return 0.0;
+    const double r = 0.01 * (sum / (double)kept.size());
+    size_t n = 0;
+    for (const double z : kept)
+        if (z > r) kept[n++] = z;
+    if (n == 0) return 0.0;         // (cannot happen for numbers: the largest block is above a hundredth of the mean)
+    kept.resize(n);
+    std::sort(kept.begin(), kept.end());
+    const double lo = kept[(size_t)(((uint64_t)(n - 1) * 10u + 50u) / 100u)];
+    const double hi = kept[(size_t)(((uint64_t)(n - 1) * 95u + 50u) / 100u)];
+    return 10.0 * std::log10(hi / lo);
+}
 
 int grail_true_peak_coefficients(double coef[GRAIL_TRUE_PEAK_PHASES * GRAIL_TRUE_PEAK_TAPS])
 {

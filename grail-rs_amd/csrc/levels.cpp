@@ -1,6 +1,6 @@
-// levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async and
-// grail_true_peak_async, grail_limit_async (checks, the scratch, the launches) and what grail_batch_mix_leveled and its
-// _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip, true_peak_kernels.hip
+// levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async,
+// grail_loudness_segmented_async and grail_true_peak_async, grail_limit_async (checks, the scratch, the launches) and what grail_batch_mix_leveled and its
+// _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip, loudness_segment_kernels.hip, true_peak_kernels.hip
 // and limiter_kernels.hip, the gains are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11, §4.12.
 #include "api_internal.hpp"
 
@@ -11,7 +11,8 @@ using namespace grail::host;
 // totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), one block's totals for the leveled mix, and the
 // hop sums of a loudness call that does not ask for them (8 B per hop of 100 ms), and the chunk maxima and counts that a
 // true-peak call folds (12 B per chunk of 4096 output times) with one block's true peaks for the limited mix, and the
-// chunk numbers that a limiter call folds (16 B per group and chunk of 4096 samples).
+// chunk numbers that a limiter call folds (16 B per group and chunk of 4096 samples), and the hops' non-finite counts that a
+// segmented loudness call folds (4 B per hop).
 struct LevelState {
     double *d_fsum = nullptr;
     float *d_fpeak = nullptr;
@@ -30,6 +31,8 @@ struct LevelState {
     size_t cap_tp = 0;
     unsigned char *d_lstat = nullptr;
     size_t cap_lstat = 0;
+    uint32_t *d_hbad = nullptr;
+    size_t cap_hbad = 0;
 };
 
 namespace grail {
@@ -40,7 +43,8 @@ void levels_release(grail_ctx *ctx)
     LevelState *st = (LevelState *)ctx->level_state;
     if (!st) return;
     for (void *p : {(void *)st->d_fsum, (void *)st->d_fpeak, (void *)st->d_fbad, (void *)st->d_sumsq, (void *)st->d_peak,
-                    (void *)st->d_bad, (void *)st->d_hops, (void *)st->d_cmax, (void *)st->d_cbad, (void *)st->d_tp, (void *)st->d_lstat})
+                    (void *)st->d_bad, (void *)st->d_hops, (void *)st->d_cmax, (void *)st->d_cbad, (void *)st->d_tp, (void *)st->d_lstat,
+                    (void *)st->d_hbad})
         if (p) (void)hipFree(p);
     delete st;
     ctx->level_state = nullptr;
@@ -115,10 +119,11 @@ int totals(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_
     return GRAIL_OK;
 }
 
-// hop sums, gated mean squares and non-finite counts (any output may be NULL; hops_dev NULL = the context's scratch)
-int loudness(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
-             uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_dev, double *hops_dev,
-             uint64_t hops_stride, uint32_t *nonfinite_dev)
+// hop sums, gated mean squares and non-finite counts (any output may be NULL; hops_dev NULL = the context's scratch);
+// segmented: every hop from a zero state GRAIL_LOUDNESS_WARMUP_HOPS hops before it, one lane per hop
+int loudness(grail_ctx *ctx, const char *who, bool segmented, const float *rows_dev, uint64_t row_stride,
+             const uint32_t *len_dev, uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_dev,
+             double *hops_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
 {
     double own[10];
     if (!coef) {
@@ -136,14 +141,51 @@ int loudness(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t ro
         if ((rc = reserve(ctx, &st->d_hops, &st->cap_hops, (size_t)n_rows * (size_t)hops_stride))) return rc;
         hops_dev = st->d_hops;
     }
-    hipError_t e = launch_loudness_hops(rows_dev, row_stride, len_dev, n_rows, hop, coef, hops_dev, hops_stride,
-                                        nonfinite_dev, ctx->stream);
-    if (e != hipSuccess) return hip_fail(e, "loudness hops kernel launch");
+    hipError_t e;
+    if (segmented) {
+        const uint64_t lanes = loudness_segment_lanes(row_stride, hop), waves = loudness_segment_waves(row_stride, hop);
+        // (the one refusal the serial call does not have: the launch is one grid of a wave per 64 hops of a row)
+        if (waves > LOUD_SEGMENT_WAVES_MAX || (uint64_t)n_rows * waves > LOUD_SEGMENT_WAVES_MAX)
+            return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^26 - 1 waves of 64 hops (n_rows * ceil(ceil(row_stride / H) / 64))");
+        uint32_t *hop_bad = nullptr;
+        if (nonfinite_dev) {
+            LevelState *st = state(ctx);
+            if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+            int rc;
+            if ((rc = reserve(ctx, &st->d_hbad, &st->cap_hbad, (size_t)n_rows * (size_t)lanes))) return rc;
+            hop_bad = st->d_hbad;
+        }
+        e = launch_loudness_segments(rows_dev, row_stride, len_dev, n_rows, hop, coef, hops_dev, hops_stride, hop_bad,
+                                     nonfinite_dev, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "loudness segments kernel launch");
+    } else {
+        e = launch_loudness_hops(rows_dev, row_stride, len_dev, n_rows, hop, coef, hops_dev, hops_stride, nonfinite_dev,
+                                 ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "loudness hops kernel launch");
+    }
     if (gated_dev) {
         e = launch_loudness_gate(len_dev, row_stride, n_rows, hop, hops_dev, hops_stride, gated_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "loudness gate kernel launch");
     }
     return GRAIL_OK;
+}
+
+// the checks of grail_loudness_async and grail_loudness_segmented_async, which differ in nothing but the kernel
+int loudness_call(grail_ctx *ctx, const char *who, bool segmented, const float *rows_dev, uint64_t row_stride,
+                  const uint32_t *len_dev, uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
+                  double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
+{
+    int rc = bind_device(ctx, who);
+    if (rc) return rc;
+    if (sample_rate < GRAIL_LOUDNESS_RATE_MIN || sample_rate > GRAIL_LOUDNESS_RATE_MAX)
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": sample_rate is outside 2 560 .. 1 048 576");
+    if (hop_sumsq_dev && hops_stride < row_stride / (sample_rate / 10u))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": hops_stride < row_stride / (sample_rate / 10)");
+    if (n_rows == 0) return GRAIL_OK;
+    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": NULL buffer");
+    if (!gated_ms_dev && !hop_sumsq_dev && !nonfinite_dev) return GRAIL_OK;
+    return loudness(ctx, who, segmented, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, gated_ms_dev, hop_sumsq_dev,
+                    hops_stride, nonfinite_dev);
 }
 
 // true peaks and non-finite counts (either output may be NULL) through the context's chunk scratch
@@ -226,7 +268,7 @@ int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const floa
     if ((rc = reserve(ctx, &st->d_peak, &st->cap_peak, n_rows))) return rc;
     if ((rc = reserve(ctx, &st->d_bad, &st->cap_bad, n_rows))) return rc;
     if (mode == GRAIL_LEVEL_LOUDNESS) {     // the gated mean squares in place of the totals: 12 bytes a row come back
-        if ((rc = loudness(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, sample_rate, nullptr,
+        if ((rc = loudness(ctx, "grail_batch_mix_leveled", false, rows_dev, row_stride, len_dev, n_rows, sample_rate, nullptr,
                            st->d_sumsq, nullptr, 0, st->d_bad)))
             return rc;
         if (ceiling_db && (rc = queue_block_true_peaks(ctx, st, rows_dev, row_stride, len_dev, n_rows, tp.data()))) return rc;
@@ -350,17 +392,16 @@ int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_str
                          uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
                          double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
 {
-    int rc = bind_device(ctx, "grail_loudness_async");
-    if (rc) return rc;
-    if (sample_rate < GRAIL_LOUDNESS_RATE_MIN || sample_rate > GRAIL_LOUDNESS_RATE_MAX)
-        return fail(GRAIL_ERR_INVALID_ARG, "grail_loudness_async: sample_rate is outside 2 560 .. 1 048 576");
-    if (hop_sumsq_dev && hops_stride < row_stride / (sample_rate / 10u))
-        return fail(GRAIL_ERR_INVALID_ARG, "grail_loudness_async: hops_stride < row_stride / (sample_rate / 10)");
-    if (n_rows == 0) return GRAIL_OK;
-    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_loudness_async: NULL buffer");
-    if (!gated_ms_dev && !hop_sumsq_dev && !nonfinite_dev) return GRAIL_OK;
-    return loudness(ctx, "grail_loudness_async", rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, gated_ms_dev,
-                    hop_sumsq_dev, hops_stride, nonfinite_dev);
+    return loudness_call(ctx, "grail_loudness_async", false, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef,
+                         gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev);
+}
+
+int grail_loudness_segmented_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                                   uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
+                                   double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
+{
+    return loudness_call(ctx, "grail_loudness_segmented_async", true, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef,
+                         gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev);
 }
 
 int grail_frame_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,

@@ -4,6 +4,7 @@
 // is serial along a row in exact arithmetic, so the parallelism is across rows: one lane per row, 64 rows per wave.
 // No atomics, every store a plain vector store.  DESIGN.md §4.10.
 #include "kernels.h"
+#include "loudness_common.h"
 
 #include "../../include/grail_hip.h"
 
@@ -11,13 +12,9 @@
 
 namespace grail {
 
-namespace {
+using namespace loud;
 
-constexpr uint32_t LOUD_ROWS = 64;          // rows of a tile = lanes of the wave
-constexpr uint32_t LOUD_T = 64;             // samples of a tile per row: 256 B of a row, 16 lanes x 16 B
-constexpr uint32_t LOUD_PITCH = LOUD_T + 1; // floats between two rows of the tile in LDS: lane r reads word 65 r + t, bank
-                                            // (r + t) mod 32, all distinct inside each half-wave
-constexpr uint32_t LOUD_LOADS = LOUD_ROWS * LOUD_T / (64 * 4);      // 16-byte loads per lane and tile: 16
+namespace {
 
 // One tile's loads: wave-instruction i reads samples [t0, t0 + 64) of the rows 4i .. 4i + 3 of the wave, lane l the four
 // samples from 4 (l mod 16) on of row 4i + l / 16: whole 256-byte pieces of rows, 16 loads in flight before the first use.
@@ -50,41 +47,6 @@ __device__ __forceinline__ void loud_load(const float *__restrict__ rows, uint64
         }
     }
 }
-
-// ... and their way into LDS, transposed: tile[row][sample] at pitch 65
-__device__ __forceinline__ void loud_stash(float *tile, uint32_t lane, const float (&x)[LOUD_LOADS][4])
-{
-#pragma unroll
-    for (uint32_t i = 0; i < LOUD_LOADS; ++i) {
-        float *dst = tile + (4u * i + (lane >> 4)) * LOUD_PITCH + 4u * (lane & 15u);
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) dst[k] = x[i][k];
-    }
-}
-
-struct KState {
-    double s1, s2, s3, s4, acc;
-    uint32_t bad;
-};
-
-// one sample through both sections, in the contract's order
-__device__ __forceinline__ void loud_sample(float xf, bool counted, const double (&c)[10], KState &k)
-{
-    const bool finite = __builtin_fabsf(xf) <= 3.4028234663852886e38f;      // false for NaN and Inf
-    k.bad += (counted && !finite) ? 1u : 0u;
-    const double v = finite ? (double)xf : 0.0;
-    const double y = c[0] * v + k.s1;
-    k.s1 = (c[1] * v - c[3] * y) + k.s2;
-    k.s2 = c[2] * v - c[4] * y;
-    const double z = c[5] * y + k.s3;
-    k.s3 = (c[6] * y - c[8] * z) + k.s4;
-    k.s4 = c[7] * y - c[9] * z;
-    k.acc = k.acc + z * z;
-}
-
-struct LoudCoef {
-    double c[10];
-};
 
 // One wave = 64 rows, lane r = row row0 + r, from the rows' first sample to the longest row's last in tiles of 64
 // samples.  The next tile's loads are issued before the current tile is filtered and land in LDS after it, so they are

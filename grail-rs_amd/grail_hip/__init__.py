@@ -76,6 +76,7 @@ EXPORTS = [
     "grail_wav_write_i16_frames",
     "grail_levels_async", "grail_frame_levels_async", "grail_level_gains", "grail_active_level", "grail_batch_mix_leveled",
     "grail_kweighting", "grail_loudness_async", "grail_gated_mean_square", "grail_loudness_lufs", "grail_loudness_level",
+    "grail_loudness_segmented_async", "grail_loudness_window_max", "grail_loudness_range",
     "grail_true_peak_coefficients", "grail_true_peak_async", "grail_true_peak_db", "grail_true_peak_limit_gains",
     "grail_batch_mix_leveled_limited",
     "grail_limit_ceiling", "grail_limit_async",
@@ -88,6 +89,7 @@ LEVEL_LOUDNESS = 4               # GRAIL_LEVEL_LOUDNESS: level = loudness_level(
 LOUDNESS_ABS_GATE = 1.1724653045822981e-07      # GRAIL_LOUDNESS_ABS_GATE: the mean square of -70 LUFS
 LOUDNESS_LEVEL_SCALE = 0.8529037030705663       # GRAIL_LOUDNESS_LEVEL_SCALE: 10^(-0.691 / 10)
 LOUDNESS_RATE_MIN, LOUDNESS_RATE_MAX = 2560, 1048576
+LOUDNESS_WARMUP_HOPS = 3                        # GRAIL_LOUDNESS_WARMUP_HOPS: loudness_segmented starts a hop's filter 3 hops early
 TRUE_PEAK_PHASES, TRUE_PEAK_TAPS = 4, 12        # GRAIL_TRUE_PEAK_*: the 4x oversampling filter of BS.1770-4 Annex 2
 LIMIT_LOOKAHEAD_LOG2_MAX = 10                   # GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX: the look-ahead is 2^0 .. 2^10 samples
 LIMIT_REFUSED = 0xFFFFFFFF                      # GRAIL_LIMIT_REFUSED: n_limited of a group whose members differ in length
@@ -352,6 +354,11 @@ def load():
     L.grail_loudness_lufs.restype = C.c_double
     L.grail_loudness_level.argtypes = [C.c_double]
     L.grail_loudness_level.restype = C.c_double
+    L.grail_loudness_segmented_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, vp, vp, vp, u64, vp]
+    L.grail_loudness_window_max.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32]
+    L.grail_loudness_window_max.restype = C.c_double
+    L.grail_loudness_range.argtypes = [vp, C.c_uint32, C.c_uint32]
+    L.grail_loudness_range.restype = C.c_double
     L.grail_true_peak_coefficients.argtypes = [vp]
     L.grail_true_peak_async.argtypes = [vp, vp, u64, vp, C.c_uint32, vp, vp]
     L.grail_true_peak_db.argtypes = [C.c_double]
@@ -670,6 +677,20 @@ def loudness_lufs(gated_ms):
 def loudness_level(gated_ms):
     """grail_loudness_level: the level whose 20 log10 is the loudness in LUFS."""
     return float(load().grail_loudness_level(float(gated_ms)))
+
+
+def loudness_window_max(hop_sumsq, hop, window_hops):
+    """grail_loudness_window_max (pure host): the largest mean square over windows of window_hops hops, one every hop:
+    4 = momentary, 30 = short-term; loudness_lufs() gives its LUFS.  0 for fewer hops than the window."""
+    hs = np.ascontiguousarray(hop_sumsq, dtype=np.float64)
+    return float(load().grail_loudness_window_max(hs.ctypes.data if len(hs) else None, len(hs), int(hop), int(window_hops)))
+
+
+def loudness_range(hop_sumsq, hop):
+    """grail_loudness_range (pure host): the loudness range in LU (EBU Tech 3342) of one row's hop sums; 0 for fewer than
+    30 hops or nothing above the absolute gate."""
+    hs = np.ascontiguousarray(hop_sumsq, dtype=np.float64)
+    return float(load().grail_loudness_range(hs.ctypes.data if len(hs) else None, len(hs), int(hop)))
 
 
 def true_peak_coefficients():
@@ -1052,10 +1073,27 @@ class Context:
         _check(load().grail_loudness_async(self.handle, rows_dev, row_stride, len_dev, n_rows, int(sample_rate), _ptr(c),
                                            gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev))
 
+    def loudness_segmented_async(self, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef=None, gated_ms_dev=None,
+                                 hop_sumsq_dev=None, hops_stride=0, nonfinite_dev=None):
+        """grail_loudness_segmented_async: loudness_async's arguments and outputs, every hop filtered from a zero state
+        LOUDNESS_WARMUP_HOPS hops before it, one lane per hop: for few long rows (a finished track)."""
+        c = None if coef is None else np.ascontiguousarray(coef, dtype=np.float64)
+        assert c is None or c.shape == (10,)
+        _check(load().grail_loudness_segmented_async(self.handle, rows_dev, row_stride, len_dev, n_rows, int(sample_rate),
+                                                     _ptr(c), gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev))
+
+    def loudness_segmented(self, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef=None, hops=True, fill=None):
+        """loudness_segmented_async, waited for and copied back: what loudness() returns."""
+        return self._loudness_sync(self.loudness_segmented_async, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, hops,
+                                   fill)
+
     def loudness(self, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef=None, hops=True, fill=None):
         """loudness_async, waited for and copied back: (gated_ms float64 [n_rows], hop_sumsq float64 [n_rows, row_stride //
         hop] or None, nonfinite uint32 [n_rows]).  Hops past a row's last hold `fill` (default NaN): the call leaves them
         unwritten."""
+        return self._loudness_sync(self.loudness_async, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, hops, fill)
+
+    def _loudness_sync(self, call, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, hops, fill):
         hop = int(sample_rate) // 10
         hs = max(int(row_stride) // hop, 1) if hop else 1
         gated = np.zeros(max(n_rows, 1), dtype=np.float64)
@@ -1067,8 +1105,8 @@ class Context:
         try:
             if hops:
                 self.h2d(d[2], hop_sumsq, hop_sumsq.nbytes)
-            self.loudness_async(rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, d[0], d[2] if hops else None,
-                                hs if hops else 0, d[1])
+            call(rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, d[0], d[2] if hops else None,
+                 hs if hops else 0, d[1])
             self.d2h(gated, d[0], gated.nbytes)
             self.d2h(bad, d[1], bad.nbytes)
             if hops:

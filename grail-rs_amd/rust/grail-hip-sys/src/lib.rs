@@ -256,7 +256,12 @@ extern "C" {
     pub fn grail_loudness_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
         n_rows: u32, sample_rate: u32, coef: *const f64, gated_ms_dev: *mut f64, hop_sumsq_dev: *mut f64,
         hops_stride: u64, nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_loudness_segmented_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, sample_rate: u32, coef: *const f64, gated_ms_dev: *mut f64, hop_sumsq_dev: *mut f64,
+        hops_stride: u64, nonfinite_dev: *mut u32) -> c_int;
     pub fn grail_gated_mean_square(hop_sumsq: *const f64, n_hops: u32, hop: u32) -> f64;
+    pub fn grail_loudness_window_max(hop_sumsq: *const f64, n_hops: u32, hop: u32, window_hops: u32) -> f64;
+    pub fn grail_loudness_range(hop_sumsq: *const f64, n_hops: u32, hop: u32) -> f64;
     pub fn grail_loudness_lufs(gated_ms: f64) -> f64;
     pub fn grail_loudness_level(gated_ms: f64) -> f64;
     pub fn grail_true_peak_coefficients(coef: *mut f64) -> c_int;

@@ -574,6 +574,67 @@ impl Gpu {
         }
         Ok((gated, bad))
     }
+
+    /// The same of few long rows (finished tracks), parallel in time (`grail_loudness_segmented_async`: every hop of
+    /// 100 ms filtered from a zero state three hops before it, one lane per hop): per row the gated mean square, the
+    /// count of non-finite samples and the row's hop sums, from which [`loudness_range`] and [`loudness_window_max`]
+    /// follow on the host.
+    pub fn track_loudness(&self, rows: &[Vec<f32>], sample_rate: u32) -> Result<(Vec<f64>, Vec<u32>, Vec<Vec<f64>>), Error> {
+        let n = rows.len();
+        let mut gated = vec![0f64; n];
+        let mut bad = vec![0u32; n];
+        if n == 0 {
+            return Ok((gated, bad, Vec::new()));
+        }
+        let hop = (sample_rate / 10) as usize;
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let hs = if hop > 0 { (stride / hop).max(1) } else { 1 };
+        let mut hops = vec![0f64; n * hs];
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let sizes = [n * stride * 4, n * 4, n * 8, n * 4, n * hs * 8];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[1], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_loudness_segmented_async(self.ctx, d[0] as *const f32, stride as u64, d[1] as *const u32,
+                                                              n as u32, sample_rate, std::ptr::null(), d[2] as *mut f64,
+                                                              d[4] as *mut f64, hs as u64, d[3] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, gated.as_mut_ptr() as *mut std::ffi::c_void, d[2], n * 8));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, hops.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * hs * 8));
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        // (hops past a row's last were never written)
+        let per_row = rows.iter().enumerate().map(|(i, row)| hops[i * hs..i * hs + row.len() / hop].to_vec()).collect();
+        Ok((gated, bad, per_row))
+    }
 }
 
 /// The ten K-weighting coefficients for a sample rate (`grail_kweighting`; pure host, no GPU).
@@ -596,6 +657,17 @@ pub fn loudness_lufs(gated_ms: f64) -> f64 {
 /// The level whose 20 log10 is the loudness in LUFS (`grail_loudness_level`).
 pub fn loudness_level(gated_ms: f64) -> f64 {
     unsafe { sys::grail_loudness_level(gated_ms) }
+}
+
+/// The largest mean square over windows of `window_hops` hops of one row's hop sums, one window every hop
+/// (`grail_loudness_window_max`; pure host): 4 hops = momentary, 30 = short-term; [`loudness_lufs`] gives its LUFS.
+pub fn loudness_window_max(hop_sumsq: &[f64], hop: u32, window_hops: u32) -> f64 {
+    unsafe { sys::grail_loudness_window_max(hop_sumsq.as_ptr(), hop_sumsq.len() as u32, hop, window_hops) }
+}
+
+/// The loudness range in LU of one row's hop sums after EBU Tech 3342 (`grail_loudness_range`; pure host).
+pub fn loudness_range(hop_sumsq: &[f64], hop: u32) -> f64 {
+    unsafe { sys::grail_loudness_range(hop_sumsq.as_ptr(), hop_sumsq.len() as u32, hop) }
 }
 
 /// The 4 x 12 taps of the true-peak filter, `[phase][tap]` (`grail_true_peak_coefficients`; pure host, no GPU).

@@ -93,6 +93,26 @@ struct Loudness {
     double lufs(size_t row) const { return grail_loudness_lufs(gated_ms[row]); }
 };
 
+// What a meter reads from one row's hop sums (pure host): the largest mean square over windows of window_hops hops (4 =
+// momentary, 30 = short-term; grail_loudness_lufs gives its LUFS), and the loudness range in LU (EBU Tech 3342)
+inline double loudness_window_max(const std::vector<double> &hop_sumsq, uint32_t hop, uint32_t window_hops)
+{
+    return grail_loudness_window_max(hop_sumsq.data(), (uint32_t)hop_sumsq.size(), hop, window_hops);
+}
+inline double loudness_range(const std::vector<double> &hop_sumsq, uint32_t hop)
+{
+    return grail_loudness_range(hop_sumsq.data(), (uint32_t)hop_sumsq.size(), hop);
+}
+
+// What Gpu::track_loudness measures (grail_loudness_segmented_async): Loudness, and each row's hop sums (100 ms each)
+struct TrackLoudness : Loudness {
+    uint32_t hop = 0;                              // samples per hop: sample_rate / 10
+    std::vector<std::vector<double>> hop_sumsq;    // per row, its floor(len / hop) hop sums
+    double range(size_t row) const { return loudness_range(hop_sumsq[row], hop); }                       // LU
+    double momentary_max(size_t row) const { return grail_loudness_lufs(loudness_window_max(hop_sumsq[row], hop, 4)); }
+    double short_term_max(size_t row) const { return grail_loudness_lufs(loudness_window_max(hop_sumsq[row], hop, 30)); }
+};
+
 // What Gpu::true_peak measures, one entry per row (grail_true_peak_async)
 struct TruePeak {
     std::vector<double> true_peak;     // largest |y| of the row oversampled four times (BS.1770-4 Annex 2); 0 for an empty row
@@ -337,31 +357,19 @@ public:
     // contract is the header's section "levels, continued").  One lane filters one row: many rows fill the device.
     Loudness loudness(const std::vector<std::vector<float>> &rows, uint32_t sample_rate) const
     {
-        const uint32_t n = (uint32_t)rows.size();
-        size_t longest = 0;
-        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
-        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64;
         Loudness out;
-        out.gated_ms.resize(n);
-        out.nonfinite.resize(n);
-        if (!n) return out;
-        std::vector<uint32_t> lens(n);
-        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
-        void *d_rows = nullptr, *d_len = nullptr, *d_ms = nullptr, *d_bad = nullptr;
-        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 8, &d_ms);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_bad);
-        for (uint32_t i = 0; !rc && i < n; ++i)
-            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
-        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
-        if (!rc) rc = grail_loudness_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, sample_rate, nullptr,
-                                           (double *)d_ms, nullptr, 0, (uint32_t *)d_bad);
-        if (!rc) rc = grail_memcpy_d2h(ctx_, out.gated_ms.data(), d_ms, (size_t)n * 8);
-        if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
-        for (void *p : {d_rows, d_len, d_ms, d_bad})
-            if (p) grail_device_free(ctx_, p);
-        check(rc);
+        measure_loudness(rows, sample_rate, false, out, nullptr);
+        return out;
+    }
+
+    // The same of few long rows (finished tracks), parallel in time (grail_loudness_segmented_async: every hop of 100 ms
+    // filtered from a zero state three hops before it, one lane per hop), with the rows' hop sums: integrated loudness,
+    // loudness range, largest momentary and short-term loudness all follow from them on the host.
+    TrackLoudness track_loudness(const std::vector<std::vector<float>> &rows, uint32_t sample_rate) const
+    {
+        TrackLoudness out;
+        out.hop = sample_rate / 10u;
+        measure_loudness(rows, sample_rate, true, out, &out.hop_sumsq);
         return out;
     }
 
@@ -468,6 +476,48 @@ public:
     }
 
 private:
+    // loudness (hop_sumsq NULL: grail_loudness_async) and track_loudness (grail_loudness_segmented_async, with the hop sums)
+    void measure_loudness(const std::vector<std::vector<float>> &rows, uint32_t sample_rate, bool segmented, Loudness &out,
+                          std::vector<std::vector<double>> *hop_sumsq) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64;
+        const uint32_t hop = sample_rate / 10u;
+        out.gated_ms.resize(n);
+        out.nonfinite.resize(n);
+        if (hop_sumsq) hop_sumsq->assign(n, {});
+        if (!n) return;
+        std::vector<uint32_t> lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        const uint64_t hs = hop_sumsq && hop ? stride / hop : 0;
+        std::vector<double> hops((size_t)n * hs);
+        void *d_rows = nullptr, *d_len = nullptr, *d_ms = nullptr, *d_bad = nullptr, *d_hops = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 8, &d_ms);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_bad);
+        if (!rc && hs) rc = grail_device_alloc(ctx_, hops.size() * 8, &d_hops);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc && !segmented)
+            rc = grail_loudness_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, sample_rate, nullptr,
+                                      (double *)d_ms, (double *)d_hops, hs, (uint32_t *)d_bad);
+        if (!rc && segmented)
+            rc = grail_loudness_segmented_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, sample_rate,
+                                                nullptr, (double *)d_ms, (double *)d_hops, hs, (uint32_t *)d_bad);
+        if (!rc && hs) rc = grail_memcpy_d2h(ctx_, hops.data(), d_hops, hops.size() * 8);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.gated_ms.data(), d_ms, (size_t)n * 8);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out.nonfinite.data(), d_bad, (size_t)n * 4);
+        for (void *p : {d_rows, d_len, d_ms, d_bad, d_hops})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        for (uint32_t i = 0; i < n && hs; ++i)      // (hops past a row's last were never written)
+            (*hop_sumsq)[i].assign(hops.begin() + (size_t)i * hs, hops.begin() + (size_t)i * hs + lens[i] / hop);
+    }
+
     // mix_leveled (ceiling_db NULL) and mix_leveled_limited
     std::vector<std::vector<float>> mix_leveled_with(const std::vector<Utterance> &utts, const std::vector<Placement> &placements,
                                                      const std::vector<float> &level_db, const float *ceiling_db,

@@ -737,11 +737,75 @@ int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_str
                          uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
                          double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev);
 
+/* THE SEGMENTED FORM: the same measurement, parallel in time, for few long rows (a finished track).  The signature is
+ * grail_loudness_async's and so is everything else: binary64, every operation rounded by itself, no fused multiply-add;
+ * the ten coefficients; H = sample_rate / 10; n = min(len[u], row_stride); non-finite samples counted and entering as
+ * +0.0; the gate; the outputs and which of them may be NULL; hops past a row's last left unwritten; the hops_stride rule,
+ * the rate range, the scratch for hop_sumsq_dev == NULL (plus 4 bytes per hop for the counts); the error returns, and one
+ * more: the call is one grid of a wavefront per 64 hops of a row, ceil(ceil(row_stride / H) / 64) per row, and more than
+ * 2^26 - 1 of them in all is GRAIL_ERR_INVALID_ARG (a grid holds fewer than 2^32 lanes).  The one difference is where the
+ * filter's state starts.  With P = GRAIL_LOUDNESS_WARMUP_HOPS:
+ *   - Hop h of a row is the acc of the serial recurrence above, run with s1 = s2 = s3 = s4 = +0.0 at sample
+ *     max(h, P) * H - P * H (that is (h - P) * H for h >= P and 0 for h < P) and over the samples from there to
+ *     (h + 1) * H - 1 in ascending order, acc = +0.0 at sample h * H.
+ *   - Hops 0 .. P are therefore grail_loudness_async's hops bit for bit, and a row of at most P + 1 hops reads exactly
+ *     what grail_loudness_async reads: hops, gated mean square and count.
+ *   - nonfinite[u] counts every non-finite sample among x[0 .. n) once: the warm-up of a later hop does not count it
+ *     again, and the samples after the last whole hop, which belong to no hop, are counted as they are there.
+ *   - A row's numbers remain a pure function of its samples, the rate and the coefficients: not of row_stride, the row's
+ *     index, its neighbours, the alignment, the device, the launch or the number of segments in flight.  No atomics.
+ *   - WHAT IT IS NOT: grail_loudness_async's bits from hop P + 1 on.  In exact arithmetic the two differ by the response
+ *     to the state s = (s1, s2, s3, s4) that the serial call holds at the segment's first sample and this call replaces
+ *     by zero.  Both sections have complex poles (Q > 1/2), of radius rho = sqrt(a2) for the shelf and r = sqrt(e2) for
+ *     the high-pass, rho < r; the all-pole response of such a pair is g[k] = r^k sin((k+1) th) / sin(th), |g[k]| <=
+ *     (k+1) r^k.  A section in transposed direct form II started from its state (p, q) with no input gives p g[k] +
+ *     q g[k-1]; the high-pass answers the shelf's decaying output through d0 g[k] + d1 g[k-1] + d2 g[k-2], at most
+ *     4 (k+1) r^(k-2).  Summing the convolution, k = P * H samples after the start and for every later sample of the hop
+ *         |dz| <= D * (|s1| + |s2| + |s3| + |s4|),    D = (P*H + 1) * r^(P*H - 2) * (1 + 4 / (rho * (1 - rho / r)^2)).
+ *     r^H is the decay of a time constant in seconds over 100 ms, so it does not depend on the rate: 3.97e-11 .. 3.99e-11
+ *     from 8 to 192 kHz, and r^(P*H) = 6.3e-32.  D is 5.0e-27 at 8 kHz, 1.8e-25 at 44.1 kHz, 2.3e-25 at 48 kHz and
+ *     1.2e-23 at 192 kHz (1.8e-21 at GRAIL_LOUDNESS_RATE_MAX): below 2^-60 of the state at every rate where the ten
+ *     numbers are a K-weighting, while every operation that formed that state rounded it by up to 2^-53 of itself.  In
+ *     the samples: the state is at most S * max|x|, with Y = (|b0| + |b1| + |b2|) / (1 - rho)^2, Z = 4 Y / (1 - r)^2 and
+ *     S = (|b1| + 2 |b2|) + (|a1| + 2 |a2|) Y + 4 Y + (|e1| + 2 |e2|) Z, so |dz| <= D * S * max|x|.
+ *     D is the truncation in EXACT arithmetic.  What remains between the two calls in binary64 is larger and is not
+ *     truncation: the rounded recurrence has a dead band.  Two trajectories fed the same samples contract towards each
+ *     other (by r per sample: 0.97 at 8 kHz, 0.995 at 48 kHz) only until they are a few units in the last place of the
+ *     state apart; there each step's roundings move them as much as the contraction pulls, and they stay that far apart,
+ *     so most hops differ in their last bits.  That floor is the same one the serial call has against its own exact
+ *     value.  Measured between the numpy models of
+ *     the two contracts over noise, a tone on DC, a square wave before silence and noise bursts (8 kHz, 30 hops): at most
+ *     6.2e-15 of full scale in a hop's mean square (|d hop| / H) and 1.8e-15 LU, 4 - 22 of the 30 hops bit-equal; P = 2
+ *     gave 2.7e-14 LU, P = 1 gave 5.2e-10 LU.  tests/test_loudness_segmented_host.py asserts 100 times the measured.
+ *   - For caller-supplied coef the call is still this pure function, but nothing is promised about its distance from
+ *     grail_loudness_async's numbers.
+ * WHICH CALL FOR WHAT: grail_loudness_async for many short rows (one pass over each sample, one lane per row);
+ * this one for few long rows (P + 1 passes over each sample, and as many lanes as the rows have hops).  Measured on an
+ * MI355X: a lone row of 10 000 000 samples at 48 kHz 2.58 ms against 750 ms (290 x); 64 rows of 10 minutes 13.8 ms; but
+ * 65 536 rows of 96 006 samples 78.8 ms against 7.6 ms: a row of 20 hops fills a third of its wavefront's lanes. */
+#define GRAIL_LOUDNESS_WARMUP_HOPS 3u
+int grail_loudness_segmented_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                                   uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
+                                   double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev);
+
 /* Pure host: the gate above over a row's n_hops hop sums, hop = H in samples; +0.0 for NULL, hop 0 or n_hops < 4. */
 double grail_gated_mean_square(const double *hop_sumsq, uint32_t n_hops, uint32_t hop);
 /* Pure host: -0.691 + 10 log10(gated_ms), -HUGE_VAL for 0; and sqrt(gated_ms * GRAIL_LOUDNESS_LEVEL_SCALE). */
 double grail_loudness_lufs(double gated_ms);
 double grail_loudness_level(double gated_ms);
+/* Pure host: what a meter reads from a row's hop sums besides the integrated loudness.  hop = H in samples.
+ * grail_loudness_window_max: the largest, over j = 0 .. n_hops - window_hops, of
+ *     (left fold from h[j] of h[j] .. h[j + window_hops - 1] in ascending order) / ((double)window_hops * (double)hop),
+ * a mean square (grail_loudness_lufs gives its LUFS); +0.0 for NULL, hop 0, window_hops 0 or n_hops < window_hops.
+ * window_hops 4 is the momentary loudness (for it the blocks are the gate's z_j bit for bit), 30 the short-term one. */
+double grail_loudness_window_max(const double *hop_sumsq, uint32_t n_hops, uint32_t hop, uint32_t window_hops);
+/* grail_loudness_range: the loudness range in LU after EBU Tech 3342.  s_j = the blocks of 30 hops as above, one every
+ * hop, j = 0 .. n_hops - 30.  A = the blocks with s_j > GRAIL_LOUDNESS_ABS_GATE; if A is empty the result is +0.0.
+ * r = 0.01 * (sum(A) / |A|), the sum a left fold from +0.0 in ascending j, the count converted to double: 20 LU below
+ * the mean.  B = the blocks of A with s_j > r, sorted ascending (never empty).  lo = B[((|B| - 1) * 10 + 50) / 100] and
+ * hi = B[((|B| - 1) * 95 + 50) / 100] in integer division (64-bit): Tech 3342's round((n - 1) p / 100 + 1), zero-based.
+ * The result is 10.0 * log10(hi / lo); the bits of log10 are the C library's.  +0.0 for NULL, hop 0 or n_hops < 30. */
+double grail_loudness_range(const double *hop_sumsq, uint32_t n_hops, uint32_t hop);
 /* GRAIL_LEVEL_LOUDNESS in grail_level_gains: the per-row level is read from active_level, exactly as GRAIL_LEVEL_ACTIVE
  * reads it (one grail_loudness_level per row).  In grail_batch_mix_leveled: item_level_db[i] is the item's target in LUFS;
  * the sample rate is that of the context's voice table (voices that do not all have one whole-numbered rate within
