@@ -1,8 +1,10 @@
 // api_internal.hpp — what the host translation units of the library share (internal; host code only: the kernel
 // units include kernels.h, never this).  grail_api.cpp: contexts, batches, voices; options.cpp: the option table,
 // grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
-// families, cost model, block planner; synthesize.cpp: launches;
-// streams.cpp: resumable and live streams; host_output.cpp: the one-call forms with a host destination; comm.cpp: RCCL.
+// families, cost model, block planner; synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
+// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak) and limited; host_output.cpp: the one-call
+// forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Device memory whose owner only
+// these units create is held in DeviceBuffer (below).
 #pragma once
 
 #include <dlfcn.h>
@@ -23,6 +25,7 @@
 #include <new>
 #include <string>
 #include <unordered_map>
+#include <utility>
 #include <vector>
 
 #include "../../include/grail_hip.h"
@@ -108,6 +111,80 @@ struct LaunchStats {
     uint64_t fast_tiles = 0, general_steps = 0;
 };
 
+namespace grail {
+namespace host {
+
+// errors: the status is returned, the message kept per thread for grail_last_error()
+int fail(int status, const std::string &msg);
+int hip_fail(hipError_t e, const char *what);
+std::string &last_error();
+
+#define HIP_TRY(expr)                                  \
+    do {                                               \
+        hipError_t e_ = (expr);                        \
+        if (e_ != hipSuccess) return ::grail::host::hip_fail(e_, #expr); \
+    } while (0)
+
+// One hipMalloc allocation of `capacity()` elements and its only owner (move-only; the destructor frees).  Every device
+// buffer of the per-context scratch (LevelState, MixState), of a stream and of the calls' temporaries is one of these;
+// `reserve` is their one growth rule: grown when too small, never shrunk.
+// NOT for grail_ctx and grail_batch (d_voices, d_voice_elems, d_truncated, the batch's buffers, PackedPerm::d_perm; the
+// three opaque state pointers stay void *): both are constructed on the stack by code that is built without hipcc and
+// linked without the HIP runtime (grail_plan_blocks and grail_plan_ragged_blocks in launch_plan.cpp, the drivers of
+// tests/test_sanitizers.py), where a member whose destructor calls hipFree would not link, and a grail_batch is copied
+// whole to make its row-group views.  Only units that call HIP themselves create the types that hold a DeviceBuffer.
+template <typename T>
+class DeviceBuffer {
+public:
+    DeviceBuffer() = default;
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept
+    {
+        if (this != &o) {
+            reset();
+            p_ = std::exchange(o.p_, nullptr);
+            cap_ = std::exchange(o.cap_, 0);
+        }
+        return *this;
+    }
+    ~DeviceBuffer() { reset(); }
+    T *get() const { return p_; }
+    size_t capacity() const { return cap_; }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        cap_ = 0;
+    }
+    // exactly max(n, 1) elements; what was held is released first
+    hipError_t alloc(size_t n)
+    {
+        reset();
+        n = std::max<size_t>(n, 1);
+        const hipError_t e = hipMalloc((void **)&p_, n * sizeof(T));
+        if (e != hipSuccess) p_ = nullptr;
+        else cap_ = n;
+        return e;
+    }
+    // room for `need` elements: nothing to do when there is; else `want` (>= need) of them, once everything queued on
+    // `stream` is through (a kernel or copy still queued may use the old buffer)
+    int reserve(hipStream_t stream, size_t need, size_t want)
+    {
+        if (cap_ >= std::max<size_t>(need, 1)) return GRAIL_OK;
+        if (p_) HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(alloc(want));
+        return GRAIL_OK;
+    }
+    int reserve(hipStream_t stream, size_t need) { return reserve(stream, need, need); }
+
+private:
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
+
+}  // namespace host
+}  // namespace grail
+
 struct grail_ctx {
     int device = 0;
     int cus = 256;                    // compute units the launch policy plans for (hipDeviceProp_t::multiProcessorCount;
@@ -135,7 +212,7 @@ struct grail_ctx {
 
 struct grail_stream {
     const grail_batch *batch = nullptr;
-    uint32_t *d_state = nullptr;   // [state_words(L)][lanes]
+    grail::host::DeviceBuffer<uint32_t> d_state;   // [state_words(L)][lanes]
     uint64_t lanes = 0;
     int L = 1;
     bool started = false;
@@ -145,19 +222,18 @@ struct grail_stream {
     // live streams (grail_stream_open_live): the stream owns its batch, whose segments sit in per-utterance rings
     grail_batch *own = nullptr;
     uint32_t ring_cap = 0;            // segments per utterance ring (a power of two); 0: not a live stream
-    uint32_t *d_counts = nullptr;     // [n_utt] segments appended so far
-    uint32_t *d_open = nullptr;       // [n_utt] 1 while the utterance's source may deliver more
-    uint32_t *d_consumed = nullptr;   // [n_utt] segments the Sequencer has pulled (written by the kernels)
+    grail::host::DeviceBuffer<uint32_t> d_counts;     // [n_utt] segments appended so far
+    grail::host::DeviceBuffer<uint32_t> d_open;       // [n_utt] 1 while the utterance's source may deliver more
+    grail::host::DeviceBuffer<uint32_t> d_consumed;   // [n_utt] segments the Sequencer has pulled (written by the kernels)
     std::vector<uint32_t> appended;   // host copy of d_counts
     std::vector<uint32_t> consumed;   // what the host last read of d_consumed (a lower bound)
     std::vector<uint8_t> open;        // host copy of d_open
     std::vector<grail_synthesis_elem> last_elem;   // elem mode: the last elem appended per utterance (sharpness of the next pair)
     std::vector<uint8_t> last_has;
     // staging of an append (kept: an interactive front end appends a phoneme every half second for hours)
-    grail::DevSeg *d_new = nullptr;
-    float *d_new_elems = nullptr;
-    uint32_t *d_new_offs = nullptr;
-    size_t new_cap = 0;
+    grail::host::DeviceBuffer<grail::DevSeg> d_new;
+    grail::host::DeviceBuffer<float> d_new_elems;
+    grail::host::DeviceBuffer<uint32_t> d_new_offs;
     // ... on the host side two pinned buffers in turn, each with the event behind its last upload: an append returns as
     // soon as its copies and its scatter kernel are queued, and waits only for the append before last (not for every
     // kernel queued on the stream) before it writes into a buffer again
@@ -227,17 +303,6 @@ struct grail_batch {
 
 namespace grail {
 namespace host {
-
-// errors: the status is returned, the message kept per thread for grail_last_error()
-int fail(int status, const std::string &msg);
-int hip_fail(hipError_t e, const char *what);
-std::string &last_error();
-
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        hipError_t e_ = (expr);                        \
-        if (e_ != hipSuccess) return ::grail::host::hip_fail(e_, #expr); \
-    } while (0)
 
 // the SIMDs and lanes the policy plans for: 4 SIMDs per compute unit, 64 lanes per wavefront.  Every family is laid out
 // for ONE resident wave per SIMD (a second wave on a SIMD costs as much as it brings: profiles/r01_lanes_sweep.txt), so

@@ -688,24 +688,20 @@ int grail_batch_lengths(grail_ctx *ctx, const grail_batch *batch, uint32_t max_l
     if ((rc = check_ready(ctx, batch))) return rc;
     if (!out_len && batch->n_utt) return fail(GRAIL_ERR_INVALID_ARG, "out_len is NULL");
     if (batch->n_utt == 0) return GRAIL_OK;
-    uint32_t *d_len = nullptr;
-    HIP_TRY(hipMalloc((void **)&d_len, (size_t)batch->n_utt * sizeof(uint32_t)));
+    DeviceBuffer<uint32_t> d_len;
+    HIP_TRY(d_len.alloc(batch->n_utt));
     LenArgs a{};
     a.segs = batch->d_segs;
     a.seg_offsets = batch->d_offsets;
     a.voice_ids = batch->d_voice_ids;
     a.voices = ctx->d_voices;
-    a.out_len = d_len;
+    a.out_len = d_len.get();
     a.n_utt = batch->n_utt;
     a.n_voices = (uint32_t)ctx->voices.size();
     a.max_len = max_len;
-    hipError_t e = launch_lengths(a, ctx->stream);
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(out_len, d_len, (size_t)batch->n_utt * sizeof(uint32_t),
-                           hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_len);
-    if (e != hipSuccess) return hip_fail(e, "grail_batch_lengths");
+    HIP_TRY(launch_lengths(a, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(out_len, d_len.get(), (size_t)batch->n_utt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return GRAIL_OK;
 }
 
@@ -771,21 +767,17 @@ int grail_batch_digest(grail_ctx *ctx, const float *in_dev, uint64_t in_stride,
     if (n_utt == 0) return GRAIL_OK;
     if (!in_dev || !len_dev || !sums || !maxabs || !nonfinite)
         return fail(GRAIL_ERR_INVALID_ARG, "NULL buffer");
-    unsigned long long *d_s = nullptr;
-    float *d_m = nullptr;
-    uint32_t *d_b = nullptr;
-    hipError_t e = hipMalloc((void **)&d_s, (size_t)n_utt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_m, (size_t)n_utt * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_b, (size_t)n_utt * 4);
-    if (e == hipSuccess) e = launch_digest(in_dev, in_stride, len_dev, n_utt, d_s, d_m, d_b, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sums, d_s, (size_t)n_utt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(maxabs, d_m, (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(nonfinite, d_b, (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_s) (void)hipFree(d_s);
-    if (d_m) (void)hipFree(d_m);
-    if (d_b) (void)hipFree(d_b);
-    if (e != hipSuccess) return hip_fail(e, "grail_batch_digest");
+    DeviceBuffer<unsigned long long> d_s;
+    DeviceBuffer<float> d_m;
+    DeviceBuffer<uint32_t> d_b;
+    HIP_TRY(d_s.alloc(n_utt));
+    HIP_TRY(d_m.alloc(n_utt));
+    HIP_TRY(d_b.alloc(n_utt));
+    HIP_TRY(launch_digest(in_dev, in_stride, len_dev, n_utt, d_s.get(), d_m.get(), d_b.get(), ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sums, d_s.get(), (size_t)n_utt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(maxabs, d_m.get(), (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(nonfinite, d_b.get(), (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return GRAIL_OK;
 }
 
@@ -798,22 +790,17 @@ int grail_batch_compare(grail_ctx *ctx, const float *a_dev, const float *b_dev, 
     if (n_utt == 0) return GRAIL_OK;
     if (!a_dev || !b_dev || !len_a_dev || !len_b_dev || !maxdiff || !sumsq || !mismatches)
         return fail(GRAIL_ERR_INVALID_ARG, "NULL buffer");
-    float *d_m = nullptr;
-    double *d_q = nullptr;
-    uint32_t *d_b = nullptr;
-    hipError_t e = hipMalloc((void **)&d_m, (size_t)n_utt * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_q, (size_t)n_utt * 8);
-    if (e == hipSuccess) e = hipMalloc((void **)&d_b, (size_t)n_utt * 4);
-    if (e == hipSuccess)
-        e = launch_compare(a_dev, b_dev, stride, len_a_dev, len_b_dev, n_utt, d_m, d_q, d_b, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(maxdiff, d_m, (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(sumsq, d_q, (size_t)n_utt * 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(mismatches, d_b, (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (d_m) (void)hipFree(d_m);
-    if (d_q) (void)hipFree(d_q);
-    if (d_b) (void)hipFree(d_b);
-    if (e != hipSuccess) return hip_fail(e, "grail_batch_compare");
+    DeviceBuffer<float> d_m;
+    DeviceBuffer<double> d_q;
+    DeviceBuffer<uint32_t> d_b;
+    HIP_TRY(d_m.alloc(n_utt));
+    HIP_TRY(d_q.alloc(n_utt));
+    HIP_TRY(d_b.alloc(n_utt));
+    HIP_TRY(launch_compare(a_dev, b_dev, stride, len_a_dev, len_b_dev, n_utt, d_m.get(), d_q.get(), d_b.get(), ctx->stream));
+    HIP_TRY(hipMemcpyAsync(maxdiff, d_m.get(), (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(sumsq, d_q.get(), (size_t)n_utt * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(mismatches, d_b.get(), (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return GRAIL_OK;
 }
 

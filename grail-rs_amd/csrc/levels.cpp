@@ -7,32 +7,25 @@
 using namespace grail;
 using namespace grail::host;
 
-// Per context (grail_ctx::level_state), grown and never shrunk, freed by grail_destroy: the per-frame numbers that a
-// totals call folds (16 B per frame of 4096 samples: 0.1 % of the rows), one block's totals for the leveled mix, and the
-// hop sums of a loudness call that does not ask for them (8 B per hop of 100 ms), and the chunk maxima and counts that a
-// true-peak call folds (12 B per chunk of 4096 output times) with one block's true peaks for the limited mix, and the
-// chunk numbers that a limiter call folds (16 B per group and chunk of 4096 samples), and the hops' non-finite counts that a
-// segmented loudness call folds (4 B per hop).
+// Per context (grail_ctx::level_state), kept from call to call and only ever grown (DeviceBuffer::reserve, to the exact
+// size), freed by grail_destroy: the per-frame numbers that a totals call folds (16 B per frame of 4096 samples: 0.1 % of
+// the rows), one block's totals for the leveled mix, the hop sums of a loudness call that does not ask for them (8 B per
+// hop of 100 ms), the chunk maxima and counts that a true-peak call folds (12 B per chunk of 4096 output times) with one
+// block's true peaks for the limited mix, the chunk numbers that a limiter call folds (16 B per group and chunk of 4096
+// samples), and the hops' non-finite counts that a segmented loudness call folds (4 B per hop).
 struct LevelState {
-    double *d_fsum = nullptr;
-    float *d_fpeak = nullptr;
-    uint32_t *d_fbad = nullptr;
-    size_t cap_fsum = 0, cap_fpeak = 0, cap_fbad = 0;
-    double *d_sumsq = nullptr;
-    float *d_peak = nullptr;
-    uint32_t *d_bad = nullptr;
-    size_t cap_sumsq = 0, cap_peak = 0, cap_bad = 0;
-    double *d_hops = nullptr;
-    size_t cap_hops = 0;
-    double *d_cmax = nullptr;
-    uint32_t *d_cbad = nullptr;
-    size_t cap_cmax = 0, cap_cbad = 0;
-    double *d_tp = nullptr;
-    size_t cap_tp = 0;
-    unsigned char *d_lstat = nullptr;
-    size_t cap_lstat = 0;
-    uint32_t *d_hbad = nullptr;
-    size_t cap_hbad = 0;
+    DeviceBuffer<double> d_fsum;            // frames: sums of squares,
+    DeviceBuffer<float> d_fpeak;            // ... peaks
+    DeviceBuffer<uint32_t> d_fbad;          // ... and non-finite counts
+    DeviceBuffer<double> d_sumsq;           // a block's rows: the same three (loudness mode: gated mean squares in d_sumsq)
+    DeviceBuffer<float> d_peak;
+    DeviceBuffer<uint32_t> d_bad;
+    DeviceBuffer<double> d_hops;            // hop sums
+    DeviceBuffer<double> d_cmax;            // true-peak chunks: maxima
+    DeviceBuffer<uint32_t> d_cbad;          // ... and non-finite counts
+    DeviceBuffer<double> d_tp;              // a block's true peaks
+    DeviceBuffer<unsigned char> d_lstat;    // limiter chunks
+    DeviceBuffer<uint32_t> d_hbad;          // segmented loudness: non-finite counts per hop
 };
 
 namespace grail {
@@ -40,13 +33,7 @@ namespace host {
 
 void levels_release(grail_ctx *ctx)
 {
-    LevelState *st = (LevelState *)ctx->level_state;
-    if (!st) return;
-    for (void *p : {(void *)st->d_fsum, (void *)st->d_fpeak, (void *)st->d_fbad, (void *)st->d_sumsq, (void *)st->d_peak,
-                    (void *)st->d_bad, (void *)st->d_hops, (void *)st->d_cmax, (void *)st->d_cbad, (void *)st->d_tp, (void *)st->d_lstat,
-                    (void *)st->d_hbad})
-        if (p) (void)hipFree(p);
-    delete st;
+    delete (LevelState *)ctx->level_state;
     ctx->level_state = nullptr;
 }
 
@@ -55,21 +42,13 @@ void levels_release(grail_ctx *ctx)
 
 namespace {
 
-template <typename T>
-int reserve(grail_ctx *ctx, T **p, size_t *cap, size_t n)
-{
-    n = std::max<size_t>(n, 1);
-    if (*cap >= n) return GRAIL_OK;
-    if (*p) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));    // (a queued measurement may still use the old buffer)
-        HIP_TRY(hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-    }
-    HIP_TRY(hipMalloc((void **)p, n * sizeof(T)));
-    *cap = n;
-    return GRAIL_OK;
-}
+// rows on the device as every measurement takes them: n rows at `stride`, row r of len[r] samples
+struct Rows {
+    const float *dev;
+    uint64_t stride;
+    const uint32_t *len;
+    uint32_t n;
+};
 
 // a context, or why there is none: the device entry points say GRAIL_ERR_NO_DEVICE on a machine without a GPU
 int bind_device(grail_ctx *ctx, const char *who)
@@ -79,6 +58,17 @@ int bind_device(grail_ctx *ctx, const char *who)
     if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
         return fail(GRAIL_ERR_NO_DEVICE, std::string(who) + ": no usable HIP device (there is no CPU fallback)");
     return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": ctx is NULL");
+}
+
+// what the measurement calls check alike, in this order: no rows is success, a missing buffer the caller's error, no
+// output asked for success again; *measure says whether anything is left to do
+int check_rows(const char *who, const Rows &r, bool any_output, bool *measure)
+{
+    *measure = false;
+    if (r.n == 0) return GRAIL_OK;
+    if (!r.len || (r.stride && !r.dev)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": NULL buffer");
+    *measure = any_output;
+    return GRAIL_OK;
 }
 
 LevelState *state(grail_ctx *ctx)
@@ -91,39 +81,37 @@ uint64_t ceil_div(uint64_t a, uint64_t b) { return a / b + (a % b != 0); }
 
 // the rows' totals with frames of GRAIL_LEVEL_FRAME through the context's frame scratch (which then holds the frames'
 // numbers at stride ceil(row_stride / GRAIL_LEVEL_FRAME) until the context's next measurement)
-int totals(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
-           uint32_t n_rows, double *sumsq_dev, float *peak_dev, uint32_t *nonfinite_dev)
+int totals(grail_ctx *ctx, const char *who, const Rows &r, double *sumsq_dev, float *peak_dev, uint32_t *nonfinite_dev)
 {
     LevelState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
-    const uint64_t frames = ceil_div(row_stride, GRAIL_LEVEL_FRAME);
+    const uint64_t frames = ceil_div(r.stride, GRAIL_LEVEL_FRAME);
     if (frames == 0) {          // rows of no samples: +0.0, +0.0f, 0
-        const hipError_t e = launch_level_totals(len_dev, 0, n_rows, GRAIL_LEVEL_FRAME, nullptr, nullptr, nullptr, 0,
-                                                 sumsq_dev, peak_dev, nonfinite_dev, ctx->stream);
+        const hipError_t e = launch_level_totals(r.len, 0, r.n, GRAIL_LEVEL_FRAME, nullptr, nullptr, nullptr, 0, sumsq_dev,
+                                                 peak_dev, nonfinite_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "level totals kernel launch");
         return GRAIL_OK;
     }
-    if (frames > 0xFFFFFFFFull || (uint64_t)n_rows * frames > (1ull << 32))
+    if (frames > 0xFFFFFFFFull || (uint64_t)r.n * frames > (1ull << 32))
         return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^32 frames");
-    const size_t cells = (size_t)n_rows * (size_t)frames;
+    const size_t cells = (size_t)r.n * (size_t)frames;
     int rc;
-    if ((rc = reserve(ctx, &st->d_fsum, &st->cap_fsum, cells))) return rc;
-    if ((rc = reserve(ctx, &st->d_fpeak, &st->cap_fpeak, cells))) return rc;
-    if ((rc = reserve(ctx, &st->d_fbad, &st->cap_fbad, cells))) return rc;
-    hipError_t e = launch_level_frames(rows_dev, row_stride, len_dev, n_rows, GRAIL_LEVEL_FRAME, (uint32_t)frames, st->d_fsum,
-                                       st->d_fpeak, st->d_fbad, frames, ctx->stream);
+    if ((rc = st->d_fsum.reserve(ctx->stream, cells))) return rc;
+    if ((rc = st->d_fpeak.reserve(ctx->stream, cells))) return rc;
+    if ((rc = st->d_fbad.reserve(ctx->stream, cells))) return rc;
+    hipError_t e = launch_level_frames(r.dev, r.stride, r.len, r.n, GRAIL_LEVEL_FRAME, (uint32_t)frames, st->d_fsum.get(),
+                                       st->d_fpeak.get(), st->d_fbad.get(), frames, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "level frames kernel launch");
-    e = launch_level_totals(len_dev, row_stride, n_rows, GRAIL_LEVEL_FRAME, st->d_fsum, st->d_fpeak, st->d_fbad, frames,
-                            sumsq_dev, peak_dev, nonfinite_dev, ctx->stream);
+    e = launch_level_totals(r.len, r.stride, r.n, GRAIL_LEVEL_FRAME, st->d_fsum.get(), st->d_fpeak.get(), st->d_fbad.get(),
+                            frames, sumsq_dev, peak_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "level totals kernel launch");
     return GRAIL_OK;
 }
 
 // hop sums, gated mean squares and non-finite counts (any output may be NULL; hops_dev NULL = the context's scratch);
 // segmented: every hop from a zero state GRAIL_LOUDNESS_WARMUP_HOPS hops before it, one lane per hop
-int loudness(grail_ctx *ctx, const char *who, bool segmented, const float *rows_dev, uint64_t row_stride,
-             const uint32_t *len_dev, uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_dev,
-             double *hops_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
+int loudness(grail_ctx *ctx, const char *who, bool segmented, const Rows &r, uint32_t sample_rate, const double *coef,
+             double *gated_dev, double *hops_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
 {
     double own[10];
     if (!coef) {
@@ -131,97 +119,89 @@ int loudness(grail_ctx *ctx, const char *who, bool segmented, const float *rows_
         coef = own;
     }
     const uint32_t hop = sample_rate / 10u;
+    int rc;
     if (!hops_dev) {
         LevelState *st = state(ctx);
         if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
-        hops_stride = row_stride / hop;
-        if (hops_stride && (uint64_t)n_rows > (1ull << 40) / hops_stride)
+        hops_stride = r.stride / hop;
+        if (hops_stride && (uint64_t)r.n > (1ull << 40) / hops_stride)
             return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^40 hops");
-        int rc;
-        if ((rc = reserve(ctx, &st->d_hops, &st->cap_hops, (size_t)n_rows * (size_t)hops_stride))) return rc;
-        hops_dev = st->d_hops;
+        if ((rc = st->d_hops.reserve(ctx->stream, (size_t)r.n * (size_t)hops_stride))) return rc;
+        hops_dev = st->d_hops.get();
     }
     hipError_t e;
     if (segmented) {
-        const uint64_t lanes = loudness_segment_lanes(row_stride, hop), waves = loudness_segment_waves(row_stride, hop);
+        const uint64_t lanes = loudness_segment_lanes(r.stride, hop), waves = loudness_segment_waves(r.stride, hop);
         // (the one refusal the serial call does not have: the launch is one grid of a wave per 64 hops of a row)
-        if (waves > LOUD_SEGMENT_WAVES_MAX || (uint64_t)n_rows * waves > LOUD_SEGMENT_WAVES_MAX)
+        if (waves > LOUD_SEGMENT_WAVES_MAX || (uint64_t)r.n * waves > LOUD_SEGMENT_WAVES_MAX)
             return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^26 - 1 waves of 64 hops (n_rows * ceil(ceil(row_stride / H) / 64))");
         uint32_t *hop_bad = nullptr;
         if (nonfinite_dev) {
             LevelState *st = state(ctx);
             if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
-            int rc;
-            if ((rc = reserve(ctx, &st->d_hbad, &st->cap_hbad, (size_t)n_rows * (size_t)lanes))) return rc;
-            hop_bad = st->d_hbad;
+            if ((rc = st->d_hbad.reserve(ctx->stream, (size_t)r.n * (size_t)lanes))) return rc;
+            hop_bad = st->d_hbad.get();
         }
-        e = launch_loudness_segments(rows_dev, row_stride, len_dev, n_rows, hop, coef, hops_dev, hops_stride, hop_bad,
-                                     nonfinite_dev, ctx->stream);
+        e = launch_loudness_segments(r.dev, r.stride, r.len, r.n, hop, coef, hops_dev, hops_stride, hop_bad, nonfinite_dev,
+                                     ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "loudness segments kernel launch");
     } else {
-        e = launch_loudness_hops(rows_dev, row_stride, len_dev, n_rows, hop, coef, hops_dev, hops_stride, nonfinite_dev,
-                                 ctx->stream);
+        e = launch_loudness_hops(r.dev, r.stride, r.len, r.n, hop, coef, hops_dev, hops_stride, nonfinite_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "loudness hops kernel launch");
     }
     if (gated_dev) {
-        e = launch_loudness_gate(len_dev, row_stride, n_rows, hop, hops_dev, hops_stride, gated_dev, ctx->stream);
+        e = launch_loudness_gate(r.len, r.stride, r.n, hop, hops_dev, hops_stride, gated_dev, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "loudness gate kernel launch");
     }
     return GRAIL_OK;
 }
 
 // the checks of grail_loudness_async and grail_loudness_segmented_async, which differ in nothing but the kernel
-int loudness_call(grail_ctx *ctx, const char *who, bool segmented, const float *rows_dev, uint64_t row_stride,
-                  const uint32_t *len_dev, uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
-                  double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
+int loudness_call(grail_ctx *ctx, const char *who, bool segmented, const Rows &r, uint32_t sample_rate, const double *coef,
+                  double *gated_ms_dev, double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
 {
     int rc = bind_device(ctx, who);
     if (rc) return rc;
     if (sample_rate < GRAIL_LOUDNESS_RATE_MIN || sample_rate > GRAIL_LOUDNESS_RATE_MAX)
         return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": sample_rate is outside 2 560 .. 1 048 576");
-    if (hop_sumsq_dev && hops_stride < row_stride / (sample_rate / 10u))
+    if (hop_sumsq_dev && hops_stride < r.stride / (sample_rate / 10u))
         return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": hops_stride < row_stride / (sample_rate / 10)");
-    if (n_rows == 0) return GRAIL_OK;
-    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": NULL buffer");
-    if (!gated_ms_dev && !hop_sumsq_dev && !nonfinite_dev) return GRAIL_OK;
-    return loudness(ctx, who, segmented, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef, gated_ms_dev, hop_sumsq_dev,
-                    hops_stride, nonfinite_dev);
+    bool measure;
+    if ((rc = check_rows(who, r, gated_ms_dev || hop_sumsq_dev || nonfinite_dev, &measure)) || !measure) return rc;
+    return loudness(ctx, who, segmented, r, sample_rate, coef, gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev);
 }
 
 // true peaks and non-finite counts (either output may be NULL) through the context's chunk scratch
-int true_peak(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
-              uint32_t n_rows, double *true_peak_dev, uint32_t *nonfinite_dev)
+int true_peak(grail_ctx *ctx, const char *who, const Rows &r, double *true_peak_dev, uint32_t *nonfinite_dev)
 {
     LevelState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
-    const uint64_t chunks = true_peak_grid_chunks(row_stride);
-    if (chunks > 0xFFFFFFFFull || (uint64_t)n_rows * chunks > (1ull << 32))
+    const uint64_t chunks = true_peak_grid_chunks(r.stride);
+    if (chunks > 0xFFFFFFFFull || (uint64_t)r.n * chunks > (1ull << 32))
         return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": more than 2^32 chunks");
     if (chunks) {               // (rows of no samples: +0.0, 0 from the totals alone)
-        const size_t cells = (size_t)n_rows * (size_t)chunks;
+        const size_t cells = (size_t)r.n * (size_t)chunks;
         int rc;
-        if ((rc = reserve(ctx, &st->d_cmax, &st->cap_cmax, cells))) return rc;
-        if ((rc = reserve(ctx, &st->d_cbad, &st->cap_cbad, cells))) return rc;
-        const hipError_t e = launch_true_peak_frames(rows_dev, row_stride, len_dev, n_rows, (uint32_t)chunks, st->d_cmax,
-                                                     st->d_cbad, ctx->stream);
+        if ((rc = st->d_cmax.reserve(ctx->stream, cells))) return rc;
+        if ((rc = st->d_cbad.reserve(ctx->stream, cells))) return rc;
+        const hipError_t e = launch_true_peak_frames(r.dev, r.stride, r.len, r.n, (uint32_t)chunks, st->d_cmax.get(),
+                                                     st->d_cbad.get(), ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "true peak frames kernel launch");
     }
-    const hipError_t e = launch_true_peak_totals(len_dev, row_stride, n_rows, st->d_cmax, st->d_cbad, (uint32_t)chunks,
+    const hipError_t e = launch_true_peak_totals(r.len, r.stride, r.n, st->d_cmax.get(), st->d_cbad.get(), (uint32_t)chunks,
                                                  true_peak_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "true peak totals kernel launch");
     return GRAIL_OK;
 }
 
 // grail_batch_mix_leveled_limited's part of a block, first half: the rows' true peaks queued behind the level's kernels
-// and their copy to tp[n_rows] on the host, complete once the caller has waited for the stream (8 bytes a row more)
-int queue_block_true_peaks(grail_ctx *ctx, LevelState *st, const float *rows_dev, uint64_t row_stride,
-                           const uint32_t *len_dev, uint32_t n_rows, double *tp)
+// and their copy to tp[r.n] on the host, complete once the caller has waited for the stream (8 bytes a row more)
+int queue_block_true_peaks(grail_ctx *ctx, LevelState *st, const Rows &r, double *tp)
 {
     int rc;
-    if ((rc = reserve(ctx, &st->d_tp, &st->cap_tp, n_rows))) return rc;
-    if ((rc = true_peak(ctx, "grail_batch_mix_leveled_limited", rows_dev, row_stride, len_dev, n_rows, st->d_tp, nullptr)))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(tp, st->d_tp, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if ((rc = st->d_tp.reserve(ctx->stream, r.n))) return rc;
+    if ((rc = true_peak(ctx, "grail_batch_mix_leveled_limited", r, st->d_tp.get(), nullptr))) return rc;
+    HIP_TRY(hipMemcpyAsync(tp, st->d_tp.get(), (size_t)r.n * 8, hipMemcpyDeviceToHost, ctx->stream));
     return GRAIL_OK;
 }
 
@@ -262,57 +242,48 @@ int level_block_gains(grail_ctx *ctx, int mode, uint32_t sample_rate, const floa
     LevelState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
     if (n_rows == 0 || n_items == 0) return GRAIL_OK;
+    const Rows r{rows_dev, row_stride, len_dev, n_rows};
+    const bool loud = mode == GRAIL_LEVEL_LOUDNESS;
     int rc;
+    if ((rc = st->d_sumsq.reserve(ctx->stream, n_rows))) return rc;
+    if ((rc = st->d_peak.reserve(ctx->stream, n_rows))) return rc;
+    if ((rc = st->d_bad.reserve(ctx->stream, n_rows))) return rc;
+    // the measurement: the gated mean squares in place of the sums of squares, or the totals
+    const char *who = "grail_batch_mix_leveled";
+    rc = loud ? loudness(ctx, who, false, r, sample_rate, nullptr, st->d_sumsq.get(), nullptr, 0, st->d_bad.get())
+              : totals(ctx, who, r, st->d_sumsq.get(), st->d_peak.get(), st->d_bad.get());
+    if (rc) return rc;
     std::vector<double> tp(ceiling_db ? n_rows : 0);      // with a ceiling: the rows' true peaks, brought back in the same wait
-    if ((rc = reserve(ctx, &st->d_sumsq, &st->cap_sumsq, n_rows))) return rc;
-    if ((rc = reserve(ctx, &st->d_peak, &st->cap_peak, n_rows))) return rc;
-    if ((rc = reserve(ctx, &st->d_bad, &st->cap_bad, n_rows))) return rc;
-    if (mode == GRAIL_LEVEL_LOUDNESS) {     // the gated mean squares in place of the totals: 12 bytes a row come back
-        if ((rc = loudness(ctx, "grail_batch_mix_leveled", false, rows_dev, row_stride, len_dev, n_rows, sample_rate, nullptr,
-                           st->d_sumsq, nullptr, 0, st->d_bad)))
-            return rc;
-        if (ceiling_db && (rc = queue_block_true_peaks(ctx, st, rows_dev, row_stride, len_dev, n_rows, tp.data()))) return rc;
-        std::vector<double> gated(n_rows), level(n_rows);
-        std::vector<uint32_t> bad(n_rows);
-        HIP_TRY(hipMemcpyAsync(gated.data(), st->d_sumsq, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(bad.data(), st->d_bad, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (uint32_t r = 0; r < n_rows; ++r) level[r] = grail_loudness_level(gated[r]);
-        uint32_t unleveled = 0;
-        rc = grail_level_gains(mode, nullptr, nullptr, bad.data(), row_len, level.data(), n_rows, item_rows, item_level_db,
-                               n_items, gains, &unleveled);
-        if (rc) return fail(rc, "grail_batch_mix_leveled: grail_level_gains refused the block");
-        *n_unleveled += unleveled;
-        return ceiling_db ? limit_block_gains(tp.data(), n_rows, item_rows, n_items, *ceiling_db, gains, n_limited) : GRAIL_OK;
-    }
-    if ((rc = totals(ctx, "grail_batch_mix_leveled", rows_dev, row_stride, len_dev, n_rows, st->d_sumsq, st->d_peak, st->d_bad)))
-        return rc;
-    if (ceiling_db && (rc = queue_block_true_peaks(ctx, st, rows_dev, row_stride, len_dev, n_rows, tp.data()))) return rc;
-    std::vector<double> sumsq(n_rows), active;
+    if (ceiling_db && (rc = queue_block_true_peaks(ctx, st, r, tp.data()))) return rc;
+    // what the mode reads comes back (12 bytes a row; active level: the frames' sums too), with one wait
+    std::vector<double> sumsq(n_rows), level, frames;
     std::vector<float> peak(n_rows);
     std::vector<uint32_t> bad(n_rows);
-    if (mode == GRAIL_LEVEL_RMS)
-        HIP_TRY(hipMemcpyAsync(sumsq.data(), st->d_sumsq, (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (loud || mode == GRAIL_LEVEL_RMS)
+        HIP_TRY(hipMemcpyAsync(sumsq.data(), st->d_sumsq.get(), (size_t)n_rows * 8, hipMemcpyDeviceToHost, ctx->stream));
     if (mode == GRAIL_LEVEL_PEAK)
-        HIP_TRY(hipMemcpyAsync(peak.data(), st->d_peak, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(bad.data(), st->d_bad, (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
-    std::vector<double> frames;
+        HIP_TRY(hipMemcpyAsync(peak.data(), st->d_peak.get(), (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(bad.data(), st->d_bad.get(), (size_t)n_rows * 4, hipMemcpyDeviceToHost, ctx->stream));
     const uint64_t fs = ceil_div(row_stride, GRAIL_LEVEL_FRAME);
     if (mode == GRAIL_LEVEL_ACTIVE && fs) {
         frames.resize((size_t)n_rows * fs);
-        HIP_TRY(hipMemcpyAsync(frames.data(), st->d_fsum, frames.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(frames.data(), st->d_fsum.get(), frames.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (mode == GRAIL_LEVEL_ACTIVE) {
-        active.assign(n_rows, 0.0);
+    // the per-row level of the two modes that have one (the other two go by the sums and peaks themselves)
+    if (loud) {
+        level.resize(n_rows);
+        for (uint32_t i = 0; i < n_rows; ++i) level[i] = grail_loudness_level(sumsq[i]);
+    } else if (mode == GRAIL_LEVEL_ACTIVE) {
+        level.assign(n_rows, 0.0);
         // (frames past a row's last were never written: grail_active_level reads ceil(len / frame) of them)
-        for (uint32_t r = 0; r < n_rows && fs; ++r)
-            active[r] = grail_active_level(frames.data() + (size_t)r * fs, row_len[r], GRAIL_LEVEL_FRAME,
-                                           GRAIL_LEVEL_ACTIVE_FLOOR_DB);
+        for (uint32_t i = 0; i < n_rows && fs; ++i)
+            level[i] = grail_active_level(frames.data() + (size_t)i * fs, row_len[i], GRAIL_LEVEL_FRAME,
+                                          GRAIL_LEVEL_ACTIVE_FLOOR_DB);
     }
     uint32_t unleveled = 0;
-    rc = grail_level_gains(mode, sumsq.data(), peak.data(), bad.data(), row_len, active.data(), n_rows, item_rows,
-                           item_level_db, n_items, gains, &unleveled);
+    rc = grail_level_gains(mode, loud ? nullptr : sumsq.data(), loud ? nullptr : peak.data(), bad.data(), row_len, level.data(),
+                           n_rows, item_rows, item_level_db, n_items, gains, &unleveled);
     if (rc) return fail(rc, "grail_batch_mix_leveled: grail_level_gains refused the block");
     *n_unleveled += unleveled;
     return ceiling_db ? limit_block_gains(tp.data(), n_rows, item_rows, n_items, *ceiling_db, gains, n_limited) : GRAIL_OK;
@@ -326,23 +297,23 @@ extern "C" {
 int grail_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
                        uint32_t n_rows, double *sumsq_dev, float *peak_dev, uint32_t *nonfinite_dev)
 {
+    const Rows r{rows_dev, row_stride, len_dev, n_rows};
     int rc = bind_device(ctx, "grail_levels_async");
     if (rc) return rc;
-    if (n_rows == 0) return GRAIL_OK;
-    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_levels_async: NULL buffer");
-    if (!sumsq_dev && !peak_dev && !nonfinite_dev) return GRAIL_OK;
-    return totals(ctx, "grail_levels_async", rows_dev, row_stride, len_dev, n_rows, sumsq_dev, peak_dev, nonfinite_dev);
+    bool measure;
+    if ((rc = check_rows("grail_levels_async", r, sumsq_dev || peak_dev || nonfinite_dev, &measure)) || !measure) return rc;
+    return totals(ctx, "grail_levels_async", r, sumsq_dev, peak_dev, nonfinite_dev);
 }
 
 int grail_true_peak_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
                           uint32_t n_rows, double *true_peak_dev, uint32_t *nonfinite_dev)
 {
+    const Rows r{rows_dev, row_stride, len_dev, n_rows};
     int rc = bind_device(ctx, "grail_true_peak_async");
     if (rc) return rc;
-    if (n_rows == 0) return GRAIL_OK;
-    if (!len_dev || (row_stride && !rows_dev)) return fail(GRAIL_ERR_INVALID_ARG, "grail_true_peak_async: NULL buffer");
-    if (!true_peak_dev && !nonfinite_dev) return GRAIL_OK;
-    return true_peak(ctx, "grail_true_peak_async", rows_dev, row_stride, len_dev, n_rows, true_peak_dev, nonfinite_dev);
+    bool measure;
+    if ((rc = check_rows("grail_true_peak_async", r, true_peak_dev || nonfinite_dev, &measure)) || !measure) return rc;
+    return true_peak(ctx, "grail_true_peak_async", r, true_peak_dev, nonfinite_dev);
 }
 
 int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev, uint32_t n_rows,
@@ -376,14 +347,14 @@ int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride
     const uint64_t chunks = limit_grid_chunks(row_stride);
     if ((uint64_t)n_groups * chunks > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: more than 2^31 chunks");
     if (chunks) {               // (rows of no samples: 1.0f, 0, 0 from the totals alone)
-        if ((rc = reserve(ctx, &st->d_lstat, &st->cap_lstat, (size_t)n_groups * (size_t)chunks * limit_chunk_bytes()))) return rc;
+        if ((rc = st->d_lstat.reserve(ctx->stream, (size_t)n_groups * (size_t)chunks * limit_chunk_bytes()))) return rc;
         const hipError_t e = launch_limit_frames(rows_dev, row_stride, len_dev, n_groups, group, ceiling, lookahead_log2,
-                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat, ctx->stream);
+                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat.get(), ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "limiter frames kernel launch");
     }
     if (!min_gain_dev && !n_limited_dev && !nonfinite_dev) return GRAIL_OK;
-    const hipError_t e = launch_limit_totals(len_dev, row_stride, n_groups, group, lookahead_log2, st->d_lstat, (uint32_t)chunks,
-                                             min_gain_dev, n_limited_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_limit_totals(len_dev, row_stride, n_groups, group, lookahead_log2, st->d_lstat.get(),
+                                             (uint32_t)chunks, min_gain_dev, n_limited_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "limiter totals kernel launch");
     return GRAIL_OK;
 }
@@ -392,7 +363,7 @@ int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_str
                          uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
                          double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
 {
-    return loudness_call(ctx, "grail_loudness_async", false, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef,
+    return loudness_call(ctx, "grail_loudness_async", false, {rows_dev, row_stride, len_dev, n_rows}, sample_rate, coef,
                          gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev);
 }
 
@@ -400,8 +371,8 @@ int grail_loudness_segmented_async(grail_ctx *ctx, const float *rows_dev, uint64
                                    uint32_t n_rows, uint32_t sample_rate, const double *coef, double *gated_ms_dev,
                                    double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *nonfinite_dev)
 {
-    return loudness_call(ctx, "grail_loudness_segmented_async", true, rows_dev, row_stride, len_dev, n_rows, sample_rate, coef,
-                         gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev);
+    return loudness_call(ctx, "grail_loudness_segmented_async", true, {rows_dev, row_stride, len_dev, n_rows}, sample_rate,
+                         coef, gated_ms_dev, hop_sumsq_dev, hops_stride, nonfinite_dev);
 }
 
 int grail_frame_levels_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,

@@ -8,17 +8,17 @@ using namespace grail;
 using namespace grail::host;
 
 // Per context (grail_ctx::mix_state): the plan of the last mix and the device buffers it went to, and grail_batch_mix's
-// scratch (one block of rows and their lengths) — all grown, never shrunk, freed by grail_destroy, so that a mix in steady
-// state costs no hipMalloc / hipFree (those of a 25 GB block cost a third of a render, and vary from call to call).  The
-// host vectors of the plan are rebuilt only once the upload from them has completed.
+// scratch (one block of rows and their lengths) — kept from call to call and only ever grown (DeviceBuffer::reserve), so
+// that a mix in steady state allocates nothing on the device (allocating and freeing a 25 GB block costs a third of a
+// render, and varies from call to call).  The plan's buffers grow by a quarter more than asked for, so that slowly growing
+// plans do not reallocate every call; the block's to the exact size.  The host vectors of the plan are rebuilt only once
+// the upload from them has completed.
 struct MixState {
     mix::Plan plan;
-    mix::MixItem *d_items = nullptr;
-    uint32_t *d_tile_start = nullptr, *d_tile_items = nullptr;
-    size_t cap_items = 0, cap_tile_start = 0, cap_tile_items = 0;
-    float *d_rows = nullptr;          // grail_batch_mix: rows of one block
-    uint32_t *d_len = nullptr;        // ... and their lengths
-    size_t cap_rows = 0, cap_len = 0;
+    DeviceBuffer<mix::MixItem> d_items;
+    DeviceBuffer<uint32_t> d_tile_start, d_tile_items;
+    DeviceBuffer<float> d_rows;       // grail_batch_mix: rows of one block
+    DeviceBuffer<uint32_t> d_len;     // ... and their lengths
     hipEvent_t uploaded = nullptr;
     bool pending = false;
 };
@@ -30,11 +30,6 @@ void mix_release(grail_ctx *ctx)
 {
     MixState *st = (MixState *)ctx->mix_state;
     if (!st) return;
-    if (st->d_items) (void)hipFree(st->d_items);
-    if (st->d_tile_start) (void)hipFree(st->d_tile_start);
-    if (st->d_tile_items) (void)hipFree(st->d_tile_items);
-    if (st->d_rows) (void)hipFree(st->d_rows);
-    if (st->d_len) (void)hipFree(st->d_len);
     if (st->uploaded) (void)hipEventDestroy(st->uploaded);
     delete st;
     ctx->mix_state = nullptr;
@@ -45,23 +40,7 @@ void mix_release(grail_ctx *ctx)
 
 namespace {
 
-// a buffer of at least n elements (headroom: a quarter more, so that slowly growing plans do not reallocate every call)
-template <typename T>
-int reserve(grail_ctx *ctx, T **p, size_t *cap, size_t n, bool headroom = true)
-{
-    n = std::max<size_t>(n, 1);
-    if (*cap >= n) return GRAIL_OK;
-    if (*p) {
-        HIP_TRY(hipStreamSynchronize(ctx->stream));    // (a queued mix may still read the old buffer)
-        HIP_TRY(hipFree(*p));
-        *p = nullptr;
-        *cap = 0;
-    }
-    const size_t want = headroom ? n + n / 4 : n;
-    HIP_TRY(hipMalloc((void **)p, want * sizeof(T)));
-    *cap = want;
-    return GRAIL_OK;
-}
+size_t quarter_more(size_t n) { return n + n / 4; }
 
 // grail_mix_async after bind(): the checks, the plan, its upload, the launch
 int mix_rows(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t row_stride, const uint32_t *row_len,
@@ -88,24 +67,24 @@ int mix_rows(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t ro
     const uint64_t wgs = (uint64_t)n_tracks * p.wgs_per_track;
     if (wgs == 0) return GRAIL_OK;
     int r;
-    if ((r = reserve(ctx, &st->d_items, &st->cap_items, p.items.size()))) return r;
-    if ((r = reserve(ctx, &st->d_tile_start, &st->cap_tile_start, p.tile_start.size()))) return r;
-    if ((r = reserve(ctx, &st->d_tile_items, &st->cap_tile_items, p.tile_items.size()))) return r;
+    if ((r = st->d_items.reserve(ctx->stream, p.items.size(), quarter_more(p.items.size())))) return r;
+    if ((r = st->d_tile_start.reserve(ctx->stream, p.tile_start.size(), quarter_more(p.tile_start.size())))) return r;
+    if ((r = st->d_tile_items.reserve(ctx->stream, p.tile_items.size(), quarter_more(p.tile_items.size())))) return r;
     if (!p.items.empty())
-        HIP_TRY(hipMemcpyAsync(st->d_items, p.items.data(), p.items.size() * sizeof(mix::MixItem), hipMemcpyHostToDevice,
+        HIP_TRY(hipMemcpyAsync(st->d_items.get(), p.items.data(), p.items.size() * sizeof(mix::MixItem), hipMemcpyHostToDevice,
                                ctx->stream));
-    HIP_TRY(hipMemcpyAsync(st->d_tile_start, p.tile_start.data(), p.tile_start.size() * sizeof(uint32_t),
+    HIP_TRY(hipMemcpyAsync(st->d_tile_start.get(), p.tile_start.data(), p.tile_start.size() * sizeof(uint32_t),
                            hipMemcpyHostToDevice, ctx->stream));
     if (!p.tile_items.empty())
-        HIP_TRY(hipMemcpyAsync(st->d_tile_items, p.tile_items.data(), p.tile_items.size() * sizeof(uint32_t),
+        HIP_TRY(hipMemcpyAsync(st->d_tile_items.get(), p.tile_items.data(), p.tile_items.size() * sizeof(uint32_t),
                                hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipEventRecord(st->uploaded, ctx->stream));
     st->pending = true;
     MixArgs a{};
     a.rows = rows_dev;
-    a.items = st->d_items;
-    a.tile_start = st->d_tile_start;
-    a.tile_items = st->d_tile_items;
+    a.items = st->d_items.get();
+    a.tile_start = st->d_tile_start.get();
+    a.tile_items = st->d_tile_items.get();
     a.tracks = tracks_dev;
     a.track_stride = track_stride;
     a.track_len = track_len;
@@ -171,7 +150,7 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
     uint64_t block = 2ull * 256ull * (uint64_t)std::max(ctx->cus, 1);
     size_t free_bytes = 0, total_bytes = 0;
     HIP_TRY(hipMemGetInfo(&free_bytes, &total_bytes));
-    const uint64_t fit = (uint64_t)((free_bytes + st->cap_rows * sizeof(float)) / 2) / (stride * sizeof(float));
+    const uint64_t fit = (uint64_t)((free_bytes + st->d_rows.capacity() * sizeof(float)) / 2) / (stride * sizeof(float));
     if (fit == 0) return fail(GRAIL_ERR_OUT_OF_MEMORY, std::string(who) + ": not one row fits in half of the free HBM");
     block = std::min(block, fit);
     const bool one_piece = n <= block;
@@ -181,10 +160,10 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
     std::vector<std::vector<uint32_t>> of_block(n_blocks);
     if (!one_piece)
         for (uint32_t i = 0; i < n_items; ++i) of_block[item_rows[i] / block].push_back(i);
-    if ((rc = reserve(ctx, &st->d_rows, &st->cap_rows, rows_alloc * stride, false))) return rc;
-    if ((rc = reserve(ctx, &st->d_len, &st->cap_len, rows_alloc, false))) return rc;
-    float *const d_rows = st->d_rows;
-    uint32_t *const d_len = st->d_len;
+    if ((rc = st->d_rows.reserve(ctx->stream, rows_alloc * stride))) return rc;
+    if ((rc = st->d_len.reserve(ctx->stream, rows_alloc))) return rc;
+    float *const d_rows = st->d_rows.get();
+    uint32_t *const d_len = st->d_len.get();
     std::vector<uint32_t> sub_rows, sub_tracks;
     std::vector<uint64_t> sub_offs;
     std::vector<float> sub_gains, sub_levels;

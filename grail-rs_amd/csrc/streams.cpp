@@ -31,8 +31,7 @@ int grail_stream_open(grail_ctx *ctx, const grail_batch *batch, grail_stream **o
             s->L = ((uint64_t)batch->n_utt * 4 + 63) / 64 <= ctx_simds(ctx) ? 4 : ((uint64_t)batch->n_utt * 2 + 63) / 64 <= ctx_simds(ctx) ? 2 : 1;
     }
     s->lanes = state_lanes(batch->n_utt, s->L);
-    const size_t bytes = (size_t)state_words(s->L) * s->lanes * sizeof(uint32_t);
-    hipError_t e = hipMalloc((void **)&s->d_state, bytes ? bytes : 4);
+    const hipError_t e = s->d_state.alloc((size_t)state_words(s->L) * s->lanes);
     if (e != hipSuccess) {
         delete s;
         return hip_fail(e, "stream state allocation");
@@ -68,9 +67,9 @@ static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_sample
     a.segs = batch->d_segs;
     a.seg_offsets = batch->d_offsets;
     a.ring_cap = stream->ring_cap;
-    a.seg_counts = stream->d_counts;
-    a.seg_open = stream->d_open;
-    a.seg_consumed = stream->d_consumed;
+    a.seg_counts = stream->d_counts.get();
+    a.seg_open = stream->d_open.get();
+    a.seg_consumed = stream->d_consumed.get();
     a.voice_ids = batch->d_voice_ids;
     a.seeds = batch->d_seeds;
     a.perm = batch->d_perm;
@@ -107,7 +106,7 @@ static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_sample
             a.pipe = ctx->opt.pipe_round32 && ((uint64_t)batch->n_utt + 7) / 8 <= cus ? 2u : 1u;
         if (a.pipe) a.fast = 0u;
     }
-    a.state = stream->d_state;
+    a.state = stream->d_state.get();
     a.state_stride = stream->lanes;
     a.resume = stream->started ? 1u : 0u;
     HIP_TRY(hipEventRecord(ctx->ev_start, ctx->stream));
@@ -138,13 +137,6 @@ int grail_stream_close(grail_ctx *ctx, grail_stream *stream)
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    if (stream->d_state) (void)hipFree(stream->d_state);
-    if (stream->d_counts) (void)hipFree(stream->d_counts);
-    if (stream->d_open) (void)hipFree(stream->d_open);
-    if (stream->d_consumed) (void)hipFree(stream->d_consumed);
-    if (stream->d_new) (void)hipFree(stream->d_new);
-    if (stream->d_new_elems) (void)hipFree(stream->d_new_elems);
-    if (stream->d_new_offs) (void)hipFree(stream->d_new_offs);
     for (int i = 0; i < 2; ++i) {
         if (stream->h_stage[i]) (void)hipHostFree(stream->h_stage[i]);
         if (stream->ev_stage[i]) (void)hipEventDestroy(stream->ev_stage[i]);
@@ -153,7 +145,7 @@ int grail_stream_close(grail_ctx *ctx, grail_stream *stream)
         free_batch_buffers(stream->own);
         delete stream->own;
     }
-    delete stream;
+    delete stream;          // (its device buffers go with it)
     return GRAIL_OK;
 }
 
@@ -201,10 +193,12 @@ int grail_stream_open_live(grail_ctx *ctx, uint32_t n_utt, const uint32_t *voice
     };
     zeroed((void **)&b->d_segs, ring_rows * sizeof(DevSeg));
     if (caller_built_elems) zeroed((void **)&b->d_elems, ring_rows * ELEM_FLOATS * sizeof(float));
-    zeroed((void **)&s->d_counts, (size_t)n_utt * 4);
-    zeroed((void **)&s->d_consumed, (size_t)n_utt * 4);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_open, (size_t)n_utt * 4);
-    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)s->d_open, 1, n_utt, ctx->stream);
+    for (DeviceBuffer<uint32_t> *p : {&s->d_counts, &s->d_consumed}) {
+        if (e == hipSuccess) e = p->alloc(n_utt);
+        if (e == hipSuccess) e = hipMemsetAsync(p->get(), 0, (size_t)n_utt * 4, ctx->stream);
+    }
+    if (e == hipSuccess) e = s->d_open.alloc(n_utt);
+    if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)s->d_open.get(), 1, n_utt, ctx->stream);
     if (e == hipSuccess && voice_ids) {
         e = hipMalloc((void **)&b->d_voice_ids, (size_t)n_utt * 4);
         if (e == hipSuccess) e = hipMemcpyAsync(b->d_voice_ids, voice_ids, (size_t)n_utt * 4, hipMemcpyHostToDevice, ctx->stream);
@@ -219,8 +213,7 @@ int grail_stream_open_live(grail_ctx *ctx, uint32_t n_utt, const uint32_t *voice
     s->voices_epoch = ctx->voices_epoch;
     s->L = ctx->opt.lanes_option ? ctx->opt.lanes_option : auto_lanes_per_utt(n_utt, ctx_simds(ctx));
     s->lanes = state_lanes(n_utt, s->L);
-    const size_t bytes = (size_t)state_words(s->L) * s->lanes * sizeof(uint32_t);
-    if (e == hipSuccess) e = hipMalloc((void **)&s->d_state, bytes ? bytes : 4);
+    if (e == hipSuccess) e = s->d_state.alloc((size_t)state_words(s->L) * s->lanes);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // voice_ids / jitter_seeds are the caller's
     if (e != hipSuccess) {
         const int st = hip_fail(e, "live stream allocation");
@@ -262,7 +255,7 @@ static int live_append(grail_ctx *ctx, grail_stream *s, const std::vector<DevSeg
     };
     if (!fits()) {
         // what the host knows of the Sequencers' progress is a lower bound: ask the device
-        HIP_TRY(hipMemcpyAsync(s->consumed.data(), s->d_consumed, (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(s->consumed.data(), s->d_consumed.get(), (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (!fits()) {
             char msg[200];
@@ -275,21 +268,14 @@ static int live_append(grail_ctx *ctx, grail_stream *s, const std::vector<DevSeg
     for (uint32_t u = 0; u < n_utt; ++u)
         if (seg_offsets[u + 1] > seg_offsets[u] && !s->open[u])
             return fail(GRAIL_ERR_INVALID_ARG, "an utterance of the live stream has been finished: nothing can be appended to it");
+    // the staging on the device: at least doubled when it grows (the first reserve that frees has waited for the stream,
+    // the next finds it idle)
+    const size_t cap_new = std::max<size_t>(std::max<size_t>(n_new, 2 * s->d_new.capacity()), 64);
+    int rc;
+    if ((rc = s->d_new.reserve(ctx->stream, n_new, cap_new))) return rc;
+    if (elems && (rc = s->d_new_elems.reserve(ctx->stream, (size_t)n_new * ELEM_FLOATS, cap_new * ELEM_FLOATS))) return rc;
+    if ((rc = s->d_new_offs.reserve(ctx->stream, (size_t)n_utt + 1))) return rc;
     hipError_t e = hipSuccess;
-    if (s->new_cap < n_new || (elems && !s->d_new_elems)) {
-        const size_t cap_new = std::max<size_t>(std::max<size_t>(n_new, 2 * s->new_cap), 64);
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        if (s->d_new) (void)hipFree(s->d_new);
-        if (s->d_new_elems) (void)hipFree(s->d_new_elems);
-        s->d_new = nullptr;
-        s->d_new_elems = nullptr;
-        s->new_cap = 0;
-        e = hipMalloc((void **)&s->d_new, cap_new * sizeof(DevSeg));
-        if (e == hipSuccess && elems) e = hipMalloc((void **)&s->d_new_elems, cap_new * ELEM_FLOATS * sizeof(float));
-        if (e == hipSuccess && !s->d_new_offs) e = hipMalloc((void **)&s->d_new_offs, ((size_t)n_utt + 1) * 4);
-        if (e != hipSuccess) return hip_fail(e, "grail_stream_append staging");
-        s->new_cap = cap_new;
-    }
     // The caller's (and this function's) buffers go through a pinned buffer of the stream's own, so that the call can return
     // with its copies queued: with tens of thousands of live streams fed a phoneme at a time a synchronisation per append
     // — behind every kernel queued so far — was the pace of the whole session.
@@ -314,13 +300,14 @@ static int live_append(grail_ctx *ctx, grail_stream *s, const std::vector<DevSeg
     std::memcpy(h, segs.data(), b_segs);
     std::memcpy(h + b_segs, seg_offsets, b_offs);
     if (elems) std::memcpy(h + b_segs + b_offs, elems, b_elems);
-    e = hipMemcpyAsync(s->d_new, h, b_segs, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(s->d_new_offs, h + b_segs, b_offs, hipMemcpyHostToDevice, ctx->stream);
-    if (e == hipSuccess && elems) e = hipMemcpyAsync(s->d_new_elems, h + b_segs + b_offs, b_elems, hipMemcpyHostToDevice, ctx->stream);
+    e = hipMemcpyAsync(s->d_new.get(), h, b_segs, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->d_new_offs.get(), h + b_segs, b_offs, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess && elems)
+        e = hipMemcpyAsync(s->d_new_elems.get(), h + b_segs + b_offs, b_elems, hipMemcpyHostToDevice, ctx->stream);
     // (stream order: behind every kernel that still reads the rings, ahead of every kernel that will)
     if (e == hipSuccess)
-        e = launch_ring_append(s->own->d_segs, s->own->d_elems, s->d_counts, cap, s->d_new, elems ? s->d_new_elems : nullptr,
-                               s->d_new_offs, n_utt, ctx->stream);
+        e = launch_ring_append(s->own->d_segs, s->own->d_elems, s->d_counts.get(), cap, s->d_new.get(),
+                               elems ? s->d_new_elems.get() : nullptr, s->d_new_offs.get(), n_utt, ctx->stream);
     if (e == hipSuccess) e = hipEventRecord(s->ev_stage[slot], ctx->stream);
     if (e != hipSuccess) {
         // some of the copies may be queued and still reading the pinned buffer, which the next append would overwrite (the
@@ -416,7 +403,7 @@ int grail_stream_finish(grail_ctx *ctx, grail_stream *stream, const uint8_t *whi
         if (!which || which[u]) stream->open[u] = 0;
         open[u] = stream->open[u];
     }
-    HIP_TRY(hipMemcpyAsync(stream->d_open, open.data(), (size_t)n_utt * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(stream->d_open.get(), open.data(), (size_t)n_utt * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     return GRAIL_OK;
 }
@@ -428,7 +415,8 @@ int grail_stream_pending(grail_ctx *ctx, grail_stream *stream, uint32_t *pending
     if (!stream || !stream->own) return fail(GRAIL_ERR_INVALID_ARG, "not a live stream (grail_stream_open_live)");
     if (!pending) return fail(GRAIL_ERR_INVALID_ARG, "pending is NULL");
     const uint32_t n_utt = stream->own->n_utt;
-    HIP_TRY(hipMemcpyAsync(stream->consumed.data(), stream->d_consumed, (size_t)n_utt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(stream->consumed.data(), stream->d_consumed.get(), (size_t)n_utt * 4, hipMemcpyDeviceToHost,
+                           ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     for (uint32_t u = 0; u < n_utt; ++u) pending[u] = stream->appended[u] - stream->consumed[u];
     return GRAIL_OK;
