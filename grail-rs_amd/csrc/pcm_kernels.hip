@@ -39,7 +39,8 @@ __global__ __launch_bounds__(256) void pcm16_kernel(const float *__restrict__ in
 
 // Per-row digest of a rendered batch: the sum of the samples' bit patterns (mod 2^64), the
 // largest magnitude, and the number of non-finite samples.  Lets a caller (and the full-size
-// tests) compare 25 GB of output on the device instead of copying it over PCIe.
+// tests) compare 25 GB of output on the device instead of copying it over PCIe.  A sum cannot see
+// samples permuted within a row: compare_kernel can (and cannot see the sign of a zero, which this can).
 __global__ __launch_bounds__(256) void digest_kernel(const float *__restrict__ in, uint64_t in_stride,
                                                      const uint32_t *__restrict__ len,
                                                      unsigned long long *__restrict__ sums,
@@ -82,8 +83,9 @@ __global__ __launch_bounds__(256) void digest_kernel(const float *__restrict__ i
 }
 
 // Per-row distance between two renderings of the same batch (tolerance mode against exact mode at
-// sizes no CPU oracle reaches): the largest |a - b|, the sum of squared differences, and the number of
-// samples at which exactly one of the two is non-finite or the lengths disagree.
+// sizes no CPU oracle reaches): the largest finite |a - b|, the sum of its squares, and the number of
+// samples whose |a - b| is not finite (unless both carry the same bits or both are NaN), plus 1 where
+// the lengths disagree.  Like digest_kernel it trusts every length to be at most the stride.
 __global__ __launch_bounds__(256) void compare_kernel(const float *__restrict__ a, const float *__restrict__ b,
                                                       uint64_t stride, const uint32_t *__restrict__ len_a,
                                                       const uint32_t *__restrict__ len_b,

@@ -1164,7 +1164,8 @@ class Context:
         return tuple(r[:n_groups] for r in res)
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
-        """(bit-pattern sums mod 2^64, max |x|, non-finite counts) per row, computed on the device."""
+        """(bit-pattern sums mod 2^64, max finite |x|, non-finite counts) per row, computed on the device (every length
+        at most the stride).  A sum is blind to samples permuted within a row: use compare beside it."""
         sums = np.zeros(max(n_utt, 1), dtype=np.uint64)
         maxabs = np.zeros(max(n_utt, 1), dtype=np.float32)
         bad = np.zeros(max(n_utt, 1), dtype=np.uint32)
@@ -1173,7 +1174,9 @@ class Context:
         return sums[:n_utt], maxabs[:n_utt], bad[:n_utt]
 
     def compare(self, a_dev, b_dev, stride, len_a_dev, len_b_dev, n_utt):
-        """(max |a-b|, sum (a-b)^2, structural mismatches) per row of two device renderings."""
+        """(max |a-b|, sum (a-b)^2, structural mismatches) per row of two device renderings, over the first len_a samples
+        (every length at most the stride).  A sample whose |a-b| is not finite enters neither number and is a mismatch
+        unless both sides carry the same bits or both are NaN; +1 where the lengths differ; -0.0 equals +0.0."""
         md = np.zeros(max(n_utt, 1), dtype=np.float32)
         sq = np.zeros(max(n_utt, 1), dtype=np.float64)
         bad = np.zeros(max(n_utt, 1), dtype=np.uint32)

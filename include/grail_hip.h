@@ -507,7 +507,10 @@ int grail_say_batch(grail_ctx *ctx, const char *const *texts_utf8, uint32_t n_te
                     const uint32_t *voice_ids, const uint32_t *jitter_seeds, float *out,
                     uint64_t out_stride, uint32_t *out_len, uint32_t flags);
 /* `(x * i16::MAX as f32) as i16` of examples/cli.rs:49 on the device: rows of f32 -> rows of
- * i16, first len_dev[u] samples of each row; all pointers are device memory. Asynchronous. */
+ * i16, first len_dev[u] samples of each row; all pointers are device memory. Asynchronous.
+ * max_len must be at least every len_dev[u] (the launch is sized from it: samples of a row at or past
+ * max_len are not converted), and every len_dev[u] at most both strides.  Any alignment of the two
+ * bases and any strides give the same samples; 16-byte aligned addresses take the vector path. */
 int grail_pcm16_async(grail_ctx *ctx, const float *in_dev, uint64_t in_stride,
                       const uint32_t *len_dev, uint32_t n_utt, uint32_t max_len,
                       int16_t *out_dev, uint64_t out_stride);
@@ -525,15 +528,26 @@ int grail_synthesize_batch_pcm16(grail_ctx *ctx, const grail_phoneme_elem *segs,
                                  uint64_t out_stride, uint32_t *out_len, uint32_t flags);
 /* Per-row digest of rendered rows, computed on the device (comparing a 25 GB batch over PCIe is
  * pointless): sums[u] = sum of the samples' IEEE bit patterns mod 2^64, maxabs[u] = largest
- * finite |x|, nonfinite[u] = count of NaN/Inf, over the first len_dev[u] samples of row u.
+ * finite |x| (0 where there is none), nonfinite[u] = count of NaN/Inf, over the first len_dev[u]
+ * samples of row u.  Every len_dev[u] must be at most in_stride (the length is not clamped).
+ * The sum sees any single changed sample, the sign of a zero included, but it is blind to a
+ * permutation of the samples within a row: use grail_batch_compare beside it where the order matters.
  * in_dev/len_dev are device memory, the three results host memory [n_utt].  Synchronous. */
 int grail_batch_digest(grail_ctx *ctx, const float *in_dev, uint64_t in_stride,
                        const uint32_t *len_dev, uint32_t n_utt, uint64_t *sums, float *maxabs,
                        uint32_t *nonfinite);
 /* Per-row distance between two renderings of one batch, computed on the device (fast mode against
- * exact mode at full size): maxdiff[u] = max |a - b|, sumsq[u] = sum (a - b)^2 over the first
- * len_a_dev[u] samples, mismatches[u] = samples where exactly one side is non-finite, plus 1 if
- * the two lengths differ.  a/b/len_* are device memory, the three results host memory [n_utt]. */
+ * exact mode at full size), over the first len_a_dev[u] samples of row u.  d = |a - b| is computed in
+ * binary32 (denormals kept).  Where d is finite it enters maxdiff[u] = max d and sumsq[u] = sum of
+ * (double)d^2 (in no particular order).  Where d is not finite the sample enters neither, and it counts
+ * in mismatches[u] unless both sides carry the same bits or both are NaN:
+ *     (NaN, NaN) of any payloads, (+Inf, +Inf), (-Inf, -Inf)        0
+ *     (+Inf, -Inf), (NaN, +-Inf), (NaN, finite), (finite, +-Inf)     1
+ *     two finite samples whose difference overflows (3e38, -3e38)   1
+ * mismatches[u] counts 1 more if len_a_dev[u] != len_b_dev[u] (the rows are still compared over
+ * len_a_dev[u] samples).  -0.0 and +0.0 compare equal (d = 0): compare is blind to the sign of a zero,
+ * which grail_batch_digest sees.  Every length must be at most stride (the lengths are not clamped).
+ * a/b/len_* are device memory, the three results host memory [n_utt].  Synchronous. */
 int grail_batch_compare(grail_ctx *ctx, const float *a_dev, const float *b_dev, uint64_t stride,
                         const uint32_t *len_a_dev, const uint32_t *len_b_dev, uint32_t n_utt,
                         float *maxdiff, double *sumsq, uint32_t *mismatches);

@@ -268,19 +268,23 @@ def test_rccl_voice_broadcast_single_rank(gpu_ctx):
 def test_config3_and_4_full_size_on_device_digest(gpu_ctx, n_voices):
     """BASELINE configs 3 and 4 at FULL size (65536 utterances x 2 s, 25 GB of PCM left in HBM):
     lengths, finiteness and the normalisation bound over all 6.3e9 samples via the on-device digest;
-    a checksum of checksums between two lane mappings (batch invariance at scale); bit parity of
-    138 utterances spread over the batch against the oracle through their digests."""
+    a checksum of checksums between two lane mappings (batch invariance at scale) AND, the first
+    rendering kept in a second buffer, an on-device compare of the two: no sample differs (the digest,
+    a sum, cannot see samples permuted within a row; compare cannot see the sign of a zero, the digest
+    can); bit parity of 138 utterances spread over the batch against the oracle, through their digests
+    and copied back sample by sample."""
     n_utt = 65536
     voices = W.single_voice() if n_voices == 1 else W.preset_voices(8)
     gpu_ctx.set_voices(voices)
     segs, offs, vids, seeds = W.make_batch(n_utt, n_voices=n_voices)
     stride = W.max_samples()
     b = gpu_ctx.upload(segs, offs, vids, seeds)
-    d_out = gpu_ctx.device_alloc(n_utt * stride * 4)
-    d_len = gpu_ctx.device_alloc(n_utt * 4)
+    d_rows = {0: gpu_ctx.device_alloc(n_utt * stride * 4), 2: gpu_ctx.device_alloc(n_utt * stride * 4)}
+    d_lens = {0: gpu_ctx.device_alloc(n_utt * 4), 2: gpu_ctx.device_alloc(n_utt * 4)}
     digests = {}
     try:
         for lanes in (0, 2):
+            d_out, d_len = d_rows[lanes], d_lens[lanes]
             gpu_ctx.set_option("lanes_per_utterance", lanes)
             b.synthesize_async(d_out, stride, d_len)
             gpu_ctx.sync()
@@ -292,20 +296,26 @@ def test_config3_and_4_full_size_on_device_digest(gpu_ctx, n_voices):
             assert maxabs.max() <= 1.0                  # synthesize_normalized (src/lib.rs:602)
             assert (maxabs > 0.01).mean() > 0.9         # (an all-Silence utterance is exactly 0)
             digests[lanes] = sums
+        assert np.array_equal(digests[0], digests[2])   # 65536 checksums agree across lane mappings
+        maxdiff, sumsq, mismatches = gpu_ctx.compare(d_rows[0], d_rows[2], stride, d_lens[0], d_lens[2], n_utt)
+        assert mismatches.sum() == 0                    # ... and so does every sample, position by position
+        assert maxdiff.max() == 0 and sumsq.max() == 0, (np.nonzero(maxdiff)[0][:8], maxdiff.max())
+        pick = sorted(set([0, 1, 63, 64, 1023, 1024, 32767, 32768, 65534, 65535] +
+                          [int(u) for u in np.random.default_rng(7).integers(0, n_utt, 128)]))
+        sub = np.concatenate([segs[offs[u]:offs[u + 1]] for u in pick])
+        sub_offs = np.arange(len(pick) + 1, dtype=np.uint32) * 4
+        ref, ref_len = O.synthesize_batch(ovoices(voices), sub, sub_offs, vids[pick], seeds[pick], stride)
+        for k, u in enumerate(pick):
+            want = int(ref[k, :ref_len[k]].view(np.uint32).astype(np.uint64).sum())
+            assert int(digests[0][u]) == want, u
+            row = np.empty(int(ref_len[k]), dtype=np.float32)
+            gpu_ctx.d2h(row, d_rows[0], row.nbytes, offset=u * stride * 4)
+            assert np.array_equal(row.view(np.uint32), ref[k, :ref_len[k]].view(np.uint32)), u
     finally:
         gpu_ctx.set_option("lanes_per_utterance", 0)
-        gpu_ctx.device_free(d_out)
-        gpu_ctx.device_free(d_len)
+        for p in list(d_rows.values()) + list(d_lens.values()):
+            gpu_ctx.device_free(p)
         b.free()
-    assert np.array_equal(digests[0], digests[2])       # 65536 checksums agree across lane mappings
-    pick = sorted(set([0, 1, 63, 64, 1023, 1024, 32767, 32768, 65534, 65535] +
-                      [int(u) for u in np.random.default_rng(7).integers(0, n_utt, 128)]))
-    sub = np.concatenate([segs[offs[u]:offs[u + 1]] for u in pick])
-    sub_offs = np.arange(len(pick) + 1, dtype=np.uint32) * 4
-    ref, ref_len = O.synthesize_batch(ovoices(voices), sub, sub_offs, vids[pick], seeds[pick], stride)
-    for k, u in enumerate(pick):
-        want = int(ref[k, :ref_len[k]].view(np.uint32).astype(np.uint64).sum())
-        assert int(digests[0][u]) == want, u
 
 
 def _elem(rng, amp_mask):
