@@ -29,6 +29,7 @@
 #include <vector>
 
 #include "../../include/grail_hip.h"
+#include "division_window.h"
 #include "kernels.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)

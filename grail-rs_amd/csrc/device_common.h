@@ -2,6 +2,7 @@
 // Reference: random_f32 src/lib.rs:36-55, tan_approx :63-70, exp_approx :75-82, Selector::next :990-1005.
 #pragma once
 
+#include "division_window.h"
 #include "kernels.h"
 
 namespace grail {

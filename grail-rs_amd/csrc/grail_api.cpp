@@ -150,7 +150,7 @@ int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowSta
         for (uint32_t u = 0; u < n_utt; ++u) {
             const RowStats &r = rows[u];
             const bool lean = r.plain && r.min_length >= 2.0f * ctx->facts.max_dt &&
-                              r.min_pitch * 0.999f - 1.002f * ctx->facts.max_pitch_jitter >= 9.5367431640625e-07f;
+                              r.min_pitch * window::MARGIN_DOWN - window::JITTER_MARGIN * ctx->facts.max_pitch_jitter >= window::X_LO;
             outlier[u] = lean ? 0 : 1;
             n_out += outlier[u];
         }

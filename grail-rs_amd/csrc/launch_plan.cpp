@@ -171,7 +171,7 @@ bool batch_live4_any_blend(const grail_ctx *ctx, const grail_batch *batch)
             used_voices_all(ctx, batch, ctx->facts.voices_live4_ok, [](const VoiceInfo &v) { return v.live4_ok; })) &&
            batch->plain &&
            batch->min_length >= 2.0f * ctx->facts.max_dt &&
-           batch->min_pitch * 0.999f - 1.002f * ctx->facts.max_pitch_jitter >= 9.5367431640625e-07f;
+           batch->min_pitch * window::MARGIN_DOWN - window::JITTER_MARGIN * ctx->facts.max_pitch_jitter >= window::X_LO;
 }
 // ... and (the lane kernels' four-formant instantiations) every blend length a power of two
 bool batch_live4(const grail_ctx *ctx, const grail_batch *batch)
@@ -326,7 +326,7 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
         used_voices_all(ctx, batch, ctx->facts.voices_scan_ok, [](const VoiceInfo &v) { return v.scan_ok; }) &&
         (batch->phoneme_mode || (batch->elems_scan_ok && batch->elems_warmup_epoch == ctx->voices_epoch)) &&
         batch->plain && batch->min_length >= 2.0f * ctx->facts.max_dt &&
-        batch->min_pitch * 0.999f - 1.002f * ctx->facts.max_pitch_jitter >= 9.5367431640625e-07f) {
+        batch->min_pitch * window::MARGIN_DOWN - window::JITTER_MARGIN * ctx->facts.max_pitch_jitter >= window::X_LO) {
         scan.scan = true;
         scan.live4 = l4ab ? 1u : 0u;                          // (the scan kernel takes any blend length)
         // three-stage workgroups for few utterances (tools/scan_split_crossover.py: up to ~1500 with four

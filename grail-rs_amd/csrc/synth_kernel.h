@@ -223,7 +223,11 @@ __global__ __launch_bounds__(64 * WAVES, MIN_WAVES_PER_SIMD) void synth_kernel(c
         if constexpr (LIVE)
             if (A.ring_cap != 0u && j == L - 1 && A.seg_consumed) A.seg_consumed[u] = seg_pos;
     }
-    if (emit && lane == 0 && slow_steps) atomicAdd(A.truncated + 1, slow_steps);
+    // (a lane decides for its own formants and its own utterance whether a pair is inside the window, and one lane outside
+    // takes its whole wave through the general step: the wave reports the most such steps any ONE of its lanes took,
+    // so a single refused lane anywhere in the wave shows)
+    const uint32_t wave_slow_steps = wave_umax(slow_steps);
+    if (emit && lane == 0 && wave_slow_steps) atomicAdd(A.truncated + 1, wave_slow_steps);
     if (emit && lane == 0 && fast_tiles) atomicAdd(A.truncated + 2, fast_tiles);
     if (emit && lane == 0 && general_steps) atomicAdd(A.truncated + 3, general_steps);
 #ifdef GRAIL_FAST_PROF

@@ -10,6 +10,24 @@ __device__ __forceinline__ uint32_t umin_dpp(const uint32_t x)
     const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, ROW_MASK, 0xF, false);
     return o < x ? o : x;
 }
+// max(x, x of the lane the DPP control names); lanes without a source keep their own
+template <int CTRL, int ROW_MASK>
+__device__ __forceinline__ uint32_t umax_dpp(const uint32_t x)
+{
+    const uint32_t o = (uint32_t)__builtin_amdgcn_update_dpp((int)x, (int)x, CTRL, ROW_MASK, 0xF, false);
+    return o > x ? o : x;
+}
+// the largest x of the wave's 64 lanes, in every lane's hands as a scalar (six DPP steps leave it in lane 63)
+__device__ __forceinline__ uint32_t wave_umax(uint32_t x)
+{
+    x = umax_dpp<0x111, 0xF>(x);    // row_shr:1
+    x = umax_dpp<0x112, 0xF>(x);    // row_shr:2
+    x = umax_dpp<0x114, 0xF>(x);    // row_shr:4
+    x = umax_dpp<0x118, 0xF>(x);    // row_shr:8
+    x = umax_dpp<0x142, 0xA>(x);    // row_bcast:15
+    x = umax_dpp<0x143, 0xC>(x);    // row_bcast:31
+    return (uint32_t)__builtin_amdgcn_readlane((int)x, 63);
+}
 // lane i takes lane i-1's value (within its row of 16 lanes)
 __device__ __forceinline__ float dpp_from_lane_below(float x)
 {
@@ -232,26 +250,23 @@ __device__ __forceinline__ bool pair_is_safe(const Part<NV, V> &X, const Part<NV
                                              float blend_length, float jinc, float d_ffreq,
                                              float d_freq)
 {
-    constexpr float X_LO = 9.5367431640625e-07f;        // 2^-20
-    constexpr float X_HI = 0.5f - 9.5367431640625e-07f;
-    constexpr float W_LO = 1.8189894035458565e-12f;     // 2^-39 (2x margin over 2^-40)
-    constexpr float W_HI = 512.0f;                      // 2^9   (2x margin under 2^10)
-    const float jm = 1.002f * __builtin_fabsf(d_ffreq);
+    using namespace window;                             // the numbers: division_window.h
+    const float jm = JITTER_MARGIN * __builtin_fabsf(d_ffreq);
     // carrier frequency (the polyBLEP divisor, src/lib.rs:505/509): in [2^-20, 1]; the
     // dividend is the phase or phase-1, a sum of such frequencies: 0 or >= 2^-24 in magnitude
-    const float jf = 1.002f * __builtin_fabsf(d_freq);
+    const float jf = JITTER_MARGIN * __builtin_fabsf(d_freq);
     bool ok = (clk >= 0.0f) && (blend_length > 0.0f) && (jinc >= 0.0f) && (jinc <= 1.0f) &&
               (jm <= 1.0f) && (jf <= 1.0f) &&
-              (X.frequency * 0.999f - jf >= X_LO) && (Y.frequency * 0.999f - jf >= X_LO) &&
-              (X.frequency * 1.001f + jf <= 1.0f) && (Y.frequency * 1.001f + jf <= 1.0f);
+              (X.frequency * MARGIN_DOWN - jf >= X_LO) && (Y.frequency * MARGIN_DOWN - jf >= X_LO) &&
+              (X.frequency * MARGIN_UP + jf <= PITCH_HI) && (Y.frequency * MARGIN_UP + jf <= PITCH_HI);
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
 #pragma unroll
         for (int c = 0; c < W; ++c) {
             const float xf = vget(X.freq[k], c), yf = vget(Y.freq[k], c);
             const float xb = vget(X.bw[k], c), yb = vget(Y.bw[k], c);
-            ok = ok && (xf * 0.999f - jm >= X_LO) && (yf * 0.999f - jm >= X_LO) &&
-                 (xf * 1.001f + jm <= X_HI) && (yf * 1.001f + jm <= X_HI) &&
+            ok = ok && (xf * MARGIN_DOWN - jm >= X_LO) && (yf * MARGIN_DOWN - jm >= X_LO) &&
+                 (xf * MARGIN_UP + jm <= X_HI) && (yf * MARGIN_UP + jm <= X_HI) &&
                  (xb >= W_LO) && (yb >= W_LO) && (xb <= W_HI) && (yb <= W_HI);
         }
     }

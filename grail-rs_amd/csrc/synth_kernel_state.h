@@ -193,7 +193,7 @@
     const uint32_t room_end = SPLIT ? (pause_at < cap32 ? pause_at : cap32) : cap32;
     bool paused = false;
     uint32_t n_out = 0;
-    uint32_t slow_steps = 0;                 // wave-steps that took the IEEE-division body
+    uint32_t slow_steps = 0;                 // this lane's steps with a pair outside the division window (the wave reports the largest)
     uint32_t fast_tiles = 0, general_steps = 0;   // statistics: tiles rendered by fast_tile, general steps taken
 #ifdef GRAIL_FAST_PROF
     unsigned long long prof_c[32] = {};
@@ -285,8 +285,8 @@
         // correctly rounded clk/b while b and clk are in the proven window (tools/div_exhaustive.hip);
         // clk <= length, and steps whose clk is below the window take the general step
         if constexpr (ANYBL)
-            blend_div_ok = (blend_length >= 0x1p-59f) && (blend_length <= 0x1p59f) &&
-                           (cur.length <= 0x1p59f) && (dt >= 0x1p-59f);
+            blend_div_ok = (blend_length >= window::BLEND_LO) && (blend_length <= window::BLEND_HI) &&
+                           (cur.length <= window::BLEND_HI) && (dt >= window::BLEND_LO);
     };
 
     constexpr bool streaming = STREAM;       // a separate instantiation: the one-shot kernel

@@ -443,8 +443,8 @@
                     const float jphase_next = jphase + jinc;
                     // bitwise on purpose: no short-circuit, so no exec-mask regions
                     // ANYBL: a blend length that is not 2^k also sends a clk below the division
-                    // window (2^-59, or zero) to the general step
-                    const float clk_floor = (ANYBL && !blend_pow2) ? 0x1p-59f : 0.0f;
+                    // window (window::BLEND_LO = 2^-59, or zero) to the general step
+                    const float clk_floor = (ANYBL && !blend_pow2) ? window::BLEND_LO : 0.0f;
                     const bool eventful = !done & (!quiet_ok | (clk_next < clk_floor) |
                                                    (jphase_next > 1.0f) | (n_out >= cap32));
                     if (__builtin_expect(__builtin_amdgcn_ballot_w64(eventful) != 0, 0)) break;

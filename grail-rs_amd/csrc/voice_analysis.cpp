@@ -21,7 +21,7 @@ namespace host {
 bool live4_ok(const grail_voice &v)
 {
     const float amp_scale = 0.5f * v.jitter_delta_amplitude;
-    const float jm = 1.002f * std::fabs(v.jitter_delta_formant_frequency);
+    const float jm = window::JITTER_MARGIN * std::fabs(v.jitter_delta_formant_frequency);
     const bool ok = (amp_scale >= 0.0f) && (amp_scale <= 0.25f) && (jm <= 1.0f) &&
                     (v.jitter_frequency >= 0.0f) && (v.jitter_frequency <= 1.0f) &&
                     (v.sample_rate > 0.0f) && std::isfinite(v.sample_rate) &&
@@ -33,9 +33,8 @@ bool live4_ok(const grail_voice &v)
 // |jitter_delta_formant_frequency| of the voices it names)
 bool live4_elems_ok(const grail_synthesis_elem *elems, size_t n_elems, float jitter_delta_formant_frequency)
 {
-    constexpr float X_LO = 9.5367431640625e-07f, X_HI = 0.5f - 9.5367431640625e-07f;
-    constexpr float W_LO = 1.8189894035458565e-12f, W_HI = 512.0f;
-    const float jm = 1.002f * std::fabs(jitter_delta_formant_frequency);
+    using namespace window;                             // the numbers: division_window.h
+    const float jm = JITTER_MARGIN * std::fabs(jitter_delta_formant_frequency);
     bool ok = jm <= 1.0f;
     for (size_t p = 0; p < n_elems && ok; ++p) {
         const grail_synthesis_elem &e = elems[p];
@@ -46,7 +45,7 @@ bool live4_elems_ok(const grail_synthesis_elem *elems, size_t n_elems, float jit
             ok = bits == 0u && e.formant_breath[i] >= 0.0f && e.formant_breath[i] <= 1.0f &&
                  e.formant_turb[i] >= 0.0f && e.formant_turb[i] <= 1.0f &&
                  e.formant_smooth[i] >= 0.0f && e.formant_smooth[i] <= 1.0f &&
-                 (f * 0.999f - jm >= X_LO) && (f * 1.001f + jm <= X_HI) && (w >= W_LO) && (w <= W_HI);
+                 (f * MARGIN_DOWN - jm >= X_LO) && (f * MARGIN_UP + jm <= X_HI) && (w >= W_LO) && (w <= W_HI);
         }
     }
     return ok;
@@ -58,7 +57,7 @@ bool live4_elems_ok(const grail_synthesis_elem *elems, size_t n_elems, float jit
 bool scan_voice_ok(const grail_voice &v)
 {
     const float amp_scale = 0.5f * v.jitter_delta_amplitude;
-    const float jm = 1.002f * std::fabs(v.jitter_delta_formant_frequency);
+    const float jm = window::JITTER_MARGIN * std::fabs(v.jitter_delta_formant_frequency);
     bool ok = std::isfinite(amp_scale) && (jm <= 1.0f) && (v.jitter_frequency >= 0.0f) &&
               (v.jitter_frequency <= 0.25f) && (v.sample_rate > 0.0f) && std::isfinite(v.sample_rate) &&
               std::isfinite(v.jitter_delta_frequency);
@@ -69,9 +68,8 @@ bool scan_voice_ok(const grail_voice &v)
 // largest |jitter_delta_formant_frequency| of the voices it names)
 bool scan_elems_ok(const grail_synthesis_elem *elems, size_t n_elems, float jitter_delta_formant_frequency)
 {
-    constexpr float X_LO = 9.5367431640625e-07f, X_HI = 0.5f - 9.5367431640625e-07f;
-    constexpr float W_LO = 1.8189894035458565e-12f, W_HI = 512.0f;
-    const float jm = 1.002f * std::fabs(jitter_delta_formant_frequency);
+    using namespace window;                             // the numbers: division_window.h
+    const float jm = JITTER_MARGIN * std::fabs(jitter_delta_formant_frequency);
     bool ok = jm <= 1.0f;
     for (size_t p = 0; p < n_elems && ok; ++p) {
         const grail_synthesis_elem &e = elems[p];
@@ -79,7 +77,7 @@ bool scan_elems_ok(const grail_synthesis_elem *elems, size_t n_elems, float jitt
             const float f = e.formant_freq[i], w = e.formant_bw[i];
             ok = std::isfinite(e.formant_amp[i]) && std::isfinite(e.formant_breath[i]) &&
                  std::isfinite(e.formant_turb[i]) && e.formant_smooth[i] >= 0.0f && e.formant_smooth[i] <= 1.0f &&
-                 (f * 0.999f - jm >= X_LO) && (f * 1.001f + jm <= X_HI) && (w >= W_LO) && (w <= W_HI);
+                 (f * MARGIN_DOWN - jm >= X_LO) && (f * MARGIN_UP + jm <= X_HI) && (w >= W_LO) && (w <= W_HI);
         }
     }
     return ok;

@@ -277,8 +277,9 @@ int grail_get_voices(grail_ctx *ctx, grail_voice *voices, uint32_t cap, uint32_t
  *   a whole: 1 / 2 / 0 exact kernels); of the last launch (its largest block): "last_launch_fast" (tier that ran, 0 exact),
  *   "last_launch_blocks", "last_launch_formants" (4 / 8), "last_launch_lanes", "last_launch_pipelined", "last_launch_chunks",
  *   "last_launch_packed" (blocks launched in packed order);
- *   statistics: "slow_division_wave_steps", "fast_wave_tiles" (tiles rendered without a slow sample), "general_wave_steps"
- *   (tolerance mode: slow samples; exact: general steps). */
+ *   statistics: "slow_division_wave_steps" (summed over the waves: the most steps any one lane of a wave took with a segment
+ *   pair outside the window of the short division; 0: every division of every lane took it), "fast_wave_tiles" (tiles
+ *   rendered without a slow sample), "general_wave_steps" (tolerance mode: slow samples; exact: general steps). */
 int grail_set_option(grail_ctx *ctx, const char *name, int64_t value);
 int grail_get_option(grail_ctx *ctx, const char *name, int64_t *value);
 /* The planning behind "time_split", as pure host functions (no GPU, no context): what a caller needs to
