@@ -18,12 +18,14 @@
 #include <cstdio>
 #include <deque>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 #include <cstdlib>
 #include <cstring>
 #include <new>
 #include <string>
+#include <type_traits>
 #include <unordered_map>
 #include <utility>
 #include <vector>
@@ -33,7 +35,6 @@
 #include "kernels.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)
-struct PlanCache;                     // synthesize.cpp
 
 // words of the device block behind grail_ctx::d_truncated: the flag and three statistics counters; debug builds
 // (-DGRAIL_FAST_PROF) keep 32 u64 profile counters behind word 8
@@ -129,11 +130,11 @@ std::string &last_error();
 // One hipMalloc allocation of `capacity()` elements and its only owner (move-only; the destructor frees).  Every device
 // buffer of the per-context scratch (LevelState, MixState), of a stream and of the calls' temporaries is one of these;
 // `reserve` is their one growth rule: grown when too small, never shrunk.
-// NOT for grail_ctx and grail_batch (d_voices, d_voice_elems, d_truncated, the batch's buffers, PackedPerm::d_perm; the
-// three opaque state pointers stay void *): both are constructed on the stack by code that is built without hipcc and
-// linked without the HIP runtime (grail_plan_blocks and grail_plan_ragged_blocks in launch_plan.cpp, the drivers of
-// tests/test_sanitizers.py), where a member whose destructor calls hipFree would not link, and a grail_batch is copied
-// whole to make its row-group views.  Only units that call HIP themselves create the types that hold a DeviceBuffer.
+// A batch's arrays and its packed launch tables are such buffers too.  NOT for grail_ctx (d_voices, d_voice_elems,
+// d_truncated; the three opaque state pointers stay void *): tests/sanitize_options_driver.cpp constructs one on the stack in
+// a program that is built without hipcc and linked without the HIP runtime, where a member whose destructor calls hipFree
+// would not link.  The launch policy (launch_plan.cpp, voice_analysis.cpp), linked into the same programs, never sees a
+// type that holds one: its inputs are PlanEnv and BatchFacts.
 template <typename T>
 class DeviceBuffer {
 public:
@@ -183,24 +184,55 @@ private:
     size_t cap_ = 0;
 };
 
+// the kernel family of a launch, a block of rows with its family (launch_plan.cpp chooses them)
+struct Family {
+    int L = 1;                 // lanes per utterance (lane kernels, pipelined workgroups)
+    uint32_t pipe = 0;         // exact pipelined workgroups: 1 = rounds of 16 samples, 2 = rounds of 32
+    uint32_t live4 = 0;        // formants 5-8 not laid out
+    bool half = false;         // one lane per utterance, exact, eight formants laid out but 5-8 silent: the half-live loops
+    uint32_t fast = 0;         // tolerance arithmetic
+    int split_k = 0;           // time-split kernels: chunks per utterance (0: not time-split)
+    uint32_t split_bounds[SPLIT_MAX_CHUNKS + 1] = {};
+    uint32_t split_active = 0; // ... rows that differ in length: how many (wave, chunk) pairs have anything to render (0: all)
+    bool scan = false;         // the time-parallel scan kernel
+    uint32_t scan_pipe = 0;    // ... its three-stage flavour
+};
+
+struct Block {
+    uint32_t rows;
+    Family f;
+};
+
+// the launch plan of the last synthesis call of a batch or of one of its row groups, with what it was made for (plan_blocks
+// lays out time-split grids by bisection: a fraction of a millisecond of host time, which a one-millisecond kernel should
+// not pay at every launch); empty: none yet
+struct PlanCache {
+    uint64_t key[6] = {};
+    std::vector<Block> plan;
+};
+
 }  // namespace host
 }  // namespace grail
 
-struct grail_ctx {
-    int device = 0;
+// What the launch policy reads of a context (grail_plan_blocks builds one without a device)
+struct PlanEnv {
     int cus = 256;                    // compute units the launch policy plans for (hipDeviceProp_t::multiProcessorCount;
                                       // "assume_compute_units" overrides it): every capacity of the policy is a multiple
-    int device_cus = 256;             // ... what the device reported
+    Options opt;
+    VoiceFacts facts;
+    uint64_t voices_epoch = 0;        // set by every install_voices: unique in the process, not per context
+};
+
+struct grail_ctx : PlanEnv {
+    int device = 0;
+    int device_cus = 256;             // what the device reported (cus: what is planned for)
     hipStream_t stream = nullptr;
     hipEvent_t ev_start = nullptr, ev_stop = nullptr;
     bool have_timing = false;
-    Options opt;
     uint64_t options_epoch = 0;       // bumped by every grail_set_option (a batch caches its launch plan against both)
     std::vector<grail_voice> voices;  // host copy of the table
     grail::DevVoice *d_voices = nullptr;
     float *d_voice_elems = nullptr;   // [n_voices * NUM_VOICED][49]
-    VoiceFacts facts;
-    uint64_t voices_epoch = 0;        // set by every install_voices: unique in the process, not per context
     LaunchStats stats;
     uint32_t *d_truncated = nullptr;  // [0] truncation flag, [1] slow-path wave-steps, [2] fast wave-tiles, [3] general wave-steps
     uint32_t seen_counters[4] = {0, 0, 0, 0};   // d_truncated[1..3] as last read: the device counters only ever grow
@@ -221,7 +253,7 @@ struct grail_stream {
     bool live4 = false, half_capable = false, any_blend = false;
     uint64_t voices_epoch = 0;
     // live streams (grail_stream_open_live): the stream owns its batch, whose segments sit in per-utterance rings
-    grail_batch *own = nullptr;
+    std::unique_ptr<grail_batch> own;
     uint32_t ring_cap = 0;            // segments per utterance ring (a power of two); 0: not a live stream
     grail::host::DeviceBuffer<uint32_t> d_counts;     // [n_utt] segments appended so far
     grail::host::DeviceBuffer<uint32_t> d_open;       // [n_utt] 1 while the utterance's source may deliver more
@@ -245,30 +277,9 @@ struct grail_stream {
     int stage_next = 0;
 };
 
-// A block of a ragged batch in PACKED launch order (launch_plan.cpp, "The workgroup dispatcher"): the slot -> utterance table
-// of rows [slot0, slot0 + rows) with its workgroups re-ordered, on the device.  Kept by the batch (never overwritten: a
-// kernel of another context may still be reading it), freed with it.
-struct PackedPerm {
-    const void *view = nullptr;       // the (view of the) batch the block belongs to
-    uint32_t slot0 = 0, rows = 0, per_block = 0, cus = 0;
-    uint32_t family = 0;              // L | fast << 8 | live4 << 16: what the workgroups' costs were priced for
-    uint32_t *d_perm = nullptr;       // [rows]; nullptr: the plain order is as good (remembered, so that it is not packed again)
-    double model_ms = 0.0, plain_ms = 0.0;
-};
-
-struct grail_batch {
-    grail::DevSeg *d_segs = nullptr;
-    uint32_t *d_offsets = nullptr;
-    uint32_t *d_voice_ids = nullptr;
-    uint32_t *d_seeds = nullptr;
-    uint32_t *d_perm = nullptr;   // ragged batches: launch slot -> utterance, longest first
-    std::vector<uint32_t> perm_host;          // ... its host copy (the root batch only; packed launch orders are cut from it)
-    mutable std::vector<PackedPerm> packed;   // ... blocks of it in packed launch order, made at their first launch
-    uint32_t *d_len_bound = nullptr;   // per utterance: an upper bound of its length in samples (plain batches; time-split kernels)
-    uint64_t len_bound_epoch = 0;      // ... for the voice table of this epoch (its highest sample rate); epochs are unique
-                                       // in the process, so a context other than the uploader never matches
-    bool len_bound_known = false;      // (the planner's question; grail_plan_ragged_blocks answers it without a device)
-    float *d_elems = nullptr;  // elem mode only
+// What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks
+// builds one without a device)
+struct BatchFacts {
     uint32_t n_utt = 0;
     uint32_t n_segs = 0;
     uint32_t max_voice_id = 0;
@@ -278,29 +289,63 @@ struct grail_batch {
     float max_seconds = 0.0f;  // longest utterance: sum of its segment lengths
     float min_length = 0.0f;   // shortest segment (plain batches)
     float min_pitch = 0.0f;    // lowest frequency.min(0.5) of any segment (plain batches)
+    uint64_t len_bound_epoch = 0;      // the device holds an upper bound of every utterance's length (plain batches; time-split
+                                       // kernels) for the voice table of this epoch (its highest sample rate); epochs are unique
+                                       // in the process, so a context other than the uploader never matches
+    bool len_bound_known = false;      // (the planner's question; grail_plan_ragged_blocks answers it without a device)
     double elems_sharpness = 0.0;   // elem mode: predicted fast-mode deviation of the caller's elems (elems_sharpness())
     uint32_t elems_warmup = 0;      // elem mode: warm-up length of the time-split kernels over the batch's distinct elems and the
                                     // jitter of the voices it names (elems_warmup()); 0: the batch does not qualify
-    uint64_t elems_warmup_epoch = 0;   // ... computed against this voice table (ctx->voices_epoch)
+    uint64_t elems_warmup_epoch = 0;   // ... computed against this voice table (voices_epoch)
     bool elems_live4_ok = false;    // elem mode: formants 5-8 of every elem (and the voices named) can be left out (live4_ok); same epoch
     bool elems_scan_ok = false;     // elem mode: every elem inside the scan kernel's window (scan_elems_ok), pitches <= 1/2; same epoch
     std::vector<uint32_t> used_voices;   // the distinct voice ids of the batch, ascending
-    // the launch plan of the last synthesis call of this batch (plan_blocks lays out time-split grids by bisection: a
-    // fraction of a millisecond of host time, which a one-millisecond kernel should not pay at every launch)
-    mutable PlanCache *plan_cache = nullptr;
-    // Row groups (whole-batch launches of length-sorted batches).  A few rows that the lean kernel families cannot take —
-    // a segment shorter than two samples, a non-finite length or pitch — would cost the whole batch its four-formant
-    // kernels, pipelined workgroups and fast families, because those are gated on the batch's worst row.  Such rows are
-    // put LAST in the slot order and the batch is planned as two batches that share the device buffers: groups[0] = the
-    // lean rows (slots [0, groups[0].n_utt)), groups[1] = the rest.  Valid for the voice table they were judged against.
-    std::vector<grail_batch> groups;
-    uint64_t groups_epoch = 0;
     // Ragged (length-sorted) batches, per granule of 8 consecutive launch slots: the longest row in samples (at the
     // context's highest rate), the rows' segments and their kinks of alpha (blend_length < length) — what ragged_plan()
     // weighs the lane mappings with.  Empty for aligned batches.
     std::vector<float> granule_samples;
     std::vector<uint32_t> granule_segs, granule_kinks;
 };
+
+// Row groups (whole-batch launches of length-sorted batches).  A few rows that the lean kernel families cannot take —
+// a segment shorter than two samples, a non-finite length or pitch — would cost the whole batch its four-formant
+// kernels, pipelined workgroups and fast families, because those are gated on the batch's worst row.  Such rows are
+// put LAST in the slot order and the batch is planned as two: groups[0] = the lean rows (launch slots [0, groups[0].n_utt)),
+// groups[1] = the rest, each with the summary of its own rows (used_voices: the batch's — a superset of the group's) and a
+// cached plan of its own.  The device arrays are the batch's.
+struct RowGroup : BatchFacts {
+    uint32_t slot0 = 0;               // its first launch slot
+    mutable grail::host::PlanCache plan_cache;
+};
+
+// A block of a ragged batch in PACKED launch order (launch_plan.cpp, "The workgroup dispatcher"): the slot -> utterance table
+// of rows [slot0, slot0 + rows) with its workgroups re-ordered, on the device.  Kept by the batch and never reallocated while
+// it lives (a kernel of another context may still be reading it), freed with it.
+struct PackedPerm {
+    uint32_t view = 0;                // whose block: 0 the batch as a whole, 1 + g its row group g
+    uint32_t slot0 = 0, rows = 0, per_block = 0, cus = 0;
+    uint32_t family = 0;              // L | fast << 8 | live4 << 16: what the workgroups' costs were priced for
+    grail::host::DeviceBuffer<uint32_t> d_perm;   // [rows]; none: the plain order is as good (remembered, so that it is not packed again)
+    double model_ms = 0.0, plain_ms = 0.0;
+};
+
+// The facts are those of all rows; the device arrays are owned (`delete batch` releases everything; an array that was never
+// allocated reads nullptr: "no ids: voice 0 for all", "no perm").
+struct grail_batch : BatchFacts {
+    grail::host::DeviceBuffer<grail::DevSeg> d_segs;
+    grail::host::DeviceBuffer<uint32_t> d_offsets, d_voice_ids, d_seeds;
+    grail::host::DeviceBuffer<uint32_t> d_perm;       // ragged batches: launch slot -> utterance, longest first
+    std::vector<uint32_t> perm_host;                  // ... its host copy (packed launch orders are cut from it)
+    grail::host::DeviceBuffer<uint32_t> d_len_bound;  // per utterance: an upper bound of its length in samples (len_bound_epoch)
+    grail::host::DeviceBuffer<float> d_elems;         // elem mode only
+    std::vector<RowGroup> groups;                     // none or two; valid for the voice table they were judged against
+    uint64_t groups_epoch = 0;
+    // one batch may be rendered by several contexts, each on a thread of its own: `lock` guards what a launch writes
+    mutable std::mutex lock;
+    mutable grail::host::PlanCache plan_cache;        // of the batch as a whole
+    mutable std::vector<PackedPerm> packed;           // blocks in packed launch order, made at their first launch
+};
+static_assert(!std::is_copy_constructible_v<grail_batch>, "a batch owns its device arrays: row groups are BatchFacts, not batches");
 
 namespace grail {
 namespace host {
@@ -309,27 +354,26 @@ namespace host {
 // for ONE resident wave per SIMD (a second wave on a SIMD costs as much as it brings: profiles/r01_lanes_sweep.txt), so
 // all capacities below are multiples of the compute-unit count hipGetDeviceProperties reports (a partitioned MI355X —
 // CPX, 32 CUs — plans for 32, not 256); "assume_compute_units" overrides it for tests.
-inline uint64_t ctx_simds(const grail_ctx *ctx) { return 4ull * (uint64_t)ctx->cus; }
-inline uint64_t ctx_lanes(const grail_ctx *ctx) { return 256ull * (uint64_t)ctx->cus; }
-inline int64_t pipe4_groups(const grail_ctx *ctx) { return ctx->opt.pipe4_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe4_max_groups; }
-inline int64_t pipe8_groups(const grail_ctx *ctx) { return ctx->opt.pipe8_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe8_max_groups; }
-inline int64_t scan_max_utts(const grail_ctx *ctx) { return ctx->opt.scan_max_utts < 0 ? 34 * (int64_t)ctx->cus : ctx->opt.scan_max_utts; }
-inline int64_t scan_split_max(const grail_ctx *ctx) { return ctx->opt.scan_split_max < 0 ? 6 * (int64_t)ctx->cus : ctx->opt.scan_split_max; }
+inline uint64_t ctx_simds(const PlanEnv *ctx) { return 4ull * (uint64_t)ctx->cus; }
+inline uint64_t ctx_lanes(const PlanEnv *ctx) { return 256ull * (uint64_t)ctx->cus; }
+inline int64_t pipe4_groups(const PlanEnv *ctx) { return ctx->opt.pipe4_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe4_max_groups; }
+inline int64_t pipe8_groups(const PlanEnv *ctx) { return ctx->opt.pipe8_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe8_max_groups; }
+inline int64_t scan_max_utts(const PlanEnv *ctx) { return ctx->opt.scan_max_utts < 0 ? 34 * (int64_t)ctx->cus : ctx->opt.scan_max_utts; }
+inline int64_t scan_split_max(const PlanEnv *ctx) { return ctx->opt.scan_split_max < 0 ? 6 * (int64_t)ctx->cus : ctx->opt.scan_split_max; }
 
 int bind(grail_ctx *ctx);
 
+// max(count, 1) elements for dst, the first `count` of them copied from src (if any) on `stream`
 template <typename Tp>
-int upload(Tp **dst, const void *src, size_t count, hipStream_t stream)
+hipError_t upload(DeviceBuffer<Tp> &dst, const void *src, size_t count, hipStream_t stream)
 {
-    *dst = nullptr;
-    if (count == 0) count = 1;
-    HIP_TRY(hipMalloc((void **)dst, count * sizeof(Tp)));
-    if (src) HIP_TRY(hipMemcpyAsync(*dst, src, count * sizeof(Tp), hipMemcpyHostToDevice, stream));
-    return GRAIL_OK;
+    const hipError_t e = dst.alloc(count);
+    if (e != hipSuccess || !src || !count) return e;
+    return hipMemcpyAsync(dst.get(), src, count * sizeof(Tp), hipMemcpyHostToDevice, stream);
 }
 
 // grail_api.cpp
-void free_batch_buffers(grail_batch *b);
+void name_voices(BatchFacts &b, const uint32_t *voice_ids, uint32_t n_utt);
 bool blend_is_pow2(float blend_length);
 int check_offsets(const uint32_t *seg_offsets, uint32_t n_utt, uint32_t *n_segs);
 int install_voices(grail_ctx *ctx, const grail_voice *voices, uint32_t n_voices);
@@ -344,57 +388,40 @@ bool scan_elems_ok(const grail_synthesis_elem *elems, size_t n_elems, float jitt
 uint32_t voice_warmup(const grail_voice &v);
 uint32_t elems_warmup(const grail_synthesis_elem *elems, size_t n_elems, double jitter_delta_formant_frequency);
 double elems_sharpness(const grail_synthesis_elem *elems, size_t n);
-double batch_sharpness(const grail_ctx *ctx, const grail_batch *batch);
-int fast_tier_for(const grail_ctx *ctx, const grail_batch *batch, int arithmetic);
-int fast_tier(const grail_ctx *ctx, const grail_batch *batch);
+double batch_sharpness(const PlanEnv *ctx, const BatchFacts *batch);
+int fast_tier_for(const PlanEnv *ctx, const BatchFacts *batch, int arithmetic);
+int fast_tier(const PlanEnv *ctx, const BatchFacts *batch);
 bool split_grid(uint32_t span, uint32_t warmup, int K, double r, uint32_t *b);
 
 // launch_plan.cpp: which kernel family renders a block of rows, what it costs, how a batch is cut into blocks
-struct Family {
-    int L = 1;                 // lanes per utterance (lane kernels, pipelined workgroups)
-    uint32_t pipe = 0;         // exact pipelined workgroups: 1 = rounds of 16 samples, 2 = rounds of 32
-    uint32_t live4 = 0;        // formants 5-8 not laid out
-    bool half = false;         // one lane per utterance, exact, eight formants laid out but 5-8 silent: the half-live loops
-    uint32_t fast = 0;         // tolerance arithmetic
-    int split_k = 0;           // time-split kernels: chunks per utterance (0: not time-split)
-    uint32_t split_bounds[SPLIT_MAX_CHUNKS + 1] = {};
-    uint32_t split_active = 0; // ... rows that differ in length: how many (wave, chunk) pairs have anything to render (0: all)
-    bool scan = false;         // the time-parallel scan kernel
-    uint32_t scan_pipe = 0;    // ... its three-stage flavour
-};
-
-struct Block {
-    uint32_t rows;
-    Family f;
-};
-
 // lanes per utterance when the option is 0 (auto): the widest mapping that gives each of `simds` SIMDs at most one wave
 int auto_lanes_per_utt(uint32_t n_utt, uint64_t simds);
-double batch_span(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride);
-double family_cost(const grail_ctx *ctx, const Family &f, uint32_t rows, double span);
+double batch_span(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride);
+double family_cost(const PlanEnv *ctx, const Family &f, uint32_t rows, double span);
 // pipelined workgroups, rows that differ in length: utterances per workgroup of a launch of `rows` rows (0: every slot)
-uint32_t pipe_fill_for(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t rows);
+uint32_t pipe_fill_for(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t rows);
 // a launch of `rows` rows with family f takes the instantiations built for two waves per SIMD (SynthArgs::cohabit)
-bool family_cohabits(const grail_ctx *ctx, const Family &f, uint32_t rows);
-bool batch_half_capable(const grail_ctx *ctx, const grail_batch *batch);
-bool batch_live4_any_blend(const grail_ctx *ctx, const grail_batch *batch);
-bool batch_live4(const grail_ctx *ctx, const grail_batch *batch);
-void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t fam, Family &f,
+bool family_cohabits(const PlanEnv *ctx, const Family &f, uint32_t rows);
+bool batch_half_capable(const PlanEnv *ctx, const BatchFacts *batch);
+bool batch_live4_any_blend(const PlanEnv *ctx, const BatchFacts *batch);
+bool batch_live4(const PlanEnv *ctx, const BatchFacts *batch);
+void choose_family(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t fam, Family &f,
                    bool exact_only = false, int pin_lanes = 0);
 // ragged batches: what a block costs given the lengths and events of ITS rows; the whole-batch plan weighed against
 // one launch of each lane mapping with as many rounds as it takes (launch_plan.cpp)
-double ragged_cost(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t slot0, uint32_t rows, double span);
+double ragged_cost(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t slot0, uint32_t rows, double span);
 // The launch order of the workgroups of such a block (one wave per SIMD, more workgroups than the device holds at once):
 // true and order[position] = workgroup (in the plain, longest-first numbering) when the packed order is worth it by the
 // dispatcher's model; *plain_ms / *packed_ms: the model's makespans.  rows_per_block: what a workgroup renders.
-bool packed_launch_order(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t slot0, uint32_t rows, double span,
+bool packed_launch_order(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t slot0, uint32_t rows, double span,
                          std::vector<uint32_t> *order, uint32_t *rows_per_block, double *plain_ms, double *packed_ms);
-void ragged_plan(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t rows, std::vector<Block> &plan);
-double plan_blocks(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t rows, double span,
+void ragged_plan(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t rows, std::vector<Block> &plan);
+double plan_blocks(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t rows, double span,
                    std::vector<Block> &out, bool exact_only = false);
 
 // synthesize.cpp: one launch per block; a batch's cached plan
-void free_plan_cache(PlanCache *p);
+// what every synthesis launch takes from (ctx, batch): the batch's arrays from utterance row0 on, the voice table, the flags
+void batch_args(const grail_ctx *ctx, const grail_batch *batch, uint32_t row0, SynthArgs &a);
 int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev, int16_t *out_pcm16_dev, uint64_t out_stride,
                     uint32_t *out_len_dev, uint32_t first = 0, uint32_t count = 0, uint32_t family_rows = 0);
 

@@ -49,27 +49,6 @@ int bind(grail_ctx *ctx)
     return GRAIL_OK;
 }
 
-void free_batch_buffers(grail_batch *b)
-{
-    free_plan_cache(b->plan_cache);
-    b->plan_cache = nullptr;
-    for (grail_batch &g : b->groups) {          // (views: they share the device buffers below)
-        free_plan_cache(g.plan_cache);
-        g.plan_cache = nullptr;
-    }
-    b->groups.clear();
-    if (b->d_segs) (void)hipFree(b->d_segs);
-    if (b->d_offsets) (void)hipFree(b->d_offsets);
-    if (b->d_voice_ids) (void)hipFree(b->d_voice_ids);
-    if (b->d_seeds) (void)hipFree(b->d_seeds);
-    if (b->d_perm) (void)hipFree(b->d_perm);
-    for (PackedPerm &pp : b->packed)
-        if (pp.d_perm) (void)hipFree(pp.d_perm);
-    b->packed.clear();
-    if (b->d_len_bound) (void)hipFree(b->d_len_bound);
-    if (b->d_elems) (void)hipFree(b->d_elems);
-}
-
 // clk / 2^k is clk * 2^-k exactly; any other blend length needs the division code of the kernel
 bool blend_is_pow2(float blend_length)
 {
@@ -113,6 +92,61 @@ static double segment_bound(float length, double dt)
     return (double)length / (dt - half_ulp) + 2.0;
 }
 
+// An utterance's segments [i0, i1) (PhonemeElems, or the DevSegs of caller-built elems); pitch_of(frequency): the pitch the
+// kernels will see.
+// min_dt: the device's dt of the table's highest sample rate, as the kernels have it (an f32 reciprocal; 0: no table).
+template <typename Seg, typename Pitch>
+static RowStats row_stats(const Seg *segs, uint32_t i0, uint32_t i1, double min_dt, Pitch pitch_of)
+{
+    RowStats r;
+    for (uint32_t i = i0; i < i1; ++i) {
+        const float pitch = pitch_of(segs[i].frequency);
+        r.plain = r.plain && std::isfinite(segs[i].length) && std::isfinite(segs[i].blend_length) &&
+                  std::isfinite(segs[i].frequency) && segs[i].blend_length > 0.0f;
+        r.any_blend = r.any_blend || !blend_is_pow2(segs[i].blend_length);
+        if (segs[i].length < r.min_length) r.min_length = segs[i].length;
+        if (pitch < r.min_pitch) r.min_pitch = pitch;
+        r.seconds += segs[i].length;
+        r.bound_samples += segment_bound(segs[i].length, min_dt);
+        r.segs += 1u;
+        r.kinks += segs[i].blend_length < segs[i].length ? 1u : 0u;
+    }
+    return r;
+}
+
+// the summary of no rows, and a row folded into it (a batch's, a row group's)
+static void clear_summary(BatchFacts &t)
+{
+    t.plain = true;
+    t.any_blend = false;
+    t.min_length = INFINITY;
+    t.min_pitch = INFINITY;
+    t.max_seconds = 0.0f;
+}
+static void add_row(BatchFacts &t, const RowStats &r)
+{
+    t.plain = t.plain && r.plain;
+    t.any_blend = t.any_blend || r.any_blend;
+    if (r.min_length < t.min_length) t.min_length = r.min_length;
+    if (r.min_pitch < t.min_pitch) t.min_pitch = r.min_pitch;
+    if (r.seconds > t.max_seconds) t.max_seconds = r.seconds;
+}
+
+// (every utterance, then the batch: what the launch policy asks of the segments)
+template <typename Seg, typename Pitch>
+static std::vector<RowStats> batch_stats(const grail_ctx *ctx, grail_batch *b, const Seg *segs, const uint32_t *seg_offsets,
+                                         uint32_t n_utt, Pitch pitch_of)
+{
+    const double min_dt = ctx->facts.max_rate > 0.0f ? (double)(1.0f / ctx->facts.max_rate) : 0.0;
+    std::vector<RowStats> rows(n_utt);
+    clear_summary(*b);
+    for (uint32_t u = 0; u < n_utt; ++u) {
+        rows[u] = row_stats(segs, seg_offsets[u], seg_offsets[u + 1], min_dt, pitch_of);
+        add_row(*b, rows[u]);
+    }
+    return rows;
+}
+
 // An upper bound of every utterance's length in samples, on the device (time-split kernels: a chunk's lane whose utterance
 // ends before the chunk begins has nothing to render and says so at once — batches whose rows differ in length then take
 // more, shorter chunks; launch_plan.cpp): grail_length_bound at the table's highest sample rate, + a tile.
@@ -124,8 +158,7 @@ int upload_len_bound(grail_ctx *ctx, grail_batch *b, const std::vector<RowStats>
         const double samples = rows[u].bound_samples + 64.0;
         bound[u] = samples < 4.0e9 ? (uint32_t)samples : 0xFFFFFFFFu;
     }
-    int rc = upload(&b->d_len_bound, bound.data(), n_utt, ctx->stream);
-    if (rc) return rc;
+    HIP_TRY(upload(b->d_len_bound, bound.data(), n_utt, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     b->len_bound_epoch = ctx->voices_epoch;
     b->len_bound_known = true;
@@ -138,7 +171,7 @@ int upload_len_bound(grail_ctx *ctx, grail_batch *b, const std::vector<RowStats>
 // batch is larger than the machine the longest waves start first.  Results do not depend on the slot
 // (batch invariance), rows stay where the caller put them.  Aligned batches (all sums equal) keep the
 // identity assignment and pay nothing.
-// Rows the lean kernel families cannot take (grail_batch::groups) go last, whatever their length: the batch is then
+// Rows the lean kernel families cannot take (RowGroup) go last, whatever their length: the batch is then
 // planned as two batches.  (Judged against the voice table of this moment: the bounds involve its sample rates and
 // pitch jitter; a batch uploaded before any table, or rendered with another one, is planned as one.)
 int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowStats> &rows, uint32_t n_utt)
@@ -170,41 +203,28 @@ int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowSta
         if (n_out && outlier[a] != outlier[c]) return outlier[a] < outlier[c];
         return ragged && key(a) > key(c);
     });
-    int rc = upload(&b->d_perm, perm.data(), n_utt, ctx->stream);
-    if (rc) return rc;
+    HIP_TRY(upload(b->d_perm, perm.data(), n_utt, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (n_out) {
-        // two views of the batch: same device buffers, each with the summary of its own rows
-        b->groups.assign(2, *b);
+        // two row groups: the batch's facts, each with the summary of its own rows
+        b->groups.resize(2);
         for (int g = 0; g < 2; ++g) {
-            grail_batch &v = b->groups[g];
-            v.groups.clear();
-            v.plan_cache = nullptr;
+            RowGroup &v = b->groups[g];
+            static_cast<BatchFacts &>(v) = *b;
+            v.slot0 = g ? n_utt - n_out : 0u;
             v.n_utt = g ? n_out : n_utt - n_out;
-            v.plain = true;
-            v.any_blend = false;
-            v.min_length = INFINITY;
-            v.min_pitch = INFINITY;
-            v.max_seconds = 0.0f;        // (used_voices: the batch's — a superset of the group's)
+            clear_summary(v);
         }
-        for (uint32_t u = 0; u < n_utt; ++u) {
-            grail_batch &v = b->groups[outlier[u]];
-            const RowStats &r = rows[u];
-            v.plain = v.plain && r.plain;
-            v.any_blend = v.any_blend || r.any_blend;
-            if (r.min_length < v.min_length) v.min_length = r.min_length;
-            if (r.min_pitch < v.min_pitch) v.min_pitch = r.min_pitch;
-            if (r.seconds > v.max_seconds) v.max_seconds = r.seconds;
-        }
+        for (uint32_t u = 0; u < n_utt; ++u) add_row(b->groups[outlier[u]], rows[u]);
         b->groups_epoch = ctx->voices_epoch;
     }
     // What ragged_plan() and ragged_cost() weigh the lane mappings with: per 8 launch slots the longest row and the rows'
     // segment and kink counts — of the whole batch in launch order, and, where a few rows the lean kernel families cannot take
-    // were put last, of the OTHER rows by themselves too: the first view of the batch is the corpus, and one zero-length
-    // segment among 65 536 speech-like utterances must not cost the rest their plan.  (A view is planned by its rows' lengths
+    // were put last, of the OTHER rows by themselves too: the first row group is the corpus, and one zero-length
+    // segment among 65 536 speech-like utterances must not cost the rest their plan.  (A group is planned by its rows' lengths
     // only if they differ THEMSELVES: an aligned batch with a few odd rows is ragged only through those, and its first group
     // keeps the aligned plan — the model prices every lane's events as its own, which an aligned group's are not.)
-    auto summarise = [&](grail_batch &t, const uint32_t n_rows) {
+    auto summarise = [&](BatchFacts &t, const uint32_t n_rows) {
         const size_t n_gran = ((size_t)n_rows + 7) / 8;
         t.granule_samples.assign(n_gran, 0.0f);
         t.granule_segs.assign(n_gran, 0u);
@@ -231,29 +251,29 @@ int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowSta
     } else if (ragged) {
         summarise(*b, n_utt);
     }
-    b->perm_host.swap(perm);          // (after the views were copied off the batch: they share d_perm, only the root keeps this)
+    b->perm_host.swap(perm);
     return GRAIL_OK;
+}
+
+// the voices a batch names: used_voices and max_voice_id (no ids: voice 0 for all)
+void name_voices(BatchFacts &b, const uint32_t *voice_ids, uint32_t n_utt)
+{
+    b.max_voice_id = 0;
+    b.used_voices.assign(1, 0u);
+    if (!voice_ids || !n_utt) return;
+    b.used_voices.assign(voice_ids, voice_ids + n_utt);
+    std::sort(b.used_voices.begin(), b.used_voices.end());
+    b.used_voices.erase(std::unique(b.used_voices.begin(), b.used_voices.end()), b.used_voices.end());
+    b.max_voice_id = b.used_voices.back();
 }
 
 int upload_common(grail_ctx *ctx, grail_batch *b, const uint32_t *seg_offsets,
                   const uint32_t *voice_ids, const uint32_t *jitter_seeds, uint32_t n_utt)
 {
-    int rc;
-    if ((rc = upload(&b->d_offsets, seg_offsets, (size_t)n_utt + 1, ctx->stream))) return rc;
-    b->max_voice_id = 0;
-    b->used_voices.assign(1, 0u);                     // no ids: voice 0 for all
-    if (voice_ids) {
-        for (uint32_t u = 0; u < n_utt; ++u)
-            if (voice_ids[u] > b->max_voice_id) b->max_voice_id = voice_ids[u];
-        if (n_utt) {
-            b->used_voices.assign(voice_ids, voice_ids + n_utt);
-            std::sort(b->used_voices.begin(), b->used_voices.end());
-            b->used_voices.erase(std::unique(b->used_voices.begin(), b->used_voices.end()), b->used_voices.end());
-        }
-        if ((rc = upload(&b->d_voice_ids, voice_ids, n_utt, ctx->stream))) return rc;
-    }
-    if (jitter_seeds)
-        if ((rc = upload(&b->d_seeds, jitter_seeds, n_utt, ctx->stream))) return rc;
+    HIP_TRY(upload(b->d_offsets, seg_offsets, (size_t)n_utt + 1, ctx->stream));
+    name_voices(*b, voice_ids, n_utt);
+    if (voice_ids) HIP_TRY(upload(b->d_voice_ids, voice_ids, n_utt, ctx->stream));
+    if (jitter_seeds) HIP_TRY(upload(b->d_seeds, jitter_seeds, n_utt, ctx->stream));
     b->n_utt = n_utt;
     // host buffers may be freed by the caller right after we return
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -481,47 +501,17 @@ int grail_batch_upload(grail_ctx *ctx, const grail_phoneme_elem *segs, const uin
     for (uint32_t i = 0; i < n_segs; ++i)
         if (segs[i].phoneme < 0 || segs[i].phoneme >= GRAIL_PH_COUNT)
             return fail(GRAIL_ERR_INVALID_ARG, "phoneme discriminant out of range");
-    // per utterance, then over the batch: what the launch policy asks of the segments
-    std::vector<RowStats> rows(n_utt);
-    // (the device's dt of the table's highest sample rate, as the kernels have it: an f32 reciprocal)
-    const double min_dt = ctx->facts.max_rate > 0.0f ? (double)(1.0f / ctx->facts.max_rate) : 0.0;
-    for (uint32_t u = 0; u < n_utt; ++u) {
-        RowStats &r = rows[u];
-        for (uint32_t i = seg_offsets[u]; i < seg_offsets[u + 1]; ++i) {
-            r.plain = r.plain && std::isfinite(segs[i].length) && std::isfinite(segs[i].blend_length) &&
-                      std::isfinite(segs[i].frequency) && segs[i].blend_length > 0.0f;
-            r.any_blend = r.any_blend || !blend_is_pow2(segs[i].blend_length);
-            if (segs[i].length < r.min_length) r.min_length = segs[i].length;
-            const float pitch = std::fmin(segs[i].frequency, 0.5f);   // copy_with_frequency :445-450
-            if (pitch < r.min_pitch) r.min_pitch = pitch;
-            r.seconds += segs[i].length;
-            r.bound_samples += segment_bound(segs[i].length, min_dt);
-            r.segs += 1u;
-            r.kinks += segs[i].blend_length < segs[i].length ? 1u : 0u;
-        }
-    }
-    grail_batch *b = new (std::nothrow) grail_batch();
+    std::unique_ptr<grail_batch> b(new (std::nothrow) grail_batch());
     if (!b) return fail(GRAIL_ERR_OUT_OF_MEMORY, "host allocation failed");
     b->phoneme_mode = true;
-    b->plain = true;
-    b->min_length = INFINITY;
-    b->min_pitch = INFINITY;
-    for (const RowStats &r : rows) {
-        b->plain = b->plain && r.plain;
-        b->any_blend = b->any_blend || r.any_blend;
-        if (r.min_length < b->min_length) b->min_length = r.min_length;
-        if (r.min_pitch < b->min_pitch) b->min_pitch = r.min_pitch;
-        if (r.seconds > b->max_seconds) b->max_seconds = r.seconds;
-    }
     b->n_segs = n_segs;
-    if ((rc = upload(&b->d_segs, segs, n_segs, ctx->stream)) ||
-        (rc = upload_common(ctx, b, seg_offsets, voice_ids, jitter_seeds, n_utt)) ||
-        (rc = upload_len_bound(ctx, b, rows, n_utt)) || (rc = upload_length_order(ctx, b, rows, n_utt))) {
-        free_batch_buffers(b);
-        delete b;
+    const std::vector<RowStats> rows = batch_stats(ctx, b.get(), segs, seg_offsets, n_utt,
+                                                   [](float f) { return std::fmin(f, 0.5f); });   // copy_with_frequency :445-450
+    HIP_TRY(upload(b->d_segs, segs, n_segs, ctx->stream));
+    if ((rc = upload_common(ctx, b.get(), seg_offsets, voice_ids, jitter_seeds, n_utt)) ||
+        (rc = upload_len_bound(ctx, b.get(), rows, n_utt)) || (rc = upload_length_order(ctx, b.get(), rows, n_utt)))
         return rc;
-    }
-    *out = b;
+    *out = b.release();
     return GRAIL_OK;
 }
 
@@ -546,39 +536,12 @@ int grail_batch_upload_elems(grail_ctx *ctx, const grail_sequence_elem *segs,
         ds[i].frequency = segs[i].elem.frequency;
         std::memcpy(&elems[(size_t)i * ELEM_FLOATS], &segs[i].elem, sizeof(grail_synthesis_elem));
     }
-    // (what the launch policy asks of the segments, per utterance and over the batch, as for phoneme batches; a
-    // caller-built elem keeps its frequency as it is, copy_with_frequency's min(f, 0.5) :445-450 belongs to the Selector)
-    std::vector<RowStats> rows(n_utt);
-    // (the device's dt of the table's highest sample rate, as the kernels have it: an f32 reciprocal)
-    const double min_dt = ctx->facts.max_rate > 0.0f ? (double)(1.0f / ctx->facts.max_rate) : 0.0;
-    for (uint32_t u = 0; u < n_utt; ++u) {
-        RowStats &r = rows[u];
-        for (uint32_t i = seg_offsets[u]; i < seg_offsets[u + 1]; ++i) {
-            r.plain = r.plain && std::isfinite(segs[i].length) && std::isfinite(segs[i].blend_length) &&
-                      std::isfinite(segs[i].elem.frequency) && segs[i].blend_length > 0.0f;
-            r.any_blend = r.any_blend || !blend_is_pow2(segs[i].blend_length);
-            if (segs[i].length < r.min_length) r.min_length = segs[i].length;
-            if (segs[i].elem.frequency < r.min_pitch) r.min_pitch = segs[i].elem.frequency;
-            r.seconds += segs[i].length;
-            r.bound_samples += segment_bound(segs[i].length, min_dt);
-            r.segs += 1u;
-            r.kinks += segs[i].blend_length < segs[i].length ? 1u : 0u;
-        }
-    }
-    grail_batch *b = new (std::nothrow) grail_batch();
+    std::unique_ptr<grail_batch> b(new (std::nothrow) grail_batch());
     if (!b) return fail(GRAIL_ERR_OUT_OF_MEMORY, "host allocation failed");
     b->phoneme_mode = false;
-    b->plain = true;
-    b->min_length = INFINITY;
-    b->min_pitch = INFINITY;
-    for (const RowStats &r : rows) {
-        b->plain = b->plain && r.plain;
-        b->any_blend = b->any_blend || r.any_blend;
-        if (r.min_length < b->min_length) b->min_length = r.min_length;
-        if (r.min_pitch < b->min_pitch) b->min_pitch = r.min_pitch;
-        if (r.seconds > b->max_seconds) b->max_seconds = r.seconds;
-    }
     b->n_segs = n_segs;
+    // (a caller-built elem keeps its frequency as it is: copy_with_frequency's min(f, 0.5) :445-450 belongs to the Selector)
+    const std::vector<RowStats> rows = batch_stats(ctx, b.get(), ds.data(), seg_offsets, n_utt, [](float f) { return f; });
     // The elems of the batch, interned by their formant arrays (everything but the pitch, which none of the analyses
     // below looks at): a corpus names a few dozen distinct parameter sets in hundreds of thousands of segments.
     struct FormantsHash {
@@ -622,14 +585,11 @@ int grail_batch_upload_elems(grail_ctx *ctx, const grail_sequence_elem *segs,
             }
             b->elems_sharpness = std::fmax(b->elems_sharpness, it->second);
         }
-    if ((rc = upload(&b->d_segs, ds.data(), n_segs, ctx->stream)) ||
-        (rc = upload(&b->d_elems, elems.data(), elems.size(), ctx->stream)) ||
-        (rc = upload_common(ctx, b, seg_offsets, voice_ids, jitter_seeds, n_utt)) ||
-        (rc = upload_len_bound(ctx, b, rows, n_utt)) || (rc = upload_length_order(ctx, b, rows, n_utt))) {
-        free_batch_buffers(b);
-        delete b;
+    HIP_TRY(upload(b->d_segs, ds.data(), n_segs, ctx->stream));
+    HIP_TRY(upload(b->d_elems, elems.data(), elems.size(), ctx->stream));
+    if ((rc = upload_common(ctx, b.get(), seg_offsets, voice_ids, jitter_seeds, n_utt)) ||
+        (rc = upload_len_bound(ctx, b.get(), rows, n_utt)) || (rc = upload_length_order(ctx, b.get(), rows, n_utt)))
         return rc;
-    }
     // the warm-up length of the time-split fast kernels for THESE elems (elems_warmup: the slowest filter over the distinct
     // elems of the batch, the formant-frequency jitter of the voices it names), valid for the voice table of this moment;
     // 0: the batch does not qualify and fast arithmetic renders it with the lane kernels
@@ -656,14 +616,14 @@ int grail_batch_upload_elems(grail_ctx *ctx, const grail_sequence_elem *segs,
         for (uint32_t i = 0; i < n_segs; ++i) max_pitch = std::fmax(max_pitch, segs[i].elem.frequency);
         b->elems_scan_ok = rates_ok && max_pitch <= 0.5f && scan_elems_ok(distinct.data(), distinct.size(), (float)jd);
         b->elems_warmup_epoch = ctx->voices_epoch;
-        for (grail_batch &g : b->groups) {          // (the views were made before these were known)
+        for (RowGroup &g : b->groups) {             // (the groups were made before these were known)
             g.elems_warmup = b->elems_warmup;
             g.elems_warmup_epoch = b->elems_warmup_epoch;
             g.elems_live4_ok = b->elems_live4_ok;
             g.elems_scan_ok = b->elems_scan_ok;
         }
     }
-    *out = b;
+    *out = b.release();
     return GRAIL_OK;
 }
 
@@ -673,8 +633,7 @@ int grail_batch_free(grail_ctx *ctx, grail_batch *batch)
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    free_batch_buffers(batch);
-    delete batch;
+    delete batch;          // (its device arrays, packed tables and plans go with it)
     return GRAIL_OK;
 }
 
@@ -691,9 +650,9 @@ int grail_batch_lengths(grail_ctx *ctx, const grail_batch *batch, uint32_t max_l
     DeviceBuffer<uint32_t> d_len;
     HIP_TRY(d_len.alloc(batch->n_utt));
     LenArgs a{};
-    a.segs = batch->d_segs;
-    a.seg_offsets = batch->d_offsets;
-    a.voice_ids = batch->d_voice_ids;
+    a.segs = batch->d_segs.get();
+    a.seg_offsets = batch->d_offsets.get();
+    a.voice_ids = batch->d_voice_ids.get();
     a.voices = ctx->d_voices;
     a.out_len = d_len.get();
     a.n_utt = batch->n_utt;

@@ -1,6 +1,6 @@
 // launch_plan.cpp — which kernel family renders a block of rows, what a block costs, how a batch is cut into blocks.
-// Pure host arithmetic over the context's options and the batch's summary (no HIP call): grail_plan_blocks runs it
-// without a device.
+// Pure host arithmetic over what a context plans with (PlanEnv) and a batch's summary (BatchFacts); no HIP call, no type
+// that owns device memory: grail_plan_blocks runs it without a device.
 #include "api_internal.hpp"
 
 #include <functional>
@@ -25,7 +25,7 @@ int auto_lanes_per_utt(uint32_t n_utt, uint64_t simds)
 }
 
 // the longest utterance of the batch in samples, as far as the host knows it (the f32 clock adds a few per segment)
-double batch_span(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride)
+double batch_span(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride)
 {
     double span = std::ceil((double)batch->max_seconds * ctx->facts.max_rate) + 64.0;
     if (!(span >= 64.0)) span = 64.0;                         // NaN / negative lengths
@@ -53,7 +53,7 @@ static double mid_ms_per_sample(bool live4) { return (live4 ? MID_MS_4 : MID_MS_
 // Exact: 49.0 instead of 53.7 and 55.1 instead of 64.6; a speech-like corpus 58.1 instead of 67.0: profiles/r05_two_waves.txt).
 // Launches that fit one wave per SIMD keep the one-wave instantiations — which cannot share a SIMD, so where the dispatcher
 // puts their waves cannot matter.
-bool family_cohabits(const grail_ctx *ctx, const Family &f, uint32_t rows)
+bool family_cohabits(const PlanEnv *ctx, const Family &f, uint32_t rows)
 {
     if (!ctx->opt.two_waves_option || f.scan || f.pipe || f.split_k || f.fast > 1u) return false;
     // (tolerance mode: 2 lanes with four formants laid out, 4 and 8 lanes; exact: 2 lanes with four formants, 4 lanes —
@@ -83,7 +83,7 @@ static double cohabit_gain(const Family &f, double density = 0.0)
 // workgroup several calm tiles, so a small batch is spread thinly — as few utterances per workgroup as give every compute
 // unit two workgroups — instead of filling 16 (8) slots of a few workgroups and leaving the other units idle: 256 speech-like
 // utterances, one per workgroup, hold no event but their own (profiles/r05_mixed_runs.txt).
-uint32_t pipe_fill_for(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t rows)
+uint32_t pipe_fill_for(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t rows)
 {
     if (!f.pipe || !ctx->opt.pipe_spread || batch == nullptr || batch->granule_samples.size() < 2 ||
         batch->granule_samples.front() == batch->granule_samples.back())
@@ -97,7 +97,7 @@ uint32_t pipe_fill_for(const grail_ctx *ctx, const grail_batch *batch, const Fam
 }
 
 // what launching `rows` rows with family f costs (model milliseconds)
-double family_cost(const grail_ctx *ctx, const Family &f, uint32_t rows, double span)
+double family_cost(const PlanEnv *ctx, const Family &f, uint32_t rows, double span)
 {
     const double cus = (double)ctx->cus, lanes = (double)ctx_lanes(ctx);
     if (f.scan) {
@@ -144,14 +144,14 @@ double family_cost(const grail_ctx *ctx, const Family &f, uint32_t rows, double 
 // live formants somewhere in the table does not take the four-formant kernels away from batches that never use it.
 // (A context without per-voice records — grail_plan_blocks — goes by the table-wide flag.)
 template <typename Pred>
-static bool used_voices_all(const grail_ctx *ctx, const grail_batch *batch, bool table_wide, Pred pred)
+static bool used_voices_all(const PlanEnv *ctx, const BatchFacts *batch, bool table_wide, Pred pred)
 {
     if (ctx->facts.voice_info.empty() || batch->used_voices.empty()) return table_wide;
     for (const uint32_t v : batch->used_voices)
         if (v >= ctx->facts.voice_info.size() || !pred(ctx->facts.voice_info[v])) return false;
     return true;
 }
-bool batch_half_capable(const grail_ctx *ctx, const grail_batch *batch)
+bool batch_half_capable(const PlanEnv *ctx, const BatchFacts *batch)
 {
     // (caller-built elems: judged at upload over the batch's distinct elems, against the voice table of that moment)
     if (!batch->phoneme_mode)
@@ -164,7 +164,7 @@ bool batch_half_capable(const grail_ctx *ctx, const grail_batch *batch)
 // two samples long, so the Sequencer clock never goes negative and alpha stays in [0,1]; and
 // every pitch stays >= 2^-20 under the pitch jitter, so the polyBLEP quotient and with it the
 // saw every formant is fed from stay finite (a dead formant fed +-inf would emit NaN)
-bool batch_live4_any_blend(const grail_ctx *ctx, const grail_batch *batch)
+bool batch_live4_any_blend(const PlanEnv *ctx, const BatchFacts *batch)
 {
     return batch_half_capable(ctx, batch) &&
            (!batch->phoneme_mode ||
@@ -174,7 +174,7 @@ bool batch_live4_any_blend(const grail_ctx *ctx, const grail_batch *batch)
            batch->min_pitch * window::MARGIN_DOWN - window::JITTER_MARGIN * ctx->facts.max_pitch_jitter >= window::X_LO;
 }
 // ... and (the lane kernels' four-formant instantiations) every blend length a power of two
-bool batch_live4(const grail_ctx *ctx, const grail_batch *batch)
+bool batch_live4(const PlanEnv *ctx, const BatchFacts *batch)
 {
     return batch_live4_any_blend(ctx, batch) && !batch->any_blend;
 }
@@ -184,7 +184,7 @@ bool batch_live4(const grail_ctx *ctx, const grail_batch *batch)
 // of the scan kernel, the time-split kernels and the fast lane kernels by the cost model above (which follows the
 // utterances' length: a time-split pays a warm-up per chunk, the scan kernel the latency of one utterance's chain),
 // unless an option pins the choice.
-void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t fam, Family &f,
+void choose_family(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t fam, Family &f,
                    bool exact_only, int pin_lanes)
 {
     const uint64_t simds = ctx_simds(ctx), cus = (uint64_t)ctx->cus;
@@ -399,8 +399,8 @@ void choose_family(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_
 // plan for the rest.  Exact arithmetic is mapping-invariant, so the cut never changes a bit; in fast arithmetic a row's
 // samples follow the family of ITS block (include/grail_hip.h, "Determinism contract").
 struct Planner {
-    const grail_ctx *ctx;
-    const grail_batch *batch;
+    const PlanEnv *ctx;
+    const BatchFacts *batch;
     uint64_t out_stride;
     double span;
     bool exact_only;                           // (the plan a fast request is weighed against: ragged_plan)
@@ -450,7 +450,7 @@ struct Planner {
     }
 };
 
-double plan_blocks(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t rows, double span,
+double plan_blocks(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t rows, double span,
                    std::vector<Block> &out, bool exact_only)
 {
     Planner p{ctx, batch, out_stride, span, exact_only, {}, {}};
@@ -518,7 +518,7 @@ static double ragged_wave_ms(const Family &f, double samples, double segs, doubl
     return samples * rate * m + events * (nfa4 ? c4 : c8)[li];
 }
 
-double ragged_cost(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t slot0, uint32_t rows, double span)
+double ragged_cost(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t slot0, uint32_t rows, double span)
 {
     const size_t n_gran = batch->granule_samples.size();
     if (n_gran == 0 || rows == 0) return family_cost(ctx, f, rows, span);
@@ -677,7 +677,7 @@ struct Dispatcher {
     uint32_t pools() const { return xcc * se; }
 };
 
-static Dispatcher dispatcher_of(const grail_ctx *ctx, const uint32_t waves_per_block)
+static Dispatcher dispatcher_of(const PlanEnv *ctx, const uint32_t waves_per_block)
 {
     Dispatcher d;
     const uint32_t cus = (uint32_t)ctx->cus;
@@ -790,7 +790,7 @@ static void pack_order(const Dispatcher &d, const std::vector<double> &cost_in, 
     }
 }
 
-bool packed_launch_order(const grail_ctx *ctx, const grail_batch *batch, const Family &f, uint32_t slot0, uint32_t rows, double span,
+bool packed_launch_order(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t slot0, uint32_t rows, double span,
                          std::vector<uint32_t> *order, uint32_t *rows_per_block, double *plain_ms, double *packed_ms)
 {
     if (order) order->clear();
@@ -834,7 +834,7 @@ bool packed_launch_order(const grail_ctx *ctx, const grail_batch *batch, const F
     return true;
 }
 
-void ragged_plan(const grail_ctx *ctx, const grail_batch *batch, uint64_t out_stride, uint32_t rows, std::vector<Block> &plan)
+void ragged_plan(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t rows, std::vector<Block> &plan)
 {
     if (!ctx->opt.ragged_option || batch->granule_samples.empty() || rows != batch->n_utt || plan.empty()) return;
     if (plan.size() == 1 && plan[0].f.scan) return;   // (a few utterances in fast arithmetic: the scan kernel's)
@@ -907,8 +907,8 @@ int grail_dispatch_model(uint32_t compute_units, uint32_t waves_per_workgroup, c
     if (!makespan_ms || (n && !workgroup_ms)) return fail(GRAIL_ERR_INVALID_ARG, "NULL argument");
     if (compute_units == 0 || compute_units > 4096 || (waves_per_workgroup != 1 && waves_per_workgroup != 4))
         return fail(GRAIL_ERR_INVALID_ARG, "compute_units must be 1 .. 4096, waves_per_workgroup 1 or 4");
-    grail_ctx ctx;
-    ctx.cus = ctx.device_cus = (int)compute_units;
+    PlanEnv ctx;
+    ctx.cus = (int)compute_units;
     std::vector<double> cost(workgroup_ms, workgroup_ms + n);
     std::vector<uint32_t> o;
     if (order) {
@@ -926,8 +926,8 @@ int grail_packed_launch_order(uint32_t compute_units, uint32_t waves_per_workgro
     if (n && (!workgroup_ms || !order)) return fail(GRAIL_ERR_INVALID_ARG, "NULL argument");
     if (compute_units == 0 || compute_units > 4096 || (waves_per_workgroup != 1 && waves_per_workgroup != 4))
         return fail(GRAIL_ERR_INVALID_ARG, "compute_units must be 1 .. 4096, waves_per_workgroup 1 or 4");
-    grail_ctx ctx;
-    ctx.cus = ctx.device_cus = (int)compute_units;
+    PlanEnv ctx;
+    ctx.cus = (int)compute_units;
     std::vector<double> cost(workgroup_ms, workgroup_ms + n);
     std::vector<uint32_t> o;
     pack_order(dispatcher_of(&ctx, waves_per_workgroup), cost, n, o);
@@ -948,8 +948,8 @@ static int plan_preview(uint32_t compute_units, int arithmetic, int live_formant
     if (rows == 0) return GRAIL_OK;
     // a context and a batch as choose_family sees them: default options, a voice table that qualifies for every
     // family (four or eight live formants), a plain phoneme batch with power-of-two blend lengths
-    grail_ctx ctx;
-    ctx.cus = ctx.device_cus = (int)compute_units;
+    PlanEnv ctx;
+    ctx.cus = (int)compute_units;
     ctx.opt.fast_option = arithmetic;
     VoiceFacts &facts = ctx.facts;
     facts.voices_sharpness = 0.0;
@@ -959,7 +959,7 @@ static int plan_preview(uint32_t compute_units, int arithmetic, int live_formant
     facts.max_warmup = warmup;
     facts.max_rate = 1.0f;                // max_seconds below is in samples
     facts.max_dt = 1.0f;
-    grail_batch batch;
+    BatchFacts batch;
     batch.n_utt = rows;
     batch.phoneme_mode = true;
     batch.plain = true;

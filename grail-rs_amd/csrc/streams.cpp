@@ -64,27 +64,18 @@ static int stream_next(grail_ctx *ctx, grail_stream *stream, uint32_t max_sample
     if (batch->n_utt == 0) return GRAIL_OK;
     if (!out_dev && !out_pcm16_dev && max_samples) return fail(GRAIL_ERR_INVALID_ARG, "out_dev is NULL");
     SynthArgs a{};
-    a.segs = batch->d_segs;
-    a.seg_offsets = batch->d_offsets;
+    batch_args(ctx, batch, 0u, a);
     a.ring_cap = stream->ring_cap;
     a.seg_counts = stream->d_counts.get();
     a.seg_open = stream->d_open.get();
     a.seg_consumed = stream->d_consumed.get();
-    a.voice_ids = batch->d_voice_ids;
-    a.seeds = batch->d_seeds;
-    a.perm = batch->d_perm;
-    a.elems = batch->phoneme_mode ? ctx->d_voice_elems : batch->d_elems;
-    a.voices = ctx->d_voices;
+    a.perm = batch->d_perm.get();
     a.out = out_dev;
     a.out_pcm16 = out_pcm16_dev;
     a.out_len = out_len_dev;
-    a.truncated = ctx->d_truncated;
     a.out_stride = out_stride;
     a.cap = max_samples;
     a.n_utt = batch->n_utt;
-    a.n_voices = (uint32_t)ctx->voices.size();
-    a.phoneme_mode = batch->phoneme_mode ? 1u : 0u;
-    a.skip_silent = ctx->opt.skip_silent_option ? 1u : 0u;
     if (stream->voices_epoch != ctx->voices_epoch)
         return fail(GRAIL_ERR_INVALID_ARG, "the voice table changed since the stream was opened");
     a.half_capable = stream->half_capable ? 1u : 0u;
@@ -141,11 +132,7 @@ int grail_stream_close(grail_ctx *ctx, grail_stream *stream)
         if (stream->h_stage[i]) (void)hipHostFree(stream->h_stage[i]);
         if (stream->ev_stage[i]) (void)hipEventDestroy(stream->ev_stage[i]);
     }
-    if (stream->own) {
-        free_batch_buffers(stream->own);
-        delete stream->own;
-    }
-    delete stream;          // (its device buffers go with it)
+    delete stream;          // (its device buffers go with it, and the batch a live stream owns)
     return GRAIL_OK;
 }
 
@@ -170,43 +157,29 @@ int grail_stream_open_live(grail_ctx *ctx, uint32_t n_utt, const uint32_t *voice
         delete s;
         return fail(GRAIL_ERR_OUT_OF_MEMORY, "host allocation failed");
     }
-    s->own = b;
+    s->own.reset(b);
     s->batch = b;
     s->ring_cap = ring_segments;
     b->phoneme_mode = !caller_built_elems;
     b->any_blend = true;          // what will be appended is not known: the general instantiations
     b->plain = false;
     b->n_utt = n_utt;
-    b->max_voice_id = 0;
-    b->used_voices.assign(1, 0u);
-    if (voice_ids) {
-        for (uint32_t u = 0; u < n_utt; ++u) b->max_voice_id = std::max(b->max_voice_id, voice_ids[u]);
-        b->used_voices.assign(voice_ids, voice_ids + n_utt);
-        std::sort(b->used_voices.begin(), b->used_voices.end());
-        b->used_voices.erase(std::unique(b->used_voices.begin(), b->used_voices.end()), b->used_voices.end());
+    name_voices(*b, voice_ids, n_utt);
+    const size_t ring_rows = (size_t)n_utt * ring_segments;      // (>= 4)
+    hipError_t e = b->d_segs.alloc(ring_rows);
+    if (e == hipSuccess) e = hipMemsetAsync(b->d_segs.get(), 0, ring_rows * sizeof(DevSeg), ctx->stream);
+    if (e == hipSuccess && caller_built_elems) {
+        e = b->d_elems.alloc(ring_rows * ELEM_FLOATS);
+        if (e == hipSuccess) e = hipMemsetAsync(b->d_elems.get(), 0, ring_rows * ELEM_FLOATS * sizeof(float), ctx->stream);
     }
-    const size_t ring_rows = (size_t)n_utt * ring_segments;
-    hipError_t e = hipSuccess;
-    auto zeroed = [&](void **p, size_t bytes) {
-        if (e == hipSuccess) e = hipMalloc(p, bytes ? bytes : 4);
-        if (e == hipSuccess) e = hipMemsetAsync(*p, 0, bytes ? bytes : 4, ctx->stream);
-    };
-    zeroed((void **)&b->d_segs, ring_rows * sizeof(DevSeg));
-    if (caller_built_elems) zeroed((void **)&b->d_elems, ring_rows * ELEM_FLOATS * sizeof(float));
     for (DeviceBuffer<uint32_t> *p : {&s->d_counts, &s->d_consumed}) {
         if (e == hipSuccess) e = p->alloc(n_utt);
         if (e == hipSuccess) e = hipMemsetAsync(p->get(), 0, (size_t)n_utt * 4, ctx->stream);
     }
     if (e == hipSuccess) e = s->d_open.alloc(n_utt);
     if (e == hipSuccess) e = hipMemsetD32Async((hipDeviceptr_t)s->d_open.get(), 1, n_utt, ctx->stream);
-    if (e == hipSuccess && voice_ids) {
-        e = hipMalloc((void **)&b->d_voice_ids, (size_t)n_utt * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(b->d_voice_ids, voice_ids, (size_t)n_utt * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
-    if (e == hipSuccess && jitter_seeds) {
-        e = hipMalloc((void **)&b->d_seeds, (size_t)n_utt * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(b->d_seeds, jitter_seeds, (size_t)n_utt * 4, hipMemcpyHostToDevice, ctx->stream);
-    }
+    if (e == hipSuccess && voice_ids) e = upload(b->d_voice_ids, voice_ids, n_utt, ctx->stream);
+    if (e == hipSuccess && jitter_seeds) e = upload(b->d_seeds, jitter_seeds, n_utt, ctx->stream);
     s->half_capable = batch_half_capable(ctx, b);
     s->any_blend = true;
     s->live4 = false;
@@ -306,7 +279,7 @@ static int live_append(grail_ctx *ctx, grail_stream *s, const std::vector<DevSeg
         e = hipMemcpyAsync(s->d_new_elems.get(), h + b_segs + b_offs, b_elems, hipMemcpyHostToDevice, ctx->stream);
     // (stream order: behind every kernel that still reads the rings, ahead of every kernel that will)
     if (e == hipSuccess)
-        e = launch_ring_append(s->own->d_segs, s->own->d_elems, s->d_counts.get(), cap, s->d_new.get(),
+        e = launch_ring_append(s->own->d_segs.get(), s->own->d_elems.get(), s->d_counts.get(), cap, s->d_new.get(),
                                elems ? s->d_new_elems.get() : nullptr, s->d_new_offs.get(), n_utt, ctx->stream);
     if (e == hipSuccess) e = hipEventRecord(s->ev_stage[slot], ctx->stream);
     if (e != hipSuccess) {

@@ -1,49 +1,60 @@
 // synthesize.cpp — a batch's rows to kernel launches: the cached block plan of a batch, one launch per block
 // (launch_plan.cpp chose the families), the device-resident entry points.
-#include <mutex>
-
 #include "api_internal.hpp"
 
 using namespace grail;
 using namespace grail::host;
 
-// the launch plan of the last synthesis call of a batch (grail_batch::plan_cache), with what it was made for
-struct PlanCache {
-    uint64_t key[6];
-    std::vector<Block> plan;
-};
-
 namespace grail {
 namespace host {
+
+// the rows a plan is made for: the batch as a whole (id 0) or its row group g (id 1 + g, from launch slot slot0 on)
+struct View {
+    const BatchFacts *facts;
+    PlanCache *cache;
+    uint32_t id, slot0;
+};
+
+void batch_args(const grail_ctx *ctx, const grail_batch *batch, uint32_t row0, SynthArgs &a)
+{
+    a.segs = batch->d_segs.get();
+    a.seg_offsets = batch->d_offsets.get() + row0;       // the offsets themselves are absolute into segs
+    a.voice_ids = batch->d_voice_ids.get() ? batch->d_voice_ids.get() + row0 : nullptr;
+    a.seeds = batch->d_seeds.get() ? batch->d_seeds.get() + row0 : nullptr;
+    a.elems = batch->phoneme_mode ? ctx->d_voice_elems : batch->d_elems.get();
+    a.voices = ctx->d_voices;
+    a.truncated = ctx->d_truncated;
+    a.n_voices = (uint32_t)ctx->voices.size();
+    a.phoneme_mode = batch->phoneme_mode ? 1u : 0u;
+    a.skip_silent = ctx->opt.skip_silent_option ? 1u : 0u;
+}
 
 // One launch: `count` launch slots from slot `slot0` of the rows [first, first + n_rows) the caller renders, with
 // family f.  out_dev / out_len_dev point at row `first`.  use_perm: the batch's length-sorted slot order applies
 // (whole-batch calls): slot s renders utterance perm[s], and every per-utterance array is indexed by the utterance.
 // The block's slot -> utterance table in PACKED launch order (launch_plan.cpp, "The workgroup dispatcher"), made at the
-// block's first launch and kept by the root batch; nullptr: the plain order (it is as good, or the block does not qualify).
-static const uint32_t *packed_perm_of(grail_ctx *ctx, const grail_batch *root, const grail_batch *view, const Family &f,
+// block's first launch and kept by the batch; nullptr: the plain order (it is as good, or the block does not qualify).
+static const uint32_t *packed_perm_of(grail_ctx *ctx, const grail_batch *root, const View &view, const Family &f,
                                       uint64_t out_stride, uint32_t slot0, uint32_t count, int *rc)
 {
     *rc = GRAIL_OK;
     if (!ctx->opt.packed_option || root->perm_host.size() < (size_t)slot0 + count) return nullptr;
     const uint32_t family = (uint32_t)f.L | f.fast << 8 | f.live4 << 16;
-    static std::mutex lock;                    // (one batch may be rendered by several contexts, each on a thread of its own)
-    std::lock_guard<std::mutex> hold(lock);
+    std::lock_guard<std::mutex> hold(root->lock);
     for (const PackedPerm &pp : root->packed)
-        if (pp.view == view && pp.slot0 == slot0 && pp.rows == count && pp.family == family && pp.cus == (uint32_t)ctx->cus)
-            return pp.d_perm;
+        if (pp.view == view.id && pp.slot0 == slot0 && pp.rows == count && pp.family == family && pp.cus == (uint32_t)ctx->cus)
+            return pp.d_perm.get();
     if (root->packed.size() >= 8) return nullptr;      // (a batch launched under ever new plans: stop collecting tables)
     PackedPerm pp;
-    pp.view = view;
+    pp.view = view.id;
     pp.slot0 = slot0;
     pp.rows = count;
     pp.family = family;
     pp.cus = (uint32_t)ctx->cus;
     std::vector<uint32_t> order;
     // (a view's granules count from ITS first slot: the second row group's slots start behind the first's)
-    const uint32_t view_slot0 = view == root || root->groups.size() != 2 || view == &root->groups[0] ? slot0 : slot0 - root->groups[0].n_utt;
-    if (packed_launch_order(ctx, view, f, view_slot0, count, batch_span(ctx, view, out_stride), &order, &pp.per_block, &pp.plain_ms,
-                            &pp.model_ms)) {
+    if (packed_launch_order(ctx, view.facts, f, slot0 - view.slot0, count, batch_span(ctx, view.facts, out_stride), &order,
+                            &pp.per_block, &pp.plain_ms, &pp.model_ms)) {
         std::vector<uint32_t> perm(count);
         const uint32_t *src = root->perm_host.data() + slot0;
         size_t at = 0;
@@ -51,58 +62,49 @@ static const uint32_t *packed_perm_of(grail_ctx *ctx, const grail_batch *root, c
             const size_t lo = (size_t)b * pp.per_block, hi = std::min<size_t>(lo + pp.per_block, count);
             for (size_t i = lo; i < hi; ++i) perm[at++] = src[i];
         }
-        hipError_t e = at == count ? hipMalloc((void **)&pp.d_perm, (size_t)count * sizeof(uint32_t)) : hipErrorInvalidValue;
-        if (e == hipSuccess) e = hipMemcpyAsync(pp.d_perm, perm.data(), (size_t)count * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+        hipError_t e = at == count ? upload(pp.d_perm, perm.data(), count, ctx->stream) : hipErrorInvalidValue;
         if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);      // (`perm` is a local; other contexts may use the table next)
         if (e != hipSuccess) {
-            if (pp.d_perm) (void)hipFree(pp.d_perm);
             *rc = hip_fail(e, "packed launch order");
             return nullptr;
         }
     }
-    root->packed.push_back(pp);
-    return pp.d_perm;
+    root->packed.push_back(std::move(pp));
+    return root->packed.back().d_perm.get();
 }
 
-static int launch_block(grail_ctx *ctx, const grail_batch *root, const grail_batch *batch, const Family &f, float *out_dev,
+// (root: the device arrays; view: the facts of the rows the block belongs to)
+static int launch_block(grail_ctx *ctx, const grail_batch *root, const View &view, const Family &f, float *out_dev,
                         int16_t *out_pcm16_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t first, uint32_t slot0,
                         uint32_t count, bool use_perm)
 {
+    const BatchFacts *batch = view.facts;
     SynthArgs a{};
     const uint32_t row0 = use_perm ? 0u : first + slot0;      // the utterance that index 0 of the launch's arrays is
     const uint64_t out_shift = use_perm ? 0ull : (uint64_t)slot0 * out_stride;
+    batch_args(ctx, root, row0, a);
     a.out_pcm16 = out_pcm16_dev ? out_pcm16_dev + out_shift : nullptr;
-    a.segs = batch->d_segs;
-    a.seg_offsets = batch->d_offsets + row0;       // the offsets themselves are absolute into segs
-    a.voice_ids = batch->d_voice_ids ? batch->d_voice_ids + row0 : nullptr;
-    a.seeds = batch->d_seeds ? batch->d_seeds + row0 : nullptr;
-    a.perm = use_perm ? batch->d_perm + slot0 : nullptr;
+    a.perm = use_perm ? root->d_perm.get() + slot0 : nullptr;
     if (use_perm) {
         int rc = GRAIL_OK;
-        const uint32_t *packed = packed_perm_of(ctx, root, batch, f, out_stride, slot0, count, &rc);
+        const uint32_t *packed = packed_perm_of(ctx, root, view, f, out_stride, slot0, count, &rc);
         if (rc) return rc;
         if (packed) {
             a.perm = packed;
             ++ctx->stats.last_packed;
         }
     }
-    a.elems = batch->phoneme_mode ? ctx->d_voice_elems : batch->d_elems;
-    a.voices = ctx->d_voices;
     a.out = out_dev ? out_dev + out_shift : nullptr;
     a.out_len = out_len_dev ? out_len_dev + (use_perm ? 0u : slot0) : nullptr;
-    a.truncated = ctx->d_truncated;
     a.out_stride = out_stride;
     a.cap = out_stride;
     a.n_utt = count;
-    a.n_voices = (uint32_t)ctx->voices.size();
-    a.phoneme_mode = batch->phoneme_mode ? 1u : 0u;
-    a.skip_silent = ctx->opt.skip_silent_option ? 1u : 0u;
     a.half_capable = batch_half_capable(ctx, batch) ? 1u : 0u;
     a.any_blend = batch->any_blend ? 1u : 0u;
     a.live4 = f.live4;
     a.fast = f.fast;
     a.cohabit = family_cohabits(ctx, f, count) ? 1u : 0u;
-    a.len_bound = batch->d_len_bound && batch->len_bound_epoch == ctx->voices_epoch ? batch->d_len_bound + row0 : nullptr;
+    a.len_bound = root->d_len_bound.get() && batch->len_bound_epoch == ctx->voices_epoch ? root->d_len_bound.get() + row0 : nullptr;
     a.pipe_fill = pipe_fill_for(ctx, batch, f, count);
     a.fold_from = 0u;
     if (a.cohabit) {
@@ -131,8 +133,6 @@ static int launch_block(grail_ctx *ctx, const grail_batch *root, const grail_bat
     if (e != hipSuccess) return hip_fail(e, "synth kernel launch");
     return GRAIL_OK;
 }
-
-void free_plan_cache(PlanCache *p) { delete p; }
 
 // the statistics of a synthesis call before its launches: f0 is the family of its largest block; the launches add the
 // kernel's name, the packed blocks and the highest tier that ran
@@ -166,72 +166,70 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev,
     if (count == 0) count = batch->n_utt - first;
     if (count == 0) return GRAIL_OK;
     // the length-sorted slot assignment covers the whole batch: row-block launches keep launch order
-    const bool use_perm = first == 0 && count == batch->n_utt && batch->d_perm;
-    // the launch plan of `rows` rows of a (view of the) batch, cached with what it was made for
-    auto plan_of = [&](const grail_batch *view, const uint32_t rows) {
+    const bool use_perm = first == 0 && count == batch->n_utt && batch->d_perm.get();
+    // the launch plan of `rows` rows of the batch or of a row group, cached with what it was made for
+    auto plan_of = [&](const View &view, const uint32_t rows) {
+        const BatchFacts *facts = view.facts;
         std::vector<Block> plan;
         const uint64_t key[6] = {rows, out_stride, family_rows, ctx->options_epoch, ctx->voices_epoch,
-                                 (uint64_t)(uintptr_t)ctx ^ (view->phoneme_mode ? 0ull : (uint64_t)(view->elems_sharpness * 1024.0))};
-        // (one batch may be rendered by several contexts, each on a thread of its own: the cache is read and replaced
-        // under a lock — the plans are a few dozen bytes, the lock is held for a copy)
-        static std::mutex cache_lock;
+                                 (uint64_t)(uintptr_t)ctx ^ (facts->phoneme_mode ? 0ull : (uint64_t)(facts->elems_sharpness * 1024.0))};
+        // (the cache is read and replaced under the batch's lock — the plans are a few dozen bytes, the lock is held for a copy)
         {
-            std::lock_guard<std::mutex> hold(cache_lock);
-            if (view->plan_cache && std::memcmp(view->plan_cache->key, key, sizeof key) == 0) return view->plan_cache->plan;
+            std::lock_guard<std::mutex> hold(batch->lock);
+            if (!view.cache->plan.empty() && std::memcmp(view.cache->key, key, sizeof key) == 0) return view.cache->plan;
         }
         // one launch when the caller fixes the family (row blocks, a pinned lane mapping or chunk grid) or asks for it
         const bool single = family_rows != 0 || !ctx->opt.composite_option || ctx->opt.lanes_option || ctx->opt.split_chunks >= 2;
         if (single) {
             Family f;
-            choose_family(ctx, view, out_stride, family_rows > rows ? family_rows : rows, f);
+            choose_family(ctx, facts, out_stride, family_rows > rows ? family_rows : rows, f);
             plan.push_back(Block{rows, f});
         } else {
-            plan_blocks(ctx, view, out_stride, rows, batch_span(ctx, view, out_stride), plan);
+            plan_blocks(ctx, facts, out_stride, rows, batch_span(ctx, facts, out_stride), plan);
             // length-sorted batches: the plan weighed against each lane mapping in as many rounds as it takes, by the
             // lengths and events of the rows (launch_plan.cpp, "Ragged batches")
             // (the batch itself, or the first of its row groups: those rows hold launch slots 0 .. rows - 1 of the sorted order)
-            if (use_perm && (view == batch || (batch->groups.size() == 2 && view == &batch->groups[0])))
-                ragged_plan(ctx, view, out_stride, rows, plan);
+            if (use_perm && view.slot0 == 0) ragged_plan(ctx, facts, out_stride, rows, plan);
         }
         {
-            std::lock_guard<std::mutex> hold(cache_lock);
-            if (!view->plan_cache) view->plan_cache = new (std::nothrow) PlanCache();
-            if (view->plan_cache) {
-                std::memcpy(view->plan_cache->key, key, sizeof key);
-                view->plan_cache->plan = plan;
-            }
+            std::lock_guard<std::mutex> hold(batch->lock);
+            std::memcpy(view.cache->key, key, sizeof key);
+            view.cache->plan = plan;
         }
         return plan;
     };
-    // Row groups (grail_batch::groups): the rows the lean families cannot take sit last in the slot order and are planned
-    // as a batch of their own, so that a few of them do not decide the kernels of all.  Whole-batch launches only, and
-    // only while the voice table is the one the rows were judged against.
+    // Row groups (RowGroup): the rows the lean families cannot take sit last in the slot order and are planned as a batch
+    // of their own, so that a few of them do not decide the kernels of all.  Whole-batch launches only, and only while
+    // the voice table is the one the rows were judged against.
     struct Part {
-        const grail_batch *view;
+        View view;
         Block block;
     };
+    const View whole{batch, &batch->plan_cache, 0u, 0u};
     std::vector<Part> plan;
-    for (const Block &b : plan_of(batch, count)) plan.push_back(Part{batch, b});
+    for (const Block &b : plan_of(whole, count)) plan.push_back(Part{whole, b});
     if (use_perm && family_rows == 0 && ctx->opt.row_groups_option && batch->groups.size() == 2 && batch->groups_epoch == ctx->voices_epoch) {
         // ... where that is cheaper by the cost model: a separate launch for four odd rows behind a full round of the
         // one-lane kernel costs more than it saves (53.7 against 46.7 ms), behind 20 000 rows it does not
-        // (by the rows' own lengths and events where the view has them — a ragged corpus: ragged_cost falls back to the
+        // (by the rows' own lengths and events where the group has them — a ragged corpus: ragged_cost falls back to the
         // one-round price of the family otherwise)
         auto cost_of = [&](const std::vector<Part> &parts) {
             double c = 0.0;
-            uint32_t at = 0;
-            const grail_batch *of = nullptr;
+            uint32_t at = 0, of = 0xFFFFFFFFu;
             for (const Part &p : parts) {
-                if (p.view != of) at = 0;        // (a view's blocks follow each other from its first slot)
-                of = p.view;
-                c += ragged_cost(ctx, p.view, p.block.f, at, p.block.rows, batch_span(ctx, p.view, out_stride)) + 0.05;
+                if (p.view.id != of) at = 0;        // (a view's blocks follow each other from its first slot)
+                of = p.view.id;
+                c += ragged_cost(ctx, p.view.facts, p.block.f, at, p.block.rows, batch_span(ctx, p.view.facts, out_stride)) + 0.05;
                 at += p.block.rows;
             }
             return c;
         };
         std::vector<Part> grouped;
-        for (const grail_batch &g : batch->groups)
-            for (const Block &b : plan_of(&g, g.n_utt)) grouped.push_back(Part{&g, b});
+        for (uint32_t g = 0; g < 2; ++g) {
+            const RowGroup &group = batch->groups[g];
+            const View view{&group, &group.plan_cache, 1u + g, group.slot0};
+            for (const Block &b : plan_of(view, group.n_utt)) grouped.push_back(Part{view, b});
+        }
         if (ctx->opt.row_groups_option == 2 || cost_of(grouped) < cost_of(plan)) plan.swap(grouped);
     }
     size_t main_block = 0;                     // the block with the most rows: the one the statistics describe

@@ -201,7 +201,7 @@ double elems_sharpness(const grail_synthesis_elem *elems, size_t n)
 // Is fast arithmetic served for this batch?  Caller-built elems are judged themselves; a phoneme batch by the sharpest of
 // the voices IT USES (one sharp voice in the table does not take fast arithmetic away from batches that never name it);
 // without a batch: by the whole table.
-double batch_sharpness(const grail_ctx *ctx, const grail_batch *batch)
+double batch_sharpness(const PlanEnv *ctx, const BatchFacts *batch)
 {
     if (!batch) return ctx->facts.voices_sharpness;
     if (!batch->phoneme_mode) return batch->elems_sharpness;
@@ -212,7 +212,7 @@ double batch_sharpness(const grail_ctx *ctx, const grail_batch *batch)
 // Which arithmetic a batch is rendered in when "arithmetic" asks for a tolerance mode: 1 = the interpolating tier (up
 // to "fast_sharpness_limit"), 2 = the reference's own band-pass coefficients at every sample (MID; sharper voices, up to
 // "fast_sharpness_limit_exact_coefficients"), 0 = the exact kernels (sharper still, or the tier switched off).
-int fast_tier_for(const grail_ctx *ctx, const grail_batch *batch, int arithmetic)
+int fast_tier_for(const PlanEnv *ctx, const BatchFacts *batch, int arithmetic)
 {
     if (!arithmetic) return 0;
     const double s = batch_sharpness(ctx, batch);
@@ -220,7 +220,7 @@ int fast_tier_for(const grail_ctx *ctx, const grail_batch *batch, int arithmetic
     if ((ctx->opt.mid_option || arithmetic == 2) && s <= (double)ctx->opt.mid_limit) return 2;
     return 0;
 }
-int fast_tier(const grail_ctx *ctx, const grail_batch *batch) { return fast_tier_for(ctx, batch, ctx->opt.fast_option); }
+int fast_tier(const PlanEnv *ctx, const BatchFacts *batch) { return fast_tier_for(ctx, batch, ctx->opt.fast_option); }
 // The chunk grid of a time-split launch: K chunks over `span` samples.  Chunk k's lane fast-forwards the chain over
 // b[k] - W samples (cost r per sample, in units of a rendered sample), warms up over W and renders b[k+1] - b[k]:
 // the bounds are spaced so that all lanes take the same time (T below, by bisection).  Bounds are multiples
