@@ -3,8 +3,8 @@
 // grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
 // families, cost model, block planner; synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
 // mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak) and limited; host_output.cpp: the one-call
-// forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Device memory whose owner only
-// these units create is held in DeviceBuffer (below).
+// forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Every HIP resource these units
+// create has one owner type (below): Event, Stream, DeviceBuffer, PinnedBuffer.
 #pragma once
 
 #include <dlfcn.h>
@@ -127,60 +127,107 @@ std::string &last_error();
         if (e_ != hipSuccess) return ::grail::host::hip_fail(e_, #expr); \
     } while (0)
 
-// One hipMalloc allocation of `capacity()` elements and its only owner (move-only; the destructor frees).  Every device
-// buffer of the per-context scratch (LevelState, MixState), of a stream and of the calls' temporaries is one of these;
-// `reserve` is their one growth rule: grown when too small, never shrunk.
-// A batch's arrays and its packed launch tables are such buffers too.  NOT for grail_ctx (d_voices, d_voice_elems,
-// d_truncated; the three opaque state pointers stay void *): tests/sanitize_options_driver.cpp constructs one on the stack in
-// a program that is built without hipcc and linked without the HIP runtime, where a member whose destructor calls hipFree
-// would not link.  The launch policy (launch_plan.cpp, voice_analysis.cpp), linked into the same programs, never sees a
-// type that holds one: its inputs are PlanEnv and BatchFacts.
-template <typename T>
-class DeviceBuffer {
+// One HIP resource and its only owner: move-only, the destructor releases, an empty one holds nothing and releases
+// nothing.  Contexts, batches, streams, the per-context parts of the units and the calls' temporaries hold their events,
+// streams, device and pinned memory in the four types below and in nothing else, so `delete` is all their tear-down.
+template <typename H, hipError_t (*Release)(H)>
+class Handle {
 public:
-    DeviceBuffer() = default;
-    DeviceBuffer(DeviceBuffer &&o) noexcept : p_(std::exchange(o.p_, nullptr)), cap_(std::exchange(o.cap_, 0)) {}
-    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept
+    Handle() = default;
+    Handle(Handle &&o) noexcept : h_(std::exchange(o.h_, H{})) {}
+    Handle &operator=(Handle &&o) noexcept
     {
         if (this != &o) {
             reset();
-            p_ = std::exchange(o.p_, nullptr);
-            cap_ = std::exchange(o.cap_, 0);
+            h_ = std::exchange(o.h_, H{});
         }
         return *this;
     }
-    ~DeviceBuffer() { reset(); }
-    T *get() const { return p_; }
-    size_t capacity() const { return cap_; }
+    ~Handle() { reset(); }
+    H get() const { return h_; }
     void reset()
     {
-        if (p_) (void)hipFree(p_);
-        p_ = nullptr;
-        cap_ = 0;
+        if (h_) (void)Release(h_);
+        h_ = H{};
     }
+    // what was held is released first, then make(&slot) fills the slot; a failure leaves it empty
+    template <typename Make>
+    hipError_t renew(Make make)
+    {
+        reset();
+        const hipError_t e = make(&h_);
+        if (e != hipSuccess) h_ = H{};
+        return e;
+    }
+
+private:
+    H h_{};
+};
+
+// created on demand (`if (!ev) ev.create()`); only the context's two timing events keep their time stamps
+struct Event : Handle<hipEvent_t, hipEventDestroy> {
+    hipError_t create(bool timing = false)
+    {
+        return renew([&](hipEvent_t *ev) { return timing ? hipEventCreate(ev) : hipEventCreateWithFlags(ev, hipEventDisableTiming); });
+    }
+    operator hipEvent_t() const { return get(); }
+};
+
+// a non-blocking stream.  Its holder declares it before whatever may be queued on it, so that it is destroyed last.
+struct Stream : Handle<hipStream_t, hipStreamDestroy> {
+    hipError_t create()
+    {
+        return renew([](hipStream_t *s) { return hipStreamCreateWithFlags(s, hipStreamNonBlocking); });
+    }
+    operator hipStream_t() const { return get(); }
+};
+
+// One hipMalloc allocation of `capacity()` elements.  `reserve` is the one growth rule of device memory: grown when too
+// small, never shrunk.  The launch policy (launch_plan.cpp, voice_analysis.cpp) never sees a type that holds one: its
+// inputs are PlanEnv and BatchFacts.
+template <typename T>
+class DeviceBuffer {
+public:
+    T *get() const { return static_cast<T *>(mem_.get()); }
+    size_t capacity() const { return mem_.get() ? cap_ : 0; }
+    void reset() { mem_.reset(); }
     // exactly max(n, 1) elements; what was held is released first
     hipError_t alloc(size_t n)
     {
-        reset();
-        n = std::max<size_t>(n, 1);
-        const hipError_t e = hipMalloc((void **)&p_, n * sizeof(T));
-        if (e != hipSuccess) p_ = nullptr;
-        else cap_ = n;
-        return e;
+        cap_ = std::max<size_t>(n, 1);
+        return mem_.renew([&](void **p) { return hipMalloc(p, cap_ * sizeof(T)); });
     }
     // room for `need` elements: nothing to do when there is; else `want` (>= need) of them, once everything queued on
     // `stream` is through (a kernel or copy still queued may use the old buffer)
     int reserve(hipStream_t stream, size_t need, size_t want)
     {
-        if (cap_ >= std::max<size_t>(need, 1)) return GRAIL_OK;
-        if (p_) HIP_TRY(hipStreamSynchronize(stream));
+        if (capacity() >= std::max<size_t>(need, 1)) return GRAIL_OK;
+        if (get()) HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(alloc(want));
         return GRAIL_OK;
     }
     int reserve(hipStream_t stream, size_t need) { return reserve(stream, need, need); }
 
 private:
-    T *p_ = nullptr;
+    Handle<void *, hipFree> mem_;
+    size_t cap_ = 0;           // of what mem_ holds (a moved-from buffer keeps the number and holds nothing)
+};
+
+// One hipHostMalloc allocation of `capacity()` bytes.  Grow-only users ask `capacity() < need` before they alloc.
+class PinnedBuffer {
+public:
+    void *get() const { return mem_.get(); }
+    size_t capacity() const { return mem_.get() ? cap_ : 0; }
+    void reset() { mem_.reset(); }
+    // exactly `bytes`; what was held is released first
+    hipError_t alloc(size_t bytes)
+    {
+        cap_ = bytes;
+        return mem_.renew([&](void **p) { return hipHostMalloc(p, bytes, hipHostMallocDefault); });
+    }
+
+private:
+    Handle<void *, hipHostFree> mem_;
     size_t cap_ = 0;
 };
 
@@ -223,24 +270,30 @@ struct PlanEnv {
     uint64_t voices_epoch = 0;        // set by every install_voices: unique in the process, not per context
 };
 
+// what a unit keeps per context: a type private to the unit, made at first use by the unit's one accessor, deleted with
+// the context
+struct CtxPart {
+    virtual ~CtxPart() = default;
+};
+
 struct grail_ctx : PlanEnv {
     int device = 0;
     int device_cus = 256;             // what the device reported (cus: what is planned for)
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_start = nullptr, ev_stop = nullptr;
+    grail::host::Stream stream;       // (before everything that may be queued on it: destroyed last)
+    grail::host::Event ev_start, ev_stop;
     bool have_timing = false;
     uint64_t options_epoch = 0;       // bumped by every grail_set_option (a batch caches its launch plan against both)
     std::vector<grail_voice> voices;  // host copy of the table
-    grail::DevVoice *d_voices = nullptr;
-    float *d_voice_elems = nullptr;   // [n_voices * NUM_VOICED][49]
+    grail::host::DeviceBuffer<grail::DevVoice> d_voices;
+    grail::host::DeviceBuffer<float> d_voice_elems;   // [n_voices * NUM_VOICED][49]
     LaunchStats stats;
-    uint32_t *d_truncated = nullptr;  // [0] truncation flag, [1] slow-path wave-steps, [2] fast wave-tiles, [3] general wave-steps
+    grail::host::DeviceBuffer<uint32_t> d_truncated;  // [0] truncation flag, [1] slow-path wave-steps, [2] fast wave-tiles, [3] general wave-steps
     uint32_t seen_counters[4] = {0, 0, 0, 0};   // d_truncated[1..3] as last read: the device counters only ever grow
-    ncclComm_t comm = nullptr;
+    ncclComm_t comm = nullptr;        // (destroyed through the dlopen table: comm_release)
     uint32_t comm_rank = 0, comm_world = 1;
-    void *host_pipe = nullptr;        // HostPipe: streams, events and buffers of the host-output path
-    void *mix_state = nullptr;        // MixState (mix.cpp): the last mix's plan and the device buffers it was uploaded to
-    void *level_state = nullptr;      // LevelState (levels.cpp): the frame scratch of grail_levels_async, a block's numbers
+    std::unique_ptr<CtxPart> host_pipe;     // HostPipe (host_output.cpp): streams, events and buffers of the host-output path
+    std::unique_ptr<CtxPart> mix_state;     // MixState (mix.cpp): the last mix's plan and the device buffers it was uploaded to
+    std::unique_ptr<CtxPart> level_state;   // LevelState (levels.cpp): the frame scratch of grail_levels_async, a block's numbers
 };
 
 struct grail_stream {
@@ -270,9 +323,8 @@ struct grail_stream {
     // ... on the host side two pinned buffers in turn, each with the event behind its last upload: an append returns as
     // soon as its copies and its scatter kernel are queued, and waits only for the append before last (not for every
     // kernel queued on the stream) before it writes into a buffer again
-    void *h_stage[2] = {nullptr, nullptr};
-    size_t h_stage_cap[2] = {0, 0};
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    grail::host::PinnedBuffer h_stage[2];
+    grail::host::Event ev_stage[2];
     bool stage_busy[2] = {false, false};
     int stage_next = 0;
 };
@@ -425,11 +477,10 @@ void batch_args(const grail_ctx *ctx, const grail_batch *batch, uint32_t row0, S
 int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev, int16_t *out_pcm16_dev, uint64_t out_stride,
                     uint32_t *out_len_dev, uint32_t first = 0, uint32_t count = 0, uint32_t family_rows = 0);
 
-// host_output.cpp / comm.cpp: what grail_destroy releases
-void pipe_destroy_opaque(void *p);
+// comm.cpp: the one thing grail_destroy releases by name
 void comm_release(grail_ctx *ctx);
-void mix_release(grail_ctx *ctx);     // mix.cpp
-void levels_release(grail_ctx *ctx);  // levels.cpp
+// host_output.cpp: grail_batch_free for a call that made the batch itself; returns rc, and grail_last_error() stays rc's
+int drop_batch(grail_ctx *ctx, grail_batch *batch, int rc);
 // levels.cpp, for grail_batch_mix_leveled: the rows of one rendered block measured on ctx's stream and their numbers
 // brought to the host (one wait), then the items' gains by grail_level_gains; gains[n_items], *n_unleveled is added to.
 // sample_rate is read in GRAIL_LEVEL_LOUDNESS only (level_table_rate).  ceiling_db (NULL: none) is

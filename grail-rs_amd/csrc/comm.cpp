@@ -143,25 +143,19 @@ int grail_broadcast_voices(grail_ctx *ctx, uint32_t n_voices, uint32_t root)
     if (ctx->comm_rank == root && ctx->voices.size() != n_voices)
         return fail(GRAIL_ERR_INVALID_ARG, "root's voice table does not hold n_voices voices");
     const size_t bytes = (size_t)n_voices * sizeof(grail_voice);
-    void *d_blob = nullptr;
-    HIP_TRY(hipMalloc(&d_blob, bytes));
+    DeviceBuffer<uint8_t> d_blob;
+    HIP_TRY(d_blob.alloc(bytes));
     hipError_t e = hipSuccess;
     if (ctx->comm_rank == root)
-        e = hipMemcpyAsync(d_blob, ctx->voices.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
-    if (e != hipSuccess) {
-        (void)hipFree(d_blob);
-        return hip_fail(e, "voice blob upload");
-    }
+        e = hipMemcpyAsync(d_blob.get(), ctx->voices.data(), bytes, hipMemcpyHostToDevice, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "voice blob upload");
     // one ncclBroadcast over xGMI: root's HBM -> every rank's HBM
-    ncclResult_t r = rccl().Broadcast(d_blob, d_blob, bytes, ncclUint8, (int)root, ctx->comm, ctx->stream);
-    if (r != ncclSuccess) {
-        (void)hipFree(d_blob);
-        return rccl_fail(r, "ncclBroadcast");
-    }
+    ncclResult_t r = rccl().Broadcast(d_blob.get(), d_blob.get(), bytes, ncclUint8, (int)root, ctx->comm, ctx->stream);
+    if (r != ncclSuccess) return rccl_fail(r, "ncclBroadcast");
     std::vector<grail_voice> got(n_voices);
-    e = hipMemcpyAsync(got.data(), d_blob, bytes, hipMemcpyDeviceToHost, ctx->stream);
+    e = hipMemcpyAsync(got.data(), d_blob.get(), bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_blob);
+    d_blob.reset();              // (before the tables of install_voices are allocated, not at the end of the call)
     if (e != hipSuccess) return hip_fail(e, "voice blob download");
     if (ctx->comm_rank == root) return GRAIL_OK;  // already installed
     return install_voices(ctx, got.data(), n_voices);

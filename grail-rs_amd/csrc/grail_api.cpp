@@ -299,17 +299,9 @@ int install_voices(grail_ctx *ctx, const grail_voice *voices, uint32_t n_voices)
     }
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // kernels may still read the old table
     ctx->voices.clear();                          // a failure below leaves "no voice table set"
-    if (ctx->d_voices) (void)hipFree(ctx->d_voices);
-    if (ctx->d_voice_elems) (void)hipFree(ctx->d_voice_elems);
-    ctx->d_voices = nullptr;
-    ctx->d_voice_elems = nullptr;
-    HIP_TRY(hipMalloc((void **)&ctx->d_voices, dv.size() * sizeof(DevVoice)));
-    HIP_TRY(hipMalloc((void **)&ctx->d_voice_elems, elems.size() * sizeof(float)));
     // on the context's own (non-blocking) stream: ordered with the kernels that read the table
-    HIP_TRY(hipMemcpyAsync(ctx->d_voices, dv.data(), dv.size() * sizeof(DevVoice), hipMemcpyHostToDevice,
-                           ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->d_voice_elems, elems.data(), elems.size() * sizeof(float),
-                           hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(upload(ctx->d_voices, dv.data(), dv.size(), ctx->stream));
+    HIP_TRY(upload(ctx->d_voice_elems, elems.data(), elems.size(), ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));   // dv / elems are locals
     // what the table qualifies for, voice by voice and folded over the table; assigned whole, so that no fact of the
     // table before survives
@@ -353,7 +345,7 @@ int install_voices(grail_ctx *ctx, const grail_voice *voices, uint32_t n_voices)
 int check_ready(grail_ctx *ctx, const grail_batch *batch)
 {
     if (!batch) return fail(GRAIL_ERR_INVALID_ARG, "batch is NULL");
-    if (ctx->voices.empty() || !ctx->d_voices || !ctx->d_voice_elems)   // also after a failed upload
+    if (ctx->voices.empty() || !ctx->d_voices.get() || !ctx->d_voice_elems.get())   // also after a failed upload
         return fail(GRAIL_ERR_NO_VOICES, "call grail_set_voices first");
     if (batch->max_voice_id >= ctx->voices.size())
         return fail(GRAIL_ERR_INVALID_ARG, "a voice id exceeds the voice table");
@@ -422,21 +414,19 @@ int grail_create(int device, grail_ctx **out)
         return fail(GRAIL_ERR_NO_DEVICE, std::string("device ") + std::to_string(device) + " is " + prop.gcnArchName +
                                              ": this library holds gfx950 (MI355X) kernels only");
     if (prop.multiProcessorCount <= 0) return fail(GRAIL_ERR_NO_DEVICE, "the device reports no compute units");
-    grail_ctx *ctx = new (std::nothrow) grail_ctx();
+    std::unique_ptr<grail_ctx> ctx(new (std::nothrow) grail_ctx());
     if (!ctx) return fail(GRAIL_ERR_OUT_OF_MEMORY, "host allocation failed");
     ctx->device = device;
     ctx->cus = ctx->device_cus = prop.multiProcessorCount;
     hipError_t err;
-    if ((err = hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking)) != hipSuccess ||
-        (err = hipEventCreate(&ctx->ev_start)) != hipSuccess ||
-        (err = hipEventCreate(&ctx->ev_stop)) != hipSuccess ||
-        (err = hipMalloc((void **)&ctx->d_truncated, TRUNCATED_WORDS * sizeof(uint32_t))) != hipSuccess ||
-        (err = hipMemsetAsync(ctx->d_truncated, 0, TRUNCATED_WORDS * sizeof(uint32_t), ctx->stream)) != hipSuccess ||
-        (err = hipStreamSynchronize(ctx->stream)) != hipSuccess) {
-        grail_destroy(ctx);
-        return hip_fail(err, "grail_create");
-    }
-    *out = ctx;
+    if ((err = ctx->stream.create()) != hipSuccess ||
+        (err = ctx->ev_start.create(true)) != hipSuccess ||
+        (err = ctx->ev_stop.create(true)) != hipSuccess ||
+        (err = ctx->d_truncated.alloc(TRUNCATED_WORDS)) != hipSuccess ||
+        (err = hipMemsetAsync(ctx->d_truncated.get(), 0, TRUNCATED_WORDS * sizeof(uint32_t), ctx->stream)) != hipSuccess ||
+        (err = hipStreamSynchronize(ctx->stream)) != hipSuccess)
+        return hip_fail(err, "grail_create");       // (what exists so far goes with ctx)
+    *out = ctx.release();
     return GRAIL_OK;
 }
 
@@ -446,15 +436,6 @@ int grail_destroy(grail_ctx *ctx)
     (void)hipSetDevice(ctx->device);
     if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
     comm_release(ctx);
-    pipe_destroy_opaque(ctx->host_pipe);
-    mix_release(ctx);
-    levels_release(ctx);
-    if (ctx->d_voices) (void)hipFree(ctx->d_voices);
-    if (ctx->d_voice_elems) (void)hipFree(ctx->d_voice_elems);
-    if (ctx->d_truncated) (void)hipFree(ctx->d_truncated);
-    if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
-    if (ctx->ev_stop) (void)hipEventDestroy(ctx->ev_stop);
-    if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     delete ctx;
     return GRAIL_OK;
 }
@@ -653,7 +634,7 @@ int grail_batch_lengths(grail_ctx *ctx, const grail_batch *batch, uint32_t max_l
     a.segs = batch->d_segs.get();
     a.seg_offsets = batch->d_offsets.get();
     a.voice_ids = batch->d_voice_ids.get();
-    a.voices = ctx->d_voices;
+    a.voices = ctx->d_voices.get();
     a.out_len = d_len.get();
     a.n_utt = batch->n_utt;
     a.n_voices = (uint32_t)ctx->voices.size();
@@ -671,7 +652,7 @@ int grail_sync(grail_ctx *ctx)
     // flag read-back and reset travel on the stream the kernels run on (a non-blocking stream has
     // no implicit ordering with the null stream)
     uint32_t flags[4] = {0, 0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(flags, ctx->d_truncated, sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(flags, ctx->d_truncated.get(), sizeof flags, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const uint32_t flag = flags[0];
     // the statistics counters are cumulative on the device (u32, wrapping): the host takes differences, so the usual
@@ -681,7 +662,7 @@ int grail_sync(grail_ctx *ctx)
     ctx->stats.general_steps += (uint32_t)(flags[3] - ctx->seen_counters[3]);
     for (int i = 1; i < 4; ++i) ctx->seen_counters[i] = flags[i];
     if (flag) {
-        HIP_TRY(hipMemsetAsync(ctx->d_truncated, 0, sizeof(uint32_t), ctx->stream));
+        HIP_TRY(hipMemsetAsync(ctx->d_truncated.get(), 0, sizeof(uint32_t), ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     if (flag) {

@@ -17,70 +17,42 @@ constexpr size_t PIECE_BYTES = 32u << 20;   // pinned staging granularity
 constexpr int N_PIECES = 12;                // ring size
 constexpr int N_COPIERS = 8;               // memcpy threads for a pageable destination
 
-struct HostPipe {
-    hipStream_t copy_stream = nullptr;
-    hipEvent_t rendered[2] = {nullptr, nullptr};   // block in dev[i] is complete (on ctx->stream)
-    hipEvent_t drained[2] = {nullptr, nullptr};    // dev[i] has been copied out (on copy_stream)
-    hipEvent_t landed[N_PIECES] = {};              // pinned piece i holds its data
-    void *dev[2] = {nullptr, nullptr};
-    size_t dev_bytes = 0;
-    void *pin[N_PIECES] = {};
-    bool have_pins = false;
+struct HostPipe : CtxPart {
+    Stream copy_stream;               // (first: destroyed after everything that may be queued on it)
+    Event rendered[2];                // block in dev[i] is complete (on ctx->stream)
+    Event drained[2];                 // dev[i] has been copied out (on copy_stream)
+    Event landed[N_PIECES];           // pinned piece i holds its data
+    DeviceBuffer<char> dev[2];        // both of one size, in bytes
+    PinnedBuffer pin[N_PIECES];       // PIECE_BYTES each
 };
-
-void pipe_destroy(HostPipe *p)
-{
-    if (!p) return;
-    for (int i = 0; i < 2; ++i) {
-        if (p->dev[i]) (void)hipFree(p->dev[i]);
-        if (p->rendered[i]) (void)hipEventDestroy(p->rendered[i]);
-        if (p->drained[i]) (void)hipEventDestroy(p->drained[i]);
-    }
-    for (int i = 0; i < N_PIECES; ++i) {
-        if (p->pin[i]) (void)hipHostFree(p->pin[i]);
-        if (p->landed[i]) (void)hipEventDestroy(p->landed[i]);
-    }
-    if (p->copy_stream) (void)hipStreamDestroy(p->copy_stream);
-    delete p;
-}
 
 // created on first use and kept in the context: pinned allocations cost tens of milliseconds
 int pipe_get(grail_ctx *ctx, size_t block_bytes, bool need_pins, HostPipe **out)
 {
-    HostPipe *p = (HostPipe *)ctx->host_pipe;
+    HostPipe *p = static_cast<HostPipe *>(ctx->host_pipe.get());
     if (!p) {
         // built in a local and published to the context only when every stream and event exists: a
         // half-built pipe left behind by a failed create would make later calls use null handles
-        p = new (std::nothrow) HostPipe();
-        if (!p) return fail(GRAIL_ERR_OUT_OF_MEMORY, "host allocation failed");
-        hipError_t e = hipStreamCreateWithFlags(&p->copy_stream, hipStreamNonBlocking);
+        std::unique_ptr<HostPipe> fresh(new (std::nothrow) HostPipe());
+        if (!fresh) return fail(GRAIL_ERR_OUT_OF_MEMORY, "host allocation failed");
+        hipError_t e = fresh->copy_stream.create();
         for (int i = 0; i < 2 && e == hipSuccess; ++i) {
-            e = hipEventCreateWithFlags(&p->rendered[i], hipEventDisableTiming);
-            if (e == hipSuccess) e = hipEventCreateWithFlags(&p->drained[i], hipEventDisableTiming);
+            e = fresh->rendered[i].create();
+            if (e == hipSuccess) e = fresh->drained[i].create();
         }
-        for (int i = 0; i < N_PIECES && e == hipSuccess; ++i)
-            e = hipEventCreateWithFlags(&p->landed[i], hipEventDisableTiming);
-        if (e != hipSuccess) {
-            pipe_destroy(p);
-            return hip_fail(e, "host-output pipe");
-        }
-        ctx->host_pipe = p;
+        for (int i = 0; i < N_PIECES && e == hipSuccess; ++i) e = fresh->landed[i].create();
+        if (e != hipSuccess) return hip_fail(e, "host-output pipe");
+        p = fresh.get();
+        ctx->host_pipe = std::move(fresh);
     }
-    if (p->dev_bytes < block_bytes) {
+    if (std::min(p->dev[0].capacity(), p->dev[1].capacity()) < block_bytes) {
         HIP_TRY(hipStreamSynchronize(p->copy_stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (int i = 0; i < 2; ++i) {
-            if (p->dev[i]) (void)hipFree(p->dev[i]);
-            p->dev[i] = nullptr;
-        }
-        p->dev_bytes = 0;
-        for (int i = 0; i < 2; ++i) HIP_TRY(hipMalloc(&p->dev[i], block_bytes));
-        p->dev_bytes = block_bytes;
+        for (auto &d : p->dev) d.reset();            // (both go before either comes back: two blocks may be most of the HBM)
+        for (auto &d : p->dev) HIP_TRY(d.alloc(block_bytes));
     }
-    if (need_pins && !p->have_pins) {
-        for (int i = 0; i < N_PIECES; ++i) HIP_TRY(hipHostMalloc(&p->pin[i], PIECE_BYTES, hipHostMallocDefault));
-        p->have_pins = true;
-    }
+    for (int i = 0; need_pins && i < N_PIECES; ++i)
+        if (!p->pin[i].get()) HIP_TRY(p->pin[i].alloc(PIECE_BYTES));
     *out = p;
     return GRAIL_OK;
 }
@@ -124,7 +96,7 @@ void copier_main(int device, HostPipe *p, CopyRing *r)
             r->jobs.pop_front();
         }
         const hipError_t e = hipEventSynchronize(p->landed[job.piece]);
-        if (e == hipSuccess) std::memcpy(job.dst, p->pin[job.piece], job.bytes);
+        if (e == hipSuccess) std::memcpy(job.dst, p->pin[job.piece].get(), job.bytes);
         {
             std::lock_guard<std::mutex> lk(r->m);
             if (e != hipSuccess && r->error == hipSuccess) r->error = e;
@@ -134,18 +106,13 @@ void copier_main(int device, HostPipe *p, CopyRing *r)
     }
 }
 
-// ELEM = 4: f32 rows, 2: i16 PCM rows
+// the rows into host memory (`out` is not NULL), their lengths into d_len on the device; elem = 4: f32 rows, 2: i16 PCM rows
 int render_to_host(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, void *out, size_t elem, uint64_t out_stride,
-                   uint32_t *out_len)
+                   uint32_t *d_len)
 {
     const size_t row_bytes = (size_t)out_stride * elem;
-    // (copier threads memcpy into `out`: a NULL destination must fail here, not fault there)
-    if (!out && n_utt && out_stride) return fail(GRAIL_ERR_INVALID_ARG, "out is NULL");
-    uint32_t *d_len = nullptr;
     hipError_t e = hipSuccess;
-    if (n_utt) e = hipMalloc((void **)&d_len, (size_t)n_utt * sizeof(uint32_t));
-    if (e != hipSuccess) return hip_fail(e, "out_len allocation");
-    int rc = GRAIL_OK, sync_rc = GRAIL_OK;
+    int rc = GRAIL_OK;
     if (n_utt && row_bytes) {
         // block = up to 4096 rows and 2 GB: big enough for the kernel to outrun PCIe (a 4096-utterance
         // launch renders > 100 GB/s of PCM), small enough for two of them to sit beside the batch
@@ -166,17 +133,17 @@ int render_to_host(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, void *out, si
             const size_t bytes = (size_t)count * row_bytes;
             // the kernel may not overwrite dev[slot] before its previous contents have left
             if (blk >= 2) e = hipStreamWaitEvent(ctx->stream, p->drained[slot], 0);
-            if (e == hipSuccess) e = hipMemsetAsync(p->dev[slot], 0, bytes, ctx->stream);
+            if (e == hipSuccess) e = hipMemsetAsync(p->dev[slot].get(), 0, bytes, ctx->stream);
             if (e != hipSuccess) { rc = hip_fail(e, "block set-up"); break; }
-            rc = synthesize_rows(ctx, b, elem == 4 ? (float *)p->dev[slot] : nullptr,
-                                 elem == 2 ? (int16_t *)p->dev[slot] : nullptr, out_stride, d_len + first,
+            rc = synthesize_rows(ctx, b, elem == 4 ? (float *)p->dev[slot].get() : nullptr,
+                                 elem == 2 ? (int16_t *)p->dev[slot].get() : nullptr, out_stride, d_len + first,
                                  (uint32_t)first, count, rows < n_utt ? (uint32_t)rows : 0u);   // (one block: plan freely)
             if (rc) break;
             e = hipEventRecord(p->rendered[slot], ctx->stream);
             if (e == hipSuccess) e = hipStreamWaitEvent(p->copy_stream, p->rendered[slot], 0);
             char *dst = (char *)out + (size_t)first * row_bytes;
             if (e == hipSuccess && direct) {
-                e = hipMemcpyAsync(dst, p->dev[slot], bytes, hipMemcpyDeviceToHost, p->copy_stream);
+                e = hipMemcpyAsync(dst, p->dev[slot].get(), bytes, hipMemcpyDeviceToHost, p->copy_stream);
             } else if (e == hipSuccess) {
                 for (size_t off = 0; off < bytes && e == hipSuccess; off += PIECE_BYTES) {
                     const size_t n = std::min(PIECE_BYTES, bytes - off);
@@ -189,7 +156,7 @@ int render_to_host(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, void *out, si
                         if (ring.error != hipSuccess) e = ring.error;
                     }
                     if (e == hipSuccess)
-                        e = hipMemcpyAsync(p->pin[piece], (char *)p->dev[slot] + off, n, hipMemcpyDeviceToHost,
+                        e = hipMemcpyAsync(p->pin[piece].get(), p->dev[slot].get() + off, n, hipMemcpyDeviceToHost,
                                            p->copy_stream);
                     if (e == hipSuccess) e = hipEventRecord(p->landed[piece], p->copy_stream);
                     {
@@ -215,17 +182,33 @@ int render_to_host(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, void *out, si
         }
         if (!rc && ring.error != hipSuccess) rc = hip_fail(ring.error, "device-to-host pipeline");
     }
-    if (!rc) {
-        sync_rc = grail_sync(ctx);
-        if (sync_rc != GRAIL_OK && sync_rc != GRAIL_ERR_BUFFER_TOO_SMALL) rc = sync_rc;
+    return rc;
+}
+
+// The one-call forms after their upload, f32 rows (elem = 4) or i16 PCM (2): lengths on the device, the rows rendered —
+// to a host destination through render_to_host's blocks, to a device destination by the one async launch (for PCM the
+// conversion is part of the synthesis kernel's tile flush: 2 B per sample of HBM and PCIe traffic) —, the wait, the
+// lengths brought back.  A row that did not end within out_stride is the soft status: everything else still happens.
+int run_one_call(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, void *out, size_t elem, uint64_t out_stride,
+                 uint32_t *out_len, uint32_t flags)
+{
+    const bool to_host = !(flags & GRAIL_OUT_DEVICE);
+    // (copier threads memcpy into `out`: a NULL destination must fail here, not fault there)
+    if (to_host && !out && n_utt && out_stride) return fail(GRAIL_ERR_INVALID_ARG, "out is NULL");
+    DeviceBuffer<uint32_t> d_len;
+    if (n_utt) HIP_TRY(d_len.alloc(n_utt));
+    int rc;
+    if (to_host) rc = render_to_host(ctx, b, n_utt, out, elem, out_stride, d_len.get());
+    else if (elem == 4) rc = grail_batch_synthesize_async(ctx, b, (float *)out, out_stride, d_len.get());
+    else rc = grail_batch_synthesize_pcm16_async(ctx, b, (int16_t *)out, out_stride, d_len.get());
+    if (rc) return rc;
+    const int sync_rc = grail_sync(ctx);
+    if (sync_rc != GRAIL_OK && sync_rc != GRAIL_ERR_BUFFER_TOO_SMALL) return sync_rc;
+    if (out_len && n_utt) {
+        HIP_TRY(hipMemcpyAsync(out_len, d_len.get(), (size_t)n_utt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
-    if (!rc && out_len && n_utt) {
-        e = hipMemcpyAsync(out_len, d_len, (size_t)n_utt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "out_len copy");
-    }
-    if (d_len) (void)hipFree(d_len);
-    return rc ? rc : sync_rc;
+    return sync_rc;
 }
 
 }  // namespace
@@ -233,7 +216,13 @@ int render_to_host(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, void *out, si
 namespace grail {
 namespace host {
 
-void pipe_destroy_opaque(void *p) { pipe_destroy((HostPipe *)p); }
+int drop_batch(grail_ctx *ctx, grail_batch *batch, int rc)
+{
+    const std::string keep = last_error();
+    grail_batch_free(ctx, batch);
+    last_error() = keep;
+    return rc;
+}
 
 // the front of examples/cli.rs:176-179 for n texts: transcribe + intonate with the voice each text names
 int say_segments(const std::vector<grail_voice> &voices, const char *const *texts_utf8, uint32_t n_texts,
@@ -263,43 +252,14 @@ int say_segments(const std::vector<grail_voice> &voices, const char *const *text
 
 extern "C" {
 
-static int run_one_call(grail_ctx *ctx, grail_batch *b, uint32_t n_utt, float *out,
-                        uint64_t out_stride, uint32_t *out_len, uint32_t flags)
-{
-    if (!(flags & GRAIL_OUT_DEVICE)) return render_to_host(ctx, b, n_utt, out, sizeof(float), out_stride, out_len);
-    int rc = GRAIL_OK;
-    uint32_t *d_len = nullptr;
-    hipError_t e = hipSuccess;
-    if (n_utt) e = hipMalloc((void **)&d_len, (size_t)n_utt * sizeof(uint32_t));
-    if (e != hipSuccess) rc = hip_fail(e, "output allocation");
-    if (!rc) rc = grail_batch_synthesize_async(ctx, b, out, out_stride, d_len);
-    int sync_rc = GRAIL_OK;
-    if (!rc) {
-        sync_rc = grail_sync(ctx);
-        if (sync_rc != GRAIL_OK && sync_rc != GRAIL_ERR_BUFFER_TOO_SMALL) rc = sync_rc;
-    }
-    if (!rc && out_len && n_utt) {
-        e = hipMemcpyAsync(out_len, d_len, (size_t)n_utt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-        if (e != hipSuccess) rc = hip_fail(e, "out_len copy");
-    }
-    if (d_len) (void)hipFree(d_len);
-    return rc ? rc : sync_rc;
-}
-
 int grail_synthesize_batch(grail_ctx *ctx, const grail_phoneme_elem *segs,
                            const uint32_t *seg_offsets, const uint32_t *voice_ids,
                            const uint32_t *jitter_seeds, uint32_t n_utt, float *out,
                            uint64_t out_stride, uint32_t *out_len, uint32_t flags)
 {
     grail_batch *b = nullptr;
-    int rc = grail_batch_upload(ctx, segs, seg_offsets, voice_ids, jitter_seeds, n_utt, &b);
-    if (rc) return rc;
-    rc = run_one_call(ctx, b, n_utt, out, out_stride, out_len, flags);
-    const std::string keep = last_error();
-    grail_batch_free(ctx, b);
-    last_error() = keep;
-    return rc;
+    const int rc = grail_batch_upload(ctx, segs, seg_offsets, voice_ids, jitter_seeds, n_utt, &b);
+    return rc ? rc : drop_batch(ctx, b, run_one_call(ctx, b, n_utt, out, sizeof(float), out_stride, out_len, flags));
 }
 
 int grail_synthesize_batch_elems(grail_ctx *ctx, const grail_sequence_elem *segs,
@@ -308,13 +268,8 @@ int grail_synthesize_batch_elems(grail_ctx *ctx, const grail_sequence_elem *segs
                                  uint64_t out_stride, uint32_t *out_len, uint32_t flags)
 {
     grail_batch *b = nullptr;
-    int rc = grail_batch_upload_elems(ctx, segs, seg_offsets, voice_ids, jitter_seeds, n_utt, &b);
-    if (rc) return rc;
-    rc = run_one_call(ctx, b, n_utt, out, out_stride, out_len, flags);
-    const std::string keep = last_error();
-    grail_batch_free(ctx, b);
-    last_error() = keep;
-    return rc;
+    const int rc = grail_batch_upload_elems(ctx, segs, seg_offsets, voice_ids, jitter_seeds, n_utt, &b);
+    return rc ? rc : drop_batch(ctx, b, run_one_call(ctx, b, n_utt, out, sizeof(float), out_stride, out_len, flags));
 }
 
 int grail_synthesize_batch_pcm16(grail_ctx *ctx, const grail_phoneme_elem *segs,
@@ -323,33 +278,8 @@ int grail_synthesize_batch_pcm16(grail_ctx *ctx, const grail_phoneme_elem *segs,
                                  uint64_t out_stride, uint32_t *out_len, uint32_t flags)
 {
     grail_batch *b = nullptr;
-    int rc = grail_batch_upload(ctx, segs, seg_offsets, voice_ids, jitter_seeds, n_utt, &b);
-    if (rc) return rc;
-    int sync_rc = GRAIL_OK;
-    // the conversion is part of the synthesis kernel's tile flush: 2 B per sample of HBM and PCIe traffic
-    if (!(flags & GRAIL_OUT_DEVICE)) {
-        rc = render_to_host(ctx, b, n_utt, out, sizeof(int16_t), out_stride, out_len);
-    } else {
-        uint32_t *d_len = nullptr;
-        hipError_t e = hipSuccess;
-        if (n_utt) e = hipMalloc((void **)&d_len, (size_t)n_utt * sizeof(uint32_t));
-        if (e != hipSuccess) rc = hip_fail(e, "pcm16 output allocation");
-        if (!rc) rc = grail_batch_synthesize_pcm16_async(ctx, b, out, out_stride, d_len);
-        if (!rc) {
-            sync_rc = grail_sync(ctx);
-            if (sync_rc != GRAIL_OK && sync_rc != GRAIL_ERR_BUFFER_TOO_SMALL) rc = sync_rc;
-        }
-        if (!rc && out_len && n_utt) {
-            e = hipMemcpyAsync(out_len, d_len, (size_t)n_utt * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = hip_fail(e, "out_len copy");
-        }
-        if (d_len) (void)hipFree(d_len);
-    }
-    const std::string keep = last_error();
-    grail_batch_free(ctx, b);
-    last_error() = keep;
-    return rc ? rc : sync_rc;
+    const int rc = grail_batch_upload(ctx, segs, seg_offsets, voice_ids, jitter_seeds, n_utt, &b);
+    return rc ? rc : drop_batch(ctx, b, run_one_call(ctx, b, n_utt, out, sizeof(int16_t), out_stride, out_len, flags));
 }
 
 int grail_say_batch(grail_ctx *ctx, const char *const *texts_utf8, uint32_t n_texts,

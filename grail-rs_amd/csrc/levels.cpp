@@ -13,7 +13,7 @@ using namespace grail::host;
 // hop of 100 ms), the chunk maxima and counts that a true-peak call folds (12 B per chunk of 4096 output times) with one
 // block's true peaks for the limited mix, the chunk numbers that a limiter call folds (16 B per group and chunk of 4096
 // samples), and the hops' non-finite counts that a segmented loudness call folds (4 B per hop).
-struct LevelState {
+struct LevelState : CtxPart {
     DeviceBuffer<double> d_fsum;            // frames: sums of squares,
     DeviceBuffer<float> d_fpeak;            // ... peaks
     DeviceBuffer<uint32_t> d_fbad;          // ... and non-finite counts
@@ -27,18 +27,6 @@ struct LevelState {
     DeviceBuffer<unsigned char> d_lstat;    // limiter chunks
     DeviceBuffer<uint32_t> d_hbad;          // segmented loudness: non-finite counts per hop
 };
-
-namespace grail {
-namespace host {
-
-void levels_release(grail_ctx *ctx)
-{
-    delete (LevelState *)ctx->level_state;
-    ctx->level_state = nullptr;
-}
-
-}  // namespace host
-}  // namespace grail
 
 namespace {
 
@@ -73,8 +61,8 @@ int check_rows(const char *who, const Rows &r, bool any_output, bool *measure)
 
 LevelState *state(grail_ctx *ctx)
 {
-    if (!ctx->level_state) ctx->level_state = new (std::nothrow) LevelState();
-    return (LevelState *)ctx->level_state;
+    if (!ctx->level_state) ctx->level_state.reset(new (std::nothrow) LevelState());
+    return static_cast<LevelState *>(ctx->level_state.get());
 }
 
 uint64_t ceil_div(uint64_t a, uint64_t b) { return a / b + (a % b != 0); }

@@ -13,32 +13,24 @@ using namespace grail::host;
 // render, and varies from call to call).  The plan's buffers grow by a quarter more than asked for, so that slowly growing
 // plans do not reallocate every call; the block's to the exact size.  The host vectors of the plan are rebuilt only once
 // the upload from them has completed.
-struct MixState {
+struct MixState : CtxPart {
     mix::Plan plan;
     DeviceBuffer<mix::MixItem> d_items;
     DeviceBuffer<uint32_t> d_tile_start, d_tile_items;
     DeviceBuffer<float> d_rows;       // grail_batch_mix: rows of one block
     DeviceBuffer<uint32_t> d_len;     // ... and their lengths
-    hipEvent_t uploaded = nullptr;
+    Event uploaded;
     bool pending = false;
 };
 
-namespace grail {
-namespace host {
-
-void mix_release(grail_ctx *ctx)
-{
-    MixState *st = (MixState *)ctx->mix_state;
-    if (!st) return;
-    if (st->uploaded) (void)hipEventDestroy(st->uploaded);
-    delete st;
-    ctx->mix_state = nullptr;
-}
-
-}  // namespace host
-}  // namespace grail
-
 namespace {
+
+// the context's, made at first use (nullptr: no host memory)
+MixState *state(grail_ctx *ctx)
+{
+    if (!ctx->mix_state) ctx->mix_state.reset(new (std::nothrow) MixState());
+    return static_cast<MixState *>(ctx->mix_state.get());
+}
 
 size_t quarter_more(size_t n) { return n + n / 4; }
 
@@ -51,10 +43,9 @@ int mix_rows(grail_ctx *ctx, const char *who, const float *rows_dev, uint64_t ro
     if (flags & ~GRAIL_MIX_ACCUMULATE) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": unknown flags");
     if (n_items && !rows_dev) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": rows_dev is NULL");
     if (n_tracks && !tracks_dev) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": tracks_dev is NULL");
-    if (!ctx->mix_state) ctx->mix_state = new (std::nothrow) MixState();
-    MixState *st = (MixState *)ctx->mix_state;
+    MixState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "mix state");
-    if (!st->uploaded) HIP_TRY(hipEventCreateWithFlags(&st->uploaded, hipEventDisableTiming));
+    if (!st->uploaded) HIP_TRY(st->uploaded.create());
     if (st->pending) {
         HIP_TRY(hipEventSynchronize(st->uploaded));
         st->pending = false;
@@ -142,8 +133,7 @@ int batch_mix(grail_ctx *ctx, const char *who, const grail_batch *batch, const u
     if ((rc = grail_batch_lengths(ctx, batch, 0xFFFFFFFFu, lens.data()))) return rc;
     const uint64_t longest = *std::max_element(lens.begin(), lens.end());
     const uint64_t stride = std::max<uint64_t>(64, (longest + 63) / 64 * 64);
-    if (!ctx->mix_state) ctx->mix_state = new (std::nothrow) MixState();
-    MixState *st = (MixState *)ctx->mix_state;
+    MixState *st = state(ctx);
     if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "mix state");
     // the block rule of the header: 2 x 256 x CUs rows, as many as half of the free HBM holds (the context's scratch from an
     // earlier call counts as free: it is this call's to reuse)

@@ -153,6 +153,36 @@ int check_node(grail_node *node, uint32_t flags)
     return GRAIL_OK;
 }
 
+// The one-call forms over the node: slot i runs `call` (a one-context form) on its shard, into dest(i, shard).  The host
+// forms pass the caller's flags and a slice of the caller's buffer; per_slot: one device buffer per slot, GRAIL_OUT_DEVICE.
+template <typename Seg, typename Call, typename Dest>
+int node_one_call(grail_node *node, bool per_slot, Call call, const Seg *segs, const uint32_t *seg_offsets,
+                  const uint32_t *voice_ids, const uint32_t *jitter_seeds, uint32_t n_utt, Dest dest, uint64_t out_stride,
+                  uint32_t *out_len, uint32_t flags)
+{
+    int rc = check_node(node, per_slot ? 0u : flags);
+    if (rc) return rc;
+    std::vector<ShardView> v;
+    std::vector<uint8_t> skip;
+    if ((rc = shard_views(node, seg_offsets, n_utt, v, skip))) return rc;
+    for (uint32_t i = 0; per_slot && i < v.size(); ++i)
+        if (!skip[i] && !dest(i, v[i].s) && out_stride)
+            return fail(GRAIL_ERR_INVALID_ARG, "out_dev[" + std::to_string(i) + "] is NULL and the slot has rows to render");
+    return run_all(node, [&](uint32_t i) {
+        const grail_node_shard &s = v[i].s;
+        return call(node->ctxs[i], segs ? segs + s.first_seg : nullptr, v[i].offs.data(),
+                    voice_ids ? voice_ids + s.first_row : nullptr, jitter_seeds ? jitter_seeds + s.first_row : nullptr,
+                    (uint32_t)s.rows, dest(i, s), out_stride, out_len ? out_len + s.first_row : nullptr, flags);
+    }, &skip);
+}
+
+// (the host forms' destination: the shard's rows of the caller's buffer)
+template <typename T>
+auto rows_of(T *out, uint64_t out_stride)
+{
+    return [=](uint32_t, const grail_node_shard &s) { return out ? out + s.first_row * out_stride : nullptr; };
+}
+
 }  // namespace
 
 extern "C" {
@@ -294,57 +324,24 @@ int grail_node_synthesize_batch(grail_node *node, const grail_phoneme_elem *segs
                                 const uint32_t *voice_ids, const uint32_t *jitter_seeds, uint32_t n_utt, float *out,
                                 uint64_t out_stride, uint32_t *out_len, uint32_t flags)
 {
-    int rc = check_node(node, flags);
-    if (rc) return rc;
-    std::vector<ShardView> v;
-    std::vector<uint8_t> skip;
-    if ((rc = shard_views(node, seg_offsets, n_utt, v, skip))) return rc;
-    return run_all(node, [&](uint32_t i) {
-        const grail_node_shard &s = v[i].s;
-        return grail_synthesize_batch(node->ctxs[i], segs ? segs + s.first_seg : nullptr, v[i].offs.data(),
-                                      voice_ids ? voice_ids + s.first_row : nullptr,
-                                      jitter_seeds ? jitter_seeds + s.first_row : nullptr, (uint32_t)s.rows,
-                                      out ? out + s.first_row * out_stride : nullptr, out_stride,
-                                      out_len ? out_len + s.first_row : nullptr, flags);
-    }, &skip);
+    return node_one_call(node, false, grail_synthesize_batch, segs, seg_offsets, voice_ids, jitter_seeds, n_utt,
+                         rows_of(out, out_stride), out_stride, out_len, flags);
 }
 
 int grail_node_synthesize_batch_elems(grail_node *node, const grail_sequence_elem *segs, const uint32_t *seg_offsets,
                                       const uint32_t *voice_ids, const uint32_t *jitter_seeds, uint32_t n_utt,
                                       float *out, uint64_t out_stride, uint32_t *out_len, uint32_t flags)
 {
-    int rc = check_node(node, flags);
-    if (rc) return rc;
-    std::vector<ShardView> v;
-    std::vector<uint8_t> skip;
-    if ((rc = shard_views(node, seg_offsets, n_utt, v, skip))) return rc;
-    return run_all(node, [&](uint32_t i) {
-        const grail_node_shard &s = v[i].s;
-        return grail_synthesize_batch_elems(node->ctxs[i], segs ? segs + s.first_seg : nullptr, v[i].offs.data(),
-                                            voice_ids ? voice_ids + s.first_row : nullptr,
-                                            jitter_seeds ? jitter_seeds + s.first_row : nullptr, (uint32_t)s.rows,
-                                            out ? out + s.first_row * out_stride : nullptr, out_stride,
-                                            out_len ? out_len + s.first_row : nullptr, flags);
-    }, &skip);
+    return node_one_call(node, false, grail_synthesize_batch_elems, segs, seg_offsets, voice_ids, jitter_seeds, n_utt,
+                         rows_of(out, out_stride), out_stride, out_len, flags);
 }
 
 int grail_node_synthesize_batch_pcm16(grail_node *node, const grail_phoneme_elem *segs, const uint32_t *seg_offsets,
                                       const uint32_t *voice_ids, const uint32_t *jitter_seeds, uint32_t n_utt,
                                       int16_t *out, uint64_t out_stride, uint32_t *out_len, uint32_t flags)
 {
-    int rc = check_node(node, flags);
-    if (rc) return rc;
-    std::vector<ShardView> v;
-    std::vector<uint8_t> skip;
-    if ((rc = shard_views(node, seg_offsets, n_utt, v, skip))) return rc;
-    return run_all(node, [&](uint32_t i) {
-        const grail_node_shard &s = v[i].s;
-        return grail_synthesize_batch_pcm16(node->ctxs[i], segs ? segs + s.first_seg : nullptr, v[i].offs.data(),
-                                            voice_ids ? voice_ids + s.first_row : nullptr,
-                                            jitter_seeds ? jitter_seeds + s.first_row : nullptr, (uint32_t)s.rows,
-                                            out ? out + s.first_row * out_stride : nullptr, out_stride,
-                                            out_len ? out_len + s.first_row : nullptr, flags);
-    }, &skip);
+    return node_one_call(node, false, grail_synthesize_batch_pcm16, segs, seg_offsets, voice_ids, jitter_seeds, n_utt,
+                         rows_of(out, out_stride), out_stride, out_len, flags);
 }
 
 int grail_node_synthesize_batch_device(grail_node *node, const grail_phoneme_elem *segs, const uint32_t *seg_offsets,
@@ -353,20 +350,9 @@ int grail_node_synthesize_batch_device(grail_node *node, const grail_phoneme_ele
 {
     if (!node) return fail(GRAIL_ERR_INVALID_ARG, "node is NULL");
     if (!out_dev) return fail(GRAIL_ERR_INVALID_ARG, "out_dev is NULL");
-    std::vector<ShardView> v;
-    std::vector<uint8_t> skip;
-    int rc = shard_views(node, seg_offsets, n_utt, v, skip);
-    if (rc) return rc;
-    for (size_t i = 0; i < v.size(); ++i)
-        if (!skip[i] && !out_dev[i] && out_stride)
-            return fail(GRAIL_ERR_INVALID_ARG, "out_dev[" + std::to_string(i) + "] is NULL and the slot has rows to render");
-    return run_all(node, [&](uint32_t i) {
-        const grail_node_shard &s = v[i].s;
-        return grail_synthesize_batch(node->ctxs[i], segs ? segs + s.first_seg : nullptr, v[i].offs.data(),
-                                      voice_ids ? voice_ids + s.first_row : nullptr,
-                                      jitter_seeds ? jitter_seeds + s.first_row : nullptr, (uint32_t)s.rows, out_dev[i],
-                                      out_stride, out_len ? out_len + s.first_row : nullptr, GRAIL_OUT_DEVICE);
-    }, &skip);
+    return node_one_call(node, true, grail_synthesize_batch, segs, seg_offsets, voice_ids, jitter_seeds, n_utt,
+                         [&](uint32_t i, const grail_node_shard &) { return out_dev[i]; }, out_stride, out_len,
+                         GRAIL_OUT_DEVICE);
 }
 
 int grail_node_say_batch(grail_node *node, const char *const *texts_utf8, uint32_t n_texts, const uint32_t *voice_ids,
@@ -398,11 +384,7 @@ int grail_node_lengths(grail_node *node, const grail_phoneme_elem *segs, const u
         int r = grail_batch_upload(node->ctxs[i], segs ? segs + s.first_seg : nullptr, v[i].offs.data(),
                                    voice_ids ? voice_ids + s.first_row : nullptr, nullptr, (uint32_t)s.rows, &b);
         if (r) return r;
-        r = grail_batch_lengths(node->ctxs[i], b, max_len, out_len + s.first_row);
-        const std::string keep = last_error();
-        grail_batch_free(node->ctxs[i], b);
-        last_error() = keep;
-        return r;
+        return drop_batch(node->ctxs[i], b, grail_batch_lengths(node->ctxs[i], b, max_len, out_len + s.first_row));
     }, &skip);
 }
 

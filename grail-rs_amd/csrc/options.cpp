@@ -139,7 +139,7 @@ int grail_get_option(grail_ctx *ctx, const char *name, int64_t *value)
         if (k < 0 || k >= 32) return fail(GRAIL_ERR_INVALID_ARG, "debug_prof_<k>: k in 0 .. 31");
         unsigned long long v = 0;
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        HIP_TRY(hipMemcpy(&v, reinterpret_cast<unsigned long long *>(ctx->d_truncated + 8) + k, sizeof v, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&v, reinterpret_cast<unsigned long long *>(ctx->d_truncated.get() + 8) + k, sizeof v, hipMemcpyDeviceToHost));
         *value = (int64_t)v;
         return GRAIL_OK;
     }

@@ -128,11 +128,7 @@ int grail_stream_close(grail_ctx *ctx, grail_stream *stream)
     int rc = bind(ctx);
     if (rc) return rc;
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int i = 0; i < 2; ++i) {
-        if (stream->h_stage[i]) (void)hipHostFree(stream->h_stage[i]);
-        if (stream->ev_stage[i]) (void)hipEventDestroy(stream->ev_stage[i]);
-    }
-    delete stream;          // (its device buffers go with it, and the batch a live stream owns)
+    delete stream;          // (its buffers and events go with it, and the batch a live stream owns)
     return GRAIL_OK;
 }
 
@@ -149,7 +145,7 @@ int grail_stream_open_live(grail_ctx *ctx, uint32_t n_utt, const uint32_t *voice
     if (ring_segments < 4 || (ring_segments & (ring_segments - 1)) != 0 || ring_segments > 65536)
         return fail(GRAIL_ERR_INVALID_ARG, "ring_segments must be a power of two, 4 .. 65536 (0: 64)");
     if ((uint64_t)n_utt * ring_segments > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "n_utt x ring_segments exceeds 2^31");
-    if (ctx->voices.empty() || !ctx->d_voices) return fail(GRAIL_ERR_NO_VOICES, "call grail_set_voices first");
+    if (ctx->voices.empty() || !ctx->d_voices.get()) return fail(GRAIL_ERR_NO_VOICES, "call grail_set_voices first");
     grail_batch *b = new (std::nothrow) grail_batch();
     grail_stream *s = new (std::nothrow) grail_stream();
     if (!b || !s) {
@@ -259,17 +255,12 @@ static int live_append(grail_ctx *ctx, grail_stream *s, const std::vector<DevSeg
         HIP_TRY(hipEventSynchronize(s->ev_stage[slot]));          // the append before last has left this buffer
         s->stage_busy[slot] = false;
     }
-    if (s->h_stage_cap[slot] < b_segs + b_offs + b_elems) {
-        if (s->h_stage[slot]) (void)hipHostFree(s->h_stage[slot]);
-        s->h_stage[slot] = nullptr;
-        s->h_stage_cap[slot] = 0;
-        const size_t want = 2 * (b_segs + b_offs + b_elems);
-        e = hipHostMalloc(&s->h_stage[slot], want, hipHostMallocDefault);
+    if (s->h_stage[slot].capacity() < b_segs + b_offs + b_elems) {
+        e = s->h_stage[slot].alloc(2 * (b_segs + b_offs + b_elems));
         if (e != hipSuccess) return hip_fail(e, "grail_stream_append pinned staging");
-        s->h_stage_cap[slot] = want;
     }
-    if (!s->ev_stage[slot]) HIP_TRY(hipEventCreateWithFlags(&s->ev_stage[slot], hipEventDisableTiming));
-    char *h = static_cast<char *>(s->h_stage[slot]);
+    if (!s->ev_stage[slot]) HIP_TRY(s->ev_stage[slot].create());
+    char *h = static_cast<char *>(s->h_stage[slot].get());
     std::memcpy(h, segs.data(), b_segs);
     std::memcpy(h + b_segs, seg_offsets, b_offs);
     if (elems) std::memcpy(h + b_segs + b_offs, elems, b_elems);

@@ -21,9 +21,9 @@ void batch_args(const grail_ctx *ctx, const grail_batch *batch, uint32_t row0, S
     a.seg_offsets = batch->d_offsets.get() + row0;       // the offsets themselves are absolute into segs
     a.voice_ids = batch->d_voice_ids.get() ? batch->d_voice_ids.get() + row0 : nullptr;
     a.seeds = batch->d_seeds.get() ? batch->d_seeds.get() + row0 : nullptr;
-    a.elems = batch->phoneme_mode ? ctx->d_voice_elems : batch->d_elems.get();
-    a.voices = ctx->d_voices;
-    a.truncated = ctx->d_truncated;
+    a.elems = batch->phoneme_mode ? ctx->d_voice_elems.get() : batch->d_elems.get();
+    a.voices = ctx->d_voices.get();
+    a.truncated = ctx->d_truncated.get();
     a.n_voices = (uint32_t)ctx->voices.size();
     a.phoneme_mode = batch->phoneme_mode ? 1u : 0u;
     a.skip_silent = ctx->opt.skip_silent_option ? 1u : 0u;

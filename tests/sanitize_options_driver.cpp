@@ -1,7 +1,9 @@
 // sanitize_options_driver.cpp — grail_set_option / grail_get_option under AddressSanitizer + UBSan, and their transcript.
 // Built by tests/test_sanitizers.py from grail-rs_amd/csrc/{options,voice_analysis,voice_host,launch_plan}.cpp with g++
 // (those units make no HIP call); the error helpers of grail_api.cpp are defined here.  Neither entry point needs a
-// device: a default-constructed grail_ctx that plans for 256 compute units suffices (as grail_plan_blocks has one).
+// device: a default-constructed grail_ctx that plans for 256 compute units suffices (as grail_plan_blocks has one).  The
+// context owns its HIP resources by type, so its destructor names HIP entry points: tests/fake_hip.h defines them, and
+// the driver checks that the context called none of them from construction to destruction.
 // argv: the option names to walk (the test passes the names of the header's option block, in the header's order).  Every
 // name, then a few the header does not list, is set to each probe value and read back; the return codes, the message of
 // a failure, the value read and the context's options_epoch go to stdout, then every name is read once more.  What the
@@ -9,6 +11,7 @@
 #include <cinttypes>
 
 #include "../grail-rs_amd/csrc/api_internal.hpp"
+#include "fake_hip.h"
 
 // ---- the error helpers of grail_api.cpp
 namespace grail {
@@ -37,7 +40,7 @@ static void read_back(grail_ctx *ctx, const char *name)
     if (rc) std::printf(" \"%s\"", grail_last_error());
 }
 
-int main(int argc, char **argv)
+static void walk_options(int argc, char **argv)
 {
     grail_ctx ctx;
     ctx.cus = ctx.device_cus = 256;
@@ -69,6 +72,15 @@ int main(int argc, char **argv)
         std::printf("  %s: ", name);
         read_back(&ctx, name);
         std::printf("\n");
+    }
+}
+
+int main(int argc, char **argv)
+{
+    walk_options(argc, argv);
+    if (!fake_hip::state().log.empty()) {
+        std::fprintf(stderr, "a grail_ctx that was given no HIP resource made HIP calls: %s\n", fake_hip::names_since(0).c_str());
+        return 1;
     }
     std::printf("sanitize options driver: ok\n");
     return 0;

@@ -85,3 +85,20 @@ def test_options_under_asan_ubsan_repeat_the_recorded_transcript(tmp_path):
     recorded = open(os.path.join(ROOT, "tests", "golden", "options_transcript.txt")).read()
     assert len(names) == 39 and recorded.count("\n[") == len(names) + 6
     assert r.stdout == recorded
+
+
+@pytest.mark.timeout(300)
+def test_resource_owners_under_asan_ubsan(tmp_path):
+    """The owner types of api_internal.hpp (Event, Stream, DeviceBuffer, PinnedBuffer) and the structs that hold them,
+    built with g++ and the sanitizers and linked against tests/fake_hip.h instead of the HIP runtime
+    (tests/sanitize_owners_driver.cpp): what each owner calls and in which order, what a failed allocation leaves, that a
+    context's stream is destroyed last, and that nothing is live or leaked at exit."""
+    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
+           "-ffp-contract=off", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+    exe = str(tmp_path / "sanitize_owners_driver")
+    subprocess.check_call(["g++", *san, os.path.join(ROOT, "tests", "sanitize_owners_driver.cpp"), "-o", exe, "-lm"])
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1")
+    r = subprocess.run([exe], capture_output=True, text=True, env=env, timeout=250)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "sanitize owners driver: ok" in r.stdout
+    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr and "LeakSanitizer" not in r.stderr
