@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--report] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--rate R] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -10,7 +10,10 @@
 // --limit (with --ceiling) then passes the two finished tracks, as one linked pair, through the look-ahead limiter
 // (grail::Gpu::limit) with the largest power of two of samples within 5 ms as look-ahead, and prints the tracks' true
 // peaks before and after: what placements that overlap, or the mix's own rounding, left above the ceiling gives way there.
-// --report measures the two finished tracks, after the last stage that ran, as a meter would (grail::Gpu::track_loudness,
+// --rate R resamples the two finished tracks, after the mix and the limiter, from the voices' 44 100 Hz to R Hz on the device
+// (grail::Gpu::resample) and writes the WAV at R; the filter overshoots a little, so the line it prints has the tracks'
+// true peaks at R.
+// --report measures the two finished tracks, after the last stage that ran and at the rate of what is written, as a meter would (grail::Gpu::track_loudness,
 // parallel in time, and grail::Gpu::true_peak) and prints one line per track: integrated loudness, loudness range, largest
 // momentary and short-term loudness, true peak; "-" where a track is too short (or too quiet) for a number.
 #include <cmath>
@@ -30,6 +33,8 @@ int main(int argc, char **argv)
     bool leveled = false, bad_level = false, lufs = false;
     bool capped = false, bad_ceiling = false, limit = false, report = false, bad_report = false;
     float level_db = 0.0f, ceiling_db = 0.0f;
+    bool resampled = false, bad_rate = false;
+    uint32_t rate = 0;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
         else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
@@ -43,6 +48,12 @@ int main(int argc, char **argv)
             ceiling_db = std::strtof(argv[++i], &rest);
             capped = true;
             bad_ceiling = rest == argv[i] || *rest || !std::isfinite(ceiling_db);
+        } else if (!std::strcmp(argv[i], "--rate") && i + 1 < argc) {
+            char *rest = nullptr;
+            const unsigned long long r = std::strtoull(argv[++i], &rest, 10);
+            resampled = true;
+            rate = (uint32_t)r;
+            bad_rate = rest == argv[i] || *rest || argv[i][0] == '-' || r == 0 || r > 0xFFFFFFFFull;
         } else if (!std::strcmp(argv[i], "--limit")) limit = true;
         else if (!std::strcmp(argv[i], "--report")) {
             bad_report = report;        // (named twice)
@@ -50,10 +61,10 @@ int main(int argc, char **argv)
         } else if (!std::strncmp(argv[i], "--report", 8)) bad_report = true;        // (it takes no value)
         else lines.push_back(argv[i]);
     }
-    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || (capped && !leveled) || (limit && !capped)) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--report] "
+    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || (capped && !leveled) || (limit && !capped)) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--rate R] [--report] "
                              "\"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit needs --ceiling, "
-                             "--report takes no value)\n");
+                             "--rate takes a whole number of Hz, --report takes no value)\n");
         return 2;
     }
     try {
@@ -105,8 +116,16 @@ int main(int argc, char **argv)
         } else {
             tracks = gpu.mix(utts, placements, 2, end);
         }
+        uint32_t out_rate = (uint32_t)first.sample_rate;
+        if (resampled && rate != out_rate) {    // (the voices' own rate: nothing to do, and the library refuses equal rates)
+            tracks = gpu.resample(tracks, out_rate, rate);
+            const grail::TruePeak tp = gpu.true_peak(tracks);
+            std::printf("Resampled from %u to %u Hz: %zu samples a track; track true peaks %.6f and %.6f dBTP\n", out_rate, rate,
+                        tracks[0].size(), tp.db(0), tp.db(1));
+            out_rate = rate;
+        }
         if (report) {           // the finished tracks as a meter reads them; "-" where there is no number
-            const grail::TrackLoudness loud = gpu.track_loudness(tracks, (uint32_t)first.sample_rate);
+            const grail::TrackLoudness loud = gpu.track_loudness(tracks, out_rate);
             const grail::TruePeak peak = gpu.true_peak(tracks);
             const auto field = [](bool has, double value, const char *unit) {
                 char text[48];
@@ -127,7 +146,7 @@ int main(int argc, char **argv)
         std::printf("%.2f seconds of stereo audio: \"%s\" (left), \"%s\" (right)\n", end / first.sample_rate,
                     lines[0].c_str(), lines[1].c_str());
         std::printf("Writing the dialogue to %s\n", out_path.c_str());
-        gpu.save_wav_frames(out_path, tracks, (uint32_t)first.sample_rate);
+        gpu.save_wav_frames(out_path, tracks, out_rate);
     } catch (const grail::Error &e) {
         std::fprintf(stderr, "grail_dialogue: %s (status %d)\n", e.what(), e.status);
         return 1;

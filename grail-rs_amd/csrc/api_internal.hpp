@@ -2,7 +2,7 @@
 // units include kernels.h, never this).  grail_api.cpp: contexts, batches, voices; options.cpp: the option table,
 // grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
 // families, cost model, block planner; synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
-// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak) and limited; host_output.cpp: the one-call
+// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak), limited and resampled; host_output.cpp: the one-call
 // forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Every HIP resource these units
 // create has one owner type (below): Event, Stream, DeviceBuffer, PinnedBuffer.
 #pragma once

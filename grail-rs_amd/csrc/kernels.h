@@ -219,4 +219,18 @@ hipError_t launch_limit_totals(const uint32_t *len, uint64_t row_stride, uint32_
                                uint32_t lookahead_log2, const void *cstat, uint32_t grid_chunks, float *min_gain,
                                uint32_t *n_limited, uint32_t *nonfinite, hipStream_t stream);
 
+// sample-rate conversion (resample_kernels.hip): one workgroup per (row, chunk of RESAMPLE_CHUNK outputs), grid_chunks =
+// resample_grid_chunks(row_stride, out_stride, U, D) of them per row; the resampled rows go to out, the count of non-finite
+// input samples a chunk owns to cbad[row * grid_chunks + c] (chunks past a row's last are left unwritten, as is out
+// there).  table: device [U][P] numerators of 2^26 (grail_resample_coefficients).
+constexpr uint32_t RESAMPLE_CHUNK = 1024;   // == GRAIL_RESAMPLE_CHUNK (not part of the contract: no number depends on it)
+uint64_t resample_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t U, uint32_t D);
+hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D,
+                           uint32_t P, const int32_t *table, uint32_t grid_chunks, float *out, uint64_t out_stride,
+                           uint32_t *cbad, hipStream_t stream);
+// ... and a row's out_len = min(ceil(n U / D), out_stride) and count from them, one lane per row (outputs may be NULL)
+hipError_t launch_resample_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t U, uint32_t D,
+                                  uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                                  uint32_t *nonfinite, hipStream_t stream);
+
 }  // namespace grail

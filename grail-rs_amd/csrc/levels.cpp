@@ -1,7 +1,8 @@
 // levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async,
-// grail_loudness_segmented_async and grail_true_peak_async, grail_limit_async (checks, the scratch, the launches) and what grail_batch_mix_leveled and its
-// _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip, loudness_segment_kernels.hip, true_peak_kernels.hip
-// and limiter_kernels.hip, the gains are level_gains.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11, §4.12.
+// grail_loudness_segmented_async and grail_true_peak_async, grail_limit_async, grail_resample_async (checks, the scratch, the launches) and what
+// grail_batch_mix_leveled and its _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip,
+// loudness_segment_kernels.hip, true_peak_kernels.hip, limiter_kernels.hip and resample_kernels.hip, the gains are level_gains.cpp and the
+// resampler's ratio and table resample_plan.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11, §4.12, §4.13.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -12,7 +13,15 @@ using namespace grail::host;
 // the rows), one block's totals for the leveled mix, the hop sums of a loudness call that does not ask for them (8 B per
 // hop of 100 ms), the chunk maxima and counts that a true-peak call folds (12 B per chunk of 4096 output times) with one
 // block's true peaks for the limited mix, the chunk numbers that a limiter call folds (16 B per group and chunk of 4096
-// samples), and the hops' non-finite counts that a segmented loudness call folds (4 B per hop).
+// samples), the hops' non-finite counts that a segmented loudness call folds (4 B per hop), the chunks' non-finite counts
+// that a resampling call folds (4 B per chunk of 1024 outputs) and the resampler's tables of the last few pairs of rates.
+struct ResampleTable {
+    uint32_t up = 0, down = 0;              // 0: the slot holds no table
+    uint64_t used = 0;                      // the call that last asked for it (the oldest is evicted)
+    std::vector<int32_t> host;              // (kept while the upload may be in flight)
+    DeviceBuffer<int32_t> dev;              // [up][taps]
+};
+
 struct LevelState : CtxPart {
     DeviceBuffer<double> d_fsum;            // frames: sums of squares,
     DeviceBuffer<float> d_fpeak;            // ... peaks
@@ -26,6 +35,9 @@ struct LevelState : CtxPart {
     DeviceBuffer<double> d_tp;              // a block's true peaks
     DeviceBuffer<unsigned char> d_lstat;    // limiter chunks
     DeviceBuffer<uint32_t> d_hbad;          // segmented loudness: non-finite counts per hop
+    DeviceBuffer<uint32_t> d_rbad;          // resampler chunks: non-finite counts
+    ResampleTable tables[4];
+    uint64_t table_calls = 0;
 };
 
 namespace {
@@ -204,6 +216,33 @@ int limit_block_gains(const double *tp, uint32_t n_rows, const uint32_t *item_ro
     return GRAIL_OK;
 }
 
+// the table of a pair of rates on the device: uploaded once per (U, D), the last four kept, the oldest evicted once
+// everything queued on the stream is through (a kernel still queued may be reading it)
+int resample_table(grail_ctx *ctx, LevelState *st, uint32_t rate_in, uint32_t rate_out, uint32_t U, uint32_t D, uint32_t P,
+                   const int32_t **table)
+{
+    ResampleTable *slot = &st->tables[0];
+    ++st->table_calls;
+    for (ResampleTable &t : st->tables) {
+        if (t.dev.get() && t.up == U && t.down == D) {
+            t.used = st->table_calls;
+            *table = t.dev.get();
+            return GRAIL_OK;
+        }
+        if (t.used < slot->used) slot = &t;
+    }
+    if (slot->dev.get()) HIP_TRY(hipStreamSynchronize(ctx->stream));
+    slot->dev.reset();
+    slot->up = slot->down = 0;              // (a failure below leaves the slot empty, not half-written under its old name)
+    slot->host.assign((size_t)U * P, 0);
+    if (grail_resample_coefficients(rate_in, rate_out, slot->host.data(), U * P))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: no table for this pair of rates");
+    HIP_TRY(upload(slot->dev, slot->host.data(), slot->host.size(), ctx->stream));
+    slot->up = U, slot->down = D, slot->used = st->table_calls;
+    *table = slot->dev.get();
+    return GRAIL_OK;
+}
+
 }  // namespace
 
 namespace grail {
@@ -344,6 +383,50 @@ int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride
     const hipError_t e = launch_limit_totals(len_dev, row_stride, n_groups, group, lookahead_log2, st->d_lstat.get(),
                                              (uint32_t)chunks, min_gain_dev, n_limited_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "limiter totals kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_resample_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev, uint32_t n_rows,
+                         uint32_t rate_in, uint32_t rate_out, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                         uint32_t *nonfinite_dev)
+{
+    // (what is wrong with the arguments is said before what is wrong with the machine)
+    uint32_t U, D, P;
+    if (grail_resample_ratio(rate_in, rate_out, &U, &D, &P))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: the rates are equal, 0, or need more than 32 768 table entries");
+    if (n_rows && (!len_dev || (row_stride && (!rows_dev || (out_stride && !out_dev)))))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: NULL buffer");
+    if (n_rows && row_stride) {
+        if (row_stride > (1ull << 60) / n_rows || out_stride > (1ull << 60) / n_rows)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: the rows span more than 2^60 samples");
+        const uintptr_t in0 = (uintptr_t)rows_dev, in1 = in0 + (uintptr_t)(n_rows * row_stride * 4u);
+        const uintptr_t out0 = (uintptr_t)out_dev, out1 = out0 + (uintptr_t)(n_rows * out_stride * 4u);
+        if (out_stride && in0 < out1 && out0 < in1)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: out_dev overlaps rows_dev (a chunk reads what another would have written)");
+        // (a row holds fewer than 2^32 samples: len is 32 bits wide)
+        const uint64_t longest = (std::min<uint64_t>(row_stride, 0xFFFFFFFFull) * U + (D - 1u)) / D;
+        if (std::min(longest, out_stride) > 0xFFFFFFFFull)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: a row could hold 2^32 output samples or more (out_len is 32 bits wide)");
+    }
+    int rc = bind_device(ctx, "grail_resample_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    const uint64_t chunks = resample_grid_chunks(row_stride, out_stride, U, D);
+    if ((uint64_t)n_rows * chunks > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: more than 2^31 chunks");
+    if (chunks) {               // (rows of no samples: 0, 0 from the totals alone)
+        const int32_t *table = nullptr;
+        if ((rc = resample_table(ctx, st, rate_in, rate_out, U, D, P, &table))) return rc;
+        if ((rc = st->d_rbad.reserve(ctx->stream, (size_t)n_rows * (size_t)chunks))) return rc;
+        const hipError_t e = launch_resample(rows_dev, row_stride, len_dev, n_rows, U, D, P, table, (uint32_t)chunks, out_dev,
+                                             out_stride, st->d_rbad.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "resample kernel launch");
+    }
+    if (!out_len_dev && !nonfinite_dev) return GRAIL_OK;
+    const hipError_t e = launch_resample_totals(len_dev, row_stride, n_rows, U, D, out_stride, st->d_rbad.get(), (uint32_t)chunks,
+                                                out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "resample totals kernel launch");
     return GRAIL_OK;
 }
 

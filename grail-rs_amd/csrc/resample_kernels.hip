@@ -1,0 +1,268 @@
+// resample_kernels.hip — rational-ratio sample-rate conversion of finished rows (grail_resample_async).  The contract
+// (include/grail_hip.h, "levels, continued: sample-rate conversion"): output m of a row sits at input time m D / U; with
+// a = m D, p = a mod U, i0 = a div U it is the left fold acc = acc + C[p][k] * v[i0 + P/2 - k] over ascending k from +0.0
+// in binary64, rounded once to binary32, C[p][k] = N / 2^26 a Kaiser-windowed sinc.  The filter is FIR, so time is
+// parallel: one workgroup per (row, chunk of RESAMPLE_CHUNK outputs), one lane per output (four passes of 256), the fold
+// serial in the lane.  The kernel folds with the integers themselves, acc' = fma((double)N, v, acc'): every N * v is exact
+// (27 bits times 24) and nothing comes near the ends of binary64's range, so acc' is 2^26 acc bit for bit at every step,
+// and y = (float)(acc' * 2^-26) is the contract's one rounding.  No atomics, every store a plain vector store.
+// DESIGN.md §4.13.
+#include "kernels.h"
+
+namespace grail {
+
+namespace {
+
+constexpr uint32_t RS_THREADS = 256;
+constexpr uint32_t RS_PASSES = RESAMPLE_CHUNK / RS_THREADS;     // outputs per lane
+constexpr uint32_t RS_LDS_MAX = 65536 - 64;                     // bytes of LDS a workgroup may ask for (64 KB less the static words)
+constexpr uint32_t RS_STAGE_SLACK = 8;                          // the stretch starts at a multiple of 4 and ends at one
+
+__device__ __forceinline__ bool rs_finite(float x) { return __builtin_fabsf(x) <= 3.4028234663852886e38f; }   // false for NaN and Inf
+
+// n = min(len, row_stride) and n_out = min(ceil(n U / D), out_stride) of a row (n < 2^32, U < 2^10: no overflow)
+__device__ __forceinline__ void rs_row(const uint32_t *__restrict__ len, uint64_t row_stride, uint64_t out_stride, uint64_t u,
+                                       uint32_t U, uint32_t D, uint64_t &n, uint64_t &n_out)
+{
+    n = len[u] < row_stride ? len[u] : row_stride;
+    const uint64_t full = (n * U + (D - 1u)) / D;
+    n_out = full < out_stride ? full : out_stride;
+}
+
+// One workgroup = one (row, chunk of RESAMPLE_CHUNK outputs).
+//   STAGED: the chunk's input stretch (the samples its outputs' taps reach) goes to LDS once, zeroed where it lies outside
+//     the row or is not finite; otherwise (a ratio whose stretch does not fit) the taps read the row itself, clamped.
+//   VEC: 16-byte loads and stores (both bases 16-byte aligned, both strides multiples of 4), else 4-byte ones: same bits.
+//   TAB: where a lane finds its coefficients.  RS_TAB_UNIFORM: U = 1, one phase: the coefficient of a tap is the same in
+//     every lane and is loaded once per wave.  RS_TAB_LDS: a lane walks its own row p of the table, which the workgroup
+//     copied to LDS (it fits beside the stretch) at a pitch of P + 1 words, odd, so that lanes on different rows fall on
+//     different banks.  RS_TAB_GLOBAL: the same walk over the table where it lies (at most 128 KB: cache-resident).
+// smem: [RESAMPLE_CHUNK] the chunk's outputs (a lane computes m0 + tid + 256 j, whose taps fall on neighbouring LDS
+// words; the stores want four consecutive outputs in a lane), then [stage_words] the stretch, then the table.
+constexpr int RS_TAB_GLOBAL = 0, RS_TAB_UNIFORM = 1, RS_TAB_LDS = 2;
+template <bool STAGED, bool VEC, int TAB>
+__global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__ rows, uint64_t row_stride,
+                                                       const uint32_t *__restrict__ len, uint32_t n_rows, uint32_t U, uint32_t D,
+                                                       uint32_t P, const int32_t *__restrict__ table, uint32_t stage_words,
+                                                       uint32_t grid_chunks, float *__restrict__ out, uint64_t out_stride,
+                                                       uint32_t *__restrict__ cbad)
+{
+    extern __shared__ float smem[];
+    float *yout = smem, *stage = smem + RESAMPLE_CHUNK;
+    int32_t *ltab = reinterpret_cast<int32_t *>(smem + RESAMPLE_CHUNK + stage_words);
+    const uint32_t pitch = TAB == RS_TAB_LDS ? P + 1u : P;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t u = blockIdx.x / grid_chunks;
+    const uint32_t c = (uint32_t)(blockIdx.x - u * grid_chunks);
+    if (u >= n_rows) return;
+    uint64_t n, n_out;
+    rs_row(len, row_stride, out_stride, u, U, D, n, n_out);
+    const uint64_t m0 = (uint64_t)c * RESAMPLE_CHUNK;
+    // a row of no samples has no chunk; chunk 0 of any other runs even with no output to write: it counts
+    if (n == 0 || (m0 >= n_out && c != 0u)) return;
+    const bool last = m0 + RESAMPLE_CHUNK >= n_out;
+    const uint32_t count = m0 >= n_out ? 0u : (last ? (uint32_t)(n_out - m0) : RESAMPLE_CHUNK);
+    const float *row = rows + u * row_stride;
+    const uint32_t half = P >> 1;
+
+    // the chunk's first output: a = m0 D, in 64 bits; every other output of the chunk is fewer than 2^20 further
+    const uint64_t a0 = m0 * D;
+    const int64_t i_base = (int64_t)(a0 / U);
+    const uint32_t p_base = (uint32_t)(a0 - (uint64_t)i_base * U);
+    // the input samples this chunk counts non-finite ones in: those between its first output's time and the next
+    // chunk's, rounded up; the row's last chunk takes the rest of the row
+    const int64_t own_lo = c ? (int64_t)((a0 + U - 1u) / U) : 0;
+    const int64_t own_hi = last ? (int64_t)n : (int64_t)(((m0 + RESAMPLE_CHUNK) * D + U - 1u) / U);
+    // the stretch: from the last tap of the first output to the first tap of the last, s_base a multiple of 4 at or below
+    const uint32_t span = count ? (uint32_t)(((uint64_t)p_base + (uint64_t)(count - 1u) * D) / U) : 0u;
+    const int64_t s_lo = i_base + 1 - (int64_t)half, s_hi = i_base + (int64_t)span + (int64_t)half + 1;
+    const int64_t s_base = s_lo & ~(int64_t)3;
+    uint32_t bad = 0u;
+    int64_t counted_to = own_lo;            // what the staging has counted of [own_lo, own_hi)
+    if (STAGED && count) {
+        const uint32_t groups = (uint32_t)((s_hi - s_base + 3) >> 2);
+        const int64_t g_hi = (int64_t)((n - 1u) >> 2), t_hi = (int64_t)n - 1;
+        for (uint32_t gi = tid; gi < groups; gi += RS_THREADS) {
+            const int64_t t0 = s_base + 4 * (int64_t)gi;
+            float x[4];
+            if (VEC) {
+                // the row's last group starts below n <= row_stride, a multiple of 4: inside the row
+                int64_t g = t0 >> 2;
+                g = g < 0 ? 0 : g;
+                g = g > g_hi ? g_hi : g;
+                const float4 v = *reinterpret_cast<const float4 *>(row + 4 * g);
+                x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    int64_t t = t0 + e;
+                    t = t < 0 ? 0 : t;
+                    t = t > t_hi ? t_hi : t;
+                    x[e] = row[t];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = t0 + e;
+                const bool inside = t >= 0 && t <= t_hi;            // (what a clamped load brought is outside)
+                const bool finite = rs_finite(x[e]);
+                bad += (inside && !finite && t >= own_lo && t < own_hi) ? 1u : 0u;
+                stage[4u * gi + e] = (inside && finite) ? x[e] : 0.0f;
+            }
+        }
+        counted_to = s_base + 4 * (int64_t)groups;
+        counted_to = counted_to < own_lo ? own_lo : counted_to;
+    }
+    // what the chunk owns past its stretch (an out_stride that cuts the row short leaves the last chunk the rest of the
+    // row; a chunk that is not staged owns all of its samples here): counted from the row itself
+    for (int64_t t = counted_to + tid; t < own_hi; t += RS_THREADS) bad += rs_finite(row[t]) ? 0u : 1u;
+    if (TAB == RS_TAB_LDS && count) {
+        for (uint32_t i = tid; i < U * P; i += RS_THREADS) {
+            const uint32_t p = i / P;
+            ltab[p * pitch + (i - p * P)] = table[i];
+        }
+    }
+    __syncthreads();
+
+    if (count) {
+        double acc[RS_PASSES];
+        uint32_t at[RS_PASSES];             // STAGED: the LDS word of tap 0; else unused
+        int64_t t_first[RS_PASSES];         // the input time of tap 0
+        uint32_t tab[RS_PASSES];            // the first word of the lane's row of the table
+#pragma unroll
+        for (uint32_t j = 0; j < RS_PASSES; ++j) {
+            uint32_t r = tid + RS_THREADS * j;
+            r = r < count ? r : count - 1u;                         // (a lane past the chunk's last output repeats it, unstored)
+            const uint32_t off = p_base + r * D;                    // < 2^10 + 2^10 2^10
+            const uint32_t q = off / U, p = off - q * U;
+            t_first[j] = i_base + (int64_t)q + (int64_t)half;
+            at[j] = (uint32_t)(t_first[j] - s_base);
+            tab[j] = TAB == RS_TAB_UNIFORM ? 0u : p * pitch;
+            acc[j] = 0.0;
+        }
+        const int64_t t_hi = (int64_t)n - 1;
+        for (uint32_t k = 0; k < P; ++k) {
+#pragma unroll
+            for (uint32_t j = 0; j < RS_PASSES; ++j) {
+                float x;
+                if (STAGED) {
+                    x = stage[at[j] - k];
+                } else {
+                    const int64_t t = t_first[j] - (int64_t)k;
+                    int64_t tc = t < 0 ? 0 : t;
+                    tc = tc > t_hi ? t_hi : tc;
+                    const float raw = row[tc];
+                    x = (t >= 0 && t <= t_hi && rs_finite(raw)) ? raw : 0.0f;
+                }
+                const int32_t num = TAB == RS_TAB_LDS ? ltab[tab[j] + k] : table[tab[j] + k];
+                acc[j] = __builtin_fma((double)num, (double)x, acc[j]);
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < RS_PASSES; ++j) yout[tid + RS_THREADS * j] = (float)(acc[j] * 1.4901161193847656e-08);   // 2^-26
+    }
+    __syncthreads();
+    // four consecutive outputs per lane; a row's last partial group goes out in 4-byte stores
+    if (4u * tid < count) {
+        float *to = out + u * out_stride + m0 + 4u * tid;
+        if (VEC && 4u * tid + 4u <= count) {
+            *reinterpret_cast<float4 *>(to) = *reinterpret_cast<const float4 *>(yout + 4u * tid);
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < 4; ++e)
+                if (4u * tid + e < count) to[e] = yout[4u * tid + e];
+        }
+    }
+    // the chunk's count: integers, so any order
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    __shared__ uint32_t red[RS_THREADS / 64];
+    if ((tid & 63u) == 0u) red[tid >> 6] = bad;
+    __syncthreads();
+    if (tid == 0u) cbad[u * grid_chunks + c] = red[0] + red[1] + red[2] + red[3];
+}
+
+// A row's numbers from its chunks, one lane per row.
+__global__ __launch_bounds__(256) void resample_totals_kernel(const uint32_t *__restrict__ len, uint64_t row_stride,
+                                                              uint32_t n_rows, uint32_t U, uint32_t D, uint64_t out_stride,
+                                                              const uint32_t *__restrict__ cbad, uint32_t grid_chunks,
+                                                              uint32_t *__restrict__ out_len, uint32_t *__restrict__ nonfinite)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (u >= n_rows) return;
+    uint64_t n, n_out;
+    rs_row(len, row_stride, out_stride, u, U, D, n, n_out);
+    uint64_t chunks = (n_out + RESAMPLE_CHUNK - 1u) / RESAMPLE_CHUNK;
+    chunks = n == 0 ? 0u : (chunks ? chunks : 1u);
+    uint32_t b = 0u;
+    for (uint64_t c = 0; c < chunks; ++c) b += cbad[u * grid_chunks + c];
+    if (out_len) out_len[u] = (uint32_t)n_out;
+    if (nonfinite) nonfinite[u] = b;
+}
+
+template <bool STAGED, bool VEC>
+void resample_launch(int tab, uint32_t workgroups, uint32_t lds, hipStream_t stream, const float *rows, uint64_t row_stride,
+                     const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t P, const int32_t *table,
+                     uint32_t stage_words, uint32_t grid_chunks, float *out, uint64_t out_stride, uint32_t *cbad)
+{
+    if (tab == RS_TAB_UNIFORM)
+        hipLaunchKernelGGL((resample_kernel<STAGED, VEC, RS_TAB_UNIFORM>), dim3(workgroups), dim3(RS_THREADS), lds, stream, rows,
+                           row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    else if (STAGED && tab == RS_TAB_LDS)       // (the table goes to LDS only beside a staged stretch)
+        hipLaunchKernelGGL((resample_kernel<STAGED, VEC, STAGED ? RS_TAB_LDS : RS_TAB_GLOBAL>), dim3(workgroups), dim3(RS_THREADS),
+                           lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    else
+        hipLaunchKernelGGL((resample_kernel<STAGED, VEC, RS_TAB_GLOBAL>), dim3(workgroups), dim3(RS_THREADS), lds, stream, rows,
+                           row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+}
+
+}  // namespace
+
+uint64_t resample_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t U, uint32_t D)
+{
+    if (row_stride == 0) return 0;
+    const unsigned __int128 full = ((unsigned __int128)row_stride * U + (D - 1u)) / D;
+    const uint64_t longest = full < out_stride ? (uint64_t)full : out_stride;
+    const uint64_t chunks = (longest + RESAMPLE_CHUNK - 1u) / RESAMPLE_CHUNK;
+    return chunks ? chunks : 1u;
+}
+
+hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D,
+                           uint32_t P, const int32_t *table, uint32_t grid_chunks, float *out, uint64_t out_stride,
+                           uint32_t *cbad, hipStream_t stream)
+{
+    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
+    if (workgroups == 0) return hipSuccess;
+    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    // the longest stretch of a chunk: floor((U - 1 + (RESAMPLE_CHUNK - 1) D) / U) + P samples, and the rounding to groups of 4
+    const uint64_t stretch = ((uint64_t)(U - 1u) + (uint64_t)(RESAMPLE_CHUNK - 1u) * D) / U + P + RS_STAGE_SLACK;
+    const uint64_t staged_bytes = (RESAMPLE_CHUNK + stretch) * 4u, table_bytes = (uint64_t)U * (P + 1u) * 4u;
+    const bool staged = staged_bytes <= RS_LDS_MAX;
+    const int tab = U == 1u ? RS_TAB_UNIFORM : (staged && staged_bytes + table_bytes <= RS_LDS_MAX ? RS_TAB_LDS : RS_TAB_GLOBAL);
+    const uint32_t stage_words = staged ? (uint32_t)stretch : 0u;
+    const uint32_t lds = (uint32_t)((staged ? staged_bytes : RESAMPLE_CHUNK * 4u) + (tab == RS_TAB_LDS ? table_bytes : 0u));
+    const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
+                     ((row_stride | out_stride) & 3u) == 0;
+    const uint32_t wg = (uint32_t)workgroups;
+    if (staged && vec)
+        resample_launch<true, true>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    else if (staged)
+        resample_launch<true, false>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    else if (vec)
+        resample_launch<false, true>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    else
+        resample_launch<false, false>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t U, uint32_t D,
+                                  uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                                  uint32_t *nonfinite, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(resample_totals_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, stream, len, row_stride, n_rows, U, D,
+                       out_stride, cbad, grid_chunks, out_len, nonfinite);
+    return hipGetLastError();
+}
+
+}  // namespace grail

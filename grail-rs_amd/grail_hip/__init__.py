@@ -80,6 +80,7 @@ EXPORTS = [
     "grail_true_peak_coefficients", "grail_true_peak_async", "grail_true_peak_db", "grail_true_peak_limit_gains",
     "grail_batch_mix_leveled_limited",
     "grail_limit_ceiling", "grail_limit_async",
+    "grail_resample_ratio", "grail_resample_coefficients", "grail_resample_len", "grail_resample_async",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -94,6 +95,9 @@ TRUE_PEAK_PHASES, TRUE_PEAK_TAPS = 4, 12        # GRAIL_TRUE_PEAK_*: the 4x over
 LIMIT_LOOKAHEAD_LOG2_MAX = 10                   # GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX: the look-ahead is 2^0 .. 2^10 samples
 LIMIT_REFUSED = 0xFFFFFFFF                      # GRAIL_LIMIT_REFUSED: n_limited of a group whose members differ in length
 LIMIT_CHUNK = 4096                              # GRAIL_LIMIT_CHUNK: one workgroup's samples (no number depends on it)
+RESAMPLE_ZERO_CROSSINGS = 24                    # GRAIL_RESAMPLE_ZERO_CROSSINGS: per side, at the lower of the two rates
+RESAMPLE_TABLE_MAX = 32768                      # GRAIL_RESAMPLE_TABLE_MAX: up * taps of a supported pair of rates
+RESAMPLE_CHUNK = 1024                           # GRAIL_RESAMPLE_CHUNK: one workgroup's outputs (no number depends on it)
 
 
 class GrailError(RuntimeError):
@@ -367,6 +371,10 @@ def load():
     L.grail_limit_ceiling.argtypes = [C.c_float]
     L.grail_limit_ceiling.restype = C.c_float
     L.grail_limit_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp, u64, vp, vp, vp]
+    L.grail_resample_ratio.argtypes = [C.c_uint32, C.c_uint32, vp, vp, vp]
+    L.grail_resample_coefficients.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32]
+    L.grail_resample_len.argtypes = [u64, C.c_uint32, C.c_uint32, vp]
+    L.grail_resample_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64, vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -708,6 +716,29 @@ def true_peak_db(true_peak):
 def limit_ceiling(ceiling_db):
     """grail_limit_ceiling (pure host): the float32 that a ceiling in dBTP is to grail_limit_async."""
     return np.float32(load().grail_limit_ceiling(float(np.float32(ceiling_db))))
+
+
+def resample_ratio(rate_in, rate_out):
+    """grail_resample_ratio (pure host): (up, down, taps) of a pair of whole-numbered rates; GrailError for a pair that is
+    not supported (a rate of 0, equal rates, more than RESAMPLE_TABLE_MAX table entries)."""
+    u, d, p = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+    _check(load().grail_resample_ratio(rate_in, rate_out, C.addressof(u), C.addressof(d), C.addressof(p)))
+    return u.value, d.value, p.value
+
+
+def resample_coefficients(rate_in, rate_out):
+    """grail_resample_coefficients (pure host): the numerators N of 2^26 of the pair's table, int32[up, taps]."""
+    u, _, p = resample_ratio(rate_in, rate_out)
+    num = np.zeros((u, p), dtype=np.int32)
+    _check(load().grail_resample_coefficients(rate_in, rate_out, num.ctypes.data, u * p))
+    return num
+
+
+def resample_len(n, rate_in, rate_out):
+    """grail_resample_len (pure host): ceil(n * up / down), the length of a row of n samples resampled."""
+    out = C.c_uint64(0)
+    _check(load().grail_resample_len(n, rate_in, rate_out, C.addressof(out)))
+    return out.value
 
 
 def true_peak_limit_gains(true_peak, item_rows, item_gains, ceiling_db, n_rows=None):
@@ -1162,6 +1193,28 @@ class Context:
             for p in d:
                 self.device_free(p)
         return tuple(r[:n_groups] for r in res)
+
+    def resample_async(self, rows_dev, row_stride, len_dev, n_rows, rate_in, rate_out, out_dev, out_stride, out_len_dev=None,
+                       nonfinite_dev=None):
+        """grail_resample_async: the rows at rate_in resampled to rate_out into out_dev (must not overlap rows_dev), output m
+        at input time m * down / up.  Results are DEVICE arrays [n_rows] (either may be None), queued on the context's
+        stream."""
+        _check(load().grail_resample_async(self.handle, rows_dev, row_stride, len_dev, n_rows, rate_in, rate_out, out_dev,
+                                           out_stride, out_len_dev, nonfinite_dev))
+
+    def resample(self, rows_dev, row_stride, len_dev, n_rows, rate_in, rate_out, out_dev, out_stride):
+        """resample_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row."""
+        res = [np.zeros(max(n_rows, 1), dtype=np.uint32) for _ in range(2)]
+        d = [self.device_alloc(max(n_rows, 1) * 4) for _ in res]
+        try:
+            self.resample_async(rows_dev, row_stride, len_dev, n_rows, rate_in, rate_out, out_dev, out_stride, *d)
+            for dst, src in zip(res, d):
+                self.d2h(dst, src, n_rows * 4)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return tuple(r[:n_rows] for r in res)
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max finite |x|, non-finite counts) per row, computed on the device (every length

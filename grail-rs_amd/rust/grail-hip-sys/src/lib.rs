@@ -278,6 +278,12 @@ extern "C" {
     pub fn grail_limit_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32, n_rows: u32,
         group: u32, ceiling: f32, lookahead_log2: u32, out_dev: *mut f32, out_stride: u64, min_gain_dev: *mut f32,
         n_limited_dev: *mut u32, nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_resample_ratio(rate_in: u32, rate_out: u32, up: *mut u32, down: *mut u32, taps: *mut u32) -> c_int;
+    pub fn grail_resample_coefficients(rate_in: u32, rate_out: u32, num: *mut i32, cap: u32) -> c_int;
+    pub fn grail_resample_len(n: u64, rate_in: u32, rate_out: u32, n_out: *mut u64) -> c_int;
+    pub fn grail_resample_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32, n_rows: u32,
+        rate_in: u32, rate_out: u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
+        nonfinite_dev: *mut u32) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

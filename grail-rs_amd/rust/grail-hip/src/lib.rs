@@ -523,6 +523,69 @@ impl Gpu {
         Ok((out, min_gain, limited, bad))
     }
 
+    /// Rows of samples at `rate_in` resampled to `rate_out` on the device (`grail_resample_async`; the contract is the header's
+    /// section "levels, continued: sample-rate conversion"): output `m` of a row sits at input time `m * rate_in / rate_out`,
+    /// a row of `n` samples gives `ceil(n * rate_out / rate_in)`.  Returns the resampled rows and, per row, the count of
+    /// non-finite input samples (they enter as +0.0).  The filter overshoots: limit or measure after resampling.
+    pub fn resample(&self, rows: &[Vec<f32>], rate_in: u32, rate_out: u32) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        let n = rows.len();
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let longest_out = resample_len(longest as u64, rate_in, rate_out)? as usize;
+        if n == 0 {
+            return Ok((out, bad));
+        }
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let out_stride = ((longest_out + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let sizes = [n * stride * 4, n * out_stride * 4, n * 4, n * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_resample_async(self.ctx, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32, rate_in,
+                                                    rate_out, d[1] as *mut f32, out_stride as u64, d[3] as *mut u32, d[4] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(self.ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad))
+    }
+
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
     /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
     /// non-finite samples.  One lane filters one row: many rows fill the device.
@@ -686,6 +749,21 @@ pub fn true_peak_db(true_peak: f64) -> f64 {
 pub const LIMIT_REFUSED: u32 = 0xFFFF_FFFF;
 /// The largest `lookahead_log2` of [`Gpu::limit`] (`GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX`).
 pub const LIMIT_LOOKAHEAD_LOG2_MAX: u32 = 10;
+
+/// `(up, down, taps)` of a pair of whole-numbered sample rates (`grail_resample_ratio`; pure host); an error for a pair
+/// that [`Gpu::resample`] does not take: a rate of 0, equal rates, more than 32 768 table entries.
+pub fn resample_ratio(rate_in: u32, rate_out: u32) -> Result<(u32, u32, u32), Error> {
+    let (mut up, mut down, mut taps) = (0u32, 0u32, 0u32);
+    check(unsafe { sys::grail_resample_ratio(rate_in, rate_out, &mut up, &mut down, &mut taps) })?;
+    Ok((up, down, taps))
+}
+
+/// The length of a row of `n` samples resampled: `ceil(n * up / down)` (`grail_resample_len`; pure host).
+pub fn resample_len(n: u64, rate_in: u32, rate_out: u32) -> Result<u64, Error> {
+    let mut n_out = 0u64;
+    check(unsafe { sys::grail_resample_len(n, rate_in, rate_out, &mut n_out) })?;
+    Ok(n_out)
+}
 
 /// The `f32` that a ceiling in dBTP is to [`Gpu::limit`] (`grail_limit_ceiling`; pure host).
 pub fn limit_ceiling(ceiling_db: f32) -> f32 {

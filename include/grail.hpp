@@ -452,6 +452,43 @@ public:
         return out;
     }
 
+    // Rows of samples at rate_in resampled to rate_out on the device (grail_resample_async; the contract is the header's
+    // section "levels, continued: sample-rate conversion"): output m of a row sits at input time m * rate_in / rate_out, a
+    // row of n samples gives ceil(n * rate_out / rate_in).  The filter overshoots: limit or measure after resampling.
+    std::vector<std::vector<float>> resample(const std::vector<std::vector<float>> &rows, uint32_t rate_in, uint32_t rate_out) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        uint64_t longest_out = 0;
+        check(grail_resample_len(longest, rate_in, rate_out, &longest_out));
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64, out_stride = longest_out ? (longest_out + 63) / 64 * 64 : 64;
+        std::vector<std::vector<float>> out(n);
+        if (!n) return out;
+        std::vector<uint32_t> lens(n), out_lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        void *d_rows = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_out_len);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc) rc = grail_resample_async(ctx_, (const float *)d_rows, stride, (const uint32_t *)d_len, n, rate_in, rate_out,
+                                           (float *)d_out, out_stride, (uint32_t *)d_out_len, nullptr);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)n * 4);
+        for (uint32_t i = 0; !rc && i < n; ++i) {
+            if (!out_lens[i]) continue;
+            out[i].resize(out_lens[i]);
+            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)out_lens[i] * 4);
+        }
+        for (void *p : {d_rows, d_out, d_len, d_out_len})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
     // Tracks of equal length as one multichannel WAV: interleaved i16 frames made on the device (grail_pcm16_frames_async,
     // the examples/cli.rs:49 conversion), then save_wav for as many channels (grail_wav_write_i16_frames).
     void save_wav_frames(const std::string &path, const std::vector<std::vector<float>> &tracks, uint32_t sample_rate) const

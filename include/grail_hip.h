@@ -947,6 +947,72 @@ int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride
                       uint32_t group, float ceiling, uint32_t lookahead_log2, float *out_dev, uint64_t out_stride,
                       float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev);
 
+/* ---- levels, continued: sample-rate conversion ----------------------------------------------------------------------------------
+ * A context's voice table has one rate, and rendering at a lower one is a different signal (formants above Nyquist are
+ * dropped, the carrier's harmonics alias).  The resampler is the stage after the mix and the limiter: finished rows at
+ * rate_in become the same audio at rate_out, by a rational-ratio polyphase FIR filter.  All arithmetic is IEEE binary64.
+ * RATIO.  Rates are whole numbers, both > 0, rate_in != rate_out.  g = gcd(rate_in, rate_out), U = rate_out / g (up),
+ * D = rate_in / g (down), Z = GRAIL_RESAMPLE_ZERO_CROSSINGS = 24 zero crossings per side at the lower of the two rates,
+ * P = 2 * ceil(Z * max(U, D) / U) taps per output sample (even).  A pair is supported when U * P <=
+ * GRAIL_RESAMPLE_TABLE_MAX = 32 768 table entries, otherwise GRAIL_ERR_INVALID_ARG: every pair among 8 000, 11 025,
+ * 16 000, 22 050, 24 000, 44 100, 48 000, 96 000 fits (44 100 -> 16 000: U = 160, D = 441, P = 134, 21 440 entries;
+ * 48 000 -> 11 025: U = 147, D = 640, P = 210, 30 870 entries) but 11 025 <-> 96 000 (61 440 and 61 446 entries: go
+ * through 48 000).  Equal rates are refused: a caller who asked for no change must not get a low-pass.
+ * TABLE.  A Kaiser-windowed sinc, beta = 8.0, cutoff f = 0.9 * min(1, U / D) cycles per input sample, half-width
+ * W = P / 2 input samples, indexed by an integer j so that it is exactly even.  For j = -(P/2) U .. (P/2) U - 1, with
+ * x = (double)|j| / (double)U:
+ *     H(j) = f * sinc(f * x) * I0(beta * sqrt(1 - (x / W)^2)) / I0(beta)
+ *     sinc(a) = sin(pi a) / (pi a), sinc(0) = 1
+ *     I0 by its power series, the terms ((y / 2)^k / k!)^2 summed ascending until a term no longer changes the sum
+ *     N(j) = llrint(H(j) * 2^26), ties to even;   C[p][k] = N((k - P/2) U + p) / 2^26,  p = 0 .. U - 1, k = 0 .. P - 1
+ * |N| < 2^26 because |H| <= 0.9.  A 27-bit numerator times a 24-bit significand is exact in binary64, so a fused
+ * multiply-add and a multiply followed by an add give the same bits (the argument of the true-peak section).  The bits
+ * of N come from the C library's sin: the table as grail_resample_coefficients returns it is the contract, as with
+ * grail_kweighting.
+ * SAMPLES.  For a row of n = min(len[u], row_stride) samples:
+ *   - v[t] = (double)x[t] for 0 <= t < n and +0.0 outside; a sample that is not finite (|x| > FLT_MAX or NaN) is counted
+ *     once and enters as +0.0; memory between n and row_stride is never looked at, whatever it holds.
+ *   - n_out = min(ceil(n U / D), out_stride), computed in 64 bits.
+ *   - For output m = 0 .. n_out - 1: a = m D in 64 bits, p = a mod U, i0 = a div U; acc = +0.0; for k = 0 .. P - 1
+ *     ascending acc = acc + C[p][k] * v[i0 + P/2 - k]; y[m] = (float)acc, one rounding.
+ *   - Output m sits at input time m D / U exactly: zero delay, linear phase.
+ *   - out between n_out and out_stride is never written.  out_len[u] = n_out; nonfinite[u] = the count over all n
+ *     samples (also where out_stride cut the output short).
+ * Nothing above depends on chunking, layout, alignment, the rows around or the launch: out and the results are a pure
+ * function of the row's samples and the two rates.  No float atomics.
+ * NOT promised: the output's peak can exceed the input's, because the filter overshoots: limit or measure after
+ * resampling, not before.  The passband ends at about 0.79 of the lower Nyquist frequency; the stopband starts at the
+ * lower Nyquist frequency, at about 80 dB.  There is no pass-through phase: no output is a copy of an input sample. */
+#define GRAIL_RESAMPLE_ZERO_CROSSINGS 24
+#define GRAIL_RESAMPLE_TABLE_MAX 32768
+/* The outputs of one workgroup's stretch of a row.  Not part of the contract (no number depends on it): it is here so
+ * that tests can aim at the seams. */
+#define GRAIL_RESAMPLE_CHUNK 1024
+
+/* Pure host: U, D and P of a pair of rates (any of the three may be NULL).  GRAIL_ERR_INVALID_ARG, nothing written: a
+ * rate of 0, equal rates, U * P > GRAIL_RESAMPLE_TABLE_MAX. */
+int grail_resample_ratio(uint32_t rate_in, uint32_t rate_out, uint32_t *up, uint32_t *down, uint32_t *taps);
+/* Pure host: num[p * taps + k] = N((k - taps/2) U + p), up * taps numerators of 2^26.  GRAIL_ERR_INVALID_ARG, nothing
+ * written: a pair grail_resample_ratio refuses, num NULL, cap < up * taps. */
+int grail_resample_coefficients(uint32_t rate_in, uint32_t rate_out, int32_t *num, uint32_t cap);
+/* Pure host: *n_out = ceil(n U / D), the length of a row of n samples resampled.  GRAIL_ERR_INVALID_ARG: a pair
+ * grail_resample_ratio refuses, n_out NULL, a length that does not fit 64 bits. */
+int grail_resample_len(uint64_t n, uint32_t rate_in, uint32_t rate_out, uint64_t *n_out);
+
+/* The resampler above, queued on ctx's stream like grail_true_peak_async: rows_dev: device [n_rows][row_stride] (finished
+ * tracks or rendered rows alike); len_dev: device [n_rows]; out_dev: device [n_rows][out_stride].  Results are DEVICE
+ * arrays [n_rows], either may be NULL: out_len, nonfinite.  out_dev must not overlap rows_dev.  16-byte loads and stores
+ * where both bases are 16-byte aligned and both strides multiples of 4, 4-byte ones otherwise: same bits.  One workgroup
+ * takes GRAIL_RESAMPLE_CHUNK outputs of one row, so a lone long track fills the device.  The table of a pair of rates is
+ * uploaded at its first use and the last four pairs' stay with the context, as does the scratch (4 bytes per row and 1024
+ * outputs), grown and never shrunk, until grail_destroy.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a pair grail_resample_ratio refuses; a NULL buffer with samples to read or
+ * write; overlapping ranges; strides that allow a row of 2^32 outputs or more.  These come first; without a usable
+ * device: GRAIL_ERR_NO_DEVICE.  n_rows = 0 is a success that queues nothing. */
+int grail_resample_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev, uint32_t n_rows,
+                         uint32_t rate_in, uint32_t rate_out, float *out_dev, uint64_t out_stride,
+                         uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
