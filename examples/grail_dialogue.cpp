@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--rate R] [--report] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--rate R] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -10,6 +10,10 @@
 // --limit (with --ceiling) then passes the two finished tracks, as one linked pair, through the look-ahead limiter
 // (grail::Gpu::limit) with the largest power of two of samples within 5 ms as look-ahead, and prints the tracks' true
 // peaks before and after: what placements that overlap, or the mix's own rounding, left above the ceiling gives way there.
+// --band LO HI passes the two mixed tracks, at the voices' rate, after the mix and before the limiter, through one band-pass
+// of LO .. HI Hz (grail::fir_design, a Kaiser window of --taps K taps, K odd, 255 unless said; grail::Gpu::fir): "--band 300
+// 3400 --rate 8000" is a telephone line.  The tracks keep their length (the filter has zero delay; its tail past the end is
+// dropped).  A filter overshoots, so with --ceiling the line that states the tracks' true peaks is measured after it.
 // --rate R resamples the two finished tracks, after the mix and the limiter, from the voices' 44 100 Hz to R Hz on the device
 // (grail::Gpu::resample) and writes the WAV at R; the filter overshoots a little, so the line it prints has the tracks'
 // true peaks at R.
@@ -35,6 +39,9 @@ int main(int argc, char **argv)
     float level_db = 0.0f, ceiling_db = 0.0f;
     bool resampled = false, bad_rate = false;
     uint32_t rate = 0;
+    bool band = false, bad_band = false, taps_given = false;
+    double band_lo = 0.0, band_hi = 0.0;
+    uint32_t band_taps = 255;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
         else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
@@ -54,6 +61,22 @@ int main(int argc, char **argv)
             resampled = true;
             rate = (uint32_t)r;
             bad_rate = rest == argv[i] || *rest || argv[i][0] == '-' || r == 0 || r > 0xFFFFFFFFull;
+        } else if (!std::strcmp(argv[i], "--band")) {
+            band = true;
+            bad_band = i + 2 >= argc;
+            if (!bad_band) {
+                char *rest_lo = nullptr, *rest_hi = nullptr;
+                band_lo = std::strtod(argv[i + 1], &rest_lo);
+                band_hi = std::strtod(argv[i + 2], &rest_hi);
+                bad_band = rest_lo == argv[i + 1] || *rest_lo || rest_hi == argv[i + 2] || *rest_hi || !(band_lo >= 0.0 && band_lo < band_hi);
+                i += 2;
+            }
+        } else if (!std::strcmp(argv[i], "--taps") && i + 1 < argc) {
+            char *rest = nullptr;
+            const unsigned long long k = std::strtoull(argv[++i], &rest, 10);
+            taps_given = true;
+            band_taps = (uint32_t)k;
+            bad_band = bad_band || rest == argv[i] || *rest || argv[i][0] == '-' || k < 3 || k > GRAIL_FIR_TAPS_MAX || k % 2 == 0;
         } else if (!std::strcmp(argv[i], "--limit")) limit = true;
         else if (!std::strcmp(argv[i], "--report")) {
             bad_report = report;        // (named twice)
@@ -61,10 +84,13 @@ int main(int argc, char **argv)
         } else if (!std::strncmp(argv[i], "--report", 8)) bad_report = true;        // (it takes no value)
         else lines.push_back(argv[i]);
     }
-    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || (capped && !leveled) || (limit && !capped)) {
-        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--rate R] [--report] "
-                             "\"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit needs --ceiling, "
-                             "--rate takes a whole number of Hz, --report takes no value)\n");
+    // (the voices are the generic ones, at 44 100 Hz: a band that ends above their Nyquist frequency is said here)
+    bad_band = bad_band || (taps_given && !band) || (band && band_hi > 22050.0);
+    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || (capped && !leveled) || (limit && !capped)) {
+        std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] "
+                             "[--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
+                             "needs --ceiling, --band takes 0 <= LO < HI <= 22050 Hz, --taps an odd number from 3 to 4096 and needs "
+                             "--band, --rate takes a whole number of Hz, --report takes no value)\n");
         return 2;
     }
     try {
@@ -84,6 +110,14 @@ int main(int argc, char **argv)
         const std::vector<grail::Placement> placements = {
             {0, 0, at[0], 0.8f}, {0, 1, at[0], 0.2f}, {1, 0, at[1], 0.2f}, {1, 1, at[1], 0.8f}};
         std::vector<std::vector<float>> tracks;
+        // --band: one designed filter for both tracks, which keep their length
+        const auto band_pass = [&]() {
+            if (!band) return;
+            const uint32_t at_rate = (uint32_t)first.sample_rate;
+            const grail::FirSet set = gpu.fir_set({grail::fir_design(at_rate, band_lo, band_hi, band_taps)});
+            tracks = gpu.fir(set, tracks, {}, false);
+            std::printf("Filtered %g - %g Hz at %u Hz (%u taps)\n", band_lo, band_hi, at_rate, band_taps);
+        };
         if (leveled) {          // the same pan as a level: 0.8 and 0.2 of the line at level_db
             std::vector<float> levels, gains;
             for (const grail::Placement &p : placements) levels.push_back(level_db + 20.0f * std::log10(p.gain));
@@ -91,6 +125,7 @@ int main(int argc, char **argv)
             const int mode = lufs ? GRAIL_LEVEL_LOUDNESS : GRAIL_LEVEL_RMS;
             tracks = capped ? gpu.mix_leveled_limited(utts, placements, levels, ceiling_db, 2, end, mode, &gains, &unleveled, &limited)
                             : gpu.mix_leveled(utts, placements, levels, 2, end, mode, &gains, &unleveled);
+            band_pass();
             if (lufs)
                 std::printf("Lines brought to %.1f LUFS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
                             unleveled ? " (a silent line or one shorter than 400 ms was left out)" : "");
@@ -115,6 +150,7 @@ int main(int argc, char **argv)
             }
         } else {
             tracks = gpu.mix(utts, placements, 2, end);
+            band_pass();
         }
         uint32_t out_rate = (uint32_t)first.sample_rate;
         if (resampled && rate != out_rate) {    // (the voices' own rate: nothing to do, and the library refuses equal rates)

@@ -2,7 +2,7 @@
 // units include kernels.h, never this).  grail_api.cpp: contexts, batches, voices; options.cpp: the option table,
 // grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
 // families, cost model, block planner; synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
-// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak), limited and resampled; host_output.cpp: the one-call
+// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak), limited, resampled and filtered; host_output.cpp: the one-call
 // forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Every HIP resource these units
 // create has one owner type (below): Event, Stream, DeviceBuffer, PinnedBuffer.
 #pragma once
@@ -32,6 +32,7 @@
 
 #include "../../include/grail_hip.h"
 #include "division_window.h"
+#include "fir_plan.h"
 #include "kernels.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)
@@ -327,6 +328,17 @@ struct grail_stream {
     grail::host::Event ev_stage[2];
     bool stage_busy[2] = {false, false};
     int stage_next = 0;
+};
+
+// A set of FIR filters (levels.cpp; the image and its descriptors are fir_plan.cpp's): owned by the context's LevelState,
+// released by grail_fir_free or with the context.
+struct grail_fir {
+    uint32_t n_filters = 0;
+    uint32_t tail_max = 0;            // the largest n_taps - 1 - origin of the set: how far a row rings out
+    std::vector<double> image;        // (host copies, kept while the upload may be in flight)
+    std::vector<uint32_t> desc;
+    grail::host::DeviceBuffer<double> d_taps;     // every filter's taps, binary64, padded to a multiple of 8
+    grail::host::DeviceBuffer<uint32_t> d_desc;   // [n_filters][FIR_DESC_WORDS]
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks

@@ -1,0 +1,258 @@
+// fir_kernels.hip — FIR filtering of finished rows with the caller's own taps (grail_fir_async).  The contract
+// (include/grail_hip.h, "levels, continued: FIR filtering"): output m of a row is the left fold acc = acc + (double)h[k] *
+// v[m + o - k] over ascending k from +0.0 in binary64, rounded once to binary32.  Every product is exact (24 bits times
+// 24), so acc = fma(h[k], v, acc) is the contract's multiply and add.  Time is parallel: one workgroup of four waves per
+// (row, chunk of FIR_CHUNK outputs).  A plain convolution has the same coefficient in every lane and lets a lane own
+// CONSECUTIVE outputs: a lane keeps eight accumulators and a window of the samples they meet in registers, so a tap step
+// brings ONE new sample from LDS and issues EIGHT multiply-adds (the resampler reads LDS once per multiply-add: §4.13).
+// No atomics, every store a plain vector store.  DESIGN.md §4.14.
+#include "kernels.h"
+
+namespace grail {
+
+namespace {
+
+constexpr uint32_t FIR_THREADS = 256;
+constexpr uint32_t FIR_OWN = FIR_CHUNK / FIR_THREADS;           // consecutive outputs per lane
+static_assert(FIR_OWN == 8, "the tap loop is written for eight outputs per lane and blocks of eight taps");
+constexpr uint32_t FIR_TAPS_PADDED_MAX = 4096;                  // GRAIL_FIR_TAPS_MAX, a multiple of 8
+// The stretch of a chunk: FIR_CHUNK + Kp - 1 samples (Kp: the taps padded to a multiple of 8), at most 6143, in groups of
+// eight.  Sample s of the stretch lies at word (s mod 8) * FIR_PITCH + s div 8: lane L reads "sample 8 (L + g) + r" for a
+// wave-uniform g and r, which in the plain layout is eight words from its neighbour's, an eight-way conflict on the 32
+// banks that a 4-byte read sees; here the 64 lanes of a wave read 64 consecutive words, free of conflicts, and r is a
+// constant offset in the instruction.  The staging writes sample 4 i + e from lane i: neighbouring lanes alternate
+// between rows r and r + 4 of the image, and 4 * FIR_PITCH = 16 mod 32 puts those on opposite halves of the banks.
+constexpr uint32_t FIR_GROUPS = (FIR_CHUNK + FIR_TAPS_PADDED_MAX) / 8;      // 768: groups of a stretch (6143 samples)
+constexpr uint32_t FIR_PITCH = FIR_GROUPS + 4;                              // 772
+static_assert((4u * FIR_PITCH) % 32u == 16u, "rows r and r + 4 of the image on opposite halves of the banks");
+
+__device__ __forceinline__ bool fir_finite(float x) { return __builtin_fabsf(x) <= 3.4028234663852886e38f; }   // false for NaN and Inf
+
+// the filter of row u, or false: an index outside the set (the row is refused: nothing of it is touched)
+struct FirFilter {
+    uint32_t first, padded, taps, origin;
+};
+__device__ __forceinline__ bool fir_filter(const uint32_t *__restrict__ filter, const uint32_t *__restrict__ desc, uint32_t n_filters,
+                                           uint64_t u, FirFilter &f)
+{
+    const uint32_t i = filter ? filter[u] : 0u;
+    if (i >= n_filters) return false;
+    const uint4 d = *reinterpret_cast<const uint4 *>(desc + 4u * i);
+    f.first = d.x, f.padded = d.y, f.taps = d.z, f.origin = d.w;
+    return true;
+}
+
+// n = min(len, row_stride) and n_out = min(n + K - 1 - o, out_stride), 0 for n = 0 (n < 2^32, K <= 2^12: no overflow)
+__device__ __forceinline__ void fir_row(const uint32_t *__restrict__ len, uint64_t row_stride, uint64_t out_stride, uint64_t u,
+                                        const FirFilter &f, uint64_t &n, uint64_t &n_out)
+{
+    n = len[u] < row_stride ? len[u] : row_stride;
+    const uint64_t full = n ? n + (f.taps - 1u - f.origin) : 0u;
+    n_out = full < out_stride ? full : out_stride;
+}
+
+// Eight taps h[0 .. 7] of a block against the lane's window.  Tap i meets, for the lane's output j, sample 7 + j - i of the
+// fifteen that start at the block's group: 0 .. 7 are that group (fresh: eight LDS reads), 8 .. 14 the first seven of the
+// group after it, which the block before brought in.  The caller swaps the two arrays from block to block, so the window
+// moves by the names of the registers, not by copies.
+__device__ __forceinline__ void fir_block(const float *__restrict__ at, const double *__restrict__ h, double (&fresh)[8],
+                                          const double (&kept)[8], double (&acc)[8])
+{
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r) fresh[r] = (double)at[r * FIR_PITCH];
+#pragma unroll
+    for (uint32_t i = 0; i < 8; ++i) {
+        const double c = h[i];
+#pragma unroll
+        for (uint32_t j = 0; j < 8; ++j) {
+            const uint32_t x = 7u + j - i;
+            acc[j] = __builtin_fma(c, x < 8u ? fresh[x] : kept[x - 8u], acc[j]);
+        }
+    }
+}
+
+// One workgroup = one (row, chunk of FIR_CHUNK outputs).  VEC: 16-byte loads and stores (both bases 16-byte aligned, both
+// strides multiples of 4), else 4-byte ones: same bits.  The chunk's stretch (the samples its outputs' taps reach) goes to
+// LDS once, zeroed where it lies outside the row or is not finite.  Chunk c counts the non-finite samples among inputs
+// [c FIR_CHUNK, (c + 1) FIR_CHUNK), the row's last chunk to the row's end.
+template <bool VEC>
+__global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows, uint64_t row_stride, const uint32_t *__restrict__ len,
+                                                  uint32_t n_rows, const uint32_t *__restrict__ filter, const double *__restrict__ taps,
+                                                  const uint32_t *__restrict__ desc, uint32_t n_filters, uint32_t grid_chunks,
+                                                  float *__restrict__ out, uint64_t out_stride, uint32_t *__restrict__ cbad)
+{
+    __shared__ float stage[8 * FIR_PITCH];
+    __shared__ uint32_t red[FIR_THREADS / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t u = blockIdx.x / grid_chunks;
+    const uint32_t c = (uint32_t)(blockIdx.x - u * grid_chunks);
+    if (u >= n_rows) return;
+    FirFilter f;
+    if (!fir_filter(filter, desc, n_filters, u, f)) return;
+    uint64_t n, n_out;
+    fir_row(len, row_stride, out_stride, u, f, n, n_out);
+    const uint64_t m0 = (uint64_t)c * FIR_CHUNK;
+    // a row of no samples has no chunk; chunk 0 of any other runs even with no output to write: it counts
+    if (n == 0 || (m0 >= n_out && c != 0u)) return;
+    const bool last = m0 + FIR_CHUNK >= n_out;
+    const uint32_t count = m0 >= n_out ? 0u : (last ? (uint32_t)(n_out - m0) : FIR_CHUNK);
+    const float *row = rows + u * row_stride;
+    const uint32_t Kp = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.padded);
+    const int64_t t_hi = (int64_t)n - 1;
+    // the input samples this chunk counts non-finite ones in
+    const int64_t own_lo = (int64_t)m0 < (int64_t)n ? (int64_t)m0 : (int64_t)n;
+    const int64_t own_hi = last || (int64_t)(m0 + FIR_CHUNK) > (int64_t)n ? (int64_t)n : (int64_t)(m0 + FIR_CHUNK);
+    // the stretch: sample s of it is input time s_base + s; output m0 + r meets, at tap k, sample r + Kp - 1 - k.  The
+    // lanes with an output to compute (each owns eight) reach samples 0 .. 8 lanes + Kp - 2.
+    const uint32_t lanes = (count + 7u) >> 3;
+    const int64_t s_base = (int64_t)m0 + (int64_t)f.origin - (int64_t)(Kp - 1u);
+    const int64_t s_need = count ? (int64_t)(8u * lanes + Kp - 1u) : 0;
+    uint32_t bad = 0u;
+    int64_t counted_to = own_lo;            // what the staging has counted of [own_lo, own_hi)
+    if (count) {
+        // whole groups of 4 input samples, the first at a multiple of 4 at or below s_base (which may be negative)
+        const int64_t g_first = s_base >> 2;
+        const uint32_t groups = (uint32_t)(((s_base + s_need + 3) >> 2) - g_first);
+        const int64_t g_hi = t_hi >> 2;
+        for (uint32_t gi = tid; gi < groups; gi += FIR_THREADS) {
+            const int64_t t0 = 4 * (g_first + (int64_t)gi);
+            float x[4];
+            if (VEC) {
+                // the row's last group starts below n <= row_stride, a multiple of 4: inside the row
+                int64_t g = g_first + (int64_t)gi;
+                g = g < 0 ? 0 : g;
+                g = g > g_hi ? g_hi : g;
+                const float4 v = *reinterpret_cast<const float4 *>(row + 4 * g);
+                x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    int64_t t = t0 + e;
+                    t = t < 0 ? 0 : t;
+                    t = t > t_hi ? t_hi : t;
+                    x[e] = row[t];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = t0 + e;
+                const bool inside = t >= 0 && t <= t_hi;            // (what a clamped load brought is outside)
+                const bool finite = fir_finite(x[e]);
+                bad += (inside && !finite && t >= own_lo && t < own_hi) ? 1u : 0u;
+                const int64_t s = t - s_base;
+                if (s >= 0 && s < s_need) stage[((uint32_t)s & 7u) * FIR_PITCH + ((uint32_t)s >> 3)] = (inside && finite) ? x[e] : 0.0f;
+            }
+        }
+        counted_to = 4 * (g_first + (int64_t)groups);
+        counted_to = counted_to < own_lo ? own_lo : counted_to;
+    }
+    // what the chunk owns past its stretch (an out_stride or an origin that ends the outputs before the samples leaves
+    // the last chunk the rest of the row): counted from the row itself
+    for (int64_t t = counted_to + tid; t < own_hi; t += FIR_THREADS) bad += fir_finite(row[t]) ? 0u : 1u;
+    __syncthreads();
+
+    if (tid < lanes) {
+        // the coefficient is the same in every lane: the taps are read through a wave-uniform address (scalar loads)
+        const double *h = taps + (uint32_t)__builtin_amdgcn_readfirstlane((int)f.first);
+        const uint32_t blocks = Kp >> 3;
+        // block b (taps 8 b .. 8 b + 7) starts at group lane + blocks - 1 - b of the stretch
+        const float *at = stage + tid + blocks;
+        double a[8], b[8], acc[8];
+#pragma unroll
+        for (uint32_t r = 0; r < 8; ++r) acc[r] = 0.0, a[r] = 0.0;
+#pragma unroll
+        for (uint32_t r = 0; r < 7; ++r) b[r] = (double)at[r * FIR_PITCH];     // samples 8 .. 14 of block 0's window
+        b[7] = 0.0;
+        uint32_t k = 0;
+        for (; k + 2u <= blocks; k += 2u) {
+            fir_block(at - 1, h, a, b, acc);
+            fir_block(at - 2, h + 8, b, a, acc);
+            at -= 2, h += 16;
+        }
+        if (k < blocks) fir_block(at - 1, h, a, b, acc);
+
+        // eight consecutive outputs per lane; a row's last partial group goes out in 4-byte stores
+        float *to = out + u * out_stride + m0 + 8u * tid;
+        if (VEC && 8u * tid + 8u <= count) {
+            reinterpret_cast<float4 *>(to)[0] = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
+            reinterpret_cast<float4 *>(to)[1] = make_float4((float)acc[4], (float)acc[5], (float)acc[6], (float)acc[7]);
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < 8; ++e)
+                if (8u * tid + e < count) to[e] = (float)acc[e];
+        }
+    }
+    // the chunk's count: integers, so any order
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    if ((tid & 63u) == 0u) red[tid >> 6] = bad;
+    __syncthreads();
+    if (tid == 0u) cbad[u * grid_chunks + c] = red[0] + red[1] + red[2] + red[3];
+}
+
+// A row's numbers from its chunks, one lane per row; a row whose filter is outside the set is refused here.
+__global__ __launch_bounds__(256) void fir_totals_kernel(const uint32_t *__restrict__ len, uint64_t row_stride, uint32_t n_rows,
+                                                         const uint32_t *__restrict__ filter, const uint32_t *__restrict__ desc,
+                                                         uint32_t n_filters, uint64_t out_stride, const uint32_t *__restrict__ cbad,
+                                                         uint32_t grid_chunks, uint32_t *__restrict__ out_len,
+                                                         uint32_t *__restrict__ nonfinite)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * 256u + threadIdx.x;
+    if (u >= n_rows) return;
+    FirFilter f;
+    if (!fir_filter(filter, desc, n_filters, u, f)) {
+        if (out_len) out_len[u] = 0xFFFFFFFFu;
+        if (nonfinite) nonfinite[u] = 0u;
+        return;
+    }
+    uint64_t n, n_out;
+    fir_row(len, row_stride, out_stride, u, f, n, n_out);
+    uint64_t chunks = (n_out + FIR_CHUNK - 1u) / FIR_CHUNK;
+    chunks = n == 0 ? 0u : (chunks ? chunks : 1u);
+    uint32_t b = 0u;
+    for (uint64_t c = 0; c < chunks; ++c) b += cbad[u * grid_chunks + c];
+    if (out_len) out_len[u] = (uint32_t)n_out;
+    if (nonfinite) nonfinite[u] = b;
+}
+
+}  // namespace
+
+uint64_t fir_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t tail_max)
+{
+    if (row_stride == 0) return 0;
+    // (a row holds fewer than 2^32 samples: len is 32 bits wide)
+    const uint64_t full = (row_stride < 0xFFFFFFFFull ? row_stride : 0xFFFFFFFFull) + tail_max;
+    const uint64_t longest = full < out_stride ? full : out_stride;
+    const uint64_t chunks = (longest + FIR_CHUNK - 1u) / FIR_CHUNK;
+    return chunks ? chunks : 1u;
+}
+
+hipError_t launch_fir(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, const uint32_t *filter,
+                      const double *taps, const uint32_t *desc, uint32_t n_filters, uint32_t grid_chunks, float *out,
+                      uint64_t out_stride, uint32_t *cbad, hipStream_t stream)
+{
+    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
+    if (workgroups == 0) return hipSuccess;
+    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
+                     ((row_stride | out_stride) & 3u) == 0;
+    if (vec)
+        hipLaunchKernelGGL(fir_kernel<true>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, rows, row_stride, len, n_rows,
+                           filter, taps, desc, n_filters, grid_chunks, out, out_stride, cbad);
+    else
+        hipLaunchKernelGGL(fir_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, rows, row_stride, len, n_rows,
+                           filter, taps, desc, n_filters, grid_chunks, out, out_stride, cbad);
+    return hipGetLastError();
+}
+
+hipError_t launch_fir_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, const uint32_t *filter, const uint32_t *desc,
+                             uint32_t n_filters, uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                             uint32_t *nonfinite, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(fir_totals_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, stream, len, row_stride, n_rows, filter, desc,
+                       n_filters, out_stride, cbad, grid_chunks, out_len, nonfinite);
+    return hipGetLastError();
+}
+
+}  // namespace grail

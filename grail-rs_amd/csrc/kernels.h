@@ -233,4 +233,21 @@ hipError_t launch_resample_totals(const uint32_t *len, uint64_t row_stride, uint
                                   uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
                                   uint32_t *nonfinite, hipStream_t stream);
 
+// FIR filtering (fir_kernels.hip): one workgroup per (row, chunk of FIR_CHUNK outputs), grid_chunks = fir_grid_chunks(
+// row_stride, out_stride, the set's longest tail) of them per row; the filtered rows go to out, the count of non-finite
+// input samples a chunk owns to cbad[row * grid_chunks + c] (chunks past a row's last are left unwritten, as is out there,
+// and as is everything of a row whose filter index is outside the set).  taps: device, the set's image as binary64, every
+// filter padded with +0.0 to a multiple of 8; desc: device [n_filters][4] = {first tap, padded taps, taps, origin}
+// (fir_plan.h); filter: device [n_rows] or NULL (filter 0 for every row).
+constexpr uint32_t FIR_CHUNK = 2048;   // == GRAIL_FIR_CHUNK (not part of the contract: no number depends on it)
+uint64_t fir_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t tail_max);
+hipError_t launch_fir(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, const uint32_t *filter,
+                      const double *taps, const uint32_t *desc, uint32_t n_filters, uint32_t grid_chunks, float *out,
+                      uint64_t out_stride, uint32_t *cbad, hipStream_t stream);
+// ... and a row's out_len = min(n + K - 1 - o, out_stride) and count from them, one lane per row (outputs may be NULL);
+// a refused row: 0xFFFFFFFF and 0
+hipError_t launch_fir_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, const uint32_t *filter, const uint32_t *desc,
+                             uint32_t n_filters, uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                             uint32_t *nonfinite, hipStream_t stream);
+
 }  // namespace grail

@@ -1,8 +1,10 @@
 // levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async,
-// grail_loudness_segmented_async and grail_true_peak_async, grail_limit_async, grail_resample_async (checks, the scratch, the launches) and what
+// grail_loudness_segmented_async and grail_true_peak_async, grail_limit_async, grail_resample_async, grail_fir_create / _free /
+// _async (checks, the scratch, the launches) and what
 // grail_batch_mix_leveled and its _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip,
-// loudness_segment_kernels.hip, true_peak_kernels.hip, limiter_kernels.hip and resample_kernels.hip, the gains are level_gains.cpp and the
-// resampler's ratio and table resample_plan.cpp (pure host).  DESIGN.md §4.9, §4.10, §4.11, §4.12, §4.13.
+// loudness_segment_kernels.hip, true_peak_kernels.hip, limiter_kernels.hip, resample_kernels.hip and fir_kernels.hip, the gains are level_gains.cpp,
+// the resampler's ratio and table resample_plan.cpp and a filter set's checks and image fir_plan.cpp (pure host).
+// DESIGN.md §4.9, §4.10, §4.11, §4.12, §4.13, §4.14.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -14,7 +16,8 @@ using namespace grail::host;
 // hop of 100 ms), the chunk maxima and counts that a true-peak call folds (12 B per chunk of 4096 output times) with one
 // block's true peaks for the limited mix, the chunk numbers that a limiter call folds (16 B per group and chunk of 4096
 // samples), the hops' non-finite counts that a segmented loudness call folds (4 B per hop), the chunks' non-finite counts
-// that a resampling call folds (4 B per chunk of 1024 outputs) and the resampler's tables of the last few pairs of rates.
+// that a resampling call folds (4 B per chunk of 1024 outputs), the resampler's tables of the last few pairs of rates,
+// the same counts of a filtering call (4 B per chunk of 2048 outputs) and the filter sets the caller has created.
 struct ResampleTable {
     uint32_t up = 0, down = 0;              // 0: the slot holds no table
     uint64_t used = 0;                      // the call that last asked for it (the oldest is evicted)
@@ -38,6 +41,8 @@ struct LevelState : CtxPart {
     DeviceBuffer<uint32_t> d_rbad;          // resampler chunks: non-finite counts
     ResampleTable tables[4];
     uint64_t table_calls = 0;
+    DeviceBuffer<uint32_t> d_firbad;        // FIR chunks: non-finite counts
+    std::vector<std::unique_ptr<grail_fir>> firs;   // the filter sets alive
 };
 
 namespace {
@@ -427,6 +432,98 @@ int grail_resample_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_str
     const hipError_t e = launch_resample_totals(len_dev, row_stride, n_rows, U, D, out_stride, st->d_rbad.get(), (uint32_t)chunks,
                                                 out_len_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "resample totals kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_fir_create(grail_ctx *ctx, const float *taps, const uint32_t *n_taps, const uint32_t *origin, uint32_t n_filters,
+                     grail_fir **out)
+{
+    // (what is wrong with the arguments is said before what is wrong with the machine)
+    if (!out) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_create: NULL argument");
+    if (const char *why = fir_set_error(taps, n_taps, origin, n_filters))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_fir_create: ") + why);
+    int rc = bind_device(ctx, "grail_fir_create");
+    if (rc) return rc;
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    std::unique_ptr<grail_fir> set(new (std::nothrow) grail_fir());
+    if (!set) return fail(GRAIL_ERR_OUT_OF_MEMORY, "filter set");
+    set->n_filters = n_filters;
+    fir_set_image(taps, n_taps, origin, n_filters, set->image, set->desc, &set->tail_max);
+    HIP_TRY(upload(set->d_taps, set->image.data(), set->image.size(), ctx->stream));
+    HIP_TRY(upload(set->d_desc, set->desc.data(), set->desc.size(), ctx->stream));
+    *out = set.get();
+    st->firs.push_back(std::move(set));
+    return GRAIL_OK;
+}
+
+int grail_fir_free(grail_ctx *ctx, grail_fir *set)
+{
+    if (!set) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_free: ctx is NULL");
+    LevelState *st = static_cast<LevelState *>(ctx->level_state.get());
+    if (st) {
+        for (auto it = st->firs.begin(); it != st->firs.end(); ++it) {
+            if (it->get() != set) continue;
+            // (a kernel or the upload still queued may be reading it)
+            int rc = bind(ctx);
+            if (rc) return rc;
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            st->firs.erase(it);
+            return GRAIL_OK;
+        }
+    }
+    return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_free: not a filter set of this context");
+}
+
+int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                    uint32_t n_rows, const uint32_t *filter_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                    uint32_t *nonfinite_dev)
+{
+    // (what is wrong with the arguments is said before what is wrong with the machine)
+    if (!set) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: set is NULL");
+    if (ctx) {          // (sets are looked up, not looked into: a stale pointer is refused, not read)
+        const LevelState *own = static_cast<const LevelState *>(ctx->level_state.get());
+        bool found = false;
+        if (own)
+            for (const auto &s : own->firs) found = found || s.get() == set;
+        if (!found) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: not a filter set of this context");
+    }
+    if (n_rows && (!len_dev || (row_stride && (!rows_dev || (out_stride && !out_dev)))))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: NULL buffer");
+    // (without a context the set was not looked up and is not looked into: the checks below run with a tail of 0, and the
+    // call ends at bind_device)
+    const uint32_t tail_max = ctx ? set->tail_max : 0u;
+    uint64_t chunks = 0;
+    if (n_rows && row_stride) {
+        if (row_stride > (1ull << 60) / n_rows || out_stride > (1ull << 60) / n_rows)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: the rows span more than 2^60 samples");
+        const uintptr_t in0 = (uintptr_t)rows_dev, in1 = in0 + (uintptr_t)(n_rows * row_stride * 4u);
+        const uintptr_t out0 = (uintptr_t)out_dev, out1 = out0 + (uintptr_t)(n_rows * out_stride * 4u);
+        if (out_stride && in0 < out1 && out0 < in1)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: out_dev overlaps rows_dev (a chunk reads what another would have written)");
+        // (a row holds fewer than 2^32 samples: len is 32 bits wide)
+        const uint64_t longest = std::min<uint64_t>(row_stride, 0xFFFFFFFFull) + tail_max;
+        if (std::min(longest, out_stride) > 0xFFFFFFFFull)
+            return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: a row could hold 2^32 output samples or more (out_len is 32 bits wide)");
+        chunks = fir_grid_chunks(row_stride, out_stride, tail_max);
+        if ((uint64_t)n_rows * chunks > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_async: more than 2^31 chunks");
+    }
+    int rc = bind_device(ctx, "grail_fir_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    if (chunks) {               // (rows of no samples: 0, 0 from the totals alone)
+        if ((rc = st->d_firbad.reserve(ctx->stream, (size_t)n_rows * (size_t)chunks))) return rc;
+        const hipError_t e = launch_fir(rows_dev, row_stride, len_dev, n_rows, filter_dev, set->d_taps.get(), set->d_desc.get(),
+                                        set->n_filters, (uint32_t)chunks, out_dev, out_stride, st->d_firbad.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "fir kernel launch");
+    }
+    if (!out_len_dev && !nonfinite_dev) return GRAIL_OK;
+    const hipError_t e = launch_fir_totals(len_dev, row_stride, n_rows, filter_dev, set->d_desc.get(), set->n_filters, out_stride,
+                                           st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "fir totals kernel launch");
     return GRAIL_OK;
 }
 

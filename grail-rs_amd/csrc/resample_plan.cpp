@@ -7,11 +7,36 @@
 #include <cstdint>
 
 #include "../../include/grail_hip.h"
+#include "fir_plan.h"
+
+namespace grail {
+
+// I0 by its power series: the terms ((y / 2)^k / k!)^2 ascending until one no longer changes the sum
+double bessel_i0(double y)
+{
+    double sum = 1.0, t = 1.0;
+    for (uint32_t k = 1;; ++k) {
+        t = t * (y / 2.0) / (double)k;
+        const double next = sum + t * t;
+        if (next == sum) return sum;
+        sum = next;
+    }
+}
+
+// sin(pi a) / (pi a), 1 at 0
+double sinc_pi(double a)
+{
+    constexpr double PI = 3.14159265358979323846;
+    return a == 0.0 ? 1.0 : std::sin(PI * a) / (PI * a);
+}
+
+}  // namespace grail
 
 namespace {
 
+using grail::bessel_i0;
+
 constexpr double RESAMPLE_BETA = 8.0;
-constexpr double RESAMPLE_PI = 3.14159265358979323846;
 
 uint32_t gcd32(uint32_t a, uint32_t b)
 {
@@ -35,24 +60,12 @@ bool ratio(uint32_t rate_in, uint32_t rate_out, uint32_t *U, uint32_t *D, uint32
     return true;
 }
 
-// I0 by its power series: the terms ((y / 2)^k / k!)^2 ascending until one no longer changes the sum
-double bessel_i0(double y)
-{
-    double sum = 1.0, t = 1.0;
-    for (uint32_t k = 1;; ++k) {
-        t = t * (y / 2.0) / (double)k;
-        const double next = sum + t * t;
-        if (next == sum) return sum;
-        sum = next;
-    }
-}
-
 // N(j) = llrint(H(|j|) * 2^26): |j| makes the table even by construction
 int32_t numerator(int64_t j, uint32_t U, double f, double W, double i0_beta)
 {
     const double x = (double)(j < 0 ? -j : j) / (double)U;
     const double a = f * x;
-    const double sinc = a == 0.0 ? 1.0 : std::sin(RESAMPLE_PI * a) / (RESAMPLE_PI * a);
+    const double sinc = grail::sinc_pi(a);
     const double r = x / W;
     const double under = 1.0 - r * r;
     const double window = bessel_i0(RESAMPLE_BETA * std::sqrt(under > 0.0 ? under : 0.0)) / i0_beta;

@@ -81,6 +81,7 @@ EXPORTS = [
     "grail_batch_mix_leveled_limited",
     "grail_limit_ceiling", "grail_limit_async",
     "grail_resample_ratio", "grail_resample_coefficients", "grail_resample_len", "grail_resample_async",
+    "grail_fir_len", "grail_fir_design", "grail_fir_create", "grail_fir_free", "grail_fir_async",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -98,6 +99,9 @@ LIMIT_CHUNK = 4096                              # GRAIL_LIMIT_CHUNK: one workgro
 RESAMPLE_ZERO_CROSSINGS = 24                    # GRAIL_RESAMPLE_ZERO_CROSSINGS: per side, at the lower of the two rates
 RESAMPLE_TABLE_MAX = 32768                      # GRAIL_RESAMPLE_TABLE_MAX: up * taps of a supported pair of rates
 RESAMPLE_CHUNK = 1024                           # GRAIL_RESAMPLE_CHUNK: one workgroup's outputs (no number depends on it)
+FIR_TAPS_MAX = 4096                             # GRAIL_FIR_TAPS_MAX: the taps of one filter
+FIR_FILTERS_MAX = 64                            # GRAIL_FIR_FILTERS_MAX: the filters of one set
+FIR_CHUNK = 2048                                # GRAIL_FIR_CHUNK: one workgroup's outputs (no number depends on it)
 
 
 class GrailError(RuntimeError):
@@ -375,6 +379,11 @@ def load():
     L.grail_resample_coefficients.argtypes = [C.c_uint32, C.c_uint32, vp, C.c_uint32]
     L.grail_resample_len.argtypes = [u64, C.c_uint32, C.c_uint32, vp]
     L.grail_resample_async.argtypes = [vp, vp, u64, vp, C.c_uint32, C.c_uint32, C.c_uint32, vp, u64, vp, vp]
+    L.grail_fir_len.argtypes = [u64, C.c_uint32, C.c_uint32, vp]
+    L.grail_fir_design.argtypes = [C.c_uint32, C.c_double, C.c_double, C.c_uint32, vp]
+    L.grail_fir_create.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+    L.grail_fir_free.argtypes = [vp, vp]
+    L.grail_fir_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, vp, u64, vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -739,6 +748,21 @@ def resample_len(n, rate_in, rate_out):
     out = C.c_uint64(0)
     _check(load().grail_resample_len(n, rate_in, rate_out, C.addressof(out)))
     return out.value
+
+
+def fir_len(n, n_taps, origin):
+    """grail_fir_len (pure host): 0 for n = 0, else n + n_taps - 1 - origin, the length of a row of n samples filtered."""
+    out = C.c_uint64(0)
+    _check(load().grail_fir_len(n, n_taps, origin, C.addressof(out)))
+    return out.value
+
+
+def fir_design(sample_rate, lo_hz, hi_hz, n_taps):
+    """grail_fir_design (pure host): float32[n_taps] of the Kaiser-windowed band-pass lo_hz .. hi_hz at sample_rate (n_taps
+    odd; lo_hz = 0: a low-pass, hi_hz = sample_rate / 2: a high-pass).  The origin to use is (n_taps - 1) // 2."""
+    taps = np.zeros(max(int(n_taps), 1), dtype=np.float32)
+    _check(load().grail_fir_design(sample_rate, lo_hz, hi_hz, n_taps, taps.ctypes.data))
+    return taps
 
 
 def true_peak_limit_gains(true_peak, item_rows, item_gains, ceiling_db, n_rows=None):
@@ -1208,6 +1232,45 @@ class Context:
         d = [self.device_alloc(max(n_rows, 1) * 4) for _ in res]
         try:
             self.resample_async(rows_dev, row_stride, len_dev, n_rows, rate_in, rate_out, out_dev, out_stride, *d)
+            for dst, src in zip(res, d):
+                self.d2h(dst, src, n_rows * 4)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return tuple(r[:n_rows] for r in res)
+
+    def fir_create(self, filters):
+        """grail_fir_create: a set of filters on this context's device.  filters: a list of (taps float32[K], origin), one per
+        filter.  Returns the set's handle, for fir / fir_async / fir_free; sets still alive go with the context."""
+        taps = [np.ascontiguousarray(t, dtype=np.float32).reshape(-1) for t, _ in filters]
+        flat = np.concatenate(taps) if taps else np.zeros(0, np.float32)
+        n_taps = np.array([len(t) for t in taps], dtype=np.uint32)
+        origin = np.array([o for _, o in filters], dtype=np.uint32)
+        out = C.c_void_p(None)
+        _check(load().grail_fir_create(self.handle, flat.ctypes.data, n_taps.ctypes.data, origin.ctypes.data, len(filters),
+                                       C.addressof(out)))
+        return out
+
+    def fir_free(self, fir_set):
+        """grail_fir_free: waits for the context's stream, then releases the set."""
+        _check(load().grail_fir_free(self.handle, fir_set))
+
+    def fir_async(self, fir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, out_dev, out_stride, out_len_dev=None,
+                  nonfinite_dev=None):
+        """grail_fir_async: the rows filtered into out_dev (must not overlap rows_dev), row u with filter filter_dev[u] of the
+        set (a DEVICE array of uint32; None: filter 0 for every row).  Results are DEVICE arrays [n_rows] (either may be
+        None), queued on the context's stream."""
+        _check(load().grail_fir_async(self.handle, fir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, out_dev, out_stride,
+                                      out_len_dev, nonfinite_dev))
+
+    def fir(self, fir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, out_dev, out_stride):
+        """fir_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a row whose
+        filter index is outside the set: (LIMIT_REFUSED, 0)."""
+        res = [np.zeros(max(n_rows, 1), dtype=np.uint32) for _ in range(2)]
+        d = [self.device_alloc(max(n_rows, 1) * 4) for _ in res]
+        try:
+            self.fir_async(fir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, out_dev, out_stride, *d)
             for dst, src in zip(res, d):
                 self.d2h(dst, src, n_rows * 4)
         finally:

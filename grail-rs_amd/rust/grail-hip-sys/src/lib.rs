@@ -122,6 +122,16 @@ pub struct grail_stream {
 pub struct grail_node {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct grail_fir {
+    _private: [u8; 0],
+}
+
+/// The most taps of one filter and the most filters of one set (`grail_fir_create`).
+pub const GRAIL_FIR_TAPS_MAX: u32 = 4096;
+pub const GRAIL_FIR_FILTERS_MAX: u32 = 64;
+/// The outputs of one workgroup of `grail_fir_async` (no number depends on it).
+pub const GRAIL_FIR_CHUNK: u32 = 2048;
 
 extern "C" {
     pub fn grail_abi_version() -> c_int;
@@ -283,6 +293,14 @@ extern "C" {
     pub fn grail_resample_len(n: u64, rate_in: u32, rate_out: u32, n_out: *mut u64) -> c_int;
     pub fn grail_resample_async(ctx: *mut grail_ctx, rows_dev: *const f32, row_stride: u64, len_dev: *const u32, n_rows: u32,
         rate_in: u32, rate_out: u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
+        nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_fir_len(n: u64, n_taps: u32, origin: u32, n_out: *mut u64) -> c_int;
+    pub fn grail_fir_design(sample_rate: u32, lo_hz: f64, hi_hz: f64, n_taps: u32, taps: *mut f32) -> c_int;
+    pub fn grail_fir_create(ctx: *mut grail_ctx, taps: *const f32, n_taps: *const u32, origin: *const u32, n_filters: u32,
+        out: *mut *mut grail_fir) -> c_int;
+    pub fn grail_fir_free(ctx: *mut grail_ctx, set: *mut grail_fir) -> c_int;
+    pub fn grail_fir_async(ctx: *mut grail_ctx, set: *const grail_fir, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, filter_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
         nonfinite_dev: *mut u32) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;

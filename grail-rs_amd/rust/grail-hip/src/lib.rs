@@ -586,6 +586,90 @@ impl Gpu {
         Ok((out, bad))
     }
 
+    /// A set of FIR filters on this device (`grail_fir_create`), for [`Gpu::fir`]: `(taps, origin)` per filter, `origin` the tap
+    /// that sits at time zero (0: causal; `(taps.len() - 1) / 2`: linear phase, zero delay).  Released when dropped.
+    pub fn fir_set(&self, filters: &[(Vec<f32>, u32)]) -> Result<FirSet<'_>, Error> {
+        let taps: Vec<f32> = filters.iter().flat_map(|(t, _)| t.iter().copied()).collect();
+        let n_taps: Vec<u32> = filters.iter().map(|(t, _)| t.len() as u32).collect();
+        let origin: Vec<u32> = filters.iter().map(|(_, o)| *o).collect();
+        let tail = filters.iter().map(|(t, o)| (t.len() as u64).saturating_sub(1 + *o as u64)).max().unwrap_or(0);
+        let mut set: *mut sys::grail_fir = std::ptr::null_mut();
+        check(unsafe {
+            sys::grail_fir_create(self.ctx, taps.as_ptr(), n_taps.as_ptr(), origin.as_ptr(), filters.len() as u32, &mut set)
+        })?;
+        Ok(FirSet { gpu: self, set, tail })
+    }
+
+    /// Rows of samples filtered on the device (`grail_fir_async`; the contract is the header's section "levels, continued: FIR
+    /// filtering"), row `i` with filter `which[i]` of the set (`None`: filter 0 for every row).  A row of `n` samples gives
+    /// `n + taps - 1 - origin`: the tail rings out.  Returns the filtered rows and, per row, the count of non-finite input
+    /// samples (they enter as +0.0); a row whose index is outside the set comes back empty.  A filter overshoots: limit or
+    /// measure after filtering.
+    pub fn fir(&self, set: &FirSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        let n = rows.len();
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        if n == 0 {
+            return Ok((out, bad));
+        }
+        if which.map_or(false, |w| w.len() != n) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "fir: one filter index per row".to_string() });
+        }
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let out_stride = ((longest + set.tail as usize + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 6] = [std::ptr::null_mut(); 6];
+            let sizes = [n * stride * 4, n * out_stride * 4, n * 4, n * 4, n * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..6 {
+                if r.is_ok() && (k < 5 || which.is_some()) {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if let (true, Some(w)) = (r.is_ok(), which) {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[5], w.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_fir_async(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
+                                               d[5] as *const u32, d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                               d[4] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 && out_lens[i] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(self.ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad))
+    }
+
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
     /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
     /// non-finite samples.  One lane filters one row: many rows fill the device.
@@ -763,6 +847,41 @@ pub fn resample_len(n: u64, rate_in: u32, rate_out: u32) -> Result<u64, Error> {
     let mut n_out = 0u64;
     check(unsafe { sys::grail_resample_len(n, rate_in, rate_out, &mut n_out) })?;
     Ok(n_out)
+}
+
+/// A set of FIR filters resident on a [`Gpu`]'s device ([`Gpu::fir_set`]); `grail_fir_free` when dropped.
+pub struct FirSet<'a> {
+    gpu: &'a Gpu,
+    set: *mut sys::grail_fir,
+    tail: u64,
+}
+
+impl Drop for FirSet<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_fir_free(self.gpu.ctx, self.set);
+        }
+    }
+}
+
+/// The most taps of a filter, the most filters of a set (`GRAIL_FIR_TAPS_MAX`, `GRAIL_FIR_FILTERS_MAX`).
+pub const FIR_TAPS_MAX: u32 = sys::GRAIL_FIR_TAPS_MAX;
+pub const FIR_FILTERS_MAX: u32 = sys::GRAIL_FIR_FILTERS_MAX;
+
+/// The length of a row of `n` samples filtered: 0 for `n` = 0, else `n + n_taps - 1 - origin` (`grail_fir_len`; pure host).
+pub fn fir_len(n: u64, n_taps: u32, origin: u32) -> Result<u64, Error> {
+    let mut n_out = 0u64;
+    check(unsafe { sys::grail_fir_len(n, n_taps, origin, &mut n_out) })?;
+    Ok(n_out)
+}
+
+/// The Kaiser-windowed band-pass `lo_hz .. hi_hz` at `sample_rate`, `n_taps` odd (`grail_fir_design`; pure host): the taps and
+/// the origin, `(n_taps - 1) / 2`, that gives the filter zero delay.  `lo_hz` = 0: a low-pass; `hi_hz` = `sample_rate / 2`: a
+/// high-pass.
+pub fn fir_design(sample_rate: u32, lo_hz: f64, hi_hz: f64, n_taps: u32) -> Result<(Vec<f32>, u32), Error> {
+    let mut taps = vec![0f32; n_taps.max(1) as usize];
+    check(unsafe { sys::grail_fir_design(sample_rate, lo_hz, hi_hz, n_taps, taps.as_mut_ptr()) })?;
+    Ok((taps, (n_taps - 1) / 2))
 }
 
 /// The `f32` that a ceiling in dBTP is to [`Gpu::limit`] (`grail_limit_ceiling`; pure host).

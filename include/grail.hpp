@@ -15,9 +15,11 @@
 // No arithmetic lives here; everything forwards to libgrail_hip.so.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "grail_hip.h"
@@ -131,6 +133,60 @@ struct Limited {
 
 // The float that a ceiling in dBTP is to Gpu::limit (grail_limit_ceiling)
 inline float limit_ceiling(float ceiling_db) { return grail_limit_ceiling(ceiling_db); }
+
+// One FIR filter: its taps and the tap that sits at time zero (0: causal; (K - 1) / 2: linear phase, zero delay)
+struct Fir {
+    std::vector<float> taps;
+    uint32_t origin = 0;
+};
+
+// The Kaiser-windowed band-pass lo_hz .. hi_hz at sample_rate, n_taps odd (grail_fir_design; lo_hz = 0: a low-pass,
+// hi_hz = sample_rate / 2: a high-pass), with the origin that gives it zero delay
+inline Fir fir_design(uint32_t sample_rate, double lo_hz, double hi_hz, uint32_t n_taps = 255)
+{
+    Fir f;
+    f.taps.resize(n_taps ? n_taps : 1);
+    check(grail_fir_design(sample_rate, lo_hz, hi_hz, n_taps, f.taps.data()));
+    f.origin = (n_taps - 1) / 2;
+    return f;
+}
+
+// A set of filters on a Gpu's device (grail_fir_create), made by Gpu::fir_set: move-only, released with grail_fir_free.
+// It must not outlive its Gpu.
+class FirSet {
+public:
+    FirSet(grail_ctx *ctx, const std::vector<Fir> &filters) : ctx_(ctx)
+    {
+        std::vector<float> taps;
+        std::vector<uint32_t> n_taps, origin;
+        for (const Fir &f : filters) {
+            taps.insert(taps.end(), f.taps.begin(), f.taps.end());
+            n_taps.push_back((uint32_t)f.taps.size());
+            origin.push_back(f.origin);
+            tail_ = std::max<uint64_t>(tail_, f.taps.size() > f.origin ? f.taps.size() - 1 - f.origin : 0);
+        }
+        check(grail_fir_create(ctx, taps.data(), n_taps.data(), origin.data(), (uint32_t)filters.size(), &set_));
+    }
+    ~FirSet() { grail_fir_free(ctx_, set_); }
+    FirSet(FirSet &&o) noexcept : ctx_(o.ctx_), set_(std::exchange(o.set_, nullptr)), tail_(o.tail_) {}
+    FirSet &operator=(FirSet &&o) noexcept
+    {
+        if (this != &o) {
+            grail_fir_free(ctx_, set_);
+            ctx_ = o.ctx_, set_ = std::exchange(o.set_, nullptr), tail_ = o.tail_;
+        }
+        return *this;
+    }
+    FirSet(const FirSet &) = delete;
+    FirSet &operator=(const FirSet &) = delete;
+    const grail_fir *get() const { return set_; }
+    uint64_t tail() const { return tail_; }     // the longest n_taps - 1 - origin: how far a row rings out
+
+private:
+    grail_ctx *ctx_ = nullptr;
+    grail_fir *set_ = nullptr;
+    uint64_t tail_ = 0;
+};
 
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
@@ -484,6 +540,51 @@ public:
             rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)out_lens[i] * 4);
         }
         for (void *p : {d_rows, d_out, d_len, d_out_len})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
+    // A set of filters for fir(), resident on this device
+    FirSet fir_set(const std::vector<Fir> &filters) const { return FirSet(ctx_, filters); }
+
+    // Rows of samples filtered on the device (grail_fir_async; the contract is the header's section "levels, continued: FIR
+    // filtering"), row i with filter which[i] of the set (which empty: filter 0 for every row).  ring_out: a row of n samples
+    // gives n + K - 1 - origin, the filter's tail included; otherwise the rows come back as long as they came.  A row whose
+    // index is outside the set comes back empty.  The output's peak can exceed the input's: limit or measure afterwards.
+    std::vector<std::vector<float>> fir(const FirSet &set, const std::vector<std::vector<float>> &rows,
+                                        const std::vector<uint32_t> &which = {}, bool ring_out = true) const
+    {
+        const uint32_t n = (uint32_t)rows.size();
+        if (!which.empty() && which.size() != rows.size()) throw Error(GRAIL_ERR_INVALID_ARG, "fir: one filter index per row");
+        size_t longest = 0;
+        for (const auto &r : rows) longest = r.size() > longest ? r.size() : longest;
+        const uint64_t longest_out = longest + (ring_out ? set.tail() : 0);
+        const uint64_t stride = longest ? (longest + 63) / 64 * 64 : 64, out_stride = longest_out ? (longest_out + 63) / 64 * 64 : 64;
+        std::vector<std::vector<float>> out(n);
+        if (!n) return out;
+        std::vector<uint32_t> lens(n), out_lens(n);
+        for (uint32_t i = 0; i < n; ++i) lens[i] = (uint32_t)rows[i].size();
+        void *d_rows = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr, *d_which = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4, &d_rows);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_out_len);
+        if (!rc && !which.empty()) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_which);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_rows + (size_t)i * stride, rows[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc && d_which) rc = grail_memcpy_h2d(ctx_, d_which, which.data(), (size_t)n * 4);
+        if (!rc) rc = grail_fir_async(ctx_, set.get(), (const float *)d_rows, stride, (const uint32_t *)d_len, n, (const uint32_t *)d_which,
+                                      (float *)d_out, out_stride, (uint32_t *)d_out_len, nullptr);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)n * 4);
+        for (uint32_t i = 0; !rc && i < n; ++i) {
+            if (!out_lens[i] || out_lens[i] == GRAIL_LIMIT_REFUSED) continue;
+            const size_t keep = ring_out ? out_lens[i] : std::min<size_t>(out_lens[i], lens[i]);
+            out[i].resize(keep);
+            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, keep * 4);
+        }
+        for (void *p : {d_rows, d_out, d_len, d_out_len, d_which})
             if (p) grail_device_free(ctx_, p);
         check(rc);
         return out;

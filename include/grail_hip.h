@@ -1013,6 +1013,79 @@ int grail_resample_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_str
                          uint32_t rate_in, uint32_t rate_out, float *out_dev, uint64_t out_stride,
                          uint32_t *out_len_dev, uint32_t *nonfinite_dev);
 
+/* ---- levels, continued: FIR filtering --------------------------------------------------------------------------------------------
+ * Every stage above shapes the sound in a fixed way; this one applies the filter the caller chose: a telephone band on
+ * the tracks a lower rate produced, a high-pass under a voice, a de-emphasis curve, the first milliseconds of a room.  A
+ * FIR filter, because time is parallel (a lone long track fills the device) and because the contract can be exact: a
+ * binary32 tap times a binary32 sample has 48 significant bits and is exact in binary64, so a fused multiply-add and a
+ * multiply followed by an add give the same bits (the argument of the true-peak section).  All arithmetic is IEEE binary64.
+ * FILTER.  K taps h[0 .. K-1] in binary32 and an origin o: 1 <= K <= GRAIL_FIR_TAPS_MAX = 4096, 0 <= o <= K - 1, every
+ * tap finite.  o is the tap that sits at time zero: o = 0 for a causal impulse response, o = (K - 1) / 2 for a
+ * linear-phase design with zero delay.
+ * SAMPLES.  For a row of n = min(len[u], row_stride) samples:
+ *   - v[t] = (double)x[t] for 0 <= t < n and +0.0 outside; a sample that is not finite (|x| > FLT_MAX or NaN) is counted
+ *     once and enters as +0.0; memory between n and row_stride is never looked at, whatever it holds.
+ *   - n_out = 0 when n = 0, otherwise n_out = min(n + K - 1 - o, out_stride): the tail rings out.
+ *   - For output m = 0 .. n_out - 1: acc = +0.0; for k = 0 .. K - 1 ascending acc = acc + (double)h[k] * v[m + o - k];
+ *     y[m] = (float)acc, one rounding.  The result may be infinite and is not counted.
+ *   - out between n_out and out_stride is never written.  out_len[u] = n_out; nonfinite[u] = the count over all n
+ *     samples (also where out_stride cut the output short).
+ * Nothing above depends on chunking, layout, alignment, the rows around or the launch: out and the results are a pure
+ * function of the row's samples and its filter.  No float atomics.
+ * h = [1.0] is NOT a copy: -0.0 and non-finite samples come back as +0.0 (acc starts at +0.0, and +0.0 + -0.0 = +0.0).
+ * FILTER SETS.  A call filters rows with the filters of one set, chosen per row.  A set holds 1 <= F <=
+ * GRAIL_FIR_FILTERS_MAX = 64 filters; filter_dev is a device array [n_rows] of indices into it, NULL means filter 0 for
+ * every row.  A row whose index is >= F is refused the way the limiter refuses a ragged group: out_len[u] =
+ * GRAIL_LIMIT_REFUSED = 0xFFFFFFFF, nonfinite[u] = 0, its out row unwritten.
+ * DESIGN.  grail_fir_design makes a Kaiser-windowed band-pass of K taps, K odd, 3 <= K <= 4096, for 0 <= lo < hi <=
+ * rate / 2.  With c = (K - 1) / 2, x = k - c, W = c + 1, beta = 8.0, f_l = lo / rate, f_h = hi / rate:
+ *     h[k] = (float)( I0(beta * sqrt(1 - (x / W)^2)) / I0(beta) * (2 f_h sinc(2 f_h x) - 2 f_l sinc(2 f_l x)) )
+ * sinc and I0 are the resampler's (above).  lo = 0 is a low-pass, hi = rate / 2 a high-pass; the origin to use is c.
+ * The bits come from the C library's sin: the table as grail_fir_design returns it is the contract, as with
+ * grail_kweighting.  With Kaiser's transition width df = (81.3 - 7.95) / (2.285 * 2 pi * (K - 1)) * rate the passband is
+ * flat within 0.001 dB from lo + df to hi - df and the stopband at or below -80 dB outside lo - df .. hi + df.
+ * NOT promised: the output's peak can exceed the input's: limit or measure after filtering, not before. */
+#define GRAIL_FIR_TAPS_MAX 4096
+#define GRAIL_FIR_FILTERS_MAX 64
+/* The outputs of one workgroup's stretch of a row.  Not part of the contract (no number depends on it): it is here so
+ * that tests can aim at the seams. */
+#define GRAIL_FIR_CHUNK 2048
+typedef struct grail_fir grail_fir; /* a set of filters, its taps resident in HBM */
+
+/* Pure host: *n_out = 0 for n = 0, else n + n_taps - 1 - origin, the length of a row of n samples filtered.
+ * GRAIL_ERR_INVALID_ARG, nothing written: n_taps outside 1 .. 4096, origin > n_taps - 1, n_out NULL, a length that does
+ * not fit 64 bits. */
+int grail_fir_len(uint64_t n, uint32_t n_taps, uint32_t origin, uint64_t *n_out);
+/* Pure host: taps[0 .. n_taps - 1] of the band-pass lo_hz .. hi_hz at sample_rate (DESIGN above).
+ * GRAIL_ERR_INVALID_ARG, nothing written: n_taps even or outside 3 .. 4096, sample_rate 0, not 0 <= lo_hz < hi_hz <=
+ * sample_rate / 2, taps NULL. */
+int grail_fir_design(uint32_t sample_rate, double lo_hz, double hi_hz, uint32_t n_taps, float *taps);
+
+/* A set of n_filters filters on ctx's device: taps holds the filters' taps one after another (n_taps[0] of filter 0,
+ * then n_taps[1] of filter 1, ...), n_taps and origin [n_filters].  The set keeps its own copy, as binary64, uploaded on
+ * ctx's stream; the arrays may be reused at once.  GRAIL_ERR_INVALID_ARG, nothing created: a NULL argument, n_filters
+ * outside 1 .. 64, an n_taps outside 1 .. 4096, an origin > n_taps - 1, a tap that is not finite.  These come first;
+ * without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_fir_create(grail_ctx *ctx, const float *taps, const uint32_t *n_taps, const uint32_t *origin,
+                     uint32_t n_filters, grail_fir **out);
+/* Releases a set once everything queued on ctx's stream is through; sets still alive at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: a pointer that is not a live set of this context (another context's, or
+ * one freed before: sets are looked up, not looked into). */
+int grail_fir_free(grail_ctx *ctx, grail_fir *set);
+/* The filter above, queued on ctx's stream like grail_resample_async: rows_dev: device [n_rows][row_stride] (finished
+ * tracks or rendered rows alike); len_dev: device [n_rows]; filter_dev: device [n_rows] or NULL; out_dev: device
+ * [n_rows][out_stride].  Results are DEVICE arrays [n_rows], either may be NULL: out_len, nonfinite.  out_dev must not
+ * overlap rows_dev.  16-byte loads and stores where both bases are 16-byte aligned and both strides multiples of 4,
+ * 4-byte ones otherwise: same bits.  One workgroup takes GRAIL_FIR_CHUNK outputs of one row, so a lone long track fills
+ * the device.  The scratch (4 bytes per row and 2048 outputs) stays with the context, grown and never shrunk, until
+ * grail_destroy.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: set NULL or of another context; a NULL buffer with samples to read or write;
+ * overlapping ranges; strides that allow a row of 2^32 outputs or more; more than 2^31 chunks.  These come first;
+ * without a usable device: GRAIL_ERR_NO_DEVICE.  n_rows = 0 is a success that queues nothing. */
+int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev, uint64_t row_stride,
+                    const uint32_t *len_dev, uint32_t n_rows, const uint32_t *filter_dev,
+                    float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
