@@ -24,8 +24,14 @@ from test_true_peak_host import db
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CHUNK = G.FIR_CHUNK
-TAPS = [1, 2, 7, 8, 9, 64, 255]
+BLOCK = 8                                       # the taps of one step of the kernel's loop, which takes the blocks in pairs
+TAPS = [1, 2, 7, 8, 9, 17, 24, 33, 40, 64, 255]   # 17, 24 and 33, 40: the first and the last tap count of 3 and of 5 blocks
 REFUSED = 0xFFFFFFFF
+
+
+def blocks(K):
+    """the blocks of eight taps that the kernel walks for K taps"""
+    return -(-K // BLOCK)
 
 
 def origins(K):
@@ -129,6 +135,8 @@ def filters_of(K, rng):
 def test_bit_parity_with_the_model(gpu_ctx, dev, K):
     """one call per tap count: a set of its filters, rows of the issue's lengths in the four kinds of content on every filter
     but the cancelling one, which gets the steps"""
+    # an odd count of blocks above one (the pair loop runs, then the tail with the windows swapped) is among the cases
+    assert [blocks(k) for k in (17, 24, 33, 40)] == [3, 3, 5, 5] and {17, 24, 33, 40} <= set(TAPS)
     rng = np.random.default_rng(100 + K)
     filters = filters_of(K, rng)
     rows, which = [], []
@@ -184,11 +192,36 @@ def test_rows_on_different_filters_of_one_set_and_an_index_outside_it(gpu_ctx, d
         gpu_ctx.fir_free(fir_set)
 
 
+def test_a_filter_of_three_blocks_between_one_of_two_and_one_of_five(gpu_ctx, dev):
+    """K = 20 between K = 9 and K = 33 in one set: neighbouring workgroups leave the pair loop after 1, 1 and 2 turns, two of
+    them into the tail for the odd block; rows of CHUNK + 1 and 2 CHUNK + 17 samples on each, in every content"""
+    rng = np.random.default_rng(23)
+    Ks = (9, 20, 33)
+    assert [blocks(K) for K in Ks] == [2, 3, 5] and all(blocks(K) % 2 == 1 and blocks(K) >= 3 for K in Ks[1:])
+    filters = [(random_taps(9, rng), 4), (random_taps(20, rng), 0), (random_taps(33, rng), 32), (cancelling_taps(20, rng), 9),
+               (random_taps(20, rng), 19)]
+    rows, which = [], []
+    for n in (CHUNK + 1, 2 * CHUNK + 17):
+        for f in (0, 1, 2, 4):
+            for x in contents(n, rng):
+                rows.append(x)
+                which.append(f)
+        rows.append(steps(n, rng))
+        which.append(3)
+    fir_set = gpu_ctx.fir_create(filters)
+    try:
+        got = run(gpu_ctx, dev, fir_set, rows, which, tail=32)
+    finally:
+        gpu_ctx.fir_free(fir_set)
+    same(rows, filters, which, got, "2, 3 and 5 blocks")
+
+
 # ---- 3. layout independence ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("K", [7, 64, 255])
+@pytest.mark.parametrize("K", [7, 20, 64, 255])
 def test_every_layout_gives_the_same_bits(gpu_ctx, dev, K):
     """aligned bases and strides that are multiples of 4; bases one float off; odd strides; an out_stride above what the rows
-    need"""
+    need.  K = 20: three blocks, so the tail for an odd block runs after the pair loop in the 4-byte variant too"""
+    assert blocks(20) % 2 == 1 and blocks(20) >= 3
     rng = np.random.default_rng(7 + K)
     filters = [(random_taps(K, rng), o) for o in origins(K)]
     ns = [K - 1, CHUNK - K, CHUNK, CHUNK + 1, 2 * CHUNK + 17, 3]

@@ -208,6 +208,51 @@ def test_a_rows_numbers_do_not_depend_on_its_layout(gpu_ctx, dev, synthetic, lay
         _check_frames(gpu_ctx, synthetic, rows_dev, stride, d_len, len(rows), pos, F, layout)
 
 
+LEVEL_CHUNKS = 8            # level_kernels.hip: a frame is walked in steps of eight chunks of 256 samples, what is left in one
+#                             step of 2, 4 or 8 slots
+
+
+def level_steps(n, F):
+    """the steps level_frames_kernel takes over a row of n samples in frames of F: {"full", "tail2", "tail4", "tail8"}"""
+    taken = set()
+    for start in range(0, n, F):
+        end = min(start + F, n)
+        chunks = (end + 255) // 256 - start // 256
+        if chunks >= LEVEL_CHUNKS:
+            taken.add("full")
+        left = chunks % LEVEL_CHUNKS
+        if left:
+            taken.add("tail8" if left > 4 else "tail4" if left > 2 else "tail2")
+    return taken
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+def test_frames_whose_last_step_is_of_every_size(gpu_ctx, dev, offset):
+    """rows of 1 to 17 chunks as one frame each, with 16-byte loads and (the base one float off) with 4-byte ones: every
+    number of chunks left over after the steps of eight, 1 to 7, meets the step of its size; LENGTHS x FRAMES leave a frame
+    of 5 to 7 chunks past a multiple of eight out"""
+    F = 65536
+    assert not any("tail8" in level_steps(n, f) for n in LENGTHS for f in FRAMES)
+    lengths = [256 * k - 3 for k in range(1, 18)]
+    assert [((n + 255) // 256) % LEVEL_CHUNKS for n in lengths] == [1, 2, 3, 4, 5, 6, 7, 0, 1, 2, 3, 4, 5, 6, 7, 0, 1]
+    assert set().union(*(level_steps(n, F) for n in lengths)) == {"full", "tail2", "tail4", "tail8"}
+    assert {"tail8", "full"} <= level_steps(lengths[12], F) and level_steps(lengths[4], F) == {"tail8"}
+    rng = np.random.default_rng(88)
+    rows = [_awkward(rng, n) for n in lengths]
+    stride = (max(lengths) + 63) // 64 * 64
+    pos = list(range(len(rows)))
+    rows_dev, d_len, _ = _place(gpu_ctx, dev, rows, pos, len(rows), stride, offset)
+    fs, fp = gpu_ctx.frame_levels(rows_dev, stride, d_len, len(rows), F, fill=CANARY)
+    sumsq, peak, bad = gpu_ctx.levels(rows_dev, stride, d_len, len(rows))
+    assert fs.shape == (len(rows), 1)
+    for i, x in enumerate(rows):
+        ws, wp, _ = frame_model(x, F)
+        assert same_bits(fs[i], ws) and same_bits(fp[i], wp), (offset, i, len(x))
+        w = row_model(x)
+        assert same_bits(sumsq[i:i + 1], np.array([w[0]])) and peak[i] == w[1] and bad[i] == w[2], (offset, i, len(x))
+    assert bad.sum() > 20
+
+
 @pytest.mark.parametrize("others", [1, 7, 3000])
 def test_a_rows_numbers_do_not_depend_on_the_rows_around_it(gpu_ctx, dev, synthetic, others):
     """the same rows scattered among 1, 7 and 3 000 other rows (12 GB of them in the last case: the million-sample row

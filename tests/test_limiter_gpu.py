@@ -20,7 +20,9 @@ from test_true_peak_host import db, true_peak_model
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = G.LIMIT_CHUNK
-ELLS = [0, 1, 6, 10]
+ELLS = list(range(11))
+SUM_LOG2 = 7                # limiter_kernels.hip's LIMIT_SUM_LOG2 (test_kernel_paths_host.py): the deficits of 2^7 minima are summed in
+#                             32 bits, the L >> 7 pieces of a longer window in 64 bits at the apply
 
 
 def _quiet(rng, n, scale=0.02):
@@ -113,6 +115,56 @@ def test_short_rows(gpu_ctx, dev, ell):
     d_len = dev.up(np.zeros(3, np.uint32))
     min_gain, n_limited, bad = gpu_ctx.limit(None, 0, d_len, 3, c, ell, None, 0)
     assert np.all(min_gain == 1) and not n_limited.any() and not bad.any()
+
+
+# ---- the sum of the deficits at its bound ----------------------------------------------------------------------------------
+_held = {}
+
+
+def _held_at_zero(ell):
+    """(row, c, what the model says of it), once per ell: quiet noise of T + 2 L + 40 samples with a run of 2 L + 30 samples
+    of +-3e38 (finite, alternating in sign) from T - L - 5 on, across the chunk seam: q = 0 for longer than two windows, so
+    every minimum of a whole window is 0, its deficits sum to L Q, and the gain is 0 for more than a window"""
+    if ell not in _held:
+        L = 1 << ell
+        rng = np.random.default_rng(800 + ell)
+        x = _quiet(rng, T + 2 * L + 40)
+        run = np.full(2 * L + 30, 3e38, np.float32)
+        run[1::2] = -run[1::2]
+        x[T - L - 5:T - L - 5 + len(run)] = run
+        assert np.all(np.isfinite(x)) and T - L - 5 + len(run) > T + L
+        x.setflags(write=False)
+        c = np.float32(0.25)
+        _held[ell] = (x, c, limiter_model([x], c, ell, curves=True))
+    return _held[ell]
+
+
+@pytest.mark.parametrize("ell", [7, 8, 9, 10])
+def test_a_window_held_at_gain_zero(gpu_ctx, dev, ell):
+    """the deficits of a whole window at their largest, L Q: at ell = 7 the 32-bit sum holds 2^7 deficits of 2^24 (2^31, what
+    LIMIT_SUM_LOG2 is sized for), at ell = 8, 9 and 10 the apply adds 2, 4 and 8 such pieces in 64 bits"""
+    L = 1 << ell
+    x, c, want = _held_at_zero(ell)
+    out, min_gain, n_limited, bad, ((q, S, g),) = want
+    assert ell >= SUM_LOG2 and L >> SUM_LOG2 == (1, 2, 4, 8)[ell - 7]
+    assert min_gain[0] == 0.0 and bad[0] == 0 and np.count_nonzero(out[0] == 0) > 2 * L
+    assert S.min() == 0 and np.count_nonzero(S == 0) > L                   # the sum of the deficits reached L Q, its bound
+    assert n_limited[0] > 4 * L and np.all(np.abs(out[0]) <= c)
+    _same([x], _run(gpu_ctx, dev, [x], c, ell), want, f"L = {L}")
+
+
+@pytest.mark.parametrize("layout", ["aligned", "offset1"])
+def test_a_window_held_at_gain_zero_by_the_third_member_of_a_group(gpu_ctx, dev, layout):
+    """group = 3 at ell = 7: the members' q's are folded by minimum twice; the run is in the last member, the others are
+    quiet and come out at gain zero where it is"""
+    ell = SUM_LOG2
+    x, c, alone = _held_at_zero(ell)
+    rng = np.random.default_rng(807)
+    rows = [_quiet(rng, len(x)), _quiet(rng, len(x)), x, _quiet(rng, 900), _seam_row(rng, 900, 1 << ell), _quiet(rng, 900)]
+    want = limiter_model(rows, c, ell, group=3)
+    assert want[1][0] == 0.0 and want[3][0] == 0 and all(np.count_nonzero(want[0][j] == 0) > 2 << ell for j in range(3))
+    assert want[2][0] >= alone[2][0] and 0 < want[1][1] < 1
+    _same(rows, _run(gpu_ctx, dev, rows, c, ell, group=3, **({} if layout == "aligned" else dict(in_offset=1))), want, layout)
 
 
 # ---- the division ------------------------------------------------------------------------------------------------------------

@@ -170,6 +170,23 @@ def test_a_rows_numbers_do_not_depend_on_its_layout(gpu_ctx, dev, rows48k, layou
     check_rows(measure(gpu_ctx, dev, rows_dev, stride, d_len, len(rows), rate), model, pos, layout)
 
 
+@pytest.mark.parametrize("offset", [0, 1])
+def test_hops_that_end_off_a_multiple_of_eight_under_either_kind_of_load(gpu_ctx, dev, offset):
+    """22 050 Hz: H = 2 205, so a hop ends at every residue of 8 within a tile of 64 samples and the samples of a run past
+    its last whole eight are filtered one by one; rows48k (H = 4 800 = 75 tiles) never leaves the unrolled loop, so the
+    layouts with 4-byte loads above do not reach this"""
+    rate = 22050
+    H = rate // 10
+    assert H % 8 != 0 and 4800 % 64 == 0
+    rng = np.random.default_rng(2205 + offset)
+    rows = [_awkward(rng, n) for n in (0, H - 1, 4 * H + 1, 9 * H + 5)]
+    stride = (9 * H + 5 + 63) // 64 * 64
+    rows_dev, d_len, _ = _place(gpu_ctx, dev, rows, [0, 1, 2, 3], 4, stride, offset)
+    model = model_of(rows, rate, G.kweighting(rate))
+    assert [len(m[0]) for m in model] == [0, 0, 4, 9] and sum(m[2] for m in model) > 20
+    check_rows(measure(gpu_ctx, dev, rows_dev, stride, d_len, 4, rate), model, [0, 1, 2, 3], f"offset {offset}")
+
+
 @pytest.mark.parametrize("stride", [96008, 96007])
 def test_a_len_above_row_stride_reads_as_row_stride(gpu_ctx, dev, stride):
     rate = 48000

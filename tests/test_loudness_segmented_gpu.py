@@ -126,6 +126,22 @@ def test_rows_equal_the_segmented_model(gpu_ctx, dev, rate):
     gpu_ctx.sync()
 
 
+def test_a_hop_of_a_multiple_of_four_but_not_of_eight_samples(gpu_ctx, dev):
+    """2 600 Hz: H = 260 keeps the 16-byte loads (H % 4 == 0) and puts the end of the warm-up, 3 H = 780 samples on, 12 into a
+    tile: a run of 12 is one unrolled eight and four samples one by one.  Of RATES only 2 560 has 16-byte loads, and its
+    warm-up and hop end with a tile"""
+    rate = 2600
+    H = rate // 10
+    assert H % 4 == 0 and (3 * H) % 64 % 8 != 0 and [r // 10 % 4 for r in RATES] == [0, 1, 2, 3] and (3 * 256) % 64 == 0
+    S = rows_at(rate)
+    rows, model = S["rows"], S["model"]
+    n = len(rows)
+    stride = (max(len(x) for x in rows) + 63) // 64 * 64
+    rows_dev, d_len, _ = _place(gpu_ctx, dev, rows, list(range(n)), n, stride)
+    check_rows(measure(gpu_ctx, dev, rows_dev, stride, d_len, n, rate), model, list(range(n)), f"rate {rate}")
+    assert [len(m[0]) for m in model] == HOPS and sum(m[2] for m in model) > 100 and model[3][1] > 0
+
+
 @pytest.mark.parametrize("rate", RATES)
 def test_the_first_hops_and_short_rows_are_the_serial_calls(gpu_ctx, dev, rate):
     """hops 0 .. P of every row, and every number of the rows of at most P + 1 hops, equal grail_loudness_async on the

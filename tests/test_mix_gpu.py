@@ -368,6 +368,45 @@ def test_pcm16_frames_interleave(gpu_ctx, dev, n_tracks):
     assert np.array_equal(got, want.astype(np.int16))
 
 
+FRAMES_GRID_CAP = 65536          # launch_pcm16_frames' largest grid (test_kernel_paths_host.py): workgroups of 256 lanes, one element each
+
+
+@pytest.fixture(scope="module")
+def samples_for_two_laps():
+    """2^24 + 262 samples with the contents of test_pcm16_frames_interleave (specials mixed in), made once and never changed"""
+    rng = np.random.default_rng(24)
+    n = 2 * (8_388_608 + 131)
+    x = rng.uniform(-1.5, 1.5, n).astype(np.float32)
+    specials = np.array([np.nan, np.inf, -np.inf, -0.0, 1.0, -1.0, 1.00002, -1.00004, 3e-5, -3e-5], np.float32)
+    mask = rng.random(n) < 0.05
+    x[mask] = specials[rng.integers(0, len(specials), int(mask.sum()))]
+    x.setflags(write=False)
+    return x
+
+
+@pytest.mark.parametrize("n_tracks,n_frames", [(2, 8_388_608 + 131), (3, 5_592_406)])
+def test_pcm16_frames_second_lap_of_the_grid(gpu_ctx, dev, samples_for_two_laps, n_tracks, n_frames):
+    """more elements than the capped grid has lanes: a lane takes a second element, gridDim.x * 256 further on (262 of them,
+    and exactly two).  The whole result against the expression of test_pcm16_frames_interleave"""
+    lanes = FRAMES_GRID_CAP * 256
+    total = n_frames * n_tracks
+    assert total > lanes and total - lanes == (262 if n_tracks == 2 else 2) and total <= len(samples_for_two_laps)
+    tracks = samples_for_two_laps[:total].reshape(n_tracks, n_frames)
+    d_t = dev.up(tracks)
+    d_f = dev.alloc(total * 2)
+    gpu_ctx.memset(d_f, 0x5A, total * 2)
+    gpu_ctx.pcm16_frames_async(d_t, n_frames, n_tracks, n_frames, d_f)
+    gpu_ctx.sync()
+    got = dev.down(d_f, total, np.int16)
+    with np.errstate(invalid="ignore"):
+        v = np.ascontiguousarray(tracks.T).reshape(-1) * np.float32(32767.0)
+        want = np.where(np.isnan(v), 0, np.clip(np.trunc(np.nan_to_num(v, nan=0.0, posinf=1e9, neginf=-1e9)), -32768, 32767)).astype(np.int16)
+    assert np.count_nonzero(want[lanes:]) >= 1                           # (0x5A5A is what an unwritten element would hold)
+    differ = np.flatnonzero(got != want)
+    assert len(differ) == 0, (f"{len(differ)} elements differ, the first at {differ[0]} "
+                              f"({'at or above' if differ[0] >= lanes else 'below'} 2^24): {got[differ[:4]]} for {want[differ[:4]]}")
+
+
 def test_invalid_arguments_leave_the_tracks_unwritten(gpu_ctx, dev):
     L = G.load()
     rng = np.random.default_rng(4)

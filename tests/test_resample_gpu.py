@@ -25,7 +25,21 @@ CHUNK = G.RESAMPLE_CHUNK
 # (48000, 2000) and (50, 3) are beside the issue's pairs: their chunks reach further than LDS holds, so the kernel reads the
 # row itself, with one phase and with three
 PAIRS = [(2, 3), (3, 2), (48000, 16000), (48000, 96000), (44100, 48000), (48000, 44100), (44100, 16000), (48000, 2000), (50, 3)]
+LAYOUT_PAIRS = [(48000, 16000), (44100, 48000), (44100, 16000), (50, 3), (48000, 2000)]
+LDS_MAX, STAGE_SLACK = 65536 - 64, 8             # resample_kernels.hip's RS_LDS_MAX and RS_STAGE_SLACK (test_kernel_paths_host.py)
+VARIANTS = ([("staged", vec, tab) for tab in ("uniform", "lds", "global") for vec in (True, False)] +
+            [("unstaged", vec, tab) for tab in ("uniform", "global") for vec in (True, False)])
 _tables = {}
+
+
+def variant(U, D, P, aligned):
+    """the resample_kernel<STAGED, VEC, TAB> that launch_resample starts for a ratio U / D with P taps a phase; aligned: both
+    bases 16-byte aligned and both strides multiples of 4"""
+    stretch = (U - 1 + (CHUNK - 1) * D) // U + P + STAGE_SLACK
+    staged_bytes, table_bytes = (CHUNK + stretch) * 4, U * (P + 1) * 4
+    staged = staged_bytes <= LDS_MAX
+    tab = "uniform" if U == 1 else ("lds" if staged and staged_bytes + table_bytes <= LDS_MAX else "global")
+    return ("staged" if staged else "unstaged", bool(aligned), tab)
 
 
 def table(pair):
@@ -115,7 +129,17 @@ def test_bit_parity_with_the_model(gpu_ctx, dev, pair):
 
 
 # ---- 2. layout independence ---------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("pair", [(48000, 16000), (44100, 48000), (44100, 16000), (50, 3)])
+def test_the_pairs_and_layouts_reach_every_variant_of_the_kernel():
+    """launch_resample's arithmetic over what the parity test (every pair, aligned) and the layout test (its pairs: aligned,
+    bases one float off, odd strides) pass: all ten variants that can be launched are started by one of them"""
+    reached = {variant(*table(pair)[1:], True) for pair in PAIRS}
+    reached |= {variant(*table(pair)[1:], aligned) for pair in LAYOUT_PAIRS for aligned in (True, False, False)}
+    assert len(VARIANTS) == 10 and reached == set(VARIANTS), sorted(set(VARIANTS) - reached)
+    assert variant(*table((48000, 2000))[1:], False) == ("unstaged", False, "uniform")
+    assert variant(*table((50, 3))[1:], False) == ("unstaged", False, "global") and table((50, 3))[1] == 3
+
+
+@pytest.mark.parametrize("pair", LAYOUT_PAIRS)
 def test_every_layout_gives_the_same_bits(gpu_ctx, dev, pair):
     """aligned bases and strides that are multiples of 4; bases one float off; odd strides and an out_stride above what the
     rows need"""
@@ -153,12 +177,14 @@ def test_nothing_is_written_outside_the_rows_outputs_and_nothing_read_past_their
 
 
 # ---- 4. the clamp ---------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("pair", [(48000, 16000), (44100, 48000), (48000, 2000)])
+@pytest.mark.parametrize("pair", [(48000, 16000), (44100, 48000), (48000, 2000), (50, 3)])
 def test_an_out_stride_below_the_rows_length_gives_the_prefix(gpu_ctx, dev, pair):
     """out_len = out_stride, the samples the prefix of the unclamped result; the non-finite count is that of the whole row,
-    also of the samples whose outputs were cut"""
+    also of the samples whose outputs were cut.  (48000, 2000) and (50, 3) are not staged: a cut row's remaining samples are
+    counted from the row itself, with one phase and with three"""
     rng = np.random.default_rng(13)
-    _, U, D, _ = table(pair)
+    _, U, D, P = table(pair)
+    assert variant(U, D, P, True)[0] == ("unstaged" if pair in ((48000, 2000), (50, 3)) else "staged")
     ns = lengths(pair)
     rows = [contents(pair, ns[9], rng)[3], contents(pair, ns[7], rng)[0], contents(pair, ns[4], rng)[3]]
     rows[0][-5] = np.nan
