@@ -12,7 +12,12 @@
 //
 // Without a sound card time is the audio itself: a line "@1.5 text" arrives once 1.5 s of audio have been rendered, a line
 // without a stamp arrives at once.  After the last line has been spoken the session runs `tail` seconds longer (the
-// reference never ends) and the source is closed.   usage: grail_interactive [chunk_samples] [tail_seconds] < script > out.f32
+// reference never ends) and the source is closed.
+//   usage: grail_interactive [--band LO HI [--taps K]] [chunk_samples] [tail_seconds] < script > out.f32
+// --band LO HI: every pulled chunk goes through a filter stream (the Kaiser-windowed band-pass LO .. HI Hz of
+// grail_fir_design, K taps, 255 unless --taps says otherwise, at its zero-delay origin) before it leaves the device, and when
+// the chain has ended the filter rings out: the output is what grail_fir_async gives for the whole session, K / 2 samples
+// longer than the session.
 // Every phoneme fed is reported on stderr ("fed <phoneme> at <sample>"), so that a test can render the same list with
 // the oracle in one piece and compare bit for bit.
 #include <cstdio>
@@ -57,15 +62,48 @@ std::vector<grail::PhonemeElem> speak(const grail::Voice &voice, const std::stri
 
 int main(int argc, char **argv)
 {
-    const uint32_t chunk = argc > 1 ? (uint32_t)std::strtoul(argv[1], nullptr, 10) : 441;
-    const double tail = argc > 2 ? std::strtod(argv[2], nullptr) : 1.0;
-    if (chunk == 0 || !(tail >= 0.0)) {        // (a chunk of 0 samples — or text strtoul makes 0 of — would never feed the stream)
-        std::fprintf(stderr, "usage: grail_interactive [samples per pull >= 1 (default 441)] [seconds of tail >= 0 (default 1)]\n");
+    std::vector<const char *> plain;
+    double lo = -1.0, hi = -1.0;
+    long taps = 0;
+    bool usage = false;
+    for (int i = 1; i < argc; ++i) {
+        const std::string a = argv[i];
+        char *end = nullptr;
+        if (a == "--band" && i + 2 < argc) {
+            lo = std::strtod(argv[i + 1], &end);
+            usage = usage || end == argv[i + 1] || *end;
+            hi = std::strtod(argv[i + 2], &end);
+            usage = usage || end == argv[i + 2] || *end;
+            i += 2;
+        } else if (a == "--taps" && i + 1 < argc) {
+            taps = std::strtol(argv[i + 1], &end, 10);
+            usage = usage || end == argv[i + 1] || *end || taps < 3 || taps > GRAIL_FIR_TAPS_MAX || taps % 2 == 0;
+            i += 1;
+        } else if (a.rfind("--", 0) == 0) {
+            usage = true;
+        } else {
+            plain.push_back(argv[i]);
+        }
+    }
+    const bool band = hi >= 0.0;
+    const uint32_t chunk = plain.size() > 0 ? (uint32_t)std::strtoul(plain[0], nullptr, 10) : 441;
+    const double tail = plain.size() > 1 ? std::strtod(plain[1], nullptr) : 1.0;
+    // (a chunk of 0 samples — or text strtoul makes 0 of — would never feed the stream)
+    if (usage || plain.size() > 2 || chunk == 0 || !(tail >= 0.0) || (taps && !band) || (band && !(lo >= 0.0 && lo < hi))) {
+        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [samples per pull >= 1 (default 441)] "
+                             "[seconds of tail >= 0 (default 1)]\n");
         return 2;
     }
     try {
         const grail::Voice voice = grail::voices::generic();       // interactive.rs:33-36
         grail::Gpu gpu(0, {voice});
+        // --band: one filter, one row; the stream is declared after its set, so it is closed first
+        std::vector<grail::FirSet> sets;
+        std::vector<grail::FirStream> filters;
+        if (band) {
+            sets.push_back(gpu.fir_set({grail::fir_design((uint32_t)voice.sample_rate, lo, hi, taps ? (uint32_t)taps : 255u)}));
+            filters.push_back(gpu.fir_stream(sets[0], 1));
+        }
         std::vector<Line> script;
         std::string raw;
         while (std::getline(std::cin, raw)) {                        // interactive.rs:77-81
@@ -80,7 +118,7 @@ int main(int argc, char **argv)
         grail::LiveStream chain(gpu, chunk, 0, 0);                   // .jitter(0, ...) interactive.rs:37
         std::deque<grail::PhonemeElem> waiting;                      // what the transcriber has, the Sequencer has not
         const grail::PhonemeElem silence = speak(voice, "", false).at(0);   // ' ': no rule matches
-        size_t next_line = 0, total = 0, fed = 0;
+        size_t next_line = 0, total = 0, fed = 0, written = 0;
         bool first = true, closed = false;
         double close_at = -1.0;
         const char *names[] = {"Silence", "Stop", "Glide", "A", "E"};
@@ -91,12 +129,20 @@ int main(int argc, char **argv)
                 first = false;
                 ++next_line;
             }
-            const std::vector<float> part = chain.next();
+            uint32_t rendered = 0;                                    // what the chain rendered in this pull
+            std::vector<float> part;
+            if (band) {
+                part = chain.next(filters[0], &rendered);            // ... filtered where it lay
+            } else {
+                part = chain.next();
+                rendered = (uint32_t)part.size();
+            }
             std::fwrite(part.data(), sizeof(float), part.size(), stdout);
-            total += part.size();
-            if (part.size() == chunk) continue;
+            total += rendered;
+            written += part.size();
+            if (rendered == chunk) continue;
             if (closed) {
-                if (part.empty()) break;                              // the chain has returned None
+                if (rendered == 0) break;                             // the chain has returned None
                 continue;
             }
             // the Sequencer asks its source for the next segment
@@ -119,6 +165,13 @@ int main(int argc, char **argv)
             chain.append({p});
             std::fprintf(stderr, "fed %s at %zu\n", names[p.phoneme], total);
             ++fed;
+        }
+        if (band) {                                                   // the chain has ended: the filter rings out
+            const std::vector<float> rest = filters[0].finish().at(0);
+            std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
+            written += rest.size();
+            std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps): %zu samples written\n", lo, hi, (double)voice.sample_rate,
+                         filters[0].tail() + 1, written);
         }
         std::fprintf(stderr, "session: %zu samples (%.2f s), %zu phonemes fed, %zu lines, buffers of %u\n", total,
                      total / voice.sample_rate, fed, script.size(), chunk);

@@ -339,6 +339,23 @@ struct grail_fir {
     std::vector<uint32_t> desc;
     grail::host::DeviceBuffer<double> d_taps;     // every filter's taps, binary64, padded to a multiple of 8
     grail::host::DeviceBuffer<uint32_t> d_desc;   // [n_filters][FIR_DESC_WORDS]
+    uint32_t taps_max = 0;            // the longest n_taps of the set (a stream's ring holds taps_max - 1 samples a row)
+};
+
+// A stream of rows filtered call by call (levels.cpp): owned by the context's LevelState, released by
+// grail_filter_stream_close or with the context.  The kernels of fir_kernels.hip read and write its state.
+struct grail_filter_stream {
+    const grail_fir *set = nullptr;   // (a set with open streams is not freed)
+    uint32_t n_rows = 0;
+    uint32_t ring_cap = 0;            // samples of a row's ring: fir_stream_ring_capacity(set->taps_max)
+    grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows] the rows' filters
+    grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows] samples fed, bit 63: the row has ended
+    grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
+    std::vector<uint32_t> filter;     // (host copies, kept while the upload may be in flight)
+    // a finishing call's marks: the host copy is written again only once the upload before has been through
+    std::vector<uint8_t> mark;
+    grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows]
+    grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks

@@ -5,7 +5,8 @@
 // (row, chunk of FIR_CHUNK outputs).  A plain convolution has the same coefficient in every lane and lets a lane own
 // CONSECUTIVE outputs: a lane keeps eight accumulators and a window of the samples they meet in registers, so a tap step
 // brings ONE new sample from LDS and issues EIGHT multiply-adds (the resampler reads LDS once per multiply-add: §4.13).
-// No atomics, every store a plain vector store.  DESIGN.md §4.14.
+// No atomics, every store a plain vector store.  DESIGN.md §4.14.  The second half of the file is the same filter on rows fed
+// chunk by chunk (grail_filter_stream_*, §4.15): the same loop over a stretch staged from a row's ring and the call's chunk.
 #include "kernels.h"
 
 namespace grail {
@@ -68,6 +69,41 @@ __device__ __forceinline__ void fir_block(const float *__restrict__ at, const do
             const uint32_t x = 7u + j - i;
             acc[j] = __builtin_fma(c, x < 8u ? fresh[x] : kept[x - 8u], acc[j]);
         }
+    }
+}
+
+// The eight outputs of lane `tid` from the stretch in LDS, stored at `to` (output 8 tid of the chunk); h: the filter's padded
+// taps, Kp of them, behind a wave-uniform address.  fir_kernel and fir_stream_kernel share it: what differs between them is
+// where the stretch came from.
+template <bool VEC>
+__device__ __forceinline__ void fir_outputs(const float *__restrict__ stage, uint32_t tid, uint32_t count, const double *__restrict__ h,
+                                            uint32_t Kp, float *__restrict__ to)
+{
+    const uint32_t blocks = Kp >> 3;
+    // block b (taps 8 b .. 8 b + 7) starts at group lane + blocks - 1 - b of the stretch
+    const float *at = stage + tid + blocks;
+    double a[8], b[8], acc[8];
+#pragma unroll
+    for (uint32_t r = 0; r < 8; ++r) acc[r] = 0.0, a[r] = 0.0;
+#pragma unroll
+    for (uint32_t r = 0; r < 7; ++r) b[r] = (double)at[r * FIR_PITCH];     // samples 8 .. 14 of block 0's window
+    b[7] = 0.0;
+    uint32_t k = 0;
+    for (; k + 2u <= blocks; k += 2u) {
+        fir_block(at - 1, h, a, b, acc);
+        fir_block(at - 2, h + 8, b, a, acc);
+        at -= 2, h += 16;
+    }
+    if (k < blocks) fir_block(at - 1, h, a, b, acc);
+
+    // eight consecutive outputs per lane; a row's last partial group goes out in 4-byte stores
+    if (VEC && 8u * tid + 8u <= count) {
+        reinterpret_cast<float4 *>(to)[0] = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
+        reinterpret_cast<float4 *>(to)[1] = make_float4((float)acc[4], (float)acc[5], (float)acc[6], (float)acc[7]);
+    } else {
+#pragma unroll
+        for (uint32_t e = 0; e < 8; ++e)
+            if (8u * tid + e < count) to[e] = (float)acc[e];
     }
 }
 
@@ -154,33 +190,7 @@ __global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows
     if (tid < lanes) {
         // the coefficient is the same in every lane: the taps are read through a wave-uniform address (scalar loads)
         const double *h = taps + (uint32_t)__builtin_amdgcn_readfirstlane((int)f.first);
-        const uint32_t blocks = Kp >> 3;
-        // block b (taps 8 b .. 8 b + 7) starts at group lane + blocks - 1 - b of the stretch
-        const float *at = stage + tid + blocks;
-        double a[8], b[8], acc[8];
-#pragma unroll
-        for (uint32_t r = 0; r < 8; ++r) acc[r] = 0.0, a[r] = 0.0;
-#pragma unroll
-        for (uint32_t r = 0; r < 7; ++r) b[r] = (double)at[r * FIR_PITCH];     // samples 8 .. 14 of block 0's window
-        b[7] = 0.0;
-        uint32_t k = 0;
-        for (; k + 2u <= blocks; k += 2u) {
-            fir_block(at - 1, h, a, b, acc);
-            fir_block(at - 2, h + 8, b, a, acc);
-            at -= 2, h += 16;
-        }
-        if (k < blocks) fir_block(at - 1, h, a, b, acc);
-
-        // eight consecutive outputs per lane; a row's last partial group goes out in 4-byte stores
-        float *to = out + u * out_stride + m0 + 8u * tid;
-        if (VEC && 8u * tid + 8u <= count) {
-            reinterpret_cast<float4 *>(to)[0] = make_float4((float)acc[0], (float)acc[1], (float)acc[2], (float)acc[3]);
-            reinterpret_cast<float4 *>(to)[1] = make_float4((float)acc[4], (float)acc[5], (float)acc[6], (float)acc[7]);
-        } else {
-#pragma unroll
-            for (uint32_t e = 0; e < 8; ++e)
-                if (8u * tid + e < count) to[e] = (float)acc[e];
-        }
+        fir_outputs<VEC>(stage, tid, count, h, Kp, out + u * out_stride + m0 + 8u * tid);
     }
     // the chunk's count: integers, so any order
 #pragma unroll
@@ -213,6 +223,190 @@ __global__ __launch_bounds__(256) void fir_totals_kernel(const uint32_t *__restr
     for (uint64_t c = 0; c < chunks; ++c) b += cbad[u * grid_chunks + c];
     if (out_len) out_len[u] = (uint32_t)n_out;
     if (nonfinite) nonfinite[u] = b;
+}
+
+// ---- streams (grail_filter_stream_*): rows fed chunk by chunk, DESIGN.md §4.15 ----------------------------------------------
+// A row's state is one 64-bit word, N = the samples fed so far with FIR_STREAM_ENDED set once the row has ended, and a ring
+// of ring_cap samples (a power of two, at least the set's longest K - 1): sample t of the row lies at t mod ring_cap, not
+// finite ones as +0.0.  In the frame of one call, local time = global time - N: the call's output r is the left fold of
+// h[k] * v[r + d - k] with d = max(0, o - N); v is the ring below 0 (+0.0 before the row's first sample), the call's
+// n samples from 0, +0.0 from n on (which only a finishing call reaches: its n is 0).
+constexpr uint64_t FIR_STREAM_ENDED = 1ull << 63;
+
+struct FirStreamRow {
+    uint64_t fed;           // N
+    uint32_t n, count, d;   // the samples this call feeds, the outputs it writes, the origin in its frame
+    bool takes, refused;    // the call changes the row's state; the row has ended and is fed
+};
+__device__ __forceinline__ FirStreamRow fir_stream_row(const uint64_t *__restrict__ state, const uint32_t *__restrict__ in_len,
+                                                       uint64_t in_stride, const uint8_t *__restrict__ mark, bool finishing, uint64_t u,
+                                                       const FirFilter &f)
+{
+    FirStreamRow r;
+    const uint64_t w = state[u];
+    const bool ended = (w & FIR_STREAM_ENDED) != 0;
+    r.fed = w & ~FIR_STREAM_ENDED;
+    r.d = r.fed < f.origin ? f.origin - (uint32_t)r.fed : 0u;
+    if (finishing) {
+        r.n = 0u;
+        r.refused = false;
+        r.takes = !ended && (!mark || mark[u]);
+        // the tail: outputs E(N) .. N + K - 1 - o - 1, none for a row that was fed nothing
+        r.count = r.takes && r.fed ? f.taps - 1u - f.origin + (r.fed < f.origin ? (uint32_t)r.fed : f.origin) : 0u;
+    } else {
+        r.n = in_len[u] < in_stride ? in_len[u] : (uint32_t)in_stride;
+        r.refused = ended && r.n;
+        r.takes = !ended;
+        // E(N + n) - E(N) with E(N) = max(0, N - o): at most n
+        const uint64_t to = r.fed + r.n;
+        r.count = ended ? 0u : (uint32_t)((to > f.origin ? to - f.origin : 0u) - (r.fed > f.origin ? r.fed - f.origin : 0u));
+    }
+    return r;
+}
+
+// fir_kernel with the row's state in place of the filter's origin and the row's length: one workgroup = one (row, chunk of
+// FIR_CHUNK of this call's outputs).  Reads the state and the ring, writes neither (fir_stream_advance_kernel, queued
+// behind it, is their only writer).  Chunk c counts the non-finite samples among this call's inputs [c FIR_CHUNK, (c + 1)
+// FIR_CHUNK), the last chunk to the end of them.
+template <bool VEC>
+__global__ __launch_bounds__(256) void fir_stream_kernel(const float *__restrict__ in, uint64_t in_stride, const uint32_t *__restrict__ in_len,
+                                                         uint32_t n_rows, const uint32_t *__restrict__ filter, const double *__restrict__ taps,
+                                                         const uint32_t *__restrict__ desc, uint32_t n_filters,
+                                                         const uint64_t *__restrict__ state, const float *__restrict__ ring, uint32_t ring_cap,
+                                                         const uint8_t *__restrict__ mark, uint32_t finishing, uint32_t grid_chunks,
+                                                         float *__restrict__ out, uint64_t out_stride, uint32_t *__restrict__ cbad)
+{
+    __shared__ float stage[8 * FIR_PITCH];
+    __shared__ uint32_t red[FIR_THREADS / 64];
+    const uint32_t tid = threadIdx.x;
+    const uint64_t u = blockIdx.x / grid_chunks;
+    const uint32_t c = (uint32_t)(blockIdx.x - u * grid_chunks);
+    if (u >= n_rows) return;
+    FirFilter f;
+    if (!fir_filter(filter, desc, n_filters, u, f)) return;         // (the indices were checked when the stream was opened)
+    const FirStreamRow r = fir_stream_row(state, in_len, in_stride, mark, finishing != 0u, u, f);
+    const uint64_t n = r.n, n_out = r.count;
+    const uint64_t m0 = (uint64_t)c * FIR_CHUNK;
+    // a refused row and one with neither samples nor outputs have no chunk; chunk 0 of any other runs even with no output
+    // to write: it counts
+    if (r.refused || (n == 0 && n_out == 0) || (m0 >= n_out && c != 0u)) return;
+    const bool last = m0 + FIR_CHUNK >= n_out;
+    const uint32_t count = m0 >= n_out ? 0u : (last ? (uint32_t)(n_out - m0) : FIR_CHUNK);
+    const float *row = in + u * in_stride;                          // (not read when n = 0)
+    const float *hist = ring + u * ring_cap;
+    const uint64_t ring_mask = ring_cap - 1u;
+    const uint32_t Kp = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.padded);
+    const int64_t t_hi = (int64_t)n - 1;
+    const int64_t t_lo = -(int64_t)(f.taps - 1u < r.fed ? f.taps - 1u : r.fed);   // how far back the taps and the row reach
+    const int64_t own_lo = (int64_t)m0 < (int64_t)n ? (int64_t)m0 : (int64_t)n;
+    const int64_t own_hi = last || (int64_t)(m0 + FIR_CHUNK) > (int64_t)n ? (int64_t)n : (int64_t)(m0 + FIR_CHUNK);
+    // the stretch: sample s of it is local time s_base + s; output m0 + j meets, at tap k, sample j + Kp - 1 - k
+    const uint32_t lanes = (count + 7u) >> 3;
+    const int64_t s_base = (int64_t)m0 + (int64_t)r.d - (int64_t)(Kp - 1u);
+    const int64_t s_need = count ? (int64_t)(8u * lanes + Kp - 1u) : 0;
+    uint32_t bad = 0u;
+    int64_t counted_to = own_lo;
+    if (count) {
+        const int64_t g_first = s_base >> 2;
+        const uint32_t groups = (uint32_t)(((s_base + s_need + 3) >> 2) - g_first);
+        const int64_t g_hi = t_hi >> 2;
+        for (uint32_t gi = tid; gi < groups; gi += FIR_THREADS) {
+            const int64_t t0 = 4 * (g_first + (int64_t)gi);
+            float x[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+            if (t0 + 3 >= 0 && t0 <= t_hi) {                        // the group holds samples of this call
+                if (VEC) {
+                    // the call's last group starts below n <= in_stride, a multiple of 4: inside the row
+                    int64_t g = g_first + (int64_t)gi;
+                    g = g < 0 ? 0 : g;
+                    g = g > g_hi ? g_hi : g;
+                    const float4 v = *reinterpret_cast<const float4 *>(row + 4 * g);
+                    x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        int64_t t = t0 + e;
+                        t = t < 0 ? 0 : t;
+                        t = t > t_hi ? t_hi : t;
+                        x[e] = row[t];
+                    }
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = t0 + e;
+                float v = 0.0f;
+                if (t < 0) {
+                    // the ring holds the last ring_cap >= K - 1 samples fed, already +0.0 where they were not finite
+                    if (t >= t_lo) v = hist[(r.fed + (uint64_t)t) & ring_mask];
+                } else if (t <= t_hi) {
+                    const bool finite = fir_finite(x[e]);
+                    bad += (!finite && t >= own_lo && t < own_hi) ? 1u : 0u;
+                    v = finite ? x[e] : 0.0f;
+                }
+                const int64_t s = t - s_base;
+                if (s >= 0 && s < s_need) stage[((uint32_t)s & 7u) * FIR_PITCH + ((uint32_t)s >> 3)] = v;
+            }
+        }
+        counted_to = 4 * (g_first + (int64_t)groups);
+        counted_to = counted_to < own_lo ? own_lo : counted_to;
+    }
+    // what the chunk owns past its stretch (a row still short of its origin writes fewer outputs than it is fed)
+    for (int64_t t = counted_to + tid; t < own_hi; t += FIR_THREADS) bad += fir_finite(row[t]) ? 0u : 1u;
+    __syncthreads();
+
+    if (tid < lanes) {
+        const double *h = taps + (uint32_t)__builtin_amdgcn_readfirstlane((int)f.first);
+        fir_outputs<VEC>(stage, tid, count, h, Kp, out + u * out_stride + m0 + 8u * tid);
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    if ((tid & 63u) == 0u) red[tid >> 6] = bad;
+    __syncthreads();
+    if (tid == 0u) cbad[u * grid_chunks + c] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Behind fir_stream_kernel on the stream, one wave per row, the only writer of a stream's state: the row's numbers from its
+// chunks, the call's last min(n, ring_cap) samples into the ring at (N + t) mod ring_cap, then N + n (a finishing call: the
+// row ended).  A row that has ended and is fed is refused: 0xFFFFFFFF, 0, its state as it was.
+__global__ __launch_bounds__(256) void fir_stream_advance_kernel(const float *__restrict__ in, uint64_t in_stride,
+                                                                 const uint32_t *__restrict__ in_len, uint32_t n_rows,
+                                                                 const uint32_t *__restrict__ filter, const uint32_t *__restrict__ desc,
+                                                                 uint32_t n_filters, uint64_t *__restrict__ state, float *__restrict__ ring,
+                                                                 uint32_t ring_cap, const uint8_t *__restrict__ mark, uint32_t finishing,
+                                                                 const uint32_t *__restrict__ cbad, uint32_t grid_chunks,
+                                                                 uint32_t *__restrict__ out_len, uint32_t *__restrict__ nonfinite)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * (FIR_THREADS / 64u) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (u >= n_rows) return;
+    FirFilter f;
+    if (!fir_filter(filter, desc, n_filters, u, f)) return;
+    const FirStreamRow r = fir_stream_row(state, in_len, in_stride, mark, finishing != 0u, u, f);
+    if (r.refused) {
+        if (lane == 0u) {
+            if (out_len) out_len[u] = 0xFFFFFFFFu;
+            if (nonfinite) nonfinite[u] = 0u;
+        }
+        return;
+    }
+    uint32_t bad = 0u;
+    if (r.takes && r.n) {
+        const uint32_t chunks = r.count ? (r.count + FIR_CHUNK - 1u) / FIR_CHUNK : 1u;
+        for (uint32_t c = lane; c < chunks; c += 64u) bad += cbad[u * grid_chunks + c];
+        const float *row = in + u * in_stride;
+        float *hist = ring + u * ring_cap;
+        const uint32_t keep = r.n < ring_cap ? r.n : ring_cap;
+        for (uint32_t t = r.n - keep + lane; t < r.n; t += 64u) {
+            const float x = row[t];
+            hist[(r.fed + t) & (uint64_t)(ring_cap - 1u)] = fir_finite(x) ? x : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    if (lane != 0u) return;
+    if (out_len) out_len[u] = r.count;
+    if (nonfinite) nonfinite[u] = bad;
+    if (r.takes) state[u] = finishing ? (r.fed | FIR_STREAM_ENDED) : r.fed + r.n;
 }
 
 }  // namespace
@@ -252,6 +446,40 @@ hipError_t launch_fir_totals(const uint32_t *len, uint64_t row_stride, uint32_t 
     if (n_rows == 0) return hipSuccess;
     hipLaunchKernelGGL(fir_totals_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, stream, len, row_stride, n_rows, filter, desc,
                        n_filters, out_stride, cbad, grid_chunks, out_len, nonfinite);
+    return hipGetLastError();
+}
+
+hipError_t launch_fir_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
+                             const double *taps, const uint32_t *desc, uint32_t n_filters, const uint64_t *state, const float *ring,
+                             uint32_t ring_cap, const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out,
+                             uint64_t out_stride, uint32_t *cbad, hipStream_t stream)
+{
+    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
+    if (workgroups == 0) return hipSuccess;
+    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
+                     ((in_stride | out_stride) & 3u) == 0;
+    if (vec)
+        hipLaunchKernelGGL(fir_stream_kernel<true>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, in, in_stride, in_len,
+                           n_rows, filter, taps, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u, grid_chunks, out,
+                           out_stride, cbad);
+    else
+        hipLaunchKernelGGL(fir_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, in, in_stride, in_len,
+                           n_rows, filter, taps, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u, grid_chunks, out,
+                           out_stride, cbad);
+    return hipGetLastError();
+}
+
+hipError_t launch_fir_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
+                                     const uint32_t *desc, uint32_t n_filters, uint64_t *state, float *ring, uint32_t ring_cap,
+                                     const uint8_t *mark, bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                                     uint32_t *nonfinite, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    const uint32_t rows_per_group = FIR_THREADS / 64u;
+    hipLaunchKernelGGL(fir_stream_advance_kernel, dim3(n_rows / rows_per_group + (n_rows % rows_per_group != 0u)), dim3(FIR_THREADS), 0, stream, in,
+                       in_stride, in_len, n_rows, filter, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u, cbad,
+                       grid_chunks, out_len, nonfinite);
     return hipGetLastError();
 }
 

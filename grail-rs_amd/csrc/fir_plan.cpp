@@ -1,4 +1,5 @@
-// fir_plan.cpp — the host side of FIR filtering that needs no device: grail_fir_len, grail_fir_design (a Kaiser-windowed
+// fir_plan.cpp — the host side of FIR filtering that needs no device: grail_fir_len, grail_filter_stream_len and the checks of
+// the calls on filter streams (tests/test_fir_stream_sanitize.py), grail_fir_design (a Kaiser-windowed
 // band-pass with the resampler's sinc and I0), the checks of a filter set and the padded image of one as the kernels read
 // it.  The contract is include/grail_hip.h, "levels, continued: FIR filtering".  No HIP call, so it builds with g++ under
 // AddressSanitizer and UBSan (tests/test_fir_sanitize.py), as resample_plan.cpp does.  DESIGN.md §4.14.
@@ -57,6 +58,62 @@ void fir_set_image(const float *taps, const uint32_t *n_taps, const uint32_t *or
     *tail_max = tail;
 }
 
+uint32_t fir_stream_ring_capacity(uint32_t longest_taps)
+{
+    uint32_t cap = 1;
+    while (cap < longest_taps - 1u && cap < GRAIL_FIR_TAPS_MAX) cap <<= 1;     // (longest_taps >= 1)
+    return cap;
+}
+
+const char *fir_stream_open_error(const uint32_t *filter, uint32_t n_rows, uint32_t n_filters)
+{
+    if (n_rows == 0) return "n_rows is 0";
+    if (filter)
+        for (uint32_t u = 0; u < n_rows; ++u)
+            if (filter[u] >= n_filters) return "a row's filter index is outside the set";
+    return nullptr;
+}
+
+namespace {
+
+// the chunks of GRAIL_FIR_CHUNK outputs of a row of at most `longest` of them (fewer than 2^32: the lengths are 32 bits wide)
+uint64_t stream_chunks(uint64_t longest)
+{
+    const uint64_t most = longest < 0xFFFFFFFFull ? longest : 0xFFFFFFFFull;
+    return (most + GRAIL_FIR_CHUNK - 1u) / GRAIL_FIR_CHUNK;
+}
+
+}  // namespace
+
+const char *fir_stream_next_error(const void *in, uint64_t in_stride, const void *in_len, uint32_t n_rows, const void *out,
+                                  uint64_t out_stride, uint64_t *chunks)
+{
+    *chunks = 0;
+    if (out_stride < in_stride) return "out_stride < in_stride (a stream never cuts outputs short)";
+    if (!in_len || (in_stride && (!in || !out))) return "NULL buffer";
+    if (in_stride == 0) return nullptr;
+    if (in_stride > (1ull << 60) / n_rows || out_stride > (1ull << 60) / n_rows) return "the rows span more than 2^60 samples";
+    const uintptr_t in0 = (uintptr_t)in, in1 = in0 + (uintptr_t)(n_rows * in_stride * 4u);
+    const uintptr_t out0 = (uintptr_t)out, out1 = out0 + (uintptr_t)(n_rows * out_stride * 4u);
+    if (in0 < out1 && out0 < in1) return "out_dev overlaps in_dev (a chunk reads what another would have written)";
+    *chunks = stream_chunks(in_stride);
+    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
+    return nullptr;
+}
+
+const char *fir_stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint32_t longest_taps, uint64_t *chunks)
+{
+    *chunks = 0;
+    const uint32_t tail = longest_taps - 1u;
+    if (out_stride < tail) return "out_stride is below the set's longest n_taps - 1";
+    if (tail == 0) return nullptr;
+    if (!out) return "NULL buffer";
+    if (out_stride > (1ull << 60) / n_rows) return "the rows span more than 2^60 samples";
+    *chunks = stream_chunks(tail);
+    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
+    return nullptr;
+}
+
 }  // namespace grail
 
 extern "C" {
@@ -67,6 +124,21 @@ int grail_fir_len(uint64_t n, uint32_t n_taps, uint32_t origin, uint64_t *n_out)
     const uint64_t tail = n_taps - 1u - origin;
     if (n > UINT64_MAX - tail) return GRAIL_ERR_INVALID_ARG;
     *n_out = n == 0 ? 0 : n + tail;
+    return GRAIL_OK;
+}
+
+int grail_filter_stream_len(uint64_t fed_before, uint64_t n, uint32_t n_taps, uint32_t origin, int finishing, uint64_t *n_out)
+{
+    if (!n_out || !filter_ok(n_taps, origin)) return GRAIL_ERR_INVALID_ARG;
+    const uint64_t tail = n_taps - 1u - origin;
+    if ((finishing && n) || fed_before > UINT64_MAX - n || fed_before + n > UINT64_MAX - tail) return GRAIL_ERR_INVALID_ARG;
+    const uint64_t known = fed_before > origin ? fed_before - origin : 0;       // E(N) = max(0, N - o)
+    if (finishing) {
+        *n_out = fed_before == 0 ? 0 : fed_before + tail - known;
+    } else {
+        const uint64_t to = fed_before + n;
+        *n_out = (to > origin ? to - origin : 0) - known;
+    }
     return GRAIL_OK;
 }
 

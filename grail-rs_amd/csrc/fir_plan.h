@@ -21,4 +21,16 @@ const char *fir_set_error(const float *taps, const uint32_t *n_taps, const uint3
 void fir_set_image(const float *taps, const uint32_t *n_taps, const uint32_t *origin, uint32_t n_filters,
                    std::vector<double> &image, std::vector<uint32_t> &desc, uint32_t *tail_max);
 
+// Streams (grail_filter_stream_*).  The samples of a row's ring: the set's longest n_taps - 1 rounded up to a power of two,
+// at least 1 and at most 4096 (16 KB)
+uint32_t fir_stream_ring_capacity(uint32_t longest_taps);
+// NULL when filter (host [n_rows], or NULL = filter 0) binds n_rows >= 1 rows to filters of a set of n_filters
+const char *fir_stream_open_error(const uint32_t *filter, uint32_t n_rows, uint32_t n_filters);
+// NULL when a call of grail_filter_stream_next_async may be queued, *chunks = the chunks of GRAIL_FIR_CHUNK outputs a row
+// can have (0: no samples at all), else what is wrong with its arguments (addresses are compared, never looked behind)
+const char *fir_stream_next_error(const void *in, uint64_t in_stride, const void *in_len, uint32_t n_rows, const void *out,
+                                  uint64_t out_stride, uint64_t *chunks);
+// ... and of grail_filter_stream_finish_async, for a set whose longest filter has longest_taps taps
+const char *fir_stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint32_t longest_taps, uint64_t *chunks);
+
 }  // namespace grail

@@ -1,10 +1,10 @@
 // levels.cpp — rendered rows measured on the device: grail_levels_async, grail_frame_levels_async, grail_loudness_async,
 // grail_loudness_segmented_async and grail_true_peak_async, grail_limit_async, grail_resample_async, grail_fir_create / _free /
-// _async (checks, the scratch, the launches) and what
+// _async, grail_filter_stream_open / _next_async / _finish_async / _close (checks, the scratch, the launches) and what
 // grail_batch_mix_leveled and its _limited form (mix.cpp) need per block.  The kernels are level_kernels.hip, loudness_kernels.hip,
 // loudness_segment_kernels.hip, true_peak_kernels.hip, limiter_kernels.hip, resample_kernels.hip and fir_kernels.hip, the gains are level_gains.cpp,
 // the resampler's ratio and table resample_plan.cpp and a filter set's checks and image fir_plan.cpp (pure host).
-// DESIGN.md §4.9, §4.10, §4.11, §4.12, §4.13, §4.14.
+// DESIGN.md §4.9, §4.10, §4.11, §4.12, §4.13, §4.14, §4.15.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -17,7 +17,8 @@ using namespace grail::host;
 // block's true peaks for the limited mix, the chunk numbers that a limiter call folds (16 B per group and chunk of 4096
 // samples), the hops' non-finite counts that a segmented loudness call folds (4 B per hop), the chunks' non-finite counts
 // that a resampling call folds (4 B per chunk of 1024 outputs), the resampler's tables of the last few pairs of rates,
-// the same counts of a filtering call (4 B per chunk of 2048 outputs) and the filter sets the caller has created.
+// the same counts of a filtering call (4 B per chunk of 2048 outputs), the filter sets the caller has created and the
+// filter streams open on them (each with its rows' state: a ring of samples and one word per row).
 struct ResampleTable {
     uint32_t up = 0, down = 0;              // 0: the slot holds no table
     uint64_t used = 0;                      // the call that last asked for it (the oldest is evicted)
@@ -43,6 +44,7 @@ struct LevelState : CtxPart {
     uint64_t table_calls = 0;
     DeviceBuffer<uint32_t> d_firbad;        // FIR chunks: non-finite counts
     std::vector<std::unique_ptr<grail_fir>> firs;   // the filter sets alive
+    std::vector<std::unique_ptr<grail_filter_stream>> fir_streams;   // ... and the filter streams open on them
 };
 
 namespace {
@@ -449,6 +451,7 @@ int grail_fir_create(grail_ctx *ctx, const float *taps, const uint32_t *n_taps, 
     std::unique_ptr<grail_fir> set(new (std::nothrow) grail_fir());
     if (!set) return fail(GRAIL_ERR_OUT_OF_MEMORY, "filter set");
     set->n_filters = n_filters;
+    for (uint32_t f = 0; f < n_filters; ++f) set->taps_max = std::max(set->taps_max, n_taps[f]);
     fir_set_image(taps, n_taps, origin, n_filters, set->image, set->desc, &set->tail_max);
     HIP_TRY(upload(set->d_taps, set->image.data(), set->image.size(), ctx->stream));
     HIP_TRY(upload(set->d_desc, set->desc.data(), set->desc.size(), ctx->stream));
@@ -465,6 +468,8 @@ int grail_fir_free(grail_ctx *ctx, grail_fir *set)
     if (st) {
         for (auto it = st->firs.begin(); it != st->firs.end(); ++it) {
             if (it->get() != set) continue;
+            for (const auto &fs : st->fir_streams)
+                if (fs->set == set) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_free: the set still has open filter streams");
             // (a kernel or the upload still queued may be reading it)
             int rc = bind(ctx);
             if (rc) return rc;
@@ -525,6 +530,142 @@ int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev,
                                            st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "fir totals kernel launch");
     return GRAIL_OK;
+}
+
+namespace {
+
+// streams are looked up, not looked into: a stale pointer or another context's is refused, not read
+grail_filter_stream *find_fir_stream(grail_ctx *ctx, const grail_filter_stream *fs)
+{
+    const LevelState *own = static_cast<const LevelState *>(ctx->level_state.get());
+    if (own)
+        for (const auto &s : own->fir_streams)
+            if (s.get() == fs) return s.get();
+    return nullptr;
+}
+
+// the two kernels of a call on a stream: the outputs (chunks = 0: there are none to write), then the state
+int fir_stream_call(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev, uint64_t in_stride,
+                    const uint32_t *in_len_dev, const uint8_t *mark_dev, bool finishing, uint64_t chunks, float *out_dev,
+                    uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev)
+{
+    LevelState *st = state(ctx);
+    if (!st) return fail(GRAIL_ERR_OUT_OF_MEMORY, "level state");
+    const grail_fir *set = fs->set;
+    if (chunks) {
+        int rc;
+        if ((rc = st->d_firbad.reserve(ctx->stream, (size_t)fs->n_rows * (size_t)chunks))) return rc;
+        const hipError_t e = launch_fir_stream(in_dev, in_stride, in_len_dev, fs->n_rows, fs->d_filter.get(), set->d_taps.get(),
+                                               set->d_desc.get(), set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap,
+                                               mark_dev, finishing, (uint32_t)chunks, out_dev, out_stride, st->d_firbad.get(),
+                                               ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "fir stream kernel launch");
+    }
+    const hipError_t e = launch_fir_stream_advance(in_dev, in_stride, in_len_dev, fs->n_rows, fs->d_filter.get(), set->d_desc.get(),
+                                                   set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap, mark_dev, finishing,
+                                                   st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "fir stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+}  // namespace
+
+int grail_filter_stream_open(grail_ctx *ctx, const grail_fir *set, uint32_t n_rows, const uint32_t *filter, grail_filter_stream **out)
+{
+    // (what is wrong with the arguments is said before what is wrong with the machine; no context exists without a device)
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_open: NULL argument");
+    bool found = false;
+    if (const LevelState *own = static_cast<const LevelState *>(ctx->level_state.get()))
+        for (const auto &s : own->firs) found = found || s.get() == set;
+    if (!found) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_open: not a filter set of this context");
+    if (const char *why = fir_stream_open_error(filter, n_rows, set->n_filters))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_filter_stream_open: ") + why);
+    int rc = bind(ctx);
+    if (rc) return rc;
+    LevelState *st = state(ctx);
+    std::unique_ptr<grail_filter_stream> fs(new (std::nothrow) grail_filter_stream());
+    if (!fs) return fail(GRAIL_ERR_OUT_OF_MEMORY, "filter stream");
+    fs->set = set;
+    fs->n_rows = n_rows;
+    fs->ring_cap = fir_stream_ring_capacity(set->taps_max);
+    fs->filter.assign(n_rows, 0u);
+    if (filter) std::copy(filter, filter + n_rows, fs->filter.begin());
+    HIP_TRY(upload(fs->d_filter, fs->filter.data(), n_rows, ctx->stream));
+    HIP_TRY(fs->d_state.alloc(n_rows));
+    HIP_TRY(fs->d_ring.alloc((size_t)n_rows * fs->ring_cap));
+    HIP_TRY(fs->d_mark.alloc(n_rows));
+    // no sample fed, no row ended; the ring is never read before it is written, zeroed all the same
+    HIP_TRY(hipMemsetAsync(fs->d_state.get(), 0, (size_t)n_rows * sizeof(uint64_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(fs->d_ring.get(), 0, (size_t)n_rows * fs->ring_cap * sizeof(float), ctx->stream));
+    *out = fs.get();
+    st->fir_streams.push_back(std::move(fs));
+    return GRAIL_OK;
+}
+
+int grail_filter_stream_close(grail_ctx *ctx, grail_filter_stream *fs)
+{
+    if (!fs) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_close: ctx is NULL");
+    LevelState *st = static_cast<LevelState *>(ctx->level_state.get());
+    if (st) {
+        for (auto it = st->fir_streams.begin(); it != st->fir_streams.end(); ++it) {
+            if (it->get() != fs) continue;
+            // (a kernel or an upload still queued may be using its state)
+            int rc = bind(ctx);
+            if (rc) return rc;
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            st->fir_streams.erase(it);
+            return GRAIL_OK;
+        }
+    }
+    return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_close: not an open filter stream of this context");
+}
+
+int grail_filter_stream_next_async(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev, uint64_t in_stride,
+                                   const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                   uint32_t *nonfinite_dev)
+{
+    // (what is wrong with the arguments is said before what is wrong with the machine)
+    if (!fs) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_next_async: the stream is NULL");
+    if (ctx && !find_fir_stream(ctx, fs))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_next_async: not an open filter stream of this context");
+    // (without a context the stream was not looked up and is not looked into: the checks run for one row, and the call ends
+    // at bind_device)
+    uint64_t chunks = 0;
+    if (const char *why = fir_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? fs->n_rows : 1u, out_dev, out_stride, &chunks))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_filter_stream_next_async: ") + why);
+    int rc = bind_device(ctx, "grail_filter_stream_next_async");
+    if (rc) return rc;
+    return fir_stream_call(ctx, fs, in_dev, in_stride, in_len_dev, nullptr, false, chunks, out_dev,
+                           out_stride, out_len_dev, nonfinite_dev);
+}
+
+int grail_filter_stream_finish_async(grail_ctx *ctx, grail_filter_stream *fs, const uint8_t *which, float *out_dev,
+                                     uint64_t out_stride, uint32_t *out_len_dev)
+{
+    if (!fs) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_finish_async: the stream is NULL");
+    if (ctx && !find_fir_stream(ctx, fs))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_finish_async: not an open filter stream of this context");
+    // (without a context: the checks of a set of one tap, and the call ends at bind_device)
+    uint64_t chunks = 0;
+    if (const char *why = fir_stream_finish_error(out_dev, out_stride, ctx ? fs->n_rows : 1u, ctx ? fs->set->taps_max : 1u, &chunks))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_filter_stream_finish_async: ") + why);
+    int rc = bind_device(ctx, "grail_filter_stream_finish_async");
+    if (rc) return rc;
+    const uint8_t *mark_dev = nullptr;
+    if (which) {
+        // (the upload of the call before may still be reading the host copy)
+        if (fs->ev_mark.get())
+            HIP_TRY(hipEventSynchronize(fs->ev_mark));
+        else
+            HIP_TRY(fs->ev_mark.create());
+        fs->mark.assign(which, which + fs->n_rows);
+        HIP_TRY(hipMemcpyAsync(fs->d_mark.get(), fs->mark.data(), fs->n_rows, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipEventRecord(fs->ev_mark, ctx->stream));
+        mark_dev = fs->d_mark.get();
+    }
+    return fir_stream_call(ctx, fs, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride,
+                           out_len_dev, nullptr);
 }
 
 int grail_loudness_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,

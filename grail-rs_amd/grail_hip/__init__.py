@@ -82,6 +82,8 @@ EXPORTS = [
     "grail_limit_ceiling", "grail_limit_async",
     "grail_resample_ratio", "grail_resample_coefficients", "grail_resample_len", "grail_resample_async",
     "grail_fir_len", "grail_fir_design", "grail_fir_create", "grail_fir_free", "grail_fir_async",
+    "grail_filter_stream_len", "grail_filter_stream_open", "grail_filter_stream_next_async", "grail_filter_stream_finish_async",
+    "grail_filter_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -384,6 +386,11 @@ def load():
     L.grail_fir_create.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
     L.grail_fir_free.argtypes = [vp, vp]
     L.grail_fir_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, vp, u64, vp, vp]
+    L.grail_filter_stream_len.argtypes = [u64, u64, C.c_uint32, C.c_uint32, C.c_int, vp]
+    L.grail_filter_stream_open.argtypes = [vp, vp, C.c_uint32, vp, vp]
+    L.grail_filter_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    L.grail_filter_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp]
+    L.grail_filter_stream_close.argtypes = [vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -754,6 +761,14 @@ def fir_len(n, n_taps, origin):
     """grail_fir_len (pure host): 0 for n = 0, else n + n_taps - 1 - origin, the length of a row of n samples filtered."""
     out = C.c_uint64(0)
     _check(load().grail_fir_len(n, n_taps, origin, C.addressof(out)))
+    return out.value
+
+
+def fir_stream_len(fed_before, n, n_taps, origin, finishing=False):
+    """grail_filter_stream_len (pure host): the outputs a call on a filter stream writes for a row that was fed fed_before
+    samples before it: a `next` call that feeds n samples, or (finishing, n = 0) the tail of `finish`."""
+    out = C.c_uint64(0)
+    _check(load().grail_filter_stream_len(fed_before, n, n_taps, origin, 1 if finishing else 0, C.addressof(out)))
     return out.value
 
 
@@ -1278,6 +1293,62 @@ class Context:
             for p in d:
                 self.device_free(p)
         return tuple(r[:n_rows] for r in res)
+
+    def fir_stream_open(self, fir_set, n_rows, filters=None):
+        """grail_filter_stream_open: a stream of n_rows rows filtered call by call, row u bound to filter filters[u] of the set
+        (a host sequence; None: filter 0 for every row).  Returns the stream's handle, for fir_stream_next / _finish /
+        _close; streams still open go with the context, and their set cannot be freed before them."""
+        which = None if filters is None else np.ascontiguousarray(filters, dtype=np.uint32)
+        out = C.c_void_p(None)
+        _check(load().grail_filter_stream_open(self.handle, fir_set, n_rows, None if which is None else which.ctypes.data,
+                                               C.addressof(out)))
+        return out
+
+    def fir_stream_next_async(self, fs, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev=None, nonfinite_dev=None):
+        """grail_filter_stream_next_async: every row is fed its next min(in_len_dev[u], in_stride) samples; the outputs that
+        became known go to out_dev + u * out_stride.  Results are DEVICE arrays [n_rows] (either may be None), queued on the
+        context's stream; in_dev may be reused by what is queued behind the call."""
+        _check(load().grail_filter_stream_next_async(self.handle, fs, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev,
+                                                     nonfinite_dev))
+
+    def fir_stream_next(self, fs, n_rows, in_dev, in_stride, in_len_dev, out_dev, out_stride):
+        """fir_stream_next_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a row
+        that had ended and was fed: (LIMIT_REFUSED, 0)."""
+        res = [np.zeros(n_rows, dtype=np.uint32) for _ in range(2)]
+        d = [self.device_alloc(n_rows * 4) for _ in res]
+        try:
+            self.fir_stream_next_async(fs, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d)
+            for dst, src in zip(res, d):
+                self.d2h(dst, src, n_rows * 4)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return tuple(res)
+
+    def fir_stream_finish(self, fs, n_rows, out_dev, out_stride, which=None, out_len_dev=None):
+        """grail_filter_stream_finish_async: the rows marked in which (a host sequence, non-zero = marked; None: every row)
+        that have not ended write their tails and end.  out_len_dev None: waited for, and the tails' lengths (uint32, one
+        per row; 0 for rows not marked or ended before) returned."""
+        marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
+        assert marks is None or len(marks) == n_rows
+        own = None if out_len_dev is not None else self.device_alloc(n_rows * 4)
+        try:
+            _check(load().grail_filter_stream_finish_async(self.handle, fs, None if marks is None else marks.ctypes.data, out_dev,
+                                                           out_stride, out_len_dev if own is None else own))
+            if own is None:
+                return None
+            res = np.zeros(n_rows, dtype=np.uint32)
+            self.d2h(res, own, n_rows * 4)
+            return res
+        finally:
+            if own is not None:
+                self.sync()
+                self.device_free(own)
+
+    def fir_stream_close(self, fs):
+        """grail_filter_stream_close: waits for the context's stream, then releases the stream."""
+        _check(load().grail_filter_stream_close(self.handle, fs))
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max finite |x|, non-finite counts) per row, computed on the device (every length

@@ -126,6 +126,10 @@ pub struct grail_node {
 pub struct grail_fir {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct grail_filter_stream {
+    _private: [u8; 0],
+}
 
 /// The most taps of one filter and the most filters of one set (`grail_fir_create`).
 pub const GRAIL_FIR_TAPS_MAX: u32 = 4096;
@@ -302,6 +306,15 @@ extern "C" {
     pub fn grail_fir_async(ctx: *mut grail_ctx, set: *const grail_fir, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
         n_rows: u32, filter_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
         nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_filter_stream_len(fed_before: u64, n: u64, n_taps: u32, origin: u32, finishing: c_int, n_out: *mut u64) -> c_int;
+    pub fn grail_filter_stream_open(ctx: *mut grail_ctx, set: *const grail_fir, n_rows: u32, filter: *const u32,
+        out: *mut *mut grail_filter_stream) -> c_int;
+    pub fn grail_filter_stream_next_async(ctx: *mut grail_ctx, fs: *mut grail_filter_stream, in_dev: *const f32, in_stride: u64,
+        in_len_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
+        nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_filter_stream_finish_async(ctx: *mut grail_ctx, fs: *mut grail_filter_stream, which: *const u8,
+        out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32) -> c_int;
+    pub fn grail_filter_stream_close(ctx: *mut grail_ctx, fs: *mut grail_filter_stream) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

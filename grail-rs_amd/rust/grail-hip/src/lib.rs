@@ -597,7 +597,8 @@ impl Gpu {
         check(unsafe {
             sys::grail_fir_create(self.ctx, taps.as_ptr(), n_taps.as_ptr(), origin.as_ptr(), filters.len() as u32, &mut set)
         })?;
-        Ok(FirSet { gpu: self, set, tail })
+        let longest = n_taps.iter().copied().max().unwrap_or(1);
+        Ok(FirSet { gpu: self, set, tail, longest })
     }
 
     /// Rows of samples filtered on the device (`grail_fir_async`; the contract is the header's section "levels, continued: FIR
@@ -668,6 +669,21 @@ impl Gpu {
             r?;
         }
         Ok((out, bad))
+    }
+
+    /// A stream of `n_rows` rows filtered chunk by chunk (`grail_filter_stream_open`; the contract is the header's section
+    /// "levels, continued: FIR filtering of streams"), row `i` bound to filter `which[i]` of the set (`None`: filter 0).  The
+    /// chunks' outputs put end to end, then the tail of [`FirStream::finish`], are the bits [`Gpu::fir`] gives for the whole
+    /// rows.  Closed when dropped; the borrow keeps the set alive for as long.
+    pub fn fir_stream<'a>(&'a self, set: &'a FirSet<'a>, n_rows: u32, which: Option<&[u32]>) -> Result<FirStream<'a>, Error> {
+        if which.map_or(false, |w| w.len() != n_rows as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "fir_stream: one filter index per row".to_string() });
+        }
+        let mut fs: *mut sys::grail_filter_stream = std::ptr::null_mut();
+        check(unsafe {
+            sys::grail_filter_stream_open(self.ctx, set.set, n_rows, which.map_or(std::ptr::null(), |w| w.as_ptr()), &mut fs)
+        })?;
+        Ok(FirStream { gpu: self, fs, n_rows, tail: set.longest.saturating_sub(1), _set: set })
     }
 
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
@@ -854,6 +870,7 @@ pub struct FirSet<'a> {
     gpu: &'a Gpu,
     set: *mut sys::grail_fir,
     tail: u64,
+    longest: u32,
 }
 
 impl Drop for FirSet<'_> {
@@ -862,6 +879,117 @@ impl Drop for FirSet<'_> {
             sys::grail_fir_free(self.gpu.ctx, self.set);
         }
     }
+}
+
+/// Rows filtered chunk by chunk on a [`Gpu`]'s device ([`Gpu::fir_stream`]), their history resident in HBM between calls;
+/// `grail_filter_stream_close` when dropped.
+pub struct FirStream<'a> {
+    gpu: &'a Gpu,
+    fs: *mut sys::grail_filter_stream,
+    n_rows: u32,
+    tail: u32,
+    _set: &'a FirSet<'a>,
+}
+
+impl FirStream<'_> {
+    // one call on the stream: `chunks` fed (None: the rows marked in `which` finish); the outputs and the counts per row
+    fn call(&mut self, chunks: Option<&[Vec<f32>]>, which: Option<&[u8]>) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        let n = self.n_rows as usize;
+        let longest = chunks.map_or(0, |c| c.iter().map(|r| r.len()).max().unwrap_or(0));
+        let stride = (longest + 63) / 64 * 64;
+        let out_stride = (longest.max(self.tail as usize) + 63) / 64 * 64;
+        let lens: Vec<u32> = chunks.map_or(vec![0u32; n], |c| c.iter().map(|r| r.len() as u32).collect());
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let sizes = [n * stride.max(1) * 4, n * out_stride.max(1) * 4, n * 4, n * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, sizes[k], &mut d[k]));
+                }
+            }
+            if let Some(c) = chunks {
+                for (i, row) in c.iter().enumerate() {
+                    if r.is_ok() && !row.is_empty() {
+                        r = check(sys::grail_memcpy_h2d(ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                        row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                    }
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_h2d(ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_filter_stream_next_async(ctx, self.fs, d[0] as *const f32, stride as u64, d[2] as *const u32,
+                                                                  d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                                                  d[4] as *mut u32));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_d2h(ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+                }
+            } else if r.is_ok() {
+                r = check(sys::grail_filter_stream_finish_async(ctx, self.fs, which.map_or(std::ptr::null(), |w| w.as_ptr()),
+                                                                d[1] as *mut f32, out_stride as u64, d[3] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 && out_lens[i] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad))
+    }
+
+    /// Feeds row `i` the samples `chunks[i]` (an empty chunk: the row pauses) and returns, per row, the outputs that became
+    /// known and the count of non-finite samples among those fed (`grail_filter_stream_next_async`).  A row that has ended
+    /// and is fed comes back empty, its state untouched.
+    pub fn next(&mut self, chunks: &[Vec<f32>]) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        if chunks.len() != self.n_rows as usize {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "FirStream::next: one chunk per row".to_string() });
+        }
+        self.call(Some(chunks), None)
+    }
+
+    /// Ends the rows marked in `which` (`None`: every row) and returns their tails: what the filter still rings out with
+    /// +0.0 to come (`grail_filter_stream_finish_async`); empty for rows not marked and rows ended before.
+    pub fn finish(&mut self, which: Option<&[bool]>) -> Result<Vec<Vec<f32>>, Error> {
+        if which.map_or(false, |w| w.len() != self.n_rows as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "FirStream::finish: one mark per row".to_string() });
+        }
+        let marks: Option<Vec<u8>> = which.map(|w| w.iter().map(|&m| m as u8).collect());
+        Ok(self.call(None, marks.as_deref())?.0)
+    }
+}
+
+impl Drop for FirStream<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_filter_stream_close(self.gpu.ctx, self.fs);
+        }
+    }
+}
+
+/// The outputs a call on a [`FirStream`] writes for a row that was fed `fed_before` samples before it: a `next` call that
+/// feeds `n` samples, or (`finishing`, `n` = 0) the tail (`grail_filter_stream_len`; pure host).
+pub fn fir_stream_len(fed_before: u64, n: u64, n_taps: u32, origin: u32, finishing: bool) -> Result<u64, Error> {
+    let mut n_out = 0u64;
+    check(unsafe { sys::grail_filter_stream_len(fed_before, n, n_taps, origin, finishing as i32, &mut n_out) })?;
+    Ok(n_out)
 }
 
 /// The most taps of a filter, the most filters of a set (`GRAIL_FIR_TAPS_MAX`, `GRAIL_FIR_FILTERS_MAX`).

@@ -164,16 +164,17 @@ public:
             n_taps.push_back((uint32_t)f.taps.size());
             origin.push_back(f.origin);
             tail_ = std::max<uint64_t>(tail_, f.taps.size() > f.origin ? f.taps.size() - 1 - f.origin : 0);
+            longest_ = std::max<uint32_t>(longest_, (uint32_t)f.taps.size());
         }
         check(grail_fir_create(ctx, taps.data(), n_taps.data(), origin.data(), (uint32_t)filters.size(), &set_));
     }
     ~FirSet() { grail_fir_free(ctx_, set_); }
-    FirSet(FirSet &&o) noexcept : ctx_(o.ctx_), set_(std::exchange(o.set_, nullptr)), tail_(o.tail_) {}
+    FirSet(FirSet &&o) noexcept : ctx_(o.ctx_), set_(std::exchange(o.set_, nullptr)), tail_(o.tail_), longest_(o.longest_) {}
     FirSet &operator=(FirSet &&o) noexcept
     {
         if (this != &o) {
             grail_fir_free(ctx_, set_);
-            ctx_ = o.ctx_, set_ = std::exchange(o.set_, nullptr), tail_ = o.tail_;
+            ctx_ = o.ctx_, set_ = std::exchange(o.set_, nullptr), tail_ = o.tail_, longest_ = o.longest_;
         }
         return *this;
     }
@@ -181,11 +182,102 @@ public:
     FirSet &operator=(const FirSet &) = delete;
     const grail_fir *get() const { return set_; }
     uint64_t tail() const { return tail_; }     // the longest n_taps - 1 - origin: how far a row rings out
+    uint32_t longest() const { return longest_; }   // the most taps of a filter of the set
 
 private:
     grail_ctx *ctx_ = nullptr;
     grail_fir *set_ = nullptr;
     uint64_t tail_ = 0;
+    uint32_t longest_ = 1;
+};
+
+// Rows filtered chunk by chunk on a Gpu's device (grail_filter_stream_open; the contract is the header's section "levels,
+// continued: FIR filtering of streams"), made by Gpu::fir_stream: move-only, closed with grail_filter_stream_close.  The
+// chunks' outputs put end to end, then the tails of finish(), are the bits Gpu::fir gives for the whole rows.  It must not
+// outlive its FirSet, which cannot be freed before it.
+class FirStream {
+public:
+    FirStream(grail_ctx *ctx, const FirSet &set, uint32_t n_rows, const std::vector<uint32_t> &which = {})
+        : ctx_(ctx), n_rows_(n_rows), tail_(set.longest() - 1)
+    {
+        if (!which.empty() && which.size() != n_rows) throw Error(GRAIL_ERR_INVALID_ARG, "fir_stream: one filter index per row");
+        check(grail_filter_stream_open(ctx, set.get(), n_rows, which.empty() ? nullptr : which.data(), &fs_));
+    }
+    ~FirStream() { grail_filter_stream_close(ctx_, fs_); }
+    FirStream(FirStream &&o) noexcept : ctx_(o.ctx_), fs_(std::exchange(o.fs_, nullptr)), n_rows_(o.n_rows_), tail_(o.tail_) {}
+    FirStream &operator=(FirStream &&o) noexcept
+    {
+        if (this != &o) {
+            grail_filter_stream_close(ctx_, fs_);
+            ctx_ = o.ctx_, fs_ = std::exchange(o.fs_, nullptr), n_rows_ = o.n_rows_, tail_ = o.tail_;
+        }
+        return *this;
+    }
+    FirStream(const FirStream &) = delete;
+    FirStream &operator=(const FirStream &) = delete;
+    uint32_t rows() const { return n_rows_; }
+    uint32_t tail() const { return tail_; }      // the set's longest n_taps - 1: the room finish() needs per row
+
+    // grail_filter_stream_next_async on device buffers (a chunk that grail_stream_next_async has just rendered, say): queued on
+    // the context's stream, nothing leaves the device
+    void next_async(const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride,
+                    uint32_t *out_len_dev, uint32_t *nonfinite_dev = nullptr)
+    {
+        check(grail_filter_stream_next_async(ctx_, fs_, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev, nonfinite_dev));
+    }
+
+    // Row i is fed chunks[i] (an empty chunk: the row pauses); returns the outputs that became known, per row.  A row that
+    // has ended and is fed comes back empty.
+    std::vector<std::vector<float>> next(const std::vector<std::vector<float>> &chunks)
+    {
+        if (chunks.size() != n_rows_) throw Error(GRAIL_ERR_INVALID_ARG, "FirStream::next: one chunk per row");
+        return call(&chunks, nullptr);
+    }
+    // The rows marked in which (empty: every row) end; returns their tails: what the filters still ring out.
+    std::vector<std::vector<float>> finish(const std::vector<uint8_t> &which = {})
+    {
+        if (!which.empty() && which.size() != n_rows_) throw Error(GRAIL_ERR_INVALID_ARG, "FirStream::finish: one mark per row");
+        return call(nullptr, which.empty() ? nullptr : which.data());
+    }
+
+private:
+    std::vector<std::vector<float>> call(const std::vector<std::vector<float>> *chunks, const uint8_t *which)
+    {
+        const uint32_t n = n_rows_;
+        size_t longest = 0;
+        if (chunks)
+            for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
+        const uint64_t stride = (longest + 63) / 64 * 64, out_stride = (std::max<uint64_t>(longest, tail_) + 63) / 64 * 64;
+        std::vector<std::vector<float>> out(n);
+        std::vector<uint32_t> lens(n, 0u), out_lens(n, 0u);
+        for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
+        void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4 + 4, &d_in);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4 + 4, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_out_len);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc)
+            rc = chunks ? grail_filter_stream_next_async(ctx_, fs_, (const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out,
+                                                         out_stride, (uint32_t *)d_out_len, nullptr)
+                        : grail_filter_stream_finish_async(ctx_, fs_, which, (float *)d_out, out_stride, (uint32_t *)d_out_len);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)n * 4);
+        for (uint32_t i = 0; !rc && i < n; ++i) {
+            if (!out_lens[i] || out_lens[i] == GRAIL_LIMIT_REFUSED) continue;
+            out[i].resize(out_lens[i]);
+            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)out_lens[i] * 4);
+        }
+        for (void *p : {d_in, d_out, d_len, d_out_len})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
+    grail_ctx *ctx_ = nullptr;
+    grail_filter_stream *fs_ = nullptr;
+    uint32_t n_rows_ = 0, tail_ = 0;
 };
 
 namespace detail {
@@ -547,6 +639,12 @@ public:
 
     // A set of filters for fir(), resident on this device
     FirSet fir_set(const std::vector<Fir> &filters) const { return FirSet(ctx_, filters); }
+    // A stream of n_rows rows filtered chunk by chunk with filters of the set, row i with filter which[i] (which empty: filter
+    // 0 for every row), their history resident on this device between calls
+    FirStream fir_stream(const FirSet &set, uint32_t n_rows, const std::vector<uint32_t> &which = {}) const
+    {
+        return FirStream(ctx_, set, n_rows, which);
+    }
 
     // Rows of samples filtered on the device (grail_fir_async; the contract is the header's section "levels, continued: FIR
     // filtering"), row i with filter which[i] of the set (which empty: filter 0 for every row).  ring_out: a row of n samples
@@ -892,21 +990,40 @@ public:
         if (n) check(grail_memcpy_d2h(ctx_, out.data(), d_out_, (size_t)n * sizeof(float)));
         return out;
     }
+    // ... through a filter stream of one row before anything leaves the device: the chunk the chain rendered is fed to
+    // `filter` where it lies, and what comes back is what the filter could write for it (fewer samples than were rendered
+    // while the filter is short of its origin).  *rendered: the chain's own count, which says whether the Sequencer waits.
+    std::vector<float> next(FirStream &filter, uint32_t *rendered)
+    {
+        if (filter.rows() != 1) throw Error(GRAIL_ERR_INVALID_ARG, "LiveStream::next: a filter stream of one row");
+        if (!d_filtered_) check(grail_device_alloc(ctx_, (size_t)stride_ * sizeof(float), &d_filtered_));
+        if (!d_filtered_len_) check(grail_device_alloc(ctx_, sizeof(uint32_t), &d_filtered_len_));
+        uint32_t n = 0;
+        check(grail_stream_next_async(ctx_, stream_, chunk_, (float *)d_out_, stride_, (uint32_t *)d_len_));
+        filter.next_async((const float *)d_out_, stride_, (const uint32_t *)d_len_, (float *)d_filtered_, stride_,
+                          (uint32_t *)d_filtered_len_);
+        check(grail_memcpy_d2h(ctx_, rendered, d_len_, sizeof *rendered));
+        check(grail_memcpy_d2h(ctx_, &n, d_filtered_len_, sizeof n));
+        std::vector<float> out(n);
+        if (n) check(grail_memcpy_d2h(ctx_, out.data(), d_filtered_, (size_t)n * sizeof(float)));
+        return out;
+    }
     uint32_t chunk() const { return chunk_; }
 
 private:
     void release()
     {
         if (stream_) grail_stream_close(ctx_, stream_);
-        if (d_out_) grail_device_free(ctx_, d_out_);
-        if (d_len_) grail_device_free(ctx_, d_len_);
-        stream_ = nullptr; d_out_ = nullptr; d_len_ = nullptr;
+        for (void *p : {d_out_, d_len_, d_filtered_, d_filtered_len_})
+            if (p) grail_device_free(ctx_, p);
+        stream_ = nullptr; d_out_ = nullptr; d_len_ = nullptr; d_filtered_ = nullptr; d_filtered_len_ = nullptr;
     }
     grail_ctx *ctx_;
     uint32_t chunk_;
     uint64_t stride_;
     grail_stream *stream_ = nullptr;
     void *d_out_ = nullptr, *d_len_ = nullptr;
+    void *d_filtered_ = nullptr, *d_filtered_len_ = nullptr;      // next(filter, ...): made at its first call
 };
 
 }  // namespace grail

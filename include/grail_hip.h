@@ -1086,6 +1086,61 @@ int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev,
                     const uint32_t *len_dev, uint32_t n_rows, const uint32_t *filter_dev,
                     float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev);
 
+/* ---- levels, continued: FIR filtering of streams ---------------------------------------------------------------------------------
+ * grail_fir_async takes finished rows.  A caller who pulls a live stream chunk by chunk (grail_stream_next_async) filters
+ * chunk by chunk with a FILTER STREAM: n_rows independent rows, each bound to one filter (K taps, origin o) of a live set
+ * when the stream is opened, their state resident in HBM between calls.
+ * THE CONTRACT.  For any split of a row's samples into calls (calls of no samples included), the outputs of the `next`
+ * calls put end to end, followed by the tail that `finish` writes, are bit for bit what grail_fir_async writes for the whole
+ * row with an out_stride that cuts nothing; the sum of the calls' nonfinite counts is its count.  This is the promise
+ * grail_stream_next_async makes for rendering.
+ * STATE.  Per row: N, the samples fed so far (64 bits); whether the row has ended; the last K - 1 samples fed, in a ring of
+ * the set's longest K - 1 samples rounded up to a power of two (at most 16 KB a row).
+ * E(N) = max(0, N - o) outputs can be known after N samples (output m needs sample m + o).  A `next` call that feeds n
+ * samples writes outputs E(N) .. E(N + n) - 1 (at most n of them; none while the row is short of its origin); `finish`
+ * writes the tail E(N) .. N + K - 1 - o - 1, the samples to come being +0.0: K - 1 - o + min(N, o) outputs, at most K - 1,
+ * none for a row that was fed nothing.
+ * (The functions are named grail_filter_stream_*, not grail_fir_*: the latter are the calls on finished rows.) */
+typedef struct grail_filter_stream grail_filter_stream;
+
+/* Pure host: *n_out = the outputs a call writes for a row that was fed fed_before samples before it: finishing = 0: a
+ * `next` call that feeds n samples; finishing != 0: `finish` (n must be 0).  GRAIL_ERR_INVALID_ARG, nothing written: as
+ * grail_fir_len; finishing with n != 0. */
+int grail_filter_stream_len(uint64_t fed_before, uint64_t n, uint32_t n_taps, uint32_t origin, int finishing, uint64_t *n_out);
+/* A stream of n_rows rows on the filters of `set`: filter is a HOST array [n_rows] of indices into the set, NULL means
+ * filter 0 for every row.  The state (a ring and one 64-bit word per row) belongs to the stream, which belongs to the
+ * context.  GRAIL_ERR_INVALID_ARG, nothing created: ctx or out NULL; a set that is not a live set of this context;
+ * n_rows = 0; an index >= the set's filter count (the array is on the host, so it is checked here: a stream has no refused
+ * rows of this kind).  These come first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_filter_stream_open(grail_ctx *ctx, const grail_fir *set, uint32_t n_rows, const uint32_t *filter,
+                             grail_filter_stream **out);
+/* Feeds every row u its next n = min(in_len_dev[u], in_stride) samples from in_dev + u * in_stride and writes the
+ * E(N + n) - E(N) outputs that became known to out_dev + u * out_stride, from index 0; queued on ctx's stream.  Results
+ * are DEVICE arrays [n_rows], either may be NULL: out_len[u] = that count; nonfinite[u] = the samples among this call's n
+ * that are not finite (a sample is counted in the call that fed it and never again; it enters as +0.0).  n = 0 is legal (a
+ * paused row): nothing is written, out_len 0.  A row that has ended and is fed n > 0 is refused as grail_fir_async refuses a
+ * row: out_len = GRAIL_LIMIT_REFUSED, nonfinite 0, nothing written, its state as it was.  out_dev past out_len is never
+ * written.  in_dev may be reused by whatever is queued behind the call: the call copies what it keeps.  16-byte loads and
+ * stores where both bases are 16-byte aligned and both strides multiples of 4, 4-byte ones otherwise: same bits.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of this context (looked up, not looked
+ * into); a NULL buffer with samples to read or write, in_len_dev NULL; out_stride < in_stride (a stream never cuts outputs
+ * short); overlapping ranges; more than 2^31 chunks of GRAIL_FIR_CHUNK outputs.  These come first; without a usable
+ * device: GRAIL_ERR_NO_DEVICE. */
+int grail_filter_stream_next_async(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev, uint64_t in_stride,
+                                   const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride,
+                                   uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+/* Rings out the rows marked in which (a HOST array [n_rows] of bytes, non-zero = marked; NULL = every row, as
+ * grail_stream_finish): a marked row that has not ended writes its tail to out_dev + u * out_stride and ends.  out_len
+ * (device [n_rows], may be NULL): the tail's length; 0, and nothing written, for unmarked rows and rows that had ended
+ * before.  The array may be reused at once.  GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of
+ * this context; out_stride below the set's longest K - 1; out_dev NULL with a tail to write. */
+int grail_filter_stream_finish_async(grail_ctx *ctx, grail_filter_stream *fs, const uint8_t *which, float *out_dev,
+                                     uint64_t out_stride, uint32_t *out_len_dev);
+/* Releases a stream once everything queued on ctx's stream is through; streams still open at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context.  While a set has open streams,
+ * grail_fir_free of it returns GRAIL_ERR_INVALID_ARG and frees nothing. */
+int grail_filter_stream_close(grail_ctx *ctx, grail_filter_stream *fs);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);

@@ -5,7 +5,12 @@
                   grail_true_peak_async (§4.11: 48 multiply-adds a sample, nothing written),
                   a plain device-to-device copy of the rows' buffer (what reading and writing the bytes costs);
   --step lone   a lone track of 10^7 samples through K = 32, 255, 1023 and 4096 (time is parallel: it fills the device);
-  --step fir    render, then grail_fir_async K = 144 alone (for a counter run).
+  --step fir    render, then grail_fir_async K = 144 alone (for a counter run);
+  --step stream the config-3 rows through a filter stream in chunks of 4 800 samples (100 ms), K = 144,
+                  against grail_fir_async on the same samples in the same process: every chunk is first copied into a
+                  buffer of its own (outside the clock: a live stream's pull writes it there), then
+                  grail_filter_stream_next_async + sync is timed; the tail by grail_filter_stream_finish_async.  The streamed
+                  output is compared with the one-shot output on the device (grail_batch_compare: no row differs).
 Wall clock around each call and its sync, best of --reps after a warm-up.  Each step is a process of its own so that each
 runs under a time limit of its own and a failure ends the chain:
     timeout -k 10 600 python tools/fir_bench.py --step rows && timeout -k 10 300 python tools/fir_bench.py --step lone
@@ -123,6 +128,71 @@ def rows_step(ctx, args, out, only_fir):
     b.free()
 
 
+def stream_step(ctx, args, out):
+    chunk = 4800
+    ctx.set_voices(W.single_voice())
+    n = args.utts
+    segs, offs, vids, seeds = W.make_batch(n)
+    stride = W.max_samples()
+    out_stride = (stride + K_ROWS + 63) // 64 * 64
+    b = ctx.upload(segs, offs, vids, seeds)
+    d_rows, d_len = ctx.device_alloc(n * stride * 4), ctx.device_alloc(n * 4)
+    d_out, d_sout = ctx.device_alloc(n * out_stride * 4), ctx.device_alloc(n * out_stride * 4)
+    b.synthesize_async(d_rows, stride, d_len)
+    ctx.sync()
+    lens = np.zeros(n, np.uint32)
+    ctx.d2h(lens, d_len, n * 4)
+    if lens.min() != lens.max():
+        raise SystemExit("the stream step wants rows of one length (the aligned corpus): every row's chunk lands at the same offset")
+    length = int(lens[0])
+    h, origin = taps_of(K_ROWS)
+    fir_set = ctx.fir_create([(h, origin)])
+    d_ol, d_b, d_sol = ctx.device_alloc(n * 4), ctx.device_alloc(n * 4), ctx.device_alloc(n * 4)
+
+    def fir():
+        ctx.fir_async(fir_set, d_rows, stride, d_len, n, None, d_out, out_stride, d_ol, d_b)
+        ctx.sync()
+
+    one_shot, one_shot_all = best(fir, args.reps)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy2D.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    d_chunk, d_clen = ctx.device_alloc(n * chunk * 4), ctx.device_alloc(n * 4)
+    calls = -(-length // chunk)
+    runs = []
+    for _ in range(2):                                   # (the first run warms up)
+        fs = ctx.fir_stream_open(fir_set, n)
+        ms, written = [], 0
+        for c in range(calls):
+            k = min(chunk, length - c * chunk)
+            rc = hip.hipMemcpy2D(d_chunk, chunk * 4, C.c_void_p(d_rows.value + 4 * c * chunk), stride * 4, k * 4, n, 3)
+            if rc:
+                raise SystemExit(f"hipMemcpy2D failed: {rc}")
+            ctx.h2d(d_clen, np.full(n, k, np.uint32), n * 4)
+            t0 = time.perf_counter()
+            ctx.fir_stream_next_async(fs, d_chunk, chunk, d_clen, C.c_void_p(d_sout.value + 4 * written), out_stride, d_sol, None)
+            ctx.sync()
+            ms.append(1e3 * (time.perf_counter() - t0))
+            written += G.fir_stream_len(c * chunk, k, K_ROWS, origin)
+        t0 = time.perf_counter()
+        ctx.fir_stream_finish(fs, n, C.c_void_p(d_sout.value + 4 * written), out_stride, None, d_sol)
+        ctx.sync()
+        ms.append(1e3 * (time.perf_counter() - t0))
+        ctx.fir_stream_close(fs)
+        runs.append(ms)
+    max_diff, _, mismatches = ctx.compare(d_sout, d_out, out_stride, d_ol, d_ol, n)
+    ms = runs[-1]
+    out.update({"rows": n, "samples_per_row": length, "chunk": chunk, "calls": calls, "one_shot_ms": one_shot, "one_shot_ms_all": one_shot_all,
+                "stream_ms": sum(ms), "stream_ms_runs": [sum(r) for r in runs], "stream_next_ms_median": float(np.median(ms[:-1])), "stream_finish_ms": ms[-1],
+                "mismatches": int(np.count_nonzero((max_diff != 0) | (mismatches != 0)))})
+    print(f"grail_fir_async K = {K_ROWS}: {one_shot:.2f} ms; the same rows through a filter stream in {calls} calls of {chunk} samples: "
+          f"{sum(ms):.2f} ms = {sum(ms) / one_shot:.2f} x (a call {np.median(ms[:-1]):.3f} ms, finish {ms[-1]:.3f} ms); "
+          f"rows that differ from the one-shot output: {out['mismatches']}")
+    ctx.fir_free(fir_set)
+    for p in (d_ol, d_b, d_sol, d_chunk, d_clen, d_rows, d_out, d_sout, d_len):
+        ctx.device_free(p)
+    b.free()
+
+
 def lone_step(ctx, args, out):
     long_n = 10_000_000
     long_out = (long_n + 4096 + 63) // 64 * 64
@@ -151,7 +221,7 @@ def lone_step(ctx, args, out):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--step", choices=["rows", "lone", "fir"], required=True)
+    ap.add_argument("--step", choices=["rows", "lone", "fir", "stream"], required=True)
     ap.add_argument("--utts", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=5)
     args = ap.parse_args()
@@ -161,6 +231,8 @@ def main():
     out = {"step": args.step, "cases": {}}
     if args.step == "lone":
         lone_step(ctx, args, out)
+    elif args.step == "stream":
+        stream_step(ctx, args, out)
     else:
         rows_step(ctx, args, out, only_fir=args.step == "fir")
     ctx.close()
