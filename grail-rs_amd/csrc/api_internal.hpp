@@ -2,9 +2,10 @@
 // units include kernels.h, never this).  grail_api.cpp: contexts, batches, voices; options.cpp: the option table,
 // grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
 // families, cost model, block planner; synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
-// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak), limited, resampled and filtered; host_output.cpp: the one-call
-// forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Every HIP resource these units
-// create has one owner type (below): Event, Stream, DeviceBuffer, PinnedBuffer.
+// mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak); transforms.cpp: rows limited, resampled and
+// filtered, at once or as streams; host_output.cpp: the one-call forms with a host destination; comm.cpp and node.cpp:
+// RCCL, the contexts of a node.  Every HIP resource these units create has one owner type (below): Event, Stream,
+// DeviceBuffer, PinnedBuffer.
 #pragma once
 
 #include <dlfcn.h>
@@ -295,6 +296,7 @@ struct grail_ctx : PlanEnv {
     std::unique_ptr<CtxPart> host_pipe;     // HostPipe (host_output.cpp): streams, events and buffers of the host-output path
     std::unique_ptr<CtxPart> mix_state;     // MixState (mix.cpp): the last mix's plan and the device buffers it was uploaded to
     std::unique_ptr<CtxPart> level_state;   // LevelState (levels.cpp): the frame scratch of grail_levels_async, a block's numbers
+    std::unique_ptr<CtxPart> transform_state;   // TransformState (transforms.cpp): chunk scratch, resampler tables, filter sets and streams
 };
 
 struct grail_stream {
@@ -330,8 +332,8 @@ struct grail_stream {
     int stage_next = 0;
 };
 
-// A set of FIR filters (levels.cpp; the image and its descriptors are fir_plan.cpp's): owned by the context's LevelState,
-// released by grail_fir_free or with the context.
+// A set of FIR filters (transforms.cpp; the image and its descriptors are fir_plan.cpp's): owned by the context's
+// TransformState, released by grail_fir_free or with the context.
 struct grail_fir {
     uint32_t n_filters = 0;
     uint32_t tail_max = 0;            // the largest n_taps - 1 - origin of the set: how far a row rings out
@@ -342,7 +344,7 @@ struct grail_fir {
     uint32_t taps_max = 0;            // the longest n_taps of the set (a stream's ring holds taps_max - 1 samples a row)
 };
 
-// A stream of rows filtered call by call (levels.cpp): owned by the context's LevelState, released by
+// A stream of rows filtered call by call (transforms.cpp): owned by the context's TransformState, released by
 // grail_filter_stream_close or with the context.  The kernels of fir_kernels.hip read and write its state.
 struct grail_filter_stream {
     const grail_fir *set = nullptr;   // (a set with open streams is not freed)
@@ -443,6 +445,9 @@ inline int64_t scan_max_utts(const PlanEnv *ctx) { return ctx->opt.scan_max_utts
 inline int64_t scan_split_max(const PlanEnv *ctx) { return ctx->opt.scan_split_max < 0 ? 6 * (int64_t)ctx->cus : ctx->opt.scan_split_max; }
 
 int bind(grail_ctx *ctx);
+// ... for the device entry points that say their own name (levels.cpp, transforms.cpp): without a context, why there is none,
+// GRAIL_ERR_NO_DEVICE on a machine without a GPU
+int bind_device(grail_ctx *ctx, const char *who);
 
 // max(count, 1) elements for dst, the first `count` of them copied from src (if any) on `stream`
 template <typename Tp>

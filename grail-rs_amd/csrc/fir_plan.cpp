@@ -8,6 +8,7 @@
 
 #include "../../include/grail_hip.h"
 #include "fir_plan.h"
+#include "row_checks.h"
 
 namespace {
 
@@ -90,12 +91,12 @@ const char *fir_stream_next_error(const void *in, uint64_t in_stride, const void
 {
     *chunks = 0;
     if (out_stride < in_stride) return "out_stride < in_stride (a stream never cuts outputs short)";
-    if (!in_len || (in_stride && (!in || !out))) return "NULL buffer";
+    // (a stream has rows: fir_stream_open_error)
+    const RowPair p{in, in_stride, in_len, n_rows, out, out_stride};
+    if (const char *why = row_pair_error(p, OutRule::always, OutRule::always,
+                                         "out_dev overlaps in_dev (a chunk reads what another would have written)", 0))
+        return why;
     if (in_stride == 0) return nullptr;
-    if (in_stride > (1ull << 60) / n_rows || out_stride > (1ull << 60) / n_rows) return "the rows span more than 2^60 samples";
-    const uintptr_t in0 = (uintptr_t)in, in1 = in0 + (uintptr_t)(n_rows * in_stride * 4u);
-    const uintptr_t out0 = (uintptr_t)out, out1 = out0 + (uintptr_t)(n_rows * out_stride * 4u);
-    if (in0 < out1 && out0 < in1) return "out_dev overlaps in_dev (a chunk reads what another would have written)";
     *chunks = stream_chunks(in_stride);
     if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
     return nullptr;
@@ -107,8 +108,8 @@ const char *fir_stream_finish_error(const void *out, uint64_t out_stride, uint32
     const uint32_t tail = longest_taps - 1u;
     if (out_stride < tail) return "out_stride is below the set's longest n_taps - 1";
     if (tail == 0) return nullptr;
-    if (!out) return "NULL buffer";
-    if (out_stride > (1ull << 60) / n_rows) return "the rows span more than 2^60 samples";
+    if (!out) return ROWS_NULL;
+    if (!rows_span_fits(out_stride, n_rows)) return ROWS_SPAN;
     *chunks = stream_chunks(tail);
     if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
     return nullptr;

@@ -49,6 +49,15 @@ int bind(grail_ctx *ctx)
     return GRAIL_OK;
 }
 
+int bind_device(grail_ctx *ctx, const char *who)
+{
+    if (ctx) return bind(ctx);
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n < 1)
+        return fail(GRAIL_ERR_NO_DEVICE, std::string(who) + ": no usable HIP device (there is no CPU fallback)");
+    return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": ctx is NULL");
+}
+
 // clk / 2^k is clk * 2^-k exactly; any other blend length needs the division code of the kernel
 bool blend_is_pow2(float blend_length)
 {
