@@ -1,7 +1,8 @@
 // api_internal.hpp — what the host translation units of the library share (internal; host code only: the kernel
 // units include kernels.h, never this).  grail_api.cpp: contexts, batches, voices; options.cpp: the option table,
-// grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; launch_plan.cpp: kernel
-// families, cost model, block planner; synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
+// grail_set_option / grail_get_option; voice_analysis.cpp: what a voice table qualifies for; family_choice.cpp,
+// family_cost.cpp, dispatch_model.cpp, launch_plan.cpp: kernel families, cost model, dispatcher model, block planner
+// (launch_plan.h); synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
 // mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak); transforms.cpp: rows limited, resampled and
 // filtered, at once or as streams; host_output.cpp: the one-call forms with a host destination; comm.cpp and node.cpp:
 // RCCL, the contexts of a node.  Every HIP resource these units create has one owner type (below): Event, Stream,
@@ -185,7 +186,7 @@ struct Stream : Handle<hipStream_t, hipStreamDestroy> {
 };
 
 // One hipMalloc allocation of `capacity()` elements.  `reserve` is the one growth rule of device memory: grown when too
-// small, never shrunk.  The launch policy (launch_plan.cpp, voice_analysis.cpp) never sees a type that holds one: its
+// small, never shrunk.  The launch policy (launch_plan.h, voice_analysis.cpp) never sees a type that holds one: its
 // inputs are PlanEnv and BatchFacts.
 template <typename T>
 class DeviceBuffer {
@@ -233,7 +234,7 @@ private:
     size_t cap_ = 0;
 };
 
-// the kernel family of a launch, a block of rows with its family (launch_plan.cpp chooses them)
+// the kernel family of a launch, a block of rows with its family (family_choice.cpp chooses them)
 struct Family {
     int L = 1;                 // lanes per utterance (lane kernels, pipelined workgroups)
     uint32_t pipe = 0;         // exact pipelined workgroups: 1 = rounds of 16 samples, 2 = rounds of 32
@@ -401,7 +402,7 @@ struct RowGroup : BatchFacts {
     mutable grail::host::PlanCache plan_cache;
 };
 
-// A block of a ragged batch in PACKED launch order (launch_plan.cpp, "The workgroup dispatcher"): the slot -> utterance table
+// A block of a ragged batch in PACKED launch order (dispatch_model.cpp, "The workgroup dispatcher"): the slot -> utterance table
 // of rows [slot0, slot0 + rows) with its workgroups re-ordered, on the device.  Kept by the batch and never reallocated while
 // it lives (a kernel of another context may still be reading it), freed with it.
 struct PackedPerm {
@@ -430,19 +431,10 @@ struct grail_batch : BatchFacts {
 };
 static_assert(!std::is_copy_constructible_v<grail_batch>, "a batch owns its device arrays: row groups are BatchFacts, not batches");
 
+#include "launch_plan.h"
+
 namespace grail {
 namespace host {
-
-// the SIMDs and lanes the policy plans for: 4 SIMDs per compute unit, 64 lanes per wavefront.  Every family is laid out
-// for ONE resident wave per SIMD (a second wave on a SIMD costs as much as it brings: profiles/r01_lanes_sweep.txt), so
-// all capacities below are multiples of the compute-unit count hipGetDeviceProperties reports (a partitioned MI355X —
-// CPX, 32 CUs — plans for 32, not 256); "assume_compute_units" overrides it for tests.
-inline uint64_t ctx_simds(const PlanEnv *ctx) { return 4ull * (uint64_t)ctx->cus; }
-inline uint64_t ctx_lanes(const PlanEnv *ctx) { return 256ull * (uint64_t)ctx->cus; }
-inline int64_t pipe4_groups(const PlanEnv *ctx) { return ctx->opt.pipe4_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe4_max_groups; }
-inline int64_t pipe8_groups(const PlanEnv *ctx) { return ctx->opt.pipe8_max_groups < 0 ? 2 * (int64_t)ctx->cus : ctx->opt.pipe8_max_groups; }
-inline int64_t scan_max_utts(const PlanEnv *ctx) { return ctx->opt.scan_max_utts < 0 ? 34 * (int64_t)ctx->cus : ctx->opt.scan_max_utts; }
-inline int64_t scan_split_max(const PlanEnv *ctx) { return ctx->opt.scan_split_max < 0 ? 6 * (int64_t)ctx->cus : ctx->opt.scan_split_max; }
 
 int bind(grail_ctx *ctx);
 // ... for the device entry points that say their own name (levels.cpp, transforms.cpp): without a context, why there is none,
@@ -478,32 +470,6 @@ double batch_sharpness(const PlanEnv *ctx, const BatchFacts *batch);
 int fast_tier_for(const PlanEnv *ctx, const BatchFacts *batch, int arithmetic);
 int fast_tier(const PlanEnv *ctx, const BatchFacts *batch);
 bool split_grid(uint32_t span, uint32_t warmup, int K, double r, uint32_t *b);
-
-// launch_plan.cpp: which kernel family renders a block of rows, what it costs, how a batch is cut into blocks
-// lanes per utterance when the option is 0 (auto): the widest mapping that gives each of `simds` SIMDs at most one wave
-int auto_lanes_per_utt(uint32_t n_utt, uint64_t simds);
-double batch_span(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride);
-double family_cost(const PlanEnv *ctx, const Family &f, uint32_t rows, double span);
-// pipelined workgroups, rows that differ in length: utterances per workgroup of a launch of `rows` rows (0: every slot)
-uint32_t pipe_fill_for(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t rows);
-// a launch of `rows` rows with family f takes the instantiations built for two waves per SIMD (SynthArgs::cohabit)
-bool family_cohabits(const PlanEnv *ctx, const Family &f, uint32_t rows);
-bool batch_half_capable(const PlanEnv *ctx, const BatchFacts *batch);
-bool batch_live4_any_blend(const PlanEnv *ctx, const BatchFacts *batch);
-bool batch_live4(const PlanEnv *ctx, const BatchFacts *batch);
-void choose_family(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t fam, Family &f,
-                   bool exact_only = false, int pin_lanes = 0);
-// ragged batches: what a block costs given the lengths and events of ITS rows; the whole-batch plan weighed against
-// one launch of each lane mapping with as many rounds as it takes (launch_plan.cpp)
-double ragged_cost(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t slot0, uint32_t rows, double span);
-// The launch order of the workgroups of such a block (one wave per SIMD, more workgroups than the device holds at once):
-// true and order[position] = workgroup (in the plain, longest-first numbering) when the packed order is worth it by the
-// dispatcher's model; *plain_ms / *packed_ms: the model's makespans.  rows_per_block: what a workgroup renders.
-bool packed_launch_order(const PlanEnv *ctx, const BatchFacts *batch, const Family &f, uint32_t slot0, uint32_t rows, double span,
-                         std::vector<uint32_t> *order, uint32_t *rows_per_block, double *plain_ms, double *packed_ms);
-void ragged_plan(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t rows, std::vector<Block> &plan);
-double plan_blocks(const PlanEnv *ctx, const BatchFacts *batch, uint64_t out_stride, uint32_t rows, double span,
-                   std::vector<Block> &out, bool exact_only = false);
 
 // synthesize.cpp: one launch per block; a batch's cached plan
 // what every synthesis launch takes from (ctx, batch): the batch's arrays from utterance row0 on, the voice table, the flags

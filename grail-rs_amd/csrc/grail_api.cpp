@@ -1,7 +1,7 @@
 // grail_api.cpp — the C ABI (include/grail_hip.h) over the HIP kernels: contexts, voice tables, HBM-resident
 // batches, synchronisation and the device utilities.  Host orchestration only (with options.cpp, voice_analysis.cpp,
-// launch_plan.cpp, synthesize.cpp, streams.cpp, host_output.cpp, comm.cpp): no arithmetic of the hot path happens here and
-// there is no CPU fallback: without a HIP device every compute call fails.
+// the launch planner (launch_plan.h), synthesize.cpp, streams.cpp, host_output.cpp, comm.cpp): no arithmetic of the hot
+// path happens here and there is no CPU fallback: without a HIP device every compute call fails.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -158,7 +158,7 @@ static std::vector<RowStats> batch_stats(const grail_ctx *ctx, grail_batch *b, c
 
 // An upper bound of every utterance's length in samples, on the device (time-split kernels: a chunk's lane whose utterance
 // ends before the chunk begins has nothing to render and says so at once — batches whose rows differ in length then take
-// more, shorter chunks; launch_plan.cpp): grail_length_bound at the table's highest sample rate, + a tile.
+// more, shorter chunks; family_choice.cpp): grail_length_bound at the table's highest sample rate, + a tile.
 int upload_len_bound(grail_ctx *ctx, grail_batch *b, const std::vector<RowStats> &rows, uint32_t n_utt)
 {
     if (!b->plain || n_utt == 0 || ctx->voices.empty()) return GRAIL_OK;
@@ -191,8 +191,7 @@ int upload_length_order(grail_ctx *ctx, grail_batch *b, const std::vector<RowSta
     if (!ctx->voices.empty()) {
         for (uint32_t u = 0; u < n_utt; ++u) {
             const RowStats &r = rows[u];
-            const bool lean = r.plain && r.min_length >= 2.0f * ctx->facts.max_dt &&
-                              r.min_pitch * window::MARGIN_DOWN - window::JITTER_MARGIN * ctx->facts.max_pitch_jitter >= window::X_LO;
+            const bool lean = r.plain && lean_window(r.min_length, r.min_pitch, ctx->facts);
             outlier[u] = lean ? 0 : 1;
             n_out += outlier[u];
         }

@@ -76,7 +76,7 @@ struct SynthArgs {
                                   // interpolated, 2 = the reference's own coefficients at every sample (MID)
     uint32_t any_blend;           // host hint: some segment has a blend length that is not +-2^k
     uint32_t cohabit;             // lane kernels on 2 / 4 / 8 lanes per utterance: the instantiation built for two waves per
-                                  // SIMD (launches of more waves than the device has SIMDs; launch_plan.cpp family_cohabits)
+                                  // SIMD (launches of more waves than the device has SIMDs; family_cost.cpp family_cohabits)
     const uint32_t *len_bound;    // time-split kernels: per utterance an upper bound of its length in samples, or nullptr — a
                                   // chunk's lane whose utterance ends before the chunk begins renders nothing
     uint32_t pipe_fill;           // pipelined workgroups, one-shot: utterances per workgroup (0: all 16 / 8 slots) — a small batch

@@ -1,6 +1,6 @@
 // mix_plan.cpp — the host side of mixing that needs no device: grail_mix_async's plan (which items each list tile of each
 // track accumulates, in which order; how long a workgroup's span is) and grail_mix_place_sequential.  No HIP call, so it
-// builds with g++ under AddressSanitizer and UBSan (tests/test_mix_host.py), as launch_plan.cpp does.  DESIGN.md §4.8.
+// builds with g++ under AddressSanitizer and UBSan (tests/test_mix_host.py), as the launch planner does.  DESIGN.md §4.8.
 #include "mix_plan.h"
 
 #include <algorithm>

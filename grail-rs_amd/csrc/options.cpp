@@ -1,6 +1,6 @@
 // options.cpp — the options of a context (include/grail_hip.h, "Options": the contract) as one table: a row per name
 // with how a value is checked and where it lives.  grail_set_option and grail_get_option look the name up here.  Pure
-// host code, like launch_plan.cpp (the debug_prof_<k> counters of -DGRAIL_FAST_PROF builds apart).
+// host code, like the launch planner (the debug_prof_<k> counters of -DGRAIL_FAST_PROF builds apart).
 #include "api_internal.hpp"
 
 using namespace grail;

@@ -767,7 +767,7 @@ hipError_t launch_scan(const SynthArgs &args, hipStream_t stream)
 {
     if (args.n_utt == 0) return hipSuccess;
     // few utterances: the time per batch is the chain's; three-stage workgroups halve it.  Many: two waves
-    // per utterance keep more utterances resident per CU (args.pipe: the host's choice, launch_plan.cpp)
+    // per utterance keep more utterances resident per CU (args.pipe: the host's choice, family_choice.cpp)
     if (args.pipe) {
         if (args.live4) hipLaunchKernelGGL((scan_kernel<2, true>), dim3(args.n_utt), dim3(192), 0, stream, args);
         else hipLaunchKernelGGL((scan_kernel<4, true>), dim3(args.n_utt), dim3(192), 0, stream, args);

@@ -77,7 +77,7 @@
         // a chunk's lane whose utterance ends before the chunk begins (the host's upper bound of its length) has nothing
         // to render — no fast-forward, no warm-up; a wave of such lanes is gone at once.  Rows that differ in length are
         // launched longest first, so the waves of the later chunks are the ones that go, and the host lays out more,
-        // shorter chunks than the device has SIMDs for (launch_plan.cpp).
+        // shorter chunks than the device has SIMDs for (family_choice.cpp).
         if (A.len_bound != nullptr && slot_used && chunk > 0u && A.len_bound[u] <= A.split_bounds[chunk]) done = true;
         if (__builtin_amdgcn_ballot_w64(!done) == 0) {
 #ifdef GRAIL_FAST_PROF

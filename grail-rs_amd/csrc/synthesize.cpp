@@ -1,5 +1,5 @@
 // synthesize.cpp — a batch's rows to kernel launches: the cached block plan of a batch, one launch per block
-// (launch_plan.cpp chose the families), the device-resident entry points.
+// (family_choice.cpp chose the families), the device-resident entry points.
 #include "api_internal.hpp"
 
 using namespace grail;
@@ -32,7 +32,7 @@ void batch_args(const grail_ctx *ctx, const grail_batch *batch, uint32_t row0, S
 // One launch: `count` launch slots from slot `slot0` of the rows [first, first + n_rows) the caller renders, with
 // family f.  out_dev / out_len_dev point at row `first`.  use_perm: the batch's length-sorted slot order applies
 // (whole-batch calls): slot s renders utterance perm[s], and every per-utterance array is indexed by the utterance.
-// The block's slot -> utterance table in PACKED launch order (launch_plan.cpp, "The workgroup dispatcher"), made at the
+// The block's slot -> utterance table in PACKED launch order (dispatch_model.cpp, "The workgroup dispatcher"), made at the
 // block's first launch and kept by the batch; nullptr: the plain order (it is as good, or the block does not qualify).
 static const uint32_t *packed_perm_of(grail_ctx *ctx, const grail_batch *root, const View &view, const Family &f,
                                       uint64_t out_stride, uint32_t slot0, uint32_t count, int *rc)
@@ -109,8 +109,8 @@ static int launch_block(grail_ctx *ctx, const grail_batch *root, const View &vie
     a.fold_from = 0u;
     if (a.cohabit) {
         // at most two rounds of the device: the workgroups of the second take their launch slots in reverse order
-        const uint32_t waves_per_block = f.L >= 4 ? 4u : 1u, per_block = (64u / (uint32_t)f.L) * waves_per_block;
-        const uint32_t blocks = (count + per_block - 1u) / per_block, round = (uint32_t)ctx_simds(ctx) / waves_per_block;
+        const WorkgroupShape wg = workgroup_shape(f);
+        const uint32_t blocks = (count + wg.rows - 1u) / wg.rows, round = (uint32_t)ctx_simds(ctx) / wg.waves;
         if (blocks > round && blocks <= 2u * round) a.fold_from = round;
     }
     a.pipe = f.pipe;
@@ -187,7 +187,7 @@ int synthesize_rows(grail_ctx *ctx, const grail_batch *batch, float *out_dev,
         } else {
             plan_blocks(ctx, facts, out_stride, rows, batch_span(ctx, facts, out_stride), plan);
             // length-sorted batches: the plan weighed against each lane mapping in as many rounds as it takes, by the
-            // lengths and events of the rows (launch_plan.cpp, "Ragged batches")
+            // lengths and events of the rows (family_cost.cpp, "Ragged batches")
             // (the batch itself, or the first of its row groups: those rows hold launch slots 0 .. rows - 1 of the sorted order)
             if (use_perm && view.slot0 == 0) ragged_plan(ctx, facts, out_stride, rows, plan);
         }

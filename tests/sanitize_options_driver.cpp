@@ -1,5 +1,5 @@
 // sanitize_options_driver.cpp — grail_set_option / grail_get_option under AddressSanitizer + UBSan, and their transcript.
-// Built by tests/test_sanitizers.py from grail-rs_amd/csrc/{options,voice_analysis,voice_host,launch_plan}.cpp with g++
+// Built by tests/test_sanitizers.py from grail-rs_amd/csrc/{options,voice_analysis,voice_host}.cpp and the planner's units with g++
 // (those units make no HIP call); the error helpers of grail_api.cpp are defined here.  Neither entry point needs a
 // device: a default-constructed grail_ctx that plans for 256 compute units suffices (as grail_plan_blocks has one).  The
 // context owns its HIP resources by type, so its destructor names HIP entry points: tests/fake_hip.h defines them, and

@@ -1,7 +1,7 @@
 // sanitize_plan_driver.cpp — the host launch policy under AddressSanitizer + UBSan: voice analysis (warm-up lengths,
 // sharpness), time-split grids and the block planner, fed random and extreme arguments through their C entry points.
-// Built by tests/test_sanitizers.py from grail-rs_amd/csrc/{launch_plan,voice_analysis,voice_host}.cpp with g++ (those
-// units make no HIP call); the three error helpers of grail_api.cpp are defined here.  Invariants checked: a plan's
+// Built by tests/test_sanitizers.py with g++ from the planner's units (family_choice, family_cost, dispatch_model,
+// launch_plan) and {voice_analysis,voice_host}.cpp of grail-rs_amd/csrc (those units make no HIP call); the three error helpers of grail_api.cpp are defined here.  Invariants checked: a plan's
 // rows add up, grids are increasing multiples of 64 inside the span, sharpness / warm-up never trap on NaN or Inf.
 #include <cmath>
 #include <cstdint>

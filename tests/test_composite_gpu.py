@@ -381,7 +381,7 @@ def _speech_like(n_utt, n_voices, seed=13):
 def test_ragged_batches_take_wider_mappings_in_several_rounds(gpu_ctx, small_machine, n_voices, fast):
     """A machine's worth of utterances (4 CUs: 1 024) that differ in length by a factor of ten.  Laid out for one wave per
     SIMD (one lane per utterance) the launch lasts as long as its longest utterance; option "ragged_plan" weighs that
-    against wider mappings in several rounds by the rows' lengths and events and takes one of them (launch_plan.cpp,
+    against wider mappings in several rounds by the rows' lengths and events and takes one of them (family_cost.cpp,
     "Ragged batches"; on the whole device: profiles/r04_ragged_plan.txt).  Exact: the oracle's bits whichever way;
     fast: within the tolerance — or, where events this dense make an exact mapping the cheaper one, the oracle's bits."""
     voices = W.single_voice() if n_voices == 1 else W.preset_voices(8)

@@ -1224,7 +1224,7 @@ def test_every_fast_family_on_a_speech_like_corpus(gpu_ctx, family, n_voices):
 @pytest.mark.parametrize("n_voices,lanes", [(1, 2), (1, 4), (8, 4), (8, 8)])
 def test_two_waves_per_simd_instantiations_give_the_same_bits(gpu_ctx, n_voices, lanes):
     """A tolerance-mode launch on 2 / 4 / 8 lanes per utterance with more wavefronts than the device has SIMDs takes the
-    instantiations built for two wavefronts per SIMD (256 registers, no AGPR claim: csrc/launch_plan.cpp family_cohabits;
+    instantiations built for two wavefronts per SIMD (256 registers, no AGPR claim: csrc/family_cost.cpp family_cohabits;
     the device made small with "assume_compute_units").  Same source, same operations in the same order: the rows are
     bit-identical to the one-wave kernels' (option "two_waves_per_simd" = 0), and within the tolerance of the oracle."""
     voices = W.single_voice() if n_voices == 1 else W.preset_voices(8)

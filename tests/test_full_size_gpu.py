@@ -165,7 +165,7 @@ def test_the_speech_like_corpus_at_full_size(gpu_ctx, n_voices):
 @pytest.mark.perf
 def test_two_rounds_of_the_device_in_packed_launch_order(gpu_ctx):
     """131 072 speech-like utterances (phonemes of 10 - 40 ms, rows of 0.12 - 0.95 s) on the REAL device: two one-wave
-    workgroups per SIMD on one lane per utterance, launched in the packed order (launch_plan.cpp, "The workgroup
+    workgroups per SIMD on one lane per utterance, launched in the packed order (dispatch_model.cpp, "The workgroup
     dispatcher").  The order of a launch's workgroups moves no bit: all 131 072 digests equal those of the longest-first
     order, 40 rows spread over the batch == the oracle; and the packed order is the faster one on this device (kernel
     time, best of three each; skipped, not failed, where the device's clocks do not hold still)."""

@@ -1,5 +1,5 @@
 """Option "packed_launch_order" on the device: a launch of more one-wave-per-SIMD workgroups than the device holds at once,
-of rows that differ in length, takes its workgroups in the packed order (launch_plan.cpp, "The workgroup dispatcher").  The
+of rows that differ in length, takes its workgroups in the packed order (dispatch_model.cpp, "The workgroup dispatcher").  The
 order of a launch's workgroups cannot change a bit — a row's samples are a function of (segments, voice, seed), reference
 src/lib.rs:594, :786-797 — and does not: every row against the plain order's digests and sampled rows against the oracle,
 exact and tolerance arithmetic, f32 and i16, for a device planned as one XCC (assume_compute_units = 32: 128 SIMDs, four

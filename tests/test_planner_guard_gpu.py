@@ -1,4 +1,4 @@
-"""An on-device guard for the launch planner.  launch_plan.cpp chooses kernel families by a cost model whose constants were
+"""An on-device guard for the launch planner.  family_choice.cpp chooses kernel families by a cost model (family_cost.cpp) whose constants were
 measured on one box of one ROCm release (milliseconds per round of each lane mapping, per chunk of the time-split grid,
 per workgroup of the scan kernel): a driver, compiler or clock change that moves one family and not another would show up
 in a user's latency and nowhere else.  This test times, on the device it runs on, the library's own choice against every
@@ -115,7 +115,7 @@ RAGGED_CELLS = [(65536, 1.0, 1), (65536, 0.1, 1), (32768, 1.0, 1), (65536, 1.0, 
 def test_the_ragged_planners_choice_is_within_ten_percent_of_the_best_pinned_mapping(gpu_ctx):
     """The same guard for batches whose rows differ in length (speech-like corpus: phonemes of 40 - 160 ms and of 4 - 16 ms),
     where the planner weighs lane mappings in several rounds by the rows' lengths and events and by what two waves per SIMD
-    gain (launch_plan.cpp ragged_cost: constants fitted on one box): the library's choice against every pinned lane mapping,
+    gain (family_cost.cpp ragged_cost: constants fitted on one box): the library's choice against every pinned lane mapping,
     exact and tolerance arithmetic.  A fast request served by an exact mapping counts as the library's choice."""
     ctx = gpu_ctx
     saved = {k: ctx.get_option(k) for k in DEFAULTS}

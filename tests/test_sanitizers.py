@@ -8,6 +8,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the launch planner's units (csrc/launch_plan.h)
+PLANNER_UNITS = ("family_choice.cpp", "family_cost.cpp", "dispatch_model.cpp", "launch_plan.cpp")
 
 
 @pytest.mark.timeout(300)
@@ -35,14 +37,14 @@ def test_oracle_and_host_sources_under_asan_ubsan(tmp_path):
 
 @pytest.mark.timeout(300)
 def test_launch_policy_under_asan_ubsan(tmp_path):
-    """launch_plan.cpp + voice_analysis.cpp make no HIP call: built with g++ and the sanitizers, then fed random and
+    """The planner's units + voice_analysis.cpp make no HIP call: built with g++ and the sanitizers, then fed random and
     hostile arguments through grail_plan_blocks / grail_time_split_grid / grail_fast_sharpness / grail_time_split_warmup
     (tests/sanitize_plan_driver.cpp checks the invariants of what comes back)."""
     san = ["-fsanitize=address,undefined,float-cast-overflow", "-fno-sanitize-recover=undefined", "-g", "-O1",
            "-ffp-contract=off", "-std=c++17", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
     csrc = os.path.join(ROOT, "grail-rs_amd", "csrc")
     objs = []
-    for name in (os.path.join(csrc, "launch_plan.cpp"), os.path.join(csrc, "voice_analysis.cpp"),
+    for name in (*(os.path.join(csrc, unit) for unit in PLANNER_UNITS), os.path.join(csrc, "voice_analysis.cpp"),
                  os.path.join(csrc, "voice_host.cpp"), os.path.join(ROOT, "tests", "sanitize_plan_driver.cpp")):
         o = str(tmp_path / (os.path.basename(name) + ".o"))
         subprocess.check_call(["g++", *san, "-c", name, "-o", o])
@@ -67,7 +69,7 @@ def test_options_under_asan_ubsan_repeat_the_recorded_transcript(tmp_path):
     csrc = os.path.join(ROOT, "grail-rs_amd", "csrc")
     objs = []
     for name in (os.path.join(csrc, "options.cpp"), os.path.join(csrc, "voice_analysis.cpp"),
-                 os.path.join(csrc, "voice_host.cpp"), os.path.join(csrc, "launch_plan.cpp"),
+                 os.path.join(csrc, "voice_host.cpp"), *(os.path.join(csrc, unit) for unit in PLANNER_UNITS),
                  os.path.join(ROOT, "tests", "sanitize_options_driver.cpp")):
         o = str(tmp_path / (os.path.basename(name) + ".o"))
         subprocess.check_call(["g++", *san, "-c", name, "-o", o])

@@ -10,7 +10,7 @@ arithmetic: the project's tolerance, i16 rows the conversion of the f32 rows of 
 
 Cells the library has no kernel for are left out, each with the reason beside the table it would stand in:
   * exact lane kernels for two waves per SIMD exist for two lanes with four formants laid out and for four lanes
-    (launch_plan.cpp family_cohabits): none for eight lanes, none for two lanes with eight formants;
+    (family_cost.cpp family_cohabits): none for eight lanes, none for two lanes with eight formants;
   * the second tolerance tier has one-lane kernels only ("arithmetic" = 2 on a pinned wider mapping runs the exact kernels);
   * the time-split grid needs 512 samples of span per chunk and the span is capped at out_stride: capacities of 1021 and
     1024 give no grid of two chunks, and the pipelined exact workgroups run; a capacity can never equal a bound of its own
@@ -180,7 +180,7 @@ def _cells():
     exact = {"hasnt": ("FAST", "PIPE", "STREAM", "SPLIT", "MID")}
     # -- exact arithmetic ----------------------------------------------------------------------------------------------
     # lane kernels with four formants laid out, both ways of dividing alpha out (eight lanes lay out eight formants
-    # whatever the voices: launch_plan.cpp choose_family)
+    # whatever the voices: family_choice.cpp choose_family)
     for L in (2, 4, 8):
         for corpus, any_blend in (("lean4", False), ("lean4_anybl", True)):
             w = dict(exact, L=L, has=("NFA=4" if L < 8 else "NFA=8",) + (("ANYBL",) if any_blend else ()))

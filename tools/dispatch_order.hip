@@ -1,7 +1,7 @@
 // dispatch_order.hip — how the hardware hands workgroups to SIMDs when a launch has more one-wave workgroups than the device
 // has SIMDs and each holds a SIMD alone (512 registers, like the one-lane synthesis kernels).  Workgroup b spins for
 // cost_us[b] microseconds and records where and when it ran: XCC, SE / CU / SIMD (HW_ID), start and end (s_memrealtime,
-// 100 MHz).  tools/dispatch_order.py feeds it launch orders and checks the list-scheduling model of launch_plan.cpp.
+// 100 MHz).  tools/dispatch_order.py feeds it launch orders and checks the list-scheduling model of dispatch_model.cpp.
 // build: hipcc --offload-arch=gfx950 -O2 tools/dispatch_order.hip -o tools/dispatch_order.bin
 // usage: dispatch_order.bin costs.u32 records.u64 [waves per workgroup: 1 (default) or 4]   (records: blocks x {start, end, hw_id, xcc_id})
 #include <hip/hip_runtime.h>

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """How the hardware hands one-wave workgroups to SIMDs (tools/dispatch_order.hip), against the list-scheduling model of
-launch_plan.cpp ("waves are handed to the SIMDs in launch order as they fall free").  Workgroups spin for the time the waves
+family_cost.cpp ("waves are handed to the SIMDs in launch order as they fall free").  Workgroups spin for the time the waves
 of a speech-like batch would take (scaled), launched (a) longest first and (b) in the packed order of
 tools/packed_order_experiment.py; the records say which XCC / CU / SIMD ran each workgroup, from when to when.
 Reports: workgroup -> XCC mapping; how many workgroups ran per SIMD; the realised makespan against the dispatcher model's

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Fits the ragged planner's model of the tolerance-mode lane kernels (launch_plan.cpp ragged_wave_ms fast branch, and the
+"""Fits the ragged planner's model of the tolerance-mode lane kernels (family_cost.cpp ragged_wave_ms fast branch, and the
 two-waves-per-SIMD simulation of ragged_cost) to pinned-mapping measurements (tools/ragged_fit_collect.sh, once with option
 "two_waves_per_simd" = 0 and once with 1).  Model of one wave alone on its SIMD: its longest row's samples at the mapping's
 aligned rate x m, plus c per event (segment boundaries and kinks of alpha) of its rows.  One wave per SIMD: waves go to the

@@ -1,5 +1,5 @@
 #!/bin/bash
-# A/B of option "ragged_plan" (launch_plan.cpp, "Ragged batches") on the speech-like corpus (tools/speech_like_bench.py; also with
+# A/B of option "ragged_plan" (family_cost.cpp, "Ragged batches") on the speech-like corpus (tools/speech_like_bench.py; also with
 # every length times 0.4 / 0.1, and on small batches) and on the ragged bench corpus (tools/ragged_bench.py): every line once with the
 # one-round launch policy, once with the plan weighed by the rows' lengths and events.
 # usage: bash tools/ragged_plan_ab.sh > gpurun_out/ragged_plan.txt
