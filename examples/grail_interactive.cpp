@@ -13,11 +13,15 @@
 // Without a sound card time is the audio itself: a line "@1.5 text" arrives once 1.5 s of audio have been rendered, a line
 // without a stamp arrives at once.  After the last line has been spoken the session runs `tail` seconds longer (the
 // reference never ends) and the source is closed.
-//   usage: grail_interactive [--band LO HI [--taps K]] [chunk_samples] [tail_seconds] < script > out.f32
+//   usage: grail_interactive [--band LO HI [--taps K]] [--rate R] [chunk_samples] [tail_seconds] < script > out.f32
 // --band LO HI: every pulled chunk goes through a filter stream (the Kaiser-windowed band-pass LO .. HI Hz of
 // grail_fir_design, K taps, 255 unless --taps says otherwise, at its zero-delay origin) before it leaves the device, and when
 // the chain has ended the filter rings out: the output is what grail_fir_async gives for the whole session, K / 2 samples
 // longer than the session.
+// --rate R: every pulled chunk, after --band if that is given, goes through a resample stream from the voice's rate to R Hz
+// before it leaves the device.  When the chain has ended the tails are flushed in chain order: the filter's tail is fed to
+// the resampler, then the resampler's own tail.  The output is what grail_resample_async gives for the whole (filtered)
+// session.
 // Every phoneme fed is reported on stderr ("fed <phoneme> at <sample>"), so that a test can render the same list with
 // the oracle in one piece and compare bit for bit.
 #include <cstdio>
@@ -64,7 +68,7 @@ int main(int argc, char **argv)
 {
     std::vector<const char *> plain;
     double lo = -1.0, hi = -1.0;
-    long taps = 0;
+    long taps = 0, rate = 0;
     bool usage = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
@@ -79,6 +83,12 @@ int main(int argc, char **argv)
             taps = std::strtol(argv[i + 1], &end, 10);
             usage = usage || end == argv[i + 1] || *end || taps < 3 || taps > GRAIL_FIR_TAPS_MAX || taps % 2 == 0;
             i += 1;
+        } else if (a == "--rate" && i + 1 < argc) {
+            rate = std::strtol(argv[i + 1], &end, 10);
+            // (the voice's own rate is refused with the others: equal rates are no conversion)
+            usage = usage || end == argv[i + 1] || *end || rate < 1 || rate > 0xFFFFFFFFl ||
+                    grail_resample_ratio((uint32_t)grail::voices::generic().sample_rate, (uint32_t)rate, nullptr, nullptr, nullptr) != GRAIL_OK;
+            i += 1;
         } else if (a.rfind("--", 0) == 0) {
             usage = true;
         } else {
@@ -90,7 +100,7 @@ int main(int argc, char **argv)
     const double tail = plain.size() > 1 ? std::strtod(plain[1], nullptr) : 1.0;
     // (a chunk of 0 samples — or text strtoul makes 0 of — would never feed the stream)
     if (usage || plain.size() > 2 || chunk == 0 || !(tail >= 0.0) || (taps && !band) || (band && !(lo >= 0.0 && lo < hi))) {
-        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [samples per pull >= 1 (default 441)] "
+        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--rate R] [samples per pull >= 1 (default 441)] "
                              "[seconds of tail >= 0 (default 1)]\n");
         return 2;
     }
@@ -104,6 +114,8 @@ int main(int argc, char **argv)
             sets.push_back(gpu.fir_set({grail::fir_design((uint32_t)voice.sample_rate, lo, hi, taps ? (uint32_t)taps : 255u)}));
             filters.push_back(gpu.fir_stream(sets[0], 1));
         }
+        std::vector<grail::ResampleStream> resamplers;
+        if (rate) resamplers.push_back(gpu.resample_stream((uint32_t)voice.sample_rate, (uint32_t)rate, 1));
         std::vector<Line> script;
         std::string raw;
         while (std::getline(std::cin, raw)) {                        // interactive.rs:77-81
@@ -131,7 +143,9 @@ int main(int argc, char **argv)
             }
             uint32_t rendered = 0;                                    // what the chain rendered in this pull
             std::vector<float> part;
-            if (band) {
+            if (rate) {
+                part = chain.next(band ? &filters[0] : nullptr, resamplers[0], &rendered);    // ... filtered and resampled where it lay
+            } else if (band) {
                 part = chain.next(filters[0], &rendered);            // ... filtered where it lay
             } else {
                 part = chain.next();
@@ -167,11 +181,21 @@ int main(int argc, char **argv)
             ++fed;
         }
         if (band) {                                                   // the chain has ended: the filter rings out
-            const std::vector<float> rest = filters[0].finish().at(0);
+            std::vector<float> rest = filters[0].finish().at(0);
+            if (rate) rest = resamplers[0].next({rest}).at(0);        // ... into the resampler, the next stage of the chain
             std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
             written += rest.size();
-            std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps): %zu samples written\n", lo, hi, (double)voice.sample_rate,
-                         filters[0].tail() + 1, written);
+            if (rate)
+                std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps)\n", lo, hi, (double)voice.sample_rate, filters[0].tail() + 1);
+            else
+                std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps): %zu samples written\n", lo, hi,
+                             (double)voice.sample_rate, filters[0].tail() + 1, written);
+        }
+        if (rate) {                                                   // ... and the resampler's own tail
+            const std::vector<float> rest = resamplers[0].finish().at(0);
+            std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
+            written += rest.size();
+            std::fprintf(stderr, "Resampled %g -> %ld Hz: %zu samples written\n", (double)voice.sample_rate, rate, written);
         }
         std::fprintf(stderr, "session: %zu samples (%.2f s), %zu phonemes fed, %zu lines, buffers of %u\n", total,
                      total / voice.sample_rate, fed, script.size(), chunk);

@@ -36,6 +36,7 @@
 #include "division_window.h"
 #include "fir_plan.h"
 #include "kernels.h"
+#include "resample_plan.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)
 
@@ -355,6 +356,23 @@ struct grail_filter_stream {
     grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows] samples fed, bit 63: the row has ended
     grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
     std::vector<uint32_t> filter;     // (host copies, kept while the upload may be in flight)
+    // a finishing call's marks: the host copy is written again only once the upload before has been through
+    std::vector<uint8_t> mark;
+    grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows]
+    grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
+};
+
+// A stream of rows resampled call by call (transforms.cpp), all on one pair of rates: owned by the context's TransformState,
+// released by grail_resample_stream_close or with the context.  The kernels of resample_kernels.hip read and write its
+// state.  The table is the stream's own copy: the context's cache of four pairs may evict the pair while the stream is open.
+struct grail_resample_stream {
+    uint32_t up = 0, down = 0, taps = 0;
+    uint32_t n_rows = 0;
+    uint32_t ring_cap = 0;            // samples of a row's ring: resample_stream_ring_capacity(taps)
+    std::vector<int32_t> table;       // (host copy, kept while the upload may be in flight)
+    grail::host::DeviceBuffer<int32_t> d_table;     // [up][taps]
+    grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows][3] samples fed (bit 63: ended), the next output's input time, its phase
+    grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
     // a finishing call's marks: the host copy is written again only once the upload before has been through
     std::vector<uint8_t> mark;
     grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows]

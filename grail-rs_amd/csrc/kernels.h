@@ -269,4 +269,24 @@ hipError_t launch_fir_stream_advance(const float *in, uint64_t in_stride, const 
                                      const uint8_t *mark, bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
                                      uint32_t *nonfinite, hipStream_t stream);
 
+// sample-rate conversion of streams (resample_kernels.hip): rows fed call by call, all on one pair of rates.  state: device
+// [n_rows][RESAMPLE_STREAM_STATE_WORDS] = {the samples a row has been fed with bit 63 set once it has ended, the input time
+// floor(M D / U) of its next output M, the phase M D mod U}; ring: device [n_rows][ring_cap], ring_cap a power of two at
+// or above P - 1: sample t of a row at t mod ring_cap, +0.0 where it was not finite.  A call launches both kernels, the
+// first reads state and ring and writes out and cbad (one workgroup per (row, chunk of RESAMPLE_STREAM_CHUNK of the call's
+// outputs), grid_chunks: enough for the most outputs a row can have in the call, resample_plan.cpp), the second is the only
+// writer of state and ring.  finishing: in and in_len are not read (no samples are fed), rows with mark[u] != 0 (mark
+// NULL: every row) that have not ended write their tail and end; nonfinite is not written.
+constexpr uint32_t RESAMPLE_STREAM_STATE_WORDS = 3;
+hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D,
+                                  uint32_t P, const int32_t *table, const uint64_t *state, const float *ring, uint32_t ring_cap,
+                                  const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
+                                  uint32_t *cbad, hipStream_t stream);
+// ... and a row's out_len and count from its chunks, its last samples into the ring and its state advanced, one wave per
+// row (outputs may be NULL); a row that has ended and is fed: 0xFFFFFFFF and 0, nothing else
+hipError_t launch_resample_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U,
+                                          uint32_t D, uint32_t P, uint64_t *state, float *ring, uint32_t ring_cap, const uint8_t *mark,
+                                          bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                                          uint32_t *nonfinite, hipStream_t stream);
+
 }  // namespace grail

@@ -6,8 +6,10 @@
 // serial in the lane.  The kernel folds with the integers themselves, acc' = fma((double)N, v, acc'): every N * v is exact
 // (27 bits times 24) and nothing comes near the ends of binary64's range, so acc' is 2^26 acc bit for bit at every step,
 // and y = (float)(acc' * 2^-26) is the contract's one rounding.  No atomics, every store a plain vector store.
-// DESIGN.md §4.13.
+// DESIGN.md §4.13.  The same fold on rows fed chunk by chunk (grail_resample_stream_*, §4.16): a stretch staged from a row's
+// ring and the call's samples, the row's place kept as an input time and a phase.
 #include "kernels.h"
+#include "resample_plan.h"
 
 namespace grail {
 
@@ -200,6 +202,313 @@ __global__ __launch_bounds__(256) void resample_totals_kernel(const uint32_t *__
     if (nonfinite) nonfinite[u] = b;
 }
 
+// ---- streams (grail_resample_stream_*): rows fed chunk by chunk, DESIGN.md §4.16 ---------------------------------------------
+// A row's state is three 64-bit words: N = the samples fed so far with RS_STREAM_ENDED set once the row has ended; i =
+// floor(M D / U), the input time of the next output M; p = M D mod U, its phase (N U outgrows 64 bits long before N does, so
+// nothing here is computed from N U).  Its ring holds ring_cap samples (a power of two, at least P - 1): sample t of the row
+// lies at t mod ring_cap, not finite ones as +0.0.  In the frame of one call, local time = global time - N: v is the ring
+// below 0 (+0.0 before the row's first sample), the call's n samples from 0, +0.0 from n on (which only a finishing call
+// reaches: its n is 0).  Output r of the call starts at local time (i - N) + (p + r D) div U and phase (p + r D) mod U.
+constexpr uint64_t RS_STREAM_ENDED = 1ull << 63;
+constexpr uint32_t RS_STATE_WORDS = RESAMPLE_STREAM_STATE_WORDS;
+constexpr uint32_t RS_STREAM_PASSES = RESAMPLE_STREAM_CHUNK / RS_THREADS;     // at most four: rs_outputs' NPASS below
+static_assert(RS_STREAM_PASSES >= 1 && RS_STREAM_PASSES <= 4 && RESAMPLE_STREAM_CHUNK % RS_THREADS == 0, "the passes of a chunk");
+
+struct RsStreamRow {
+    uint64_t fed, i;        // N; the next output's input time
+    uint32_t p, n, count;   // its phase; the samples this call feeds, the outputs it writes
+    bool takes, refused;    // the call changes the row's state; the row has ended and is fed
+};
+__device__ __forceinline__ RsStreamRow rs_stream_row(const uint64_t *__restrict__ state, const uint32_t *__restrict__ in_len,
+                                                     uint64_t in_stride, const uint8_t *__restrict__ mark, bool finishing, uint64_t u,
+                                                     uint32_t U, uint32_t D, uint32_t half)
+{
+    RsStreamRow r;
+    const uint64_t w = state[RS_STATE_WORDS * u];
+    const bool ended = (w & RS_STREAM_ENDED) != 0;
+    r.fed = w & ~RS_STREAM_ENDED;
+    r.i = state[RS_STATE_WORDS * u + 1u];
+    r.p = (uint32_t)state[RS_STATE_WORDS * u + 2u];
+    int64_t T;              // the last input time an output of this call may start at
+    if (finishing) {
+        r.n = 0u;
+        r.refused = false;
+        r.takes = !ended && (!mark || mark[u]);
+        T = (int64_t)r.fed - 1;                                     // the samples to come are +0.0: every i0 <= N - 1
+    } else {
+        r.n = in_len[u] < in_stride ? in_len[u] : (uint32_t)in_stride;
+        r.refused = ended && r.n;
+        r.takes = !ended;
+        T = (int64_t)(r.fed + r.n) - 1 - (int64_t)half;             // output m needs sample i0 + h
+    }
+    // the outputs r with i + (p + r D) div U <= T: ceil(((T - i + 1) U - p) / D), T - i + 1 <= n + h < 2^33, U < 2^10
+    r.count = r.takes && T >= (int64_t)r.i ? (uint32_t)(((uint64_t)(T - (int64_t)r.i + 1) * U - r.p + (D - 1u)) / D) : 0u;
+    return r;
+}
+
+// The fold and the stores of a chunk of the stream kernel: resample_kernel's, line for line, for NPASS passes of 256 outputs
+// and with `tap` for what an unstaged tap reads.  It is a copy on purpose: with both kernels on one inline function
+// resample_kernel kept its registers and its LDS but ran 0.5 % slower at full size, more than its own runs differ, so
+// resample_kernel stays textually as it was (profiles/r17_resample_stream.txt).  Output r of the chunk,
+// r < count <= 256 NPASS, starts at input time i_base + (p_base + r D) div U and phase (p_base + r D) mod U; lane tid folds
+// r = tid + 256 j serially over ascending k, the outputs go through yout to `to` (the chunk's first output in the row),
+// four consecutive ones per lane.  Every lane of the workgroup comes here (there is a barrier inside).
+template <bool STAGED, bool VEC, int TAB, uint32_t NPASS, typename Tap>
+__device__ __forceinline__ void rs_outputs(float *yout, const float *stage, const int32_t *ltab, const int32_t *__restrict__ table,
+                                           uint32_t pitch, uint32_t tid, uint32_t count, int64_t i_base, uint32_t p_base,
+                                           int64_t s_base, uint32_t U, uint32_t D, uint32_t P, const Tap &tap, float *to)
+{
+    const uint32_t half = P >> 1;
+    if (count) {
+        double acc[NPASS];
+        uint32_t at[NPASS];                 // STAGED: the LDS word of tap 0; else unused
+        int64_t t_first[NPASS];             // the input time of tap 0
+        uint32_t tab[NPASS];                // the first word of the lane's row of the table
+#pragma unroll
+        for (uint32_t j = 0; j < NPASS; ++j) {
+            uint32_t r = tid + RS_THREADS * j;
+            r = r < count ? r : count - 1u;                         // (a lane past the chunk's last output repeats it, unstored)
+            const uint32_t off = p_base + r * D;                    // < 2^10 + 2^10 2^10
+            const uint32_t q = off / U, p = off - q * U;
+            t_first[j] = i_base + (int64_t)q + (int64_t)half;
+            at[j] = (uint32_t)(t_first[j] - s_base);
+            tab[j] = TAB == RS_TAB_UNIFORM ? 0u : p * pitch;
+            acc[j] = 0.0;
+        }
+        for (uint32_t k = 0; k < P; ++k) {
+#pragma unroll
+            for (uint32_t j = 0; j < NPASS; ++j) {
+                const float x = STAGED ? stage[at[j] - k] : tap(t_first[j] - (int64_t)k);
+                const int32_t num = TAB == RS_TAB_LDS ? ltab[tab[j] + k] : table[tab[j] + k];
+                acc[j] = __builtin_fma((double)num, (double)x, acc[j]);
+            }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < NPASS; ++j) yout[tid + RS_THREADS * j] = (float)(acc[j] * 1.4901161193847656e-08);   // 2^-26
+    }
+    __syncthreads();
+    // four consecutive outputs per lane; a row's last partial group goes out in 4-byte stores
+    if (4u * tid < count) {
+        to += 4u * tid;
+        if (VEC && 4u * tid + 4u <= count) {
+            *reinterpret_cast<float4 *>(to) = *reinterpret_cast<const float4 *>(yout + 4u * tid);
+        } else {
+#pragma unroll
+            for (uint32_t e = 0; e < 4; ++e)
+                if (4u * tid + e < count) to[e] = yout[4u * tid + e];
+        }
+    }
+}
+
+// What a tap of the stream kernel reads where the stretch is not staged: the ring below local time 0, the call's samples
+// from there, both addresses clamped and both loads issued, then selected.
+struct RsStreamTap {
+    const float *__restrict__ row;
+    const float *__restrict__ hist;
+    uint64_t fed, ring_mask;
+    int64_t t_lo, t_hi, t_top;      // how far back the row reaches; n - 1; max(n - 1, 0)
+    __device__ __forceinline__ float operator()(int64_t t) const
+    {
+        int64_t tc = t < 0 ? 0 : t;
+        tc = tc > t_top ? t_top : tc;
+        const float raw = row[tc];
+        const float old = hist[(fed + (uint64_t)t) & ring_mask];
+        const float cur = (t <= t_hi && rs_finite(raw)) ? raw : 0.0f;
+        return t < 0 ? (t >= t_lo ? old : 0.0f) : cur;
+    }
+};
+
+// resample_kernel with the row's state in place of m0 D and of the row's length: one workgroup = one (row, chunk of
+// RESAMPLE_STREAM_CHUNK of this call's outputs).  Reads the state and the ring, writes neither (resample_stream_advance_kernel,
+// queued behind it, is their only writer).  STAGED, VEC, TAB as in resample_kernel; the stretch is staged from the ring by
+// 4-byte loads and from the call's samples by 16-byte ones (VEC), no load behind a branch.  Chunk c counts the non-finite
+// samples among this call's inputs between its first output's time and the next chunk's, the last chunk to the end of them.
+// A streaming call is small (480 samples of 48 000 -> 16 000 are 160 outputs): the passes of 256 outputs past the chunk's
+// count are not run.
+template <bool STAGED, bool VEC, int TAB>
+__global__ __launch_bounds__(256) void resample_stream_kernel(const float *__restrict__ in, uint64_t in_stride,
+                                                              const uint32_t *__restrict__ in_len, uint32_t n_rows, uint32_t U,
+                                                              uint32_t D, uint32_t P, const int32_t *__restrict__ table,
+                                                              uint32_t stage_words, uint32_t grid_chunks,
+                                                              const uint64_t *__restrict__ state, const float *__restrict__ ring,
+                                                              uint32_t ring_cap, const uint8_t *__restrict__ mark, uint32_t finishing,
+                                                              float *__restrict__ out, uint64_t out_stride, uint32_t *__restrict__ cbad)
+{
+    extern __shared__ float smem[];
+    float *yout = smem, *stage = smem + RESAMPLE_STREAM_CHUNK;
+    int32_t *ltab = reinterpret_cast<int32_t *>(smem + RESAMPLE_STREAM_CHUNK + stage_words);
+    const uint32_t pitch = TAB == RS_TAB_LDS ? P + 1u : P;
+    const uint32_t tid = threadIdx.x;
+    const uint64_t u = blockIdx.x / grid_chunks;
+    const uint32_t c = (uint32_t)(blockIdx.x - u * grid_chunks);
+    if (u >= n_rows) return;
+    const uint32_t half = P >> 1;
+    const RsStreamRow r = rs_stream_row(state, in_len, in_stride, mark, finishing != 0u, u, U, D, half);
+    const int64_t n = r.n;
+    const uint64_t n_out = r.count;
+    const uint64_t m0 = (uint64_t)c * RESAMPLE_STREAM_CHUNK;
+    // a refused row and one with neither samples nor outputs have no chunk; chunk 0 of any other runs even with no output
+    // to write: it counts
+    if (r.refused || (n == 0 && n_out == 0) || (m0 >= n_out && c != 0u)) return;
+    const bool last = m0 + RESAMPLE_STREAM_CHUNK >= n_out;
+    const uint32_t count = m0 >= n_out ? 0u : (last ? (uint32_t)(n_out - m0) : RESAMPLE_STREAM_CHUNK);
+    const float *hist = ring + u * ring_cap;
+    const float *row = n ? in + u * in_stride : hist;               // (a call of no samples: a clamped load lands in the ring)
+    const uint64_t ring_mask = ring_cap - 1u;
+    const int64_t t_hi = n - 1, t_top = n ? n - 1 : 0;
+    const int64_t t_lo = -(int64_t)(P - 1u < r.fed ? P - 1u : r.fed);   // how far back the taps and the row reach
+
+    // the chunk's first output in the call's frame: a = p + m0 D above (i - N) U; every other is fewer than 2^20 further
+    const int64_t rel = (int64_t)(r.i - r.fed);                     // >= -h: what starts lower was written before
+    const uint64_t a0 = (uint64_t)r.p + m0 * D;
+    const int64_t i_base = rel + (int64_t)(a0 / U);
+    const uint32_t p_base = (uint32_t)(a0 % U);
+    // the call's samples this chunk counts non-finite ones in, cut to [0, n]
+    int64_t own_lo = c ? rel + (int64_t)((a0 + U - 1u) / U) : 0;
+    int64_t own_hi = last ? n : rel + (int64_t)((a0 + (uint64_t)RESAMPLE_STREAM_CHUNK * D + U - 1u) / U);
+    own_lo = own_lo < 0 ? 0 : (own_lo > n ? n : own_lo);
+    own_hi = own_hi < 0 ? 0 : (own_hi > n ? n : own_hi);
+    const uint32_t span = count ? (uint32_t)(((uint64_t)p_base + (uint64_t)(count - 1u) * D) / U) : 0u;
+    const int64_t s_lo = i_base + 1 - (int64_t)half, s_hi = i_base + (int64_t)span + (int64_t)half + 1;
+    const int64_t s_base = s_lo & ~(int64_t)3;
+    uint32_t bad = 0u;
+    int64_t counted_to = own_lo;            // what the staging has counted of [own_lo, own_hi)
+    if (STAGED && count) {
+        const uint32_t groups = (uint32_t)((s_hi - s_base + 3) >> 2);
+        const int64_t g_hi = t_top >> 2;
+        for (uint32_t gi = tid; gi < groups; gi += RS_THREADS) {
+            const int64_t t0 = s_base + 4 * (int64_t)gi;           // a multiple of 4: a group is all ring or all call
+            float x[4], old[4];
+            if (VEC) {
+                // the call's last group starts below n <= in_stride, a multiple of 4: inside the row
+                int64_t g = t0 >> 2;
+                g = g < 0 ? 0 : g;
+                g = g > g_hi ? g_hi : g;
+                const float4 v = *reinterpret_cast<const float4 *>(row + 4 * g);
+                x[0] = v.x, x[1] = v.y, x[2] = v.z, x[3] = v.w;
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    int64_t t = t0 + e;
+                    t = t < 0 ? 0 : t;
+                    t = t > t_top ? t_top : t;
+                    x[e] = row[t];
+                }
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) old[e] = hist[(r.fed + (uint64_t)(t0 + e)) & ring_mask];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int64_t t = t0 + e;
+                const bool inside = t >= 0 && t <= t_hi;            // (what a clamped load brought is outside)
+                const bool finite = rs_finite(x[e]);
+                bad += (inside && !finite && t >= own_lo && t < own_hi) ? 1u : 0u;
+                const float cur = (inside && finite) ? x[e] : 0.0f;
+                // the ring holds the last ring_cap >= P - 1 samples fed, already +0.0 where they were not finite
+                stage[4u * gi + e] = t < 0 ? (t >= t_lo ? old[e] : 0.0f) : cur;
+            }
+        }
+        counted_to = s_base + 4 * (int64_t)groups;
+        counted_to = counted_to < own_lo ? own_lo : counted_to;
+    }
+    // what the chunk owns past its stretch (a chunk that is not staged owns all of its samples here)
+    for (int64_t t = counted_to + tid; t < own_hi; t += RS_THREADS) bad += rs_finite(row[t]) ? 0u : 1u;
+    if (TAB == RS_TAB_LDS && count) {
+        for (uint32_t i = tid; i < U * P; i += RS_THREADS) {
+            const uint32_t p = i / P;
+            ltab[p * pitch + (i - p * P)] = table[i];
+        }
+    }
+    __syncthreads();
+
+    const RsStreamTap tap{row, hist, r.fed, ring_mask, t_lo, t_hi, t_top};
+    float *to = out + u * out_stride + m0;
+    const uint32_t passes = (count + RS_THREADS - 1u) / RS_THREADS;     // the same in every lane of the workgroup
+    if (passes <= 1u)
+        rs_outputs<STAGED, VEC, TAB, 1>(yout, stage, ltab, table, pitch, tid, count, i_base, p_base, s_base, U, D, P, tap, to);
+    else if (passes == 2u)
+        rs_outputs<STAGED, VEC, TAB, 2>(yout, stage, ltab, table, pitch, tid, count, i_base, p_base, s_base, U, D, P, tap, to);
+    else if (passes == 3u)
+        rs_outputs<STAGED, VEC, TAB, 3>(yout, stage, ltab, table, pitch, tid, count, i_base, p_base, s_base, U, D, P, tap, to);
+    else
+        rs_outputs<STAGED, VEC, TAB, RS_STREAM_PASSES>(yout, stage, ltab, table, pitch, tid, count, i_base, p_base, s_base, U, D, P, tap, to);
+    // the chunk's count: integers, so any order
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    __shared__ uint32_t red[RS_THREADS / 64];
+    if ((tid & 63u) == 0u) red[tid >> 6] = bad;
+    __syncthreads();
+    if (tid == 0u) cbad[u * grid_chunks + c] = red[0] + red[1] + red[2] + red[3];
+}
+
+// Behind resample_stream_kernel on the stream, one wave per row, the only writer of a stream's state: the row's numbers
+// from its chunks, the call's last min(n, ring_cap) samples into the ring at (N + t) mod ring_cap, then N + n (a finishing
+// call: the row ended) and the next output's i and p.  A row that has ended and is fed is refused: 0xFFFFFFFF, 0, its state
+// as it was.
+__global__ __launch_bounds__(256) void resample_stream_advance_kernel(const float *__restrict__ in, uint64_t in_stride,
+                                                                      const uint32_t *__restrict__ in_len, uint32_t n_rows, uint32_t U,
+                                                                      uint32_t D, uint32_t P, uint64_t *__restrict__ state,
+                                                                      float *__restrict__ ring, uint32_t ring_cap,
+                                                                      const uint8_t *__restrict__ mark, uint32_t finishing,
+                                                                      const uint32_t *__restrict__ cbad, uint32_t grid_chunks,
+                                                                      uint32_t *__restrict__ out_len, uint32_t *__restrict__ nonfinite)
+{
+    const uint64_t u = (uint64_t)blockIdx.x * (RS_THREADS / 64u) + (threadIdx.x >> 6);
+    const uint32_t lane = threadIdx.x & 63u;
+    if (u >= n_rows) return;
+    const RsStreamRow r = rs_stream_row(state, in_len, in_stride, mark, finishing != 0u, u, U, D, P >> 1);
+    if (r.refused) {
+        if (lane == 0u) {
+            if (out_len) out_len[u] = 0xFFFFFFFFu;
+            if (nonfinite) nonfinite[u] = 0u;
+        }
+        return;
+    }
+    uint32_t bad = 0u;
+    if (r.takes && r.n) {
+        const uint32_t chunks = r.count ? (r.count + RESAMPLE_STREAM_CHUNK - 1u) / RESAMPLE_STREAM_CHUNK : 1u;
+        for (uint32_t c = lane; c < chunks; c += 64u) bad += cbad[u * grid_chunks + c];
+        const float *row = in + u * in_stride;
+        float *hist = ring + u * ring_cap;
+        const uint32_t keep = r.n < ring_cap ? r.n : ring_cap;
+        for (uint32_t t = r.n - keep + lane; t < r.n; t += 64u) {
+            const float x = row[t];
+            hist[(r.fed + t) & (uint64_t)(ring_cap - 1u)] = rs_finite(x) ? x : 0.0f;
+        }
+    }
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    if (lane != 0u) return;
+    if (out_len) out_len[u] = r.count;
+    if (nonfinite) nonfinite[u] = bad;
+    if (r.takes) {
+        const uint64_t a = (uint64_t)r.p + (uint64_t)r.count * D;  // < 2^10 + 2^32 2^10
+        state[RS_STATE_WORDS * u] = finishing ? (r.fed | RS_STREAM_ENDED) : r.fed + r.n;
+        state[RS_STATE_WORDS * u + 1u] = r.i + a / U;
+        state[RS_STATE_WORDS * u + 2u] = a % U;
+    }
+}
+
+template <bool STAGED, bool VEC>
+void resample_stream_launch(int tab, uint32_t workgroups, uint32_t lds, hipStream_t stream, const float *in, uint64_t in_stride,
+                            const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t P, const int32_t *table,
+                            uint32_t stage_words, uint32_t grid_chunks, const uint64_t *state, const float *ring, uint32_t ring_cap,
+                            const uint8_t *mark, uint32_t finishing, float *out, uint64_t out_stride, uint32_t *cbad)
+{
+    if (tab == RS_TAB_UNIFORM)
+        hipLaunchKernelGGL((resample_stream_kernel<STAGED, VEC, RS_TAB_UNIFORM>), dim3(workgroups), dim3(RS_THREADS), lds, stream, in,
+                           in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, finishing,
+                           out, out_stride, cbad);
+    else if (STAGED && tab == RS_TAB_LDS)       // (the table goes to LDS only beside a staged stretch)
+        hipLaunchKernelGGL((resample_stream_kernel<STAGED, VEC, STAGED ? RS_TAB_LDS : RS_TAB_GLOBAL>), dim3(workgroups),
+                           dim3(RS_THREADS), lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks,
+                           state, ring, ring_cap, mark, finishing, out, out_stride, cbad);
+    else
+        hipLaunchKernelGGL((resample_stream_kernel<STAGED, VEC, RS_TAB_GLOBAL>), dim3(workgroups), dim3(RS_THREADS), lds, stream, in,
+                           in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, finishing,
+                           out, out_stride, cbad);
+}
+
 template <bool STAGED, bool VEC>
 void resample_launch(int tab, uint32_t workgroups, uint32_t lds, hipStream_t stream, const float *rows, uint64_t row_stride,
                      const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t P, const int32_t *table,
@@ -252,6 +561,48 @@ hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_
         resample_launch<false, true>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
     else
         resample_launch<false, false>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D,
+                                  uint32_t P, const int32_t *table, const uint64_t *state, const float *ring, uint32_t ring_cap,
+                                  const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
+                                  uint32_t *cbad, hipStream_t stream)
+{
+    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
+    if (workgroups == 0) return hipSuccess;
+    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    // the stretch, the table and the three ways to the coefficients as in launch_resample, for the stream's chunk
+    const uint64_t stretch = ((uint64_t)(U - 1u) + (uint64_t)(RESAMPLE_STREAM_CHUNK - 1u) * D) / U + P + RS_STAGE_SLACK;
+    const uint64_t staged_bytes = (RESAMPLE_STREAM_CHUNK + stretch) * 4u, table_bytes = (uint64_t)U * (P + 1u) * 4u;
+    const bool staged = staged_bytes <= RS_LDS_MAX;
+    const int tab = U == 1u ? RS_TAB_UNIFORM : (staged && staged_bytes + table_bytes <= RS_LDS_MAX ? RS_TAB_LDS : RS_TAB_GLOBAL);
+    const uint32_t stage_words = staged ? (uint32_t)stretch : 0u;
+    const uint32_t lds = (uint32_t)((staged ? staged_bytes : RESAMPLE_STREAM_CHUNK * 4u) + (tab == RS_TAB_LDS ? table_bytes : 0u));
+    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
+                     ((in_stride | out_stride) & 3u) == 0;
+    const uint32_t wg = (uint32_t)workgroups, fin = finishing ? 1u : 0u;
+    if (staged && vec)
+        resample_stream_launch<true, true>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
+    else if (staged)
+        resample_stream_launch<true, false>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
+    else if (vec)
+        resample_stream_launch<false, true>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
+    else
+        resample_stream_launch<false, false>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
+    return hipGetLastError();
+}
+
+hipError_t launch_resample_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U,
+                                          uint32_t D, uint32_t P, uint64_t *state, float *ring, uint32_t ring_cap, const uint8_t *mark,
+                                          bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
+                                          uint32_t *nonfinite, hipStream_t stream)
+{
+    if (n_rows == 0) return hipSuccess;
+    const uint32_t rows_per_group = RS_THREADS / 64u;
+    hipLaunchKernelGGL(resample_stream_advance_kernel, dim3(n_rows / rows_per_group + (n_rows % rows_per_group != 0u)), dim3(RS_THREADS), 0,
+                       stream, in, in_stride, in_len, n_rows, U, D, P, state, ring, ring_cap, mark, finishing ? 1u : 0u, cbad,
+                       grid_chunks, out_len, nonfinite);
     return hipGetLastError();
 }
 

@@ -2,12 +2,15 @@
 // -> up, down, taps), grail_resample_coefficients (the Kaiser-windowed sinc as integers over 2^26) and grail_resample_len.
 // The contract is include/grail_hip.h, "levels, continued: sample-rate conversion".  No HIP call, so it builds with g++
 // under AddressSanitizer and UBSan (tests/test_resample_sanitize.py), as mix_plan.cpp and level_gains.cpp do.
-// DESIGN.md §4.13.
+// DESIGN.md §4.13.  Also grail_resample_stream_len, the ring's capacity and the checks of the calls on resample streams
+// (tests/test_resample_stream_sanitize.py; §4.16).
 #include <cmath>
 #include <cstdint>
 
 #include "../../include/grail_hip.h"
 #include "fir_plan.h"
+#include "resample_plan.h"
+#include "row_checks.h"
 
 namespace grail {
 
@@ -72,9 +75,78 @@ int32_t numerator(int64_t j, uint32_t U, double f, double W, double i0_beta)
     return (int32_t)std::llrint(f * sinc * window * 67108864.0);
 }
 
+// E(N): the outputs known after N samples, 0 for N <= h, else ceil((N - h) U / D)
+unsigned __int128 known_outputs(uint64_t N, uint32_t U, uint32_t D, uint32_t P)
+{
+    const uint64_t h = P / 2;
+    return N <= h ? 0 : ((unsigned __int128)(N - h) * U + (D - 1u)) / D;
+}
+
+// the chunks of RESAMPLE_STREAM_CHUNK outputs of a row of at most `longest` of them
+uint64_t stream_chunks(uint64_t longest) { return (longest + grail::RESAMPLE_STREAM_CHUNK - 1u) / grail::RESAMPLE_STREAM_CHUNK; }
+
 }  // namespace
 
+namespace grail {
+
+uint32_t resample_stream_ring_capacity(uint32_t taps)
+{
+    uint32_t cap = 1;
+    while (cap < taps - 1u && cap < GRAIL_RESAMPLE_TABLE_MAX) cap <<= 1;        // (taps >= 2; U taps <= the table's limit)
+    return cap;
+}
+
+unsigned __int128 resample_stream_most(uint64_t n, uint32_t U, uint32_t D) { return ((unsigned __int128)n * U + (D - 1u)) / D; }
+
+uint64_t resample_stream_tail(uint32_t U, uint32_t D, uint32_t taps) { return (uint64_t)resample_stream_most(taps / 2u, U, D); }
+
+const char *resample_stream_next_error(const void *in, uint64_t in_stride, const void *in_len, uint32_t n_rows, const void *out,
+                                       uint64_t out_stride, uint32_t U, uint32_t D, uint64_t *chunks)
+{
+    *chunks = 0;
+    if ((unsigned __int128)out_stride < resample_stream_most(in_stride, U, D))
+        return "out_stride < ceil(in_stride * up / down) (a stream never cuts outputs short)";
+    // (a stream has rows: grail_resample_stream_open; a call feeds a row fewer than 2^32 samples: in_len is 32 bits wide)
+    const uint64_t longest = (uint64_t)resample_stream_most(in_stride < 0xFFFFFFFFull ? in_stride : 0xFFFFFFFFull, U, D);
+    const RowPair p{in, in_stride, in_len, n_rows, out, out_stride};
+    if (const char *why = row_pair_error(p, OutRule::always, OutRule::always,
+                                         "out_dev overlaps in_dev (a chunk reads what another would have written)", longest))
+        return why;
+    if (in_stride == 0) return nullptr;
+    *chunks = stream_chunks(longest);
+    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
+    return nullptr;
+}
+
+const char *resample_stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t taps,
+                                         uint64_t *chunks)
+{
+    *chunks = 0;
+    const uint64_t tail = resample_stream_tail(U, D, taps);         // at least 1
+    if (out_stride < tail) return "out_stride < ceil((taps / 2) * up / down), the longest tail";
+    if (!out) return ROWS_NULL;
+    if (!rows_span_fits(out_stride, n_rows)) return ROWS_SPAN;
+    *chunks = stream_chunks(tail);
+    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
+    return nullptr;
+}
+
+}  // namespace grail
+
 extern "C" {
+
+int grail_resample_stream_len(uint64_t fed_before, uint64_t n, uint32_t rate_in, uint32_t rate_out, int finishing, uint64_t *n_out)
+{
+    uint32_t U, D, P;
+    if (!n_out || !ratio(rate_in, rate_out, &U, &D, &P)) return GRAIL_ERR_INVALID_ARG;
+    if ((finishing && n) || fed_before > UINT64_MAX - n) return GRAIL_ERR_INVALID_ARG;
+    const unsigned __int128 before = known_outputs(fed_before, U, D, P);
+    const unsigned __int128 count = finishing ? grail::resample_stream_most(fed_before, U, D) - before
+                                              : known_outputs(fed_before + n, U, D, P) - before;
+    if (count > (unsigned __int128)UINT64_MAX) return GRAIL_ERR_INVALID_ARG;
+    *n_out = (uint64_t)count;
+    return GRAIL_OK;
+}
 
 int grail_resample_ratio(uint32_t rate_in, uint32_t rate_out, uint32_t *up, uint32_t *down, uint32_t *taps)
 {

@@ -1,7 +1,8 @@
 // transforms.cpp — the calls that read finished rows and write rows: grail_limit_async (limiter_kernels.hip),
 // grail_resample_async (resample_kernels.hip, the ratio and table resample_plan.cpp, §4.13), grail_fir_create / _free / _async
 // (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_filter_stream_open / _next_async / _finish_async /
-// _close (§4.15): their checks, their scratch, their launches.  What they check of a pair of rows is row_checks.h.
+// _close (§4.15) and grail_resample_stream_open / _next_async / _finish_async / _close (§4.16): their checks, their scratch,
+// their launches.  What they check of a pair of rows is row_checks.h.
 #include "api_internal.hpp"
 #include "row_checks.h"
 
@@ -54,6 +55,7 @@ struct TransformState : CtxPart {
     DeviceBuffer<uint32_t> d_firbad;        // FIR chunks: non-finite counts
     Owned<grail_fir> firs;                  // the filter sets alive
     Owned<grail_filter_stream> fir_streams; // ... and, after them (they die first), the filter streams open on them
+    Owned<grail_resample_stream> resample_streams;  // the resample streams open (each with its own copy of its pair's table)
 };
 
 // what the context has, made by nobody: NULL before the first call that needed it
@@ -71,6 +73,11 @@ grail_fir *own_set(grail_ctx *ctx, const grail_fir *set) { return peek(ctx) ? pe
 grail_filter_stream *own_stream(grail_ctx *ctx, const grail_filter_stream *fs)
 {
     return peek(ctx) ? peek(ctx)->fir_streams.find(fs) : nullptr;
+}
+
+grail_resample_stream *own_resample_stream(grail_ctx *ctx, const grail_resample_stream *rs)
+{
+    return peek(ctx) ? peek(ctx)->resample_streams.find(rs) : nullptr;
 }
 
 // the table of a pair of rates on the device: uploaded once per (U, D), the last four kept, the oldest evicted once
@@ -121,6 +128,28 @@ int fir_stream_call(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev
                                                    set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap, mark_dev, finishing,
                                                    st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "fir stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+// ... and of a call on a resample stream
+int resample_stream_call(grail_ctx *ctx, grail_resample_stream *rs, const float *in_dev, uint64_t in_stride,
+                         const uint32_t *in_len_dev, const uint8_t *mark_dev, bool finishing, uint64_t chunks, float *out_dev,
+                         uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev)
+{
+    TransformState *st;
+    int rc = state(ctx, &st);
+    if (rc) return rc;
+    if (chunks) {
+        if ((rc = st->d_rbad.reserve(ctx->stream, (size_t)rs->n_rows * (size_t)chunks))) return rc;
+        const hipError_t e = launch_resample_stream(in_dev, in_stride, in_len_dev, rs->n_rows, rs->up, rs->down, rs->taps,
+                                                    rs->d_table.get(), rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev,
+                                                    finishing, (uint32_t)chunks, out_dev, out_stride, st->d_rbad.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "resample stream kernel launch");
+    }
+    const hipError_t e = launch_resample_stream_advance(in_dev, in_stride, in_len_dev, rs->n_rows, rs->up, rs->down, rs->taps,
+                                                        rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev, finishing,
+                                                        st->d_rbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "resample stream advance kernel launch");
     return GRAIL_OK;
 }
 
@@ -358,6 +387,98 @@ int grail_filter_stream_finish_async(grail_ctx *ctx, grail_filter_stream *fs, co
     }
     return fir_stream_call(ctx, fs, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride,
                            out_len_dev, nullptr);
+}
+
+int grail_resample_stream_open(grail_ctx *ctx, uint32_t rate_in, uint32_t rate_out, uint32_t n_rows, grail_resample_stream **out)
+{
+    // (no context exists without a device)
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: NULL argument");
+    uint32_t U, D, P;
+    if (grail_resample_ratio(rate_in, rate_out, &U, &D, &P))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: the rates are equal, 0, or need more than 32 768 table entries");
+    if (n_rows == 0) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: n_rows is 0");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_resample_stream> rs(new (std::nothrow) grail_resample_stream());
+    if (!rs) return fail(GRAIL_ERR_OUT_OF_MEMORY, "resample stream");
+    rs->up = U, rs->down = D, rs->taps = P;
+    rs->n_rows = n_rows;
+    rs->ring_cap = resample_stream_ring_capacity(P);
+    rs->table.assign((size_t)U * P, 0);
+    if (grail_resample_coefficients(rate_in, rate_out, rs->table.data(), U * P))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: no table for this pair of rates");
+    HIP_TRY(upload(rs->d_table, rs->table.data(), rs->table.size(), ctx->stream));
+    HIP_TRY(rs->d_state.alloc((size_t)n_rows * RESAMPLE_STREAM_STATE_WORDS));
+    HIP_TRY(rs->d_ring.alloc((size_t)n_rows * rs->ring_cap));
+    HIP_TRY(rs->d_mark.alloc(n_rows));
+    // no sample fed, no row ended, the next output is output 0; the ring is never read before it is written, zeroed all the same
+    HIP_TRY(hipMemsetAsync(rs->d_state.get(), 0, (size_t)n_rows * RESAMPLE_STREAM_STATE_WORDS * sizeof(uint64_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(rs->d_ring.get(), 0, (size_t)n_rows * rs->ring_cap * sizeof(float), ctx->stream));
+    *out = st->resample_streams.add(std::move(rs));
+    return GRAIL_OK;
+}
+
+int grail_resample_stream_close(grail_ctx *ctx, grail_resample_stream *rs)
+{
+    if (!rs) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_close: ctx is NULL");
+    if (!own_resample_stream(ctx, rs))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_close: not an open resample stream of this context");
+    // (a kernel or an upload still queued may be using its state or its table)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    peek(ctx)->resample_streams.remove(rs);
+    return GRAIL_OK;
+}
+
+int grail_resample_stream_next_async(grail_ctx *ctx, grail_resample_stream *rs, const float *in_dev, uint64_t in_stride,
+                                     const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                     uint32_t *nonfinite_dev)
+{
+    if (!rs) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_next_async: the stream is NULL");
+    if (ctx && !own_resample_stream(ctx, rs))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_next_async: not an open resample stream of this context");
+    // (without a context the stream was not looked up and is not looked into: the checks run for one row at a ratio of 1 / 1,
+    // and the call ends at bind_device)
+    uint64_t chunks = 0;
+    if (const char *why = resample_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? rs->n_rows : 1u, out_dev, out_stride,
+                                                     ctx ? rs->up : 1u, ctx ? rs->down : 1u, &chunks))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_resample_stream_next_async: ") + why);
+    int rc = bind_device(ctx, "grail_resample_stream_next_async");
+    if (rc) return rc;
+    return resample_stream_call(ctx, rs, in_dev, in_stride, in_len_dev, nullptr, false, chunks, out_dev, out_stride, out_len_dev,
+                                nonfinite_dev);
+}
+
+int grail_resample_stream_finish_async(grail_ctx *ctx, grail_resample_stream *rs, const uint8_t *which, float *out_dev,
+                                       uint64_t out_stride, uint32_t *out_len_dev)
+{
+    if (!rs) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_finish_async: the stream is NULL");
+    if (ctx && !own_resample_stream(ctx, rs))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_finish_async: not an open resample stream of this context");
+    // (without a context: the checks of a ratio of 1 / 1 with two taps, a tail of one output, and the call ends at bind_device)
+    uint64_t chunks = 0;
+    if (const char *why = resample_stream_finish_error(out_dev, out_stride, ctx ? rs->n_rows : 1u, ctx ? rs->up : 1u,
+                                                       ctx ? rs->down : 1u, ctx ? rs->taps : 2u, &chunks))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_resample_stream_finish_async: ") + why);
+    int rc = bind_device(ctx, "grail_resample_stream_finish_async");
+    if (rc) return rc;
+    const uint8_t *mark_dev = nullptr;
+    if (which) {
+        // (the upload of the call before may still be reading the host copy)
+        if (rs->ev_mark.get())
+            HIP_TRY(hipEventSynchronize(rs->ev_mark));
+        else
+            HIP_TRY(rs->ev_mark.create());
+        rs->mark.assign(which, which + rs->n_rows);
+        HIP_TRY(hipMemcpyAsync(rs->d_mark.get(), rs->mark.data(), rs->n_rows, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipEventRecord(rs->ev_mark, ctx->stream));
+        mark_dev = rs->d_mark.get();
+    }
+    return resample_stream_call(ctx, rs, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, nullptr);
 }
 
 }  // extern "C"

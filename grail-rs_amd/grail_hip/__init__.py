@@ -84,6 +84,8 @@ EXPORTS = [
     "grail_fir_len", "grail_fir_design", "grail_fir_create", "grail_fir_free", "grail_fir_async",
     "grail_filter_stream_len", "grail_filter_stream_open", "grail_filter_stream_next_async", "grail_filter_stream_finish_async",
     "grail_filter_stream_close",
+    "grail_resample_stream_len", "grail_resample_stream_open", "grail_resample_stream_next_async",
+    "grail_resample_stream_finish_async", "grail_resample_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -391,6 +393,11 @@ def load():
     L.grail_filter_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
     L.grail_filter_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp]
     L.grail_filter_stream_close.argtypes = [vp, vp]
+    L.grail_resample_stream_len.argtypes = [u64, u64, C.c_uint32, C.c_uint32, C.c_int, vp]
+    L.grail_resample_stream_open.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_uint32, vp]
+    L.grail_resample_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    L.grail_resample_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp]
+    L.grail_resample_stream_close.argtypes = [vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -754,6 +761,14 @@ def resample_len(n, rate_in, rate_out):
     """grail_resample_len (pure host): ceil(n * up / down), the length of a row of n samples resampled."""
     out = C.c_uint64(0)
     _check(load().grail_resample_len(n, rate_in, rate_out, C.addressof(out)))
+    return out.value
+
+
+def resample_stream_len(fed_before, n, rate_in, rate_out, finishing=False):
+    """grail_resample_stream_len (pure host): the outputs a call on a resample stream writes for a row that was fed
+    fed_before samples before it: a `next` call that feeds n samples, or (finishing, n = 0) the tail of `finish`."""
+    out = C.c_uint64(0)
+    _check(load().grail_resample_stream_len(fed_before, n, rate_in, rate_out, 1 if finishing else 0, C.addressof(out)))
     return out.value
 
 
@@ -1349,6 +1364,60 @@ class Context:
     def fir_stream_close(self, fs):
         """grail_filter_stream_close: waits for the context's stream, then releases the stream."""
         _check(load().grail_filter_stream_close(self.handle, fs))
+
+    def resample_stream_open(self, rate_in, rate_out, n_rows):
+        """grail_resample_stream_open: a stream of n_rows rows resampled call by call from rate_in to rate_out.  Returns the
+        stream's handle, for resample_stream_next / _finish / _close; streams still open go with the context."""
+        out = C.c_void_p(None)
+        _check(load().grail_resample_stream_open(self.handle, rate_in, rate_out, n_rows, C.addressof(out)))
+        return out
+
+    def resample_stream_next_async(self, rs, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev=None,
+                                   nonfinite_dev=None):
+        """grail_resample_stream_next_async: every row is fed its next min(in_len_dev[u], in_stride) samples; the outputs that
+        became known go to out_dev + u * out_stride (out_stride >= resample_len(in_stride)).  Results are DEVICE arrays
+        [n_rows] (either may be None), queued on the context's stream; in_dev may be reused by what is queued behind the call."""
+        _check(load().grail_resample_stream_next_async(self.handle, rs, in_dev, in_stride, in_len_dev, out_dev, out_stride,
+                                                       out_len_dev, nonfinite_dev))
+
+    def resample_stream_next(self, rs, n_rows, in_dev, in_stride, in_len_dev, out_dev, out_stride):
+        """resample_stream_next_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a
+        row that had ended and was fed: (LIMIT_REFUSED, 0)."""
+        res = [np.zeros(n_rows, dtype=np.uint32) for _ in range(2)]
+        d = [self.device_alloc(n_rows * 4) for _ in res]
+        try:
+            self.resample_stream_next_async(rs, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d)
+            for dst, src in zip(res, d):
+                self.d2h(dst, src, n_rows * 4)
+        finally:
+            self.sync()
+            for p in d:
+                self.device_free(p)
+        return tuple(res)
+
+    def resample_stream_finish(self, rs, n_rows, out_dev, out_stride, which=None, out_len_dev=None):
+        """grail_resample_stream_finish_async: the rows marked in which (a host sequence, non-zero = marked; None: every row)
+        that have not ended write their tails and end.  out_len_dev None: waited for, and the tails' lengths (uint32, one
+        per row; 0 for rows not marked or ended before) returned."""
+        marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
+        assert marks is None or len(marks) == n_rows
+        own = None if out_len_dev is not None else self.device_alloc(n_rows * 4)
+        try:
+            _check(load().grail_resample_stream_finish_async(self.handle, rs, None if marks is None else marks.ctypes.data, out_dev,
+                                                             out_stride, out_len_dev if own is None else own))
+            if own is None:
+                return None
+            res = np.zeros(n_rows, dtype=np.uint32)
+            self.d2h(res, own, n_rows * 4)
+            return res
+        finally:
+            if own is not None:
+                self.sync()
+                self.device_free(own)
+
+    def resample_stream_close(self, rs):
+        """grail_resample_stream_close: waits for the context's stream, then releases the stream."""
+        _check(load().grail_resample_stream_close(self.handle, rs))
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max finite |x|, non-finite counts) per row, computed on the device (every length

@@ -686,6 +686,17 @@ impl Gpu {
         Ok(FirStream { gpu: self, fs, n_rows, tail: set.longest.saturating_sub(1), _set: set })
     }
 
+    /// A stream of `n_rows` rows resampled chunk by chunk from `rate_in` to `rate_out` (`grail_resample_stream_open`; the
+    /// contract is the header's section "levels, continued: sample-rate conversion of streams").  The chunks' outputs put
+    /// end to end, then the tail of [`ResampleStream::finish`], are the bits [`Gpu::resample`] gives for the whole rows.
+    /// Closed when dropped.
+    pub fn resample_stream(&self, rate_in: u32, rate_out: u32, n_rows: u32) -> Result<ResampleStream<'_>, Error> {
+        let (up, down, taps) = resample_ratio(rate_in, rate_out)?;
+        let mut rs: *mut sys::grail_resample_stream = std::ptr::null_mut();
+        check(unsafe { sys::grail_resample_stream_open(self.ctx, rate_in, rate_out, n_rows, &mut rs) })?;
+        Ok(ResampleStream { gpu: self, rs, n_rows, up, down, taps })
+    }
+
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
     /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
     /// non-finite samples.  One lane filters one row: many rows fill the device.
@@ -982,6 +993,123 @@ impl Drop for FirStream<'_> {
             sys::grail_filter_stream_close(self.gpu.ctx, self.fs);
         }
     }
+}
+
+/// Rows resampled chunk by chunk on a [`Gpu`]'s device ([`Gpu::resample_stream`]), their history and their place between
+/// two output samples resident in HBM between calls; `grail_resample_stream_close` when dropped.
+pub struct ResampleStream<'a> {
+    gpu: &'a Gpu,
+    rs: *mut sys::grail_resample_stream,
+    n_rows: u32,
+    up: u32,
+    down: u32,
+    taps: u32,
+}
+
+impl ResampleStream<'_> {
+    // the most outputs of a call that feeds `n` samples: ceil(n up / down)
+    fn most(&self, n: usize) -> usize {
+        ((n as u128 * self.up as u128 + (self.down as u128 - 1)) / self.down as u128) as usize
+    }
+
+    // one call on the stream: `chunks` fed (None: the rows marked in `which` finish); the outputs and the counts per row
+    fn call(&mut self, chunks: Option<&[Vec<f32>]>, which: Option<&[u8]>) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        let n = self.n_rows as usize;
+        let longest = chunks.map_or(0, |c| c.iter().map(|r| r.len()).max().unwrap_or(0));
+        let stride = (longest + 63) / 64 * 64;
+        let out_stride = (self.most(stride).max(self.most(self.taps as usize / 2)) + 63) / 64 * 64;
+        let lens: Vec<u32> = chunks.map_or(vec![0u32; n], |c| c.iter().map(|r| r.len() as u32).collect());
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let sizes = [n * stride.max(1) * 4, n * out_stride.max(1) * 4, n * 4, n * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, sizes[k], &mut d[k]));
+                }
+            }
+            if let Some(c) = chunks {
+                for (i, row) in c.iter().enumerate() {
+                    if r.is_ok() && !row.is_empty() {
+                        r = check(sys::grail_memcpy_h2d(ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                        row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                    }
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_h2d(ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_resample_stream_next_async(ctx, self.rs, d[0] as *const f32, stride as u64, d[2] as *const u32,
+                                                                    d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                                                    d[4] as *mut u32));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_d2h(ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+                }
+            } else if r.is_ok() {
+                r = check(sys::grail_resample_stream_finish_async(ctx, self.rs, which.map_or(std::ptr::null(), |w| w.as_ptr()),
+                                                                  d[1] as *mut f32, out_stride as u64, d[3] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 && out_lens[i] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad))
+    }
+
+    /// Feeds row `i` the samples `chunks[i]` (an empty chunk: the row pauses) and returns, per row, the outputs that became
+    /// known and the count of non-finite samples among those fed (`grail_resample_stream_next_async`).  A row that has
+    /// ended and is fed comes back empty, its state untouched.
+    pub fn next(&mut self, chunks: &[Vec<f32>]) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        if chunks.len() != self.n_rows as usize {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "ResampleStream::next: one chunk per row".to_string() });
+        }
+        self.call(Some(chunks), None)
+    }
+
+    /// Ends the rows marked in `which` (`None`: every row) and returns their tails: the outputs that still read samples
+    /// fed, with +0.0 to come (`grail_resample_stream_finish_async`); empty for rows not marked and rows ended before.
+    pub fn finish(&mut self, which: Option<&[bool]>) -> Result<Vec<Vec<f32>>, Error> {
+        if which.map_or(false, |w| w.len() != self.n_rows as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "ResampleStream::finish: one mark per row".to_string() });
+        }
+        let marks: Option<Vec<u8>> = which.map(|w| w.iter().map(|&m| m as u8).collect());
+        Ok(self.call(None, marks.as_deref())?.0)
+    }
+}
+
+impl Drop for ResampleStream<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_resample_stream_close(self.gpu.ctx, self.rs);
+        }
+    }
+}
+
+/// The outputs a call on a [`ResampleStream`] writes for a row that was fed `fed_before` samples before it: a `next` call
+/// that feeds `n` samples, or (`finishing`, `n` = 0) the tail (`grail_resample_stream_len`; pure host).
+pub fn resample_stream_len(fed_before: u64, n: u64, rate_in: u32, rate_out: u32, finishing: bool) -> Result<u64, Error> {
+    let mut n_out = 0u64;
+    check(unsafe { sys::grail_resample_stream_len(fed_before, n, rate_in, rate_out, finishing as i32, &mut n_out) })?;
+    Ok(n_out)
 }
 
 /// The outputs a call on a [`FirStream`] writes for a row that was fed `fed_before` samples before it: a `next` call that

@@ -280,6 +280,109 @@ private:
     uint32_t n_rows_ = 0, tail_ = 0;
 };
 
+// Rows resampled chunk by chunk on a Gpu's device (grail_resample_stream_open; the contract is the header's section "levels,
+// continued: sample-rate conversion of streams"), made by Gpu::resample_stream: move-only, closed with
+// grail_resample_stream_close.  The chunks' outputs put end to end, then the tails of finish(), are the bits Gpu::resample
+// gives for the whole rows.  It must not outlive its Gpu.
+class ResampleStream {
+public:
+    ResampleStream(grail_ctx *ctx, uint32_t rate_in, uint32_t rate_out, uint32_t n_rows)
+        : ctx_(ctx), rate_in_(rate_in), rate_out_(rate_out), n_rows_(n_rows)
+    {
+        uint32_t up = 0, down = 0, taps = 0;
+        check(grail_resample_ratio(rate_in, rate_out, &up, &down, &taps));
+        tail_ = most(taps / 2);
+        check(grail_resample_stream_open(ctx, rate_in, rate_out, n_rows, &rs_));
+    }
+    ~ResampleStream() { grail_resample_stream_close(ctx_, rs_); }
+    ResampleStream(ResampleStream &&o) noexcept
+        : ctx_(o.ctx_), rs_(std::exchange(o.rs_, nullptr)), rate_in_(o.rate_in_), rate_out_(o.rate_out_), n_rows_(o.n_rows_), tail_(o.tail_)
+    {
+    }
+    ResampleStream &operator=(ResampleStream &&o) noexcept
+    {
+        if (this != &o) {
+            grail_resample_stream_close(ctx_, rs_);
+            ctx_ = o.ctx_, rs_ = std::exchange(o.rs_, nullptr), rate_in_ = o.rate_in_, rate_out_ = o.rate_out_;
+            n_rows_ = o.n_rows_, tail_ = o.tail_;
+        }
+        return *this;
+    }
+    ResampleStream(const ResampleStream &) = delete;
+    ResampleStream &operator=(const ResampleStream &) = delete;
+    uint32_t rows() const { return n_rows_; }
+    uint64_t tail() const { return tail_; }      // ceil(h up / down): the room finish() needs per row
+    // ceil(n up / down): the room a call that feeds rows of stride n needs per row (grail_resample_len)
+    uint64_t most(uint64_t n) const
+    {
+        uint64_t out = 0;
+        check(grail_resample_len(n, rate_in_, rate_out_, &out));
+        return out;
+    }
+
+    // grail_resample_stream_next_async on device buffers (a chunk that a live stream has just rendered or a filter stream has
+    // just written, say): queued on the context's stream, nothing leaves the device
+    void next_async(const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride,
+                    uint32_t *out_len_dev, uint32_t *nonfinite_dev = nullptr)
+    {
+        check(grail_resample_stream_next_async(ctx_, rs_, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev, nonfinite_dev));
+    }
+
+    // Row i is fed chunks[i] (an empty chunk: the row pauses); returns the outputs that became known, per row.  A row that
+    // has ended and is fed comes back empty.
+    std::vector<std::vector<float>> next(const std::vector<std::vector<float>> &chunks)
+    {
+        if (chunks.size() != n_rows_) throw Error(GRAIL_ERR_INVALID_ARG, "ResampleStream::next: one chunk per row");
+        return call(&chunks, nullptr);
+    }
+    // The rows marked in which (empty: every row) end; returns their tails: the outputs that still read samples fed.
+    std::vector<std::vector<float>> finish(const std::vector<uint8_t> &which = {})
+    {
+        if (!which.empty() && which.size() != n_rows_) throw Error(GRAIL_ERR_INVALID_ARG, "ResampleStream::finish: one mark per row");
+        return call(nullptr, which.empty() ? nullptr : which.data());
+    }
+
+private:
+    std::vector<std::vector<float>> call(const std::vector<std::vector<float>> *chunks, const uint8_t *which)
+    {
+        const uint32_t n = n_rows_;
+        size_t longest = 0;
+        if (chunks)
+            for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
+        const uint64_t stride = (longest + 63) / 64 * 64, out_stride = (std::max<uint64_t>(most(stride), tail_) + 63) / 64 * 64;
+        std::vector<std::vector<float>> out(n);
+        std::vector<uint32_t> lens(n, 0u), out_lens(n, 0u);
+        for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
+        void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4 + 4, &d_in);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4 + 4, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_out_len);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc)
+            rc = chunks ? grail_resample_stream_next_async(ctx_, rs_, (const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out,
+                                                           out_stride, (uint32_t *)d_out_len, nullptr)
+                        : grail_resample_stream_finish_async(ctx_, rs_, which, (float *)d_out, out_stride, (uint32_t *)d_out_len);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)n * 4);
+        for (uint32_t i = 0; !rc && i < n; ++i) {
+            if (!out_lens[i] || out_lens[i] == GRAIL_LIMIT_REFUSED) continue;
+            out[i].resize(out_lens[i]);
+            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)out_lens[i] * 4);
+        }
+        for (void *p : {d_in, d_out, d_len, d_out_len})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
+    grail_ctx *ctx_ = nullptr;
+    grail_resample_stream *rs_ = nullptr;
+    uint32_t rate_in_ = 0, rate_out_ = 0, n_rows_ = 0;
+    uint64_t tail_ = 0;
+};
+
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
                     std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
@@ -645,6 +748,11 @@ public:
     {
         return FirStream(ctx_, set, n_rows, which);
     }
+    // n_rows rows resampled chunk by chunk from rate_in to rate_out, their state resident in HBM between the calls.
+    ResampleStream resample_stream(uint32_t rate_in, uint32_t rate_out, uint32_t n_rows) const
+    {
+        return ResampleStream(ctx_, rate_in, rate_out, n_rows);
+    }
 
     // Rows of samples filtered on the device (grail_fir_async; the contract is the header's section "levels, continued: FIR
     // filtering"), row i with filter which[i] of the set (which empty: filter 0 for every row).  ring_out: a row of n samples
@@ -1008,15 +1116,42 @@ public:
         if (n) check(grail_memcpy_d2h(ctx_, out.data(), d_filtered_, (size_t)n * sizeof(float)));
         return out;
     }
+    // ... through a resample stream of one row, behind `filter` if that is not NULL (a filter stream of one row): the
+    // three-stage live chain, every stage reading what the stage before wrote where it lies.  What comes back is what the
+    // resampler could write for the chunk, at its output rate.
+    std::vector<float> next(FirStream *filter, ResampleStream &resampler, uint32_t *rendered)
+    {
+        if ((filter && filter->rows() != 1) || resampler.rows() != 1)
+            throw Error(GRAIL_ERR_INVALID_ARG, "LiveStream::next: streams of one row");
+        if (filter && !d_filtered_) check(grail_device_alloc(ctx_, (size_t)stride_ * sizeof(float), &d_filtered_));
+        if (filter && !d_filtered_len_) check(grail_device_alloc(ctx_, sizeof(uint32_t), &d_filtered_len_));
+        const uint64_t room = (resampler.most(stride_) + 63) / 64 * 64;
+        if (!d_resampled_) check(grail_device_alloc(ctx_, (size_t)room * sizeof(float), &d_resampled_));
+        if (!d_resampled_len_) check(grail_device_alloc(ctx_, sizeof(uint32_t), &d_resampled_len_));
+        uint32_t n = 0;
+        check(grail_stream_next_async(ctx_, stream_, chunk_, (float *)d_out_, stride_, (uint32_t *)d_len_));
+        if (filter)
+            filter->next_async((const float *)d_out_, stride_, (const uint32_t *)d_len_, (float *)d_filtered_, stride_,
+                               (uint32_t *)d_filtered_len_);
+        resampler.next_async((const float *)(filter ? d_filtered_ : d_out_), stride_,
+                             (const uint32_t *)(filter ? d_filtered_len_ : d_len_), (float *)d_resampled_, room,
+                             (uint32_t *)d_resampled_len_);
+        check(grail_memcpy_d2h(ctx_, rendered, d_len_, sizeof *rendered));
+        check(grail_memcpy_d2h(ctx_, &n, d_resampled_len_, sizeof n));
+        std::vector<float> out(n);
+        if (n) check(grail_memcpy_d2h(ctx_, out.data(), d_resampled_, (size_t)n * sizeof(float)));
+        return out;
+    }
     uint32_t chunk() const { return chunk_; }
 
 private:
     void release()
     {
         if (stream_) grail_stream_close(ctx_, stream_);
-        for (void *p : {d_out_, d_len_, d_filtered_, d_filtered_len_})
+        for (void *p : {d_out_, d_len_, d_filtered_, d_filtered_len_, d_resampled_, d_resampled_len_})
             if (p) grail_device_free(ctx_, p);
         stream_ = nullptr; d_out_ = nullptr; d_len_ = nullptr; d_filtered_ = nullptr; d_filtered_len_ = nullptr;
+        d_resampled_ = nullptr; d_resampled_len_ = nullptr;
     }
     grail_ctx *ctx_;
     uint32_t chunk_;
@@ -1024,6 +1159,7 @@ private:
     grail_stream *stream_ = nullptr;
     void *d_out_ = nullptr, *d_len_ = nullptr;
     void *d_filtered_ = nullptr, *d_filtered_len_ = nullptr;      // next(filter, ...): made at its first call
+    void *d_resampled_ = nullptr, *d_resampled_len_ = nullptr;    // next(filter, resampler, ...): made at its first call
 };
 
 }  // namespace grail

@@ -1141,6 +1141,63 @@ int grail_filter_stream_finish_async(grail_ctx *ctx, grail_filter_stream *fs, co
  * grail_fir_free of it returns GRAIL_ERR_INVALID_ARG and frees nothing. */
 int grail_filter_stream_close(grail_ctx *ctx, grail_filter_stream *fs);
 
+/* ---- levels, continued: sample-rate conversion of streams ------------------------------------------------------------------------
+ * grail_resample_async takes finished rows.  A caller who pulls a live stream chunk by chunk and needs another rate (10 ms
+ * chunks at 48 000 for a telephone path at 8 000) resamples chunk by chunk with a RESAMPLE STREAM: n_rows independent rows,
+ * all on one pair of rates fixed when the stream is opened, their state resident in HBM between calls.  U, D, P and the
+ * table C are those of the one-shot section for the pair; h = P / 2.
+ * THE CONTRACT.  For any split of a row's samples into calls (calls of no samples included), the outputs of the `next`
+ * calls put end to end, followed by the tail that `finish` writes, are bit for bit what grail_resample_async writes for the
+ * whole row with an out_stride that cuts nothing; the sum of the calls' nonfinite counts is its count.
+ * One-shot output m reads the samples i0 - h + 1 .. i0 + h with i0 = floor(m D / U), so after N samples the outputs known
+ * are E(N) = 0 for N <= h, else ceil((N - h) U / D).
+ * STATE.  Per row: N, the samples fed so far (64 bits); whether the row has ended; the last P - 1 samples fed, already +0.0
+ * where they were not finite, in a ring of P - 1 samples rounded up to a power of two (at most 4 KB a row for the eight rates
+ * listed above, 128 KB at the table limit).
+ * A `next` call that feeds n samples writes outputs E(N) .. E(N + n) - 1 of the one-shot contract applied to everything fed
+ * so far (at most ceil(n U / D) of them; none while the row is short of h + 1 samples); `finish` writes the tail E(N) ..
+ * ceil(N U / D) - 1, the samples to come being +0.0: at most ceil(h U / D) outputs, none for a row that was fed nothing.
+ * A stream never cuts outputs short: out_stride is at least the most a call can write. */
+typedef struct grail_resample_stream grail_resample_stream;
+
+/* Pure host, 128-bit inside: *n_out = the outputs a call writes for a row that was fed fed_before samples before it:
+ * finishing = 0: a `next` call that feeds n samples; finishing != 0: `finish` (n must be 0).  GRAIL_ERR_INVALID_ARG,
+ * nothing written: a pair grail_resample_ratio refuses; n_out NULL; finishing with n != 0; fed_before + n or the count
+ * does not fit 64 bits. */
+int grail_resample_stream_len(uint64_t fed_before, uint64_t n, uint32_t rate_in, uint32_t rate_out, int finishing,
+                              uint64_t *n_out);
+/* A stream of n_rows rows from rate_in to rate_out.  The state (a ring, N, and the next output's place per row) and a copy
+ * of the pair's table belong to the stream, which belongs to the context: the stream does not depend on the four tables
+ * grail_resample_async keeps.  GRAIL_ERR_INVALID_ARG, nothing created: ctx or out NULL; a pair grail_resample_ratio
+ * refuses; n_rows = 0.  These come first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_resample_stream_open(grail_ctx *ctx, uint32_t rate_in, uint32_t rate_out, uint32_t n_rows,
+                               grail_resample_stream **out);
+/* Feeds every row u its next n = min(in_len_dev[u], in_stride) samples from in_dev + u * in_stride and writes the
+ * E(N + n) - E(N) outputs that became known to out_dev + u * out_stride, from index 0; queued on ctx's stream.  Results
+ * are DEVICE arrays [n_rows], either may be NULL: out_len[u] = that count; nonfinite[u] = the samples among this call's n
+ * that are not finite (a sample is counted in the call that fed it and never again; it enters as +0.0).  n = 0 is legal (a
+ * paused row): nothing is written, out_len 0.  A row that has ended and is fed n > 0 is refused: out_len =
+ * GRAIL_LIMIT_REFUSED, nonfinite 0, nothing written, its state as it was.  out_dev past out_len is never written.  in_dev
+ * may be reused by whatever is queued behind the call: the call copies what it keeps.  16-byte loads and stores where both
+ * bases are 16-byte aligned and both strides multiples of 4, 4-byte ones otherwise: same bits.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of this context (looked up, not looked
+ * into); a NULL buffer with samples to read or write, in_len_dev NULL; out_stride < ceil(in_stride U / D) =
+ * grail_resample_len(in_stride); overlapping ranges; an in_stride that allows 2^32 outputs or more in a call; more than 2^31
+ * chunks of GRAIL_RESAMPLE_CHUNK outputs.  These come first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_resample_stream_next_async(grail_ctx *ctx, grail_resample_stream *rs, const float *in_dev, uint64_t in_stride,
+                                     const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride,
+                                     uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+/* Flushes the rows marked in which (a HOST array [n_rows] of bytes, non-zero = marked; NULL = every row, as
+ * grail_filter_stream_finish_async): a marked row that has not ended writes its tail to out_dev + u * out_stride and ends.
+ * out_len (device [n_rows], may be NULL): the tail's length; 0, and nothing written, for unmarked rows and rows that had
+ * ended before.  The array may be reused at once.  GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open
+ * stream of this context; out_stride < ceil(h U / D); out_dev NULL. */
+int grail_resample_stream_finish_async(grail_ctx *ctx, grail_resample_stream *rs, const uint8_t *which, float *out_dev,
+                                       uint64_t out_stride, uint32_t *out_len_dev);
+/* Releases a stream once everything queued on ctx's stream is through; streams still open at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context. */
+int grail_resample_stream_close(grail_ctx *ctx, grail_resample_stream *rs);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);

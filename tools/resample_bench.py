@@ -9,7 +9,10 @@ and a lone track of 10^7 samples through the same three pairs (time is parallel:
 call and its sync, best of --reps after a warm-up.  Kernel times: run under `rocprofv3 --kernel-trace --stats -- python
 tools/resample_bench.py`; bytes fetched and written: under `rocprofv3 --pmc FETCH_SIZE -- python tools/resample_bench.py
 --only-resample` and the same with WRITE_SIZE (a run of its own each: the two do not fit one pass).  Prints one line per
-case and a JSON summary."""
+case and a JSON summary.
+  --step stream   the config-3 rows through a resample stream in 21 calls of 4 800 samples (100 ms), then
+                  the tail, for 48 000 -> 16 000 and 44 100 -> 48 000: wall clock around each call and its sync, summed, beside
+                  grail_resample_async on the same samples in the same process; the two outputs must be equal in every bit."""
 import argparse
 import ctypes as C
 import json
@@ -38,8 +41,103 @@ def best(fn, reps):
     return min(ms), ms
 
 
+STREAM_PAIRS = [(48000, 16000), (44100, 48000)]
+
+
+def stream_step(ctx, args, out):
+    chunk = 4800
+    ctx.set_voices(W.single_voice())
+    n = args.utts
+    segs, offs, vids, seeds = W.make_batch(n)
+    stride = W.max_samples()
+    out_stride = (max(G.resample_len(stride, *pair) for pair in STREAM_PAIRS) + 63) // 64 * 64
+    chunk_out = (max(max(G.resample_len(chunk, *pair), G.resample_stream_len(2 ** 20, 0, *pair, finishing=True)) for pair in STREAM_PAIRS) + 63) // 64 * 64
+    b = ctx.upload(segs, offs, vids, seeds)
+    d_rows, d_len = ctx.device_alloc(n * stride * 4), ctx.device_alloc(n * 4)
+    d_out, d_sout = ctx.device_alloc(n * out_stride * 4), ctx.device_alloc(n * out_stride * 4)
+    b.synthesize_async(d_rows, stride, d_len)
+    ctx.sync()
+    lens = np.zeros(n, np.uint32)
+    ctx.d2h(lens, d_len, n * 4)
+    if lens.min() != lens.max():
+        raise SystemExit("the stream step wants rows of one length (the aligned corpus): every row's chunk lands at the same offset")
+    length = int(lens[0])
+    d_ol, d_b, d_sol = ctx.device_alloc(n * 4), ctx.device_alloc(n * 4), ctx.device_alloc(n * 4)
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy2D.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    hip.hipDeviceSynchronize.argtypes = []
+    d_chunk, d_clen, d_cout = ctx.device_alloc(n * chunk * 4), ctx.device_alloc(n * 4), ctx.device_alloc(n * chunk_out * 4)
+    calls = -(-length // chunk)
+    out.update({"rows": n, "samples_per_row": length, "chunk": chunk, "calls": calls})
+
+    def copy2d(dst, dst_pitch, src, src_pitch, width):
+        if width:
+            # (a copy between device buffers may return before it is through, and the context's stream does not wait for it)
+            rc = hip.hipMemcpy2D(dst, dst_pitch * 4, src, src_pitch * 4, width * 4, n, 3)      # hipMemcpyDeviceToDevice
+            rc = rc or hip.hipDeviceSynchronize()
+            if rc:
+                raise SystemExit(f"hipMemcpy2D failed: {rc}")
+
+    for pair in STREAM_PAIRS:
+        def one_shot_call():
+            ctx.resample_async(d_rows, stride, d_len, n, pair[0], pair[1], d_out, out_stride, d_ol, d_b)
+            ctx.sync()
+
+        one_shot, one_shot_all = best(one_shot_call, args.reps)
+        runs = []
+        for _ in range(2):                                   # (the first run warms up)
+            rs = ctx.resample_stream_open(pair[0], pair[1], n)
+            ms, written = [], 0
+            for c in range(calls):
+                k = min(chunk, length - c * chunk)
+                copy2d(d_chunk, chunk, C.c_void_p(d_rows.value + 4 * c * chunk), stride, k)
+                ctx.h2d(d_clen, np.full(n, k, np.uint32), n * 4)
+                t0 = time.perf_counter()
+                ctx.resample_stream_next_async(rs, d_chunk, chunk, d_clen, d_cout, chunk_out, d_sol, None)
+                ctx.sync()
+                ms.append(1e3 * (time.perf_counter() - t0))
+                # (untimed: the call's outputs behind those of the calls before, as a consumer would put them)
+                count = G.resample_stream_len(c * chunk, k, *pair)
+                copy2d(C.c_void_p(d_sout.value + 4 * written), out_stride, d_cout, chunk_out, count)
+                written += count
+            t0 = time.perf_counter()
+            ctx.resample_stream_finish(rs, n, d_cout, chunk_out, None, d_sol)
+            ctx.sync()
+            ms.append(1e3 * (time.perf_counter() - t0))
+            count = G.resample_stream_len(length, 0, *pair, finishing=True)
+            copy2d(C.c_void_p(d_sout.value + 4 * written), out_stride, d_cout, chunk_out, count)
+            written += count
+            ctx.resample_stream_close(rs)
+            runs.append(ms)
+        if written != G.resample_len(length, *pair):
+            raise SystemExit(f"the stream wrote {written} outputs a row, the one-shot call {G.resample_len(length, *pair)}")
+        max_diff, _, mismatches = ctx.compare(d_sout, d_out, out_stride, d_ol, d_ol, n)
+        differ = int(np.count_nonzero((max_diff != 0) | (mismatches != 0)))
+        ms = runs[-1]
+        name = f"{pair[0]}->{pair[1]}"
+        out["cases"][name] = {"one_shot_ms": one_shot, "one_shot_ms_all": one_shot_all, "stream_ms": sum(ms),
+                              "stream_ms_runs": [sum(r) for r in runs], "stream_next_ms_median": float(np.median(ms[:-1])),
+                              "stream_finish_ms": ms[-1], "ratio": sum(ms) / one_shot, "mismatches": differ}
+        print(f"grail_resample_async {name}: {one_shot:.2f} ms; the same rows through a resample stream in {calls} calls of {chunk} samples: "
+              f"{sum(ms):.2f} ms = {sum(ms) / one_shot:.2f} x (a call {np.median(ms[:-1]):.3f} ms, finish {ms[-1]:.3f} ms); "
+              f"rows that differ from the one-shot output: {differ}")
+        if differ:
+            u = int(np.flatnonzero((max_diff != 0) | (mismatches != 0))[0])
+            a, b_ = np.zeros(written, np.float32), np.zeros(written, np.float32)
+            ctx.d2h(a, C.c_void_p(d_sout.value + 4 * u * out_stride), written * 4)
+            ctx.d2h(b_, C.c_void_p(d_out.value + 4 * u * out_stride), written * 4)
+            at = np.flatnonzero(a.view(np.uint32) != b_.view(np.uint32))
+            print(f"row {u}: {len(at)} of {written} outputs differ, the first at {at[:8]}: {a[at[:4]]} for {b_[at[:4]]}")
+        assert differ == 0, f"{name}: {differ} rows of the stream differ from the one-shot output"
+    for p in (d_ol, d_b, d_sol, d_chunk, d_clen, d_cout, d_rows, d_out, d_sout, d_len):
+        ctx.device_free(p)
+    b.free()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--step", choices=["rows", "stream"], default="rows", help="rows: the one-shot call at full size (the default); "
+                    "stream: the same rows through a resample stream, chunk by chunk")
     ap.add_argument("--utts", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--only-resample", action="store_true", help="render, then grail_resample_async 48 000 -> 16 000 alone (for a counter run)")
@@ -47,6 +145,12 @@ def main():
     if G.device_count() < 1:
         raise SystemExit("resample_bench needs a HIP device (no CPU fallback)")
     ctx = G.Context(0)
+    if args.step == "stream":
+        out = {"step": "stream", "cases": {}}
+        stream_step(ctx, args, out)
+        ctx.close()
+        print(json.dumps(out))
+        return
     ctx.set_voices(W.single_voice())
     n = args.utts
     segs, offs, vids, seeds = W.make_batch(n)
