@@ -60,9 +60,10 @@ void launch_one_exact(const SynthArgs &args, hipStream_t stream)
     if constexpr (MINW == 1 || L == 4) {
         if (args.any_blend)
             start<L, T, WAVES, MINW, false, true, true>(args, grid, block, stream);
-        else if (L == 1 && args.half_capable)
-            start<L, T, WAVES, MINW, false, true, false>(args, grid, block, stream);
-        else
+        else if (L == 1 && args.half_capable) {
+            // (taken at L = 1 only: no other mapping compiles the HALF-only kernel)
+            if constexpr (L == 1) start<L, T, WAVES, MINW, false, true, false>(args, grid, block, stream);
+        } else
             start<L, T, WAVES, MINW, false, false, false>(args, grid, block, stream);
     }
 }
