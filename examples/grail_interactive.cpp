@@ -13,14 +13,19 @@
 // Without a sound card time is the audio itself: a line "@1.5 text" arrives once 1.5 s of audio have been rendered, a line
 // without a stamp arrives at once.  After the last line has been spoken the session runs `tail` seconds longer (the
 // reference never ends) and the source is closed.
-//   usage: grail_interactive [--band LO HI [--taps K]] [--rate R] [chunk_samples] [tail_seconds] < script > out.f32
+//   usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [chunk_samples] [tail_seconds]
+//          < script > out.f32
 // --band LO HI: every pulled chunk goes through a filter stream (the Kaiser-windowed band-pass LO .. HI Hz of
 // grail_fir_design, K taps, 255 unless --taps says otherwise, at its zero-delay origin) before it leaves the device, and when
 // the chain has ended the filter rings out: the output is what grail_fir_async gives for the whole session, K / 2 samples
 // longer than the session.
-// --rate R: every pulled chunk, after --band if that is given, goes through a resample stream from the voice's rate to R Hz
+// --ceiling DB: every pulled chunk, after --band if that is given, goes through a limit stream that holds it under DB dBTP
+// with a look-ahead of 2^l samples (l = 8 unless --lookahead says otherwise) before it leaves the device; the output lags
+// the chain by 2^l + 10 samples, which the limiter's tail delivers at the end.  The output is what grail_limit_async gives
+// for the whole (filtered) session.
+// --rate R: every pulled chunk, after --band and --ceiling if those are given, goes through a resample stream from the voice's rate to R Hz
 // before it leaves the device.  When the chain has ended the tails are flushed in chain order: the filter's tail is fed to
-// the resampler, then the resampler's own tail.  The output is what grail_resample_async gives for the whole (filtered)
+// the limiter and what that gives to the resampler, then the limiter's own tail likewise, then the resampler's.  The output is what grail_resample_async gives for the whole (filtered)
 // session.
 // Every phoneme fed is reported on stderr ("fed <phoneme> at <sample>"), so that a test can render the same list with
 // the oracle in one piece and compare bit for bit.
@@ -68,8 +73,9 @@ int main(int argc, char **argv)
 {
     std::vector<const char *> plain;
     double lo = -1.0, hi = -1.0;
-    long taps = 0, rate = 0;
-    bool usage = false;
+    long taps = 0, rate = 0, lookahead = -1;
+    double ceiling_db = 0.0;
+    bool usage = false, limit = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         char *end = nullptr;
@@ -82,6 +88,16 @@ int main(int argc, char **argv)
         } else if (a == "--taps" && i + 1 < argc) {
             taps = std::strtol(argv[i + 1], &end, 10);
             usage = usage || end == argv[i + 1] || *end || taps < 3 || taps > GRAIL_FIR_TAPS_MAX || taps % 2 == 0;
+            i += 1;
+        } else if (a == "--ceiling" && i + 1 < argc) {
+            ceiling_db = std::strtod(argv[i + 1], &end);
+            // (written so that a NaN fails; the ceiling must come out a finite float above 0)
+            usage = usage || end == argv[i + 1] || *end || !(ceiling_db >= -300.0 && ceiling_db <= 300.0);
+            limit = true;
+            i += 1;
+        } else if (a == "--lookahead" && i + 1 < argc) {
+            lookahead = std::strtol(argv[i + 1], &end, 10);
+            usage = usage || end == argv[i + 1] || *end || lookahead < 0 || lookahead > GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX;
             i += 1;
         } else if (a == "--rate" && i + 1 < argc) {
             rate = std::strtol(argv[i + 1], &end, 10);
@@ -99,9 +115,10 @@ int main(int argc, char **argv)
     const uint32_t chunk = plain.size() > 0 ? (uint32_t)std::strtoul(plain[0], nullptr, 10) : 441;
     const double tail = plain.size() > 1 ? std::strtod(plain[1], nullptr) : 1.0;
     // (a chunk of 0 samples — or text strtoul makes 0 of — would never feed the stream)
-    if (usage || plain.size() > 2 || chunk == 0 || !(tail >= 0.0) || (taps && !band) || (band && !(lo >= 0.0 && lo < hi))) {
-        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--rate R] [samples per pull >= 1 (default 441)] "
-                             "[seconds of tail >= 0 (default 1)]\n");
+    if (usage || plain.size() > 2 || chunk == 0 || !(tail >= 0.0) || (taps && !band) || (band && !(lo >= 0.0 && lo < hi)) ||
+        (lookahead >= 0 && !limit)) {
+        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] "
+                             "[samples per pull >= 1 (default 441)] [seconds of tail >= 0 (default 1)]\n");
         return 2;
     }
     try {
@@ -114,6 +131,8 @@ int main(int argc, char **argv)
             sets.push_back(gpu.fir_set({grail::fir_design((uint32_t)voice.sample_rate, lo, hi, taps ? (uint32_t)taps : 255u)}));
             filters.push_back(gpu.fir_stream(sets[0], 1));
         }
+        std::vector<grail::LimitStream> limiters;
+        if (limit) limiters.push_back(gpu.limit_stream(1, grail_limit_ceiling((float)ceiling_db), lookahead < 0 ? 8u : (uint32_t)lookahead));
         std::vector<grail::ResampleStream> resamplers;
         if (rate) resamplers.push_back(gpu.resample_stream((uint32_t)voice.sample_rate, (uint32_t)rate, 1));
         std::vector<Line> script;
@@ -143,7 +162,10 @@ int main(int argc, char **argv)
             }
             uint32_t rendered = 0;                                    // what the chain rendered in this pull
             std::vector<float> part;
-            if (rate) {
+            if (limit) {
+                // ... filtered, limited and resampled where it lay
+                part = chain.next(band ? &filters[0] : nullptr, limiters[0], rate ? &resamplers[0] : nullptr, &rendered);
+            } else if (rate) {
                 part = chain.next(band ? &filters[0] : nullptr, resamplers[0], &rendered);    // ... filtered and resampled where it lay
             } else if (band) {
                 part = chain.next(filters[0], &rendered);            // ... filtered where it lay
@@ -182,14 +204,26 @@ int main(int argc, char **argv)
         }
         if (band) {                                                   // the chain has ended: the filter rings out
             std::vector<float> rest = filters[0].finish().at(0);
-            if (rate) rest = resamplers[0].next({rest}).at(0);        // ... into the resampler, the next stage of the chain
+            if (limit) rest = limiters[0].next({rest}).at(0);         // ... into the next stages of the chain
+            if (rate) rest = resamplers[0].next({rest}).at(0);
             std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
             written += rest.size();
-            if (rate)
+            if (rate || limit)
                 std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps)\n", lo, hi, (double)voice.sample_rate, filters[0].tail() + 1);
             else
                 std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps): %zu samples written\n", lo, hi,
                              (double)voice.sample_rate, filters[0].tail() + 1, written);
+        }
+        if (limit) {                                                  // ... the limiter's own tail: what its look-ahead held back
+            std::vector<float> rest = limiters[0].finish().at(0);
+            if (rate) rest = resamplers[0].next({rest}).at(0);
+            std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
+            written += rest.size();
+            if (rate)
+                std::fprintf(stderr, "Limited to %g dBTP, %u samples late\n", ceiling_db, limiters[0].delay());
+            else
+                std::fprintf(stderr, "Limited to %g dBTP, %u samples late: %zu samples written\n", ceiling_db, limiters[0].delay(),
+                             written);
         }
         if (rate) {                                                   // ... and the resampler's own tail
             const std::vector<float> rest = resamplers[0].finish().at(0);

@@ -36,6 +36,7 @@
 #include "division_window.h"
 #include "fir_plan.h"
 #include "kernels.h"
+#include "limit_plan.h"
 #include "resample_plan.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)
@@ -376,6 +377,22 @@ struct grail_resample_stream {
     // a finishing call's marks: the host copy is written again only once the upload before has been through
     std::vector<uint8_t> mark;
     grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows]
+    grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
+};
+
+// A stream of groups of rows limited call by call (transforms.cpp), all under one ceiling with one look-ahead: owned by the
+// context's TransformState, released by grail_limit_stream_close or with the context.  The stream kernels of
+// limiter_kernels.hip read and write its state.
+struct grail_limit_stream {
+    uint32_t n_rows = 0, group = 1;
+    float ceiling = 0.0f;
+    uint32_t ell = 0;                 // lookahead_log2
+    uint32_t ring_cap = 0;            // samples of a row's ring: limit_stream_ring_capacity(ell)
+    grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows / group] samples fed, bit 63: the group has ended
+    grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
+    // a finishing call's marks: the host copy is written again only once the upload before has been through
+    std::vector<uint8_t> mark;
+    grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows / group]
     grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
 };
 

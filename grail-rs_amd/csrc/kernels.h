@@ -289,4 +289,25 @@ hipError_t launch_resample_stream_advance(const float *in, uint64_t in_stride, c
                                           bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
                                           uint32_t *nonfinite, hipStream_t stream);
 
+// the limiter on streams (limiter_kernels.hip): groups of rows fed call by call, one ceiling and look-ahead for all.  state:
+// device [n_groups], the samples a group's members have been fed with bit 63 set once it has ended; ring: device
+// [n_groups * group][ring_cap], ring_cap a power of two at or above 3 * 2^lookahead_log2 + 19: sample s of a row at s mod
+// ring_cap, +0.0 where it was not finite.  A call launches both kernels, the first only when grid_chunks != 0: one workgroup
+// per (group, chunk of LIMIT_CHUNK of the call's outputs) writes out and the chunk's numbers (limit_chunk_bytes() each) to
+// cstat[group * grid_chunks + c], and reads the state; the advance kernel, queued behind it, alone writes it.  finishing:
+// in, in_len are not read, the groups marked in mark (device [n_groups], or NULL: every group) that have not ended write
+// their tail and end; nonfinite is not written.
+hipError_t launch_limit_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups, uint32_t group,
+                               float ceiling, uint32_t lookahead_log2, const uint64_t *state, const float *ring, uint32_t ring_cap,
+                               const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
+                               void *cstat, hipStream_t stream);
+// ... and a group's out_len and numbers from its chunks, its members' last samples into their rings and its state advanced,
+// one wave per group (outputs may be NULL); a group whose members are fed different n, or that has ended and is fed:
+// 0xFFFFFFFF, NaN, 0, 0, nothing else
+hipError_t launch_limit_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups,
+                                       uint32_t group, uint32_t lookahead_log2, uint64_t *state, float *ring, uint32_t ring_cap,
+                                       const uint8_t *mark, bool finishing, const void *cstat, uint32_t grid_chunks,
+                                       uint32_t *out_len, float *min_gain, uint32_t *n_limited, uint32_t *nonfinite,
+                                       hipStream_t stream);
+
 }  // namespace grail

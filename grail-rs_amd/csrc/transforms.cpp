@@ -1,8 +1,8 @@
 // transforms.cpp — the calls that read finished rows and write rows: grail_limit_async (limiter_kernels.hip),
 // grail_resample_async (resample_kernels.hip, the ratio and table resample_plan.cpp, §4.13), grail_fir_create / _free / _async
 // (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_filter_stream_open / _next_async / _finish_async /
-// _close (§4.15) and grail_resample_stream_open / _next_async / _finish_async / _close (§4.16): their checks, their scratch,
-// their launches.  What they check of a pair of rows is row_checks.h.
+// _close (§4.15), grail_resample_stream_open / _next_async / _finish_async / _close (§4.16) and grail_limit_stream_open /
+// _next_async / _finish_async / _close (limit_plan.cpp, §4.17): their checks, their scratch, their launches.  What they check of a pair of rows is row_checks.h.
 #include "api_internal.hpp"
 #include "row_checks.h"
 
@@ -56,6 +56,7 @@ struct TransformState : CtxPart {
     Owned<grail_fir> firs;                  // the filter sets alive
     Owned<grail_filter_stream> fir_streams; // ... and, after them (they die first), the filter streams open on them
     Owned<grail_resample_stream> resample_streams;  // the resample streams open (each with its own copy of its pair's table)
+    Owned<grail_limit_stream> limit_streams;        // the limit streams open (their chunks' numbers go to d_lstat)
 };
 
 // what the context has, made by nobody: NULL before the first call that needed it
@@ -78,6 +79,11 @@ grail_filter_stream *own_stream(grail_ctx *ctx, const grail_filter_stream *fs)
 grail_resample_stream *own_resample_stream(grail_ctx *ctx, const grail_resample_stream *rs)
 {
     return peek(ctx) ? peek(ctx)->resample_streams.find(rs) : nullptr;
+}
+
+grail_limit_stream *own_limit_stream(grail_ctx *ctx, const grail_limit_stream *ls)
+{
+    return peek(ctx) ? peek(ctx)->limit_streams.find(ls) : nullptr;
 }
 
 // the table of a pair of rates on the device: uploaded once per (U, D), the last four kept, the oldest evicted once
@@ -150,6 +156,30 @@ int resample_stream_call(grail_ctx *ctx, grail_resample_stream *rs, const float 
                                                         rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev, finishing,
                                                         st->d_rbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "resample stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+// ... and of a call on a limit stream
+int limit_stream_call(grail_ctx *ctx, grail_limit_stream *ls, const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev,
+                      const uint8_t *mark_dev, bool finishing, uint64_t chunks, float *out_dev, uint64_t out_stride,
+                      uint32_t *out_len_dev, float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev)
+{
+    TransformState *st;
+    int rc = state(ctx, &st);
+    if (rc) return rc;
+    const uint32_t n_groups = ls->n_rows / ls->group;
+    if (chunks) {
+        if ((rc = st->d_lstat.reserve(ctx->stream, (size_t)n_groups * (size_t)chunks * limit_chunk_bytes()))) return rc;
+        const hipError_t e = launch_limit_stream(in_dev, in_stride, in_len_dev, n_groups, ls->group, ls->ceiling, ls->ell,
+                                                 ls->d_state.get(), ls->d_ring.get(), ls->ring_cap, mark_dev, finishing,
+                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "limit stream kernel launch");
+    }
+    const hipError_t e = launch_limit_stream_advance(in_dev, in_stride, in_len_dev, n_groups, ls->group, ls->ell, ls->d_state.get(),
+                                                     ls->d_ring.get(), ls->ring_cap, mark_dev, finishing, st->d_lstat.get(),
+                                                     (uint32_t)chunks, out_len_dev, min_gain_dev, n_limited_dev, nonfinite_dev,
+                                                     ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "limit stream advance kernel launch");
     return GRAIL_OK;
 }
 
@@ -479,6 +509,96 @@ int grail_resample_stream_finish_async(grail_ctx *ctx, grail_resample_stream *rs
         mark_dev = rs->d_mark.get();
     }
     return resample_stream_call(ctx, rs, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, nullptr);
+}
+
+int grail_limit_stream_open(grail_ctx *ctx, uint32_t n_rows, uint32_t group, float ceiling, uint32_t lookahead_log2,
+                            grail_limit_stream **out)
+{
+    if (const char *why = limit_stream_open_error(n_rows, group, ceiling, lookahead_log2))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_limit_stream_open: ") + why);
+    // (no context exists without a device)
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_open: NULL argument");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_limit_stream> ls(new (std::nothrow) grail_limit_stream());
+    if (!ls) return fail(GRAIL_ERR_OUT_OF_MEMORY, "limit stream");
+    ls->n_rows = n_rows, ls->group = group;
+    ls->ceiling = ceiling, ls->ell = lookahead_log2;
+    ls->ring_cap = limit_stream_ring_capacity(lookahead_log2);
+    const size_t n_groups = n_rows / group;
+    HIP_TRY(ls->d_state.alloc(n_groups));
+    HIP_TRY(ls->d_ring.alloc((size_t)n_rows * ls->ring_cap));
+    HIP_TRY(ls->d_mark.alloc(n_groups));
+    // no sample fed, no group ended; the rings are read before they are written only where the index arithmetic discards
+    // what was read: zeroed all the same
+    HIP_TRY(hipMemsetAsync(ls->d_state.get(), 0, n_groups * sizeof(uint64_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(ls->d_ring.get(), 0, (size_t)n_rows * ls->ring_cap * sizeof(float), ctx->stream));
+    *out = st->limit_streams.add(std::move(ls));
+    return GRAIL_OK;
+}
+
+int grail_limit_stream_close(grail_ctx *ctx, grail_limit_stream *ls)
+{
+    if (!ls) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_close: ctx is NULL");
+    if (!own_limit_stream(ctx, ls)) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_close: not an open limit stream of this context");
+    // (a kernel or an upload still queued may be using its state)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    peek(ctx)->limit_streams.remove(ls);
+    return GRAIL_OK;
+}
+
+int grail_limit_stream_next_async(grail_ctx *ctx, grail_limit_stream *ls, const float *in_dev, uint64_t in_stride,
+                                  const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                  float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev)
+{
+    if (!ls) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_next_async: the stream is NULL");
+    if (ctx && !own_limit_stream(ctx, ls))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_next_async: not an open limit stream of this context");
+    // (without a context the stream was not looked up and is not looked into: the checks run for one row alone, and the call
+    // ends at bind_device)
+    uint64_t chunks = 0;
+    if (const char *why = limit_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? ls->n_rows : 1u, ctx ? ls->group : 1u, out_dev,
+                                                  out_stride, &chunks))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_limit_stream_next_async: ") + why);
+    int rc = bind_device(ctx, "grail_limit_stream_next_async");
+    if (rc) return rc;
+    return limit_stream_call(ctx, ls, in_dev, in_stride, in_len_dev, nullptr, false, chunks, out_dev, out_stride, out_len_dev,
+                             min_gain_dev, n_limited_dev, nonfinite_dev);
+}
+
+int grail_limit_stream_finish_async(grail_ctx *ctx, grail_limit_stream *ls, const uint8_t *which, float *out_dev,
+                                    uint64_t out_stride, uint32_t *out_len_dev, float *min_gain_dev, uint32_t *n_limited_dev)
+{
+    if (!ls) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_finish_async: the stream is NULL");
+    if (ctx && !own_limit_stream(ctx, ls))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_finish_async: not an open limit stream of this context");
+    // (without a context: the checks of one row alone at a look-ahead of one sample, and the call ends at bind_device)
+    uint64_t chunks = 0;
+    if (const char *why = limit_stream_finish_error(out_dev, out_stride, ctx ? ls->n_rows : 1u, ctx ? ls->group : 1u,
+                                                    ctx ? ls->ell : 0u, &chunks))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_limit_stream_finish_async: ") + why);
+    int rc = bind_device(ctx, "grail_limit_stream_finish_async");
+    if (rc) return rc;
+    const uint8_t *mark_dev = nullptr;
+    if (which) {
+        // (the upload of the call before may still be reading the host copy)
+        if (ls->ev_mark.get())
+            HIP_TRY(hipEventSynchronize(ls->ev_mark));
+        else
+            HIP_TRY(ls->ev_mark.create());
+        const uint32_t n_groups = ls->n_rows / ls->group;
+        ls->mark.assign(which, which + n_groups);
+        HIP_TRY(hipMemcpyAsync(ls->d_mark.get(), ls->mark.data(), n_groups, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(hipEventRecord(ls->ev_mark, ctx->stream));
+        mark_dev = ls->d_mark.get();
+    }
+    return limit_stream_call(ctx, ls, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, min_gain_dev,
+                             n_limited_dev, nullptr);
 }
 
 }  // extern "C"

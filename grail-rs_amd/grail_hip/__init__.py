@@ -86,6 +86,8 @@ EXPORTS = [
     "grail_filter_stream_close",
     "grail_resample_stream_len", "grail_resample_stream_open", "grail_resample_stream_next_async",
     "grail_resample_stream_finish_async", "grail_resample_stream_close",
+    "grail_limit_stream_len", "grail_limit_stream_open", "grail_limit_stream_next_async", "grail_limit_stream_finish_async",
+    "grail_limit_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -100,6 +102,13 @@ TRUE_PEAK_PHASES, TRUE_PEAK_TAPS = 4, 12        # GRAIL_TRUE_PEAK_*: the 4x over
 LIMIT_LOOKAHEAD_LOG2_MAX = 10                   # GRAIL_LIMIT_LOOKAHEAD_LOG2_MAX: the look-ahead is 2^0 .. 2^10 samples
 LIMIT_REFUSED = 0xFFFFFFFF                      # GRAIL_LIMIT_REFUSED: n_limited of a group whose members differ in length
 LIMIT_CHUNK = 4096                              # GRAIL_LIMIT_CHUNK: one workgroup's samples (no number depends on it)
+
+
+def limit_stream_delay(lookahead_log2):
+    """GRAIL_LIMIT_STREAM_DELAY: the samples a limit stream's output lags its input by, 2^lookahead_log2 + 10"""
+    return (1 << lookahead_log2) + 10
+
+
 RESAMPLE_ZERO_CROSSINGS = 24                    # GRAIL_RESAMPLE_ZERO_CROSSINGS: per side, at the lower of the two rates
 RESAMPLE_TABLE_MAX = 32768                      # GRAIL_RESAMPLE_TABLE_MAX: up * taps of a supported pair of rates
 RESAMPLE_CHUNK = 1024                           # GRAIL_RESAMPLE_CHUNK: one workgroup's outputs (no number depends on it)
@@ -398,6 +407,11 @@ def load():
     L.grail_resample_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
     L.grail_resample_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp]
     L.grail_resample_stream_close.argtypes = [vp, vp]
+    L.grail_limit_stream_len.argtypes = [u64, u64, C.c_uint32, C.c_int, vp]
+    L.grail_limit_stream_open.argtypes = [vp, C.c_uint32, C.c_uint32, C.c_float, C.c_uint32, vp]
+    L.grail_limit_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
+    L.grail_limit_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp]
+    L.grail_limit_stream_close.argtypes = [vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -741,6 +755,14 @@ def limit_ceiling(ceiling_db):
     return np.float32(load().grail_limit_ceiling(float(np.float32(ceiling_db))))
 
 
+def limit_stream_len(fed_before, n, lookahead_log2, finishing=False):
+    """grail_limit_stream_len (pure host): the outputs a call on a limit stream writes for a group that was fed fed_before
+    samples before it: a `next` call that feeds n samples, or (finishing, n = 0) the tail of `finish`."""
+    out = C.c_uint64(0)
+    _check(load().grail_limit_stream_len(fed_before, n, lookahead_log2, 1 if finishing else 0, C.addressof(out)))
+    return out.value
+
+
 def resample_ratio(rate_in, rate_out):
     """grail_resample_ratio (pure host): (up, down, taps) of a pair of whole-numbered rates; GrailError for a pair that is
     not supported (a rate of 0, equal rates, more than RESAMPLE_TABLE_MAX table entries)."""
@@ -939,6 +961,62 @@ class LiveStream(Stream):
         out = np.zeros(self.n_utt, dtype=np.uint32)
         _check(load().grail_stream_pending(self.ctx.handle, self.handle, out.ctypes.data))
         return out
+
+
+class LimitStream:
+    """A limit stream of a Context (Context.limit_stream_open), beside the fir_stream_* and resample_stream_* helpers: the
+    handle with what the waited-for forms need to size their results, one per group."""
+
+    def __init__(self, ctx, handle, n_rows, group, lookahead_log2):
+        self.ctx, self.handle, self.n_rows, self.group, self.lookahead_log2 = ctx, handle, n_rows, group, lookahead_log2
+        self.n_groups = n_rows // group
+        self.delay = limit_stream_delay(lookahead_log2)
+
+    def next_async(self, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev=None, min_gain_dev=None,
+                   n_limited_dev=None, nonfinite_dev=None):
+        """grail_limit_stream_next_async: every row is fed its next min(in_len_dev[u], in_stride) samples; the outputs that
+        became known go to out_dev + u * out_stride.  Results are DEVICE arrays [n_groups] (any may be None), queued on the
+        context's stream; in_dev may be reused by what is queued behind the call."""
+        _check(load().grail_limit_stream_next_async(self.ctx.handle, self.handle, in_dev, in_stride, in_len_dev, out_dev, out_stride,
+                                                    out_len_dev, min_gain_dev, n_limited_dev, nonfinite_dev))
+
+    def _waited(self, types, call):
+        res = [np.zeros(self.n_groups, dtype=t) for t in types]
+        d = [self.ctx.device_alloc(self.n_groups * 4) for _ in res]
+        try:
+            call(*d)
+            for dst, src in zip(res, d):
+                self.ctx.d2h(dst, src, self.n_groups * 4)
+        finally:
+            self.ctx.sync()
+            for p in d:
+                self.ctx.device_free(p)
+        return tuple(res)
+
+    def next(self, in_dev, in_stride, in_len_dev, out_dev, out_stride):
+        """next_async, waited for, the results copied back: (out_len uint32, min_gain float32, n_limited uint32, nonfinite
+        uint32), one per group; a refused group reads (LIMIT_REFUSED, NaN, 0, 0)."""
+        return self._waited((np.uint32, np.float32, np.uint32, np.uint32),
+                            lambda *d: self.next_async(in_dev, in_stride, in_len_dev, out_dev, out_stride, *d))
+
+    def finish_async(self, out_dev, out_stride, which=None, out_len_dev=None, min_gain_dev=None, n_limited_dev=None):
+        """grail_limit_stream_finish_async: the groups marked in which (a host sequence, non-zero = marked; None: every group)
+        that have not ended write their tails (at most `delay` samples a row) and end."""
+        marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
+        assert marks is None or len(marks) == self.n_groups
+        _check(load().grail_limit_stream_finish_async(self.ctx.handle, self.handle, None if marks is None else marks.ctypes.data,
+                                                      out_dev, out_stride, out_len_dev, min_gain_dev, n_limited_dev))
+
+    def finish(self, out_dev, out_stride, which=None):
+        """finish_async, waited for: (out_len uint32, min_gain float32, n_limited uint32), one per group; (0, 1.0, 0) for
+        groups not marked or ended before."""
+        return self._waited((np.uint32, np.float32, np.uint32), lambda *d: self.finish_async(out_dev, out_stride, which, *d))
+
+    def close(self):
+        """grail_limit_stream_close: waits for the context's stream, then releases the stream."""
+        if self.handle is not None:
+            _check(load().grail_limit_stream_close(self.ctx.handle, self.handle))
+            self.handle = None
 
 
 class Context:
@@ -1418,6 +1496,13 @@ class Context:
     def resample_stream_close(self, rs):
         """grail_resample_stream_close: waits for the context's stream, then releases the stream."""
         _check(load().grail_resample_stream_close(self.handle, rs))
+
+    def limit_stream_open(self, n_rows, ceiling, lookahead_log2, group=1):
+        """grail_limit_stream_open: a stream of n_rows rows in groups of `group`, limited call by call under `ceiling` (linear)
+        with a look-ahead of 2^lookahead_log2 samples.  Returns a LimitStream; streams still open go with the context."""
+        out = C.c_void_p(None)
+        _check(load().grail_limit_stream_open(self.handle, n_rows, group, float(np.float32(ceiling)), lookahead_log2, C.addressof(out)))
+        return LimitStream(self, out, n_rows, group, lookahead_log2)
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max finite |x|, non-finite counts) per row, computed on the device (every length

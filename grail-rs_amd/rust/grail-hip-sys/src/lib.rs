@@ -134,6 +134,10 @@ pub struct grail_filter_stream {
 pub struct grail_resample_stream {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct grail_limit_stream {
+    _private: [u8; 0],
+}
 
 /// The most taps of one filter and the most filters of one set (`grail_fir_create`).
 pub const GRAIL_FIR_TAPS_MAX: u32 = 4096;
@@ -328,6 +332,15 @@ extern "C" {
     pub fn grail_resample_stream_finish_async(ctx: *mut grail_ctx, rs: *mut grail_resample_stream, which: *const u8,
         out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32) -> c_int;
     pub fn grail_resample_stream_close(ctx: *mut grail_ctx, rs: *mut grail_resample_stream) -> c_int;
+    pub fn grail_limit_stream_len(fed_before: u64, n: u64, lookahead_log2: u32, finishing: c_int, n_out: *mut u64) -> c_int;
+    pub fn grail_limit_stream_open(ctx: *mut grail_ctx, n_rows: u32, group: u32, ceiling: f32, lookahead_log2: u32,
+        out: *mut *mut grail_limit_stream) -> c_int;
+    pub fn grail_limit_stream_next_async(ctx: *mut grail_ctx, ls: *mut grail_limit_stream, in_dev: *const f32, in_stride: u64,
+        in_len_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32, min_gain_dev: *mut f32,
+        n_limited_dev: *mut u32, nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_limit_stream_finish_async(ctx: *mut grail_ctx, ls: *mut grail_limit_stream, which: *const u8,
+        out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32, min_gain_dev: *mut f32, n_limited_dev: *mut u32) -> c_int;
+    pub fn grail_limit_stream_close(ctx: *mut grail_ctx, ls: *mut grail_limit_stream) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

@@ -697,6 +697,16 @@ impl Gpu {
         Ok(ResampleStream { gpu: self, rs, n_rows, up, down, taps })
     }
 
+    /// A stream of `n_rows` rows in groups of `group`, limited chunk by chunk under `ceiling` (linear) with a look-ahead of
+    /// 2^`lookahead_log2` samples (`grail_limit_stream_open`; the contract is the header's section "levels, continued: the
+    /// limiter on streams").  The chunks' outputs put end to end, then the tail of [`LimitStream::finish`], are the bits
+    /// [`Gpu::limit`] gives for the whole rows, 2^`lookahead_log2` + 10 samples late.  Closed when dropped.
+    pub fn limit_stream(&self, n_rows: u32, group: u32, ceiling: f32, lookahead_log2: u32) -> Result<LimitStream<'_>, Error> {
+        let mut ls: *mut sys::grail_limit_stream = std::ptr::null_mut();
+        check(unsafe { sys::grail_limit_stream_open(self.ctx, n_rows, group, ceiling, lookahead_log2, &mut ls) })?;
+        Ok(LimitStream { gpu: self, ls, n_rows, group, delay: (1u32 << lookahead_log2) + 10 })
+    }
+
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
     /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
     /// non-finite samples.  One lane filters one row: many rows fill the device.
@@ -1102,6 +1112,141 @@ impl Drop for ResampleStream<'_> {
             sys::grail_resample_stream_close(self.gpu.ctx, self.rs);
         }
     }
+}
+
+/// What one call on a [`LimitStream`] gives: per row the outputs that became known (empty for the rows of a refused
+/// group), per group the smallest gain and the count of limited samples among them and the count of non-finite samples
+/// among those fed.
+pub struct LimitChunk {
+    pub out: Vec<Vec<f32>>,
+    pub min_gain: Vec<f32>,
+    pub n_limited: Vec<u32>,
+    pub nonfinite: Vec<u32>,
+}
+
+/// Groups of rows limited chunk by chunk on a [`Gpu`]'s device ([`Gpu::limit_stream`]), their look-ahead resident in HBM
+/// between calls; `grail_limit_stream_close` when dropped.
+pub struct LimitStream<'a> {
+    gpu: &'a Gpu,
+    ls: *mut sys::grail_limit_stream,
+    n_rows: u32,
+    group: u32,
+    delay: u32,
+}
+
+impl LimitStream<'_> {
+    /// The samples the output lags the input by: `GRAIL_LIMIT_STREAM_DELAY`.
+    pub fn delay(&self) -> u32 {
+        self.delay
+    }
+
+    // one call on the stream: `chunks` fed (None: the groups marked in `which` finish)
+    fn call(&mut self, chunks: Option<&[Vec<f32>]>, which: Option<&[u8]>) -> Result<LimitChunk, Error> {
+        let n = self.n_rows as usize;
+        let groups = (self.n_rows / self.group) as usize;
+        let longest = chunks.map_or(0, |c| c.iter().map(|r| r.len()).max().unwrap_or(0));
+        let stride = (longest + 63) / 64 * 64;
+        let out_stride = (stride.max(self.delay as usize) + 63) / 64 * 64;
+        let lens: Vec<u32> = chunks.map_or(vec![0u32; n], |c| c.iter().map(|r| r.len() as u32).collect());
+        let mut res = LimitChunk { out: vec![Vec::new(); n], min_gain: vec![1f32; groups], n_limited: vec![0u32; groups],
+                                   nonfinite: vec![0u32; groups] };
+        let mut out_lens = vec![0u32; groups];
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 7] = [std::ptr::null_mut(); 7];
+            let sizes = [n * stride.max(1) * 4, n * out_stride * 4, n * 4, groups * 4, groups * 4, groups * 4, groups * 4];
+            let mut r = Ok(());
+            for k in 0..7 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, sizes[k], &mut d[k]));
+                }
+            }
+            if let Some(c) = chunks {
+                for (i, row) in c.iter().enumerate() {
+                    if r.is_ok() && !row.is_empty() {
+                        r = check(sys::grail_memcpy_h2d(ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                        row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                    }
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_h2d(ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_limit_stream_next_async(ctx, self.ls, d[0] as *const f32, stride as u64, d[2] as *const u32,
+                                                                 d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                                                 d[4] as *mut f32, d[5] as *mut u32, d[6] as *mut u32));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_d2h(ctx, res.nonfinite.as_mut_ptr() as *mut std::ffi::c_void, d[6], groups * 4));
+                }
+            } else if r.is_ok() {
+                r = check(sys::grail_limit_stream_finish_async(ctx, self.ls, which.map_or(std::ptr::null(), |w| w.as_ptr()),
+                                                               d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                                               d[4] as *mut f32, d[5] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], groups * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, res.min_gain.as_mut_ptr() as *mut std::ffi::c_void, d[4], groups * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, res.n_limited.as_mut_ptr() as *mut std::ffi::c_void, d[5], groups * 4));
+            }
+            for i in 0..n {
+                let len = out_lens[i / self.group as usize];
+                if r.is_ok() && len != 0 && len != LIMIT_REFUSED {
+                    res.out[i] = vec![0f32; len as usize];
+                    r = check(sys::grail_memcpy_d2h(ctx, res.out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    len as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok(res)
+    }
+
+    /// Feeds row `i` the samples `chunks[i]` (empty chunks: the group pauses) and returns what became known
+    /// (`grail_limit_stream_next_async`).  A group whose members are fed different lengths, or that has ended and is fed,
+    /// is refused for the call: its rows come back empty, its `min_gain` NaN, its state untouched.
+    pub fn next(&mut self, chunks: &[Vec<f32>]) -> Result<LimitChunk, Error> {
+        if chunks.len() != self.n_rows as usize {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "LimitStream::next: one chunk per row".to_string() });
+        }
+        self.call(Some(chunks), None)
+    }
+
+    /// Ends the groups marked in `which` (`None`: every group) and returns their tails, the last `delay()` outputs at most
+    /// (`grail_limit_stream_finish_async`); empty for groups not marked and groups ended before.
+    pub fn finish(&mut self, which: Option<&[bool]>) -> Result<LimitChunk, Error> {
+        if which.map_or(false, |w| w.len() != (self.n_rows / self.group) as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "LimitStream::finish: one mark per group".to_string() });
+        }
+        let marks: Option<Vec<u8>> = which.map(|w| w.iter().map(|&m| m as u8).collect());
+        self.call(None, marks.as_deref())
+    }
+}
+
+impl Drop for LimitStream<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_limit_stream_close(self.gpu.ctx, self.ls);
+        }
+    }
+}
+
+/// The outputs a call on a [`LimitStream`] writes for a group that was fed `fed_before` samples before it: a `next` call
+/// that feeds `n` samples, or (`finishing`, `n` = 0) the tail (`grail_limit_stream_len`; pure host).
+pub fn limit_stream_len(fed_before: u64, n: u64, lookahead_log2: u32, finishing: bool) -> Result<u64, Error> {
+    let mut n_out = 0u64;
+    check(unsafe { sys::grail_limit_stream_len(fed_before, n, lookahead_log2, finishing as i32, &mut n_out) })?;
+    Ok(n_out)
 }
 
 /// The outputs a call on a [`ResampleStream`] writes for a row that was fed `fed_before` samples before it: a `next` call

@@ -383,6 +383,108 @@ private:
     uint64_t tail_ = 0;
 };
 
+// Groups of rows limited chunk by chunk on a Gpu's device (grail_limit_stream_open; the contract is the header's section
+// "levels, continued: the limiter on streams"), made by Gpu::limit_stream: move-only, closed with grail_limit_stream_close.
+// The chunks' outputs put end to end, then the tails of finish(), are the bits Gpu::limit gives for the whole rows, delay()
+// samples late.  It must not outlive its Gpu.
+class LimitStream {
+public:
+    LimitStream(grail_ctx *ctx, uint32_t n_rows, uint32_t group, float ceiling, uint32_t lookahead_log2)
+        : ctx_(ctx), n_rows_(n_rows), group_(group)
+    {
+        check(grail_limit_stream_open(ctx, n_rows, group, ceiling, lookahead_log2, &ls_));
+        delay_ = GRAIL_LIMIT_STREAM_DELAY(lookahead_log2);
+    }
+    ~LimitStream() { grail_limit_stream_close(ctx_, ls_); }
+    LimitStream(LimitStream &&o) noexcept
+        : ctx_(o.ctx_), ls_(std::exchange(o.ls_, nullptr)), n_rows_(o.n_rows_), group_(o.group_), delay_(o.delay_)
+    {
+    }
+    LimitStream &operator=(LimitStream &&o) noexcept
+    {
+        if (this != &o) {
+            grail_limit_stream_close(ctx_, ls_);
+            ctx_ = o.ctx_, ls_ = std::exchange(o.ls_, nullptr), n_rows_ = o.n_rows_, group_ = o.group_, delay_ = o.delay_;
+        }
+        return *this;
+    }
+    LimitStream(const LimitStream &) = delete;
+    LimitStream &operator=(const LimitStream &) = delete;
+    uint32_t rows() const { return n_rows_; }
+    uint32_t groups() const { return n_rows_ / group_; }
+    uint32_t delay() const { return delay_; }    // GRAIL_LIMIT_STREAM_DELAY: the output's lag, and the room finish() needs per row
+
+    // grail_limit_stream_next_async on device buffers (a chunk that a live stream has just rendered or a filter stream has
+    // just written, say): queued on the context's stream, nothing leaves the device.  The results are per group.
+    void next_async(const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride,
+                    uint32_t *out_len_dev, float *min_gain_dev = nullptr, uint32_t *n_limited_dev = nullptr,
+                    uint32_t *nonfinite_dev = nullptr)
+    {
+        check(grail_limit_stream_next_async(ctx_, ls_, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev, min_gain_dev,
+                                            n_limited_dev, nonfinite_dev));
+    }
+    // grail_limit_stream_finish_async on a device buffer (out_stride >= delay())
+    void finish_async(float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, const uint8_t *which = nullptr)
+    {
+        check(grail_limit_stream_finish_async(ctx_, ls_, which, out_dev, out_stride, out_len_dev, nullptr, nullptr));
+    }
+
+    // Row i is fed chunks[i] (empty chunks: the group pauses); returns the outputs that became known, per row.  The rows of
+    // a group whose members are fed different lengths, or that has ended and is fed, come back empty.
+    std::vector<std::vector<float>> next(const std::vector<std::vector<float>> &chunks)
+    {
+        if (chunks.size() != n_rows_) throw Error(GRAIL_ERR_INVALID_ARG, "LimitStream::next: one chunk per row");
+        return call(&chunks, nullptr);
+    }
+    // The groups marked in which (empty: every group) end; returns their rows' tails: the last delay() outputs at most.
+    std::vector<std::vector<float>> finish(const std::vector<uint8_t> &which = {})
+    {
+        if (!which.empty() && which.size() != groups()) throw Error(GRAIL_ERR_INVALID_ARG, "LimitStream::finish: one mark per group");
+        return call(nullptr, which.empty() ? nullptr : which.data());
+    }
+
+private:
+    std::vector<std::vector<float>> call(const std::vector<std::vector<float>> *chunks, const uint8_t *which)
+    {
+        const uint32_t n = n_rows_, g = groups();
+        size_t longest = 0;
+        if (chunks)
+            for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
+        const uint64_t stride = (longest + 63) / 64 * 64, out_stride = (std::max<uint64_t>(longest, delay_) + 63) / 64 * 64;
+        std::vector<std::vector<float>> out(n);
+        std::vector<uint32_t> lens(n, 0u), out_lens(g, 0u);
+        for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
+        void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
+        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4 + 4, &d_in);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4 + 4, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)g * 4, &d_out_len);
+        for (uint32_t i = 0; !rc && i < n; ++i)
+            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
+        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
+        if (!rc)
+            rc = chunks ? grail_limit_stream_next_async(ctx_, ls_, (const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out,
+                                                        out_stride, (uint32_t *)d_out_len, nullptr, nullptr, nullptr)
+                        : grail_limit_stream_finish_async(ctx_, ls_, which, (float *)d_out, out_stride, (uint32_t *)d_out_len, nullptr,
+                                                          nullptr);
+        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)g * 4);
+        for (uint32_t i = 0; !rc && i < n; ++i) {
+            const uint32_t len = out_lens[i / group_];
+            if (!len || len == GRAIL_LIMIT_REFUSED) continue;
+            out[i].resize(len);
+            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)len * 4);
+        }
+        for (void *p : {d_in, d_out, d_len, d_out_len})
+            if (p) grail_device_free(ctx_, p);
+        check(rc);
+        return out;
+    }
+
+    grail_ctx *ctx_ = nullptr;
+    grail_limit_stream *ls_ = nullptr;
+    uint32_t n_rows_ = 0, group_ = 1, delay_ = 0;
+};
+
 namespace detail {
 inline void flatten(const std::vector<Utterance> &utts, std::vector<PhonemeElem> &segs, std::vector<uint32_t> &offs,
                     std::vector<uint32_t> &vids, std::vector<uint32_t> &seeds)
@@ -752,6 +854,12 @@ public:
     ResampleStream resample_stream(uint32_t rate_in, uint32_t rate_out, uint32_t n_rows) const
     {
         return ResampleStream(ctx_, rate_in, rate_out, n_rows);
+    }
+    // n_rows rows in groups of `group` limited chunk by chunk under `ceiling` (linear) with a look-ahead of 2^lookahead_log2
+    // samples, their look-ahead resident in HBM between the calls.
+    LimitStream limit_stream(uint32_t n_rows, float ceiling, uint32_t lookahead_log2, uint32_t group = 1) const
+    {
+        return LimitStream(ctx_, n_rows, group, ceiling, lookahead_log2);
     }
 
     // Rows of samples filtered on the device (grail_fir_async; the contract is the header's section "levels, continued: FIR
@@ -1142,16 +1250,45 @@ public:
         if (n) check(grail_memcpy_d2h(ctx_, out.data(), d_resampled_, (size_t)n * sizeof(float)));
         return out;
     }
+    // ... through a limit stream of one row, behind `filter` and ahead of `resampler` where those are not NULL: the one-shot
+    // order (filter, limit, resample), every stage reading what the stage before wrote where it lies.
+    std::vector<float> next(FirStream *filter, LimitStream &limiter, ResampleStream *resampler, uint32_t *rendered)
+    {
+        if ((filter && filter->rows() != 1) || limiter.rows() != 1 || (resampler && resampler->rows() != 1))
+            throw Error(GRAIL_ERR_INVALID_ARG, "LiveStream::next: streams of one row");
+        if (filter && !d_filtered_) check(grail_device_alloc(ctx_, (size_t)stride_ * sizeof(float), &d_filtered_));
+        if (filter && !d_filtered_len_) check(grail_device_alloc(ctx_, sizeof(uint32_t), &d_filtered_len_));
+        if (!d_limited_) check(grail_device_alloc(ctx_, (size_t)stride_ * sizeof(float), &d_limited_));
+        if (!d_limited_len_) check(grail_device_alloc(ctx_, sizeof(uint32_t), &d_limited_len_));
+        const uint64_t room = resampler ? (resampler->most(stride_) + 63) / 64 * 64 : 0;
+        if (resampler && !d_resampled_) check(grail_device_alloc(ctx_, (size_t)room * sizeof(float), &d_resampled_));
+        if (resampler && !d_resampled_len_) check(grail_device_alloc(ctx_, sizeof(uint32_t), &d_resampled_len_));
+        uint32_t n = 0;
+        check(grail_stream_next_async(ctx_, stream_, chunk_, (float *)d_out_, stride_, (uint32_t *)d_len_));
+        if (filter)
+            filter->next_async((const float *)d_out_, stride_, (const uint32_t *)d_len_, (float *)d_filtered_, stride_,
+                               (uint32_t *)d_filtered_len_);
+        limiter.next_async((const float *)(filter ? d_filtered_ : d_out_), stride_, (const uint32_t *)(filter ? d_filtered_len_ : d_len_),
+                           (float *)d_limited_, stride_, (uint32_t *)d_limited_len_);
+        if (resampler)
+            resampler->next_async((const float *)d_limited_, stride_, (const uint32_t *)d_limited_len_, (float *)d_resampled_, room,
+                                  (uint32_t *)d_resampled_len_);
+        check(grail_memcpy_d2h(ctx_, rendered, d_len_, sizeof *rendered));
+        check(grail_memcpy_d2h(ctx_, &n, resampler ? d_resampled_len_ : d_limited_len_, sizeof n));
+        std::vector<float> out(n);
+        if (n) check(grail_memcpy_d2h(ctx_, out.data(), resampler ? d_resampled_ : d_limited_, (size_t)n * sizeof(float)));
+        return out;
+    }
     uint32_t chunk() const { return chunk_; }
 
 private:
     void release()
     {
         if (stream_) grail_stream_close(ctx_, stream_);
-        for (void *p : {d_out_, d_len_, d_filtered_, d_filtered_len_, d_resampled_, d_resampled_len_})
+        for (void *p : {d_out_, d_len_, d_filtered_, d_filtered_len_, d_resampled_, d_resampled_len_, d_limited_, d_limited_len_})
             if (p) grail_device_free(ctx_, p);
         stream_ = nullptr; d_out_ = nullptr; d_len_ = nullptr; d_filtered_ = nullptr; d_filtered_len_ = nullptr;
-        d_resampled_ = nullptr; d_resampled_len_ = nullptr;
+        d_resampled_ = nullptr; d_resampled_len_ = nullptr; d_limited_ = nullptr; d_limited_len_ = nullptr;
     }
     grail_ctx *ctx_;
     uint32_t chunk_;
@@ -1160,6 +1297,7 @@ private:
     void *d_out_ = nullptr, *d_len_ = nullptr;
     void *d_filtered_ = nullptr, *d_filtered_len_ = nullptr;      // next(filter, ...): made at its first call
     void *d_resampled_ = nullptr, *d_resampled_len_ = nullptr;    // next(filter, resampler, ...): made at its first call
+    void *d_limited_ = nullptr, *d_limited_len_ = nullptr;        // next(filter, limiter, resampler, ...): made at its first call
 };
 
 }  // namespace grail

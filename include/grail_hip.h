@@ -1198,6 +1198,75 @@ int grail_resample_stream_finish_async(grail_ctx *ctx, grail_resample_stream *rs
  * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context. */
 int grail_resample_stream_close(grail_ctx *ctx, grail_resample_stream *rs);
 
+/* ---- levels, continued: the limiter on streams -----------------------------------------------------------------------------------
+ * grail_limit_async takes finished rows.  Live voices summed into a track overlap above the ceiling, and a band-pass
+ * overshoots its input: a caller who pulls a live stream chunk by chunk limits chunk by chunk with a LIMIT STREAM: n_rows rows
+ * in groups of `group` consecutive rows that share one gain curve, as in grail_limit_async; c = ceiling and l =
+ * lookahead_log2 (L = 2^l) fixed when the stream is opened, its state resident in HBM between calls.
+ * THE CONTRACT.  For any split of a group's samples into calls (calls of no samples included), the rows the `next` calls
+ * write put end to end, followed by the tail that `finish` writes, are bit for bit what grail_limit_async writes for the whole
+ * group with the same c, l and group and an out_stride that cuts nothing.  Over all calls and the finish the per-call results
+ * combine to the one-shot call's: the minimum of the min_gain values is its min_gain, the sum of the n_limited values its
+ * n_limited, the sum of the nonfinite values its nonfinite.  This holds because every step of the limiter's contract is FIR (a
+ * 12-tap detector, a minimum over L, a sum of L integers): a prefix of the output is final after a prefix of the input.
+ * With LAMBDA = L + 10 = GRAIL_LIMIT_STREAM_DELAY(l): z[t] needs q up to t + L - 1 and q[s] needs x up to s + 11, so after N
+ * samples E(N) = max(0, N - LAMBDA) outputs are known, and output N - LAMBDA does change with the next sample.  A `next` call
+ * that feeds n samples writes outputs E(N) .. E(N + n) - 1 (at most n of them; none while the group is short of LAMBDA + 1
+ * samples); `finish` writes the tail E(N) .. N - 1: min(N, LAMBDA) outputs, none for a group that was fed nothing.  At
+ * `finish` the one-shot rule for the row's end applies: q[s] = Q for s >= N, and the samples to come enter the detector as
+ * +0.0.  Fed zeros are NOT the row's end to the detector: after the last sample the e's are not zero (the filter rings on
+ * for eleven outputs), and a fed zero gets their q where the row's end gets Q.  The outputs below N cannot tell, though: such a
+ * q sees only e's that q[N - 1] sees as well, so it is never below q[N - 1], and every window that reaches past the end
+ * holds q[N - 1].  `finish` is the row's end without LAMBDA samples fed and counted, and it ends the group.
+ * The output lags the input by LAMBDA samples: 266 samples (5.5 ms) at l = 8 and 48 kHz.
+ * STATE.  Per group: N, the samples fed so far (64 bits); whether the group has ended.  Per row: the last 3 L + 19 samples
+ * fed (the oldest sample the next output may still need is x[N - 3 L - 19]), already +0.0 where they were not finite, in a
+ * ring rounded up to a power of two (at most 16 KB a row, at l = 10).
+ * A stream never cuts outputs short: out_stride is at least the most a call can write. */
+#define GRAIL_LIMIT_STREAM_DELAY(l) ((1u << (l)) + 10u)
+typedef struct grail_limit_stream grail_limit_stream;
+
+/* Pure host: *n_out = the outputs a call writes for a group that was fed fed_before samples before it: finishing = 0: a
+ * `next` call that feeds n samples; finishing != 0: `finish` (n must be 0).  GRAIL_ERR_INVALID_ARG, nothing written:
+ * lookahead_log2 > 10; n_out NULL; finishing with n != 0; fed_before + n does not fit 64 bits. */
+int grail_limit_stream_len(uint64_t fed_before, uint64_t n, uint32_t lookahead_log2, int finishing, uint64_t *n_out);
+/* A stream of n_rows rows in groups of `group`, held under `ceiling` with a look-ahead of 2^lookahead_log2 samples.  The
+ * state (one 64-bit word per group, a ring per row) belongs to the stream, which belongs to the context.
+ * GRAIL_ERR_INVALID_ARG, nothing created: what grail_limit_async refuses (lookahead_log2 > 10; group 0 or no divisor of
+ * n_rows; a ceiling that is not a finite number above 0); n_rows = 0; ctx or out NULL.  These come first; without a usable
+ * device: GRAIL_ERR_NO_DEVICE. */
+int grail_limit_stream_open(grail_ctx *ctx, uint32_t n_rows, uint32_t group, float ceiling, uint32_t lookahead_log2,
+                            grail_limit_stream **out);
+/* Feeds every row u its next n = min(in_len_dev[u], in_stride) samples from in_dev + u * in_stride and writes the
+ * E(N + n) - E(N) outputs that became known to out_dev + u * out_stride, from index 0; queued on ctx's stream.  in_len_dev:
+ * device [n_rows].  Results are DEVICE arrays [n_rows / group], any may be NULL: out_len = that count; min_gain = the smallest
+ * g among the outputs this call wrote, 1.0f if it wrote none; n_limited counts among the outputs this call wrote; nonfinite
+ * counts among the samples this call fed, summed over the members (a sample is counted in the call that fed it and never
+ * again; it enters as +0.0).  n = 0 is legal (a paused group): nothing is written, out_len 0.  A group whose members are fed
+ * different n in one call is REFUSED for that call: out_len = GRAIL_LIMIT_REFUSED, min_gain = NaN, both counts 0, nothing
+ * written, its state as it was; a correct call may follow it.  A group that has ended and is fed n > 0 is refused in the same
+ * way.  out_dev past out_len is never written.  in_dev may be reused by whatever is queued behind the call: the call copies
+ * what it keeps.  16-byte loads and stores where both bases are 16-byte aligned and both strides multiples of 4, 4-byte ones
+ * otherwise: same bits.  Scratch stays with the context, as for grail_limit_async.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of this context (looked up, not looked into);
+ * a NULL buffer with samples to read or write, in_len_dev NULL; out_stride < in_stride (a stream never cuts outputs short);
+ * overlapping ranges; more than 2^31 chunks of GRAIL_LIMIT_CHUNK outputs.  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE. */
+int grail_limit_stream_next_async(grail_ctx *ctx, grail_limit_stream *ls, const float *in_dev, uint64_t in_stride,
+                                  const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                  float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev);
+/* Ends the groups marked in which (a HOST array [n_rows / group] of bytes, non-zero = marked; NULL = every group, as
+ * grail_filter_stream_finish_async): every member of a marked group that has not ended writes its tail to out_dev + u *
+ * out_stride, and the group ends.  Results are DEVICE arrays [n_rows / group], any may be NULL: out_len = the tail's length,
+ * min_gain and n_limited among the tail's outputs; 0, 1.0f, 0 and nothing written for groups that are unmarked or had
+ * ended before.  The array may be reused at once.  GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open
+ * stream of this context; out_stride < GRAIL_LIMIT_STREAM_DELAY(l); out_dev NULL. */
+int grail_limit_stream_finish_async(grail_ctx *ctx, grail_limit_stream *ls, const uint8_t *which, float *out_dev,
+                                    uint64_t out_stride, uint32_t *out_len_dev, float *min_gain_dev, uint32_t *n_limited_dev);
+/* Releases a stream once everything queued on ctx's stream is through; streams still open at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context. */
+int grail_limit_stream_close(grail_ctx *ctx, grail_limit_stream *ls);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);

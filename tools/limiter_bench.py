@@ -8,7 +8,10 @@ once, then on the same buffer, in the same process,
 and a lone track of 10^7 samples (time is parallel: it fills the device).  Wall clock around each call and its sync, best of
 --reps after a warm-up.  Kernel times: run under `rocprofv3 --kernel-trace --stats -- python tools/limiter_bench.py`; bytes
 fetched and written: under `rocprofv3 --pmc FETCH_SIZE WRITE_SIZE -- python tools/limiter_bench.py --only-limit` (a run of
-its own).  Prints one line per case and a JSON summary."""
+its own).  Prints one line per case and a JSON summary.
+  --step stream   the same rows through a limit stream in calls of 4 800 samples (100 ms), then finish,
+                  beside grail_limit_async on the same rows at the hot ceiling, at L = 256 and L = 1024: the stream's calls
+                  summed as a multiple of the one-shot call, the outputs compared on the device."""
 import argparse
 import ctypes as C
 import json
@@ -35,15 +38,105 @@ def best(fn, reps):
     return min(ms), ms
 
 
+def stream_step(ctx, args):
+    chunk = 4800
+    ctx.set_voices(W.single_voice())
+    n = args.utts
+    segs, offs, vids, seeds = W.make_batch(n)
+    stride = W.max_samples()
+    b = ctx.upload(segs, offs, vids, seeds)
+    d_rows, d_len = ctx.device_alloc(n * stride * 4), ctx.device_alloc(n * 4)
+    d_out, d_sout = ctx.device_alloc(n * stride * 4), ctx.device_alloc(n * stride * 4)
+    b.synthesize_async(d_rows, stride, d_len)
+    ctx.sync()
+    lens = np.zeros(n, np.uint32)
+    ctx.d2h(lens, d_len, n * 4)
+    if lens.min() != lens.max():
+        raise SystemExit("the stream step wants rows of one length (the aligned corpus): every row's chunk lands at the same offset")
+    length = int(lens[0])
+    _, peak, _ = ctx.levels(d_rows, stride, d_len, n)
+    hot_c = np.float32(np.median(peak[peak > 0]) / 2.0)
+    d_g, d_l, d_b, d_sol = (ctx.device_alloc(n * 4) for _ in range(4))
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMemcpy2D.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_int]
+    hip.hipDeviceSynchronize.argtypes = []
+    chunk_out = (max(chunk, G.limit_stream_delay(10)) + 63) // 64 * 64
+    d_chunk, d_clen, d_cout = ctx.device_alloc(n * chunk * 4), ctx.device_alloc(n * 4), ctx.device_alloc(n * chunk_out * 4)
+    calls = -(-length // chunk)
+    out = {"step": "stream", "rows": n, "samples_per_row": length, "chunk": chunk, "calls": calls, "ceiling": float(hot_c), "cases": {}}
+
+    def copy2d(dst, dst_pitch, src, src_pitch, width):
+        if width:
+            # (a copy between device buffers may return before it is through, and the context's stream does not wait for it)
+            rc = hip.hipMemcpy2D(dst, dst_pitch * 4, src, src_pitch * 4, width * 4, n, 3)      # hipMemcpyDeviceToDevice
+            rc = rc or hip.hipDeviceSynchronize()
+            if rc:
+                raise SystemExit(f"hipMemcpy2D failed: {rc}")
+
+    for ell in (8, 10):
+        def one_shot_call():
+            ctx.limit_async(d_rows, stride, d_len, n, hot_c, ell, d_out, stride, 1, d_g, d_l, d_b)
+            ctx.sync()
+
+        one_shot, one_shot_all = best(one_shot_call, args.reps)
+        runs = []
+        for _ in range(2):                                   # (the first run warms up)
+            ls = ctx.limit_stream_open(n, hot_c, ell)
+            ms, written = [], 0
+            for c in range(calls):
+                k = min(chunk, length - c * chunk)
+                copy2d(d_chunk, chunk, C.c_void_p(d_rows.value + 4 * c * chunk), stride, k)
+                ctx.h2d(d_clen, np.full(n, k, np.uint32), n * 4)
+                t0 = time.perf_counter()
+                ls.next_async(d_chunk, chunk, d_clen, d_cout, chunk_out, d_sol)
+                ctx.sync()
+                ms.append(1e3 * (time.perf_counter() - t0))
+                # (untimed: the call's outputs behind those of the calls before, as a consumer would put them)
+                count = G.limit_stream_len(c * chunk, k, ell)
+                copy2d(C.c_void_p(d_sout.value + 4 * written), stride, d_cout, chunk_out, count)
+                written += count
+            t0 = time.perf_counter()
+            ls.finish_async(d_cout, chunk_out, None, d_sol)
+            ctx.sync()
+            ms.append(1e3 * (time.perf_counter() - t0))
+            count = G.limit_stream_len(length, 0, ell, finishing=True)
+            copy2d(C.c_void_p(d_sout.value + 4 * written), stride, d_cout, chunk_out, count)
+            written += count
+            ls.close()
+            runs.append(ms)
+        if written != length:
+            raise SystemExit(f"the stream wrote {written} outputs a row, the one-shot call {length}")
+        max_diff, _, mismatches = ctx.compare(d_sout, d_out, stride, d_len, d_len, n)
+        differ = int(np.count_nonzero((max_diff != 0) | (mismatches != 0)))
+        ms = runs[-1]
+        name = f"L={1 << ell}"
+        out["cases"][name] = {"one_shot_ms": one_shot, "one_shot_ms_all": one_shot_all, "stream_ms": sum(ms),
+                              "stream_ms_runs": [sum(r) for r in runs], "stream_next_ms_median": float(np.median(ms[:-1])),
+                              "stream_finish_ms": ms[-1], "ratio": sum(ms) / one_shot, "mismatches": differ}
+        print(f"grail_limit_async {name} hot: {one_shot:.2f} ms; the same rows through a limit stream in {calls} calls of {chunk} samples: "
+              f"{sum(ms):.2f} ms = {sum(ms) / one_shot:.2f} x (a call {np.median(ms[:-1]):.3f} ms, finish {ms[-1]:.3f} ms); "
+              f"rows that differ from the one-shot output: {differ}")
+        assert differ == 0, f"{name}: {differ} rows of the stream differ from the one-shot output"
+    for p in (d_g, d_l, d_b, d_sol, d_chunk, d_clen, d_cout, d_rows, d_out, d_sout, d_len):
+        ctx.device_free(p)
+    b.free()
+    ctx.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--utts", type=int, default=65536)
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only-limit", action="store_true", help="render, then the hot grail_limit_async case alone (for a counter run)")
+    ap.add_argument("--step", choices=["rows", "stream"], default="rows", help="rows: the one-shot call at full size (the default); "
+                    "stream: the same rows through a limit stream, chunk by chunk")
     args = ap.parse_args()
     if G.device_count() < 1:
         raise SystemExit("limiter_bench needs a HIP device (no CPU fallback)")
     ctx = G.Context(0)
+    if args.step == "stream":
+        return stream_step(ctx, args)
     ctx.set_voices(W.single_voice())
     n = args.utts
     segs, offs, vids, seeds = W.make_batch(n)
