@@ -4,9 +4,9 @@
 // family_cost.cpp, dispatch_model.cpp, launch_plan.cpp: kernel families, cost model, dispatcher model, block planner
 // (launch_plan.h); synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
 // mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak); transforms.cpp: rows limited, resampled and
-// filtered, at once or as streams; host_output.cpp: the one-call forms with a host destination; comm.cpp and node.cpp:
-// RCCL, the contexts of a node.  Every HIP resource these units create has one owner type (below): Event, Stream,
-// DeviceBuffer, PinnedBuffer.
+// filtered at once, transform_streams.cpp: the same as streams (both on transform_state.h); host_output.cpp: the one-call
+// forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Every HIP resource these units
+// create has one owner type (below): Event, Stream, DeviceBuffer, PinnedBuffer.
 #pragma once
 
 #include <dlfcn.h>
@@ -299,7 +299,7 @@ struct grail_ctx : PlanEnv {
     std::unique_ptr<CtxPart> host_pipe;     // HostPipe (host_output.cpp): streams, events and buffers of the host-output path
     std::unique_ptr<CtxPart> mix_state;     // MixState (mix.cpp): the last mix's plan and the device buffers it was uploaded to
     std::unique_ptr<CtxPart> level_state;   // LevelState (levels.cpp): the frame scratch of grail_levels_async, a block's numbers
-    std::unique_ptr<CtxPart> transform_state;   // TransformState (transforms.cpp): chunk scratch, resampler tables, filter sets and streams
+    std::unique_ptr<CtxPart> transform_state;   // TransformState (transform_state.h): chunk scratch, resampler tables, filter sets and streams
 };
 
 struct grail_stream {
@@ -347,53 +347,43 @@ struct grail_fir {
     uint32_t taps_max = 0;            // the longest n_taps of the set (a stream's ring holds taps_max - 1 samples a row)
 };
 
-// A stream of rows filtered call by call (transforms.cpp): owned by the context's TransformState, released by
-// grail_filter_stream_close or with the context.  The kernels of fir_kernels.hip read and write its state.
-struct grail_filter_stream {
-    const grail_fir *set = nullptr;   // (a set with open streams is not freed)
+// What the three kinds of chunked stream on finished rows hold alike (transform_streams.cpp): rows that each keep a ring of
+// their last samples in device memory, and units (rows, or groups of rows) that each keep their state words there.  The kind's
+// kernels read and write both.  Owned by the context's TransformState, released by the kind's close or with the context.
+struct ChunkedStream {
     uint32_t n_rows = 0;
-    uint32_t ring_cap = 0;            // samples of a row's ring: fir_stream_ring_capacity(set->taps_max)
-    grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows] the rows' filters
-    grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows] samples fed, bit 63: the row has ended
+    uint32_t units = 0;               // whose the state words and the marks are: the rows, or a limit stream's n_rows / group groups
+    uint32_t ring_cap = 0;            // samples of a row's ring (a power of two: the kind's *_stream_ring_capacity)
+    grail::host::DeviceBuffer<uint64_t> d_state;    // [units][the kind's words]; word 0: samples fed, bit 63: the unit has ended
     grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
-    std::vector<uint32_t> filter;     // (host copies, kept while the upload may be in flight)
     // a finishing call's marks: the host copy is written again only once the upload before has been through
     std::vector<uint8_t> mark;
-    grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows]
+    grail::host::DeviceBuffer<uint8_t> d_mark;      // [units]
     grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
 };
 
-// A stream of rows resampled call by call (transforms.cpp), all on one pair of rates: owned by the context's TransformState,
-// released by grail_resample_stream_close or with the context.  The kernels of resample_kernels.hip read and write its
-// state.  The table is the stream's own copy: the context's cache of four pairs may evict the pair while the stream is open.
-struct grail_resample_stream {
-    uint32_t up = 0, down = 0, taps = 0;
-    uint32_t n_rows = 0;
-    uint32_t ring_cap = 0;            // samples of a row's ring: resample_stream_ring_capacity(taps)
+// A stream of rows filtered call by call (fir_kernels.hip): one state word a row.
+struct grail_filter_stream : ChunkedStream {
+    const grail_fir *set = nullptr;   // (a set with open streams is not freed); ring_cap is fir_stream_ring_capacity(set->taps_max)
+    std::vector<uint32_t> filter;     // the rows' filters (host copy, kept while the upload may be in flight)
+    grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows]
+};
+
+// A stream of rows resampled call by call (resample_kernels.hip), all on one pair of rates: three state words a row (samples
+// fed, the next output's input time, its phase).  The table is the stream's own copy: the context's cache of four pairs may
+// evict the pair while the stream is open.
+struct grail_resample_stream : ChunkedStream {
+    uint32_t up = 0, down = 0, taps = 0;    // ring_cap is resample_stream_ring_capacity(taps)
     std::vector<int32_t> table;       // (host copy, kept while the upload may be in flight)
     grail::host::DeviceBuffer<int32_t> d_table;     // [up][taps]
-    grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows][3] samples fed (bit 63: ended), the next output's input time, its phase
-    grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
-    // a finishing call's marks: the host copy is written again only once the upload before has been through
-    std::vector<uint8_t> mark;
-    grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows]
-    grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
 };
 
-// A stream of groups of rows limited call by call (transforms.cpp), all under one ceiling with one look-ahead: owned by the
-// context's TransformState, released by grail_limit_stream_close or with the context.  The stream kernels of
-// limiter_kernels.hip read and write its state.
-struct grail_limit_stream {
-    uint32_t n_rows = 0, group = 1;
+// A stream of groups of rows limited call by call (the stream kernels of limiter_kernels.hip), all under one ceiling with one
+// look-ahead: one state word a group.
+struct grail_limit_stream : ChunkedStream {
+    uint32_t group = 1;
     float ceiling = 0.0f;
-    uint32_t ell = 0;                 // lookahead_log2
-    uint32_t ring_cap = 0;            // samples of a row's ring: limit_stream_ring_capacity(ell)
-    grail::host::DeviceBuffer<uint64_t> d_state;    // [n_rows / group] samples fed, bit 63: the group has ended
-    grail::host::DeviceBuffer<float> d_ring;        // [n_rows][ring_cap]
-    // a finishing call's marks: the host copy is written again only once the upload before has been through
-    std::vector<uint8_t> mark;
-    grail::host::DeviceBuffer<uint8_t> d_mark;      // [n_rows / group]
-    grail::host::Event ev_mark;       // behind the last upload of the marks (made at the first)
+    uint32_t ell = 0;                 // lookahead_log2; ring_cap is limit_stream_ring_capacity(ell)
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks
@@ -472,7 +462,7 @@ namespace grail {
 namespace host {
 
 int bind(grail_ctx *ctx);
-// ... for the device entry points that say their own name (levels.cpp, transforms.cpp): without a context, why there is none,
+// ... for the device entry points that say their own name (levels.cpp, transforms.cpp, transform_streams.cpp): without a context, why there is none,
 // GRAIL_ERR_NO_DEVICE on a machine without a GPU
 int bind_device(grail_ctx *ctx, const char *who);
 

@@ -1,5 +1,6 @@
 // fir_plan.cpp — the host side of FIR filtering that needs no device: grail_fir_len, grail_filter_stream_len and the checks of
-// the calls on filter streams (tests/test_fir_stream_sanitize.py), grail_fir_design (a Kaiser-windowed
+// the calls on filter streams (tests/test_fir_stream_sanitize.py; where they end as every stream's do: row_checks.h),
+// grail_fir_design (a Kaiser-windowed
 // band-pass with the resampler's sinc and I0), the checks of a filter set and the padded image of one as the kernels read
 // it.  The contract is include/grail_hip.h, "levels, continued: FIR filtering".  No HIP call, so it builds with g++ under
 // AddressSanitizer and UBSan (tests/test_fir_sanitize.py), as resample_plan.cpp does.  DESIGN.md §4.14.
@@ -75,31 +76,14 @@ const char *fir_stream_open_error(const uint32_t *filter, uint32_t n_rows, uint3
     return nullptr;
 }
 
-namespace {
-
-// the chunks of GRAIL_FIR_CHUNK outputs of a row of at most `longest` of them (fewer than 2^32: the lengths are 32 bits wide)
-uint64_t stream_chunks(uint64_t longest)
-{
-    const uint64_t most = longest < 0xFFFFFFFFull ? longest : 0xFFFFFFFFull;
-    return (most + GRAIL_FIR_CHUNK - 1u) / GRAIL_FIR_CHUNK;
-}
-
-}  // namespace
-
+// (a stream has rows: fir_stream_open_error; a call feeds a row fewer than 2^32 samples: in_len is 32 bits wide)
 const char *fir_stream_next_error(const void *in, uint64_t in_stride, const void *in_len, uint32_t n_rows, const void *out,
                                   uint64_t out_stride, uint64_t *chunks)
 {
     *chunks = 0;
     if (out_stride < in_stride) return "out_stride < in_stride (a stream never cuts outputs short)";
-    // (a stream has rows: fir_stream_open_error)
-    const RowPair p{in, in_stride, in_len, n_rows, out, out_stride};
-    if (const char *why = row_pair_error(p, OutRule::always, OutRule::always,
-                                         "out_dev overlaps in_dev (a chunk reads what another would have written)", 0))
-        return why;
-    if (in_stride == 0) return nullptr;
-    *chunks = stream_chunks(in_stride);
-    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
-    return nullptr;
+    const uint64_t longest = in_stride < 0xFFFFFFFFull ? in_stride : 0xFFFFFFFFull;
+    return stream_next_error({in, in_stride, in_len, n_rows, out, out_stride}, longest, n_rows, GRAIL_FIR_CHUNK, chunks);
 }
 
 const char *fir_stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint32_t longest_taps, uint64_t *chunks)
@@ -107,12 +91,7 @@ const char *fir_stream_finish_error(const void *out, uint64_t out_stride, uint32
     *chunks = 0;
     const uint32_t tail = longest_taps - 1u;
     if (out_stride < tail) return "out_stride is below the set's longest n_taps - 1";
-    if (tail == 0) return nullptr;
-    if (!out) return ROWS_NULL;
-    if (!rows_span_fits(out_stride, n_rows)) return ROWS_SPAN;
-    *chunks = stream_chunks(tail);
-    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
-    return nullptr;
+    return stream_finish_error(out, out_stride, n_rows, tail, n_rows, GRAIL_FIR_CHUNK, chunks);
 }
 
 }  // namespace grail

@@ -1,5 +1,6 @@
-// fir_plan.h — what the pure-host side of FIR filtering (fir_plan.cpp) shares with transforms.cpp, and the two functions it
-// shares with the resampler's table (resample_plan.cpp).  No HIP type: it builds with g++ (tests/test_fir_sanitize.py).
+// fir_plan.h — what the pure-host side of FIR filtering (fir_plan.cpp) shares with transforms.cpp and transform_streams.cpp,
+// and the two functions it shares with the resampler's table (resample_plan.cpp).  No HIP type: it builds with g++
+// (tests/test_fir_sanitize.py).
 #pragma once
 
 #include <cstdint>

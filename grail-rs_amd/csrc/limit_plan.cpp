@@ -1,7 +1,7 @@
 // limit_plan.cpp — the host side of limit streams that needs no device: E(N) and grail_limit_stream_len, the ring's capacity,
-// the chunk count and the checks of the calls on limit streams.  The contract is include/grail_hip.h, "levels, continued: the
-// limiter on streams".  No HIP call, so it builds with g++ under AddressSanitizer and UBSan
-// (tests/test_limit_stream_sanitize.py), as fir_plan.cpp and resample_plan.cpp do.  DESIGN.md §4.17.
+// and the checks of the calls on limit streams (where they end as every stream's do: row_checks.h).  The contract is
+// include/grail_hip.h, "levels, continued: the limiter on streams".  No HIP call, so it builds with g++ under AddressSanitizer
+// and UBSan (tests/test_limit_stream_sanitize.py), as fir_plan.cpp and resample_plan.cpp do.  DESIGN.md §4.17.
 #include <cstdint>
 
 #include "../../include/grail_hip.h"
@@ -36,31 +36,14 @@ const char *limit_stream_open_error(uint32_t n_rows, uint32_t group, float ceili
     return nullptr;
 }
 
-namespace {
-
-// the chunks of GRAIL_LIMIT_CHUNK outputs of a group of at most `longest` of them (fewer than 2^32: the lengths are 32 bits wide)
-uint64_t stream_chunks(uint64_t longest)
-{
-    const uint64_t most = longest < 0xFFFFFFFFull ? longest : 0xFFFFFFFFull;
-    return (most + GRAIL_LIMIT_CHUNK - 1u) / GRAIL_LIMIT_CHUNK;
-}
-
-}  // namespace
-
+// (a stream has rows in whole groups: limit_stream_open_error; a call feeds a row fewer than 2^32 samples: in_len is 32 bits wide)
 const char *limit_stream_next_error(const void *in, uint64_t in_stride, const void *in_len, uint32_t n_rows, uint32_t group,
                                     const void *out, uint64_t out_stride, uint64_t *chunks)
 {
     *chunks = 0;
     if (out_stride < in_stride) return "out_stride < in_stride (a stream never cuts outputs short)";
-    // (a stream has rows in whole groups: limit_stream_open_error)
-    const RowPair p{in, in_stride, in_len, n_rows, out, out_stride};
-    if (const char *why = row_pair_error(p, OutRule::always, OutRule::always,
-                                         "out_dev overlaps in_dev (a chunk reads what another would have written)", 0))
-        return why;
-    if (in_stride == 0) return nullptr;
-    *chunks = stream_chunks(in_stride);
-    if ((uint64_t)(n_rows / group) * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
-    return nullptr;
+    const uint64_t longest = in_stride < 0xFFFFFFFFull ? in_stride : 0xFFFFFFFFull;
+    return stream_next_error({in, in_stride, in_len, n_rows, out, out_stride}, longest, n_rows / group, GRAIL_LIMIT_CHUNK, chunks);
 }
 
 const char *limit_stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint32_t group, uint32_t ell,
@@ -69,11 +52,7 @@ const char *limit_stream_finish_error(const void *out, uint64_t out_stride, uint
     *chunks = 0;
     const uint32_t tail = limit_stream_delay(ell);
     if (out_stride < tail) return "out_stride is below the stream's delay, GRAIL_LIMIT_STREAM_DELAY(lookahead_log2)";
-    if (!out) return ROWS_NULL;
-    if (!rows_span_fits(out_stride, n_rows)) return ROWS_SPAN;
-    *chunks = stream_chunks(tail);
-    if ((uint64_t)(n_rows / group) * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
-    return nullptr;
+    return stream_finish_error(out, out_stride, n_rows, tail, n_rows / group, GRAIL_LIMIT_CHUNK, chunks);
 }
 
 }  // namespace grail

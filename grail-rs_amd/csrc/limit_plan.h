@@ -1,5 +1,5 @@
-// limit_plan.h — what the pure-host side of limit streams (limit_plan.cpp) shares with transforms.cpp.  No HIP type: it builds
-// with g++ (tests/test_limit_stream_sanitize.py), as fir_plan.h and resample_plan.h do.
+// limit_plan.h — what the pure-host side of limit streams (limit_plan.cpp) shares with transform_streams.cpp.  No HIP type: it
+// builds with g++ (tests/test_limit_stream_sanitize.py), as fir_plan.h and resample_plan.h do.
 #pragma once
 
 #include <cstdint>

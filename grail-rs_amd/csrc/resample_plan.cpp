@@ -3,7 +3,7 @@
 // The contract is include/grail_hip.h, "levels, continued: sample-rate conversion".  No HIP call, so it builds with g++
 // under AddressSanitizer and UBSan (tests/test_resample_sanitize.py), as mix_plan.cpp and level_gains.cpp do.
 // DESIGN.md §4.13.  Also grail_resample_stream_len, the ring's capacity and the checks of the calls on resample streams
-// (tests/test_resample_stream_sanitize.py; §4.16).
+// (tests/test_resample_stream_sanitize.py; §4.16; where they end as every stream's do: row_checks.h).
 #include <cmath>
 #include <cstdint>
 
@@ -82,9 +82,6 @@ unsigned __int128 known_outputs(uint64_t N, uint32_t U, uint32_t D, uint32_t P)
     return N <= h ? 0 : ((unsigned __int128)(N - h) * U + (D - 1u)) / D;
 }
 
-// the chunks of RESAMPLE_STREAM_CHUNK outputs of a row of at most `longest` of them
-uint64_t stream_chunks(uint64_t longest) { return (longest + grail::RESAMPLE_STREAM_CHUNK - 1u) / grail::RESAMPLE_STREAM_CHUNK; }
-
 }  // namespace
 
 namespace grail {
@@ -108,14 +105,7 @@ const char *resample_stream_next_error(const void *in, uint64_t in_stride, const
         return "out_stride < ceil(in_stride * up / down) (a stream never cuts outputs short)";
     // (a stream has rows: grail_resample_stream_open; a call feeds a row fewer than 2^32 samples: in_len is 32 bits wide)
     const uint64_t longest = (uint64_t)resample_stream_most(in_stride < 0xFFFFFFFFull ? in_stride : 0xFFFFFFFFull, U, D);
-    const RowPair p{in, in_stride, in_len, n_rows, out, out_stride};
-    if (const char *why = row_pair_error(p, OutRule::always, OutRule::always,
-                                         "out_dev overlaps in_dev (a chunk reads what another would have written)", longest))
-        return why;
-    if (in_stride == 0) return nullptr;
-    *chunks = stream_chunks(longest);
-    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
-    return nullptr;
+    return stream_next_error({in, in_stride, in_len, n_rows, out, out_stride}, longest, n_rows, RESAMPLE_STREAM_CHUNK, chunks);
 }
 
 const char *resample_stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t taps,
@@ -124,11 +114,7 @@ const char *resample_stream_finish_error(const void *out, uint64_t out_stride, u
     *chunks = 0;
     const uint64_t tail = resample_stream_tail(U, D, taps);         // at least 1
     if (out_stride < tail) return "out_stride < ceil((taps / 2) * up / down), the longest tail";
-    if (!out) return ROWS_NULL;
-    if (!rows_span_fits(out_stride, n_rows)) return ROWS_SPAN;
-    *chunks = stream_chunks(tail);
-    if ((uint64_t)n_rows * *chunks > 0x7FFFFFFFull) return "more than 2^31 chunks";
-    return nullptr;
+    return stream_finish_error(out, out_stride, n_rows, tail, n_rows, RESAMPLE_STREAM_CHUNK, chunks);
 }
 
 }  // namespace grail

@@ -1,6 +1,6 @@
-// resample_plan.h — what the pure-host side of sample-rate conversion (resample_plan.cpp) shares with transforms.cpp: the
-// ring and the checks of the calls on resample streams (grail_resample_stream_*).  No HIP type: it builds with g++
-// (tests/test_resample_stream_sanitize.py).  The convention is fir_plan.h's: NULL means fine, else what is wrong.
+// resample_plan.h — what the pure-host side of sample-rate conversion (resample_plan.cpp) shares with transforms.cpp and
+// transform_streams.cpp: the ring and the checks of the calls on resample streams (grail_resample_stream_*).  No HIP type: it
+// builds with g++ (tests/test_resample_stream_sanitize.py).  The convention is fir_plan.h's: NULL means fine, else what is wrong.
 #pragma once
 
 #include <cstdint>

@@ -1,8 +1,9 @@
-// row_checks.h — what the calls that read rows and write rows (transforms.cpp; the stream checks of fir_plan.cpp) check of
-// the pair alike, written once: the buffers are there, neither side spans more than 2^60 samples, the two do not overlap,
-// and no row's output length outgrows 32 bits.  Pure host code, no HIP type: it builds with g++, and
-// tests/test_row_checks_sanitize.py walks its edges under AddressSanitizer and UBSan.  The convention is fir_plan.h's: NULL
-// means fine, else what is wrong, and the entry point puts its own name in front.
+// row_checks.h — what the calls that read rows and write rows (transforms.cpp; for transform_streams.cpp the stream checks of
+// fir_plan.cpp, resample_plan.cpp and limit_plan.cpp) check of the pair alike, written once: the buffers are there, neither
+// side spans more than 2^60 samples, the two do not overlap, and no row's output length outgrows 32 bits.  Below that, where
+// the checks of the three kinds of stream end alike: the chunks of a call and their count.  Pure host code, no HIP type: it
+// builds with g++, and tests/test_row_checks_sanitize.py walks its edges under AddressSanitizer and UBSan.  The convention is
+// fir_plan.h's: NULL means fine, else what is wrong, and the entry point puts its own name in front.
 #pragma once
 
 #include <cstdint>
@@ -53,6 +54,41 @@ inline const char *row_pair_error(const RowPair &p, OutRule need_out, OutRule ov
     if ((overlap == OutRule::always || writes) && rows_overlap(p)) return overlap_message;
     if ((longest_out < p.out_stride ? longest_out : p.out_stride) > 0xFFFFFFFFull) return ROWS_TOO_LONG;
     return nullptr;
+}
+
+// ---- calls on streams: each kind says its own first check (its out_stride against what the call may write), then one of these
+
+constexpr const char *STREAM_CHUNKS = "more than 2^31 chunks";
+
+// the chunks of `chunk` outputs of a row of at most `longest` of them (fewer than 2^32: the lengths are 32 bits wide)
+inline uint64_t stream_chunks(uint64_t longest, uint32_t chunk)
+{
+    const uint64_t most = longest < 0xFFFFFFFFull ? longest : 0xFFFFFFFFull;
+    return (most + chunk - 1u) / chunk;
+}
+
+// A feeding call: the pair (a stream has rows, and always writes), whose rows give at most `longest` outputs, then the chunks
+// of the call's grid, `units` (rows, or groups of rows) times *chunks of them.  Strides of 0 feed nothing: no chunks.
+inline const char *stream_next_error(const RowPair &p, uint64_t longest, uint32_t units, uint32_t chunk, uint64_t *chunks)
+{
+    if (const char *why = row_pair_error(p, OutRule::always, OutRule::always,
+                                         "out_dev overlaps in_dev (a chunk reads what another would have written)", longest))
+        return why;
+    if (p.in_stride == 0) return nullptr;
+    *chunks = stream_chunks(longest, chunk);
+    return (uint64_t)units * *chunks > 0x7FFFFFFFull ? STREAM_CHUNKS : nullptr;
+}
+
+// A finishing call, which writes up to `tail` outputs a row (the caller has held out_stride against it).  No tail (a filter
+// stream whose filters have one tap each): nothing is written, and `out` is not looked at.
+inline const char *stream_finish_error(const void *out, uint64_t out_stride, uint32_t n_rows, uint64_t tail, uint32_t units,
+                                       uint32_t chunk, uint64_t *chunks)
+{
+    if (tail == 0) return nullptr;
+    if (!out) return ROWS_NULL;
+    if (!rows_span_fits(out_stride, n_rows)) return ROWS_SPAN;
+    *chunks = stream_chunks(tail, chunk);
+    return (uint64_t)units * *chunks > 0x7FFFFFFFull ? STREAM_CHUNKS : nullptr;
 }
 
 }  // namespace grail

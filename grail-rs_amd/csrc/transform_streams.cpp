@@ -1,0 +1,327 @@
+// transform_streams.cpp — finished rows filtered, resampled and limited chunk by chunk: grail_filter_stream_open / _next_async /
+// _finish_async / _close (fir_kernels.hip), grail_resample_stream_* (resample_kernels.hip, §4.16) and
+// grail_limit_stream_* (limiter_kernels.hip, §4.17).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp,
+// limit_plan.cpp; their common end row_checks.h), what it keeps beside the rings, and its two launches.  What the three do alike
+// stands once, first: telling a stream of the context's, its device state, a finishing call's marks, its close.
+#include "transform_state.h"
+
+using namespace grail;
+using namespace grail::host;
+
+namespace {
+
+int refuse(const char *who, const std::string &why) { return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": " + why); }
+
+// The first two refusals of a call `who` on a stream of the context's `list`, which the refusals call a `noun` stream.  Without a
+// context the stream is not looked up, and the caller does not look into it: its checks run with stand-in numbers, and the call
+// ends at bind_device.
+template <typename T>
+int known(grail_ctx *ctx, Owned<T> TransformState::*list, const T *s, const char *who, const char *noun)
+{
+    if (!s) return refuse(who, "the stream is NULL");
+    if (ctx && !own(ctx, list, s)) return refuse(who, std::string("not an open ") + noun + " stream of this context");
+    return GRAIL_OK;
+}
+
+template <typename T>
+int stream_close(grail_ctx *ctx, Owned<T> TransformState::*list, T *s, const char *who, const char *noun)
+{
+    if (!s) return GRAIL_OK;
+    if (!ctx) return refuse(who, "ctx is NULL");
+    if (!own(ctx, list, s)) return refuse(who, std::string("not an open ") + noun + " stream of this context");
+    // (a kernel or an upload still queued may be using its state, or what the kind keeps beside it)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    (peek(ctx)->*list).remove(s);
+    return GRAIL_OK;
+}
+
+// The device state of a stream just opened (n_rows, units and ring_cap are set), `words` state words a unit: no sample fed,
+// nothing ended.  The rings are zeroed all the same: a kernel reads a ring before it was written at most where the index
+// arithmetic discards what was read.
+int alloc_state(grail_ctx *ctx, ChunkedStream &s, size_t words)
+{
+    HIP_TRY(s.d_state.alloc(s.units * words));
+    HIP_TRY(s.d_ring.alloc((size_t)s.n_rows * s.ring_cap));
+    HIP_TRY(s.d_mark.alloc(s.units));
+    HIP_TRY(hipMemsetAsync(s.d_state.get(), 0, s.units * words * sizeof(uint64_t), ctx->stream));
+    HIP_TRY(hipMemsetAsync(s.d_ring.get(), 0, (size_t)s.n_rows * s.ring_cap * sizeof(float), ctx->stream));
+    return GRAIL_OK;
+}
+
+// A finishing call's marks, one byte a unit, on their way to the device: *mark_dev is where the kernels read them, NULL
+// (every unit) where the caller gave none.  The upload reads the stream's host copy when the queue gets to it, so the copy is
+// rewritten only behind the event of the upload before.
+int marks(grail_ctx *ctx, ChunkedStream &s, const uint8_t *which, const uint8_t **mark_dev)
+{
+    *mark_dev = nullptr;
+    if (!which) return GRAIL_OK;
+    if (s.ev_mark.get())
+        HIP_TRY(hipEventSynchronize(s.ev_mark));
+    else
+        HIP_TRY(s.ev_mark.create());
+    s.mark.assign(which, which + s.units);
+    HIP_TRY(hipMemcpyAsync(s.d_mark.get(), s.mark.data(), s.units, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipEventRecord(s.ev_mark, ctx->stream));
+    *mark_dev = s.d_mark.get();
+    return GRAIL_OK;
+}
+
+// The two kernels of a call on a stream: the outputs (chunks = 0: there are none to write), then the state.  One function a
+// kind, for their launches take what the kind keeps.
+int fir_stream_call(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev, uint64_t in_stride,
+                    const uint32_t *in_len_dev, const uint8_t *mark_dev, bool finishing, uint64_t chunks, float *out_dev,
+                    uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev)
+{
+    TransformState *st;
+    int rc = state(ctx, &st);
+    if (rc) return rc;
+    const grail_fir *set = fs->set;
+    if (chunks) {
+        if ((rc = st->d_firbad.reserve(ctx->stream, (size_t)fs->units * (size_t)chunks))) return rc;
+        const hipError_t e = launch_fir_stream(in_dev, in_stride, in_len_dev, fs->n_rows, fs->d_filter.get(), set->d_taps.get(),
+                                               set->d_desc.get(), set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap,
+                                               mark_dev, finishing, (uint32_t)chunks, out_dev, out_stride, st->d_firbad.get(),
+                                               ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "fir stream kernel launch");
+    }
+    const hipError_t e = launch_fir_stream_advance(in_dev, in_stride, in_len_dev, fs->n_rows, fs->d_filter.get(), set->d_desc.get(),
+                                                   set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap, mark_dev, finishing,
+                                                   st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "fir stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+int resample_stream_call(grail_ctx *ctx, grail_resample_stream *rs, const float *in_dev, uint64_t in_stride,
+                         const uint32_t *in_len_dev, const uint8_t *mark_dev, bool finishing, uint64_t chunks, float *out_dev,
+                         uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev)
+{
+    TransformState *st;
+    int rc = state(ctx, &st);
+    if (rc) return rc;
+    if (chunks) {
+        if ((rc = st->d_rbad.reserve(ctx->stream, (size_t)rs->units * (size_t)chunks))) return rc;
+        const hipError_t e = launch_resample_stream(in_dev, in_stride, in_len_dev, rs->n_rows, rs->up, rs->down, rs->taps,
+                                                    rs->d_table.get(), rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev,
+                                                    finishing, (uint32_t)chunks, out_dev, out_stride, st->d_rbad.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "resample stream kernel launch");
+    }
+    const hipError_t e = launch_resample_stream_advance(in_dev, in_stride, in_len_dev, rs->n_rows, rs->up, rs->down, rs->taps,
+                                                        rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev, finishing,
+                                                        st->d_rbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "resample stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+int limit_stream_call(grail_ctx *ctx, grail_limit_stream *ls, const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev,
+                      const uint8_t *mark_dev, bool finishing, uint64_t chunks, float *out_dev, uint64_t out_stride,
+                      uint32_t *out_len_dev, float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev)
+{
+    TransformState *st;
+    int rc = state(ctx, &st);
+    if (rc) return rc;
+    if (chunks) {
+        if ((rc = st->d_lstat.reserve(ctx->stream, (size_t)ls->units * (size_t)chunks * limit_chunk_bytes()))) return rc;
+        const hipError_t e = launch_limit_stream(in_dev, in_stride, in_len_dev, ls->units, ls->group, ls->ceiling, ls->ell,
+                                                 ls->d_state.get(), ls->d_ring.get(), ls->ring_cap, mark_dev, finishing,
+                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "limit stream kernel launch");
+    }
+    const hipError_t e = launch_limit_stream_advance(in_dev, in_stride, in_len_dev, ls->units, ls->group, ls->ell, ls->d_state.get(),
+                                                     ls->d_ring.get(), ls->ring_cap, mark_dev, finishing, st->d_lstat.get(),
+                                                     (uint32_t)chunks, out_len_dev, min_gain_dev, n_limited_dev, nonfinite_dev,
+                                                     ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "limit stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+// In every call below, what is wrong with the arguments is said before what is wrong with the machine (bind_device).  An open
+// has no context without a device, so its "NULL argument" stands for both.
+
+int grail_filter_stream_open(grail_ctx *ctx, const grail_fir *set, uint32_t n_rows, const uint32_t *filter, grail_filter_stream **out)
+{
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_open: NULL argument");
+    if (!own(ctx, &TransformState::firs, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_filter_stream_open: not a filter set of this context");
+    if (const char *why = fir_stream_open_error(filter, n_rows, set->n_filters)) return refuse("grail_filter_stream_open", why);
+    int rc = bind(ctx);
+    if (rc) return rc;
+    std::unique_ptr<grail_filter_stream> fs(new (std::nothrow) grail_filter_stream());
+    if (!fs) return fail(GRAIL_ERR_OUT_OF_MEMORY, "filter stream");
+    fs->set = set;
+    fs->n_rows = fs->units = n_rows;
+    fs->ring_cap = fir_stream_ring_capacity(set->taps_max);
+    fs->filter.assign(n_rows, 0u);
+    if (filter) std::copy(filter, filter + n_rows, fs->filter.begin());
+    HIP_TRY(upload(fs->d_filter, fs->filter.data(), n_rows, ctx->stream));
+    if ((rc = alloc_state(ctx, *fs, 1))) return rc;
+    *out = peek(ctx)->fir_streams.add(std::move(fs));       // (the set was found: the state is there)
+    return GRAIL_OK;
+}
+
+int grail_filter_stream_close(grail_ctx *ctx, grail_filter_stream *fs)
+{
+    return stream_close(ctx, &TransformState::fir_streams, fs, "grail_filter_stream_close", "filter");
+}
+
+int grail_filter_stream_next_async(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev, uint64_t in_stride,
+                                   const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                   uint32_t *nonfinite_dev)
+{
+    const char *who = "grail_filter_stream_next_async";
+    int rc = known(ctx, &TransformState::fir_streams, fs, who, "filter");
+    if (rc) return rc;
+    // (without a context: the checks of one row)
+    uint64_t chunks = 0;
+    if (const char *why = fir_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? fs->n_rows : 1u, out_dev, out_stride, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    return fir_stream_call(ctx, fs, in_dev, in_stride, in_len_dev, nullptr, false, chunks, out_dev, out_stride, out_len_dev,
+                           nonfinite_dev);
+}
+
+int grail_filter_stream_finish_async(grail_ctx *ctx, grail_filter_stream *fs, const uint8_t *which, float *out_dev,
+                                     uint64_t out_stride, uint32_t *out_len_dev)
+{
+    const char *who = "grail_filter_stream_finish_async";
+    int rc = known(ctx, &TransformState::fir_streams, fs, who, "filter");
+    if (rc) return rc;
+    // (without a context: the checks of one row and a set of one tap)
+    uint64_t chunks = 0;
+    if (const char *why = fir_stream_finish_error(out_dev, out_stride, ctx ? fs->n_rows : 1u, ctx ? fs->set->taps_max : 1u, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    const uint8_t *mark_dev;
+    if ((rc = marks(ctx, *fs, which, &mark_dev))) return rc;
+    return fir_stream_call(ctx, fs, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, nullptr);
+}
+
+int grail_resample_stream_open(grail_ctx *ctx, uint32_t rate_in, uint32_t rate_out, uint32_t n_rows, grail_resample_stream **out)
+{
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: NULL argument");
+    uint32_t U, D, P;
+    if (grail_resample_ratio(rate_in, rate_out, &U, &D, &P))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: the rates are equal, 0, or need more than 32 768 table entries");
+    if (n_rows == 0) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: n_rows is 0");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_resample_stream> rs(new (std::nothrow) grail_resample_stream());
+    if (!rs) return fail(GRAIL_ERR_OUT_OF_MEMORY, "resample stream");
+    rs->up = U, rs->down = D, rs->taps = P;
+    rs->n_rows = rs->units = n_rows;
+    rs->ring_cap = resample_stream_ring_capacity(P);
+    rs->table.assign((size_t)U * P, 0);
+    if (grail_resample_coefficients(rate_in, rate_out, rs->table.data(), U * P))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_stream_open: no table for this pair of rates");
+    HIP_TRY(upload(rs->d_table, rs->table.data(), rs->table.size(), ctx->stream));
+    if ((rc = alloc_state(ctx, *rs, RESAMPLE_STREAM_STATE_WORDS))) return rc;       // (the next output is output 0)
+    *out = st->resample_streams.add(std::move(rs));
+    return GRAIL_OK;
+}
+
+int grail_resample_stream_close(grail_ctx *ctx, grail_resample_stream *rs)
+{
+    return stream_close(ctx, &TransformState::resample_streams, rs, "grail_resample_stream_close", "resample");
+}
+
+int grail_resample_stream_next_async(grail_ctx *ctx, grail_resample_stream *rs, const float *in_dev, uint64_t in_stride,
+                                     const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                     uint32_t *nonfinite_dev)
+{
+    const char *who = "grail_resample_stream_next_async";
+    int rc = known(ctx, &TransformState::resample_streams, rs, who, "resample");
+    if (rc) return rc;
+    // (without a context: the checks of one row at a ratio of 1 / 1)
+    uint64_t chunks = 0;
+    if (const char *why = resample_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? rs->n_rows : 1u, out_dev, out_stride,
+                                                     ctx ? rs->up : 1u, ctx ? rs->down : 1u, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    return resample_stream_call(ctx, rs, in_dev, in_stride, in_len_dev, nullptr, false, chunks, out_dev, out_stride, out_len_dev,
+                                nonfinite_dev);
+}
+
+int grail_resample_stream_finish_async(grail_ctx *ctx, grail_resample_stream *rs, const uint8_t *which, float *out_dev,
+                                       uint64_t out_stride, uint32_t *out_len_dev)
+{
+    const char *who = "grail_resample_stream_finish_async";
+    int rc = known(ctx, &TransformState::resample_streams, rs, who, "resample");
+    if (rc) return rc;
+    // (without a context: the checks of one row at a ratio of 1 / 1 with two taps, a tail of one output)
+    uint64_t chunks = 0;
+    if (const char *why = resample_stream_finish_error(out_dev, out_stride, ctx ? rs->n_rows : 1u, ctx ? rs->up : 1u,
+                                                       ctx ? rs->down : 1u, ctx ? rs->taps : 2u, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    const uint8_t *mark_dev;
+    if ((rc = marks(ctx, *rs, which, &mark_dev))) return rc;
+    return resample_stream_call(ctx, rs, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, nullptr);
+}
+
+int grail_limit_stream_open(grail_ctx *ctx, uint32_t n_rows, uint32_t group, float ceiling, uint32_t lookahead_log2,
+                            grail_limit_stream **out)
+{
+    // (this one says what is wrong with its numbers first)
+    if (const char *why = limit_stream_open_error(n_rows, group, ceiling, lookahead_log2)) return refuse("grail_limit_stream_open", why);
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_stream_open: NULL argument");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_limit_stream> ls(new (std::nothrow) grail_limit_stream());
+    if (!ls) return fail(GRAIL_ERR_OUT_OF_MEMORY, "limit stream");
+    ls->n_rows = n_rows, ls->group = group, ls->units = n_rows / group;
+    ls->ceiling = ceiling, ls->ell = lookahead_log2;
+    ls->ring_cap = limit_stream_ring_capacity(lookahead_log2);
+    if ((rc = alloc_state(ctx, *ls, 1))) return rc;
+    *out = st->limit_streams.add(std::move(ls));
+    return GRAIL_OK;
+}
+
+int grail_limit_stream_close(grail_ctx *ctx, grail_limit_stream *ls)
+{
+    return stream_close(ctx, &TransformState::limit_streams, ls, "grail_limit_stream_close", "limit");
+}
+
+int grail_limit_stream_next_async(grail_ctx *ctx, grail_limit_stream *ls, const float *in_dev, uint64_t in_stride,
+                                  const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                  float *min_gain_dev, uint32_t *n_limited_dev, uint32_t *nonfinite_dev)
+{
+    const char *who = "grail_limit_stream_next_async";
+    int rc = known(ctx, &TransformState::limit_streams, ls, who, "limit");
+    if (rc) return rc;
+    // (without a context: the checks of one row alone)
+    uint64_t chunks = 0;
+    if (const char *why = limit_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? ls->n_rows : 1u, ctx ? ls->group : 1u, out_dev,
+                                                  out_stride, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    return limit_stream_call(ctx, ls, in_dev, in_stride, in_len_dev, nullptr, false, chunks, out_dev, out_stride, out_len_dev,
+                             min_gain_dev, n_limited_dev, nonfinite_dev);
+}
+
+int grail_limit_stream_finish_async(grail_ctx *ctx, grail_limit_stream *ls, const uint8_t *which, float *out_dev,
+                                    uint64_t out_stride, uint32_t *out_len_dev, float *min_gain_dev, uint32_t *n_limited_dev)
+{
+    const char *who = "grail_limit_stream_finish_async";
+    int rc = known(ctx, &TransformState::limit_streams, ls, who, "limit");
+    if (rc) return rc;
+    // (without a context: the checks of one row alone at a look-ahead of one sample)
+    uint64_t chunks = 0;
+    if (const char *why = limit_stream_finish_error(out_dev, out_stride, ctx ? ls->n_rows : 1u, ctx ? ls->group : 1u,
+                                                    ctx ? ls->ell : 0u, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    const uint8_t *mark_dev;
+    if ((rc = marks(ctx, *ls, which, &mark_dev))) return rc;
+    return limit_stream_call(ctx, ls, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, min_gain_dev,
+                             n_limited_dev, nullptr);
+}
+
+}  // extern "C"

@@ -963,6 +963,22 @@ class LiveStream(Stream):
         return out
 
 
+def _waited(ctx, n, types, call):
+    """The waited-for form of a call whose results are device arrays: n words of each of `types` in device memory, call(*them),
+    the results copied back; the wait and the release whatever happened.  A tuple of arrays, one per type."""
+    res = [np.zeros(n, dtype=t) for t in types]
+    d = [ctx.device_alloc(n * 4) for _ in res]
+    try:
+        call(*d)
+        for dst, src in zip(res, d):
+            ctx.d2h(dst, src, n * 4)
+    finally:
+        ctx.sync()
+        for p in d:
+            ctx.device_free(p)
+    return tuple(res)
+
+
 class LimitStream:
     """A limit stream of a Context (Context.limit_stream_open), beside the fir_stream_* and resample_stream_* helpers: the
     handle with what the waited-for forms need to size their results, one per group."""
@@ -981,17 +997,7 @@ class LimitStream:
                                                     out_len_dev, min_gain_dev, n_limited_dev, nonfinite_dev))
 
     def _waited(self, types, call):
-        res = [np.zeros(self.n_groups, dtype=t) for t in types]
-        d = [self.ctx.device_alloc(self.n_groups * 4) for _ in res]
-        try:
-            call(*d)
-            for dst, src in zip(res, d):
-                self.ctx.d2h(dst, src, self.n_groups * 4)
-        finally:
-            self.ctx.sync()
-            for p in d:
-                self.ctx.device_free(p)
-        return tuple(res)
+        return _waited(self.ctx, self.n_groups, types, call)
 
     def next(self, in_dev, in_stride, in_len_dev, out_dev, out_stride):
         """next_async, waited for, the results copied back: (out_len uint32, min_gain float32, n_limited uint32, nonfinite
@@ -1407,17 +1413,8 @@ class Context:
     def fir_stream_next(self, fs, n_rows, in_dev, in_stride, in_len_dev, out_dev, out_stride):
         """fir_stream_next_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a row
         that had ended and was fed: (LIMIT_REFUSED, 0)."""
-        res = [np.zeros(n_rows, dtype=np.uint32) for _ in range(2)]
-        d = [self.device_alloc(n_rows * 4) for _ in res]
-        try:
-            self.fir_stream_next_async(fs, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d)
-            for dst, src in zip(res, d):
-                self.d2h(dst, src, n_rows * 4)
-        finally:
-            self.sync()
-            for p in d:
-                self.device_free(p)
-        return tuple(res)
+        return _waited(self, n_rows, (np.uint32, np.uint32),
+                       lambda *d: self.fir_stream_next_async(fs, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d))
 
     def fir_stream_finish(self, fs, n_rows, out_dev, out_stride, which=None, out_len_dev=None):
         """grail_filter_stream_finish_async: the rows marked in which (a host sequence, non-zero = marked; None: every row)
@@ -1425,19 +1422,11 @@ class Context:
         per row; 0 for rows not marked or ended before) returned."""
         marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
         assert marks is None or len(marks) == n_rows
-        own = None if out_len_dev is not None else self.device_alloc(n_rows * 4)
-        try:
+
+        def finish(out_len):
             _check(load().grail_filter_stream_finish_async(self.handle, fs, None if marks is None else marks.ctypes.data, out_dev,
-                                                           out_stride, out_len_dev if own is None else own))
-            if own is None:
-                return None
-            res = np.zeros(n_rows, dtype=np.uint32)
-            self.d2h(res, own, n_rows * 4)
-            return res
-        finally:
-            if own is not None:
-                self.sync()
-                self.device_free(own)
+                                                          out_stride, out_len))
+        return finish(out_len_dev) if out_len_dev is not None else _waited(self, n_rows, (np.uint32,), finish)[0]
 
     def fir_stream_close(self, fs):
         """grail_filter_stream_close: waits for the context's stream, then releases the stream."""
@@ -1461,17 +1450,8 @@ class Context:
     def resample_stream_next(self, rs, n_rows, in_dev, in_stride, in_len_dev, out_dev, out_stride):
         """resample_stream_next_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a
         row that had ended and was fed: (LIMIT_REFUSED, 0)."""
-        res = [np.zeros(n_rows, dtype=np.uint32) for _ in range(2)]
-        d = [self.device_alloc(n_rows * 4) for _ in res]
-        try:
-            self.resample_stream_next_async(rs, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d)
-            for dst, src in zip(res, d):
-                self.d2h(dst, src, n_rows * 4)
-        finally:
-            self.sync()
-            for p in d:
-                self.device_free(p)
-        return tuple(res)
+        return _waited(self, n_rows, (np.uint32, np.uint32),
+                       lambda *d: self.resample_stream_next_async(rs, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d))
 
     def resample_stream_finish(self, rs, n_rows, out_dev, out_stride, which=None, out_len_dev=None):
         """grail_resample_stream_finish_async: the rows marked in which (a host sequence, non-zero = marked; None: every row)
@@ -1479,19 +1459,11 @@ class Context:
         per row; 0 for rows not marked or ended before) returned."""
         marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
         assert marks is None or len(marks) == n_rows
-        own = None if out_len_dev is not None else self.device_alloc(n_rows * 4)
-        try:
+
+        def finish(out_len):
             _check(load().grail_resample_stream_finish_async(self.handle, rs, None if marks is None else marks.ctypes.data, out_dev,
-                                                             out_stride, out_len_dev if own is None else own))
-            if own is None:
-                return None
-            res = np.zeros(n_rows, dtype=np.uint32)
-            self.d2h(res, own, n_rows * 4)
-            return res
-        finally:
-            if own is not None:
-                self.sync()
-                self.device_free(own)
+                                                            out_stride, out_len))
+        return finish(out_len_dev) if out_len_dev is not None else _waited(self, n_rows, (np.uint32,), finish)[0]
 
     def resample_stream_close(self, rs):
         """grail_resample_stream_close: waits for the context's stream, then releases the stream."""

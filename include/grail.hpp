@@ -191,6 +191,52 @@ private:
     uint32_t longest_ = 1;
 };
 
+namespace detail {
+// the stride that holds the longest of a call's chunks, a multiple of 64 (no chunks, a finishing call: 0)
+inline uint64_t chunk_stride(const std::vector<std::vector<float>> *chunks)
+{
+    size_t longest = 0;
+    if (chunks)
+        for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
+    return (longest + 63) / 64 * 64;
+}
+
+// One call on a stream of n rows, there and back: the rows' chunks (NULL: a finishing call, nothing goes in) and their lengths
+// to device buffers of `stride` samples a row, entry(in, stride, len, out, out_stride, out_len) for the entry point, which writes
+// at most `room` samples a row and one length per `group` rows, and each row cut at its length (none for a length of 0, or of
+// a unit that was refused).  Everything is freed before a failure is thrown.
+template <typename Entry>
+std::vector<std::vector<float>> stream_round_trip(grail_ctx *ctx, uint32_t n, uint32_t group, const std::vector<std::vector<float>> *chunks,
+                                                  uint64_t stride, uint64_t room, Entry entry)
+{
+    const uint32_t units = n / group;
+    const uint64_t out_stride = (room + 63) / 64 * 64;
+    std::vector<std::vector<float>> out(n);
+    std::vector<uint32_t> lens(n, 0u), out_lens(units, 0u);
+    for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
+    void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
+    int rc = grail_device_alloc(ctx, (size_t)n * stride * 4 + 4, &d_in);
+    if (!rc) rc = grail_device_alloc(ctx, (size_t)n * out_stride * 4 + 4, &d_out);
+    if (!rc) rc = grail_device_alloc(ctx, (size_t)n * 4, &d_len);
+    if (!rc) rc = grail_device_alloc(ctx, (size_t)units * 4, &d_out_len);
+    for (uint32_t i = 0; !rc && i < n; ++i)
+        if (lens[i]) rc = grail_memcpy_h2d(ctx, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
+    if (!rc) rc = grail_memcpy_h2d(ctx, d_len, lens.data(), (size_t)n * 4);
+    if (!rc) rc = entry((const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out, out_stride, (uint32_t *)d_out_len);
+    if (!rc) rc = grail_memcpy_d2h(ctx, out_lens.data(), d_out_len, (size_t)units * 4);
+    for (uint32_t i = 0; !rc && i < n; ++i) {
+        const uint32_t len = out_lens[i / group];
+        if (!len || len == GRAIL_LIMIT_REFUSED) continue;
+        out[i].resize(len);
+        rc = grail_memcpy_d2h(ctx, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)len * 4);
+    }
+    for (void *p : {d_in, d_out, d_len, d_out_len})
+        if (p) grail_device_free(ctx, p);
+    check(rc);
+    return out;
+}
+}  // namespace detail
+
 // Rows filtered chunk by chunk on a Gpu's device (grail_filter_stream_open; the contract is the header's section "levels,
 // continued: FIR filtering of streams"), made by Gpu::fir_stream: move-only, closed with grail_filter_stream_close.  The
 // chunks' outputs put end to end, then the tails of finish(), are the bits Gpu::fir gives for the whole rows.  It must not
@@ -243,36 +289,12 @@ public:
 private:
     std::vector<std::vector<float>> call(const std::vector<std::vector<float>> *chunks, const uint8_t *which)
     {
-        const uint32_t n = n_rows_;
-        size_t longest = 0;
-        if (chunks)
-            for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
-        const uint64_t stride = (longest + 63) / 64 * 64, out_stride = (std::max<uint64_t>(longest, tail_) + 63) / 64 * 64;
-        std::vector<std::vector<float>> out(n);
-        std::vector<uint32_t> lens(n, 0u), out_lens(n, 0u);
-        for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
-        void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
-        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4 + 4, &d_in);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4 + 4, &d_out);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_out_len);
-        for (uint32_t i = 0; !rc && i < n; ++i)
-            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
-        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
-        if (!rc)
-            rc = chunks ? grail_filter_stream_next_async(ctx_, fs_, (const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out,
-                                                         out_stride, (uint32_t *)d_out_len, nullptr)
-                        : grail_filter_stream_finish_async(ctx_, fs_, which, (float *)d_out, out_stride, (uint32_t *)d_out_len);
-        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)n * 4);
-        for (uint32_t i = 0; !rc && i < n; ++i) {
-            if (!out_lens[i] || out_lens[i] == GRAIL_LIMIT_REFUSED) continue;
-            out[i].resize(out_lens[i]);
-            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)out_lens[i] * 4);
-        }
-        for (void *p : {d_in, d_out, d_len, d_out_len})
-            if (p) grail_device_free(ctx_, p);
-        check(rc);
-        return out;
+        const uint64_t stride = detail::chunk_stride(chunks);
+        return detail::stream_round_trip(ctx_, n_rows_, 1, chunks, stride, std::max<uint64_t>(stride, tail_),
+            [&](const float *in, uint64_t in_stride, const uint32_t *len, float *out, uint64_t out_stride, uint32_t *out_len) {
+                return chunks ? grail_filter_stream_next_async(ctx_, fs_, in, in_stride, len, out, out_stride, out_len, nullptr)
+                              : grail_filter_stream_finish_async(ctx_, fs_, which, out, out_stride, out_len);
+            });
     }
 
     grail_ctx *ctx_ = nullptr;
@@ -345,36 +367,12 @@ public:
 private:
     std::vector<std::vector<float>> call(const std::vector<std::vector<float>> *chunks, const uint8_t *which)
     {
-        const uint32_t n = n_rows_;
-        size_t longest = 0;
-        if (chunks)
-            for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
-        const uint64_t stride = (longest + 63) / 64 * 64, out_stride = (std::max<uint64_t>(most(stride), tail_) + 63) / 64 * 64;
-        std::vector<std::vector<float>> out(n);
-        std::vector<uint32_t> lens(n, 0u), out_lens(n, 0u);
-        for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
-        void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
-        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4 + 4, &d_in);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4 + 4, &d_out);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_out_len);
-        for (uint32_t i = 0; !rc && i < n; ++i)
-            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
-        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
-        if (!rc)
-            rc = chunks ? grail_resample_stream_next_async(ctx_, rs_, (const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out,
-                                                           out_stride, (uint32_t *)d_out_len, nullptr)
-                        : grail_resample_stream_finish_async(ctx_, rs_, which, (float *)d_out, out_stride, (uint32_t *)d_out_len);
-        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)n * 4);
-        for (uint32_t i = 0; !rc && i < n; ++i) {
-            if (!out_lens[i] || out_lens[i] == GRAIL_LIMIT_REFUSED) continue;
-            out[i].resize(out_lens[i]);
-            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)out_lens[i] * 4);
-        }
-        for (void *p : {d_in, d_out, d_len, d_out_len})
-            if (p) grail_device_free(ctx_, p);
-        check(rc);
-        return out;
+        const uint64_t stride = detail::chunk_stride(chunks);
+        return detail::stream_round_trip(ctx_, n_rows_, 1, chunks, stride, std::max<uint64_t>(most(stride), tail_),
+            [&](const float *in, uint64_t in_stride, const uint32_t *len, float *out, uint64_t out_stride, uint32_t *out_len) {
+                return chunks ? grail_resample_stream_next_async(ctx_, rs_, in, in_stride, len, out, out_stride, out_len, nullptr)
+                              : grail_resample_stream_finish_async(ctx_, rs_, which, out, out_stride, out_len);
+            });
     }
 
     grail_ctx *ctx_ = nullptr;
@@ -444,40 +442,15 @@ public:
     }
 
 private:
+    // (one length per group)
     std::vector<std::vector<float>> call(const std::vector<std::vector<float>> *chunks, const uint8_t *which)
     {
-        const uint32_t n = n_rows_, g = groups();
-        size_t longest = 0;
-        if (chunks)
-            for (const auto &c : *chunks) longest = c.size() > longest ? c.size() : longest;
-        const uint64_t stride = (longest + 63) / 64 * 64, out_stride = (std::max<uint64_t>(longest, delay_) + 63) / 64 * 64;
-        std::vector<std::vector<float>> out(n);
-        std::vector<uint32_t> lens(n, 0u), out_lens(g, 0u);
-        for (uint32_t i = 0; chunks && i < n; ++i) lens[i] = (uint32_t)(*chunks)[i].size();
-        void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr, *d_out_len = nullptr;
-        int rc = grail_device_alloc(ctx_, (size_t)n * stride * 4 + 4, &d_in);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * out_stride * 4 + 4, &d_out);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 4, &d_len);
-        if (!rc) rc = grail_device_alloc(ctx_, (size_t)g * 4, &d_out_len);
-        for (uint32_t i = 0; !rc && i < n; ++i)
-            if (lens[i]) rc = grail_memcpy_h2d(ctx_, (float *)d_in + (size_t)i * stride, (*chunks)[i].data(), (size_t)lens[i] * 4);
-        if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, lens.data(), (size_t)n * 4);
-        if (!rc)
-            rc = chunks ? grail_limit_stream_next_async(ctx_, ls_, (const float *)d_in, stride, (const uint32_t *)d_len, (float *)d_out,
-                                                        out_stride, (uint32_t *)d_out_len, nullptr, nullptr, nullptr)
-                        : grail_limit_stream_finish_async(ctx_, ls_, which, (float *)d_out, out_stride, (uint32_t *)d_out_len, nullptr,
-                                                          nullptr);
-        if (!rc) rc = grail_memcpy_d2h(ctx_, out_lens.data(), d_out_len, (size_t)g * 4);
-        for (uint32_t i = 0; !rc && i < n; ++i) {
-            const uint32_t len = out_lens[i / group_];
-            if (!len || len == GRAIL_LIMIT_REFUSED) continue;
-            out[i].resize(len);
-            rc = grail_memcpy_d2h(ctx_, out[i].data(), (const float *)d_out + (size_t)i * out_stride, (size_t)len * 4);
-        }
-        for (void *p : {d_in, d_out, d_len, d_out_len})
-            if (p) grail_device_free(ctx_, p);
-        check(rc);
-        return out;
+        const uint64_t stride = detail::chunk_stride(chunks);
+        return detail::stream_round_trip(ctx_, n_rows_, group_, chunks, stride, std::max<uint64_t>(stride, delay_),
+            [&](const float *in, uint64_t in_stride, const uint32_t *len, float *out, uint64_t out_stride, uint32_t *out_len) {
+                return chunks ? grail_limit_stream_next_async(ctx_, ls_, in, in_stride, len, out, out_stride, out_len, nullptr, nullptr, nullptr)
+                              : grail_limit_stream_finish_async(ctx_, ls_, which, out, out_stride, out_len, nullptr, nullptr);
+            });
     }
 
     grail_ctx *ctx_ = nullptr;

@@ -1,7 +1,8 @@
 // Drives the row-pair check (csrc/row_checks.h: the buffers, the 2^60 span, the overlap of the two address ranges, the 32 bits
 // of an output length) along the edges of each rule under AddressSanitizer and UBSan (tests/test_row_checks_sanitize.py builds
 // and runs it).  Every address is a number nobody may look behind.  grail_limit_async, grail_resample_async and
-// grail_fir_async (csrc/transforms.cpp) reach this arithmetic only through the loaded library; here it runs observed.
+// grail_fir_async (csrc/transforms.cpp) reach this arithmetic only through the loaded library; here it runs observed.  Then
+// the same for where the checks of the calls on streams (csrc/transform_streams.cpp) end alike: a call's chunks and their count.
 #include <cstdint>
 #include <cstdio>
 #include <initializer_list>
@@ -106,6 +107,48 @@ int main()
     CHECK(pair(4096, P32, 1, FAR, P32, STRIDED, STRIDED, P32) == ROWS_TOO_LONG && pair(4096, 1, 2, FAR, ~0ull >> 5, STRIDED, STRIDED, ~0ull) == ROWS_TOO_LONG);
     CHECK(pair(4096, P32, 1, FAR, P32, STRIDED, STRIDED, 0) == nullptr && pair(4096, 64, 2, FAR, 0, STRIDED, STRIDED, ~0ull) == nullptr);
     CHECK(pair(4096, P32, 1, 4096, P32, STRIDED, STRIDED, P32) == OVER && pair(4096, P32, 1, FAR, P60 + 1, STRIDED, STRIDED, P32) == ROWS_SPAN);
+
+    // ---- the calls on streams
+    // the chunks of a row: longest at 0, 1, chunk, chunk + 1, 2^32 - 1, and cut there
+    const uint32_t CH = 2048;
+    CHECK(stream_chunks(0, CH) == 0 && stream_chunks(1, CH) == 1 && stream_chunks(CH, CH) == 1 && stream_chunks(CH + 1, CH) == 2);
+    CHECK(stream_chunks(P32 - 1, CH) == 1u << 21 && stream_chunks(P32, CH) == 1u << 21 && stream_chunks(~0ull, CH) == 1u << 21);
+    CHECK(stream_chunks(P32 - 1, 1) == P32 - 1 && stream_chunks(~0ull, 1) == P32 - 1 && stream_chunks(P32 - 1, 0xFFFFFFFFu) == 1);
+    // a feeding call: the pair's refusals first, no chunks of strides of 0, else the chunks of the longest output
+    const uint64_t longests[] = {1, CH, CH + 1, P32 - 1};
+    const uint64_t counts[] = {1, 1, 2, 1u << 21};
+    for (int i = 0; i < 4; ++i) {
+        uint64_t chunks = 77;
+        CHECK(stream_next_error({at(A), longests[i], at(LEN), 3, at(FAR), longests[i]}, longests[i], 3, CH, &chunks) == nullptr);
+        CHECK(chunks == counts[i]);
+    }
+    uint64_t chunks = 77;
+    CHECK(stream_next_error({nullptr, 0, at(LEN), 3, nullptr, 0}, 0, 3, CH, &chunks) == nullptr && chunks == 77);
+    CHECK(stream_next_error({nullptr, 0, nullptr, 3, nullptr, 0}, 0, 3, CH, &chunks) == ROWS_NULL && chunks == 77);
+    CHECK(stream_next_error({at(A), 64, at(LEN), 3, nullptr, 64}, 64, 3, CH, &chunks) == ROWS_NULL);
+    CHECK(stream_next_error({at(A), P60, at(LEN), 3, at(FAR), P60}, P32 - 1, 3, CH, &chunks) == ROWS_SPAN);
+    CHECK(stream_next_error({at(A), 64, at(LEN), 3, at(A + 4), 64}, 64, 3, CH, &chunks) != nullptr && chunks == 77);
+    CHECK(stream_next_error({at(A), 1, at(LEN), 1, at(FAR), P32}, P32, 1, CH, &chunks) == ROWS_TOO_LONG && chunks == 77);
+    // ... units x chunks at 2^31 - 1 and at 2^31, by the chunks and by the units
+    const uint32_t P31 = 1u << 31;
+    CHECK(stream_next_error({at(A), P31 - 1, at(LEN), 1, at(FAR), P31 - 1}, P31 - 1, 1, 1, &chunks) == nullptr && chunks == P31 - 1);
+    CHECK(stream_next_error({at(A), P31, at(LEN), 1, at(FAR), P31}, P31, 1, 1, &chunks) == STREAM_CHUNKS && chunks == P31);
+    CHECK(stream_next_error({at(A), 1, at(LEN), P31 - 1, at(FAR), 1}, 1, P31 - 1, CH, &chunks) == nullptr && chunks == 1);
+    CHECK(stream_next_error({at(A), 1, at(LEN), P31, at(FAR), 1}, 1, P31, CH, &chunks) == STREAM_CHUNKS);
+    CHECK(stream_next_error({at(A), CH + 1, at(LEN), P31, at(FAR), CH + 1}, CH + 1, P31 / 2 - 1, CH, &chunks) == nullptr && chunks == 2);
+    CHECK(stream_next_error({at(A), CH + 1, at(LEN), P31, at(FAR), CH + 1}, CH + 1, P31 / 2, CH, &chunks) == STREAM_CHUNKS);
+    // a finishing call: no tail, nothing looked at; else out, its span, the chunks of the tail
+    chunks = 77;
+    CHECK(stream_finish_error(nullptr, P60 + 1, 0xFFFFFFFFu, 0, 0xFFFFFFFFu, CH, &chunks) == nullptr && chunks == 77);
+    CHECK(stream_finish_error(nullptr, 64, 3, 1, 3, CH, &chunks) == ROWS_NULL && chunks == 77);
+    CHECK(stream_finish_error(at(FAR), P60 / 3 + 1, 3, 1, 3, CH, &chunks) == ROWS_SPAN && chunks == 77);
+    CHECK(stream_finish_error(at(FAR), P60 / 3, 3, 1, 3, CH, &chunks) == nullptr && chunks == 1);
+    CHECK(stream_finish_error(at(FAR), 4096, 3, CH, 3, CH, &chunks) == nullptr && chunks == 1);
+    CHECK(stream_finish_error(at(FAR), 4096, 3, CH + 1, 3, CH, &chunks) == nullptr && chunks == 2);
+    CHECK(stream_finish_error(at(FAR), P32, 3, P32 - 1, 3, CH, &chunks) == nullptr && chunks == 1u << 21);
+    CHECK(stream_finish_error(at(FAR), 64, P31 - 1, 1, P31 - 1, CH, &chunks) == nullptr && chunks == 1);
+    CHECK(stream_finish_error(at(FAR), 64, P31, 1, P31, CH, &chunks) == STREAM_CHUNKS);
+    CHECK(stream_finish_error(at(FAR), P32, 1, P31 - 1, 1, 1, &chunks) == nullptr && stream_finish_error(at(FAR), P32, 1, P31, 1, 1, &chunks) == STREAM_CHUNKS);
     std::printf("sanitize row checks driver: ok\n");
     return 0;
 }

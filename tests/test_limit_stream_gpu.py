@@ -345,6 +345,41 @@ def test_invalid_arguments_leave_outputs_and_state_untouched(gpu_ctx, dev):
         other.close()
 
 
+def test_two_finishing_calls_with_marks_queued_back_to_back(gpu_ctx, dev):
+    """two `finish` calls with marks, their results left on the device, and no wait between them: the second writes the
+    stream's host copy of the marks anew, which the first's upload may not have read yet, so it waits for the event behind that
+    upload.  The first unit's tail comes from the first call alone and the others' from the second; behind what the feeding
+    call wrote they are the one-shot rows"""
+    ell, n, n_rows, group = 2, 40, 4, 2
+    rng = np.random.default_rng(795)
+    rows = [rng.uniform(-0.6, 0.6, n).astype(np.float32) for _ in range(n_rows)]
+    stride, guard, marks = (delay(ell) + 3) // 4 * 4, 64, ([1, 0], [0, 1])
+    ls = gpu_ctx.limit_stream_open(n_rows, CEILING, ell, group)
+    try:
+        out, res = feed(gpu_ctx, dev, ls, rows)
+        joined = [[out[i, :res[0][i // group]]] for i in range(n_rows)]
+        d_outs = [dev.up(np.full(guard + n_rows * stride + guard, CANARY, np.float32)) for _ in range(2)]
+        d_lens = [dev.up(np.full(n_rows // group, 77, np.uint32)) for _ in range(2)]
+        for d_out, d_len, which in zip(d_outs, d_lens, marks):
+            ls.finish_async(at(d_out, guard), stride, which, d_len)
+        gpu_ctx.sync()
+        lens = [dev.down(p, n_rows // group, np.uint32) for p in d_lens]
+        assert lens[0][0] > 0 and not lens[0][1:].any() and lens[1][0] == 0 and lens[1][1:].all(), lens
+        for d_out, out_len in zip(d_outs, lens):
+            flat = dev.down(d_out, guard + n_rows * stride + guard, np.float32)
+            out = flat[guard:guard + n_rows * stride].reshape(n_rows, stride)
+            assert np.all(flat[:guard] == CANARY) and np.all(flat[guard + n_rows * stride:] == CANARY), "written outside out"
+            for i in range(n_rows):
+                assert np.all(out[i, out_len[i // group]:] == CANARY), (i, "written past the row's tail")
+                joined[i].append(out[i, :out_len[i // group]])
+    finally:
+        ls.close()
+    for g in range(n_rows // group):
+        device, _ = one_shot_on_device(gpu_ctx, dev, rows[g * group:(g + 1) * group], CEILING, ell, group)
+        for j in range(group):
+            assert same_bits(np.concatenate(joined[g * group + j]), device[j]), (g, j)
+
+
 # ---- 11 --------------------------------------------------------------------------------------------------------------------
 def test_interactive_example_limits_what_it_renders(gpu_ctx, dev):
     """grail_interactive --ceiling -6 --lookahead 8 on a short script writes what the same run without the option writes,

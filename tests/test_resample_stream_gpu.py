@@ -351,6 +351,38 @@ def test_calls_queued_with_their_input_overwritten_behind_them(gpu_ctx, dev):
         gpu_ctx.resample_stream_close(rs)
 
 
+def test_two_finishing_calls_with_marks_queued_back_to_back(gpu_ctx, dev):
+    """two `finish` calls with marks, their results left on the device, and no wait between them: the second writes the
+    stream's host copy of the marks anew, which the first's upload may not have read yet, so it waits for the event behind that
+    upload.  The first unit's tail comes from the first call alone and the others' from the second; behind what the feeding
+    call wrote they are the one-shot rows"""
+    rng = np.random.default_rng(67)
+    pair, n_rows, n = (2, 3), 3, 40
+    rows = [noise(n, rng) for _ in range(n_rows)]
+    stride, guard, marks = (tail_room(pair) + 7) // 4 * 4, 64, ([1, 0, 0], [0, 1, 1])
+    rs = gpu_ctx.resample_stream_open(pair[0], pair[1], n_rows)
+    try:
+        out, out_len, _ = feed(gpu_ctx, dev, rs, pair, rows)
+        joined = [[out[i, :out_len[i]]] for i in range(n_rows)]
+        d_outs = [dev.up(np.full(guard + n_rows * stride + guard, CANARY, np.float32)) for _ in range(2)]
+        d_lens = [dev.up(np.full(n_rows, 77, np.uint32)) for _ in range(2)]
+        for d_out, d_len, which in zip(d_outs, d_lens, marks):
+            gpu_ctx.resample_stream_finish(rs, n_rows, at(d_out, guard), stride, which, out_len_dev=d_len)
+        gpu_ctx.sync()
+        lens = [dev.down(p, n_rows, np.uint32) for p in d_lens]
+        assert lens[0][0] > 0 and not lens[0][1:].any() and lens[1][0] == 0 and lens[1][1:].all(), lens
+        for d_out, out_len in zip(d_outs, lens):
+            flat = dev.down(d_out, guard + n_rows * stride + guard, np.float32)
+            out = flat[guard:guard + n_rows * stride].reshape(n_rows, stride)
+            assert np.all(flat[:guard] == CANARY) and np.all(flat[guard + n_rows * stride:] == CANARY), "written outside out"
+            for i in range(n_rows):
+                assert np.all(out[i, out_len[i]:] == CANARY), (i, "written past the row's tail")
+                joined[i].append(out[i, :out_len[i]])
+    finally:
+        gpu_ctx.resample_stream_close(rs)
+    whole_rows([np.concatenate(j) for j in joined], pair, rows)
+
+
 # ---- 7. the chain ------------------------------------------------------------------------------------------------------------------
 def test_a_live_stream_through_the_telephone_band_down_to_8000(built):
     """one live row of a quarter second at 48 kHz, pulled 441 samples at a time straight into the filter stream (300 - 3 400

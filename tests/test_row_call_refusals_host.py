@@ -1,14 +1,19 @@
-"""What the calls that write rows (csrc/transforms.cpp: grail_limit_async, grail_resample_async, grail_fir_async,
-grail_filter_stream_next_async, grail_filter_stream_finish_async) answer to arguments from the edges of their checks, held
-against a recorded table: tests/golden/row_call_refusals.json is what the library of commit 8af9941 answered, when the four
-copies of the row-pair check still stood in levels.cpp and fir_plan.cpp, to the tuples that the seeded generator below
-produces.  Every call passes ctx = NULL and addresses nobody looks behind, so no device is needed and none is used: a tuple
-that gets past every argument check ends at the question for the device (GRAIL_ERR_NO_DEVICE on a machine without one,
-"ctx is NULL" on a machine with one), and both are recorded as "past the checks".  Status and full message must be equal
-tuple by tuple.
+"""What the calls that write rows (csrc/transforms.cpp: grail_limit_async, grail_resample_async, grail_fir_async;
+csrc/transform_streams.cpp: grail_filter_stream_next_async, grail_filter_stream_finish_async) answer to arguments from the
+edges of their checks, held against a recorded table: tests/golden/row_call_refusals.json is what the library of commit
+8af9941 answered, when the four copies of the row-pair check still stood in levels.cpp and fir_plan.cpp, to the tuples that
+the seeded generator below produces.  Every call passes ctx = NULL and addresses nobody looks behind, so no device is needed
+and none is used: a tuple that gets past every argument check ends at the question for the device (GRAIL_ERR_NO_DEVICE on a
+machine without one, "ctx is NULL" on a machine with one), and both are recorded as "past the checks".  Status and full
+message must be equal tuple by tuple.
 
-`PYTHONPATH=.:grail-rs_amd python tests/test_row_call_refusals_host.py` writes the table anew from the built library: only
-on a commit whose refusals are meant to change."""
+The table's second part, "streams", holds the other calls on streams to the same: the feeding and finishing calls of resample
+and limit streams, and all three kinds' open and close.  It is what the library of commit 19f4b0d answered, when every kind of
+stream still had its own copy of the host code in transforms.cpp, to the tuples of a second seeded generator: the first
+part's draws, digest and answers are as they were recorded.
+
+`PYTHONPATH=.:grail-rs_amd python tests/test_row_call_refusals_host.py [rows] [streams]` writes the parts named (none: both)
+anew from the built library: only on a commit whose refusals are meant to change."""
 import ctypes as C
 import hashlib
 import json
@@ -21,8 +26,10 @@ import grail_hip as G
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TABLE = os.path.join(ROOT, "tests", "golden", "row_call_refusals.json")
 SEED = 0x8AF9941
+STREAM_SEED = 0x19F4B0D
 PER_ENTRY = 320
 PAST = "past the checks"
+FINE = (0, "")                   # GRAIL_OK (the message of an earlier refusal is not this call's)
 M64 = (1 << 64) - 1
 
 # ---- the edge grid ------------------------------------------------------------------------------------------------------------------
@@ -107,6 +114,30 @@ def tuples():
     return calls
 
 
+def stream_tuples():
+    """{entry point: [argument tuple, ...]} of the table's second part, ctx (NULL) left out"""
+    d = Draws(STREAM_SEED)
+    kinds = ("filter", "resample", "limit")
+    calls = {f"grail_{kind}_stream_{call}": [] for kind in kinds[1:] for call in ("next_async", "finish_async")}
+    calls.update({f"grail_{kind}_stream_{call}": [] for call in ("open", "close") for kind in kinds})
+    some = lambda address, one_in: None if d.chance(one_in) else address
+    for _ in range(PER_ENTRY):
+        # (without a context a stream's checks run for one row, alone in its group: a ratio of 1 / 1 with two taps, a tail of
+        # one output; a look-ahead of one sample, a delay of 11)
+        for kind, results in (("resample", 2), ("limit", 4)):
+            rows, stride, ln, out, out_stride = row_pair(d, 1, stream=True)
+            calls[f"grail_{kind}_stream_next_async"].append((some(HANDLE, 16), rows, stride, ln, out, out_stride) + (None,) * results)
+            rows, stride, ln, out, out_stride = row_pair(d, 1)
+            calls[f"grail_{kind}_stream_finish_async"].append((some(HANDLE, 8), some(LEN, 2), out, out_stride) + (None,) * (results - 1))
+        # (open without a context: the arguments from both sides of every check, `out` there and not)
+        calls["grail_filter_stream_open"].append((some(HANDLE, 4), d.pick(N_ROWS), some(LEN, 2), some(HANDLE + 64, 4)))
+        calls["grail_resample_stream_open"].append((*d.pick(RATES), d.pick(N_ROWS), some(HANDLE + 64, 4)))
+        calls["grail_limit_stream_open"].append((d.pick(N_ROWS), d.pick(GROUPS), d.pick(CEILINGS), d.pick(LOOKAHEADS), some(HANDLE + 64, 4)))
+        for kind in kinds:
+            calls[f"grail_{kind}_stream_close"].append((some(HANDLE, 2),))
+    return calls
+
+
 def tuples_digest(calls):
     h = hashlib.sha256()
     for name in sorted(calls):
@@ -125,11 +156,11 @@ def answers(lib, calls):
             status = fn(None, *args)
             message = lib.grail_last_error().decode()
             past = status == G.ERR_NO_DEVICE or (status == G.ERR_INVALID_ARG and message == name + ": ctx is NULL")
-            got[name].append(PAST if past else (status, message))
+            got[name].append(PAST if past else FINE if status == G.OK else (status, message))
     return got
 
 
-# Every refusal that a call with ctx = NULL can get from transforms.cpp, row_checks.h and the stream checks of fir_plan.cpp.
+# Every refusal that a call with ctx = NULL can get from transforms.cpp, transform_streams.cpp, row_checks.h and the stream checks of the three plan files.
 # Not reachable without a context, and so not in the table: "not a filter set / not an open filter stream of this context"
 # (nothing is looked up), "more than 2^31 chunks" of the limiter and the resampler (said after the device is asked for) and
 # of a stream call (one row has at most 2^21 chunks), the FIR call's "2^32 output samples" (a tail of 0 adds nothing to a
@@ -147,11 +178,43 @@ REACHABLE = {
                                        "the rows span more than 2^60 samples",
                                        "out_dev overlaps in_dev (a chunk reads what another would have written)"],
     "grail_filter_stream_finish_async": ["the stream is NULL"],
+    # (the second part.  One row at 1 / 1 has a tail of one output and one row alone a delay of 11, so these two finishing
+    # calls do look at out; "more than 2^31 chunks" stays out of reach as above)
+    "grail_resample_stream_next_async": ["the stream is NULL", "out_stride < ceil(in_stride * up / down) (a stream never cuts outputs short)",
+                                         "NULL buffer", "the rows span more than 2^60 samples",
+                                         "out_dev overlaps in_dev (a chunk reads what another would have written)"],
+    "grail_resample_stream_finish_async": ["the stream is NULL", "out_stride < ceil((taps / 2) * up / down), the longest tail",
+                                           "NULL buffer", "the rows span more than 2^60 samples"],
+    "grail_limit_stream_next_async": ["the stream is NULL", "out_stride < in_stride (a stream never cuts outputs short)", "NULL buffer",
+                                      "the rows span more than 2^60 samples",
+                                      "out_dev overlaps in_dev (a chunk reads what another would have written)"],
+    "grail_limit_stream_finish_async": ["the stream is NULL",
+                                        "out_stride is below the stream's delay, GRAIL_LIMIT_STREAM_DELAY(lookahead_log2)",
+                                        "NULL buffer", "the rows span more than 2^60 samples"],
+}
+
+# What open and close can answer without a context, in full: two opens say "NULL argument" before they look at anything, the
+# limit stream's says what is wrong with its numbers first; a close of no stream is fine, and one of a stream asks for the
+# context ("ctx is NULL": recorded as past the checks).
+OPEN_CLOSE = {
+    "grail_filter_stream_open": ["NULL argument"],
+    "grail_resample_stream_open": ["NULL argument"],
+    "grail_limit_stream_open": ["lookahead_log2 is above 10", "n_rows is no multiple of group", "the ceiling is not a finite number above 0",
+                                "n_rows is 0", "NULL argument"],
+    "grail_filter_stream_close": [FINE, PAST],
+    "grail_resample_stream_close": [FINE, PAST],
+    "grail_limit_stream_close": [FINE, PAST],
 }
 
 
 def check_coverage(got):
     for name, rows in got.items():
+        assert len(rows) == PER_ENTRY, name
+        if name in OPEN_CLOSE:
+            want = {a if isinstance(a, tuple) or a == PAST else (G.ERR_INVALID_ARG, name + ": " + a) for a in OPEN_CLOSE[name]}
+            assert set(rows) == want, (name, sorted(map(str, set(rows))))
+            print(f"{name}: {len(want)} distinct answers")
+            continue
         said = {a[1] for a in rows if a != PAST}
         assert all(a[0] == G.ERR_INVALID_ARG for a in rows if a != PAST), name
         assert said == {name + ": " + text for text in REACHABLE[name]}, (name, sorted(said))
@@ -160,10 +223,7 @@ def check_coverage(got):
         assert len(rows) == PER_ENTRY and 4 * past >= len(rows), (name, past)
 
 
-def test_every_call_answers_as_recorded(built):
-    with open(TABLE) as f:
-        table = json.load(f)
-    calls = tuples()
+def held_to(table, calls):
     assert tuples_digest(calls) == table["tuples_sha256"], "the generator no longer produces the tuples that were recorded"
     messages = [PAST if m == PAST else tuple(m) for m in table["messages"]]
     want = {name: [messages[i] for i in table["answers"][name]] for name in calls}
@@ -174,18 +234,38 @@ def test_every_call_answers_as_recorded(built):
             assert g == w, (name, args)
 
 
-if __name__ == "__main__":
-    import subprocess
+def test_every_call_answers_as_recorded(built):
+    with open(TABLE) as f:
+        held_to(json.load(f), tuples())
 
-    import __graft_entry__ as ge
-    ge.build()
-    calls = tuples()
+
+def test_every_stream_call_answers_as_recorded(built):
+    with open(TABLE) as f:
+        held_to(json.load(f)["streams"], stream_tuples())
+
+
+def recorded(seed, calls, commit):
     got = answers(G.load(), calls)
     check_coverage(got)
     messages = [PAST] + sorted({a for rows in got.values() for a in rows if a != PAST})
+    return {"recorded_at": commit, "seed": seed, "tuples_sha256": tuples_digest(calls), "messages": messages,
+            "answers": {name: [messages.index(a) for a in rows] for name, rows in got.items()}}
+
+
+if __name__ == "__main__":
+    import subprocess
+    import sys
+
+    import __graft_entry__ as ge
+    ge.build()
+    parts = sys.argv[1:] or ["rows", "streams"]
     commit = subprocess.run(["git", "-C", ROOT, "rev-parse", "HEAD"], capture_output=True, text=True).stdout.strip()
-    table = {"recorded_at": commit, "seed": SEED, "tuples_sha256": tuples_digest(calls), "messages": messages,
-             "answers": {name: [messages.index(a) for a in rows] for name, rows in got.items()}}
+    with open(TABLE) as f:
+        table = json.load(f)
+    streams = table.pop("streams", None)
+    if "rows" in parts:
+        table = recorded(SEED, tuples(), commit)
+    table["streams"] = recorded(STREAM_SEED, stream_tuples(), commit) if "streams" in parts else streams
     with open(TABLE, "w") as f:
         json.dump(table, f, separators=(",", ":"))
         f.write("\n")
