@@ -548,18 +548,17 @@ public:
         const uint32_t n = (uint32_t)pcm.size();
         void *d_in = nullptr, *d_out = nullptr, *d_len = nullptr;
         std::vector<int16_t> i16(n);
-        check(grail_device_alloc(ctx_, (size_t)n * 4 + 4, &d_in));
-        check(grail_device_alloc(ctx_, (size_t)n * 2 + 16, &d_out));
-        check(grail_device_alloc(ctx_, 4, &d_len));
-        int rc = grail_memcpy_h2d(ctx_, d_in, pcm.data(), (size_t)n * 4);
+        int rc = grail_device_alloc(ctx_, (size_t)n * 4 + 4, &d_in);
+        if (!rc) rc = grail_device_alloc(ctx_, (size_t)n * 2 + 16, &d_out);
+        if (!rc) rc = grail_device_alloc(ctx_, 4, &d_len);
+        if (!rc && n) rc = grail_memcpy_h2d(ctx_, d_in, pcm.data(), (size_t)n * 4);
         if (!rc) rc = grail_memcpy_h2d(ctx_, d_len, &n, 4);
         if (!rc) rc = grail_pcm16_async(ctx_, (const float *)d_in, n, (const uint32_t *)d_len, 1, n,
                                         (int16_t *)d_out, n);
         if (!rc) rc = grail_sync(ctx_);
         if (!rc && n) rc = grail_memcpy_d2h(ctx_, i16.data(), d_out, (size_t)n * 2);
-        grail_device_free(ctx_, d_in);
-        grail_device_free(ctx_, d_out);
-        grail_device_free(ctx_, d_len);
+        for (void *p : {d_in, d_out, d_len})
+            if (p) grail_device_free(ctx_, p);
         check(rc);
         check(grail_wav_write_i16(path.c_str(), i16.data(), n, sample_rate));
     }
