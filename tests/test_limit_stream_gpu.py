@@ -202,6 +202,28 @@ def test_short_groups(gpu_ctx, dev, ell):
         ls.close()
 
 
+def pair_short_of_its_delay():
+    """-> (ell, the pair's members, the split): two calls that leave the pair short of its delay, each with a sample that is not
+    finite in either member, then the rest"""
+    ell = 4
+    rng = np.random.default_rng(735)
+    split = [10, 12, 100]
+    assert split[0] + split[1] < delay(ell) < sum(split)
+    members = [rng.uniform(-0.6, 0.6, sum(split)).astype(np.float32) for _ in range(2)]
+    members[0][[3, 9, 10]] = [np.nan, np.inf, -np.inf]
+    members[1][[0, 21, 22]] = [np.inf, np.nan, np.nan]
+    return ell, members, split
+
+
+def test_a_pair_fed_less_than_its_delay_counts_both_members(gpu_ctx, dev):
+    """group = 2 and calls that write no output: chunk 0 runs all the same and counts what is not finite in both members (the
+    `count == 0` loop over the group), which no other case reaches with more than one member"""
+    ell, members, split = pair_short_of_its_delay()
+    calls, _ = stream_model(members, CEILING, ell, split)
+    assert [(len(k[0][0]), k[3]) for k in calls[:2]] == [(0, 3), (0, 2)] and len(calls[2][0][0]) > 0
+    stream_groups(gpu_ctx, dev, [members], [split], ell)
+
+
 # ---- 5 ---------------------------------------------------------------------------------------------------------------------
 def test_a_window_held_at_gain_zero_across_calls(gpu_ctx, dev):
     ell = 8

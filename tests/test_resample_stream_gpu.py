@@ -12,7 +12,7 @@ import grail_hip as G
 from grail_hip import workload as W
 from fir_model import fir_model
 from resample_model import resample_model
-from resample_stream_model import ceil_div, splits, stream_model
+from resample_stream_model import ceil_div, splits, stream_len, stream_model
 from test_levels_gpu import CANARY, Dev, dev  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -142,12 +142,8 @@ def whole_rows(joined, pair, rows):
 
 
 # ---- 1. every split gives the one-shot row -----------------------------------------------------------------------------------
-@pytest.mark.parametrize("pair", PAIRS)
-def test_every_split_gives_the_one_shot_row(gpu_ctx, dev, pair):
-    """one stream per pair: a row for every length and split.  Rows short of h write only a tail; [1, h, h + 1, 0, rest]
-    lands a call exactly on the first output; Ci + 1 and 2 Ci + 17 put a chunk seam inside a call; every call but the first
-    reads the ring, and the long rows wrap it; (48000, 2000) and (50, 3) are not staged (stream_model asserts that the
-    calls' counts add up to the row's and that their non-finite counts do)"""
+def every_split_rows(pair):
+    """the rows and splits of the test below (tests/test_kernel_paths_host.py walks the same ones for the kernel's variants)"""
     rng = np.random.default_rng(300 + pair[0] % 97 + pair[1] % 89)
     _, U, D, P = table(pair)
     h, Ci = P // 2, ceil_div(CHUNK * D, U)
@@ -156,7 +152,18 @@ def test_every_split_gives_the_one_shot_row(gpu_ctx, dev, pair):
         for split in splits(N, P, Ci, rng):
             rows.append(noise(N, rng, np.cumsum(split)))
             row_splits.append(split)
-    assert any(max(s) > Ci for s in row_splits)                             # a seam inside a call
+    return rows, row_splits
+
+
+@pytest.mark.parametrize("pair", PAIRS)
+def test_every_split_gives_the_one_shot_row(gpu_ctx, dev, pair):
+    """one stream per pair: a row for every length and split.  Rows short of h write only a tail; [1, h, h + 1, 0, rest]
+    lands a call exactly on the first output; Ci + 1 and 2 Ci + 17 put a chunk seam inside a call; every call but the first
+    reads the ring, and the long rows wrap it; (48000, 2000) and (50, 3) are not staged (stream_model asserts that the
+    calls' counts add up to the row's and that their non-finite counts do)"""
+    _, U, D, P = table(pair)
+    rows, row_splits = every_split_rows(pair)
+    assert any(max(s) > ceil_div(CHUNK * D, U) for s in row_splits)         # a seam inside a call
     joined = stream_rows(gpu_ctx, dev, pair, rows, row_splits)
     whole_rows(joined, pair, rows)
     # the calls' counts add up to the row's
@@ -178,25 +185,64 @@ def test_one_sample_per_call(gpu_ctx, dev, pair):
 
 
 # ---- 3. layout independence ------------------------------------------------------------------------------------------------------
+def layout_splits(pair):
+    """the splits and the four layouts of the test below (tests/test_kernel_paths_host.py walks the same ones)"""
+    _, U, D, P = table(pair)
+    Ci = ceil_div(CHUNK * D, U)
+    row_splits = [[Ci + 1, 3, Ci // 2 + 13], [5, Ci - 4, 0], [1, 0, 699]]
+    stride = (Ci + 1 + 63) // 64 * 64
+    need, room = ceil_div(stride * U, D), tail_room(pair)
+    return row_splits, [dict(stride=stride),
+                        dict(stride=stride, in_offset=1, out_offset=1),
+                        dict(stride=stride + 1, out_stride=(ceil_div((stride + 1) * U, D) + 7) | 1, tail_stride=room | 1),
+                        dict(stride=stride, out_stride=need, tail_stride=room)]
+
+
 @pytest.mark.parametrize("pair", LAYOUT_PAIRS)
 def test_every_layout_gives_the_same_bits(gpu_ctx, dev, pair):
     """aligned bases and strides that are multiples of 4 (16-byte loads and stores); both bases one float off; odd strides
     with an out_stride above the need (the 4-byte variant)"""
     rng = np.random.default_rng(70 + pair[0] % 97 + pair[1] % 89)
-    _, U, D, P = table(pair)
-    Ci = ceil_div(CHUNK * D, U)
-    row_splits = [[Ci + 1, 3, Ci // 2 + 13], [5, Ci - 4, 0], [1, 0, 699]]
+    row_splits, layouts = layout_splits(pair)
     rows = [noise(sum(s), rng, np.cumsum(s)) for s in row_splits]
-    stride = (Ci + 1 + 63) // 64 * 64
-    need, room = ceil_div(stride * U, D), tail_room(pair)
-    a = stream_rows(gpu_ctx, dev, pair, rows, row_splits, stride=stride)
-    b = stream_rows(gpu_ctx, dev, pair, rows, row_splits, stride=stride, in_offset=1, out_offset=1)
-    c = stream_rows(gpu_ctx, dev, pair, rows, row_splits, stride=stride + 1, out_stride=(ceil_div((stride + 1) * U, D) + 7) | 1,
-                    tail_stride=room | 1)
-    d = stream_rows(gpu_ctx, dev, pair, rows, row_splits, stride=stride, out_stride=need, tail_stride=room)
+    a, b, c, d = [stream_rows(gpu_ctx, dev, pair, rows, row_splits, **layout) for layout in layouts]
     whole_rows(a, pair, rows)
     for other in (b, c, d):
         assert all(np.array_equal(bits(p), bits(q)) for p, q in zip(a, other))
+
+
+# ---- 3b. every count of passes ---------------------------------------------------------------------------------------------------
+PASS = 256      # the outputs of one pass of a chunk (resample_kernels.hip's RS_THREADS; tests/test_kernel_paths_host.py)
+
+
+def pass_calls(pair):
+    """calls of 300, 600 and 900 outputs: a chunk of two, of three and of four passes (a chunk of one is everywhere), which the
+    splits above reach only where their seeds happen to -> (the samples of each call, the outputs of each).  Where a sample
+    brings two outputs a call may write one more than asked."""
+    _, U, D, P = table(pair)
+    split, counts, N = [], [], 0
+    for target in (300, 600, 900):
+        n = 0
+        while stream_len(N, n, U, D, P) < target:
+            n += 1
+        split.append(n)
+        counts.append(stream_len(N, n, U, D, P))
+        N += n
+    assert all(t <= c <= t + 1 for t, c in zip((300, 600, 900), counts)) and [ceil_div(c, PASS) for c in counts] == [2, 3, 4]
+    return split, counts
+
+
+@pytest.mark.parametrize("aligned", [True, False], ids=["aligned", "offset"])
+@pytest.mark.parametrize("pair", LAYOUT_PAIRS)
+def test_calls_of_two_three_and_four_passes(gpu_ctx, dev, pair, aligned):
+    """the five ways to the stretch and the coefficients, with 16-byte and with 4-byte loads and stores: all ten variants of
+    the kernel, each under rs_outputs<..., 2>, <..., 3> and <..., 4>"""
+    split, _ = pass_calls(pair)
+    rng = np.random.default_rng(170 + pair[0] % 97 + pair[1] % 89)
+    rows = [noise(sum(split), rng, np.cumsum(split))]
+    layout = {} if aligned else dict(in_offset=1, out_offset=1)
+    joined = stream_rows(gpu_ctx, dev, pair, rows, [split], **layout)
+    whole_rows(joined, pair, rows)
 
 
 # ---- 4. refusals and state -------------------------------------------------------------------------------------------------------
