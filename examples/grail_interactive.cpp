@@ -13,7 +13,7 @@
 // Without a sound card time is the audio itself: a line "@1.5 text" arrives once 1.5 s of audio have been rendered, a line
 // without a stamp arrives at once.  After the last line has been spoken the session runs `tail` seconds longer (the
 // reference never ends) and the source is closed.
-//   usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [chunk_samples] [tail_seconds]
+//   usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [--meter] [chunk_samples] [tail_seconds]
 //          < script > out.f32
 // --band LO HI: every pulled chunk goes through a filter stream (the Kaiser-windowed band-pass LO .. HI Hz of
 // grail_fir_design, K taps, 255 unless --taps says otherwise, at its zero-delay origin) before it leaves the device, and when
@@ -27,12 +27,18 @@
 // before it leaves the device.  When the chain has ended the tails are flushed in chain order: the filter's tail is fed to
 // the limiter and what that gives to the resampler, then the limiter's own tail likewise, then the resampler's.  The output is what grail_resample_async gives for the whole (filtered)
 // session.
+// --meter: everything that is written goes through a meter stream (grail_meter_stream_*) at the rate it is written at, chunk by
+// chunk and the tails too; after the last of them the row is finished and stderr gets the report of grail_dialogue --report
+// (integrated loudness, range, max momentary, max short-term, true peak), then the gated mean square and the true peak as
+// their own bits (%a): what grail_loudness_async and grail_true_peak_async give for the finished track.
 // Every phoneme fed is reported on stderr ("fed <phoneme> at <sample>"), so that a test can render the same list with
 // the oracle in one piece and compare bit for bit.
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <deque>
 #include <iostream>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -67,6 +73,85 @@ std::vector<grail::PhonemeElem> speak(const grail::Voice &voice, const std::stri
     return out;
 }
 
+// --meter: a meter stream of one row on what leaves the chain, through the C ABI (grail_meter_stream_*).  The ledger holds an
+// hour of hops; a session that outgrows it is refused from there on, and the report says so.
+class Meter {
+public:
+    Meter(grail_ctx *ctx, uint32_t rate) : ctx_(ctx), rate_(rate)
+    {
+        grail::check(grail_meter_stream_open(ctx, 1, rate, nullptr, 36000, &ms_));
+    }
+    Meter(const Meter &) = delete;
+    Meter &operator=(const Meter &) = delete;
+    ~Meter()
+    {
+        grail_meter_stream_close(ctx_, ms_);
+        for (void *p : {in_, len_, res_}) grail_device_free(ctx_, p);
+    }
+    // the samples just written go back to the device and through the meter where they lie
+    void feed(const std::vector<float> &part)
+    {
+        if (part.empty()) return;
+        if (part.size() > cap_) {
+            grail::check(grail_sync(ctx_));
+            grail_device_free(ctx_, in_);
+            in_ = nullptr;
+            cap_ = (part.size() + 63) / 64 * 64;
+            grail::check(grail_device_alloc(ctx_, cap_ * sizeof(float), &in_));
+        }
+        if (!len_) grail::check(grail_device_alloc(ctx_, sizeof(uint32_t), &len_));
+        if (!res_) grail::check(grail_device_alloc(ctx_, 5 * sizeof(double), &res_));
+        const uint32_t n = (uint32_t)part.size();
+        grail::check(grail_memcpy_h2d(ctx_, in_, part.data(), n * sizeof(float)));
+        grail::check(grail_memcpy_h2d(ctx_, len_, &n, sizeof n));
+        uint32_t n_hops = 0;
+        grail::check(grail_meter_stream_next_async(ctx_, ms_, (const float *)in_, cap_, (const uint32_t *)len_, nullptr, 0,
+                                                   (uint32_t *)res_, nullptr, nullptr));
+        grail::check(grail_memcpy_d2h(ctx_, &n_hops, res_, sizeof n_hops));
+        full_ = full_ || n_hops == GRAIL_LIMIT_REFUSED;
+    }
+    // the row ends; I, max M, max S, LRA and TP as grail_dialogue --report prints them, then the two numbers' own bits
+    void report(uint32_t track)
+    {
+        if (!res_) grail::check(grail_device_alloc(ctx_, 5 * sizeof(double), &res_));
+        double *r = (double *)res_;
+        grail::check(grail_meter_stream_finish_async(ctx_, ms_, nullptr, nullptr));
+        grail::check(grail_meter_stream_read_async(ctx_, ms_, r, r + 1, r + 2, r + 3, (uint64_t *)(r + 4)));
+        double got[4];
+        uint64_t hops = 0;
+        grail::check(grail_memcpy_d2h(ctx_, got, r, sizeof got));
+        grail::check(grail_memcpy_d2h(ctx_, &hops, r + 4, sizeof hops));
+        const double *ledger = nullptr;
+        uint64_t stride = 0;
+        grail::check(grail_meter_stream_ledger(ctx_, ms_, &ledger, &stride));
+        std::vector<double> h((size_t)hops);
+        if (hops) grail::check(grail_memcpy_d2h(ctx_, h.data(), ledger, h.size() * sizeof(double)));
+        const uint32_t H = rate_ / 10u;
+        const double short_max = grail_loudness_lufs(grail_loudness_window_max(h.data(), (uint32_t)hops, H, 30));
+        const auto field = [](bool has, double value, const char *unit) {
+            char text[48];
+            if (has && std::isfinite(value)) std::snprintf(text, sizeof text, "%.2f %s", value, unit);
+            else std::snprintf(text, sizeof text, "-");
+            return std::string(text);
+        };
+        std::fprintf(stderr, "Track %u: integrated %s, range %s, max momentary %s, max short-term %s, true peak %s\n", track,
+                     field(got[0] > 0.0, grail_loudness_lufs(got[0]), "LUFS").c_str(),
+                     field(hops >= 30 && short_max > -70.0, grail_loudness_range(h.data(), (uint32_t)hops, H), "LU").c_str(),
+                     field(hops >= 4, grail_loudness_lufs(grail_loudness_window_max(h.data(), (uint32_t)hops, H, 4)), "LUFS").c_str(),
+                     field(hops >= 30, short_max, "LUFS").c_str(), field(got[3] > 0.0, grail_true_peak_db(got[3]), "dBTP").c_str());
+        std::fprintf(stderr, "Metered at %u Hz: %llu hops, gated mean square %a, true peak %a%s\n", rate_, (unsigned long long)hops,
+                     got[0], got[3], full_ ? " (the ledger was full: the end of the session is not in these numbers)" : "");
+    }
+
+private:
+    grail_ctx *ctx_;
+    uint32_t rate_;
+    grail_meter_stream *ms_ = nullptr;
+    void *in_ = nullptr, *len_ = nullptr, *res_ = nullptr;
+    size_t cap_ = 0;
+    bool full_ = false;
+};
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -75,7 +160,7 @@ int main(int argc, char **argv)
     double lo = -1.0, hi = -1.0;
     long taps = 0, rate = 0, lookahead = -1;
     double ceiling_db = 0.0;
-    bool usage = false, limit = false;
+    bool usage = false, limit = false, meter = false;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         char *end = nullptr;
@@ -105,6 +190,8 @@ int main(int argc, char **argv)
             usage = usage || end == argv[i + 1] || *end || rate < 1 || rate > 0xFFFFFFFFl ||
                     grail_resample_ratio((uint32_t)grail::voices::generic().sample_rate, (uint32_t)rate, nullptr, nullptr, nullptr) != GRAIL_OK;
             i += 1;
+        } else if (a == "--meter") {
+            meter = true;
         } else if (a.rfind("--", 0) == 0) {
             usage = true;
         } else {
@@ -117,7 +204,7 @@ int main(int argc, char **argv)
     // (a chunk of 0 samples — or text strtoul makes 0 of — would never feed the stream)
     if (usage || plain.size() > 2 || chunk == 0 || !(tail >= 0.0) || (taps && !band) || (band && !(lo >= 0.0 && lo < hi)) ||
         (lookahead >= 0 && !limit)) {
-        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] "
+        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [--meter] "
                              "[samples per pull >= 1 (default 441)] [seconds of tail >= 0 (default 1)]\n");
         return 2;
     }
@@ -135,6 +222,9 @@ int main(int argc, char **argv)
         if (limit) limiters.push_back(gpu.limit_stream(1, grail_limit_ceiling((float)ceiling_db), lookahead < 0 ? 8u : (uint32_t)lookahead));
         std::vector<grail::ResampleStream> resamplers;
         if (rate) resamplers.push_back(gpu.resample_stream((uint32_t)voice.sample_rate, (uint32_t)rate, 1));
+        // (declared after the other streams: closed before them)
+        std::unique_ptr<Meter> metered;
+        if (meter) metered.reset(new Meter(gpu.ctx(), rate ? (uint32_t)rate : (uint32_t)voice.sample_rate));
         std::vector<Line> script;
         std::string raw;
         while (std::getline(std::cin, raw)) {                        // interactive.rs:77-81
@@ -174,6 +264,7 @@ int main(int argc, char **argv)
                 rendered = (uint32_t)part.size();
             }
             std::fwrite(part.data(), sizeof(float), part.size(), stdout);
+            if (meter) metered->feed(part);
             total += rendered;
             written += part.size();
             if (rendered == chunk) continue;
@@ -207,6 +298,7 @@ int main(int argc, char **argv)
             if (limit) rest = limiters[0].next({rest}).at(0);         // ... into the next stages of the chain
             if (rate) rest = resamplers[0].next({rest}).at(0);
             std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
+            if (meter) metered->feed(rest);
             written += rest.size();
             if (rate || limit)
                 std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps)\n", lo, hi, (double)voice.sample_rate, filters[0].tail() + 1);
@@ -218,6 +310,7 @@ int main(int argc, char **argv)
             std::vector<float> rest = limiters[0].finish().at(0);
             if (rate) rest = resamplers[0].next({rest}).at(0);
             std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
+            if (meter) metered->feed(rest);
             written += rest.size();
             if (rate)
                 std::fprintf(stderr, "Limited to %g dBTP, %u samples late\n", ceiling_db, limiters[0].delay());
@@ -228,9 +321,11 @@ int main(int argc, char **argv)
         if (rate) {                                                   // ... and the resampler's own tail
             const std::vector<float> rest = resamplers[0].finish().at(0);
             std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
+            if (meter) metered->feed(rest);
             written += rest.size();
             std::fprintf(stderr, "Resampled %g -> %ld Hz: %zu samples written\n", (double)voice.sample_rate, rate, written);
         }
+        if (meter) metered->report(1);
         std::fprintf(stderr, "session: %zu samples (%.2f s), %zu phonemes fed, %zu lines, buffers of %u\n", total,
                      total / voice.sample_rate, fed, script.size(), chunk);
     } catch (const grail::Error &e) {

@@ -37,6 +37,7 @@
 #include "fir_plan.h"
 #include "kernels.h"
 #include "limit_plan.h"
+#include "meter_plan.h"
 #include "resample_plan.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)
@@ -384,6 +385,16 @@ struct grail_limit_stream : ChunkedStream {
     uint32_t group = 1;
     float ceiling = 0.0f;
     uint32_t ell = 0;                 // lookahead_log2; ring_cap is limit_stream_ring_capacity(ell)
+};
+
+// A stream of rows metered call by call (meter_stream_kernels.hip), all at one rate with one set of K-weighting coefficients:
+// METER_STREAM_STATE_WORDS state words a row (samples fed, s1 .. s4, acc, the running true peak, the hops completed), a ring of
+// METER_STREAM_RING samples a row, and the ledger of the rows' hop sums, which the read kernel gates.
+struct grail_meter_stream : ChunkedStream {
+    uint32_t sample_rate = 0, hop = 0;      // hop = sample_rate / 10
+    uint64_t max_hops = 0;                  // the ledger's capacity a row, fixed at open
+    double coef[10] = {};
+    grail::host::DeviceBuffer<double> d_ledger;     // [n_rows][max_hops]
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks

@@ -310,4 +310,30 @@ hipError_t launch_limit_stream_advance(const float *in, uint64_t in_stride, cons
                                        uint32_t *out_len, float *min_gain, uint32_t *n_limited, uint32_t *nonfinite,
                                        hipStream_t stream);
 
+// meter streams (meter_stream_kernels.hip): rows metered call by call.  state: DEVICE [n_rows][METER_STREAM_STATE_WORDS] (word 0:
+// samples fed, bit 63: ended; 1 .. 5: s1 .. s4 and acc as their bits; 6: the running true peak; 7: the hops completed), ring:
+// DEVICE [n_rows][METER_STREAM_RING], ledger: DEVICE [n_rows][max_hops].  A call is three launches in this order: the hops (one
+// lane per row; a feeding call only), the call's true peak (one wave per row and chunk of METER_STREAM_CHUNK output times,
+// grid_chunks of them a row, the chunk's maximum and non-finite count to cmax / cbad [row * grid_chunks + c]), the advance (one
+// wave per row: the call's results, any of which may be NULL, the ring, N, the running peak, the hop count).  The first two
+// read N and the hop count, only the third writes them.  coef: HOST [10].  A row that has ended and is fed, or that the call
+// would carry past max_hops: 0xFFFFFFFF, NaN, 0, nothing else.
+constexpr uint32_t METER_STREAM_STATE_WORDS = 8;
+constexpr uint32_t METER_STREAM_RING = 16;
+constexpr uint32_t METER_STREAM_CHUNK = 4096;
+hipError_t launch_meter_stream_hops(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
+                                    const double *coef, uint64_t *state, double *ledger, uint64_t max_hops, double *hops_out,
+                                    uint64_t hops_stride, hipStream_t stream);
+hipError_t launch_meter_stream_peak(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
+                                    const uint64_t *state, uint64_t max_hops, const float *ring, const uint8_t *mark, bool finishing,
+                                    uint32_t grid_chunks, double *cmax, uint32_t *cbad, hipStream_t stream);
+hipError_t launch_meter_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
+                                       uint64_t *state, uint64_t max_hops, float *ring, const uint8_t *mark, bool finishing,
+                                       const double *cmax, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *n_hops,
+                                       double *true_peak, uint32_t *nonfinite, hipStream_t stream);
+// ... and what a meter shows of every row now, one lane per row (outputs may be NULL); changes nothing
+hipError_t launch_meter_stream_read(const uint64_t *state, uint32_t n_rows, uint32_t hop, const double *ledger, uint64_t max_hops,
+                                    double *integrated, double *momentary, double *short_term, double *true_peak, uint64_t *hops,
+                                    hipStream_t stream);
+
 }  // namespace grail

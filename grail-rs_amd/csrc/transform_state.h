@@ -54,6 +54,9 @@ struct TransformState : CtxPart {
     Owned<grail_filter_stream> fir_streams; // ... and, after them (they die first), the filter streams open on them
     Owned<grail_resample_stream> resample_streams;  // the resample streams open (each with its own copy of its pair's table)
     Owned<grail_limit_stream> limit_streams;        // the limit streams open
+    DeviceBuffer<double> d_mpeak;           // meter stream chunks (4096 output times each): the largest |y|
+    DeviceBuffer<uint32_t> d_mbad;          // ... and the non-finite counts
+    Owned<grail_meter_stream> meter_streams;        // the meter streams open
 };
 
 // what the context has, made by nobody: NULL before the first call that needed it

@@ -1,8 +1,9 @@
 // transform_streams.cpp — finished rows filtered, resampled and limited chunk by chunk: grail_filter_stream_open / _next_async /
 // _finish_async / _close (fir_kernels.hip), grail_resample_stream_* (resample_kernels.hip, §4.16) and
-// grail_limit_stream_* (limiter_kernels.hip, §4.17).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp,
-// limit_plan.cpp; their common end row_checks.h), what it keeps beside the rings, and its two launches.  What the three do alike
-// stands once, first: telling a stream of the context's, its device state, a finishing call's marks, its close.
+// grail_limit_stream_* (limiter_kernels.hip, §4.17), and metered chunk by chunk: grail_meter_stream_* (meter_stream_kernels.hip,
+// §4.18).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp, limit_plan.cpp, meter_plan.cpp; their common
+// end row_checks.h), what it keeps beside the rings, and its launches (two; the meter's three).  What the kinds do alike stands
+// once, first: telling a stream of the context's, its device state, a finishing call's marks, its close.
 #include "transform_state.h"
 
 using namespace grail;
@@ -133,6 +134,34 @@ int limit_stream_call(grail_ctx *ctx, grail_limit_stream *ls, const float *in_de
                                                      (uint32_t)chunks, out_len_dev, min_gain_dev, n_limited_dev, nonfinite_dev,
                                                      ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "limit stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+// A meter stream's call is three kernels: the hops (a feeding call with samples only), the call's true peak, the state.
+int meter_stream_call(grail_ctx *ctx, grail_meter_stream *ms, const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev,
+                      const uint8_t *mark_dev, bool finishing, uint64_t chunks, double *hop_sumsq_dev, uint64_t hops_stride,
+                      uint32_t *n_hops_dev, double *true_peak_dev, uint32_t *nonfinite_dev)
+{
+    TransformState *st;
+    int rc = state(ctx, &st);
+    if (rc) return rc;
+    if (chunks) {
+        if ((rc = st->d_mpeak.reserve(ctx->stream, (size_t)ms->n_rows * (size_t)chunks))) return rc;
+        if ((rc = st->d_mbad.reserve(ctx->stream, (size_t)ms->n_rows * (size_t)chunks))) return rc;
+        if (!finishing) {
+            const hipError_t e = launch_meter_stream_hops(in_dev, in_stride, in_len_dev, ms->n_rows, ms->hop, ms->coef, ms->d_state.get(),
+                                                          ms->d_ledger.get(), ms->max_hops, hop_sumsq_dev, hops_stride, ctx->stream);
+            if (e != hipSuccess) return hip_fail(e, "meter stream hops kernel launch");
+        }
+        const hipError_t e = launch_meter_stream_peak(in_dev, in_stride, in_len_dev, ms->n_rows, ms->hop, ms->d_state.get(), ms->max_hops,
+                                                      ms->d_ring.get(), mark_dev, finishing, (uint32_t)chunks, st->d_mpeak.get(),
+                                                      st->d_mbad.get(), ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "meter stream peak kernel launch");
+    }
+    const hipError_t e = launch_meter_stream_advance(in_dev, in_stride, in_len_dev, ms->n_rows, ms->hop, ms->d_state.get(), ms->max_hops,
+                                                     ms->d_ring.get(), mark_dev, finishing, st->d_mpeak.get(), st->d_mbad.get(),
+                                                     (uint32_t)chunks, n_hops_dev, true_peak_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "meter stream advance kernel launch");
     return GRAIL_OK;
 }
 
@@ -322,6 +351,92 @@ int grail_limit_stream_finish_async(grail_ctx *ctx, grail_limit_stream *ls, cons
     if ((rc = marks(ctx, *ls, which, &mark_dev))) return rc;
     return limit_stream_call(ctx, ls, nullptr, 0, nullptr, mark_dev, true, chunks, out_dev, out_stride, out_len_dev, min_gain_dev,
                              n_limited_dev, nullptr);
+}
+
+int grail_meter_stream_open(grail_ctx *ctx, uint32_t n_rows, uint32_t sample_rate, const double *coef, uint64_t max_hops,
+                            grail_meter_stream **out)
+{
+    // (as the limit stream's: what is wrong with the numbers first)
+    if (const char *why = meter_stream_open_error(n_rows, sample_rate, max_hops)) return refuse("grail_meter_stream_open", why);
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_meter_stream_open: NULL argument");
+    int rc = bind(ctx);
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_meter_stream> ms(new (std::nothrow) grail_meter_stream());
+    if (!ms) return fail(GRAIL_ERR_OUT_OF_MEMORY, "meter stream");
+    ms->n_rows = ms->units = n_rows;
+    ms->sample_rate = sample_rate, ms->hop = meter_stream_hop(sample_rate), ms->max_hops = max_hops;
+    ms->ring_cap = METER_STREAM_RING;
+    if (coef)
+        std::copy(coef, coef + 10, ms->coef);
+    else if (grail_kweighting(sample_rate, ms->coef))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_meter_stream_open: no K-weighting for this rate");
+    HIP_TRY(ms->d_ledger.alloc((size_t)n_rows * (size_t)max_hops));
+    HIP_TRY(hipMemsetAsync(ms->d_ledger.get(), 0, (size_t)n_rows * (size_t)max_hops * sizeof(double), ctx->stream));
+    if ((rc = alloc_state(ctx, *ms, METER_STREAM_STATE_WORDS))) return rc;       // (no sample fed, every double +0.0)
+    *out = st->meter_streams.add(std::move(ms));
+    return GRAIL_OK;
+}
+
+int grail_meter_stream_close(grail_ctx *ctx, grail_meter_stream *ms)
+{
+    return stream_close(ctx, &TransformState::meter_streams, ms, "grail_meter_stream_close", "meter");
+}
+
+int grail_meter_stream_next_async(grail_ctx *ctx, grail_meter_stream *ms, const float *in_dev, uint64_t in_stride,
+                                  const uint32_t *in_len_dev, double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *n_hops_dev,
+                                  double *true_peak_dev, uint32_t *nonfinite_dev)
+{
+    const char *who = "grail_meter_stream_next_async";
+    int rc = known(ctx, &TransformState::meter_streams, ms, who, "meter");
+    if (rc) return rc;
+    // (without a context: the checks of one row at the smallest hop)
+    uint64_t chunks = 0;
+    if (const char *why = meter_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? ms->n_rows : 1u, hop_sumsq_dev, hops_stride,
+                                                  ctx ? ms->hop : GRAIL_LOUDNESS_RATE_MIN / 10u, &chunks))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    return meter_stream_call(ctx, ms, in_dev, in_stride, in_len_dev, nullptr, false, chunks, hop_sumsq_dev, hops_stride, n_hops_dev,
+                             true_peak_dev, nonfinite_dev);
+}
+
+int grail_meter_stream_read_async(grail_ctx *ctx, grail_meter_stream *ms, double *integrated_ms_dev, double *momentary_ms_dev,
+                                  double *short_term_ms_dev, double *true_peak_dev, uint64_t *hops_dev)
+{
+    const char *who = "grail_meter_stream_read_async";
+    int rc = known(ctx, &TransformState::meter_streams, ms, who, "meter");
+    if (rc) return rc;
+    if ((rc = bind_device(ctx, who))) return rc;
+    const hipError_t e = launch_meter_stream_read(ms->d_state.get(), ms->n_rows, ms->hop, ms->d_ledger.get(), ms->max_hops,
+                                                  integrated_ms_dev, momentary_ms_dev, short_term_ms_dev, true_peak_dev, hops_dev,
+                                                  ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "meter stream read kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_meter_stream_ledger(grail_ctx *ctx, grail_meter_stream *ms, const double **hops_dev, uint64_t *stride)
+{
+    const char *who = "grail_meter_stream_ledger";
+    int rc = known(ctx, &TransformState::meter_streams, ms, who, "meter");
+    if (rc) return rc;
+    if (!hops_dev || !stride) return refuse(who, "NULL argument");
+    if ((rc = bind_device(ctx, who))) return rc;
+    *hops_dev = ms->d_ledger.get();
+    *stride = ms->max_hops;
+    return GRAIL_OK;
+}
+
+int grail_meter_stream_finish_async(grail_ctx *ctx, grail_meter_stream *ms, const uint8_t *which, double *true_peak_dev)
+{
+    const char *who = "grail_meter_stream_finish_async";
+    int rc = known(ctx, &TransformState::meter_streams, ms, who, "meter");
+    if (rc) return rc;
+    if ((rc = bind_device(ctx, who))) return rc;
+    const uint8_t *mark_dev;
+    if ((rc = marks(ctx, *ms, which, &mark_dev))) return rc;
+    // (one chunk a row: the eleven outputs after its last sample)
+    return meter_stream_call(ctx, ms, nullptr, 0, nullptr, mark_dev, true, 1, nullptr, 0, nullptr, true_peak_dev, nullptr);
 }
 
 }  // extern "C"

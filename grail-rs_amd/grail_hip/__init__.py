@@ -88,6 +88,8 @@ EXPORTS = [
     "grail_resample_stream_finish_async", "grail_resample_stream_close",
     "grail_limit_stream_len", "grail_limit_stream_open", "grail_limit_stream_next_async", "grail_limit_stream_finish_async",
     "grail_limit_stream_close",
+    "grail_meter_stream_hops", "grail_meter_stream_open", "grail_meter_stream_next_async", "grail_meter_stream_read_async",
+    "grail_meter_stream_ledger", "grail_meter_stream_finish_async", "grail_meter_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -412,6 +414,13 @@ def load():
     L.grail_limit_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp, vp]
     L.grail_limit_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp]
     L.grail_limit_stream_close.argtypes = [vp, vp]
+    L.grail_meter_stream_hops.argtypes = [u64, u64, C.c_uint32, vp]
+    L.grail_meter_stream_open.argtypes = [vp, C.c_uint32, C.c_uint32, vp, u64, vp]
+    L.grail_meter_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, vp]
+    L.grail_meter_stream_read_async.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.grail_meter_stream_ledger.argtypes = [vp, vp, vp, vp]
+    L.grail_meter_stream_finish_async.argtypes = [vp, vp, vp, vp]
+    L.grail_meter_stream_close.argtypes = [vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -1025,6 +1034,103 @@ class LimitStream:
             self.handle = None
 
 
+def meter_stream_hops(fed_before, n, sample_rate):
+    """grail_meter_stream_hops (pure host): the hops a `next` call on a meter stream completes for a row that was fed fed_before
+    samples before it and is fed n: (fed_before + n) // H - fed_before // H, H = sample_rate // 10."""
+    out = C.c_uint64()
+    _check(load().grail_meter_stream_hops(fed_before, n, sample_rate, C.addressof(out)))
+    return out.value
+
+
+class MeterStream:
+    """A meter stream of a Context (Context.meter_stream_open), in the style of LimitStream: the handle with what the waited-for
+    forms need to size their results, one per row."""
+
+    def __init__(self, ctx, handle, n_rows, sample_rate, max_hops):
+        self.ctx, self.handle, self.n_rows, self.sample_rate, self.max_hops = ctx, handle, n_rows, sample_rate, max_hops
+        self.hop = sample_rate // 10
+
+    def hops_stride(self, in_stride):
+        """the least hops_stride of a call that feeds rows of in_stride: the most hops a row can complete in it"""
+        return (in_stride + self.hop - 1) // self.hop
+
+    def next_async(self, in_dev, in_stride, in_len_dev, hop_sumsq_dev=None, hops_stride=0, n_hops_dev=None, true_peak_dev=None,
+                   nonfinite_dev=None):
+        """grail_meter_stream_next_async: every row is fed its next min(in_len_dev[u], in_stride) samples; the hops the call
+        completes go to hop_sumsq_dev + u * hops_stride (float64).  Results are DEVICE arrays [n_rows] (uint32, float64,
+        uint32; any may be None), queued on the context's stream; in_dev may be reused by what is queued behind the call."""
+        _check(load().grail_meter_stream_next_async(self.ctx.handle, self.handle, in_dev, in_stride, in_len_dev, hop_sumsq_dev,
+                                                    hops_stride, n_hops_dev, true_peak_dev, nonfinite_dev))
+
+    def _waited(self, types, call):
+        """_waited for results of 4 or 8 bytes each"""
+        res = [np.zeros(self.n_rows, dtype=t) for t in types]
+        d = [self.ctx.device_alloc(r.nbytes) for r in res]
+        try:
+            call(*d)
+            for dst, src in zip(res, d):
+                self.ctx.d2h(dst, src, dst.nbytes)
+        finally:
+            self.ctx.sync()
+            for p in d:
+                self.ctx.device_free(p)
+        return tuple(res)
+
+    def next(self, in_dev, in_stride, in_len_dev, hop_sumsq_dev=None, hops_stride=0):
+        """next_async, waited for, the results copied back: (n_hops uint32, true_peak float64, nonfinite uint32), one per
+        row; a refused row reads (LIMIT_REFUSED, NaN, 0)."""
+        return self._waited((np.uint32, np.float64, np.uint32),
+                            lambda *d: self.next_async(in_dev, in_stride, in_len_dev, hop_sumsq_dev, hops_stride, *d))
+
+    def read_async(self, integrated_ms_dev=None, momentary_ms_dev=None, short_term_ms_dev=None, true_peak_dev=None, hops_dev=None):
+        """grail_meter_stream_read_async: what the meter shows of every row now, DEVICE arrays [n_rows] of float64 (hops_dev:
+        uint64), any may be None; changes no state."""
+        _check(load().grail_meter_stream_read_async(self.ctx.handle, self.handle, integrated_ms_dev, momentary_ms_dev,
+                                                    short_term_ms_dev, true_peak_dev, hops_dev))
+
+    def read(self):
+        """read_async, waited for: (integrated_ms, momentary_ms, short_term_ms, true_peak float64, hops uint64), one per row."""
+        return self._waited((np.float64, np.float64, np.float64, np.float64, np.uint64), self.read_async)
+
+    def ledger(self):
+        """grail_meter_stream_ledger: (the ledger's device address, its stride in float64); row u's hop sums lie at
+        address + 8 * (u * stride + h), h below the row's hops."""
+        base, stride = C.c_void_p(), C.c_uint64()
+        _check(load().grail_meter_stream_ledger(self.ctx.handle, self.handle, C.addressof(base), C.addressof(stride)))
+        return base, stride.value
+
+    def ledger_rows(self):
+        """the rows' hop sums so far, copied from the ledger: a list of float64 arrays, one per row"""
+        hops = self.read()[4]
+        base, stride = self.ledger()
+        rows = []
+        for u, h in enumerate(hops):
+            row = np.zeros(int(h), dtype=np.float64)
+            if h:
+                self.ctx.d2h(row, C.c_void_p(base.value + 8 * u * stride), row.nbytes)
+            rows.append(row)
+        return rows
+
+    def finish_async(self, which=None, true_peak_dev=None):
+        """grail_meter_stream_finish_async: the rows marked in which (a host sequence, non-zero = marked; None: every row) that
+        have not ended ring out over the eleven outputs after their last sample and end."""
+        marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
+        assert marks is None or len(marks) == self.n_rows
+        _check(load().grail_meter_stream_finish_async(self.ctx.handle, self.handle, None if marks is None else marks.ctypes.data,
+                                                      true_peak_dev))
+
+    def finish(self, which=None):
+        """finish_async, waited for: the largest of each row's eleven last outputs, float64; +0.0 for rows not marked or ended
+        before."""
+        return self._waited((np.float64,), lambda d: self.finish_async(which, d))[0]
+
+    def close(self):
+        """grail_meter_stream_close: waits for the context's stream, then releases the stream."""
+        if self.handle is not None:
+            _check(load().grail_meter_stream_close(self.ctx.handle, self.handle))
+            self.handle = None
+
+
 class Context:
     """grail_ctx: one per (process, GPU)."""
 
@@ -1475,6 +1581,16 @@ class Context:
         out = C.c_void_p(None)
         _check(load().grail_limit_stream_open(self.handle, n_rows, group, float(np.float32(ceiling)), lookahead_log2, C.addressof(out)))
         return LimitStream(self, out, n_rows, group, lookahead_log2)
+
+    def meter_stream_open(self, n_rows, sample_rate, max_hops, coef=None):
+        """grail_meter_stream_open: a stream of n_rows rows metered call by call at sample_rate (coef: float64 [10], None:
+        kweighting(sample_rate)), each row's ledger holding max_hops hops.  Returns a MeterStream; streams still open go
+        with the context."""
+        out = C.c_void_p()
+        c = None if coef is None else np.ascontiguousarray(coef, dtype=np.float64)
+        assert c is None or c.shape == (10,)
+        _check(load().grail_meter_stream_open(self.handle, n_rows, int(sample_rate), _ptr(c), int(max_hops), C.addressof(out)))
+        return MeterStream(self, out, n_rows, int(sample_rate), int(max_hops))
 
     def digest(self, in_dev, in_stride, len_dev, n_utt):
         """(bit-pattern sums mod 2^64, max finite |x|, non-finite counts) per row, computed on the device (every length

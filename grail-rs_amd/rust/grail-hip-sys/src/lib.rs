@@ -138,6 +138,10 @@ pub struct grail_resample_stream {
 pub struct grail_limit_stream {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct grail_meter_stream {
+    _private: [u8; 0],
+}
 
 /// The most taps of one filter and the most filters of one set (`grail_fir_create`).
 pub const GRAIL_FIR_TAPS_MAX: u32 = 4096;
@@ -341,6 +345,19 @@ extern "C" {
     pub fn grail_limit_stream_finish_async(ctx: *mut grail_ctx, ls: *mut grail_limit_stream, which: *const u8,
         out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32, min_gain_dev: *mut f32, n_limited_dev: *mut u32) -> c_int;
     pub fn grail_limit_stream_close(ctx: *mut grail_ctx, ls: *mut grail_limit_stream) -> c_int;
+    pub fn grail_meter_stream_hops(fed_before: u64, n: u64, sample_rate: u32, n_hops: *mut u64) -> c_int;
+    pub fn grail_meter_stream_open(ctx: *mut grail_ctx, n_rows: u32, sample_rate: u32, coef: *const f64, max_hops: u64,
+        out: *mut *mut grail_meter_stream) -> c_int;
+    pub fn grail_meter_stream_next_async(ctx: *mut grail_ctx, ms: *mut grail_meter_stream, in_dev: *const f32, in_stride: u64,
+        in_len_dev: *const u32, hop_sumsq_dev: *mut f64, hops_stride: u64, n_hops_dev: *mut u32, true_peak_dev: *mut f64,
+        nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_meter_stream_read_async(ctx: *mut grail_ctx, ms: *mut grail_meter_stream, integrated_ms_dev: *mut f64,
+        momentary_ms_dev: *mut f64, short_term_ms_dev: *mut f64, true_peak_dev: *mut f64, hops_dev: *mut u64) -> c_int;
+    pub fn grail_meter_stream_ledger(ctx: *mut grail_ctx, ms: *mut grail_meter_stream, hops_dev: *mut *const f64,
+        stride: *mut u64) -> c_int;
+    pub fn grail_meter_stream_finish_async(ctx: *mut grail_ctx, ms: *mut grail_meter_stream, which: *const u8,
+        true_peak_dev: *mut f64) -> c_int;
+    pub fn grail_meter_stream_close(ctx: *mut grail_ctx, ms: *mut grail_meter_stream) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

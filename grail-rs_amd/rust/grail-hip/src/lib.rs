@@ -707,6 +707,16 @@ impl Gpu {
         Ok(LimitStream { gpu: self, ls, n_rows, group, delay: (1u32 << lookahead_log2) + 10 })
     }
 
+    /// A stream of `n_rows` rows metered chunk by chunk at `sample_rate` with grail_kweighting's coefficients, each row's
+    /// ledger holding `max_hops` hops of 100 ms (`grail_meter_stream_open`; the contract is the header's section "levels,
+    /// continued: the meters on streams").  The chunks' hop sums put end to end are the bits [`Gpu::loudness`]'s kernels give
+    /// for the whole rows, the largest of the chunks' true peaks is [`Gpu::true_peak`]'s.  Closed when dropped.
+    pub fn meter_stream(&self, n_rows: u32, sample_rate: u32, max_hops: u64) -> Result<MeterStream<'_>, Error> {
+        let mut ms: *mut sys::grail_meter_stream = std::ptr::null_mut();
+        check(unsafe { sys::grail_meter_stream_open(self.ctx, n_rows, sample_rate, std::ptr::null(), max_hops, &mut ms) })?;
+        Ok(MeterStream { gpu: self, ms, n_rows, hop: sample_rate / 10 })
+    }
+
     /// K-weighted gated loudness of rows of samples, measured on the device (`grail_loudness_async`; the contract is the
     /// header's section "levels, continued"): per row the gated mean square (see [`loudness_lufs`]) and the count of
     /// non-finite samples.  One lane filters one row: many rows fill the device.
@@ -1247,6 +1257,194 @@ pub fn limit_stream_len(fed_before: u64, n: u64, lookahead_log2: u32, finishing:
     let mut n_out = 0u64;
     check(unsafe { sys::grail_limit_stream_len(fed_before, n, lookahead_log2, finishing as i32, &mut n_out) })?;
     Ok(n_out)
+}
+
+/// What one call on a [`MeterStream`] gives, per row: the hop sums the call completed, the largest true-peak output among
+/// the call's own, the count of non-finite samples fed.  A refused row: no hops, a NaN peak, `refused[i]` set.
+pub struct MeterChunk {
+    pub hop_sumsq: Vec<Vec<f64>>,
+    pub true_peak: Vec<f64>,
+    pub nonfinite: Vec<u32>,
+    pub refused: Vec<bool>,
+}
+
+/// What a [`MeterStream`] shows of its rows at one moment (`grail_meter_stream_read_async`): mean squares (see
+/// [`loudness_lufs`]), the running true peak and the hops completed.
+pub struct MeterReading {
+    pub integrated_ms: Vec<f64>,
+    pub momentary_ms: Vec<f64>,
+    pub short_term_ms: Vec<f64>,
+    pub true_peak: Vec<f64>,
+    pub hops: Vec<u64>,
+}
+
+/// Rows metered chunk by chunk on a [`Gpu`]'s device ([`Gpu::meter_stream`]), the filter's state, the running peak and the
+/// ledger of hop sums resident in HBM between calls; `grail_meter_stream_close` when dropped.
+pub struct MeterStream<'a> {
+    gpu: &'a Gpu,
+    ms: *mut sys::grail_meter_stream,
+    n_rows: u32,
+    hop: u32,
+}
+
+impl MeterStream<'_> {
+    // `count` elements of `T` from device memory
+    unsafe fn down<T: Clone + Default>(&self, src: *const std::ffi::c_void, count: usize) -> Result<Vec<T>, Error> {
+        let mut v = vec![T::default(); count];
+        check(sys::grail_memcpy_d2h(self.gpu.ctx, v.as_mut_ptr() as *mut std::ffi::c_void, src, count * std::mem::size_of::<T>()))?;
+        Ok(v)
+    }
+
+    /// Feeds row `i` the samples `chunks[i]` (an empty chunk: the row pauses; `grail_meter_stream_next_async`).
+    pub fn next(&mut self, chunks: &[Vec<f32>]) -> Result<MeterChunk, Error> {
+        let n = self.n_rows as usize;
+        if chunks.len() != n {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "MeterStream::next: one chunk per row".to_string() });
+        }
+        let longest = chunks.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let hops_stride = (stride + self.hop as usize - 1) / self.hop as usize;
+        let lens: Vec<u32> = chunks.iter().map(|r| r.len() as u32).collect();
+        let ctx = self.gpu.ctx;
+        let mut res = MeterChunk { hop_sumsq: vec![Vec::new(); n], true_peak: Vec::new(), nonfinite: Vec::new(), refused: vec![false; n] };
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 6] = [std::ptr::null_mut(); 6];
+            let sizes = [n * stride * 4, n * 4, n * hops_stride * 8, n * 4, n * 8, n * 4];
+            let mut r = Ok(());
+            for k in 0..6 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in chunks.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(ctx, d[1], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_meter_stream_next_async(ctx, self.ms, d[0] as *const f32, stride as u64, d[1] as *const u32,
+                                                             d[2] as *mut f64, hops_stride as u64, d[3] as *mut u32,
+                                                             d[4] as *mut f64, d[5] as *mut u32));
+            }
+            let mut got = Ok(());
+            if r.is_ok() {
+                got = (|| {
+                    let n_hops: Vec<u32> = self.down(d[3], n)?;
+                    res.true_peak = self.down(d[4], n)?;
+                    res.nonfinite = self.down(d[5], n)?;
+                    for i in 0..n {
+                        res.refused[i] = n_hops[i] == LIMIT_REFUSED;
+                        if !res.refused[i] && n_hops[i] != 0 {
+                            res.hop_sumsq[i] = self.down((d[2] as *const f64).add(i * hops_stride) as *const std::ffi::c_void,
+                                                         n_hops[i] as usize)?;
+                        }
+                    }
+                    Ok(())
+                })();
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+            got?;
+        }
+        Ok(res)
+    }
+
+    /// What the meter shows of every row now (`grail_meter_stream_read_async`); changes no state.
+    pub fn read(&self) -> Result<MeterReading, Error> {
+        let n = self.n_rows as usize;
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, n * 8, &mut d[k]));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_meter_stream_read_async(ctx, self.ms, d[0] as *mut f64, d[1] as *mut f64, d[2] as *mut f64,
+                                                             d[3] as *mut f64, d[4] as *mut u64));
+            }
+            let mut got = Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: String::new() });
+            if r.is_ok() {
+                got = (|| {
+                    Ok(MeterReading { integrated_ms: self.down(d[0], n)?, momentary_ms: self.down(d[1], n)?,
+                                      short_term_ms: self.down(d[2], n)?, true_peak: self.down(d[3], n)?, hops: self.down(d[4], n)? })
+                })();
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+            got
+        }
+    }
+
+    /// Row `row`'s hop sums so far, copied from the ledger (`grail_meter_stream_ledger`): what [`loudness_range`] and
+    /// [`loudness_window_max`] take.
+    pub fn ledger(&self, row: u32) -> Result<Vec<f64>, Error> {
+        if row >= self.n_rows {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "MeterStream::ledger: no such row".to_string() });
+        }
+        let hops = self.read()?.hops[row as usize] as usize;
+        let mut base: *const f64 = std::ptr::null();
+        let mut stride = 0u64;
+        check(unsafe { sys::grail_meter_stream_ledger(self.gpu.ctx, self.ms, &mut base, &mut stride) })?;
+        unsafe { self.down(base.add(row as usize * stride as usize) as *const std::ffi::c_void, hops) }
+    }
+
+    /// Ends the rows marked in `which` (`None`: every row) and returns, per row, the largest of the eleven true-peak
+    /// outputs after its last sample (`grail_meter_stream_finish_async`); 0 for rows not marked and rows ended before.
+    pub fn finish(&mut self, which: Option<&[bool]>) -> Result<Vec<f64>, Error> {
+        let n = self.n_rows as usize;
+        if which.map_or(false, |w| w.len() != n) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "MeterStream::finish: one mark per row".to_string() });
+        }
+        let marks: Option<Vec<u8>> = which.map(|w| w.iter().map(|&m| m as u8).collect());
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: *mut std::ffi::c_void = std::ptr::null_mut();
+            check(sys::grail_device_alloc(ctx, n * 8, &mut d))?;
+            let mut r = check(sys::grail_meter_stream_finish_async(ctx, self.ms, marks.as_deref().map_or(std::ptr::null(), |w| w.as_ptr()),
+                                                                   d as *mut f64));
+            let mut peaks = Vec::new();
+            if r.is_ok() {
+                match self.down::<f64>(d, n) {
+                    Ok(v) => peaks = v,
+                    Err(e) => r = Err(e),
+                }
+            }
+            sys::grail_device_free(ctx, d);
+            r?;
+            Ok(peaks)
+        }
+    }
+}
+
+impl Drop for MeterStream<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_meter_stream_close(self.gpu.ctx, self.ms);
+        }
+    }
+}
+
+/// The hops a call on a [`MeterStream`] completes for a row that was fed `fed_before` samples before it and is fed `n`
+/// (`grail_meter_stream_hops`; pure host).
+pub fn meter_stream_hops(fed_before: u64, n: u64, sample_rate: u32) -> Result<u64, Error> {
+    let mut n_hops = 0u64;
+    check(unsafe { sys::grail_meter_stream_hops(fed_before, n, sample_rate, &mut n_hops) })?;
+    Ok(n_hops)
 }
 
 /// The outputs a call on a [`ResampleStream`] writes for a row that was fed `fed_before` samples before it: a `next` call

@@ -1267,6 +1267,84 @@ int grail_limit_stream_finish_async(grail_ctx *ctx, grail_limit_stream *ls, cons
  * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context. */
 int grail_limit_stream_close(grail_ctx *ctx, grail_limit_stream *ls);
 
+/* ---- levels, continued: the meters on streams ------------------------------------------------------------------------------------
+ * grail_loudness_async and grail_true_peak_async take finished rows.  A caller who pulls a live stream chunk by chunk, and
+ * filters, resamples and limits it chunk by chunk, meters it chunk by chunk with a METER STREAM: n_rows independent rows, the
+ * sample rate, the ten K-weighting coefficients and a hop capacity fixed when the stream is opened, its state resident in HBM
+ * between calls.  H = sample_rate / 10; rates are limited as for grail_loudness_async.
+ * STATE.  Per row: N, the samples fed so far (64 bits, bit 63: the row has ended); s1 .. s4 and acc of the loudness
+ * recurrence; the running true peak; the hops completed; the last 11 samples fed, already +0.0 where they were not finite, in
+ * a ring of 16 floats; a ledger of the row's hop sums, double [max_hops], in HBM.  Every double crosses a call as its 64 bits:
+ * nothing is recomputed, rounded or flushed on the way.
+ * THE CONTRACT, for any split of a row's samples into calls, calls of no samples included:
+ *   - The hop sums the `next` calls write, put end to end, are bit for bit the hop_sumsq grail_loudness_async writes for the
+ *     whole row with the same coefficients and rate, and they are the ledger's first floor(N / H) entries.
+ *   - The true_peak of a `next` call is the largest |y[p][t]| (the true-peak section's y) over the call's own output times
+ *     t = N .. N + n - 1, +0.0 for n = 0; that of `finish` is the largest over the eleven outputs t = N .. N + 10, the samples
+ *     to come being +0.0.  The maximum of all these values is grail_true_peak_async's number for the whole row, bit for bit
+ *     (a row [0, ..., 0, 1.0] whose 1.0 is a call's last sample: the calls read at most 239 / 8192, `finish` 7964 / 8192).
+ *   - The sum of the calls' nonfinite counts is either one-shot call's count: a sample is counted in the call that fed it and
+ *     enters both meters as +0.0.
+ *   - `read`, at any moment, gives for each row what the one-shot calls give for a row that holds exactly the N samples fed so
+ *     far: integrated_ms, grail_loudness_async's gated mean square over the ledger's hops (+0.0 below four hops);
+ *     momentary_ms = (((h[j] + h[j+1]) + h[j+2]) + h[j+3]) / (4.0 * H) at j = hops - 4, the gate's last z_j (+0.0 below four
+ *     hops); short_term_ms = the left fold of the last 30 hops from the oldest, divided by (30.0 * H), the last block of
+ *     grail_loudness_window_max(..., 30) (+0.0 below 30 hops); true_peak, the running maximum (before `finish` it lacks the
+ *     eleven outputs after the row's last sample; after it, it is the one-shot number); hops, the count of hops completed.
+ *   - REFUSED for that call, as in the other kinds: a row that has ended and is fed n > 0, and a row that the call would carry
+ *     past max_hops completed hops: n_hops = GRAIL_LIMIT_REFUSED, true_peak = NaN, nonfinite = 0, nothing written, its state as
+ *     it was; a correct call may follow.
+ * One lane filters one row's chunk (the recurrence is serial), 64 rows to a wavefront; a wavefront whose rows all stand at the
+ * same place in their hops and are fed the same n takes the one-shot kernel's walk, any other a walk with a test a sample:
+ * same bits.  The true peak of a call is parallel in time.  Measured on an MI355X: 65 536 rows of 96 006 samples fed whole in
+ * one call, the hops in 7.3 ms where grail_loudness_async's take 7.4 - 7.6 (10.8 against 11.3 ms right behind a call's
+ * true peak, which takes 16 ms); 4 096 rows fed 480 samples: 0.07 ms a call, 0.03 ms a read. */
+typedef struct grail_meter_stream grail_meter_stream;
+
+/* Pure host: *n_hops = the hops a `next` call completes for a row that was fed fed_before samples before it and is fed n:
+ * (fed_before + n) / H - fed_before / H.  GRAIL_ERR_INVALID_ARG, nothing written: a rate outside GRAIL_LOUDNESS_RATE_MIN ..
+ * GRAIL_LOUDNESS_RATE_MAX; n_hops NULL; fed_before + n does not fit 64 bits. */
+int grail_meter_stream_hops(uint64_t fed_before, uint64_t n, uint32_t sample_rate, uint64_t *n_hops);
+/* A stream of n_rows rows metered at sample_rate.  coef: HOST [10], copied before the call returns; NULL =
+ * grail_kweighting(sample_rate).  max_hops: the hops a row's ledger holds (8 bytes each); a row is never carried past it.  The
+ * state belongs to the stream, which belongs to the context.  GRAIL_ERR_INVALID_ARG, nothing created: a rate out of range;
+ * n_rows = 0; max_hops = 0, or n_rows x max_hops x 8 does not fit size_t; ctx or out NULL.  These come first; without a
+ * usable device: GRAIL_ERR_NO_DEVICE.  GRAIL_ERR_OUT_OF_MEMORY: the device refuses the ledger. */
+int grail_meter_stream_open(grail_ctx *ctx, uint32_t n_rows, uint32_t sample_rate, const double *coef, uint64_t max_hops,
+                            grail_meter_stream **out);
+/* Feeds every row u its next n = min(in_len_dev[u], in_stride) samples from in_dev + u * in_stride; queued on ctx's stream.
+ * in_len_dev: device [n_rows].  hop_sumsq_dev: DEVICE double [n_rows][hops_stride], the hops the call completes from index 0,
+ * entries past n_hops never written; hops_stride >= (in_stride + H - 1) / H, the most hops a call can complete.  n_hops_dev,
+ * true_peak_dev (double), nonfinite_dev: DEVICE arrays [n_rows].  All four may be NULL; the ledger is kept either way.  n = 0
+ * is legal (a paused row): 0, +0.0, 0.  in_dev may be reused by whatever is queued behind the call: the call copies what it
+ * keeps.  16-byte loads where in_dev is 16-byte aligned and in_stride a multiple of 4, 4-byte loads otherwise: same bits.
+ * The chunks' maxima go through scratch that stays with the context (12 bytes per 4096 samples of n_rows x in_stride).
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of this context (looked up, not looked into); a
+ * NULL in_dev with samples to read, in_len_dev NULL; hop_sumsq_dev with a hops_stride below the rule; rows that span more
+ * than 2^60 samples; more than 2^31 chunks of 4096 output times.  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE. */
+int grail_meter_stream_next_async(grail_ctx *ctx, grail_meter_stream *ms, const float *in_dev, uint64_t in_stride,
+                                  const uint32_t *in_len_dev, double *hop_sumsq_dev, uint64_t hops_stride, uint32_t *n_hops_dev,
+                                  double *true_peak_dev, uint32_t *nonfinite_dev);
+/* What the meter shows of every row now (THE CONTRACT, `read`), queued on ctx's stream: DEVICE arrays [n_rows], four of
+ * double and hops_dev of uint64, any may be NULL.  It changes no state.  GRAIL_ERR_INVALID_ARG: not an open stream of this
+ * context. */
+int grail_meter_stream_read_async(grail_ctx *ctx, grail_meter_stream *ms, double *integrated_ms_dev, double *momentary_ms_dev,
+                                  double *short_term_ms_dev, double *true_peak_dev, uint64_t *hops_dev);
+/* The ledger's device address: row u's hop sums are (*hops_dev)[u * *stride + h], h below the row's hops; *stride = max_hops.
+ * It stays valid until the stream is closed; the stream's calls write it on ctx's stream.  A caller copies a track's hops from
+ * it for grail_loudness_range and grail_loudness_window_max.  GRAIL_ERR_INVALID_ARG: not an open stream of this context; a
+ * NULL argument. */
+int grail_meter_stream_ledger(grail_ctx *ctx, grail_meter_stream *ms, const double **hops_dev, uint64_t *stride);
+/* Ends the rows marked in which (a HOST array [n_rows] of bytes, non-zero = marked; NULL = every row; the array may be reused
+ * at once): the true-peak filter rings out over the eleven outputs after the row's last sample.  true_peak_dev: DEVICE double
+ * [n_rows], may be NULL: the largest of those eleven, +0.0 for rows that are unmarked or had ended before.  The running
+ * peak takes it in.  GRAIL_ERR_INVALID_ARG, nothing queued: not an open stream of this context. */
+int grail_meter_stream_finish_async(grail_ctx *ctx, grail_meter_stream *ms, const uint8_t *which, double *true_peak_dev);
+/* Releases a stream once everything queued on ctx's stream is through; streams still open at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context. */
+int grail_meter_stream_close(grail_ctx *ctx, grail_meter_stream *ms);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
