@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--rate R] [--report] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--rate R] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -14,6 +14,11 @@
 // of LO .. HI Hz (grail::fir_design, a Kaiser window of --taps K taps, K odd, 255 unless said; grail::Gpu::fir): "--band 300
 // 3400 --rate 8000" is a telephone line.  The tracks keep their length (the filter has zero delay; its tail past the end is
 // dropped).  A filter overshoots, so with --ceiling the line that states the tracks' true peaks is measured after it.
+// --eq KIND:F0:Q[:GAIN] (up to eight times) passes the two mixed tracks, after --band and before the limiter, through one
+// recursive filter of as many biquad sections as there are --eq (grail_iir_design at the voices' rate, grail_iir_async): KIND is
+// lowpass, highpass, bandpass, notch, peak, lowshelf or highshelf, F0 in Hz, GAIN in dB for peak and the shelves:
+// "--eq highpass:100:0.707 --eq peak:3000:1.5:4" is a high-pass under the voices and a presence peak.  The tracks keep their
+// length (no tail).  A filter overshoots, so with --ceiling the tracks' true peaks are measured after it.
 // --rate R resamples the two finished tracks, after the mix and the limiter, from the voices' 44 100 Hz to R Hz on the device
 // (grail::Gpu::resample) and writes the WAV at R; the filter overshoots a little, so the line it prints has the tracks'
 // true peaks at R.
@@ -28,6 +33,7 @@
 #include <utility>
 #include <vector>
 
+#include "eq_option.h"
 #include "grail.hpp"
 
 int main(int argc, char **argv)
@@ -42,6 +48,7 @@ int main(int argc, char **argv)
     bool band = false, bad_band = false, taps_given = false;
     double band_lo = 0.0, band_hi = 0.0;
     uint32_t band_taps = 255;
+    EqOption eq_option;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
         else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
@@ -77,20 +84,25 @@ int main(int argc, char **argv)
             taps_given = true;
             band_taps = (uint32_t)k;
             bad_band = bad_band || rest == argv[i] || *rest || argv[i][0] == '-' || k < 3 || k > GRAIL_FIR_TAPS_MAX || k % 2 == 0;
-        } else if (!std::strcmp(argv[i], "--limit")) limit = true;
+        } else if (!std::strcmp(argv[i], "--eq")) eq_option.take(argc, argv, i);      // (examples/eq_option.h)
+        else if (!std::strcmp(argv[i], "--limit")) limit = true;
         else if (!std::strcmp(argv[i], "--report")) {
             bad_report = report;        // (named twice)
             report = true;
         } else if (!std::strncmp(argv[i], "--report", 8)) bad_report = true;        // (it takes no value)
         else lines.push_back(argv[i]);
     }
-    // (the voices are the generic ones, at 44 100 Hz: a band that ends above their Nyquist frequency is said here)
+    // (the voices are the generic ones, at 44 100 Hz: a band that ends above their Nyquist frequency is said here, and the
+    // sections of --eq are designed: the designer refuses what it cannot make)
+    std::vector<double> eq;         // five numbers a section
+    const bool bad_eq = eq_option.bad || !eq_option.design(44100, eq);
     bad_band = bad_band || (taps_given && !band) || (band && band_hi > 22050.0);
-    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || (capped && !leveled) || (limit && !capped)) {
+    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || bad_eq || (capped && !leveled) || (limit && !capped)) {
         std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] "
-                             "[--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
+                             "[--eq KIND:F0:Q[:GAIN]]... [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
                              "needs --ceiling, --band takes 0 <= LO < HI <= 22050 Hz, --taps an odd number from 3 to 4096 and needs "
-                             "--band, --rate takes a whole number of Hz, --report takes no value)\n");
+                             "--band, --eq takes lowpass, highpass, bandpass, notch, peak, lowshelf or highshelf, 0 < F0 < 22050 Hz, Q > 0 and a "
+                             "gain in dB, up to eight times, --rate takes a whole number of Hz, --report takes no value)\n");
         return 2;
     }
     try {
@@ -118,6 +130,34 @@ int main(int argc, char **argv)
             tracks = gpu.fir(set, tracks, {}, false);
             std::printf("Filtered %g - %g Hz at %u Hz (%u taps)\n", band_lo, band_hi, at_rate, band_taps);
         };
+        // --eq: one recursive filter of as many sections as were named, for both tracks, which keep their length (the C ABI on
+        // the Gpu's context: the facade has no class for it yet)
+        const auto equalise = [&]() {
+            if (eq.empty()) return;
+            grail_ctx *ctx = gpu.ctx();
+            const uint32_t sections = (uint32_t)(eq.size() / 5), n = (uint32_t)tracks.size();
+            const uint64_t stride = ((uint64_t)end + 63) / 64 * 64;
+            grail_iir *set = nullptr;
+            grail::check(grail_iir_create(ctx, eq.data(), &sections, 1, &set));
+            void *d_rows = nullptr, *d_out = nullptr, *d_len = nullptr;
+            int rc = grail_device_alloc(ctx, n * stride * 4, &d_rows);
+            if (!rc) rc = grail_device_alloc(ctx, n * stride * 4, &d_out);
+            if (!rc) rc = grail_device_alloc(ctx, n * 4, &d_len);
+            std::vector<uint32_t> track_len;
+            for (const std::vector<float> &t : tracks) track_len.push_back((uint32_t)t.size());
+            for (uint32_t t = 0; t < n && !rc; ++t)
+                rc = grail_memcpy_h2d(ctx, (float *)d_rows + t * stride, tracks[t].data(), tracks[t].size() * 4);
+            if (!rc) rc = grail_memcpy_h2d(ctx, d_len, track_len.data(), n * 4);
+            if (!rc) rc = grail_iir_async(ctx, set, (const float *)d_rows, stride, (const uint32_t *)d_len, n, nullptr, 0, (float *)d_out, stride, nullptr, nullptr);
+            for (uint32_t t = 0; t < n && !rc; ++t)
+                rc = grail_memcpy_d2h(ctx, tracks[t].data(), (const float *)d_out + t * stride, tracks[t].size() * 4);
+            for (void *p : {d_rows, d_out, d_len})
+                if (p) grail_device_free(ctx, p);
+            const int freed = grail_iir_free(ctx, set);
+            grail::check(rc ? rc : freed);
+            std::printf("Equalised, %u section%s:", sections, sections == 1 ? "" : "s");
+            std::printf("%s\n", eq_option.text().c_str());
+        };
         if (leveled) {          // the same pan as a level: 0.8 and 0.2 of the line at level_db
             std::vector<float> levels, gains;
             for (const grail::Placement &p : placements) levels.push_back(level_db + 20.0f * std::log10(p.gain));
@@ -126,6 +166,7 @@ int main(int argc, char **argv)
             tracks = capped ? gpu.mix_leveled_limited(utts, placements, levels, ceiling_db, 2, end, mode, &gains, &unleveled, &limited)
                             : gpu.mix_leveled(utts, placements, levels, 2, end, mode, &gains, &unleveled);
             band_pass();
+            equalise();
             if (lufs)
                 std::printf("Lines brought to %.1f LUFS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
                             unleveled ? " (a silent line or one shorter than 400 ms was left out)" : "");
@@ -151,6 +192,7 @@ int main(int argc, char **argv)
         } else {
             tracks = gpu.mix(utts, placements, 2, end);
             band_pass();
+            equalise();
         }
         uint32_t out_rate = (uint32_t)first.sample_rate;
         if (resampled && rate != out_rate) {    // (the voices' own rate: nothing to do, and the library refuses equal rates)

@@ -13,7 +13,7 @@
 // Without a sound card time is the audio itself: a line "@1.5 text" arrives once 1.5 s of audio have been rendered, a line
 // without a stamp arrives at once.  After the last line has been spoken the session runs `tail` seconds longer (the
 // reference never ends) and the source is closed.
-//   usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [--meter] [chunk_samples] [tail_seconds]
+//   usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [--eq KIND:F0:Q[:GAIN]]... [--meter] [chunk_samples] [tail_seconds]
 //          < script > out.f32
 // --band LO HI: every pulled chunk goes through a filter stream (the Kaiser-windowed band-pass LO .. HI Hz of
 // grail_fir_design, K taps, 255 unless --taps says otherwise, at its zero-delay origin) before it leaves the device, and when
@@ -27,6 +27,10 @@
 // before it leaves the device.  When the chain has ended the tails are flushed in chain order: the filter's tail is fed to
 // the limiter and what that gives to the resampler, then the limiter's own tail likewise, then the resampler's.  The output is what grail_resample_async gives for the whole (filtered)
 // session.
+// --eq KIND:F0:Q[:GAIN] (up to eight times; examples/eq_option.h): everything that leaves the chain above, chunk by chunk and
+// the tails too, goes through an IIR stream (grail_iir_stream_*) of one recursive filter of as many biquad sections as there
+// are --eq, designed at the rate that is written (grail_iir_design), before it is written; after the last of them the filter
+// rings out for a tenth of a second.  The output is what grail_iir_async gives for the whole session's samples with that tail.
 // --meter: everything that is written goes through a meter stream (grail_meter_stream_*) at the rate it is written at, chunk by
 // chunk and the tails too; after the last of them the row is finished and stderr gets the report of grail_dialogue --report
 // (integrated loudness, range, max momentary, max short-term, true peak), then the gated mean square and the true peak as
@@ -42,6 +46,7 @@
 #include <string>
 #include <vector>
 
+#include "eq_option.h"
 #include "grail.hpp"
 
 namespace {
@@ -72,6 +77,72 @@ std::vector<grail::PhonemeElem> speak(const grail::Voice &voice, const std::stri
     if (n) grail::check(grail_intonate(&voice, ph.data(), n, out.data()));
     return out;
 }
+
+// --eq: an IIR stream of one row on what leaves the chain, through the C ABI (grail_iir_create, grail_iir_stream_*): the
+// filter's state stays on the device from one pull to the next.
+class Eq {
+public:
+    Eq(grail_ctx *ctx, const std::vector<double> &coef, uint32_t tail) : ctx_(ctx), tail_(tail)
+    {
+        const uint32_t sections = (uint32_t)(coef.size() / 5);
+        grail::check(grail_iir_create(ctx, coef.data(), &sections, 1, &set_));
+        grail::check(grail_iir_stream_open(ctx, set_, 1, nullptr, tail, &stream_));
+    }
+    Eq(const Eq &) = delete;
+    Eq &operator=(const Eq &) = delete;
+    ~Eq()
+    {
+        grail_iir_stream_close(ctx_, stream_);      // (before its set: a set with open streams is not freed)
+        grail_iir_free(ctx_, set_);
+        for (void *p : {in_, out_, len_}) grail_device_free(ctx_, p);
+    }
+    // the samples that left the chain go back to the device and through the filter; as many come back
+    std::vector<float> next(const std::vector<float> &part)
+    {
+        if (part.empty()) return {};
+        room(part.size());
+        const uint32_t n = (uint32_t)part.size();
+        grail::check(grail_memcpy_h2d(ctx_, in_, part.data(), n * sizeof(float)));
+        grail::check(grail_memcpy_h2d(ctx_, len_, &n, sizeof n));
+        grail::check(grail_iir_stream_next_async(ctx_, stream_, (const float *)in_, cap_, (const uint32_t *)len_, (float *)out_, cap_,
+                                                 nullptr, nullptr));
+        std::vector<float> out(n);
+        grail::check(grail_memcpy_d2h(ctx_, out.data(), out_, n * sizeof(float)));
+        return out;
+    }
+    // the row ends: what the filter rings out on +0.0 input (nothing if it was fed nothing)
+    std::vector<float> finish()
+    {
+        room(tail_ ? tail_ : 1u);
+        uint32_t n = 0;
+        grail::check(grail_iir_stream_finish_async(ctx_, stream_, nullptr, (float *)out_, cap_, (uint32_t *)len_));
+        grail::check(grail_memcpy_d2h(ctx_, &n, len_, sizeof n));
+        std::vector<float> out(n);
+        if (n) grail::check(grail_memcpy_d2h(ctx_, out.data(), out_, n * sizeof(float)));
+        return out;
+    }
+
+private:
+    void room(size_t samples)
+    {
+        if (!len_) grail::check(grail_device_alloc(ctx_, sizeof(uint32_t), &len_));
+        if (samples <= cap_) return;
+        grail::check(grail_sync(ctx_));
+        for (void **p : {&in_, &out_}) {
+            grail_device_free(ctx_, *p);
+            *p = nullptr;
+        }
+        cap_ = (samples + 63) / 64 * 64;
+        grail::check(grail_device_alloc(ctx_, cap_ * sizeof(float), &in_));
+        grail::check(grail_device_alloc(ctx_, cap_ * sizeof(float), &out_));
+    }
+    grail_ctx *ctx_;
+    uint32_t tail_;
+    grail_iir *set_ = nullptr;
+    grail_iir_stream *stream_ = nullptr;
+    void *in_ = nullptr, *out_ = nullptr, *len_ = nullptr;
+    size_t cap_ = 0;
+};
 
 // --meter: a meter stream of one row on what leaves the chain, through the C ABI (grail_meter_stream_*).  The ledger holds an
 // hour of hops; a session that outgrows it is refused from there on, and the report says so.
@@ -161,6 +232,7 @@ int main(int argc, char **argv)
     long taps = 0, rate = 0, lookahead = -1;
     double ceiling_db = 0.0;
     bool usage = false, limit = false, meter = false;
+    EqOption eq_option;
     for (int i = 1; i < argc; ++i) {
         const std::string a = argv[i];
         char *end = nullptr;
@@ -190,6 +262,8 @@ int main(int argc, char **argv)
             usage = usage || end == argv[i + 1] || *end || rate < 1 || rate > 0xFFFFFFFFl ||
                     grail_resample_ratio((uint32_t)grail::voices::generic().sample_rate, (uint32_t)rate, nullptr, nullptr, nullptr) != GRAIL_OK;
             i += 1;
+        } else if (a == "--eq") {
+            eq_option.take(argc, argv, i);
         } else if (a == "--meter") {
             meter = true;
         } else if (a.rfind("--", 0) == 0) {
@@ -201,11 +275,15 @@ int main(int argc, char **argv)
     const bool band = hi >= 0.0;
     const uint32_t chunk = plain.size() > 0 ? (uint32_t)std::strtoul(plain[0], nullptr, 10) : 441;
     const double tail = plain.size() > 1 ? std::strtod(plain[1], nullptr) : 1.0;
+    // (--eq runs at the rate that is written: the designer refuses what it cannot make there)
+    const uint32_t out_rate = rate ? (uint32_t)rate : (uint32_t)grail::voices::generic().sample_rate;
+    std::vector<double> eq_coef;
+    usage = usage || eq_option.bad || !eq_option.design(out_rate, eq_coef);
     // (a chunk of 0 samples — or text strtoul makes 0 of — would never feed the stream)
     if (usage || plain.size() > 2 || chunk == 0 || !(tail >= 0.0) || (taps && !band) || (band && !(lo >= 0.0 && lo < hi)) ||
         (lookahead >= 0 && !limit)) {
-        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [--meter] "
-                             "[samples per pull >= 1 (default 441)] [seconds of tail >= 0 (default 1)]\n");
+        std::fprintf(stderr, "usage: grail_interactive [--band LO HI [--taps K]] [--ceiling DB [--lookahead l]] [--rate R] [--eq KIND:F0:Q[:GAIN]]... "
+                             "[--meter] [samples per pull >= 1 (default 441)] [seconds of tail >= 0 (default 1)]\n");
         return 2;
     }
     try {
@@ -223,6 +301,8 @@ int main(int argc, char **argv)
         std::vector<grail::ResampleStream> resamplers;
         if (rate) resamplers.push_back(gpu.resample_stream((uint32_t)voice.sample_rate, (uint32_t)rate, 1));
         // (declared after the other streams: closed before them)
+        std::unique_ptr<Eq> equaliser;
+        if (eq_option.given()) equaliser.reset(new Eq(gpu.ctx(), eq_coef, out_rate / 10u));
         std::unique_ptr<Meter> metered;
         if (meter) metered.reset(new Meter(gpu.ctx(), rate ? (uint32_t)rate : (uint32_t)voice.sample_rate));
         std::vector<Line> script;
@@ -243,6 +323,13 @@ int main(int argc, char **argv)
         bool first = true, closed = false;
         double close_at = -1.0;
         const char *names[] = {"Silence", "Stop", "Glide", "A", "E"};
+        // what leaves the chain: through --eq, to stdout, through --meter
+        const auto emit = [&](std::vector<float> samples, bool through_eq = true) {
+            if (equaliser && through_eq) samples = equaliser->next(samples);
+            std::fwrite(samples.data(), sizeof(float), samples.size(), stdout);
+            if (meter) metered->feed(samples);
+            written += samples.size();
+        };
         for (;;) {
             const double now = (double)total / voice.sample_rate;
             while (next_line < script.size() && script[next_line].at <= now) {      // the channel receives a line
@@ -263,10 +350,8 @@ int main(int argc, char **argv)
                 part = chain.next();
                 rendered = (uint32_t)part.size();
             }
-            std::fwrite(part.data(), sizeof(float), part.size(), stdout);
-            if (meter) metered->feed(part);
+            emit(part);
             total += rendered;
-            written += part.size();
             if (rendered == chunk) continue;
             if (closed) {
                 if (rendered == 0) break;                             // the chain has returned None
@@ -297,9 +382,7 @@ int main(int argc, char **argv)
             std::vector<float> rest = filters[0].finish().at(0);
             if (limit) rest = limiters[0].next({rest}).at(0);         // ... into the next stages of the chain
             if (rate) rest = resamplers[0].next({rest}).at(0);
-            std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
-            if (meter) metered->feed(rest);
-            written += rest.size();
+            emit(rest);
             if (rate || limit)
                 std::fprintf(stderr, "Filtered %g - %g Hz at %g Hz (%u taps)\n", lo, hi, (double)voice.sample_rate, filters[0].tail() + 1);
             else
@@ -309,9 +392,7 @@ int main(int argc, char **argv)
         if (limit) {                                                  // ... the limiter's own tail: what its look-ahead held back
             std::vector<float> rest = limiters[0].finish().at(0);
             if (rate) rest = resamplers[0].next({rest}).at(0);
-            std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
-            if (meter) metered->feed(rest);
-            written += rest.size();
+            emit(rest);
             if (rate)
                 std::fprintf(stderr, "Limited to %g dBTP, %u samples late\n", ceiling_db, limiters[0].delay());
             else
@@ -320,10 +401,12 @@ int main(int argc, char **argv)
         }
         if (rate) {                                                   // ... and the resampler's own tail
             const std::vector<float> rest = resamplers[0].finish().at(0);
-            std::fwrite(rest.data(), sizeof(float), rest.size(), stdout);
-            if (meter) metered->feed(rest);
-            written += rest.size();
+            emit(rest);
             std::fprintf(stderr, "Resampled %g -> %ld Hz: %zu samples written\n", (double)voice.sample_rate, rate, written);
+        }
+        if (equaliser) {                                              // ... and the equaliser's: a tenth of a second of ringing
+            emit(equaliser->finish(), false);
+            std::fprintf(stderr, "Equalised at %u Hz,%s: %zu samples written\n", out_rate, eq_option.text().c_str(), written);
         }
         if (meter) metered->report(1);
         std::fprintf(stderr, "session: %zu samples (%.2f s), %zu phonemes fed, %zu lines, buffers of %u\n", total,

@@ -4,7 +4,7 @@
 // family_cost.cpp, dispatch_model.cpp, launch_plan.cpp: kernel families, cost model, dispatcher model, block planner
 // (launch_plan.h); synthesize.cpp: launches; streams.cpp: resumable and live streams; mix.cpp: rows
 // mixed into tracks; levels.cpp: rows measured (levels, loudness, true peak); transforms.cpp: rows limited, resampled and
-// filtered at once, transform_streams.cpp: the same as streams (both on transform_state.h); host_output.cpp: the one-call
+// filtered (FIR, recursive) at once, transform_streams.cpp: the same as streams (both on transform_state.h); host_output.cpp: the one-call
 // forms with a host destination; comm.cpp and node.cpp: RCCL, the contexts of a node.  Every HIP resource these units
 // create has one owner type (below): Event, Stream, DeviceBuffer, PinnedBuffer.
 #pragma once
@@ -35,6 +35,7 @@
 #include "../../include/grail_hip.h"
 #include "division_window.h"
 #include "fir_plan.h"
+#include "iir_plan.h"
 #include "kernels.h"
 #include "limit_plan.h"
 #include "meter_plan.h"
@@ -395,6 +396,26 @@ struct grail_meter_stream : ChunkedStream {
     uint64_t max_hops = 0;                  // the ledger's capacity a row, fixed at open
     double coef[10] = {};
     grail::host::DeviceBuffer<double> d_ledger;     // [n_rows][max_hops]
+};
+
+// A set of recursive filters (transforms.cpp; the image is iir_plan.cpp's): owned by the context's TransformState, released by
+// grail_iir_free or with the context.
+struct grail_iir {
+    uint32_t n_filters = 0;
+    uint32_t bound = 1;               // the set's largest S rounded up to 1, 2, 4 or 8: the kernel instantiation that serves it
+    std::vector<double> image;        // (host copies, kept while the upload may be in flight)
+    std::vector<uint32_t> sections;
+    grail::host::DeviceBuffer<double> d_image;        // [n_filters][IIR_IMAGE_DOUBLES]
+    grail::host::DeviceBuffer<uint32_t> d_sections;   // [n_filters]
+};
+
+// A stream of rows filtered recursively call by call (iir_kernels.hip): iir_stream_state_words(set->bound) state words a row
+// (samples fed, then s1, s2 of each section), no ring (ring_cap 0: a recursive filter's memory is its state).
+struct grail_iir_stream : ChunkedStream {
+    const grail_iir *set = nullptr;   // (a set with open streams is not freed)
+    uint32_t tail = 0;                // the outputs a row rings out over at its finish
+    std::vector<uint32_t> filter;     // the rows' filters (host copy, kept while the upload may be in flight)
+    grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows]
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks

@@ -336,4 +336,34 @@ hipError_t launch_meter_stream_read(const uint64_t *state, uint32_t n_rows, uint
                                     double *integrated, double *momentary, double *short_term, double *true_peak, uint64_t *hops,
                                     hipStream_t stream);
 
+// recursive filtering (iir_kernels.hip): one lane per row through the S sections of its filter, 64 rows to a wave, the
+// filtered rows to out.  image: DEVICE [n_filters][40], section j of a filter at 5 j, +0.0 past its own; sections: DEVICE
+// [n_filters], each filter's S; bound: 1, 2, 4 or 8, at or above every S of the set (iir_plan.h); filter: DEVICE [n_rows] or
+// NULL (filter 0 for every row).  A row's n_out = min(n + tail, out_stride), 0 for n = 0; out_len, nonfinite: DEVICE
+// [n_rows], may be NULL; a row whose filter index is outside the set: 0xFFFFFFFF and 0, nothing written.
+// state != NULL: a call on a stream, the one kernel with the state read at entry and written at exit.  state: DEVICE
+// [n_rows][1 + 2 * bound] = {the samples a row has been fed with bit 63 set once it has ended, then s1, s2 of each section as
+// their bits}.  Feeding: n = min(len, row_stride) samples in, n out (tail is not read).  finishing: rows and len are not
+// read, the rows with mark[u] != 0 (mark NULL: every row) that have not ended write tail outputs (none if fed nothing) and
+// end; nonfinite is not written.  A row that has ended and is fed: 0xFFFFFFFF and 0, nothing else.
+struct IirArgs {
+    const float *rows;
+    uint64_t row_stride;
+    const uint32_t *len;
+    uint32_t n_rows;
+    const uint32_t *filter;
+    const double *image;
+    const uint32_t *sections;
+    uint32_t n_filters;
+    uint32_t tail;
+    float *out;
+    uint64_t out_stride;
+    uint32_t *out_len;
+    uint32_t *nonfinite;
+    uint64_t *state;
+    const uint8_t *mark;
+    uint32_t finishing;
+};
+hipError_t launch_iir(const IirArgs &args, uint32_t bound, hipStream_t stream);
+
 }  // namespace grail

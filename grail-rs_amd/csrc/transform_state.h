@@ -57,6 +57,8 @@ struct TransformState : CtxPart {
     DeviceBuffer<double> d_mpeak;           // meter stream chunks (4096 output times each): the largest |y|
     DeviceBuffer<uint32_t> d_mbad;          // ... and the non-finite counts
     Owned<grail_meter_stream> meter_streams;        // the meter streams open
+    Owned<grail_iir> iirs;                  // the recursive filter sets alive
+    Owned<grail_iir_stream> iir_streams;    // ... and, after them (they die first), the IIR streams open on them
 };
 
 // what the context has, made by nobody: NULL before the first call that needed it

@@ -1,7 +1,8 @@
 // transform_streams.cpp — finished rows filtered, resampled and limited chunk by chunk: grail_filter_stream_open / _next_async /
 // _finish_async / _close (fir_kernels.hip), grail_resample_stream_* (resample_kernels.hip, §4.16) and
 // grail_limit_stream_* (limiter_kernels.hip, §4.17), and metered chunk by chunk: grail_meter_stream_* (meter_stream_kernels.hip,
-// §4.18).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp, limit_plan.cpp, meter_plan.cpp; their common
+// §4.18), and filtered recursively chunk by chunk: grail_iir_stream_* (iir_kernels.hip, §4.20; checks iir_plan.cpp; one launch
+// a call, no ring).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp, limit_plan.cpp, meter_plan.cpp; their common
 // end row_checks.h), what it keeps beside the rings, and its launches (two; the meter's three).  What the kinds do alike stands
 // once, first: telling a stream of the context's, its device state, a finishing call's marks, its close.
 #include "transform_state.h"
@@ -162,6 +163,22 @@ int meter_stream_call(grail_ctx *ctx, grail_meter_stream *ms, const float *in_de
                                                      ms->d_ring.get(), mark_dev, finishing, st->d_mpeak.get(), st->d_mbad.get(),
                                                      (uint32_t)chunks, n_hops_dev, true_peak_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "meter stream advance kernel launch");
+    return GRAIL_OK;
+}
+
+// An IIR stream's call is one kernel: grail_iir_async's, with the rows' state read at entry and written at exit.
+int iir_stream_call(grail_ctx *ctx, grail_iir_stream *is, const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev,
+                    const uint8_t *mark_dev, bool finishing, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                    uint32_t *nonfinite_dev)
+{
+    const grail_iir *set = is->set;
+    IirArgs a = {};
+    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev, a.n_rows = is->n_rows, a.filter = is->d_filter.get();
+    a.image = set->d_image.get(), a.sections = set->d_sections.get(), a.n_filters = set->n_filters, a.tail = is->tail;
+    a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
+    a.state = is->d_state.get(), a.mark = mark_dev, a.finishing = finishing ? 1u : 0u;
+    const hipError_t e = launch_iir(a, set->bound, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "iir stream kernel launch");
     return GRAIL_OK;
 }
 
@@ -437,6 +454,61 @@ int grail_meter_stream_finish_async(grail_ctx *ctx, grail_meter_stream *ms, cons
     if ((rc = marks(ctx, *ms, which, &mark_dev))) return rc;
     // (one chunk a row: the eleven outputs after its last sample)
     return meter_stream_call(ctx, ms, nullptr, 0, nullptr, mark_dev, true, 1, nullptr, 0, nullptr, true_peak_dev, nullptr);
+}
+
+int grail_iir_stream_open(grail_ctx *ctx, const grail_iir *set, uint32_t n_rows, const uint32_t *filter, uint32_t tail,
+                          grail_iir_stream **out)
+{
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_stream_open: NULL argument");
+    if (!own(ctx, &TransformState::iirs, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_stream_open: not a filter set of this context");
+    if (const char *why = iir_stream_open_error(filter, n_rows, set->n_filters)) return refuse("grail_iir_stream_open", why);
+    int rc = bind(ctx);
+    if (rc) return rc;
+    std::unique_ptr<grail_iir_stream> is(new (std::nothrow) grail_iir_stream());
+    if (!is) return fail(GRAIL_ERR_OUT_OF_MEMORY, "IIR stream");
+    is->set = set;
+    is->tail = tail;
+    is->n_rows = is->units = n_rows;
+    is->ring_cap = 0;                                       // (no ring: the filter's memory is its state)
+    is->filter.assign(n_rows, 0u);
+    if (filter) std::copy(filter, filter + n_rows, is->filter.begin());
+    HIP_TRY(upload(is->d_filter, is->filter.data(), n_rows, ctx->stream));
+    if ((rc = alloc_state(ctx, *is, iir_stream_state_words(set->bound)))) return rc;       // (nothing fed, every state +0.0)
+    *out = peek(ctx)->iir_streams.add(std::move(is));       // (the set was found: the state is there)
+    return GRAIL_OK;
+}
+
+int grail_iir_stream_close(grail_ctx *ctx, grail_iir_stream *is)
+{
+    return stream_close(ctx, &TransformState::iir_streams, is, "grail_iir_stream_close", "IIR");
+}
+
+int grail_iir_stream_next_async(grail_ctx *ctx, grail_iir_stream *is, const float *in_dev, uint64_t in_stride,
+                                const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                                uint32_t *nonfinite_dev)
+{
+    const char *who = "grail_iir_stream_next_async";
+    int rc = known(ctx, &TransformState::iir_streams, is, who, "IIR");
+    if (rc) return rc;
+    // (without a context: the checks of one row)
+    if (const char *why = iir_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? is->n_rows : 1u, out_dev, out_stride))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    return iir_stream_call(ctx, is, in_dev, in_stride, in_len_dev, nullptr, false, out_dev, out_stride, out_len_dev, nonfinite_dev);
+}
+
+int grail_iir_stream_finish_async(grail_ctx *ctx, grail_iir_stream *is, const uint8_t *which, float *out_dev, uint64_t out_stride,
+                                  uint32_t *out_len_dev)
+{
+    const char *who = "grail_iir_stream_finish_async";
+    int rc = known(ctx, &TransformState::iir_streams, is, who, "IIR");
+    if (rc) return rc;
+    // (without a context: the checks of one row with a tail of one output)
+    if (const char *why = iir_stream_finish_error(out_dev, out_stride, ctx ? is->n_rows : 1u, ctx ? is->tail : 1u)) return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    const uint8_t *mark_dev;
+    if ((rc = marks(ctx, *is, which, &mark_dev))) return rc;
+    return iir_stream_call(ctx, is, nullptr, 0, nullptr, mark_dev, true, out_dev, out_stride, out_len_dev, nullptr);
 }
 
 }  // extern "C"

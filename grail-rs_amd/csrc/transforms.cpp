@@ -1,6 +1,7 @@
 // transforms.cpp — the calls that read finished rows and write rows, at once: grail_limit_async (limiter_kernels.hip, DESIGN.md
 // §4.12), grail_resample_async (resample_kernels.hip, the ratio and table resample_plan.cpp, §4.13) and grail_fir_create /
-// _free / _async (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14): their checks, their scratch, their launches.
+// _free / _async (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_iir_create / _free / _async
+// (iir_kernels.hip, a set's checks and image iir_plan.cpp, §4.19): their checks, their scratch, their launches.
 // What they check of a pair of rows is row_checks.h.  The same chunk by chunk, on streams, is transform_streams.cpp; what a
 // context keeps for both is transform_state.h.
 #include "row_checks.h"
@@ -185,6 +186,67 @@ int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev,
     const hipError_t e = launch_fir_totals(len_dev, row_stride, n_rows, filter_dev, set->d_desc.get(), set->n_filters, out_stride,
                                            st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "fir totals kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_iir_create(grail_ctx *ctx, const double *coef, const uint32_t *n_sections, uint32_t n_filters, grail_iir **out)
+{
+    if (!out) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_create: NULL argument");
+    if (const char *why = iir_set_error(coef, n_sections, n_filters))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_iir_create: ") + why);
+    int rc = bind_device(ctx, "grail_iir_create");
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_iir> set(new (std::nothrow) grail_iir());
+    if (!set) return fail(GRAIL_ERR_OUT_OF_MEMORY, "recursive filter set");
+    set->n_filters = n_filters;
+    iir_set_image(coef, n_sections, n_filters, set->image, set->sections, &set->bound);
+    HIP_TRY(upload(set->d_image, set->image.data(), set->image.size(), ctx->stream));
+    HIP_TRY(upload(set->d_sections, set->sections.data(), set->sections.size(), ctx->stream));
+    *out = st->iirs.add(std::move(set));
+    return GRAIL_OK;
+}
+
+int grail_iir_free(grail_ctx *ctx, grail_iir *set)
+{
+    if (!set) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_free: ctx is NULL");
+    if (!own(ctx, &TransformState::iirs, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_free: not a filter set of this context");
+    TransformState *st = peek(ctx);
+    if (st->iir_streams.any([set](const grail_iir_stream &is) { return is.set == set; }))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_free: the set still has open IIR streams");
+    // (a kernel or the upload still queued may be reading it)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st->iirs.remove(set);
+    return GRAIL_OK;
+}
+
+int grail_iir_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                    uint32_t n_rows, const uint32_t *filter_dev, uint32_t tail, float *out_dev, uint64_t out_stride,
+                    uint32_t *out_len_dev, uint32_t *nonfinite_dev)
+{
+    if (!set) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_async: set is NULL");
+    // (without a context the set was not looked up and is not looked into: the call ends at bind_device)
+    if (ctx && !own(ctx, &TransformState::iirs, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_async: not a filter set of this context");
+    // (a row holds fewer than 2^32 samples: len is 32 bits wide)
+    const uint64_t longest = std::min<uint64_t>(row_stride, 0xFFFFFFFFull) + tail;
+    if (const char *why = row_pair_error({rows_dev, row_stride, len_dev, n_rows, out_dev, out_stride}, OutRule::when_out_stride,
+                                         OutRule::when_out_stride, "out_dev overlaps rows_dev (a wave reads ahead of another's stores)",
+                                         longest))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_iir_async: ") + why);
+    int rc = bind_device(ctx, "grail_iir_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (row_stride == 0 && !out_len_dev && !nonfinite_dev) return GRAIL_OK;     // (rows of no samples, and nobody asks)
+    IirArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows, a.filter = filter_dev;
+    a.image = set->d_image.get(), a.sections = set->d_sections.get(), a.n_filters = set->n_filters, a.tail = tail;
+    a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
+    const hipError_t e = launch_iir(a, set->bound, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "iir kernel launch");
     return GRAIL_OK;
 }
 

@@ -90,6 +90,9 @@ EXPORTS = [
     "grail_limit_stream_close",
     "grail_meter_stream_hops", "grail_meter_stream_open", "grail_meter_stream_next_async", "grail_meter_stream_read_async",
     "grail_meter_stream_ledger", "grail_meter_stream_finish_async", "grail_meter_stream_close",
+    "grail_iir_design", "grail_iir_create", "grail_iir_free", "grail_iir_async",
+    "grail_iir_stream_len", "grail_iir_stream_open", "grail_iir_stream_next_async", "grail_iir_stream_finish_async",
+    "grail_iir_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -117,6 +120,10 @@ RESAMPLE_CHUNK = 1024                           # GRAIL_RESAMPLE_CHUNK: one work
 FIR_TAPS_MAX = 4096                             # GRAIL_FIR_TAPS_MAX: the taps of one filter
 FIR_FILTERS_MAX = 64                            # GRAIL_FIR_FILTERS_MAX: the filters of one set
 FIR_CHUNK = 2048                                # GRAIL_FIR_CHUNK: one workgroup's outputs (no number depends on it)
+IIR_SECTIONS_MAX = 8                            # GRAIL_IIR_SECTIONS_MAX: the biquad sections of one recursive filter
+IIR_FILTERS_MAX = 64                            # GRAIL_IIR_FILTERS_MAX: the filters of one set
+# GRAIL_IIR_*: the kinds grail_iir_design knows
+IIR_LOWPASS, IIR_HIGHPASS, IIR_BANDPASS, IIR_NOTCH, IIR_PEAK, IIR_LOWSHELF, IIR_HIGHSHELF = range(7)
 
 
 class GrailError(RuntimeError):
@@ -421,6 +428,15 @@ def load():
     L.grail_meter_stream_ledger.argtypes = [vp, vp, vp, vp]
     L.grail_meter_stream_finish_async.argtypes = [vp, vp, vp, vp]
     L.grail_meter_stream_close.argtypes = [vp, vp]
+    L.grail_iir_design.argtypes = [C.c_int, C.c_uint32, C.c_double, C.c_double, C.c_double, vp]
+    L.grail_iir_create.argtypes = [vp, vp, vp, C.c_uint32, vp]
+    L.grail_iir_free.argtypes = [vp, vp]
+    L.grail_iir_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, C.c_uint32, vp, u64, vp, vp]
+    L.grail_iir_stream_len.argtypes = [u64, u64, C.c_uint32, C.c_int, vp]
+    L.grail_iir_stream_open.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp]
+    L.grail_iir_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
+    L.grail_iir_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp]
+    L.grail_iir_stream_close.argtypes = [vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -824,6 +840,22 @@ def fir_design(sample_rate, lo_hz, hi_hz, n_taps):
     taps = np.zeros(max(int(n_taps), 1), dtype=np.float32)
     _check(load().grail_fir_design(sample_rate, lo_hz, hi_hz, n_taps, taps.ctypes.data))
     return taps
+
+
+def iir_design(kind, sample_rate, f0_hz, q, gain_db=0.0):
+    """grail_iir_design (pure host): float64[5] = b0 b1 b2 a1 a2 of one biquad section of `kind` (IIR_LOWPASS ... IIR_HIGHSHELF)
+    at f0_hz with quality q; gain_db is read by the shelves and the peak."""
+    coef = np.zeros(5, dtype=np.float64)
+    _check(load().grail_iir_design(kind, sample_rate, f0_hz, q, gain_db, coef.ctypes.data))
+    return coef
+
+
+def iir_stream_len(fed_before, n, tail, finishing=False):
+    """grail_iir_stream_len (pure host): the outputs a call on an IIR stream writes for a row that was fed fed_before samples
+    before it: n for a `next` call that feeds n; for `finish` (n must be 0) the tail, or 0 for a row that was fed nothing."""
+    out = C.c_uint64(0)
+    _check(load().grail_iir_stream_len(fed_before, n, tail, 1 if finishing else 0, C.addressof(out)))
+    return out.value
 
 
 def true_peak_limit_gains(true_peak, item_rows, item_gains, ceiling_db, n_rows=None):
@@ -1537,6 +1569,75 @@ class Context:
     def fir_stream_close(self, fs):
         """grail_filter_stream_close: waits for the context's stream, then releases the stream."""
         _check(load().grail_filter_stream_close(self.handle, fs))
+
+    def iir_create(self, filters):
+        """grail_iir_create: a set of recursive filters on this context's device.  filters: a list of float64 arrays [S][5]
+        (or flat [5 S]), the sections b0 b1 b2 a1 a2 of one filter each.  Returns the set's handle, for iir / iir_async /
+        iir_free / iir_stream_open; sets still alive go with the context."""
+        secs = [np.ascontiguousarray(f, dtype=np.float64).reshape(-1) for f in filters]
+        flat = np.concatenate(secs) if secs else np.zeros(0, np.float64)
+        n_sections = np.array([len(f) // 5 for f in secs], dtype=np.uint32)
+        assert all(len(f) % 5 == 0 for f in secs)
+        out = C.c_void_p(None)
+        _check(load().grail_iir_create(self.handle, flat.ctypes.data, n_sections.ctypes.data, len(filters), C.addressof(out)))
+        return out
+
+    def iir_free(self, iir_set):
+        """grail_iir_free: waits for the context's stream, then releases the set (refused while it has open streams)."""
+        _check(load().grail_iir_free(self.handle, iir_set))
+
+    def iir_async(self, iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev, out_stride, out_len_dev=None,
+                  nonfinite_dev=None):
+        """grail_iir_async: the rows filtered into out_dev (must not overlap rows_dev), row u with filter filter_dev[u] of the
+        set (a DEVICE array of uint32; None: filter 0 for every row), ringing out over `tail` outputs past its last sample.
+        Results are DEVICE arrays [n_rows] (either may be None), queued on the context's stream."""
+        _check(load().grail_iir_async(self.handle, iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev,
+                                      out_stride, out_len_dev, nonfinite_dev))
+
+    def iir(self, iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev, out_stride):
+        """iir_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a row whose
+        filter index is outside the set: (LIMIT_REFUSED, 0)."""
+        return _waited(self, n_rows, (np.uint32, np.uint32),
+                       lambda *d: self.iir_async(iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev,
+                                                 out_stride, *d))
+
+    def iir_stream_open(self, iir_set, n_rows, filters=None, tail=0):
+        """grail_iir_stream_open: a stream of n_rows rows filtered recursively call by call, row u bound to filter filters[u]
+        of the set (a host sequence; None: filter 0 for every row), every row ringing out over `tail` outputs at its finish.
+        Returns the stream's handle, for iir_stream_next / _finish / _close."""
+        which = None if filters is None else np.ascontiguousarray(filters, dtype=np.uint32)
+        out = C.c_void_p(None)
+        _check(load().grail_iir_stream_open(self.handle, iir_set, n_rows, None if which is None else which.ctypes.data, tail,
+                                            C.addressof(out)))
+        return out
+
+    def iir_stream_next_async(self, st, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev=None, nonfinite_dev=None):
+        """grail_iir_stream_next_async: every row is fed its next min(in_len_dev[u], in_stride) samples and writes as many
+        outputs to out_dev + u * out_stride.  Results are DEVICE arrays [n_rows] (either may be None)."""
+        _check(load().grail_iir_stream_next_async(self.handle, st, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev,
+                                                  nonfinite_dev))
+
+    def iir_stream_next(self, st, n_rows, in_dev, in_stride, in_len_dev, out_dev, out_stride):
+        """iir_stream_next_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a row
+        that had ended and was fed: (LIMIT_REFUSED, 0)."""
+        return _waited(self, n_rows, (np.uint32, np.uint32),
+                       lambda *d: self.iir_stream_next_async(st, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d))
+
+    def iir_stream_finish(self, st, n_rows, out_dev, out_stride, which=None, out_len_dev=None):
+        """grail_iir_stream_finish_async: the rows marked in which (a host sequence, non-zero = marked; None: every row) that
+        have not ended write their tails and end.  out_len_dev None: waited for, and the tails' lengths (uint32, one per row;
+        0 for rows not marked, ended before or fed nothing) returned."""
+        marks = None if which is None else np.ascontiguousarray(which, dtype=np.uint8)
+        assert marks is None or len(marks) == n_rows
+
+        def finish(out_len):
+            _check(load().grail_iir_stream_finish_async(self.handle, st, None if marks is None else marks.ctypes.data, out_dev,
+                                                       out_stride, out_len))
+        return finish(out_len_dev) if out_len_dev is not None else _waited(self, n_rows, (np.uint32,), finish)[0]
+
+    def iir_stream_close(self, st):
+        """grail_iir_stream_close: waits for the context's stream, then releases the stream."""
+        _check(load().grail_iir_stream_close(self.handle, st))
 
     def resample_stream_open(self, rate_in, rate_out, n_rows):
         """grail_resample_stream_open: a stream of n_rows rows resampled call by call from rate_in to rate_out.  Returns the

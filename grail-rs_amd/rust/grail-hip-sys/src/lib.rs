@@ -143,6 +143,27 @@ pub struct grail_meter_stream {
     _private: [u8; 0],
 }
 
+#[repr(C)]
+pub struct grail_iir {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct grail_iir_stream {
+    _private: [u8; 0],
+}
+
+/// The most biquad sections of one recursive filter and the most filters of one set (`grail_iir_create`).
+pub const GRAIL_IIR_SECTIONS_MAX: u32 = 8;
+pub const GRAIL_IIR_FILTERS_MAX: u32 = 64;
+/// The kinds of section `grail_iir_design` knows.
+pub const GRAIL_IIR_LOWPASS: c_int = 0;
+pub const GRAIL_IIR_HIGHPASS: c_int = 1;
+pub const GRAIL_IIR_BANDPASS: c_int = 2;
+pub const GRAIL_IIR_NOTCH: c_int = 3;
+pub const GRAIL_IIR_PEAK: c_int = 4;
+pub const GRAIL_IIR_LOWSHELF: c_int = 5;
+pub const GRAIL_IIR_HIGHSHELF: c_int = 6;
+
 /// The most taps of one filter and the most filters of one set (`grail_fir_create`).
 pub const GRAIL_FIR_TAPS_MAX: u32 = 4096;
 pub const GRAIL_FIR_FILTERS_MAX: u32 = 64;
@@ -358,6 +379,22 @@ extern "C" {
     pub fn grail_meter_stream_finish_async(ctx: *mut grail_ctx, ms: *mut grail_meter_stream, which: *const u8,
         true_peak_dev: *mut f64) -> c_int;
     pub fn grail_meter_stream_close(ctx: *mut grail_ctx, ms: *mut grail_meter_stream) -> c_int;
+    pub fn grail_iir_design(kind: c_int, sample_rate: u32, f0_hz: f64, q: f64, gain_db: f64, coef: *mut f64) -> c_int;
+    pub fn grail_iir_create(ctx: *mut grail_ctx, coef: *const f64, n_sections: *const u32, n_filters: u32,
+        out: *mut *mut grail_iir) -> c_int;
+    pub fn grail_iir_free(ctx: *mut grail_ctx, set: *mut grail_iir) -> c_int;
+    pub fn grail_iir_async(ctx: *mut grail_ctx, set: *const grail_iir, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, filter_dev: *const u32, tail: u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
+        nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_iir_stream_len(fed_before: u64, n: u64, tail: u32, finishing: c_int, n_out: *mut u64) -> c_int;
+    pub fn grail_iir_stream_open(ctx: *mut grail_ctx, set: *const grail_iir, n_rows: u32, filter: *const u32, tail: u32,
+        out: *mut *mut grail_iir_stream) -> c_int;
+    pub fn grail_iir_stream_next_async(ctx: *mut grail_ctx, is: *mut grail_iir_stream, in_dev: *const f32, in_stride: u64,
+        in_len_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
+        nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_iir_stream_finish_async(ctx: *mut grail_ctx, is: *mut grail_iir_stream, which: *const u8,
+        out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32) -> c_int;
+    pub fn grail_iir_stream_close(ctx: *mut grail_ctx, is: *mut grail_iir_stream) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

@@ -686,6 +686,102 @@ impl Gpu {
         Ok(FirStream { gpu: self, fs, n_rows, tail: set.longest.saturating_sub(1), _set: set })
     }
 
+    /// A set of recursive filters on this device (`grail_iir_create`), for [`Gpu::iir`] and [`Gpu::iir_stream`]: per filter its
+    /// biquad sections `[b0, b1, b2, a1, a2]`, one to eight of them ([`iir_design`] makes one).  Released when dropped.
+    pub fn iir_set(&self, filters: &[Vec<[f64; 5]>]) -> Result<IirSet<'_>, Error> {
+        let coef: Vec<f64> = filters.iter().flat_map(|f| f.iter().flat_map(|s| s.iter().copied())).collect();
+        let n_sections: Vec<u32> = filters.iter().map(|f| f.len() as u32).collect();
+        let mut set: *mut sys::grail_iir = std::ptr::null_mut();
+        check(unsafe { sys::grail_iir_create(self.ctx, coef.as_ptr(), n_sections.as_ptr(), filters.len() as u32, &mut set) })?;
+        Ok(IirSet { gpu: self, set })
+    }
+
+    /// Rows of samples filtered recursively on the device (`grail_iir_async`; the contract is the header's section "levels,
+    /// continued: recursive filtering"), row `i` with filter `which[i]` of the set (`None`: filter 0 for every row).  A row of
+    /// `n` samples gives `n + tail`: the filter rings out on +0.0 input.  Returns the filtered rows and, per row, the count of
+    /// non-finite input samples (they enter as +0.0); a row whose index is outside the set comes back empty.  A filter
+    /// overshoots: limit or measure after filtering.
+    pub fn iir(&self, set: &IirSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, tail: u32) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        let n = rows.len();
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        if n == 0 {
+            return Ok((out, bad));
+        }
+        if which.map_or(false, |w| w.len() != n) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "iir: one filter index per row".to_string() });
+        }
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let out_stride = ((longest + tail as usize + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 6] = [std::ptr::null_mut(); 6];
+            let sizes = [n * stride * 4, n * out_stride * 4, n * 4, n * 4, n * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..6 {
+                if r.is_ok() && (k < 5 || which.is_some()) {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if let (true, Some(w)) = (r.is_ok(), which) {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[5], w.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_iir_async(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
+                                               d[5] as *const u32, tail, d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                               d[4] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 && out_lens[i] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(self.ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad))
+    }
+
+    /// A stream of `n_rows` rows filtered recursively chunk by chunk (`grail_iir_stream_open`; the contract is the header's
+    /// section "levels, continued: recursive filtering of streams"), row `i` bound to filter `which[i]` of the set (`None`:
+    /// filter 0), every row ringing out over `tail` outputs at its finish.  The chunks' outputs put end to end, then the tail of
+    /// [`IirStream::finish`], are the bits [`Gpu::iir`] gives for the whole rows with the same tail.  Closed when dropped; the
+    /// borrow keeps the set alive for as long.
+    pub fn iir_stream<'a>(&'a self, set: &'a IirSet<'a>, n_rows: u32, which: Option<&[u32]>, tail: u32) -> Result<IirStream<'a>, Error> {
+        if which.map_or(false, |w| w.len() != n_rows as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "iir_stream: one filter index per row".to_string() });
+        }
+        let mut is: *mut sys::grail_iir_stream = std::ptr::null_mut();
+        check(unsafe {
+            sys::grail_iir_stream_open(self.ctx, set.set, n_rows, which.map_or(std::ptr::null(), |w| w.as_ptr()), tail, &mut is)
+        })?;
+        Ok(IirStream { gpu: self, is, n_rows, tail, _set: set })
+    }
+
     /// A stream of `n_rows` rows resampled chunk by chunk from `rate_in` to `rate_out` (`grail_resample_stream_open`; the
     /// contract is the header's section "levels, continued: sample-rate conversion of streams").  The chunks' outputs put
     /// end to end, then the tail of [`ResampleStream::finish`], are the bits [`Gpu::resample`] gives for the whole rows.
@@ -1011,6 +1107,124 @@ impl Drop for FirStream<'_> {
     fn drop(&mut self) {
         unsafe {
             sys::grail_filter_stream_close(self.gpu.ctx, self.fs);
+        }
+    }
+}
+
+/// A set of recursive filters resident on a [`Gpu`]'s device ([`Gpu::iir_set`]); `grail_iir_free` when dropped.
+pub struct IirSet<'a> {
+    gpu: &'a Gpu,
+    set: *mut sys::grail_iir,
+}
+
+impl Drop for IirSet<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_iir_free(self.gpu.ctx, self.set);
+        }
+    }
+}
+
+/// Rows filtered recursively chunk by chunk on a [`Gpu`]'s device ([`Gpu::iir_stream`]), their filters' state resident in HBM
+/// between calls; `grail_iir_stream_close` when dropped.
+pub struct IirStream<'a> {
+    gpu: &'a Gpu,
+    is: *mut sys::grail_iir_stream,
+    n_rows: u32,
+    tail: u32,
+    _set: &'a IirSet<'a>,
+}
+
+impl IirStream<'_> {
+    // one call on the stream: `chunks` fed (None: the rows marked in `which` finish); the outputs and the counts per row
+    fn call(&mut self, chunks: Option<&[Vec<f32>]>, which: Option<&[u8]>) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        let n = self.n_rows as usize;
+        let longest = chunks.map_or(0, |c| c.iter().map(|r| r.len()).max().unwrap_or(0));
+        let stride = (longest + 63) / 64 * 64;
+        let out_stride = (longest.max(self.tail as usize) + 63) / 64 * 64;
+        let lens: Vec<u32> = chunks.map_or(vec![0u32; n], |c| c.iter().map(|r| r.len() as u32).collect());
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let sizes = [n * stride.max(1) * 4, n * out_stride.max(1) * 4, n * 4, n * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, sizes[k], &mut d[k]));
+                }
+            }
+            if let Some(c) = chunks {
+                for (i, row) in c.iter().enumerate() {
+                    if r.is_ok() && !row.is_empty() {
+                        r = check(sys::grail_memcpy_h2d(ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                        row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                    }
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_h2d(ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_iir_stream_next_async(ctx, self.is, d[0] as *const f32, stride as u64, d[2] as *const u32,
+                                                               d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
+                                                               d[4] as *mut u32));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_d2h(ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+                }
+            } else if r.is_ok() {
+                r = check(sys::grail_iir_stream_finish_async(ctx, self.is, which.map_or(std::ptr::null(), |w| w.as_ptr()),
+                                                             d[1] as *mut f32, out_stride as u64, d[3] as *mut u32));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 && out_lens[i] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * out_stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad))
+    }
+
+    /// Feeds row `i` the samples `chunks[i]` (an empty chunk: the row pauses) and returns, per row, as many outputs and the
+    /// count of non-finite samples among those fed (`grail_iir_stream_next_async`).  A row that has ended and is fed comes
+    /// back empty, its state untouched.
+    pub fn next(&mut self, chunks: &[Vec<f32>]) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        if chunks.len() != self.n_rows as usize {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "IirStream::next: one chunk per row".to_string() });
+        }
+        self.call(Some(chunks), None)
+    }
+
+    /// Ends the rows marked in `which` (`None`: every row) and returns their tails: what the filter still rings out over the
+    /// stream's `tail` outputs with +0.0 to come (`grail_iir_stream_finish_async`); empty for rows not marked, rows ended
+    /// before and rows that were fed nothing.
+    pub fn finish(&mut self, which: Option<&[bool]>) -> Result<Vec<Vec<f32>>, Error> {
+        if which.map_or(false, |w| w.len() != self.n_rows as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "IirStream::finish: one mark per row".to_string() });
+        }
+        let marks: Option<Vec<u8>> = which.map(|w| w.iter().map(|&m| m as u8).collect());
+        Ok(self.call(None, marks.as_deref())?.0)
+    }
+}
+
+impl Drop for IirStream<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_iir_stream_close(self.gpu.ctx, self.is);
         }
     }
 }
@@ -1466,6 +1680,22 @@ pub fn fir_stream_len(fed_before: u64, n: u64, n_taps: u32, origin: u32, finishi
 /// The most taps of a filter, the most filters of a set (`GRAIL_FIR_TAPS_MAX`, `GRAIL_FIR_FILTERS_MAX`).
 pub const FIR_TAPS_MAX: u32 = sys::GRAIL_FIR_TAPS_MAX;
 pub const FIR_FILTERS_MAX: u32 = sys::GRAIL_FIR_FILTERS_MAX;
+
+/// One biquad section `[b0, b1, b2, a1, a2]` of `kind` (`sys::GRAIL_IIR_LOWPASS` ... `sys::GRAIL_IIR_HIGHSHELF`) at `f0_hz`
+/// with quality `q`; `gain_db` is read by the shelves and the peak (`grail_iir_design`; pure host).
+pub fn iir_design(kind: i32, sample_rate: u32, f0_hz: f64, q: f64, gain_db: f64) -> Result<[f64; 5], Error> {
+    let mut coef = [0f64; 5];
+    check(unsafe { sys::grail_iir_design(kind, sample_rate, f0_hz, q, gain_db, coef.as_mut_ptr()) })?;
+    Ok(coef)
+}
+
+/// The outputs a call on an [`IirStream`] writes for a row that was fed `fed_before` samples before it: a `next` call that
+/// feeds `n` samples, or (`finishing`, `n` = 0) the finish (`grail_iir_stream_len`; pure host).
+pub fn iir_stream_len(fed_before: u64, n: u64, tail: u32, finishing: bool) -> Result<u64, Error> {
+    let mut n_out = 0u64;
+    check(unsafe { sys::grail_iir_stream_len(fed_before, n, tail, finishing as i32, &mut n_out) })?;
+    Ok(n_out)
+}
 
 /// The length of a row of `n` samples filtered: 0 for `n` = 0, else `n + n_taps - 1 - origin` (`grail_fir_len`; pure host).
 pub fn fir_len(n: u64, n_taps: u32, origin: u32) -> Result<u64, Error> {

@@ -1345,6 +1345,135 @@ int grail_meter_stream_finish_async(grail_ctx *ctx, grail_meter_stream *ms, cons
  * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context. */
 int grail_meter_stream_close(grail_ctx *ctx, grail_meter_stream *ms);
 
+/* ---- levels, continued: recursive filtering --------------------------------------------------------------------------------------
+ * What is done to a voice between render and mix is mostly recursive: a high-pass under it, a presence peak, a shelf, a
+ * notch, de-emphasis, a DC blocker, a resonance that rings out.  A FIR of 4 096 taps approximates a 100 Hz high-pass badly
+ * at thousands of operations a sample; a biquad costs nine.  This is the K-weighting recurrence of the loudness section with
+ * the caller's coefficients, and it writes samples.
+ * ARITHMETIC.  All of it IEEE binary64, every operation rounded by itself (no fused multiply-add anywhere), evaluated in
+ * the order written; denormals are not flushed.  The numbers are a pure function of the row's samples, its filter and the
+ * call's tail: not of row_stride, out_stride beyond where it cuts, the row's index, the rows around it, the other filters
+ * of the set, alignment, the device or the launch.  No atomics.
+ * FILTER.  S sections in series, 1 <= S <= GRAIL_IIR_SECTIONS_MAX = 8, each five binary64 numbers b0 b1 b2 a1 a2, all
+ * finite.  Stability is not checked: a filter with poles outside the unit circle overflows, and says so in its output.
+ * SET.  1 <= F <= GRAIL_IIR_FILTERS_MAX = 64 filters, each with its own S.
+ * ROW.  For a row of n = min(len[u], row_stride) samples and the call's `tail`:
+ *   - n_out = 0 when n = 0, otherwise min(n + tail, out_stride).
+ *   - The 2 S states s1[j] = s2[j] = +0.0 at the row's first sample.  For t = 0 .. n_out - 1 in ascending order:
+ *         v = (double)x[t] for t < n, +0.0 for t >= n   (a sample that is not finite is counted once and enters as +0.0)
+ *         for j = 0 .. S - 1 ascending:
+ *             y = b0*v + s1;   s1 = (b1*v - a1*y) + s2;   s2 = b2*v - a2*y;   v = y       (transposed direct form II)
+ *         out[t] = (float)v                             (one rounding; nothing is rounded to binary32 between sections)
+ *   - The result may be infinite or NaN and is not counted; where it is NaN, which NaN is not promised.  Everything else is
+ *     bit-exact.  out between n_out and out_stride is never written.  out_len[u] = n_out; nonfinite[u] is the count over all
+ *     n samples (also where out_stride cut the output short).  Memory between n and row_stride enters no result, whatever it holds.
+ * PER-ROW FILTER.  filter_dev is a device array [n_rows] of indices into the set, NULL means filter 0 for every row, as in
+ * grail_fir_async.  A row whose index is >= F is refused: out_len[u] = GRAIL_LIMIT_REFUSED, nonfinite[u] = 0, its out row
+ * unwritten.
+ * IDENTITY IS NOT A COPY.  b0 = 1 with b1 = b2 = a1 = a2 = 0 gives y = 1*v + s1 with s1 = +0.0 at first: a row's first
+ * -0.0 comes back as +0.0, as with h = [1.0] in FIR filtering (later ones may or may not: 0*v - 0*y can leave -0.0 in the
+ * state).  So a filter of S sections is never computed as eight sections padded with identities, and a
+ * row's result depends neither on the other filters of the set nor on the rows that share its wavefront.
+ * DESIGN.  grail_iir_design returns one section.  With pi = 3.141592653589793, K = tan(pi * f0 / rate), KQ = K / Q,
+ * KK = K * K, D = (1 + KQ) + KK, and for the kinds with a gain G in dB: V = 10^(G / 20) = pow(10, G / 20), W = sqrt(V):
+ *     every kind but a PEAK that cuts:   a1 = 2 * (KK - 1) / D,   a2 = ((1 - KQ) + KK) / D,   and b0 b1 b2 =
+ *     GRAIL_IIR_LOWPASS     KK / D,                       2 * KK / D,             KK / D
+ *     GRAIL_IIR_HIGHPASS    1 / D,                        -2 / D,                 1 / D
+ *     GRAIL_IIR_BANDPASS    KQ / D,                       0,                      -KQ / D             (peak gain 1 at f0)
+ *     GRAIL_IIR_NOTCH       (1 + KK) / D,                 2 * (KK - 1) / D,       (1 + KK) / D
+ *     GRAIL_IIR_HIGHSHELF   ((V + W*KQ) + KK) / D,        2 * (KK - V) / D,       ((V - W*KQ) + KK) / D   (the K-weighting shelf's form)
+ *     GRAIL_IIR_LOWSHELF    ((1 + W*KQ) + V*KK) / D,      2 * (V*KK - 1) / D,     ((1 - W*KQ) + V*KK) / D
+ *     GRAIL_IIR_PEAK, G >= 0, V = 10^(G / 20):  ((1 + V*KQ) + KK) / D,   2 * (KK - 1) / D,   ((1 - V*KQ) + KK) / D
+ *     GRAIL_IIR_PEAK, G < 0, V = 10^(-G / 20), E = (1 + V*KQ) + KK:  numerator and denominator change places,
+ *         b = D / E,  2 * (KK - 1) / E,  ((1 - KQ) + KK) / E;   a1 = 2 * (KK - 1) / E,   a2 = ((1 - V*KQ) + KK) / E
+ * G is read by the shelves and the peak only.  The bits of tan, pow and sqrt are the C library's: the table as
+ * grail_iir_design returns it is the contract, as with grail_kweighting.  A Butterworth low-pass or high-pass of order 2m
+ * is m sections of that kind at the same f0 with Q_k = 1 / (2 cos(pi (2k + 1) / (4m))), k = 0 .. m - 1.
+ * A LONE LONG ROW is one lane's serial work, as in grail_loudness_async: many rows fill the device.  A form parallel in time
+ * is another contract (its order of operations differs) and is not offered.
+ * NOT promised: the output's peak can exceed the input's: limit or measure after filtering, not before. */
+#define GRAIL_IIR_SECTIONS_MAX 8
+#define GRAIL_IIR_FILTERS_MAX 64
+#define GRAIL_IIR_LOWPASS   0
+#define GRAIL_IIR_HIGHPASS  1
+#define GRAIL_IIR_BANDPASS  2
+#define GRAIL_IIR_NOTCH     3
+#define GRAIL_IIR_PEAK      4
+#define GRAIL_IIR_LOWSHELF  5
+#define GRAIL_IIR_HIGHSHELF 6
+typedef struct grail_iir grail_iir; /* a set of recursive filters, its coefficients resident in HBM */
+
+/* Pure host: coef[0 .. 4] = b0 b1 b2 a1 a2 of one section (DESIGN above).  GRAIL_ERR_INVALID_ARG, nothing written: an
+ * unknown kind, sample_rate 0, f0_hz not inside (0, sample_rate / 2), q not a finite number above 0, a gain_db that is not
+ * finite, coef NULL, a section whose five numbers are not all finite (f0 next to half the rate, a gain of thousands of dB). */
+int grail_iir_design(int kind, uint32_t sample_rate, double f0_hz, double q, double gain_db, double coef[5]);
+
+/* A set of n_filters filters on ctx's device: coef holds the sections of filter 0, then of filter 1, and so on, five
+ * doubles each; n_sections [n_filters].  The set keeps its own copy, uploaded on ctx's stream; the arrays may be reused at
+ * once.  GRAIL_ERR_INVALID_ARG, nothing created: a NULL argument, n_filters outside 1 .. 64, an n_sections outside 1 .. 8,
+ * a coefficient that is not finite.  These come first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_iir_create(grail_ctx *ctx, const double *coef, const uint32_t *n_sections, uint32_t n_filters, grail_iir **out);
+/* Releases a set once everything queued on ctx's stream is through; sets still alive at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: a pointer that is not a live set of this context (sets are looked up,
+ * not looked into); a set that still has open streams. */
+int grail_iir_free(grail_ctx *ctx, grail_iir *set);
+/* The filter above, queued on ctx's stream like grail_fir_async: rows_dev: device [n_rows][row_stride]; len_dev: device
+ * [n_rows]; filter_dev: device [n_rows] or NULL; out_dev: device [n_rows][out_stride] (out_stride = 0: the lengths and
+ * counts only).  Results are DEVICE arrays [n_rows], either may be NULL: out_len, nonfinite.  out_dev must not overlap
+ * rows_dev.  16-byte loads and stores where both bases are 16-byte aligned and both strides multiples of 4, 4-byte ones
+ * otherwise: same bits.  One lane filters one row, 64 rows to a wavefront (A LONE LONG ROW above).
+ * GRAIL_ERR_INVALID_ARG, nothing queued: set NULL or of another context; a NULL buffer with samples to read or write;
+ * overlapping ranges; strides that allow a row of 2^32 outputs or more.  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE.  n_rows = 0 is a success that queues nothing. */
+int grail_iir_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev, uint64_t row_stride,
+                    const uint32_t *len_dev, uint32_t n_rows, const uint32_t *filter_dev, uint32_t tail,
+                    float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+
+/* ---- levels, continued: recursive filtering of streams ---------------------------------------------------------------------------
+ * grail_iir_async takes finished rows.  A caller who pulls a live stream chunk by chunk filters chunk by chunk with an IIR
+ * STREAM: n_rows independent rows, each bound to one filter of a live set when the stream is opened, with one `tail` for
+ * all, their state resident in HBM between calls.
+ * THE CONTRACT.  For any split of a row's samples into calls (calls of no samples included), the outputs of the `next`
+ * calls put end to end, followed by the tail that `finish` writes, are bit for bit what grail_iir_async writes for the whole
+ * row with the same tail and an out_stride that cuts nothing; the sum of the calls' nonfinite counts is its count.
+ * STATE.  Per row: N, the samples fed so far (64 bits); whether the row has ended; the 2 S doubles s1[j], s2[j] (room for
+ * the set's largest S).  A `next` call that feeds n samples writes n outputs: there is no delay.  `finish` writes `tail`
+ * outputs on +0.0 input (none for a row that was fed nothing) and ends the row. */
+typedef struct grail_iir_stream grail_iir_stream;
+
+/* Pure host: *n_out = the outputs a call writes for a row that was fed fed_before samples before it: finishing = 0: a
+ * `next` call that feeds n samples (n of them); finishing != 0: `finish` (n must be 0): tail, or 0 when fed_before = 0.
+ * GRAIL_ERR_INVALID_ARG, nothing written: n_out NULL; finishing with n != 0; fed_before + n above 2^63 - 1. */
+int grail_iir_stream_len(uint64_t fed_before, uint64_t n, uint32_t tail, int finishing, uint64_t *n_out);
+/* A stream of n_rows rows on the filters of `set`: filter is a HOST array [n_rows] of indices into the set, NULL means
+ * filter 0 for every row.  GRAIL_ERR_INVALID_ARG, nothing created: ctx or out NULL; a set that is not a live set of this
+ * context; n_rows = 0; an index >= the set's filter count (checked here: a stream has no refused rows of this kind).
+ * These come first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_iir_stream_open(grail_ctx *ctx, const grail_iir *set, uint32_t n_rows, const uint32_t *filter, uint32_t tail,
+                          grail_iir_stream **out);
+/* Feeds every row u its next n = min(in_len_dev[u], in_stride) samples from in_dev + u * in_stride and writes their n
+ * outputs to out_dev + u * out_stride, from index 0; queued on ctx's stream.  Results are DEVICE arrays [n_rows], either
+ * may be NULL: out_len[u] = n; nonfinite[u] = the samples among this call's n that are not finite.  n = 0 is legal (a
+ * paused row).  A row that has ended and is fed n > 0 is refused: out_len = GRAIL_LIMIT_REFUSED, nonfinite 0, nothing
+ * written, its state as it was.  out_dev past out_len is never written.  GRAIL_ERR_INVALID_ARG, nothing queued: a stream
+ * that is not an open stream of this context (looked up, not looked into); a NULL buffer with samples to read or write,
+ * in_len_dev NULL; out_stride < in_stride; overlapping ranges.  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE. */
+int grail_iir_stream_next_async(grail_ctx *ctx, grail_iir_stream *is, const float *in_dev, uint64_t in_stride,
+                                const uint32_t *in_len_dev, float *out_dev, uint64_t out_stride,
+                                uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+/* Rings out the rows marked in which (a HOST array [n_rows] of bytes, non-zero = marked; NULL = every row): a marked row
+ * that has not ended writes its tail to out_dev + u * out_stride and ends.  out_len (device [n_rows], may be NULL): the
+ * tail's length; 0, and nothing written, for unmarked rows, rows that had ended before and rows that were fed nothing.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of this context; out_stride below the
+ * stream's tail; out_dev NULL with a tail to write. */
+int grail_iir_stream_finish_async(grail_ctx *ctx, grail_iir_stream *is, const uint8_t *which, float *out_dev,
+                                  uint64_t out_stride, uint32_t *out_len_dev);
+/* Releases a stream once everything queued on ctx's stream is through; streams still open at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context.  While a set has open streams,
+ * grail_iir_free of it returns GRAIL_ERR_INVALID_ARG and frees nothing. */
+int grail_iir_stream_close(grail_ctx *ctx, grail_iir_stream *is);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
