@@ -7,7 +7,9 @@
 // brings ONE new sample from LDS and issues EIGHT multiply-adds (the resampler reads LDS once per multiply-add: §4.13).
 // No atomics, every store a plain vector store.  DESIGN.md §4.14.  The second half of the file is the same filter on rows fed
 // chunk by chunk (grail_filter_stream_*, §4.15): the same loop over a stretch staged from a row's ring and the call's chunk.
+// The bookkeeping of a chunk, the counts, the state word and the ring are row_kernel_common.h's (§4.21).
 #include "kernels.h"
+#include "row_kernel_common.h"
 
 namespace grail {
 
@@ -26,8 +28,6 @@ constexpr uint32_t FIR_TAPS_PADDED_MAX = 4096;                  // GRAIL_FIR_TAP
 constexpr uint32_t FIR_GROUPS = (FIR_CHUNK + FIR_TAPS_PADDED_MAX) / 8;      // 768: groups of a stretch (6143 samples)
 constexpr uint32_t FIR_PITCH = FIR_GROUPS + 4;                              // 772
 static_assert((4u * FIR_PITCH) % 32u == 16u, "rows r and r + 4 of the image on opposite halves of the banks");
-
-__device__ __forceinline__ bool fir_finite(float x) { return __builtin_fabsf(x) <= 3.4028234663852886e38f; }   // false for NaN and Inf
 
 // the filter of row u, or false: an index outside the set (the row is refused: nothing of it is touched)
 struct FirFilter {
@@ -120,8 +120,9 @@ __global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows
     __shared__ float stage[8 * FIR_PITCH];
     __shared__ uint32_t red[FIR_THREADS / 64];
     const uint32_t tid = threadIdx.x;
-    const uint64_t u = blockIdx.x / grid_chunks;
-    const uint32_t c = (uint32_t)(blockIdx.x - u * grid_chunks);
+    uint64_t u;
+    uint32_t c;
+    chunk_of_block(grid_chunks, u, c);
     if (u >= n_rows) return;
     FirFilter f;
     if (!fir_filter(filter, desc, n_filters, u, f)) return;
@@ -129,15 +130,16 @@ __global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows
     fir_row(len, row_stride, out_stride, u, f, n, n_out);
     const uint64_t m0 = (uint64_t)c * FIR_CHUNK;
     // a row of no samples has no chunk; chunk 0 of any other runs even with no output to write: it counts
-    if (n == 0 || (m0 >= n_out && c != 0u)) return;
-    const bool last = m0 + FIR_CHUNK >= n_out;
-    const uint32_t count = m0 >= n_out ? 0u : (last ? (uint32_t)(n_out - m0) : FIR_CHUNK);
+    if (n == 0 || chunk_idle(m0, n_out, c)) return;
+    bool last;
+    uint32_t count;
+    chunk_extent<FIR_CHUNK>(m0, n_out, last, count);
     const float *row = rows + u * row_stride;
     const uint32_t Kp = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.padded);
     const int64_t t_hi = (int64_t)n - 1;
     // the input samples this chunk counts non-finite ones in
-    const int64_t own_lo = (int64_t)m0 < (int64_t)n ? (int64_t)m0 : (int64_t)n;
-    const int64_t own_hi = last || (int64_t)(m0 + FIR_CHUNK) > (int64_t)n ? (int64_t)n : (int64_t)(m0 + FIR_CHUNK);
+    int64_t own_lo, own_hi;
+    chunk_owned<FIR_CHUNK>(m0, n, last, own_lo, own_hi);
     // the stretch: sample s of it is input time s_base + s; output m0 + r meets, at tap k, sample r + Kp - 1 - k.  The
     // lanes with an output to compute (each owns eight) reach samples 0 .. 8 lanes + Kp - 2.
     const uint32_t lanes = (count + 7u) >> 3;
@@ -173,7 +175,7 @@ __global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows
             for (int e = 0; e < 4; ++e) {
                 const int64_t t = t0 + e;
                 const bool inside = t >= 0 && t <= t_hi;            // (what a clamped load brought is outside)
-                const bool finite = fir_finite(x[e]);
+                const bool finite = finite_f32(x[e]);
                 bad += (inside && !finite && t >= own_lo && t < own_hi) ? 1u : 0u;
                 const int64_t s = t - s_base;
                 if (s >= 0 && s < s_need) stage[((uint32_t)s & 7u) * FIR_PITCH + ((uint32_t)s >> 3)] = (inside && finite) ? x[e] : 0.0f;
@@ -184,7 +186,7 @@ __global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows
     }
     // what the chunk owns past its stretch (an out_stride or an origin that ends the outputs before the samples leaves
     // the last chunk the rest of the row): counted from the row itself
-    for (int64_t t = counted_to + tid; t < own_hi; t += FIR_THREADS) bad += fir_finite(row[t]) ? 0u : 1u;
+    count_owned_tail(row, counted_to, own_hi, tid, bad);
     __syncthreads();
 
     if (tid < lanes) {
@@ -192,12 +194,7 @@ __global__ __launch_bounds__(256) void fir_kernel(const float *__restrict__ rows
         const double *h = taps + (uint32_t)__builtin_amdgcn_readfirstlane((int)f.first);
         fir_outputs<VEC>(stage, tid, count, h, Kp, out + u * out_stride + m0 + 8u * tid);
     }
-    // the chunk's count: integers, so any order
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
-    if ((tid & 63u) == 0u) red[tid >> 6] = bad;
-    __syncthreads();
-    if (tid == 0u) cbad[u * grid_chunks + c] = red[0] + red[1] + red[2] + red[3];
+    block_count_store(bad, red, tid, cbad, u, grid_chunks, c);
 }
 
 // A row's numbers from its chunks, one lane per row; a row whose filter is outside the set is refused here.
@@ -211,28 +208,21 @@ __global__ __launch_bounds__(256) void fir_totals_kernel(const uint32_t *__restr
     if (u >= n_rows) return;
     FirFilter f;
     if (!fir_filter(filter, desc, n_filters, u, f)) {
-        if (out_len) out_len[u] = 0xFFFFFFFFu;
-        if (nonfinite) nonfinite[u] = 0u;
+        refuse_counts(out_len, nonfinite, u);
         return;
     }
     uint64_t n, n_out;
     fir_row(len, row_stride, out_stride, u, f, n, n_out);
-    uint64_t chunks = (n_out + FIR_CHUNK - 1u) / FIR_CHUNK;
-    chunks = n == 0 ? 0u : (chunks ? chunks : 1u);
-    uint32_t b = 0u;
-    for (uint64_t c = 0; c < chunks; ++c) b += cbad[u * grid_chunks + c];
+    const uint32_t b = sum_chunks(cbad, u, grid_chunks, row_chunks<FIR_CHUNK>(n, n_out));
     if (out_len) out_len[u] = (uint32_t)n_out;
     if (nonfinite) nonfinite[u] = b;
 }
 
 // ---- streams (grail_filter_stream_*): rows fed chunk by chunk, DESIGN.md §4.15 ----------------------------------------------
-// A row's state is one 64-bit word, N = the samples fed so far with FIR_STREAM_ENDED set once the row has ended, and a ring
-// of ring_cap samples (a power of two, at least the set's longest K - 1): sample t of the row lies at t mod ring_cap, not
-// finite ones as +0.0.  In the frame of one call, local time = global time - N: the call's output r is the left fold of
+// A row's state is the state word of row_kernel_common.h and nothing else; its ring (there too) holds at least the set's
+// longest K - 1 samples.  In the frame of one call, local time = global time - N: the call's output r is the left fold of
 // h[k] * v[r + d - k] with d = max(0, o - N); v is the ring below 0 (+0.0 before the row's first sample), the call's
 // n samples from 0, +0.0 from n on (which only a finishing call reaches: its n is 0).
-constexpr uint64_t FIR_STREAM_ENDED = 1ull << 63;
-
 struct FirStreamRow {
     uint64_t fed;           // N
     uint32_t n, count, d;   // the samples this call feeds, the outputs it writes, the origin in its frame
@@ -244,8 +234,8 @@ __device__ __forceinline__ FirStreamRow fir_stream_row(const uint64_t *__restric
 {
     FirStreamRow r;
     const uint64_t w = state[u];
-    const bool ended = (w & FIR_STREAM_ENDED) != 0;
-    r.fed = w & ~FIR_STREAM_ENDED;
+    const bool ended = stream_ended(w);
+    r.fed = stream_fed(w);
     r.d = r.fed < f.origin ? f.origin - (uint32_t)r.fed : 0u;
     if (finishing) {
         r.n = 0u;
@@ -279,8 +269,9 @@ __global__ __launch_bounds__(256) void fir_stream_kernel(const float *__restrict
     __shared__ float stage[8 * FIR_PITCH];
     __shared__ uint32_t red[FIR_THREADS / 64];
     const uint32_t tid = threadIdx.x;
-    const uint64_t u = blockIdx.x / grid_chunks;
-    const uint32_t c = (uint32_t)(blockIdx.x - u * grid_chunks);
+    uint64_t u;
+    uint32_t c;
+    chunk_of_block(grid_chunks, u, c);
     if (u >= n_rows) return;
     FirFilter f;
     if (!fir_filter(filter, desc, n_filters, u, f)) return;         // (the indices were checked when the stream was opened)
@@ -289,17 +280,18 @@ __global__ __launch_bounds__(256) void fir_stream_kernel(const float *__restrict
     const uint64_t m0 = (uint64_t)c * FIR_CHUNK;
     // a refused row and one with neither samples nor outputs have no chunk; chunk 0 of any other runs even with no output
     // to write: it counts
-    if (r.refused || (n == 0 && n_out == 0) || (m0 >= n_out && c != 0u)) return;
-    const bool last = m0 + FIR_CHUNK >= n_out;
-    const uint32_t count = m0 >= n_out ? 0u : (last ? (uint32_t)(n_out - m0) : FIR_CHUNK);
+    if (r.refused || (n == 0 && n_out == 0) || chunk_idle(m0, n_out, c)) return;
+    bool last;
+    uint32_t count;
+    chunk_extent<FIR_CHUNK>(m0, n_out, last, count);
     const float *row = in + u * in_stride;                          // (not read when n = 0)
     const float *hist = ring + u * ring_cap;
     const uint64_t ring_mask = ring_cap - 1u;
     const uint32_t Kp = (uint32_t)__builtin_amdgcn_readfirstlane((int)f.padded);
     const int64_t t_hi = (int64_t)n - 1;
     const int64_t t_lo = -(int64_t)(f.taps - 1u < r.fed ? f.taps - 1u : r.fed);   // how far back the taps and the row reach
-    const int64_t own_lo = (int64_t)m0 < (int64_t)n ? (int64_t)m0 : (int64_t)n;
-    const int64_t own_hi = last || (int64_t)(m0 + FIR_CHUNK) > (int64_t)n ? (int64_t)n : (int64_t)(m0 + FIR_CHUNK);
+    int64_t own_lo, own_hi;
+    chunk_owned<FIR_CHUNK>(m0, n, last, own_lo, own_hi);
     // the stretch: sample s of it is local time s_base + s; output m0 + j meets, at tap k, sample j + Kp - 1 - k
     const uint32_t lanes = (count + 7u) >> 3;
     const int64_t s_base = (int64_t)m0 + (int64_t)r.d - (int64_t)(Kp - 1u);
@@ -339,7 +331,7 @@ __global__ __launch_bounds__(256) void fir_stream_kernel(const float *__restrict
                     // the ring holds the last ring_cap >= K - 1 samples fed, already +0.0 where they were not finite
                     if (t >= t_lo) v = hist[(r.fed + (uint64_t)t) & ring_mask];
                 } else if (t <= t_hi) {
-                    const bool finite = fir_finite(x[e]);
+                    const bool finite = finite_f32(x[e]);
                     bad += (!finite && t >= own_lo && t < own_hi) ? 1u : 0u;
                     v = finite ? x[e] : 0.0f;
                 }
@@ -351,23 +343,19 @@ __global__ __launch_bounds__(256) void fir_stream_kernel(const float *__restrict
         counted_to = counted_to < own_lo ? own_lo : counted_to;
     }
     // what the chunk owns past its stretch (a row still short of its origin writes fewer outputs than it is fed)
-    for (int64_t t = counted_to + tid; t < own_hi; t += FIR_THREADS) bad += fir_finite(row[t]) ? 0u : 1u;
+    count_owned_tail(row, counted_to, own_hi, tid, bad);
     __syncthreads();
 
     if (tid < lanes) {
         const double *h = taps + (uint32_t)__builtin_amdgcn_readfirstlane((int)f.first);
         fir_outputs<VEC>(stage, tid, count, h, Kp, out + u * out_stride + m0 + 8u * tid);
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
-    if ((tid & 63u) == 0u) red[tid >> 6] = bad;
-    __syncthreads();
-    if (tid == 0u) cbad[u * grid_chunks + c] = red[0] + red[1] + red[2] + red[3];
+    block_count_store(bad, red, tid, cbad, u, grid_chunks, c);
 }
 
 // Behind fir_stream_kernel on the stream, one wave per row, the only writer of a stream's state: the row's numbers from its
-// chunks, the call's last min(n, ring_cap) samples into the ring at (N + t) mod ring_cap, then N + n (a finishing call: the
-// row ended).  A row that has ended and is fed is refused: 0xFFFFFFFF, 0, its state as it was.
+// chunks, the call's last samples into the ring (ring_keep), then N + n (a finishing call: the row ended).  A row that has
+// ended and is fed is refused (refuse_counts), its state as it was.
 __global__ __launch_bounds__(256) void fir_stream_advance_kernel(const float *__restrict__ in, uint64_t in_stride,
                                                                  const uint32_t *__restrict__ in_len, uint32_t n_rows,
                                                                  const uint32_t *__restrict__ filter, const uint32_t *__restrict__ desc,
@@ -383,30 +371,20 @@ __global__ __launch_bounds__(256) void fir_stream_advance_kernel(const float *__
     if (!fir_filter(filter, desc, n_filters, u, f)) return;
     const FirStreamRow r = fir_stream_row(state, in_len, in_stride, mark, finishing != 0u, u, f);
     if (r.refused) {
-        if (lane == 0u) {
-            if (out_len) out_len[u] = 0xFFFFFFFFu;
-            if (nonfinite) nonfinite[u] = 0u;
-        }
+        if (lane == 0u) refuse_counts(out_len, nonfinite, u);
         return;
     }
     uint32_t bad = 0u;
     if (r.takes && r.n) {
         const uint32_t chunks = r.count ? (r.count + FIR_CHUNK - 1u) / FIR_CHUNK : 1u;
         for (uint32_t c = lane; c < chunks; c += 64u) bad += cbad[u * grid_chunks + c];
-        const float *row = in + u * in_stride;
-        float *hist = ring + u * ring_cap;
-        const uint32_t keep = r.n < ring_cap ? r.n : ring_cap;
-        for (uint32_t t = r.n - keep + lane; t < r.n; t += 64u) {
-            const float x = row[t];
-            hist[(r.fed + t) & (uint64_t)(ring_cap - 1u)] = fir_finite(x) ? x : 0.0f;
-        }
+        ring_keep(in + u * in_stride, r.n, r.fed, ring + u * ring_cap, ring_cap, ring_cap, lane);
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    bad = wave_sum(bad);
     if (lane != 0u) return;
     if (out_len) out_len[u] = r.count;
     if (nonfinite) nonfinite[u] = bad;
-    if (r.takes) state[u] = finishing ? (r.fed | FIR_STREAM_ENDED) : r.fed + r.n;
+    if (r.takes) state[u] = finishing ? (r.fed | STREAM_ENDED) : r.fed + r.n;
 }
 
 }  // namespace
@@ -430,12 +408,8 @@ hipError_t launch_fir(const float *rows, uint64_t row_stride, const uint32_t *le
     if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
                      ((row_stride | out_stride) & 3u) == 0;
-    if (vec)
-        hipLaunchKernelGGL(fir_kernel<true>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, rows, row_stride, len, n_rows,
-                           filter, taps, desc, n_filters, grid_chunks, out, out_stride, cbad);
-    else
-        hipLaunchKernelGGL(fir_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, rows, row_stride, len, n_rows,
-                           filter, taps, desc, n_filters, grid_chunks, out, out_stride, cbad);
+    launch_either(vec, fir_kernel<true>, fir_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, rows, row_stride,
+                  len, n_rows, filter, taps, desc, n_filters, grid_chunks, out, out_stride, cbad);
     return hipGetLastError();
 }
 
@@ -459,14 +433,9 @@ hipError_t launch_fir_stream(const float *in, uint64_t in_stride, const uint32_t
     if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
                      ((in_stride | out_stride) & 3u) == 0;
-    if (vec)
-        hipLaunchKernelGGL(fir_stream_kernel<true>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, in, in_stride, in_len,
-                           n_rows, filter, taps, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u, grid_chunks, out,
-                           out_stride, cbad);
-    else
-        hipLaunchKernelGGL(fir_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, in, in_stride, in_len,
-                           n_rows, filter, taps, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u, grid_chunks, out,
-                           out_stride, cbad);
+    launch_either(vec, fir_stream_kernel<true>, fir_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, in,
+                  in_stride, in_len, n_rows, filter, taps, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u,
+                  grid_chunks, out, out_stride, cbad);
     return hipGetLastError();
 }
 

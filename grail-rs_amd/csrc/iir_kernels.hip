@@ -7,6 +7,7 @@
 #include "kernels.h"
 #include "iir_plan.h"
 #include "loudness_common.h"
+#include "row_kernel_common.h"
 
 #include "../../include/grail_hip.h"
 
@@ -17,8 +18,6 @@ namespace grail {
 using namespace loud;
 
 namespace {
-
-constexpr uint64_t IIR_ENDED = 1ull << 63;
 
 // loud_load of loudness_kernels.hip: wave-instruction i reads samples [t0, t0 + 64) of the rows 4i .. 4i + 3 of the wave,
 // lane l the four samples from 4 (l mod 16) on of row 4i + l / 16: whole 256-byte pieces of rows.  A row past the launch's
@@ -91,7 +90,7 @@ template <uint32_t SB, bool KEEP>
 __device__ __forceinline__ float iir_sample(float xf, bool counted, bool live, uint32_t S, const double (&c)[SB][5],
                                             double (&s1)[SB], double (&s2)[SB], uint32_t &bad)
 {
-    const bool finite = __builtin_fabsf(xf) <= 3.4028234663852886e38f;      // false for NaN and Inf
+    const bool finite = finite_f32(xf);
     bad += (counted && !finite) ? 1u : 0u;
     double v = (counted && finite) ? (double)xf : 0.0;
 #pragma unroll
@@ -133,8 +132,8 @@ __global__ __launch_bounds__(64) void iir_kernel(IirArgs a)
         f = a.filter ? a.filter[u] : 0u;
         if (STREAM) {
             const uint64_t w0 = w[0];
-            const bool ended = (w0 & IIR_ENDED) != 0;
-            fed = w0 & ~IIR_ENDED;
+            const bool ended = stream_ended(w0);
+            fed = stream_fed(w0);
             if (finishing) {
                 takes = !ended && (!a.mark || a.mark[u]);
                 n_out = takes && fed ? a.tail : 0u;
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(64) void iir_kernel(IirArgs a)
             w[1u + 2u * j] = (uint64_t)__double_as_longlong(s1[j]);
             w[2u + 2u * j] = (uint64_t)__double_as_longlong(s2[j]);
         }
-        w[0] = (fed + n) | (finishing ? IIR_ENDED : 0ull);
+        w[0] = (fed + n) | (finishing ? STREAM_ENDED : 0ull);
     }
     if (a.out_len) a.out_len[u] = refused ? GRAIL_LIMIT_REFUSED : (uint32_t)n_out;
     if (a.nonfinite) a.nonfinite[u] = bad;

@@ -113,6 +113,15 @@ struct LenArgs {
     uint32_t max_len;
 };
 
+// Launches `yes` where `flag` holds and `no` otherwise, two instantiations of one kernel template (16-byte against 4-byte
+// accesses, say): a launcher names its kernel's arguments once, whichever variant runs.
+template <typename... Params, typename... Args>
+void launch_either(bool flag, void (*yes)(Params...), void (*no)(Params...), dim3 grid, dim3 block, uint32_t lds, hipStream_t stream,
+                   Args... args)
+{
+    hipLaunchKernelGGL(flag ? yes : no, grid, block, lds, stream, static_cast<Params>(args)...);
+}
+
 // the instantiation the calling thread's last launch_synth started, e.g. "synth_kernel<L=1,T=32,...>"
 const char *last_kernel_name();
 // lanes_per_utt in {1, 2, 4, 8}; returns hipSuccess or the launch error.
@@ -250,53 +259,50 @@ hipError_t launch_fir_totals(const uint32_t *len, uint64_t row_stride, uint32_t 
                              uint32_t n_filters, uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
                              uint32_t *nonfinite, hipStream_t stream);
 
-// FIR filtering of streams (fir_kernels.hip): rows fed call by call.  state: device [n_rows], the samples a row has been fed
-// with bit 63 set once it has ended; ring: device [n_rows][ring_cap], ring_cap a power of two at or above the set's
-// longest n_taps - 1: sample t of a row at t mod ring_cap, +0.0 where it was not finite.  A call launches both kernels, the
-// first reads state and ring and writes out and cbad (one workgroup per (row, chunk of FIR_CHUNK of the call's outputs),
-// grid_chunks: enough for the most outputs a row can have in the call, fir_plan.cpp), the second is the only writer of
-// state and ring.  finishing: in and in_len are not read (no samples are fed), rows with mark[u] != 0 (mark NULL: every
-// row) that have not ended write their tail and end; nonfinite is not written.  filter: device [n_rows], checked by the
-// host.
+// Streams: rows (the limiter: groups of rows) fed call by call.  What every kind keeps, said once in row_kernel_common.h:
+// the state word (the samples fed so far, bit 63 set once the row has ended), word 0 of a row's state, and a ring of ring_cap
+// samples a row, ring_cap a power of two: sample t of a row at t mod ring_cap, +0.0 where it was not finite.  A call launches
+// a chunk kernel that reads state and ring and writes out and the chunks' numbers (grid_chunks of them a row: enough for the
+// most outputs a row can have in the call, *_plan.cpp), then an advance kernel, the only writer of state and ring.  A row
+// that has ended and is fed is refused: 0xFFFFFFFF where its length would stand, 0 non-finite samples, nothing else.
+// finishing: in and in_len are not read (no samples are fed), the rows with mark[u] != 0 (mark NULL: every row) that have
+// not ended write their tail and end; nonfinite is not written.
+//
+// FIR filtering of streams (fir_kernels.hip): state: device [n_rows], the state word; ring: device [n_rows][ring_cap], at or
+// above the set's longest n_taps - 1.  One workgroup per (row, chunk of FIR_CHUNK of the call's outputs).  filter: device
+// [n_rows], checked by the host.
 hipError_t launch_fir_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
                              const double *taps, const uint32_t *desc, uint32_t n_filters, const uint64_t *state, const float *ring,
                              uint32_t ring_cap, const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out,
                              uint64_t out_stride, uint32_t *cbad, hipStream_t stream);
 // ... and a row's out_len and count from its chunks, its last samples into the ring and its state advanced, one wave per
-// row (outputs may be NULL); a row that has ended and is fed: 0xFFFFFFFF and 0, nothing else
+// row (outputs may be NULL)
 hipError_t launch_fir_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
                                      const uint32_t *desc, uint32_t n_filters, uint64_t *state, float *ring, uint32_t ring_cap,
                                      const uint8_t *mark, bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
                                      uint32_t *nonfinite, hipStream_t stream);
 
-// sample-rate conversion of streams (resample_kernels.hip): rows fed call by call, all on one pair of rates.  state: device
-// [n_rows][RESAMPLE_STREAM_STATE_WORDS] = {the samples a row has been fed with bit 63 set once it has ended, the input time
-// floor(M D / U) of its next output M, the phase M D mod U}; ring: device [n_rows][ring_cap], ring_cap a power of two at
-// or above P - 1: sample t of a row at t mod ring_cap, +0.0 where it was not finite.  A call launches both kernels, the
-// first reads state and ring and writes out and cbad (one workgroup per (row, chunk of RESAMPLE_STREAM_CHUNK of the call's
-// outputs), grid_chunks: enough for the most outputs a row can have in the call, resample_plan.cpp), the second is the only
-// writer of state and ring.  finishing: in and in_len are not read (no samples are fed), rows with mark[u] != 0 (mark
-// NULL: every row) that have not ended write their tail and end; nonfinite is not written.
+// sample-rate conversion of streams (resample_kernels.hip): all rows on one pair of rates.  state: device
+// [n_rows][RESAMPLE_STREAM_STATE_WORDS] = {the state word, the input time floor(M D / U) of the row's next output M, the
+// phase M D mod U}; ring: device [n_rows][ring_cap], at or above P - 1.  One workgroup per (row, chunk of
+// RESAMPLE_STREAM_CHUNK of the call's outputs).
 constexpr uint32_t RESAMPLE_STREAM_STATE_WORDS = 3;
 hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D,
                                   uint32_t P, const int32_t *table, const uint64_t *state, const float *ring, uint32_t ring_cap,
                                   const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
                                   uint32_t *cbad, hipStream_t stream);
 // ... and a row's out_len and count from its chunks, its last samples into the ring and its state advanced, one wave per
-// row (outputs may be NULL); a row that has ended and is fed: 0xFFFFFFFF and 0, nothing else
+// row (outputs may be NULL)
 hipError_t launch_resample_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U,
                                           uint32_t D, uint32_t P, uint64_t *state, float *ring, uint32_t ring_cap, const uint8_t *mark,
                                           bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
                                           uint32_t *nonfinite, hipStream_t stream);
 
-// the limiter on streams (limiter_kernels.hip): groups of rows fed call by call, one ceiling and look-ahead for all.  state:
-// device [n_groups], the samples a group's members have been fed with bit 63 set once it has ended; ring: device
-// [n_groups * group][ring_cap], ring_cap a power of two at or above 3 * 2^lookahead_log2 + 19: sample s of a row at s mod
-// ring_cap, +0.0 where it was not finite.  A call launches both kernels, the first only when grid_chunks != 0: one workgroup
-// per (group, chunk of LIMIT_CHUNK of the call's outputs) writes out and the chunk's numbers (limit_chunk_bytes() each) to
-// cstat[group * grid_chunks + c], and reads the state; the advance kernel, queued behind it, alone writes it.  finishing:
-// in, in_len are not read, the groups marked in mark (device [n_groups], or NULL: every group) that have not ended write
-// their tail and end; nonfinite is not written.
+// the limiter on streams (limiter_kernels.hip): groups of rows, one ceiling and look-ahead for all.  state: device
+// [n_groups], the state word of a group's members; ring: device [n_groups * group][ring_cap], at or above
+// 3 * 2^lookahead_log2 + 19.  The chunk kernel only when grid_chunks != 0: one workgroup per (group, chunk of LIMIT_CHUNK
+// of the call's outputs), the chunk's numbers (limit_chunk_bytes() each) to cstat[group * grid_chunks + c].  mark: device
+// [n_groups].
 hipError_t launch_limit_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups, uint32_t group,
                                float ceiling, uint32_t lookahead_log2, const uint64_t *state, const float *ring, uint32_t ring_cap,
                                const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
@@ -311,7 +317,7 @@ hipError_t launch_limit_stream_advance(const float *in, uint64_t in_stride, cons
                                        hipStream_t stream);
 
 // meter streams (meter_stream_kernels.hip): rows metered call by call.  state: DEVICE [n_rows][METER_STREAM_STATE_WORDS] (word 0:
-// samples fed, bit 63: ended; 1 .. 5: s1 .. s4 and acc as their bits; 6: the running true peak; 7: the hops completed), ring:
+// the state word; 1 .. 5: s1 .. s4 and acc as their bits; 6: the running true peak; 7: the hops completed), ring:
 // DEVICE [n_rows][METER_STREAM_RING], ledger: DEVICE [n_rows][max_hops].  A call is three launches in this order: the hops (one
 // lane per row; a feeding call only), the call's true peak (one wave per row and chunk of METER_STREAM_CHUNK output times,
 // grid_chunks of them a row, the chunk's maximum and non-finite count to cmax / cbad [row * grid_chunks + c]), the advance (one
@@ -342,8 +348,7 @@ hipError_t launch_meter_stream_read(const uint64_t *state, uint32_t n_rows, uint
 // NULL (filter 0 for every row).  A row's n_out = min(n + tail, out_stride), 0 for n = 0; out_len, nonfinite: DEVICE
 // [n_rows], may be NULL; a row whose filter index is outside the set: 0xFFFFFFFF and 0, nothing written.
 // state != NULL: a call on a stream, the one kernel with the state read at entry and written at exit.  state: DEVICE
-// [n_rows][1 + 2 * bound] = {the samples a row has been fed with bit 63 set once it has ended, then s1, s2 of each section as
-// their bits}.  Feeding: n = min(len, row_stride) samples in, n out (tail is not read).  finishing: rows and len are not
+// [n_rows][1 + 2 * bound] = {the state word, then s1, s2 of each section as their bits}.  Feeding: n = min(len, row_stride) samples in, n out (tail is not read).  finishing: rows and len are not
 // read, the rows with mark[u] != 0 (mark NULL: every row) that have not ended write tail outputs (none if fed nothing) and
 // end; nonfinite is not written.  A row that has ended and is fed: 0xFFFFFFFF and 0, nothing else.
 struct IirArgs {

@@ -6,8 +6,11 @@
 // out the q it needs (its samples and L - 1 either side) in LDS from the rows themselves.  x -> min(Q, floor(c Q / x)) does
 // not rise with x, so the q of a maximum is the minimum of the q's: the kernel quantises every |v| and e by itself (in
 // binary64, the contract's division) and takes minima of integers from there on, across the twelve outputs and across the
-// members of a group alike.  No atomics, every store a plain vector store.  DESIGN.md §4.12.
+// members of a group alike.  No atomics, every store a plain vector store.  DESIGN.md §4.12.  The passes after the detector
+// are written once for rows and streams (limit_window_sums, limit_gains, limit_wave_fold, limit_chunk_store); the finite test,
+// the state word and the ring are row_kernel_common.h's (§4.21).
 #include "kernels.h"
+#include "row_kernel_common.h"
 #include "true_peak_taps.h"
 
 namespace grail {
@@ -66,7 +69,7 @@ __device__ __forceinline__ void limit_detect(const float *__restrict__ row, int6
 #pragma unroll
     for (int j = 1; j < 16; ++j) {
         const bool inside = r0 + j - lo < hi - lo;
-        const bool finite = __builtin_fabsf(x[j]) <= 3.4028234663852886e38f;            // false for NaN and Inf
+        const bool finite = finite_f32(x[j]);
         // (the lane's own four, and only in the chunk's own samples: a sample is counted once)
         if (j >= 12) bad += (inside && !finite && r0 + j - own_lo < own_hi - own_lo) ? 1u : 0u;
         v[j] = (double)((inside && finite) ? x[j] : 0.0f);
@@ -123,6 +126,104 @@ __device__ __forceinline__ bool limit_group_len(const uint32_t *__restrict__ len
     return same;
 }
 
+// Steps 2 to 4 of a chunk of `count` outputs, alike for a row and for a stream: from the quantised |v| (cells_a) and e (cells_b)
+// of the n_q samples from time a on (the row ends at `end`) to the deficits Q - m of the n_m window minima, summed in blocks of
+// 2^sum_log2; `src` is the array that holds them.  It takes the few uniforms both kernels hold anyway and works out n_m and
+// n_q again: limit_frames_kernel has no scalar register to spare (passing them, or folding the wave inside
+// limit_chunk_store, moved its count).  Every lane of the workgroup comes here (there are barriers inside).
+__device__ __forceinline__ void limit_window_sums(uint32_t *cells_a, uint32_t *cells_b, uint32_t tid, uint32_t count, int64_t a,
+                                                  int64_t end, uint32_t ell, uint32_t *&src, uint32_t &sum_log2)
+{
+    const uint32_t L = 1u << ell, n_m = count + L - 1u, n_q = n_m + L - 1u;
+    uint32_t *dst = cells_b;
+    src = cells_a;
+    // q[s] = min(|v|'s q, the twelve e's q's) inside the row, Q outside (cells_a, in place: a cell has one reader)
+    for (uint32_t i = tid; i < n_q; i += 256u) {
+        uint32_t q = cells_a[i];
+#pragma unroll
+        for (uint32_t k = 0; k <= LIMIT_TAPS_AFTER; ++k) q = cells_b[i + k] < q ? cells_b[i + k] : q;
+        const int64_t s = a + (int64_t)i;
+        cells_a[i] = (s >= 0 && s < end) ? q : LIMIT_Q;
+    }
+    __syncthreads();
+    // 3: the minimum over L = 2^ell by doubling; a window of 2 w exists for n_q - 2 w + 1 starts
+    for (uint32_t w = 1; w < L; w <<= 1) {
+        const uint32_t starts = n_q - 2u * w + 1u;
+        for (uint32_t i = tid; i < starts; i += 256u) dst[i] = src[i] < src[i + w] ? src[i] : src[i + w];
+        __syncthreads();
+        uint32_t *t = src;
+        src = dst;
+        dst = t;
+    }
+    // 4: deficits Q - m, summed by doubling while 32 bits hold them; the apply adds the blocks that are left
+    for (uint32_t i = tid; i < n_m; i += 256u) src[i] = LIMIT_Q - src[i];
+    __syncthreads();
+    sum_log2 = ell < LIMIT_SUM_LOG2 ? ell : LIMIT_SUM_LOG2;
+    for (uint32_t w = 1; w < (1u << sum_log2); w <<= 1) {
+        const uint32_t starts = n_m - 2u * w + 1u;
+        for (uint32_t i = tid; i < starts; i += 256u) dst[i] = src[i] + src[i + w];
+        __syncthreads();
+        uint32_t *t = src;
+        src = dst;
+        dst = t;
+    }
+}
+
+// Step 5's gains of the four outputs from `at` on: S[t] = L Q - the deficits of m[t - L + 1 .. t], the pieces left to add
+__device__ __forceinline__ void limit_gains(const uint32_t *src, bool work, uint32_t at, uint32_t count, uint32_t pieces, uint32_t piece,
+                                            uint64_t full, double scale, float (&g)[4], uint64_t &maxdef, uint32_t &limited)
+{
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        uint64_t def = 0;
+        if (work && at + k < count)
+            for (uint32_t j = 0; j < pieces; ++j) def += src[at + k + j * piece];
+        maxdef = def > maxdef ? def : maxdef;
+        limited += def ? 1u : 0u;
+        g[k] = (float)((double)(full - def) * scale);
+    }
+}
+
+// a chunk's three numbers across a wave: integers, so any order
+__device__ __forceinline__ void limit_wave_fold(uint64_t &maxdef, uint32_t &limited, uint32_t &bad)
+{
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const uint64_t other = __shfl_xor((unsigned long long)maxdef, s, 64);
+        maxdef = other > maxdef ? other : maxdef;
+        limited += (uint32_t)__shfl_xor((int)limited, s, 64);
+        bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    }
+}
+
+// ... and, folded so, across the workgroup's four waves into the chunk's slot; red: LDS.  Every lane comes here (a barrier).
+__device__ __forceinline__ void limit_chunk_store(uint64_t maxdef, uint32_t limited, uint32_t bad, LimitChunk *red, uint32_t wave,
+                                                  uint32_t lane, uint32_t tid, LimitChunk *slot)
+{
+    if (lane == 0u) {
+        red[wave].maxdef = maxdef;
+        red[wave].limited = limited;
+        red[wave].bad = bad;
+    }
+    __syncthreads();
+    if (tid == 0u) {
+        LimitChunk c = red[0];
+        for (int w = 1; w < 4; ++w) {
+            c.maxdef = red[w].maxdef > c.maxdef ? red[w].maxdef : c.maxdef;
+            c.limited += red[w].limited;
+            c.bad += red[w].bad;
+        }
+        *slot = c;
+    }
+}
+
+// the smallest gain of a group from its largest deficit
+__device__ __forceinline__ float limit_min_gain(uint64_t maxdef, uint32_t ell)
+{
+    const uint64_t full = (uint64_t)1 << (24u + ell);
+    return (float)((double)(full - maxdef) * __builtin_ldexp(1.0, -(int)(24u + ell)));
+}
+
 // One workgroup = one (group, chunk of LIMIT_CHUNK samples).  VEC = false is the same mapping with 4-byte loads and
 // stores, for bases that are not 16-byte aligned or strides that are no multiple of 4.
 template <bool VEC>
@@ -170,40 +271,9 @@ __global__ __launch_bounds__(256) void limit_frames_kernel(const float *__restri
     }
     // nothing above the ceiling in reach: every q is Q, every sum L Q and every gain 1.0f; the rest is skipped, same bits
     const bool work = __syncthreads_or(hot ? 1 : 0) != 0;
-    uint32_t *src = cells_a, *dst = cells_b;
+    uint32_t *src = cells_a;
     uint32_t sum_log2 = 0;
-    if (work) {
-        // q[s] = min(|v|'s q, the twelve e's q's) inside the row, Q outside (cells_a, in place: a cell has one reader)
-        for (uint32_t i = tid; i < n_q; i += 256u) {
-            uint32_t q = cells_a[i];
-#pragma unroll
-            for (uint32_t k = 0; k <= LIMIT_TAPS_AFTER; ++k) q = cells_b[i + k] < q ? cells_b[i + k] : q;
-            const int64_t s = a + (int64_t)i;
-            cells_a[i] = (s >= 0 && s < (int64_t)n) ? q : LIMIT_Q;
-        }
-        __syncthreads();
-        // 3: the minimum over L = 2^ell by doubling; a window of 2 w exists for n_q - 2 w + 1 starts
-        for (uint32_t w = 1; w < L; w <<= 1) {
-            const uint32_t starts = n_q - 2u * w + 1u;
-            for (uint32_t i = tid; i < starts; i += 256u) dst[i] = src[i] < src[i + w] ? src[i] : src[i + w];
-            __syncthreads();
-            uint32_t *t = src;
-            src = dst;
-            dst = t;
-        }
-        // 4: deficits Q - m, summed by doubling while 32 bits hold them; the apply adds the blocks that are left
-        for (uint32_t i = tid; i < n_m; i += 256u) src[i] = LIMIT_Q - src[i];
-        __syncthreads();
-        sum_log2 = ell < LIMIT_SUM_LOG2 ? ell : LIMIT_SUM_LOG2;
-        for (uint32_t w = 1; w < (1u << sum_log2); w <<= 1) {
-            const uint32_t starts = n_m - 2u * w + 1u;
-            for (uint32_t i = tid; i < starts; i += 256u) dst[i] = src[i] + src[i + w];
-            __syncthreads();
-            uint32_t *t = src;
-            src = dst;
-            dst = t;
-        }
-    }
+    if (work) limit_window_sums(cells_a, cells_b, tid, count, a, (int64_t)n, ell, src, sum_log2);
     // 5: S[t] = L Q - the deficits of m[t - L + 1 .. t], cells (t - t0) + j 2^sum_log2; g; the product; the clamp
     const uint32_t pieces = L >> sum_log2, piece = 1u << sum_log2;
     const uint64_t full = (uint64_t)L << 24;
@@ -212,15 +282,7 @@ __global__ __launch_bounds__(256) void limit_frames_kernel(const float *__restri
     uint32_t limited = 0u;
     for (uint32_t at = 4u * tid; at < count; at += 1024u) {
         float g[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {
-            uint64_t def = 0;
-            if (work && at + k < count)
-                for (uint32_t j = 0; j < pieces; ++j) def += src[at + k + j * piece];
-            maxdef = def > maxdef ? def : maxdef;
-            limited += def ? 1u : 0u;
-            g[k] = (float)((double)(full - def) * scale);
-        }
+        limit_gains(src, work, at, count, pieces, piece, full, scale, g, maxdef, limited);
         const bool whole = at + 4u <= count;
         for (uint32_t j = 0; j < group; ++j) {
             const float *row = rows + (first_row + j) * row_stride + t0 + at;
@@ -237,7 +299,7 @@ __global__ __launch_bounds__(256) void limit_frames_kernel(const float *__restri
             float z[4];
 #pragma unroll
             for (uint32_t k = 0; k < 4; ++k) {
-                const bool finite = __builtin_fabsf(x[k]) <= 3.4028234663852886e38f;
+                const bool finite = finite_f32(x[k]);
                 float p = g[k] * x[k];
                 p = p < -ceiling ? -ceiling : p;
                 p = p > ceiling ? ceiling : p;
@@ -252,29 +314,8 @@ __global__ __launch_bounds__(256) void limit_frames_kernel(const float *__restri
             }
         }
     }
-    // the chunk's numbers: integers, so any order
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint64_t other = __shfl_xor((unsigned long long)maxdef, s, 64);
-        maxdef = other > maxdef ? other : maxdef;
-        limited += (uint32_t)__shfl_xor((int)limited, s, 64);
-        bad += (uint32_t)__shfl_xor((int)bad, s, 64);
-    }
-    if (lane == 0u) {
-        red[wave].maxdef = maxdef;
-        red[wave].limited = limited;
-        red[wave].bad = bad;
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        LimitChunk c = red[0];
-        for (int w = 1; w < 4; ++w) {
-            c.maxdef = red[w].maxdef > c.maxdef ? red[w].maxdef : c.maxdef;
-            c.limited += red[w].limited;
-            c.bad += red[w].bad;
-        }
-        cstat[(uint64_t)grp * grid_chunks + chunk] = c;
-    }
+    limit_wave_fold(maxdef, limited, bad);
+    limit_chunk_store(maxdef, limited, bad, red, wave, lane, tid, cstat + ((uint64_t)grp * grid_chunks + chunk));
 }
 
 // A group's numbers from its chunks, one lane per group; a refused group says so in all three.
@@ -289,8 +330,7 @@ __global__ __launch_bounds__(256) void limit_totals_kernel(const uint32_t *__res
     uint64_t n;
     if (!limit_group_len(len, row_stride, grp * group, group, n)) {
         if (min_gain) min_gain[grp] = __uint_as_float(0x7FC00000u);
-        if (n_limited) n_limited[grp] = 0xFFFFFFFFu;
-        if (nonfinite) nonfinite[grp] = 0u;
+        refuse_counts(n_limited, nonfinite, grp);
         return;
     }
     const uint64_t chunks = (n + LIMIT_CHUNK - 1u) / LIMIT_CHUNK;
@@ -302,21 +342,17 @@ __global__ __launch_bounds__(256) void limit_totals_kernel(const uint32_t *__res
         limited += s.limited;
         bad += s.bad;
     }
-    const uint64_t full = (uint64_t)1 << (24u + ell);
-    if (min_gain) min_gain[grp] = (float)((double)(full - maxdef) * __builtin_ldexp(1.0, -(int)(24u + ell)));
+    if (min_gain) min_gain[grp] = limit_min_gain(maxdef, ell);
     if (n_limited) n_limited[grp] = limited;
     if (nonfinite) nonfinite[grp] = bad;
 }
 
 // ---- streams (grail_limit_stream_*): groups fed chunk by chunk, DESIGN.md §4.17 ---------------------------------------------
-// A group's state is one 64-bit word, N = the samples fed so far with LIMIT_STREAM_ENDED set once the group has ended; a row's
-// is a ring of ring_cap samples (a power of two, at least 3 L + 19): sample s of the row lies at s mod ring_cap, not finite
-// ones as +0.0.  Times are absolute (counted from the group's first sample): after N samples the outputs below E(N) =
+// A group's state is the state word of row_kernel_common.h, N counting the samples fed to each member; every member row has
+// a ring (there too) of at least 3 L + 19 samples.  Times are absolute (counted from the group's first sample): after N samples the outputs below E(N) =
 // max(0, N - (L + 10)) are final, a call that feeds n writes E(N) .. E(N + n) - 1, a finishing call E(N) .. N - 1.  Either
 // way the outputs are those of the one-shot kernel for a row of N + n samples: the last one a feeding call writes needs
 // q up to N + n - 12 and so samples up to N + n - 1, and a finishing call is the one-shot row's end.
-constexpr uint64_t LIMIT_STREAM_ENDED = 1ull << 63;
-
 struct LimitStreamGroup {
     uint64_t fed, first;    // N; E(N), the first output this call writes
     uint32_t n, count;      // the samples this call feeds each member, the outputs it writes
@@ -328,9 +364,9 @@ __device__ __forceinline__ LimitStreamGroup limit_stream_group(const uint64_t *_
 {
     LimitStreamGroup r;
     const uint64_t w = state[grp];
-    const bool ended = (w & LIMIT_STREAM_ENDED) != 0;
+    const bool ended = (w & STREAM_ENDED) != 0;
     const uint64_t delay = L + 10u;
-    r.fed = w & ~LIMIT_STREAM_ENDED;
+    r.fed = w & ~STREAM_ENDED;
     r.first = r.fed > delay ? r.fed - delay : 0u;
     if (finishing) {
         r.n = 0u;
@@ -358,8 +394,6 @@ __device__ __forceinline__ T limit_in_vgpr(T x)
     asm volatile("" : "+v"(x));
     return x;
 }
-
-__device__ __forceinline__ bool limit_finite(float x) { return __builtin_fabsf(x) <= 3.4028234663852886e38f; }
 
 // limit_detect for a stream (its own copy: limit_frames_kernel pays nothing for it).  Everything is counted from o as there.
 // A sample at r lies in the group when lo <= r < hi; below `split` (= N - o, or 0 when o is past N) it comes from the ring,
@@ -415,7 +449,7 @@ __device__ __forceinline__ void limit_stream_detect(const float *__restrict__ hi
 #pragma unroll
     for (int j = 1; j < 16; ++j) {
         const bool inside = r0 + j - lo < hi - lo;
-        const bool finite = limit_finite(x[j]);
+        const bool finite = finite_f32(x[j]);
         // (the lane's own four, and only among the chunk's share of the call's samples: a sample is counted once; what the
         // ring holds is finite)
         if (j >= 12) bad += (inside && !finite && r0 + j - own_lo < own_hi - own_lo) ? 1u : 0u;
@@ -503,7 +537,7 @@ __global__ __launch_bounds__(256) void limit_stream_kernel(const float *__restri
     if (count == 0u) {
         for (uint32_t j = 0; j < group; ++j) {
             const float *row = in + (first_row + j) * in_stride;
-            for (uint32_t t = own_lo + tid; t < own_hi; t += 256u) bad += limit_finite(row[t]) ? 0u : 1u;
+            for (uint32_t t = own_lo + tid; t < own_hi; t += 256u) bad += finite_f32(row[t]) ? 0u : 1u;
         }
     }
 
@@ -545,40 +579,9 @@ __global__ __launch_bounds__(256) void limit_stream_kernel(const float *__restri
     }
     // nothing above the ceiling in reach: every q is Q, every sum L Q and every gain 1.0f; the rest is skipped, same bits
     const bool work = __syncthreads_or(hot ? 1 : 0) != 0;
-    uint32_t *src = cells_a, *dst = cells_b;
+    uint32_t *src = cells_a;
     uint32_t sum_log2 = 0;
-    if (work) {
-        // q[s] = min(|v|'s q, the twelve e's q's) inside the row, Q outside (cells_a, in place: a cell has one reader)
-        for (uint32_t i = tid; i < n_q; i += 256u) {
-            uint32_t q = cells_a[i];
-#pragma unroll
-            for (uint32_t k = 0; k <= LIMIT_TAPS_AFTER; ++k) q = cells_b[i + k] < q ? cells_b[i + k] : q;
-            const int64_t s = a + (int64_t)i;
-            cells_a[i] = (s >= 0 && s < (int64_t)total) ? q : LIMIT_Q;
-        }
-        __syncthreads();
-        // 3: the minimum over L = 2^ell by doubling; a window of 2 w exists for n_q - 2 w + 1 starts
-        for (uint32_t w = 1; w < L; w <<= 1) {
-            const uint32_t starts = n_q - 2u * w + 1u;
-            for (uint32_t i = tid; i < starts; i += 256u) dst[i] = src[i] < src[i + w] ? src[i] : src[i + w];
-            __syncthreads();
-            uint32_t *t = src;
-            src = dst;
-            dst = t;
-        }
-        // 4: deficits Q - m, summed by doubling while 32 bits hold them; the apply adds the blocks that are left
-        for (uint32_t i = tid; i < n_m; i += 256u) src[i] = LIMIT_Q - src[i];
-        __syncthreads();
-        sum_log2 = ell < LIMIT_SUM_LOG2 ? ell : LIMIT_SUM_LOG2;
-        for (uint32_t w = 1; w < (1u << sum_log2); w <<= 1) {
-            const uint32_t starts = n_m - 2u * w + 1u;
-            for (uint32_t i = tid; i < starts; i += 256u) dst[i] = src[i] + src[i + w];
-            __syncthreads();
-            uint32_t *t = src;
-            src = dst;
-            dst = t;
-        }
-    }
+    if (work) limit_window_sums(cells_a, cells_b, tid, count, a, (int64_t)total, ell, src, sum_log2);
     // 5: S[t], g, the product, the clamp.  Output t0 + i goes to out[m0 + i]: the stores are 16-byte aligned when VEC; the
     // sample itself comes from the ring (already +0.0 where it was not finite: g * +0.0 is the +0.0 the contract writes) or
     // from the call's samples by 4-byte loads, the seam and the outputs' own offset in time being anywhere.
@@ -589,15 +592,7 @@ __global__ __launch_bounds__(256) void limit_stream_kernel(const float *__restri
     uint32_t limited = 0u;
     for (uint32_t at = 4u * tid; at < count; at += 1024u) {
         float g[4];
-#pragma unroll
-        for (uint32_t k = 0; k < 4; ++k) {
-            uint64_t def = 0;
-            if (work && at + k < count)
-                for (uint32_t j = 0; j < pieces; ++j) def += src[at + k + j * piece];
-            maxdef = def > maxdef ? def : maxdef;
-            limited += def ? 1u : 0u;
-            g[k] = (float)((double)(full - def) * scale);
-        }
+        limit_gains(src, work, at, count, pieces, piece, full, scale, g, maxdef, limited);
         const bool whole = at + 4u <= count;
         for (uint32_t j = 0; j < group; ++j) {
             const float *hist = ring + (first_row + j) * ring_cap;
@@ -619,7 +614,7 @@ __global__ __launch_bounds__(256) void limit_stream_kernel(const float *__restri
                 float p = g[k] * x;
                 p = p < -ceiling ? -ceiling : p;
                 p = p > ceiling ? ceiling : p;
-                z[k] = limit_finite(x) ? p : 0.0f;
+                z[k] = finite_f32(x) ? p : 0.0f;
             }
             if (VEC && whole) {
                 *reinterpret_cast<float4 *>(to) = make_float4(z[0], z[1], z[2], z[3]);
@@ -630,34 +625,13 @@ __global__ __launch_bounds__(256) void limit_stream_kernel(const float *__restri
             }
         }
     }
-    // the chunk's numbers: integers, so any order
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint64_t other = __shfl_xor((unsigned long long)maxdef, s, 64);
-        maxdef = other > maxdef ? other : maxdef;
-        limited += (uint32_t)__shfl_xor((int)limited, s, 64);
-        bad += (uint32_t)__shfl_xor((int)bad, s, 64);
-    }
-    if (lane == 0u) {
-        red[wave].maxdef = maxdef;
-        red[wave].limited = limited;
-        red[wave].bad = bad;
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        LimitChunk c = red[0];
-        for (int w = 1; w < 4; ++w) {
-            c.maxdef = red[w].maxdef > c.maxdef ? red[w].maxdef : c.maxdef;
-            c.limited += red[w].limited;
-            c.bad += red[w].bad;
-        }
-        cstat[(uint64_t)grp * grid_chunks + chunk] = c;
-    }
+    limit_wave_fold(maxdef, limited, bad);
+    limit_chunk_store(maxdef, limited, bad, red, wave, lane, tid, cstat + ((uint64_t)grp * grid_chunks + chunk));
 }
 
 // Behind limit_stream_kernel on the stream, one wave per group, the only writer of a stream's state: the group's numbers from
-// its chunks, every member's last min(n, ring_cap) samples of the call into its ring at (N + t) mod ring_cap, then N + n (a
-// finishing call: the group ended).  A refused group: GRAIL_LIMIT_REFUSED, NaN, 0, 0, its state as it was.  No LDS.
+// its chunks, every member's last samples of the call into its ring (ring_keep), then N + n (a finishing call: the group
+// ended).  A refused group: refuse_counts and NaN, 0 beside them, its state as it was.  No LDS.
 __global__ __launch_bounds__(256) void limit_stream_advance_kernel(const float *__restrict__ in, uint64_t in_stride,
                                                                    const uint32_t *__restrict__ in_len, uint32_t n_groups,
                                                                    uint32_t group, uint32_t ell, uint64_t *__restrict__ state,
@@ -673,10 +647,9 @@ __global__ __launch_bounds__(256) void limit_stream_advance_kernel(const float *
     const LimitStreamGroup sg = limit_stream_group(state, in_len, in_stride, mark, finishing != 0u, grp, group, 1u << ell);
     if (sg.refused) {
         if (lane == 0u) {
-            if (out_len) out_len[grp] = 0xFFFFFFFFu;
+            refuse_counts(out_len, nonfinite, grp);
             if (min_gain) min_gain[grp] = __uint_as_float(0x7FC00000u);
             if (n_limited) n_limited[grp] = 0u;
-            if (nonfinite) nonfinite[grp] = 0u;
         }
         return;
     }
@@ -690,30 +663,16 @@ __global__ __launch_bounds__(256) void limit_stream_advance_kernel(const float *
             limited += s.limited;
             bad += s.bad;
         }
-        const uint32_t keep = sg.n < ring_cap ? sg.n : ring_cap;
-        for (uint32_t j = 0; j < group; ++j) {
-            const float *row = in + (grp * group + j) * in_stride;
-            float *hist = ring + (grp * group + j) * ring_cap;
-            for (uint32_t t = sg.n - keep + lane; t < sg.n; t += 64u) {
-                const float x = row[t];
-                hist[(uint32_t)(sg.fed + t) & (ring_cap - 1u)] = limit_finite(x) ? x : 0.0f;
-            }
-        }
+        for (uint32_t j = 0; j < group; ++j)
+            ring_keep(in + (grp * group + j) * in_stride, sg.n, (uint32_t)sg.fed, ring + (grp * group + j) * ring_cap, ring_cap, ring_cap, lane);
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) {
-        const uint64_t other = __shfl_xor((unsigned long long)maxdef, s, 64);
-        maxdef = other > maxdef ? other : maxdef;
-        limited += (uint32_t)__shfl_xor((int)limited, s, 64);
-        bad += (uint32_t)__shfl_xor((int)bad, s, 64);
-    }
+    limit_wave_fold(maxdef, limited, bad);
     if (lane != 0u) return;
-    const uint64_t full = (uint64_t)1 << (24u + ell);
     if (out_len) out_len[grp] = sg.count;
-    if (min_gain) min_gain[grp] = (float)((double)(full - maxdef) * __builtin_ldexp(1.0, -(int)(24u + ell)));
+    if (min_gain) min_gain[grp] = limit_min_gain(maxdef, ell);
     if (n_limited) n_limited[grp] = limited;
     if (nonfinite) nonfinite[grp] = bad;
-    if (sg.takes) state[grp] = finishing ? (sg.fed | LIMIT_STREAM_ENDED) : sg.fed + sg.n;
+    if (sg.takes) state[grp] = finishing ? (sg.fed | STREAM_ENDED) : sg.fed + sg.n;
 }
 
 }  // namespace
@@ -731,12 +690,8 @@ hipError_t launch_limit_frames(const float *rows, uint64_t row_stride, const uin
     if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
                      ((row_stride | out_stride) & 3u) == 0;
-    if (vec)
-        hipLaunchKernelGGL(limit_frames_kernel<true>, dim3((uint32_t)workgroups), dim3(256), 0, stream, rows, row_stride, len,
-                           n_groups, group, ceiling, lookahead_log2, grid_chunks, out, out_stride, (LimitChunk *)cstat);
-    else
-        hipLaunchKernelGGL(limit_frames_kernel<false>, dim3((uint32_t)workgroups), dim3(256), 0, stream, rows, row_stride, len,
-                           n_groups, group, ceiling, lookahead_log2, grid_chunks, out, out_stride, (LimitChunk *)cstat);
+    launch_either(vec, limit_frames_kernel<true>, limit_frames_kernel<false>, dim3((uint32_t)workgroups), dim3(256), 0, stream, rows,
+                  row_stride, len, n_groups, group, ceiling, lookahead_log2, grid_chunks, out, out_stride, (LimitChunk *)cstat);
     return hipGetLastError();
 }
 
@@ -760,14 +715,9 @@ hipError_t launch_limit_stream(const float *in, uint64_t in_stride, const uint32
     if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
     const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
                      ((in_stride | out_stride) & 3u) == 0;
-    if (vec)
-        hipLaunchKernelGGL(limit_stream_kernel<true>, dim3((uint32_t)workgroups), dim3(256), 0, stream, in, in_stride, in_len,
-                           n_groups, group, ceiling, lookahead_log2, state, ring, ring_cap, mark, finishing ? 1u : 0u, grid_chunks,
-                           out, out_stride, (LimitChunk *)cstat);
-    else
-        hipLaunchKernelGGL(limit_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(256), 0, stream, in, in_stride, in_len,
-                           n_groups, group, ceiling, lookahead_log2, state, ring, ring_cap, mark, finishing ? 1u : 0u, grid_chunks,
-                           out, out_stride, (LimitChunk *)cstat);
+    launch_either(vec, limit_stream_kernel<true>, limit_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(256), 0, stream, in,
+                  in_stride, in_len, n_groups, group, ceiling, lookahead_log2, state, ring, ring_cap, mark, finishing ? 1u : 0u,
+                  grid_chunks, out, out_stride, (LimitChunk *)cstat);
     return hipGetLastError();
 }
 

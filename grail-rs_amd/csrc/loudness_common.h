@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "row_kernel_common.h"
+
 #pragma clang fp contract(off)
 
 namespace grail {
@@ -36,7 +38,7 @@ struct KState {
 // one sample through both sections, in the contract's order
 __device__ __forceinline__ void loud_sample(float xf, bool counted, const double (&c)[10], KState &k)
 {
-    const bool finite = __builtin_fabsf(xf) <= 3.4028234663852886e38f;      // false for NaN and Inf
+    const bool finite = finite_f32(xf);
     k.bad += (counted && !finite) ? 1u : 0u;
     const double v = finite ? (double)xf : 0.0;
     const double y = c[0] * v + k.s1;

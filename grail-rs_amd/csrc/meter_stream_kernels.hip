@@ -8,6 +8,7 @@
 // plain vector store.  DESIGN.md §4.18.
 #include "kernels.h"
 #include "loudness_common.h"
+#include "row_kernel_common.h"
 #include "true_peak_taps.h"
 
 #include "../../include/grail_hip.h"
@@ -21,10 +22,9 @@ using namespace loud;
 namespace {
 
 // A row's state: METER_STREAM_STATE_WORDS 64-bit words.  Every double crosses a call as its 64 bits.
-//   0: N, the samples fed so far, bit 63: the row has ended     1 .. 4: s1 .. s4     5: acc (of the hop the next sample lies in)
+//   0: the state word of row_kernel_common.h (N)                1 .. 4: s1 .. s4     5: acc (of the hop the next sample lies in)
 //   6: the running true peak                                    7: the hops completed, floor(N / H)
 // Its ring: METER_STREAM_RING floats, sample s of the row at s mod 16, +0.0 where it was not finite; the last eleven count.
-constexpr uint64_t METER_ENDED = 1ull << 63;
 constexpr uint32_t METER_WORDS = METER_STREAM_STATE_WORDS;
 constexpr uint32_t METER_RING = METER_STREAM_RING;
 constexpr uint32_t METER_TAIL = 11;         // the outputs after a row's last sample: taps - 1
@@ -32,7 +32,6 @@ constexpr uint32_t METER_CHUNK = METER_STREAM_CHUNK;
 
 __device__ __forceinline__ double meter_double(uint64_t w) { return __longlong_as_double((long long)w); }
 __device__ __forceinline__ uint64_t meter_bits(double d) { return (uint64_t)__double_as_longlong(d); }
-__device__ __forceinline__ bool meter_finite(float x) { return __builtin_fabsf(x) <= 3.4028234663852886e38f; }
 
 // What a call does to a row, read alike by the three kernels of the call (the advance kernel, last of them, is the only one
 // that writes what this reads).
@@ -50,8 +49,8 @@ __device__ __forceinline__ MeterRow meter_row(const uint64_t *__restrict__ state
     MeterRow r;
     const uint64_t *w = state + u * METER_WORDS;
     const uint64_t w0 = w[0];
-    const bool ended = (w0 & METER_ENDED) != 0;
-    r.fed = w0 & ~METER_ENDED;
+    const bool ended = stream_ended(w0);
+    r.fed = stream_fed(w0);
     r.hops = w[7];
     r.pos = (uint32_t)(r.fed - r.hops * H);
     if (finishing) {
@@ -290,7 +289,7 @@ __global__ __launch_bounds__(256) void meter_stream_peak_kernel(const float *__r
 #pragma unroll
         for (int j = 1; j < 16; ++j) {
             const int64_t i = i0 - 12 + j;
-            const bool finite = meter_finite(x[j]);
+            const bool finite = finite_f32(x[j]);
             if (j >= 12) bad += (i < n && !finite) ? 1u : 0u;           // (the lane's own four; what the ring holds is finite)
             v[j] = (double)((i < n && finite) ? x[j] : 0.0f);
         }
@@ -341,9 +340,8 @@ __global__ __launch_bounds__(256) void meter_stream_advance_kernel(const float *
     const MeterRow r = meter_row(state, in_len, in_stride, mark, finishing != 0u, u, H, max_hops);
     if (r.refused) {
         if (lane == 0u) {
-            if (n_hops) n_hops[u] = 0xFFFFFFFFu;
+            refuse_counts(n_hops, nonfinite, u);
             if (true_peak) true_peak[u] = meter_double(0x7FF8000000000000ull);
-            if (nonfinite) nonfinite[u] = 0u;
         }
         return;
     }
@@ -362,15 +360,8 @@ __global__ __launch_bounds__(256) void meter_stream_advance_kernel(const float *
         bad += (uint32_t)__shfl_xor((int)bad, d, 64);
     }
     const bool moves = r.takes && (r.n != 0u || finishing != 0u);
-    if (moves && r.n) {
-        const uint32_t keep = r.n < METER_TAIL ? r.n : METER_TAIL;
-        const float *row = in + u * in_stride;
-        float *hist = ring + u * METER_RING;
-        for (uint32_t t = r.n - keep + lane; t < r.n; t += 64u) {
-            const float x = row[t];
-            hist[(uint32_t)(r.fed + t) & (METER_RING - 1u)] = meter_finite(x) ? x : 0.0f;
-        }
-    }
+    if (moves && r.n)
+        ring_keep(in + u * in_stride, r.n, (uint32_t)r.fed, ring + u * METER_RING, METER_RING, METER_TAIL, lane);
     if (lane != 0u) return;
     if (n_hops) n_hops[u] = r.new_hops;
     if (true_peak) true_peak[u] = m;
@@ -379,7 +370,7 @@ __global__ __launch_bounds__(256) void meter_stream_advance_kernel(const float *
         uint64_t *w = state + u * METER_WORDS;
         w[6] = meter_bits(__builtin_fmax(meter_double(w[6]), m));
         w[7] = r.hops + r.new_hops;
-        w[0] = finishing ? (r.fed | METER_ENDED) : r.fed + r.n;
+        w[0] = finishing ? (r.fed | STREAM_ENDED) : r.fed + r.n;
     }
 }
 

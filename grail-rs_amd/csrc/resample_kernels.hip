@@ -7,9 +7,12 @@
 // (27 bits times 24) and nothing comes near the ends of binary64's range, so acc' is 2^26 acc bit for bit at every step,
 // and y = (float)(acc' * 2^-26) is the contract's one rounding.  No atomics, every store a plain vector store.
 // DESIGN.md §4.13.  The same fold on rows fed chunk by chunk (grail_resample_stream_*, §4.16): a stretch staged from a row's
-// ring and the call's samples, the row's place kept as an input time and a phase.
+// ring and the call's samples, the row's place kept as an input time and a phase.  The finite test, the state word, the ring
+// and what the totals and advance kernels do are row_kernel_common.h's; the two chunk kernels keep their bookkeeping in their
+// own text, because any call inside them moved their instruction streams and registers (§4.21).
 #include "kernels.h"
 #include "resample_plan.h"
+#include "row_kernel_common.h"
 
 namespace grail {
 
@@ -19,8 +22,6 @@ constexpr uint32_t RS_THREADS = 256;
 constexpr uint32_t RS_PASSES = RESAMPLE_CHUNK / RS_THREADS;     // outputs per lane
 constexpr uint32_t RS_LDS_MAX = 65536 - 64;                     // bytes of LDS a workgroup may ask for (64 KB less the static words)
 constexpr uint32_t RS_STAGE_SLACK = 8;                          // the stretch starts at a multiple of 4 and ends at one
-
-__device__ __forceinline__ bool rs_finite(float x) { return __builtin_fabsf(x) <= 3.4028234663852886e38f; }   // false for NaN and Inf
 
 // n = min(len, row_stride) and n_out = min(ceil(n U / D), out_stride) of a row (n < 2^32, U < 2^10: no overflow)
 __device__ __forceinline__ void rs_row(const uint32_t *__restrict__ len, uint64_t row_stride, uint64_t out_stride, uint64_t u,
@@ -107,7 +108,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__
             for (int e = 0; e < 4; ++e) {
                 const int64_t t = t0 + e;
                 const bool inside = t >= 0 && t <= t_hi;            // (what a clamped load brought is outside)
-                const bool finite = rs_finite(x[e]);
+                const bool finite = finite_f32(x[e]);
                 bad += (inside && !finite && t >= own_lo && t < own_hi) ? 1u : 0u;
                 stage[4u * gi + e] = (inside && finite) ? x[e] : 0.0f;
             }
@@ -117,7 +118,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__
     }
     // what the chunk owns past its stretch (an out_stride that cuts the row short leaves the last chunk the rest of the
     // row; a chunk that is not staged owns all of its samples here): counted from the row itself
-    for (int64_t t = counted_to + tid; t < own_hi; t += RS_THREADS) bad += rs_finite(row[t]) ? 0u : 1u;
+    for (int64_t t = counted_to + tid; t < own_hi; t += RS_THREADS) bad += finite_f32(row[t]) ? 0u : 1u;
     if (TAB == RS_TAB_LDS && count) {
         for (uint32_t i = tid; i < U * P; i += RS_THREADS) {
             const uint32_t p = i / P;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256) void resample_kernel(const float *__restrict__
                     int64_t tc = t < 0 ? 0 : t;
                     tc = tc > t_hi ? t_hi : tc;
                     const float raw = row[tc];
-                    x = (t >= 0 && t <= t_hi && rs_finite(raw)) ? raw : 0.0f;
+                    x = (t >= 0 && t <= t_hi && finite_f32(raw)) ? raw : 0.0f;
                 }
                 const int32_t num = TAB == RS_TAB_LDS ? ltab[tab[j] + k] : table[tab[j] + k];
                 acc[j] = __builtin_fma((double)num, (double)x, acc[j]);
@@ -194,22 +195,17 @@ __global__ __launch_bounds__(256) void resample_totals_kernel(const uint32_t *__
     if (u >= n_rows) return;
     uint64_t n, n_out;
     rs_row(len, row_stride, out_stride, u, U, D, n, n_out);
-    uint64_t chunks = (n_out + RESAMPLE_CHUNK - 1u) / RESAMPLE_CHUNK;
-    chunks = n == 0 ? 0u : (chunks ? chunks : 1u);
-    uint32_t b = 0u;
-    for (uint64_t c = 0; c < chunks; ++c) b += cbad[u * grid_chunks + c];
+    const uint32_t b = sum_chunks(cbad, u, grid_chunks, row_chunks<RESAMPLE_CHUNK>(n, n_out));
     if (out_len) out_len[u] = (uint32_t)n_out;
     if (nonfinite) nonfinite[u] = b;
 }
 
 // ---- streams (grail_resample_stream_*): rows fed chunk by chunk, DESIGN.md §4.16 ---------------------------------------------
-// A row's state is three 64-bit words: N = the samples fed so far with RS_STREAM_ENDED set once the row has ended; i =
-// floor(M D / U), the input time of the next output M; p = M D mod U, its phase (N U outgrows 64 bits long before N does, so
-// nothing here is computed from N U).  Its ring holds ring_cap samples (a power of two, at least P - 1): sample t of the row
-// lies at t mod ring_cap, not finite ones as +0.0.  In the frame of one call, local time = global time - N: v is the ring
+// A row's state is three 64-bit words: the state word of row_kernel_common.h; i = floor(M D / U), the input time of the next
+// output M; p = M D mod U, its phase (N U outgrows 64 bits long before N does, so nothing here is computed from N U).  Its
+// ring (there too) holds at least P - 1 samples.  In the frame of one call, local time = global time - N: v is the ring
 // below 0 (+0.0 before the row's first sample), the call's n samples from 0, +0.0 from n on (which only a finishing call
 // reaches: its n is 0).  Output r of the call starts at local time (i - N) + (p + r D) div U and phase (p + r D) mod U.
-constexpr uint64_t RS_STREAM_ENDED = 1ull << 63;
 constexpr uint32_t RS_STATE_WORDS = RESAMPLE_STREAM_STATE_WORDS;
 constexpr uint32_t RS_STREAM_PASSES = RESAMPLE_STREAM_CHUNK / RS_THREADS;     // at most four: rs_outputs' NPASS below
 static_assert(RS_STREAM_PASSES >= 1 && RS_STREAM_PASSES <= 4 && RESAMPLE_STREAM_CHUNK % RS_THREADS == 0, "the passes of a chunk");
@@ -225,8 +221,8 @@ __device__ __forceinline__ RsStreamRow rs_stream_row(const uint64_t *__restrict_
 {
     RsStreamRow r;
     const uint64_t w = state[RS_STATE_WORDS * u];
-    const bool ended = (w & RS_STREAM_ENDED) != 0;
-    r.fed = w & ~RS_STREAM_ENDED;
+    const bool ended = (w & STREAM_ENDED) != 0;
+    r.fed = w & ~STREAM_ENDED;
     r.i = state[RS_STATE_WORDS * u + 1u];
     r.p = (uint32_t)state[RS_STATE_WORDS * u + 2u];
     int64_t T;              // the last input time an output of this call may start at
@@ -313,7 +309,7 @@ struct RsStreamTap {
         tc = tc > t_top ? t_top : tc;
         const float raw = row[tc];
         const float old = hist[(fed + (uint64_t)t) & ring_mask];
-        const float cur = (t <= t_hi && rs_finite(raw)) ? raw : 0.0f;
+        const float cur = (t <= t_hi && finite_f32(raw)) ? raw : 0.0f;
         return t < 0 ? (t >= t_lo ? old : 0.0f) : cur;
     }
 };
@@ -401,7 +397,7 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float *__res
             for (int e = 0; e < 4; ++e) {
                 const int64_t t = t0 + e;
                 const bool inside = t >= 0 && t <= t_hi;            // (what a clamped load brought is outside)
-                const bool finite = rs_finite(x[e]);
+                const bool finite = finite_f32(x[e]);
                 bad += (inside && !finite && t >= own_lo && t < own_hi) ? 1u : 0u;
                 const float cur = (inside && finite) ? x[e] : 0.0f;
                 // the ring holds the last ring_cap >= P - 1 samples fed, already +0.0 where they were not finite
@@ -412,7 +408,7 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float *__res
         counted_to = counted_to < own_lo ? own_lo : counted_to;
     }
     // what the chunk owns past its stretch (a chunk that is not staged owns all of its samples here)
-    for (int64_t t = counted_to + tid; t < own_hi; t += RS_THREADS) bad += rs_finite(row[t]) ? 0u : 1u;
+    for (int64_t t = counted_to + tid; t < own_hi; t += RS_THREADS) bad += finite_f32(row[t]) ? 0u : 1u;
     if (TAB == RS_TAB_LDS && count) {
         for (uint32_t i = tid; i < U * P; i += RS_THREADS) {
             const uint32_t p = i / P;
@@ -442,9 +438,8 @@ __global__ __launch_bounds__(256) void resample_stream_kernel(const float *__res
 }
 
 // Behind resample_stream_kernel on the stream, one wave per row, the only writer of a stream's state: the row's numbers
-// from its chunks, the call's last min(n, ring_cap) samples into the ring at (N + t) mod ring_cap, then N + n (a finishing
-// call: the row ended) and the next output's i and p.  A row that has ended and is fed is refused: 0xFFFFFFFF, 0, its state
-// as it was.
+// from its chunks, the call's last samples into the ring (ring_keep), then N + n (a finishing call: the row ended) and the
+// next output's i and p.  A row that has ended and is fed is refused (refuse_counts), its state as it was.
 __global__ __launch_bounds__(256) void resample_stream_advance_kernel(const float *__restrict__ in, uint64_t in_stride,
                                                                       const uint32_t *__restrict__ in_len, uint32_t n_rows, uint32_t U,
                                                                       uint32_t D, uint32_t P, uint64_t *__restrict__ state,
@@ -458,71 +453,42 @@ __global__ __launch_bounds__(256) void resample_stream_advance_kernel(const floa
     if (u >= n_rows) return;
     const RsStreamRow r = rs_stream_row(state, in_len, in_stride, mark, finishing != 0u, u, U, D, P >> 1);
     if (r.refused) {
-        if (lane == 0u) {
-            if (out_len) out_len[u] = 0xFFFFFFFFu;
-            if (nonfinite) nonfinite[u] = 0u;
-        }
+        if (lane == 0u) refuse_counts(out_len, nonfinite, u);
         return;
     }
     uint32_t bad = 0u;
     if (r.takes && r.n) {
         const uint32_t chunks = r.count ? (r.count + RESAMPLE_STREAM_CHUNK - 1u) / RESAMPLE_STREAM_CHUNK : 1u;
         for (uint32_t c = lane; c < chunks; c += 64u) bad += cbad[u * grid_chunks + c];
-        const float *row = in + u * in_stride;
-        float *hist = ring + u * ring_cap;
-        const uint32_t keep = r.n < ring_cap ? r.n : ring_cap;
-        for (uint32_t t = r.n - keep + lane; t < r.n; t += 64u) {
-            const float x = row[t];
-            hist[(r.fed + t) & (uint64_t)(ring_cap - 1u)] = rs_finite(x) ? x : 0.0f;
-        }
+        ring_keep(in + u * in_stride, r.n, r.fed, ring + u * ring_cap, ring_cap, ring_cap, lane);
     }
-#pragma unroll
-    for (int s = 32; s > 0; s >>= 1) bad += (uint32_t)__shfl_xor((int)bad, s, 64);
+    bad = wave_sum(bad);
     if (lane != 0u) return;
     if (out_len) out_len[u] = r.count;
     if (nonfinite) nonfinite[u] = bad;
     if (r.takes) {
         const uint64_t a = (uint64_t)r.p + (uint64_t)r.count * D;  // < 2^10 + 2^32 2^10
-        state[RS_STATE_WORDS * u] = finishing ? (r.fed | RS_STREAM_ENDED) : r.fed + r.n;
+        state[RS_STATE_WORDS * u] = finishing ? (r.fed | STREAM_ENDED) : r.fed + r.n;
         state[RS_STATE_WORDS * u + 1u] = r.i + a / U;
         state[RS_STATE_WORDS * u + 2u] = a % U;
     }
 }
 
+// The instantiation a launch runs, but for VEC (launch_either's to choose): TAB by `tab`, the table in LDS only beside a staged
+// stretch.
 template <bool STAGED, bool VEC>
-void resample_stream_launch(int tab, uint32_t workgroups, uint32_t lds, hipStream_t stream, const float *in, uint64_t in_stride,
-                            const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t P, const int32_t *table,
-                            uint32_t stage_words, uint32_t grid_chunks, const uint64_t *state, const float *ring, uint32_t ring_cap,
-                            const uint8_t *mark, uint32_t finishing, float *out, uint64_t out_stride, uint32_t *cbad)
+auto resample_variant(int tab)
 {
-    if (tab == RS_TAB_UNIFORM)
-        hipLaunchKernelGGL((resample_stream_kernel<STAGED, VEC, RS_TAB_UNIFORM>), dim3(workgroups), dim3(RS_THREADS), lds, stream, in,
-                           in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, finishing,
-                           out, out_stride, cbad);
-    else if (STAGED && tab == RS_TAB_LDS)       // (the table goes to LDS only beside a staged stretch)
-        hipLaunchKernelGGL((resample_stream_kernel<STAGED, VEC, STAGED ? RS_TAB_LDS : RS_TAB_GLOBAL>), dim3(workgroups),
-                           dim3(RS_THREADS), lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks,
-                           state, ring, ring_cap, mark, finishing, out, out_stride, cbad);
-    else
-        hipLaunchKernelGGL((resample_stream_kernel<STAGED, VEC, RS_TAB_GLOBAL>), dim3(workgroups), dim3(RS_THREADS), lds, stream, in,
-                           in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, finishing,
-                           out, out_stride, cbad);
+    return tab == RS_TAB_UNIFORM             ? resample_kernel<STAGED, VEC, RS_TAB_UNIFORM>
+           : (STAGED && tab == RS_TAB_LDS) ? resample_kernel<STAGED, VEC, STAGED ? RS_TAB_LDS : RS_TAB_GLOBAL>
+                                             : resample_kernel<STAGED, VEC, RS_TAB_GLOBAL>;
 }
-
 template <bool STAGED, bool VEC>
-void resample_launch(int tab, uint32_t workgroups, uint32_t lds, hipStream_t stream, const float *rows, uint64_t row_stride,
-                     const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D, uint32_t P, const int32_t *table,
-                     uint32_t stage_words, uint32_t grid_chunks, float *out, uint64_t out_stride, uint32_t *cbad)
+auto resample_stream_variant(int tab)
 {
-    if (tab == RS_TAB_UNIFORM)
-        hipLaunchKernelGGL((resample_kernel<STAGED, VEC, RS_TAB_UNIFORM>), dim3(workgroups), dim3(RS_THREADS), lds, stream, rows,
-                           row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
-    else if (STAGED && tab == RS_TAB_LDS)       // (the table goes to LDS only beside a staged stretch)
-        hipLaunchKernelGGL((resample_kernel<STAGED, VEC, STAGED ? RS_TAB_LDS : RS_TAB_GLOBAL>), dim3(workgroups), dim3(RS_THREADS),
-                           lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
-    else
-        hipLaunchKernelGGL((resample_kernel<STAGED, VEC, RS_TAB_GLOBAL>), dim3(workgroups), dim3(RS_THREADS), lds, stream, rows,
-                           row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    return tab == RS_TAB_UNIFORM             ? resample_stream_kernel<STAGED, VEC, RS_TAB_UNIFORM>
+           : (STAGED && tab == RS_TAB_LDS) ? resample_stream_kernel<STAGED, VEC, STAGED ? RS_TAB_LDS : RS_TAB_GLOBAL>
+                                             : resample_stream_kernel<STAGED, VEC, RS_TAB_GLOBAL>;
 }
 
 }  // namespace
@@ -552,15 +518,10 @@ hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_
     const uint32_t lds = (uint32_t)((staged ? staged_bytes : RESAMPLE_CHUNK * 4u) + (tab == RS_TAB_LDS ? table_bytes : 0u));
     const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
                      ((row_stride | out_stride) & 3u) == 0;
-    const uint32_t wg = (uint32_t)workgroups;
-    if (staged && vec)
-        resample_launch<true, true>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
-    else if (staged)
-        resample_launch<true, false>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
-    else if (vec)
-        resample_launch<false, true>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
-    else
-        resample_launch<false, false>(tab, wg, lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride, cbad);
+    launch_either(vec, staged ? resample_variant<true, true>(tab) : resample_variant<false, true>(tab),
+                  staged ? resample_variant<true, false>(tab) : resample_variant<false, false>(tab), dim3((uint32_t)workgroups),
+                  dim3(RS_THREADS), lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride,
+                  cbad);
     return hipGetLastError();
 }
 
@@ -581,15 +542,10 @@ hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uin
     const uint32_t lds = (uint32_t)((staged ? staged_bytes : RESAMPLE_STREAM_CHUNK * 4u) + (tab == RS_TAB_LDS ? table_bytes : 0u));
     const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
                      ((in_stride | out_stride) & 3u) == 0;
-    const uint32_t wg = (uint32_t)workgroups, fin = finishing ? 1u : 0u;
-    if (staged && vec)
-        resample_stream_launch<true, true>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
-    else if (staged)
-        resample_stream_launch<true, false>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
-    else if (vec)
-        resample_stream_launch<false, true>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
-    else
-        resample_stream_launch<false, false>(tab, wg, lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words, grid_chunks, state, ring, ring_cap, mark, fin, out, out_stride, cbad);
+    launch_either(vec, staged ? resample_stream_variant<true, true>(tab) : resample_stream_variant<false, true>(tab),
+                  staged ? resample_stream_variant<true, false>(tab) : resample_stream_variant<false, false>(tab),
+                  dim3((uint32_t)workgroups), dim3(RS_THREADS), lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words,
+                  grid_chunks, state, ring, ring_cap, mark, finishing ? 1u : 0u, out, out_stride, cbad);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 // wave per (row, chunk of output times), and a lone long row fills the device.  No atomics, every store a plain vector
 // store.  DESIGN.md §4.11.
 #include "kernels.h"
+#include "row_kernel_common.h"
 #include "true_peak_taps.h"
 
 namespace grail {
@@ -62,7 +63,7 @@ __device__ __forceinline__ void true_peak_steps(const float *__restrict__ row, i
 #pragma unroll
         for (int j = 1; j < 16; ++j) {
             const bool inside = r0 + j - lo < hi - lo;
-            const bool finite = __builtin_fabsf(x[i][j]) <= 3.4028234663852886e38f;     // false for NaN and Inf
+            const bool finite = finite_f32(x[i][j]);
             if (j >= 12) bad += (inside && !finite) ? 1u : 0u;                           // (the lane's own four: counted once)
             v[j] = (double)((inside && finite) ? x[i][j] : 0.0f);
         }
