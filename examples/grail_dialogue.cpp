@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--rate R] [--report] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--rate R] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -19,6 +19,8 @@
 // lowpass, highpass, bandpass, notch, peak, lowshelf or highshelf, F0 in Hz, GAIN in dB for peak and the shelves:
 // "--eq highpass:100:0.707 --eq peak:3000:1.5:4" is a high-pass under the voices and a presence peak.  The tracks keep their
 // length (no tail).  A filter overshoots, so with --ceiling the tracks' true peaks are measured after it.
+// --eq-blocked (with --eq) filters them with grail_biquad_blocked_async instead, the form parallel in time that is meant for a few
+// long tracks: the same samples up to the 1024th, within a rounding of the 16-bit scale after it.  The line printed names the call.
 // --rate R resamples the two finished tracks, after the mix and the limiter, from the voices' 44 100 Hz to R Hz on the device
 // (grail::Gpu::resample) and writes the WAV at R; the filter overshoots a little, so the line it prints has the tracks'
 // true peaks at R.
@@ -49,6 +51,7 @@ int main(int argc, char **argv)
     double band_lo = 0.0, band_hi = 0.0;
     uint32_t band_taps = 255;
     EqOption eq_option;
+    bool eq_blocked = false;
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
         else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
@@ -85,6 +88,7 @@ int main(int argc, char **argv)
             band_taps = (uint32_t)k;
             bad_band = bad_band || rest == argv[i] || *rest || argv[i][0] == '-' || k < 3 || k > GRAIL_FIR_TAPS_MAX || k % 2 == 0;
         } else if (!std::strcmp(argv[i], "--eq")) eq_option.take(argc, argv, i);      // (examples/eq_option.h)
+        else if (!std::strcmp(argv[i], "--eq-blocked")) eq_blocked = true;
         else if (!std::strcmp(argv[i], "--limit")) limit = true;
         else if (!std::strcmp(argv[i], "--report")) {
             bad_report = report;        // (named twice)
@@ -95,14 +99,14 @@ int main(int argc, char **argv)
     // (the voices are the generic ones, at 44 100 Hz: a band that ends above their Nyquist frequency is said here, and the
     // sections of --eq are designed: the designer refuses what it cannot make)
     std::vector<double> eq;         // five numbers a section
-    const bool bad_eq = eq_option.bad || !eq_option.design(44100, eq);
+    const bool bad_eq = eq_option.bad || !eq_option.design(44100, eq) || (eq_blocked && eq.empty());
     bad_band = bad_band || (taps_given && !band) || (band && band_hi > 22050.0);
     if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || bad_eq || (capped && !leveled) || (limit && !capped)) {
         std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] "
-                             "[--eq KIND:F0:Q[:GAIN]]... [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
+                             "[--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
                              "needs --ceiling, --band takes 0 <= LO < HI <= 22050 Hz, --taps an odd number from 3 to 4096 and needs "
                              "--band, --eq takes lowpass, highpass, bandpass, notch, peak, lowshelf or highshelf, 0 < F0 < 22050 Hz, Q > 0 and a "
-                             "gain in dB, up to eight times, --rate takes a whole number of Hz, --report takes no value)\n");
+                             "gain in dB, up to eight times, --eq-blocked needs --eq, --rate takes a whole number of Hz, --report takes no value)\n");
         return 2;
     }
     try {
@@ -148,14 +152,14 @@ int main(int argc, char **argv)
             for (uint32_t t = 0; t < n && !rc; ++t)
                 rc = grail_memcpy_h2d(ctx, (float *)d_rows + t * stride, tracks[t].data(), tracks[t].size() * 4);
             if (!rc) rc = grail_memcpy_h2d(ctx, d_len, track_len.data(), n * 4);
-            if (!rc) rc = grail_iir_async(ctx, set, (const float *)d_rows, stride, (const uint32_t *)d_len, n, nullptr, 0, (float *)d_out, stride, nullptr, nullptr);
+            if (!rc) rc = (eq_blocked ? grail_biquad_blocked_async : grail_iir_async)(ctx, set, (const float *)d_rows, stride, (const uint32_t *)d_len, n, nullptr, 0, (float *)d_out, stride, nullptr, nullptr);
             for (uint32_t t = 0; t < n && !rc; ++t)
                 rc = grail_memcpy_d2h(ctx, tracks[t].data(), (const float *)d_out + t * stride, tracks[t].size() * 4);
             for (void *p : {d_rows, d_out, d_len})
                 if (p) grail_device_free(ctx, p);
             const int freed = grail_iir_free(ctx, set);
             grail::check(rc ? rc : freed);
-            std::printf("Equalised, %u section%s:", sections, sections == 1 ? "" : "s");
+            std::printf("Equalised (%s), %u section%s:", eq_blocked ? "grail_biquad_blocked_async" : "grail_iir_async", sections, sections == 1 ? "" : "s");
             std::printf("%s\n", eq_option.text().c_str());
         };
         if (leveled) {          // the same pan as a level: 0.8 and 0.2 of the line at level_db

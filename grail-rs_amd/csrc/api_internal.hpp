@@ -407,6 +407,9 @@ struct grail_iir {
     std::vector<uint32_t> sections;
     grail::host::DeviceBuffer<double> d_image;        // [n_filters][IIR_IMAGE_DOUBLES]
     grail::host::DeviceBuffer<uint32_t> d_sections;   // [n_filters]
+    // the filters' block matrices, made at the set's first grail_biquad_blocked_async (iir_block_image; empty before it)
+    std::vector<double> block_image;
+    grail::host::DeviceBuffer<double> d_block;        // [n_filters][16][16]
 };
 
 // A stream of rows filtered recursively call by call (iir_kernels.hip): iir_stream_state_words(set->bound) state words a row

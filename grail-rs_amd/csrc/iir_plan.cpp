@@ -1,6 +1,7 @@
 // iir_plan.cpp — the host side of recursive filtering that needs no device: grail_iir_design (one biquad by the bilinear
 // transform, the K-weighting's form), grail_iir_stream_len, the checks of a filter set and of the calls on IIR streams (their
-// common end: row_checks.h), the image of a set as the kernels read it, and the length rule.  The contract is
+// common end: row_checks.h), the image of a set as the kernels read it, the length rule, and of the form parallel in time (grail_biquad_blocked_async,
+// §4.22) the block transition matrix (grail_biquad_block_matrix), the grid and the scratch size.  The contract is
 // include/grail_hip.h, "levels, continued: recursive filtering".  No HIP call, so it builds with g++ under AddressSanitizer
 // and UBSan (tests/test_iir_sanitize.py), as fir_plan.cpp does.  DESIGN.md §4.19, §4.20.
 #include <cmath>
@@ -10,9 +11,17 @@
 #include "iir_plan.h"
 #include "row_checks.h"
 
+// the block matrix below is the recurrence itself: every operation rounded by itself under either compiler, whatever its flags
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#elif defined(__GNUC__)
+#pragma GCC optimize("fp-contract=off")
+#endif
+
 namespace grail {
 
 static_assert(IIR_SECTIONS == GRAIL_IIR_SECTIONS_MAX, "the image's pitch is the header's bound");
+static_assert(IIR_BLOCK == GRAIL_BIQUAD_BLOCK, "the block is the header's");
 
 const char *iir_set_error(const double *coef, const uint32_t *n_sections, uint32_t n_filters)
 {
@@ -53,6 +62,55 @@ uint64_t iir_len(uint64_t n, uint32_t tail, uint64_t out_stride)
     return whole < out_stride ? whole : out_stride;
 }
 
+void iir_block_matrix(const double *coef, uint32_t n_sections, double *matrix, uint32_t pitch)
+{
+    for (uint32_t c = 0; c < 2u * n_sections; ++c) {
+        double s1[IIR_SECTIONS] = {}, s2[IIR_SECTIONS] = {};
+        if (c & 1u)
+            s2[c / 2u] = 1.0;
+        else
+            s1[c / 2u] = 1.0;
+        for (uint32_t t = 0; t < IIR_BLOCK; ++t) {
+            double v = 0.0;
+            for (uint32_t j = 0; j < n_sections; ++j) {
+                const double *k = coef + 5u * j;
+                const double y = k[0] * v + s1[j];
+                s1[j] = (k[1] * v - k[3] * y) + s2[j];
+                s2[j] = k[2] * v - k[4] * y;
+                v = y;
+            }
+        }
+        for (uint32_t j = 0; j < n_sections; ++j) {
+            matrix[(size_t)(2u * j) * pitch + c] = s1[j];
+            matrix[(size_t)(2u * j + 1u) * pitch + c] = s2[j];
+        }
+    }
+}
+
+void iir_block_image(const std::vector<double> &image, const std::vector<uint32_t> &sections, std::vector<double> &matrices)
+{
+    matrices.assign(sections.size() * (size_t)IIR_MATRIX_DOUBLES, 0.0);
+    for (size_t f = 0; f < sections.size(); ++f)
+        iir_block_matrix(image.data() + f * IIR_IMAGE_DOUBLES, sections[f], matrices.data() + f * IIR_MATRIX_DOUBLES, IIR_MATRIX_STATES);
+}
+
+uint64_t iir_block_grid_blocks(uint64_t row_stride, uint32_t tail)
+{
+    // (a row holds fewer than 2^32 samples: len is 32 bits wide)
+    const uint64_t most = (row_stride < 0xFFFFFFFFull ? row_stride : 0xFFFFFFFFull) + tail;
+    return most / IIR_BLOCK + (most % IIR_BLOCK != 0u);
+}
+
+uint64_t iir_block_groups(uint64_t grid_blocks) { return grid_blocks / IIR_BLOCK_LANES + (grid_blocks % IIR_BLOCK_LANES != 0u); }
+
+uint64_t iir_block_scratch_doubles(uint32_t n_rows, uint64_t grid_blocks, uint32_t bound)
+{
+    const uint64_t per_block = 2u * bound;
+    if (grid_blocks > UINT64_MAX / per_block) return UINT64_MAX;
+    const uint64_t a_row = grid_blocks * per_block;
+    return n_rows && a_row > UINT64_MAX / n_rows ? UINT64_MAX : a_row * n_rows;
+}
+
 const char *iir_stream_open_error(const uint32_t *filter, uint32_t n_rows, uint32_t n_filters)
 {
     if (n_rows == 0) return "n_rows is 0";
@@ -89,6 +147,15 @@ int grail_iir_stream_len(uint64_t fed_before, uint64_t n, uint32_t tail, int fin
     if (!n_out || (finishing && n) || fed_before > (1ull << 63) - 1u || n > (1ull << 63) - 1u - fed_before)
         return GRAIL_ERR_INVALID_ARG;
     *n_out = finishing ? (fed_before ? tail : 0u) : n;
+    return GRAIL_OK;
+}
+
+int grail_biquad_block_matrix(const double *coef, uint32_t n_sections, double *matrix)
+{
+    if (!coef || !matrix || n_sections < 1 || n_sections > GRAIL_IIR_SECTIONS_MAX) return GRAIL_ERR_INVALID_ARG;
+    for (uint32_t k = 0; k < 5u * n_sections; ++k)
+        if (!std::isfinite(coef[k])) return GRAIL_ERR_INVALID_ARG;
+    grail::iir_block_matrix(coef, n_sections, matrix, 2u * n_sections);
     return GRAIL_OK;
 }
 

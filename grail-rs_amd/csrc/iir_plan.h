@@ -23,6 +23,23 @@ void iir_set_image(const double *coef, const uint32_t *n_sections, uint32_t n_fi
 // n_out of a row of n samples: 0 for n = 0, else min(n + tail, out_stride)
 uint64_t iir_len(uint64_t n, uint32_t tail, uint64_t out_stride);
 
+// The form parallel in time (grail_biquad_blocked_async, biquad_block_kernels.hip).  A row's steps are cut into
+// blocks of IIR_BLOCK; IIR_BLOCK_LANES consecutive blocks of one row make a workgroup of one wave.
+constexpr uint32_t IIR_BLOCK = 1024;        // == GRAIL_BIQUAD_BLOCK
+constexpr uint32_t IIR_BLOCK_LANES = 64;
+constexpr uint32_t IIR_MATRIX_STATES = 2 * IIR_SECTIONS;
+constexpr uint32_t IIR_MATRIX_DOUBLES = IIR_MATRIX_STATES * IIR_MATRIX_STATES;     // one filter of a set's matrix image
+// T of one checked filter of S sections (coef [5 S]): matrix[i * pitch + c] = state i (s1[0] s2[0] s1[1] ...) after IIR_BLOCK
+// steps of the recurrence on +0.0 from the state that is 1.0 in place c, for i, c < 2 S; nothing else of matrix is written
+void iir_block_matrix(const double *coef, uint32_t n_sections, double *matrix, uint32_t pitch);
+// the matrices of a set as the propagate kernel reads them: [n_filters][16][16], +0.0 past a filter's own 2 S
+void iir_block_image(const std::vector<double> &image, const std::vector<uint32_t> &sections, std::vector<double> &matrices);
+// G: the blocks a row of the call can have, ceil((min(row_stride, 2^32 - 1) + tail) / IIR_BLOCK); the grid's workgroups a row,
+// ceil(G / 64); the doubles of scratch, n_rows * G * 2 * bound (UINT64_MAX where that is past 64 bits)
+uint64_t iir_block_grid_blocks(uint64_t row_stride, uint32_t tail);
+uint64_t iir_block_groups(uint64_t grid_blocks);
+uint64_t iir_block_scratch_doubles(uint32_t n_rows, uint64_t grid_blocks, uint32_t bound);
+
 // Streams (grail_iir_stream_*).  NULL when filter (host [n_rows], or NULL = filter 0) binds n_rows >= 1 rows to filters of
 // a set of n_filters
 const char *iir_stream_open_error(const uint32_t *filter, uint32_t n_rows, uint32_t n_filters);

@@ -371,4 +371,36 @@ struct IirArgs {
 };
 hipError_t launch_iir(const IirArgs &args, uint32_t bound, hipStream_t stream);
 
+// recursive filtering parallel in time (biquad_block_kernels.hip; the contract is grail_hip.h's "recursive filtering, parallel
+// in time"): a row's steps in blocks of IIR_BLOCK, one lane per (row, block), 64 consecutive blocks of a row
+// to a workgroup of one wave, `groups` = iir_block_groups(grid_blocks) workgroups a row.  rows .. out_stride as in IirArgs;
+// matrices: DEVICE [n_filters][16][16], iir_block_image's; state: DEVICE [n_rows][grid_blocks][2 * bound] doubles: slot k of a
+// row holds z_k after the rest pass and e_{k+1} after the propagate; cbad: DEVICE [n_rows][groups], the non-finite samples
+// the output pass's workgroups read.  Slots and counts past a row's own blocks are left as they were and read by nobody.
+struct BiquadBlockArgs {
+    const float *rows;
+    uint64_t row_stride;
+    const uint32_t *len;
+    uint32_t n_rows;
+    const uint32_t *filter;
+    const double *image;
+    const uint32_t *sections;
+    const double *matrices;
+    uint32_t n_filters;
+    uint32_t tail;
+    float *out;
+    uint64_t out_stride;
+    double *state;
+    uint32_t *cbad;
+    uint32_t grid_blocks;
+    uint32_t groups;
+};
+// the rest pass (z_k of every block but a row's last), the propagate (one wave a row: the call's serial chain) and the output
+// pass, in this order on one stream; n_rows * groups is at most 2^31 - 1
+hipError_t launch_biquad_block_rest(const BiquadBlockArgs &args, uint32_t bound, hipStream_t stream);
+hipError_t launch_biquad_block_propagate(const BiquadBlockArgs &args, uint32_t bound, hipStream_t stream);
+hipError_t launch_biquad_block_output(const BiquadBlockArgs &args, uint32_t bound, hipStream_t stream);
+// ... and a row's out_len and count from cbad, one lane per row (outputs may be NULL); a refused row: 0xFFFFFFFF and 0
+hipError_t launch_biquad_block_totals(const BiquadBlockArgs &args, uint32_t *out_len, uint32_t *nonfinite, hipStream_t stream);
+
 }  // namespace grail

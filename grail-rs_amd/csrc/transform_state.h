@@ -42,7 +42,8 @@ struct ResampleTable {
 // size), freed by grail_destroy: the chunk numbers that a limiter call folds (16 B per group and chunk of 4096 samples), the
 // chunks' non-finite counts that a resampling call folds (4 B per chunk of 1024 outputs), the resampler's tables of the
 // last few pairs of rates, the same counts of a filtering call (4 B per chunk of 2048 outputs), the filter sets the caller
-// has created and the streams open (each with its rows' state: api_internal.hpp, ChunkedStream).  A stream's calls use the
+// has created, the block states (16 B per section of the set's bound and block of 1024 steps) and counts of a blocked
+// recursive-filtering call, and the streams open (each with its rows' state: api_internal.hpp, ChunkedStream).  A stream's calls use the
 // chunk scratch of their kind.
 struct TransformState : CtxPart {
     DeviceBuffer<unsigned char> d_lstat;    // limiter chunks
@@ -57,6 +58,8 @@ struct TransformState : CtxPart {
     DeviceBuffer<double> d_mpeak;           // meter stream chunks (4096 output times each): the largest |y|
     DeviceBuffer<uint32_t> d_mbad;          // ... and the non-finite counts
     Owned<grail_meter_stream> meter_streams;        // the meter streams open
+    DeviceBuffer<double> d_iirblock;        // blocked recursive filtering: 2 S' doubles of state a block (iir_plan.h)
+    DeviceBuffer<uint32_t> d_iirbad;        // ... and the non-finite counts of its output pass's workgroups
     Owned<grail_iir> iirs;                  // the recursive filter sets alive
     Owned<grail_iir_stream> iir_streams;    // ... and, after them (they die first), the IIR streams open on them
 };

@@ -1,7 +1,8 @@
 // transforms.cpp — the calls that read finished rows and write rows, at once: grail_limit_async (limiter_kernels.hip, DESIGN.md
 // §4.12), grail_resample_async (resample_kernels.hip, the ratio and table resample_plan.cpp, §4.13) and grail_fir_create /
 // _free / _async (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_iir_create / _free / _async
-// (iir_kernels.hip, a set's checks and image iir_plan.cpp, §4.19): their checks, their scratch, their launches.
+// (iir_kernels.hip, a set's checks and image iir_plan.cpp, §4.19) and grail_biquad_blocked_async (biquad_block_kernels.hip, its
+// matrices, grid and scratch size iir_plan.cpp, §4.22): their checks, their scratch, their launches.
 // What they check of a pair of rows is row_checks.h.  The same chunk by chunk, on streams, is transform_streams.cpp; what a
 // context keeps for both is transform_state.h.
 #include "row_checks.h"
@@ -247,6 +248,61 @@ int grail_iir_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev,
     a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     const hipError_t e = launch_iir(a, set->bound, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "iir kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_biquad_blocked_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                            uint32_t n_rows, const uint32_t *filter_dev, uint32_t tail, float *out_dev, uint64_t out_stride,
+                            uint32_t *out_len_dev, uint32_t *nonfinite_dev)
+{
+    if (!set) return fail(GRAIL_ERR_INVALID_ARG, "grail_biquad_blocked_async: set is NULL");
+    // (without a context the set was not looked up and is not looked into: the call ends at bind_device)
+    grail_iir *mine = ctx ? own(ctx, &TransformState::iirs, set) : nullptr;
+    if (ctx && !mine) return fail(GRAIL_ERR_INVALID_ARG, "grail_biquad_blocked_async: not a filter set of this context");
+    // (a row holds fewer than 2^32 samples: len is 32 bits wide)
+    const uint64_t longest = std::min<uint64_t>(row_stride, 0xFFFFFFFFull) + tail;
+    if (const char *why = row_pair_error({rows_dev, row_stride, len_dev, n_rows, out_dev, out_stride}, OutRule::when_out_stride,
+                                         OutRule::when_out_stride, "out_dev overlaps rows_dev (a wave reads ahead of another's stores)",
+                                         longest))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_biquad_blocked_async: ") + why);
+    const uint64_t blocks = n_rows && row_stride ? iir_block_grid_blocks(row_stride, tail) : 0;
+    const uint64_t groups = iir_block_groups(blocks);
+    if ((uint64_t)n_rows * groups > 0x7FFFFFFFull)
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_biquad_blocked_async: more than 2^31 workgroups");
+    int rc = bind_device(ctx, "grail_biquad_blocked_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (row_stride == 0 && !out_len_dev && !nonfinite_dev) return GRAIL_OK;     // (rows of no samples, and nobody asks)
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    BiquadBlockArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows, a.filter = filter_dev;
+    a.image = mine->d_image.get(), a.sections = mine->d_sections.get(), a.n_filters = mine->n_filters, a.tail = tail;
+    a.out = out_dev, a.out_stride = out_stride, a.grid_blocks = (uint32_t)blocks, a.groups = (uint32_t)groups;
+    if (blocks) {               // (rows of no samples: 0, 0 from the totals alone)
+        if (!mine->d_block.get()) {
+            iir_block_image(mine->image, mine->sections, mine->block_image);
+            const hipError_t up = upload(mine->d_block, mine->block_image.data(), mine->block_image.size(), ctx->stream);
+            if (up != hipSuccess) {     // (a later call starts over, not from an image that was never copied)
+                mine->d_block.reset();
+                return hip_fail(up, "block matrices upload");
+            }
+        }
+        const uint64_t doubles = iir_block_scratch_doubles(n_rows, blocks, mine->bound);
+        if (doubles > SIZE_MAX / sizeof(double)) return fail(GRAIL_ERR_OUT_OF_MEMORY, "grail_biquad_blocked_async: block states");
+        if ((rc = st->d_iirblock.reserve(ctx->stream, (size_t)doubles))) return rc;
+        if ((rc = st->d_iirbad.reserve(ctx->stream, (size_t)n_rows * (size_t)groups))) return rc;
+        a.matrices = mine->d_block.get(), a.state = st->d_iirblock.get(), a.cbad = st->d_iirbad.get();
+        hipError_t e = launch_biquad_block_rest(a, mine->bound, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "biquad block rest kernel launch");
+        if ((e = launch_biquad_block_propagate(a, mine->bound, ctx->stream)) != hipSuccess)
+            return hip_fail(e, "biquad block propagate kernel launch");
+        if ((e = launch_biquad_block_output(a, mine->bound, ctx->stream)) != hipSuccess)
+            return hip_fail(e, "biquad block output kernel launch");
+    }
+    if (!out_len_dev && !nonfinite_dev) return GRAIL_OK;
+    const hipError_t e = launch_biquad_block_totals(a, out_len_dev, nonfinite_dev, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "biquad block totals kernel launch");
     return GRAIL_OK;
 }
 

@@ -91,6 +91,7 @@ EXPORTS = [
     "grail_meter_stream_hops", "grail_meter_stream_open", "grail_meter_stream_next_async", "grail_meter_stream_read_async",
     "grail_meter_stream_ledger", "grail_meter_stream_finish_async", "grail_meter_stream_close",
     "grail_iir_design", "grail_iir_create", "grail_iir_free", "grail_iir_async",
+    "grail_biquad_blocked_async", "grail_biquad_block_matrix",
     "grail_iir_stream_len", "grail_iir_stream_open", "grail_iir_stream_next_async", "grail_iir_stream_finish_async",
     "grail_iir_stream_close",
 ]
@@ -122,6 +123,7 @@ FIR_FILTERS_MAX = 64                            # GRAIL_FIR_FILTERS_MAX: the fil
 FIR_CHUNK = 2048                                # GRAIL_FIR_CHUNK: one workgroup's outputs (no number depends on it)
 IIR_SECTIONS_MAX = 8                            # GRAIL_IIR_SECTIONS_MAX: the biquad sections of one recursive filter
 IIR_FILTERS_MAX = 64                            # GRAIL_IIR_FILTERS_MAX: the filters of one set
+IIR_BLOCK = 1024                                # GRAIL_BIQUAD_BLOCK: the steps of a block of grail_biquad_blocked_async
 # GRAIL_IIR_*: the kinds grail_iir_design knows
 IIR_LOWPASS, IIR_HIGHPASS, IIR_BANDPASS, IIR_NOTCH, IIR_PEAK, IIR_LOWSHELF, IIR_HIGHSHELF = range(7)
 
@@ -432,6 +434,8 @@ def load():
     L.grail_iir_create.argtypes = [vp, vp, vp, C.c_uint32, vp]
     L.grail_iir_free.argtypes = [vp, vp]
     L.grail_iir_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, C.c_uint32, vp, u64, vp, vp]
+    L.grail_biquad_blocked_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, C.c_uint32, vp, u64, vp, vp]
+    L.grail_biquad_block_matrix.argtypes = [vp, C.c_uint32, vp]
     L.grail_iir_stream_len.argtypes = [u64, u64, C.c_uint32, C.c_int, vp]
     L.grail_iir_stream_open.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp]
     L.grail_iir_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
@@ -848,6 +852,17 @@ def iir_design(kind, sample_rate, f0_hz, q, gain_db=0.0):
     coef = np.zeros(5, dtype=np.float64)
     _check(load().grail_iir_design(kind, sample_rate, f0_hz, q, gain_db, coef.ctypes.data))
     return coef
+
+
+def iir_block_matrix(coef):
+    """grail_biquad_block_matrix (pure host): float64 [2 S][2 S], the block transition matrix of one filter (float64 [S][5] or
+    flat [5 S]): state i (s1[0] s2[0] s1[1] ...) after IIR_BLOCK steps on +0.0 from the unit state c, at [i][c]."""
+    flat = np.ascontiguousarray(coef, dtype=np.float64).reshape(-1)
+    assert len(flat) % 5 == 0
+    S = len(flat) // 5
+    matrix = np.zeros((2 * S, 2 * S), dtype=np.float64)
+    _check(load().grail_biquad_block_matrix(flat.ctypes.data, S, matrix.ctypes.data))
+    return matrix
 
 
 def iir_stream_len(fed_before, n, tail, finishing=False):
@@ -1600,6 +1615,21 @@ class Context:
         return _waited(self, n_rows, (np.uint32, np.uint32),
                        lambda *d: self.iir_async(iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev,
                                                  out_stride, *d))
+
+    def iir_blocked_async(self, iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev, out_stride,
+                          out_len_dev=None, nonfinite_dev=None):
+        """grail_biquad_blocked_async: iir_async's arguments and results, parallel in time: a row's steps in blocks of IIR_BLOCK,
+        a lane each.  The call for a few long rows; bit for bit iir_async's up to a row's IIR_BLOCK-th output, its own
+        contract from there on."""
+        _check(load().grail_biquad_blocked_async(self.handle, iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail,
+                                              out_dev, out_stride, out_len_dev, nonfinite_dev))
+
+    def iir_blocked(self, iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail, out_dev, out_stride):
+        """iir_blocked_async, waited for, the results copied back: (out_len uint32, nonfinite uint32), one per row; a row
+        whose filter index is outside the set: (LIMIT_REFUSED, 0)."""
+        return _waited(self, n_rows, (np.uint32, np.uint32),
+                       lambda *d: self.iir_blocked_async(iir_set, rows_dev, row_stride, len_dev, n_rows, filter_dev, tail,
+                                                         out_dev, out_stride, *d))
 
     def iir_stream_open(self, iir_set, n_rows, filters=None, tail=0):
         """grail_iir_stream_open: a stream of n_rows rows filtered recursively call by call, row u bound to filter filters[u]

@@ -155,6 +155,7 @@ pub struct grail_iir_stream {
 /// The most biquad sections of one recursive filter and the most filters of one set (`grail_iir_create`).
 pub const GRAIL_IIR_SECTIONS_MAX: u32 = 8;
 pub const GRAIL_IIR_FILTERS_MAX: u32 = 64;
+pub const GRAIL_BIQUAD_BLOCK: u32 = 1024;
 /// The kinds of section `grail_iir_design` knows.
 pub const GRAIL_IIR_LOWPASS: c_int = 0;
 pub const GRAIL_IIR_HIGHPASS: c_int = 1;
@@ -386,6 +387,10 @@ extern "C" {
     pub fn grail_iir_async(ctx: *mut grail_ctx, set: *const grail_iir, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
         n_rows: u32, filter_dev: *const u32, tail: u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32,
         nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_biquad_blocked_async(ctx: *mut grail_ctx, set: *const grail_iir, rows_dev: *const f32, row_stride: u64,
+        len_dev: *const u32, n_rows: u32, filter_dev: *const u32, tail: u32, out_dev: *mut f32, out_stride: u64,
+        out_len_dev: *mut u32, nonfinite_dev: *mut u32) -> c_int;
+    pub fn grail_biquad_block_matrix(coef: *const f64, n_sections: u32, matrix: *mut f64) -> c_int;
     pub fn grail_iir_stream_len(fed_before: u64, n: u64, tail: u32, finishing: c_int, n_out: *mut u64) -> c_int;
     pub fn grail_iir_stream_open(ctx: *mut grail_ctx, set: *const grail_iir, n_rows: u32, filter: *const u32, tail: u32,
         out: *mut *mut grail_iir_stream) -> c_int;

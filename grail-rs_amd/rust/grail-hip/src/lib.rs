@@ -702,6 +702,18 @@ impl Gpu {
     /// non-finite input samples (they enter as +0.0); a row whose index is outside the set comes back empty.  A filter
     /// overshoots: limit or measure after filtering.
     pub fn iir(&self, set: &IirSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, tail: u32) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        self.iir_rows(set, rows, which, tail, false)
+    }
+
+    /// [`Gpu::iir`] parallel in time (`grail_biquad_blocked_async`; the contract is the header's section "levels, continued:
+    /// recursive filtering, parallel in time"): a row's steps in blocks of 1024, a lane each.  The call for a few long rows
+    /// (the tracks of a mix); [`Gpu::iir`] is the one for many rows.  Bit for bit [`Gpu::iir`] up to a row's 1024th output, a
+    /// contract of its own from there on (the two differ by some 1e-11 of the row's peak before the rounding to `f32`).
+    pub fn iir_blocked(&self, set: &IirSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, tail: u32) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
+        self.iir_rows(set, rows, which, tail, true)
+    }
+
+    fn iir_rows(&self, set: &IirSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, tail: u32, blocked: bool) -> Result<(Vec<Vec<f32>>, Vec<u32>), Error> {
         let n = rows.len();
         let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
         let mut out_lens = vec![0u32; n];
@@ -738,9 +750,9 @@ impl Gpu {
                 r = check(sys::grail_memcpy_h2d(self.ctx, d[5], w.as_ptr() as *const std::ffi::c_void, n * 4));
             }
             if r.is_ok() {
-                r = check(sys::grail_iir_async(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
-                                               d[5] as *const u32, tail, d[1] as *mut f32, out_stride as u64, d[3] as *mut u32,
-                                               d[4] as *mut u32));
+                let call = if blocked { sys::grail_biquad_blocked_async } else { sys::grail_iir_async };
+                r = check(call(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
+                               d[5] as *const u32, tail, d[1] as *mut f32, out_stride as u64, d[3] as *mut u32, d[4] as *mut u32));
             }
             if r.is_ok() {
                 r = check(sys::grail_memcpy_d2h(self.ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
@@ -1687,6 +1699,16 @@ pub fn iir_design(kind: i32, sample_rate: u32, f0_hz: f64, q: f64, gain_db: f64)
     let mut coef = [0f64; 5];
     check(unsafe { sys::grail_iir_design(kind, sample_rate, f0_hz, q, gain_db, coef.as_mut_ptr()) })?;
     Ok(coef)
+}
+
+/// The block transition matrix of one filter, `[2 S][2 S]` row-major: state `i` (`s1[0] s2[0] s1[1] ...`) after 1024 steps on
+/// +0.0 input from the unit state `c`, at `i * 2 S + c` (`grail_biquad_block_matrix`; pure host).  It is what
+/// [`Gpu::iir_blocked`] carries a row's state from block to block with.
+pub fn iir_block_matrix(sections: &[[f64; 5]]) -> Result<Vec<f64>, Error> {
+    let coef: Vec<f64> = sections.iter().flat_map(|s| s.iter().copied()).collect();
+    let mut matrix = vec![0f64; 4 * sections.len() * sections.len()];
+    check(unsafe { sys::grail_biquad_block_matrix(coef.as_ptr(), sections.len() as u32, matrix.as_mut_ptr()) })?;
+    Ok(matrix)
 }
 
 /// The outputs a call on an [`IirStream`] writes for a row that was fed `fed_before` samples before it: a `next` call that

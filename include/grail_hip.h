@@ -1390,7 +1390,9 @@ int grail_meter_stream_close(grail_ctx *ctx, grail_meter_stream *ms);
  * grail_iir_design returns it is the contract, as with grail_kweighting.  A Butterworth low-pass or high-pass of order 2m
  * is m sections of that kind at the same f0 with Q_k = 1 / (2 cos(pi (2k + 1) / (4m))), k = 0 .. m - 1.
  * A LONE LONG ROW is one lane's serial work, as in grail_loudness_async: many rows fill the device.  A form parallel in time
- * is another contract (its order of operations differs) and is not offered.
+ * is another contract (its order of operations differs): grail_biquad_blocked_async, "recursive filtering, parallel in time" below.
+ * WHICH CALL FOR WHAT: grail_iir_async for many rows (thousands of rendered utterances), grail_biquad_blocked_async for a few
+ * long ones (the tracks of a mix).
  * NOT promised: the output's peak can exceed the input's: limit or measure after filtering, not before. */
 #define GRAIL_IIR_SECTIONS_MAX 8
 #define GRAIL_IIR_FILTERS_MAX 64
@@ -1428,6 +1430,44 @@ int grail_iir_free(grail_ctx *ctx, grail_iir *set);
 int grail_iir_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev, uint64_t row_stride,
                     const uint32_t *len_dev, uint32_t n_rows, const uint32_t *filter_dev, uint32_t tail,
                     float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+
+/* ---- levels, continued: recursive filtering, parallel in time ----------------------------------------------------------------------
+ * grail_iir_async gives a row to one lane.  The few long tracks of a mix leave the device idle that way: grail_biquad_blocked_async
+ * cuts a row's steps into blocks of B = GRAIL_BIQUAD_BLOCK = 1024 and gives every block a lane.  Warming a block up would not do:
+ * a caller's notch at Q = 30 or a high-pass at 20 Hz does not decay in any fixed number of samples.  This form is exact in
+ * exact arithmetic for any coefficients; in binary64 it is a contract of its own, because its order of operations differs.
+ * A row's n, its steps (its outputs, and its samples where out_stride cut the outputs short), n_out, the non-finite count,
+ * the refused rows, `tail` and the cut by out_stride are exactly grail_iir_async's.  The row's inputs are its samples as
+ * binary64, +0.0 for those that are not finite and +0.0 past n.  The 2 S states of a filter are ordered s1[0], s2[0], s1[1],
+ * s2[1], ...; "the recurrence" is the one above, operation for operation, every operation rounded by itself.
+ *   1. MATRIX.  T[i][c] is state i after B steps of the recurrence on +0.0 input from the state that is 1.0 in place c and
+ *      +0.0 elsewhere: a function of the filter only, returned by grail_biquad_block_matrix.
+ *   2. REST PASS.  Block k covers the steps [k B, (k + 1) B) of the row.  For every block that is not the row's last, z_k is
+ *      the state after the block's B inputs through the recurrence from the state that is +0.0 in every place.
+ *   3. ENTRY STATES.  e_0 = +0.0 in every place.  For k >= 0 and m = 2 (i / 2) + 1:
+ *          e_{k+1}[i] = (...((T[i][0]*e_k[0] + T[i][1]*e_k[1]) + T[i][2]*e_k[2]) ... + T[i][m]*e_k[m]) + z_k[i]
+ *      over the states of i's own section and of the sections before it (the others cannot reach it), ascending, one
+ *      product and one addition each, each rounded by itself, nothing fused; z_k[i] is added last.
+ *   4. OUTPUT PASS.  Block k's outputs are the recurrence from the state e_k over the block's steps, with the one rounding to
+ *      binary32 at the end.  No block is stepped past the row's last step.
+ * SO: a row of at most B steps is bit for bit grail_iir_async's row, and so are the first B outputs of every row.  From
+ * output B on the two calls differ by the rounding of (3): within 1e-9 of the row's peak before the rounding to binary32 for
+ * the filters of DESIGN.md §4.22, where they differed by 2e-11 at most.  A row's result depends on its samples, its filter
+ * and the call's tail: not on the other rows, the other filters of the set, alignment, the device or the launch.  No atomics.
+ * WHICH CALL FOR WHAT: this one for a few long rows (it is the faster of the two while the rows are too few to fill the
+ * device with one lane each), grail_iir_async for many rows: this call runs the recurrence twice and holds scratch of
+ * 16 S' bytes a block (S' the set's largest S rounded up to 1, 2, 4 or 8).  Streams have no blocked form. */
+#define GRAIL_BIQUAD_BLOCK 1024
+/* grail_iir_async's arguments, checks and refusals, under its own name; further GRAIL_ERR_INVALID_ARG, nothing queued: strides,
+ * tail and n_rows that ask for more than 2^31 workgroups (n_rows * ceil(ceil((row_stride + tail) / 1024) / 64)).
+ * GRAIL_ERR_OUT_OF_MEMORY: the scratch could not be had.  The set's matrices are computed at its first blocked call and
+ * kept with it.  Queues four kernels on ctx's stream. */
+int grail_biquad_blocked_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev, uint64_t row_stride,
+                            const uint32_t *len_dev, uint32_t n_rows, const uint32_t *filter_dev, uint32_t tail,
+                            float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev);
+/* Pure host, like grail_iir_design: T of (1) for one filter of n_sections = S sections, coef [5 S]: matrix [2 S][2 S],
+ * row-major.  GRAIL_ERR_INVALID_ARG, nothing written: a NULL pointer, S outside 1 .. 8, a coefficient that is not finite. */
+int grail_biquad_block_matrix(const double *coef, uint32_t n_sections, double *matrix);
 
 /* ---- levels, continued: recursive filtering of streams ---------------------------------------------------------------------------
  * grail_iir_async takes finished rows.  A caller who pulls a live stream chunk by chunk filters chunk by chunk with an IIR
