@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--rate R] [--report] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] [--makeup DB]] [--rate R] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -21,6 +21,11 @@
 // length (no tail).  A filter overshoots, so with --ceiling the tracks' true peaks are measured after it.
 // --eq-blocked (with --eq) filters them with grail_biquad_blocked_async instead, the form parallel in time that is meant for a few
 // long tracks: the same samples up to the 1024th, within a rounding of the 16-bit scale after it.  The line printed names the call.
+// --compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] passes the two mixed tracks, after --eq and before the limiter, through a soft-knee
+// compressor on the peak detector (grail_dyn_design, grail_dyn_ballistics at the voices' rate, grail_dyn_async; each track follows
+// itself): threshold T in dB, ratio R >= 1, a knee of KNEE dB (6 unless given), attack and release in milliseconds (5 and 120
+// unless given).  --makeup DB (with --compress) is built into the curve.  Prints each track's largest gain reduction in dB.  The
+// make-up can lift peaks, so with --ceiling the tracks' true peaks are measured after it.
 // --rate R resamples the two finished tracks, after the mix and the limiter, from the voices' 44 100 Hz to R Hz on the device
 // (grail::Gpu::resample) and writes the WAV at R; the filter overshoots a little, so the line it prints has the tracks'
 // true peaks at R.
@@ -52,6 +57,8 @@ int main(int argc, char **argv)
     uint32_t band_taps = 255;
     EqOption eq_option;
     bool eq_blocked = false;
+    bool compress = false, bad_compress = false, makeup_given = false;
+    double comp[5] = {0.0, 1.0, 6.0, 5.0, 120.0}, makeup_db = 0.0;        // T, R, knee, attack ms, release ms
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
         else if ((!std::strcmp(argv[i], "--level") || !std::strcmp(argv[i], "--lufs")) && i + 1 < argc) {
@@ -89,6 +96,28 @@ int main(int argc, char **argv)
             bad_band = bad_band || rest == argv[i] || *rest || argv[i][0] == '-' || k < 3 || k > GRAIL_FIR_TAPS_MAX || k % 2 == 0;
         } else if (!std::strcmp(argv[i], "--eq")) eq_option.take(argc, argv, i);      // (examples/eq_option.h)
         else if (!std::strcmp(argv[i], "--eq-blocked")) eq_blocked = true;
+        else if (!std::strcmp(argv[i], "--compress")) {
+            bad_compress = bad_compress || compress || i + 1 >= argc;      // (named twice, or without a value)
+            compress = true;
+            if (i + 1 < argc) {     // two, three or five numbers between colons
+                const char *at = argv[++i];
+                int fields = 0;
+                for (;; ++at) {
+                    char *rest = nullptr;
+                    const double v = std::strtod(at, &rest);
+                    if (rest == at || fields == 5 || !std::isfinite(v)) { bad_compress = true; break; }
+                    comp[fields++] = v;
+                    at = rest;
+                    if (*at != ':') break;
+                }
+                bad_compress = bad_compress || *at || (fields != 2 && fields != 3 && fields != 5);
+            }
+        } else if (!std::strcmp(argv[i], "--makeup") && i + 1 < argc) {
+            char *rest = nullptr;
+            makeup_db = std::strtod(argv[++i], &rest);
+            bad_compress = bad_compress || makeup_given || rest == argv[i] || *rest || !std::isfinite(makeup_db);
+            makeup_given = true;
+        }
         else if (!std::strcmp(argv[i], "--limit")) limit = true;
         else if (!std::strcmp(argv[i], "--report")) {
             bad_report = report;        // (named twice)
@@ -101,12 +130,19 @@ int main(int argc, char **argv)
     std::vector<double> eq;         // five numbers a section
     const bool bad_eq = eq_option.bad || !eq_option.design(44100, eq) || (eq_blocked && eq.empty());
     bad_band = bad_band || (taps_given && !band) || (band && band_hi > 22050.0);
-    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || bad_eq || (capped && !leveled) || (limit && !capped)) {
+    // (the curve and the alphas of --compress are made here: the designer refuses what it cannot make)
+    std::vector<double> comp_gain(GRAIL_DYN_POINTS);
+    double comp_alpha[2] = {0.0, 0.0};
+    bad_compress = bad_compress || (makeup_given && !compress) ||
+                   (compress && (grail_dyn_design(GRAIL_DYN_COMPRESS, GRAIL_DYN_PEAK, comp[0], comp[1], comp[2], 0.0, makeup_db, comp_gain.data()) ||
+                                 grail_dyn_ballistics(44100, comp[3], comp[4], comp_alpha)));
+    if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || bad_eq || bad_compress || (capped && !leveled) || (limit && !capped)) {
         std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] "
-                             "[--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
+                             "[--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] [--makeup DB]] [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
                              "needs --ceiling, --band takes 0 <= LO < HI <= 22050 Hz, --taps an odd number from 3 to 4096 and needs "
                              "--band, --eq takes lowpass, highpass, bandpass, notch, peak, lowshelf or highshelf, 0 < F0 < 22050 Hz, Q > 0 and a "
-                             "gain in dB, up to eight times, --eq-blocked needs --eq, --rate takes a whole number of Hz, --report takes no value)\n");
+                             "gain in dB, up to eight times, --eq-blocked needs --eq, --compress takes a threshold in dB, a ratio of 1 or more, a knee of 0 dB or more and "
+                             "two times of 0 ms or more, once, --makeup needs --compress, --rate takes a whole number of Hz, --report takes no value)\n");
         return 2;
     }
     try {
@@ -162,6 +198,40 @@ int main(int argc, char **argv)
             std::printf("Equalised (%s), %u section%s:", eq_blocked ? "grail_biquad_blocked_async" : "grail_iir_async", sections, sections == 1 ? "" : "s");
             std::printf("%s\n", eq_option.text().c_str());
         };
+        // --compress: one curve for both tracks, each following itself; they keep their length (the C ABI, as --eq)
+        const auto compress_tracks = [&]() {
+            if (!compress) return;
+            grail_ctx *ctx = gpu.ctx();
+            const uint32_t n = (uint32_t)tracks.size(), detector = GRAIL_DYN_PEAK;
+            const uint64_t stride = ((uint64_t)end + 63) / 64 * 64;
+            grail_dyn *set = nullptr;
+            grail::check(grail_dyn_create(ctx, comp_gain.data(), comp_alpha, &detector, 1, &set));
+            void *d_rows = nullptr, *d_out = nullptr, *d_len = nullptr, *d_gain = nullptr;
+            int rc = grail_device_alloc(ctx, n * stride * 4, &d_rows);
+            if (!rc) rc = grail_device_alloc(ctx, n * stride * 4, &d_out);
+            if (!rc) rc = grail_device_alloc(ctx, n * 4, &d_len);
+            if (!rc) rc = grail_device_alloc(ctx, n * 8, &d_gain);
+            std::vector<uint32_t> track_len;
+            for (const std::vector<float> &t : tracks) track_len.push_back((uint32_t)t.size());
+            for (uint32_t t = 0; t < n && !rc; ++t)
+                rc = grail_memcpy_h2d(ctx, (float *)d_rows + t * stride, tracks[t].data(), tracks[t].size() * 4);
+            if (!rc) rc = grail_memcpy_h2d(ctx, d_len, track_len.data(), n * 4);
+            if (!rc) rc = grail_dyn_async(ctx, set, (const float *)d_rows, stride, (const uint32_t *)d_len, n, nullptr, nullptr, 0, nullptr, 0, nullptr,
+                                          (float *)d_out, stride, nullptr, nullptr, (double *)d_gain);
+            for (uint32_t t = 0; t < n && !rc; ++t)
+                rc = grail_memcpy_d2h(ctx, tracks[t].data(), (const float *)d_out + t * stride, tracks[t].size() * 4);
+            std::vector<double> min_gain(n, 1.0);
+            if (!rc) rc = grail_memcpy_d2h(ctx, min_gain.data(), d_gain, n * 8);
+            for (void *p : {d_rows, d_out, d_len, d_gain})
+                if (p) grail_device_free(ctx, p);
+            const int freed = grail_dyn_free(ctx, set);
+            grail::check(rc ? rc : freed);
+            std::printf("Compressed (grail_dyn_async) above %g dB at %g:1, knee %g dB, attack %g ms, release %g ms, make-up %g dB: largest gain reduction",
+                        comp[0], comp[1], comp[2], comp[3], comp[4], makeup_db);
+            for (uint32_t t = 0; t < n; ++t)    // (the curve holds the make-up: the reduction is what lies under it)
+                std::printf("%s %.2f dB", t ? " and" : "", makeup_db - 20.0 * std::log10(min_gain[t]));
+            std::printf("\n");
+        };
         if (leveled) {          // the same pan as a level: 0.8 and 0.2 of the line at level_db
             std::vector<float> levels, gains;
             for (const grail::Placement &p : placements) levels.push_back(level_db + 20.0f * std::log10(p.gain));
@@ -171,6 +241,7 @@ int main(int argc, char **argv)
                             : gpu.mix_leveled(utts, placements, levels, 2, end, mode, &gains, &unleveled);
             band_pass();
             equalise();
+            compress_tracks();
             if (lufs)
                 std::printf("Lines brought to %.1f LUFS: gains %.4g and %.4g%s\n", level_db, gains[0] / 0.8f, gains[3] / 0.8f,
                             unleveled ? " (a silent line or one shorter than 400 ms was left out)" : "");
@@ -197,6 +268,7 @@ int main(int argc, char **argv)
             tracks = gpu.mix(utts, placements, 2, end);
             band_pass();
             equalise();
+            compress_tracks();
         }
         uint32_t out_rate = (uint32_t)first.sample_rate;
         if (resampled && rate != out_rate) {    // (the voices' own rate: nothing to do, and the library refuses equal rates)

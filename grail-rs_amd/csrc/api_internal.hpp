@@ -34,6 +34,7 @@
 
 #include "../../include/grail_hip.h"
 #include "division_window.h"
+#include "dyn_plan.h"
 #include "fir_plan.h"
 #include "iir_plan.h"
 #include "kernels.h"
@@ -419,6 +420,29 @@ struct grail_iir_stream : ChunkedStream {
     uint32_t tail = 0;                // the outputs a row rings out over at its finish
     std::vector<uint32_t> filter;     // the rows' filters (host copy, kept while the upload may be in flight)
     grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows]
+};
+
+// A set of gain curves with their ballistics (transforms.cpp; the image is dyn_plan.cpp's): owned by the context's TransformState,
+// released by grail_dyn_free or with the context.
+struct grail_dyn {
+    uint32_t n_curves = 0;
+    std::vector<double> image;        // (host copies, kept while the upload may be in flight)
+    std::vector<double> alpha;
+    std::vector<uint32_t> detector;
+    grail::host::DeviceBuffer<double> d_image;        // [n_curves][DYN_IMAGE_DOUBLES]
+    grail::host::DeviceBuffer<double> d_alpha;        // [n_curves][2]
+    grail::host::DeviceBuffer<uint32_t> d_detector;   // [n_curves]
+};
+
+// A stream of rows compressed call by call (dyn_kernels.hip): DYN_STREAM_STATE_WORDS state words a row (samples fed, then the
+// envelope's bits), no ring (ring_cap 0: the envelope is all a row remembers), no marks (a row never ends).
+struct grail_dyn_stream : ChunkedStream {
+    const grail_dyn *set = nullptr;   // (a set with open streams is not freed)
+    uint32_t n_keys = 0;              // 0: self-keyed
+    std::vector<uint32_t> curve;      // the rows' curves and keys (host copies, kept while the upload may be in flight)
+    std::vector<uint32_t> key_row;
+    grail::host::DeviceBuffer<uint32_t> d_curve;    // [n_rows]
+    grail::host::DeviceBuffer<uint32_t> d_key_row;  // [n_rows] (a keyed stream's)
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks

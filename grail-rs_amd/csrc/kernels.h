@@ -403,4 +403,37 @@ hipError_t launch_biquad_block_output(const BiquadBlockArgs &args, uint32_t boun
 // ... and a row's out_len and count from cbad, one lane per row (outputs may be NULL); a refused row: 0xFFFFFFFF and 0
 hipError_t launch_biquad_block_totals(const BiquadBlockArgs &args, uint32_t *out_len, uint32_t *nonfinite, hipStream_t stream);
 
+// dynamics (dyn_kernels.hip; the contract is grail_hip.h's "levels, continued: dynamics"): one lane per row
+// through envelope, table and gain, 64 rows to a wave, the rows to out.  image: DEVICE [n_curves][641] pairs {G[k], G[k+1] -
+// G[k]} (dyn_plan.h); alpha: DEVICE [n_curves][2]; detector: DEVICE [n_curves]; curve: DEVICE [n_rows] or NULL (curve 0).
+// key != NULL: keyed, key [n_keys][key_stride] (n_keys >= 1), key_len: DEVICE [n_keys] or NULL (key_stride), key_row: DEVICE
+// [n_rows] or NULL (row u to key u).  out_len, nonfinite, min_gain: DEVICE [n_rows], may be NULL; a row whose curve or key
+// index is outside: 0xFFFFFFFF, 0 and NaN, nothing written.
+// state != NULL: a call on a stream: state: DEVICE [n_rows][2] = {N, the bits of e}, read at entry and written at exit; n =
+// min(len, row_stride) samples in, n out; a keyed row's key has the row's n samples (key_len is not read, key_row is the
+// stream's and was checked when it was opened).
+struct DynArgs {
+    const float *rows;
+    uint64_t row_stride;
+    const uint32_t *len;
+    uint32_t n_rows;
+    const uint32_t *curve;
+    const double *image;
+    const double *alpha;
+    const uint32_t *detector;
+    uint32_t n_curves;
+    const float *key;
+    uint64_t key_stride;
+    const uint32_t *key_len;
+    uint32_t n_keys;
+    const uint32_t *key_row;
+    float *out;
+    uint64_t out_stride;
+    uint32_t *out_len;
+    uint32_t *nonfinite;
+    double *min_gain;
+    uint64_t *state;
+};
+hipError_t launch_dyn(const DynArgs &args, hipStream_t stream);
+
 }  // namespace grail

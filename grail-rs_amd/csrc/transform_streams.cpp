@@ -2,7 +2,8 @@
 // _finish_async / _close (fir_kernels.hip), grail_resample_stream_* (resample_kernels.hip, §4.16) and
 // grail_limit_stream_* (limiter_kernels.hip, §4.17), and metered chunk by chunk: grail_meter_stream_* (meter_stream_kernels.hip,
 // §4.18), and filtered recursively chunk by chunk: grail_iir_stream_* (iir_kernels.hip, §4.20; checks iir_plan.cpp; one launch
-// a call, no ring).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp, limit_plan.cpp, meter_plan.cpp; their common
+// a call, no ring), and compressed chunk by chunk: grail_dyn_stream_* (dyn_kernels.hip, §4.23; checks dyn_plan.cpp; one launch a call,
+// no ring, no finish).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp, limit_plan.cpp, meter_plan.cpp; their common
 // end row_checks.h), what it keeps beside the rings, and its launches (two; the meter's three).  What the kinds do alike stands
 // once, first: telling a stream of the context's, its device state, a finishing call's marks, its close.
 #include "transform_state.h"
@@ -179,6 +180,24 @@ int iir_stream_call(grail_ctx *ctx, grail_iir_stream *is, const float *in_dev, u
     a.state = is->d_state.get(), a.mark = mark_dev, a.finishing = finishing ? 1u : 0u;
     const hipError_t e = launch_iir(a, set->bound, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "iir stream kernel launch");
+    return GRAIL_OK;
+}
+
+// A dynamics stream's call is one kernel too: grail_dyn_async's, with the rows' envelopes read at entry and written at exit.
+int dyn_stream_call(grail_ctx *ctx, grail_dyn_stream *ds, const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev,
+                    const float *key_dev, uint64_t key_stride, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                    uint32_t *nonfinite_dev, double *min_gain_dev)
+{
+    const grail_dyn *set = ds->set;
+    DynArgs a = {};
+    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev, a.n_rows = ds->n_rows, a.curve = ds->d_curve.get();
+    a.image = set->d_image.get(), a.alpha = set->d_alpha.get(), a.detector = set->d_detector.get(), a.n_curves = set->n_curves;
+    if (ds->n_keys && in_stride)        // (a call of no samples reads no key and may come without one)
+        a.key = key_dev, a.key_stride = key_stride, a.n_keys = ds->n_keys, a.key_row = ds->d_key_row.get();
+    a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev, a.min_gain = min_gain_dev;
+    a.state = ds->d_state.get();
+    const hipError_t e = launch_dyn(a, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "dyn stream kernel launch");
     return GRAIL_OK;
 }
 
@@ -509,6 +528,54 @@ int grail_iir_stream_finish_async(grail_ctx *ctx, grail_iir_stream *is, const ui
     const uint8_t *mark_dev;
     if ((rc = marks(ctx, *is, which, &mark_dev))) return rc;
     return iir_stream_call(ctx, is, nullptr, 0, nullptr, mark_dev, true, out_dev, out_stride, out_len_dev, nullptr);
+}
+
+int grail_dyn_stream_open(grail_ctx *ctx, const grail_dyn *set, uint32_t n_rows, const uint32_t *curve, uint32_t n_keys,
+                          const uint32_t *key_row, grail_dyn_stream **out)
+{
+    if (!ctx || !out) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_stream_open: NULL argument");
+    if (!own(ctx, &TransformState::dyns, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_stream_open: not a curve set of this context");
+    if (const char *why = dyn_stream_open_error(curve, n_rows, set->n_curves, n_keys, key_row)) return refuse("grail_dyn_stream_open", why);
+    int rc = bind(ctx);
+    if (rc) return rc;
+    std::unique_ptr<grail_dyn_stream> ds(new (std::nothrow) grail_dyn_stream());
+    if (!ds) return fail(GRAIL_ERR_OUT_OF_MEMORY, "dynamics stream");
+    ds->set = set;
+    ds->n_keys = n_keys;
+    ds->n_rows = ds->units = n_rows;
+    ds->ring_cap = 0;                                       // (no ring: the envelope is the row's memory)
+    ds->curve.assign(n_rows, 0u);
+    if (curve) std::copy(curve, curve + n_rows, ds->curve.begin());
+    HIP_TRY(upload(ds->d_curve, ds->curve.data(), n_rows, ctx->stream));
+    if (n_keys) {
+        ds->key_row.resize(n_rows);
+        for (uint32_t u = 0; u < n_rows; ++u) ds->key_row[u] = key_row ? key_row[u] : u;
+        HIP_TRY(upload(ds->d_key_row, ds->key_row.data(), n_rows, ctx->stream));
+    }
+    if ((rc = alloc_state(ctx, *ds, DYN_STREAM_STATE_WORDS))) return rc;       // (nothing fed, e = +0.0)
+    *out = peek(ctx)->dyn_streams.add(std::move(ds));       // (the set was found: the state is there)
+    return GRAIL_OK;
+}
+
+int grail_dyn_stream_close(grail_ctx *ctx, grail_dyn_stream *ds)
+{
+    return stream_close(ctx, &TransformState::dyn_streams, ds, "grail_dyn_stream_close", "dynamics");
+}
+
+int grail_dyn_stream_next_async(grail_ctx *ctx, grail_dyn_stream *ds, const float *in_dev, uint64_t in_stride,
+                                const uint32_t *in_len_dev, const float *key_dev, uint64_t key_stride, float *out_dev,
+                                uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev, double *min_gain_dev)
+{
+    const char *who = "grail_dyn_stream_next_async";
+    int rc = known(ctx, &TransformState::dyn_streams, ds, who, "dynamics");
+    if (rc) return rc;
+    // (without a context: the checks of one row, keyed by one key if a key comes with the call)
+    if (const char *why = dyn_stream_next_error(in_dev, in_stride, in_len_dev, ctx ? ds->n_rows : 1u, ctx ? ds->n_keys != 0u : key_dev != nullptr,
+                                                ctx ? ds->n_keys : 1u, key_dev, key_stride, out_dev, out_stride))
+        return refuse(who, why);
+    if ((rc = bind_device(ctx, who))) return rc;
+    return dyn_stream_call(ctx, ds, in_dev, in_stride, in_len_dev, key_dev, key_stride, out_dev, out_stride, out_len_dev, nonfinite_dev,
+                           min_gain_dev);
 }
 
 }  // extern "C"

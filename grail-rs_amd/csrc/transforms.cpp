@@ -2,7 +2,8 @@
 // §4.12), grail_resample_async (resample_kernels.hip, the ratio and table resample_plan.cpp, §4.13) and grail_fir_create /
 // _free / _async (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_iir_create / _free / _async
 // (iir_kernels.hip, a set's checks and image iir_plan.cpp, §4.19) and grail_biquad_blocked_async (biquad_block_kernels.hip, its
-// matrices, grid and scratch size iir_plan.cpp, §4.22): their checks, their scratch, their launches.
+// matrices, grid and scratch size iir_plan.cpp, §4.22) and grail_dyn_create / _free / _async (dyn_kernels.hip, a set's checks and
+// image dyn_plan.cpp, §4.23): their checks, their scratch, their launches.
 // What they check of a pair of rows is row_checks.h.  The same chunk by chunk, on streams, is transform_streams.cpp; what a
 // context keeps for both is transform_state.h.
 #include "row_checks.h"
@@ -248,6 +249,69 @@ int grail_iir_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev,
     a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     const hipError_t e = launch_iir(a, set->bound, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "iir kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_dyn_create(grail_ctx *ctx, const double *gain, const double *alpha, const uint32_t *detector, uint32_t n_curves,
+                     grail_dyn **out)
+{
+    if (!out) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_create: NULL argument");
+    if (const char *why = dyn_set_error(gain, alpha, detector, n_curves))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_dyn_create: ") + why);
+    int rc = bind_device(ctx, "grail_dyn_create");
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_dyn> set(new (std::nothrow) grail_dyn());
+    if (!set) return fail(GRAIL_ERR_OUT_OF_MEMORY, "curve set");
+    set->n_curves = n_curves;
+    dyn_set_image(gain, n_curves, set->image);
+    set->alpha.assign(alpha, alpha + 2u * n_curves);
+    set->detector.assign(detector, detector + n_curves);
+    HIP_TRY(upload(set->d_image, set->image.data(), set->image.size(), ctx->stream));
+    HIP_TRY(upload(set->d_alpha, set->alpha.data(), set->alpha.size(), ctx->stream));
+    HIP_TRY(upload(set->d_detector, set->detector.data(), set->detector.size(), ctx->stream));
+    *out = st->dyns.add(std::move(set));
+    return GRAIL_OK;
+}
+
+int grail_dyn_free(grail_ctx *ctx, grail_dyn *set)
+{
+    if (!set) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_free: ctx is NULL");
+    if (!own(ctx, &TransformState::dyns, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_free: not a curve set of this context");
+    TransformState *st = peek(ctx);
+    if (st->dyn_streams.any([set](const grail_dyn_stream &ds) { return ds.set == set; }))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_free: the set still has open dynamics streams");
+    // (a kernel or the upload still queued may be reading it)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    st->dyns.remove(set);
+    return GRAIL_OK;
+}
+
+int grail_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                    uint32_t n_rows, const uint32_t *curve_dev, const float *key_dev, uint64_t key_stride, const uint32_t *key_len_dev,
+                    uint32_t n_keys, const uint32_t *key_row_dev, float *out_dev, uint64_t out_stride, uint32_t *out_len_dev,
+                    uint32_t *nonfinite_dev, double *min_gain_dev)
+{
+    if (!set) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_async: set is NULL");
+    // (without a context the set was not looked up and is not looked into: the call ends at bind_device)
+    if (ctx && !own(ctx, &TransformState::dyns, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_async: not a curve set of this context");
+    if (const char *why = dyn_call_error(rows_dev, row_stride, len_dev, n_rows, key_dev, key_stride, n_keys, key_row_dev, out_dev, out_stride))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_dyn_async: ") + why);
+    int rc = bind_device(ctx, "grail_dyn_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (row_stride == 0 && !out_len_dev && !nonfinite_dev && !min_gain_dev) return GRAIL_OK;    // (rows of no samples, and nobody asks)
+    DynArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows, a.curve = curve_dev;
+    a.image = set->d_image.get(), a.alpha = set->d_alpha.get(), a.detector = set->d_detector.get(), a.n_curves = set->n_curves;
+    a.key = key_dev, a.key_stride = key_stride, a.key_len = key_len_dev, a.n_keys = n_keys, a.key_row = key_row_dev;
+    a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev, a.min_gain = min_gain_dev;
+    const hipError_t e = launch_dyn(a, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "dyn kernel launch");
     return GRAIL_OK;
 }
 

@@ -94,6 +94,8 @@ EXPORTS = [
     "grail_biquad_blocked_async", "grail_biquad_block_matrix",
     "grail_iir_stream_len", "grail_iir_stream_open", "grail_iir_stream_next_async", "grail_iir_stream_finish_async",
     "grail_iir_stream_close",
+    "grail_dyn_design", "grail_dyn_ballistics", "grail_dyn_create", "grail_dyn_free", "grail_dyn_async",
+    "grail_dyn_stream_open", "grail_dyn_stream_next_async", "grail_dyn_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
 LEVEL_PEAK, LEVEL_RMS, LEVEL_ACTIVE = 0, 1, 2    # GRAIL_LEVEL_*: what "level" means to level_gains / mix_leveled
@@ -126,6 +128,12 @@ IIR_FILTERS_MAX = 64                            # GRAIL_IIR_FILTERS_MAX: the fil
 IIR_BLOCK = 1024                                # GRAIL_BIQUAD_BLOCK: the steps of a block of grail_biquad_blocked_async
 # GRAIL_IIR_*: the kinds grail_iir_design knows
 IIR_LOWPASS, IIR_HIGHPASS, IIR_BANDPASS, IIR_NOTCH, IIR_PEAK, IIR_LOWSHELF, IIR_HIGHSHELF = range(7)
+DYN_STEPS_PER_OCTAVE = 16                       # GRAIL_DYN_STEPS_PER_OCTAVE: the points of a gain curve an octave of the envelope
+DYN_LOG2_LO, DYN_LOG2_HI = -32, 8               # GRAIL_DYN_LOG2_LO / _HI: the curve spans 2^-32 .. 2^8
+DYN_POINTS = 641                                # GRAIL_DYN_POINTS: the gains of one curve
+DYN_CURVES_MAX = 16                             # GRAIL_DYN_CURVES_MAX: the curves of one set
+DYN_PEAK, DYN_SQUARE = 0, 1                     # GRAIL_DYN_PEAK / _SQUARE: what the envelope follows, |w| or w * w
+DYN_COMPRESS, DYN_EXPAND = 0, 1                 # GRAIL_DYN_COMPRESS / _EXPAND: the kinds grail_dyn_design knows
 
 
 class GrailError(RuntimeError):
@@ -441,6 +449,14 @@ def load():
     L.grail_iir_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp]
     L.grail_iir_stream_finish_async.argtypes = [vp, vp, vp, vp, u64, vp]
     L.grail_iir_stream_close.argtypes = [vp, vp]
+    L.grail_dyn_design.argtypes = [C.c_int, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]
+    L.grail_dyn_ballistics.argtypes = [C.c_uint32, C.c_double, C.c_double, vp]
+    L.grail_dyn_create.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
+    L.grail_dyn_free.argtypes = [vp, vp]
+    L.grail_dyn_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, vp, u64, vp, C.c_uint32, vp, vp, u64, vp, vp, vp]
+    L.grail_dyn_stream_open.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
+    L.grail_dyn_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp]
+    L.grail_dyn_stream_close.argtypes = [vp, vp]
     L.grail_batch_mix_leveled_limited.argtypes = [vp, vp, vp, vp, vp, vp, C.c_int, C.c_uint32, vp, u64, C.c_uint32, u64, vp,
                                                   vp, vp, C.c_float, vp, C.c_uint32]
     _lib = L
@@ -873,6 +889,22 @@ def iir_stream_len(fed_before, n, tail, finishing=False):
     return out.value
 
 
+def dyn_design(kind, detector, threshold_db, ratio, knee_db=0.0, range_db=0.0, makeup_db=0.0):
+    """grail_dyn_design (pure host): float64[DYN_POINTS], the gain curve of a compressor (DYN_COMPRESS) or a downward expander
+    (DYN_EXPAND; range_db: the most it takes away) over the levels of the detector's envelope (DYN_PEAK or DYN_SQUARE)."""
+    gain = np.zeros(DYN_POINTS, dtype=np.float64)
+    _check(load().grail_dyn_design(kind, detector, threshold_db, ratio, knee_db, range_db, makeup_db, gain.ctypes.data))
+    return gain
+
+
+def dyn_ballistics(sample_rate, attack_ms, release_ms):
+    """grail_dyn_ballistics (pure host): float64[2] = alpha_attack, alpha_release of an envelope that covers 1 - 1/e of a step
+    in attack_ms on the way up and release_ms on the way down; 0.0 for a time of 0."""
+    alpha = np.zeros(2, dtype=np.float64)
+    _check(load().grail_dyn_ballistics(sample_rate, attack_ms, release_ms, alpha.ctypes.data))
+    return alpha
+
+
 def true_peak_limit_gains(true_peak, item_rows, item_gains, ceiling_db, n_rows=None):
     """grail_true_peak_limit_gains (pure host): the gains capped so that |gain| * true_peak[row] <= 10^(ceiling_db / 20).
     Returns (gains float32[n_items], a copy; n_limited: the items that were changed)."""
@@ -1028,6 +1060,22 @@ def _waited(ctx, n, types, call):
         call(*d)
         for dst, src in zip(res, d):
             ctx.d2h(dst, src, n * 4)
+    finally:
+        ctx.sync()
+        for p in d:
+            ctx.device_free(p)
+    return tuple(res)
+
+
+def _waited_sized(ctx, n, types, call):
+    """_waited for results of 4 or 8 bytes each"""
+    res = [np.zeros(n, dtype=t) for t in types]
+    d = [ctx.device_alloc(max(r.nbytes, 8)) for r in res]
+    try:
+        call(*d)
+        for dst, src in zip(res, d):
+            if dst.nbytes:
+                ctx.d2h(dst, src, dst.nbytes)
     finally:
         ctx.sync()
         for p in d:
@@ -1668,6 +1716,73 @@ class Context:
     def iir_stream_close(self, st):
         """grail_iir_stream_close: waits for the context's stream, then releases the stream."""
         _check(load().grail_iir_stream_close(self.handle, st))
+
+    def dyn_create(self, curves):
+        """grail_dyn_create: a set of gain curves on this context's device.  curves: a list of (gain float64[DYN_POINTS], (alpha_attack,
+        alpha_release), detector), as dyn_design and dyn_ballistics return them or the caller's own.  Returns the set's handle, for
+        dyn / dyn_async / dyn_free / dyn_stream_open; sets still alive go with the context."""
+        gain = np.ascontiguousarray([np.asarray(c[0], dtype=np.float64) for c in curves], dtype=np.float64).reshape(-1)
+        assert len(gain) == DYN_POINTS * len(curves)
+        alpha = np.ascontiguousarray([c[1] for c in curves], dtype=np.float64).reshape(-1)
+        detector = np.array([c[2] for c in curves], dtype=np.uint32)
+        out = C.c_void_p(None)
+        _check(load().grail_dyn_create(self.handle, gain.ctypes.data, alpha.ctypes.data, detector.ctypes.data, len(curves),
+                                       C.addressof(out)))
+        return out
+
+    def dyn_free(self, dyn_set):
+        """grail_dyn_free: waits for the context's stream, then releases the set (refused while it has open streams)."""
+        _check(load().grail_dyn_free(self.handle, dyn_set))
+
+    def dyn_async(self, dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev, out_stride, out_len_dev=None,
+                  nonfinite_dev=None, min_gain_dev=None, key_dev=None, key_stride=0, key_len_dev=None, n_keys=0, key_row_dev=None):
+        """grail_dyn_async: the rows times the gain their curve (curve_dev: a DEVICE array of uint32; None: curve 0 for every row)
+        gives at their envelope, into out_dev (must overlap neither rows_dev nor the keys).  key_dev None: every row follows
+        itself; else row u follows key key_row_dev[u] (None: key u) of the n_keys rows at key_dev.  Results are DEVICE arrays
+        [n_rows] (each may be None; min_gain is float64), queued on the context's stream."""
+        _check(load().grail_dyn_async(self.handle, dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, key_dev, key_stride,
+                                      key_len_dev, n_keys, key_row_dev, out_dev, out_stride, out_len_dev, nonfinite_dev, min_gain_dev))
+
+    def dyn(self, dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev, out_stride, key_dev=None, key_stride=0,
+            key_len_dev=None, n_keys=0, key_row_dev=None):
+        """dyn_async, waited for, the results copied back: (out_len uint32, nonfinite uint32, min_gain float64), one per row; a
+        row whose curve or key index is outside: (LIMIT_REFUSED, 0, NaN)."""
+        return _waited_sized(self, n_rows, (np.uint32, np.uint32, np.float64),
+                             lambda *d: self.dyn_async(dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev, out_stride,
+                                                       *d, key_dev=key_dev, key_stride=key_stride, key_len_dev=key_len_dev,
+                                                       n_keys=n_keys, key_row_dev=key_row_dev))
+
+    def dyn_stream_open(self, dyn_set, n_rows, curves=None, n_keys=0, key_rows=None):
+        """grail_dyn_stream_open: a stream of n_rows rows compressed call by call, row u bound to curve curves[u] of the set (a
+        host sequence; None: curve 0 for every row).  n_keys = 0: every row follows itself; else row u follows key key_rows[u]
+        (a host sequence; None: key u) of the n_keys key rows each call brings.  Returns the stream's handle, for
+        dyn_stream_next / _close."""
+        which = None if curves is None else np.ascontiguousarray(curves, dtype=np.uint32)
+        keys = None if key_rows is None else np.ascontiguousarray(key_rows, dtype=np.uint32)
+        assert (which is None or len(which) == n_rows) and (keys is None or len(keys) == n_rows)
+        out = C.c_void_p(None)
+        _check(load().grail_dyn_stream_open(self.handle, dyn_set, n_rows, None if which is None else which.ctypes.data, n_keys,
+                                            None if keys is None else keys.ctypes.data, C.addressof(out)))
+        return out
+
+    def dyn_stream_next_async(self, st, in_dev, in_stride, in_len_dev, out_dev, out_stride, out_len_dev=None, nonfinite_dev=None,
+                              min_gain_dev=None, key_dev=None, key_stride=0):
+        """grail_dyn_stream_next_async: every row is fed its next min(in_len_dev[u], in_stride) samples (and, keyed, reads as many
+        of its key at key_dev) and writes as many outputs to out_dev + u * out_stride.  Results are DEVICE arrays [n_rows] (each
+        may be None; min_gain is float64)."""
+        _check(load().grail_dyn_stream_next_async(self.handle, st, in_dev, in_stride, in_len_dev, key_dev, key_stride, out_dev,
+                                                  out_stride, out_len_dev, nonfinite_dev, min_gain_dev))
+
+    def dyn_stream_next(self, st, n_rows, in_dev, in_stride, in_len_dev, out_dev, out_stride, key_dev=None, key_stride=0):
+        """dyn_stream_next_async, waited for, the results copied back: (out_len uint32, nonfinite uint32, min_gain float64), one
+        per row."""
+        return _waited_sized(self, n_rows, (np.uint32, np.uint32, np.float64),
+                             lambda *d: self.dyn_stream_next_async(st, in_dev, in_stride, in_len_dev, out_dev, out_stride, *d,
+                                                                   key_dev=key_dev, key_stride=key_stride))
+
+    def dyn_stream_close(self, st):
+        """grail_dyn_stream_close: waits for the context's stream, then releases the stream."""
+        _check(load().grail_dyn_stream_close(self.handle, st))
 
     def resample_stream_open(self, rate_in, rate_out, n_rows):
         """grail_resample_stream_open: a stream of n_rows rows resampled call by call from rate_in to rate_out.  Returns the

@@ -151,6 +151,14 @@ pub struct grail_iir {
 pub struct grail_iir_stream {
     _private: [u8; 0],
 }
+#[repr(C)]
+pub struct grail_dyn {
+    _private: [u8; 0],
+}
+#[repr(C)]
+pub struct grail_dyn_stream {
+    _private: [u8; 0],
+}
 
 /// The most biquad sections of one recursive filter and the most filters of one set (`grail_iir_create`).
 pub const GRAIL_IIR_SECTIONS_MAX: u32 = 8;
@@ -164,6 +172,19 @@ pub const GRAIL_IIR_NOTCH: c_int = 3;
 pub const GRAIL_IIR_PEAK: c_int = 4;
 pub const GRAIL_IIR_LOWSHELF: c_int = 5;
 pub const GRAIL_IIR_HIGHSHELF: c_int = 6;
+
+/// A gain curve of `grail_dyn_create`: its points an octave of the envelope, the octaves it spans, its points, and the most
+/// curves of one set.
+pub const GRAIL_DYN_STEPS_PER_OCTAVE: u32 = 16;
+pub const GRAIL_DYN_LOG2_LO: i32 = -32;
+pub const GRAIL_DYN_LOG2_HI: i32 = 8;
+pub const GRAIL_DYN_POINTS: u32 = 641;
+pub const GRAIL_DYN_CURVES_MAX: u32 = 16;
+/// What the envelope follows, and the kinds of curve `grail_dyn_design` knows.
+pub const GRAIL_DYN_PEAK: c_int = 0;
+pub const GRAIL_DYN_SQUARE: c_int = 1;
+pub const GRAIL_DYN_COMPRESS: c_int = 0;
+pub const GRAIL_DYN_EXPAND: c_int = 1;
 
 /// The most taps of one filter and the most filters of one set (`grail_fir_create`).
 pub const GRAIL_FIR_TAPS_MAX: u32 = 4096;
@@ -400,6 +421,22 @@ extern "C" {
     pub fn grail_iir_stream_finish_async(ctx: *mut grail_ctx, is: *mut grail_iir_stream, which: *const u8,
         out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32) -> c_int;
     pub fn grail_iir_stream_close(ctx: *mut grail_ctx, is: *mut grail_iir_stream) -> c_int;
+    pub fn grail_dyn_design(kind: c_int, detector: c_int, threshold_db: f64, ratio: f64, knee_db: f64, range_db: f64,
+        makeup_db: f64, gain: *mut f64) -> c_int;
+    pub fn grail_dyn_ballistics(sample_rate: u32, attack_ms: f64, release_ms: f64, alpha: *mut f64) -> c_int;
+    pub fn grail_dyn_create(ctx: *mut grail_ctx, gain: *const f64, alpha: *const f64, detector: *const u32, n_curves: u32,
+        out: *mut *mut grail_dyn) -> c_int;
+    pub fn grail_dyn_free(ctx: *mut grail_ctx, set: *mut grail_dyn) -> c_int;
+    pub fn grail_dyn_async(ctx: *mut grail_ctx, set: *const grail_dyn, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, curve_dev: *const u32, key_dev: *const f32, key_stride: u64, key_len_dev: *const u32, n_keys: u32,
+        key_row_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32, nonfinite_dev: *mut u32,
+        min_gain_dev: *mut f64) -> c_int;
+    pub fn grail_dyn_stream_open(ctx: *mut grail_ctx, set: *const grail_dyn, n_rows: u32, curve: *const u32, n_keys: u32,
+        key_row: *const u32, out: *mut *mut grail_dyn_stream) -> c_int;
+    pub fn grail_dyn_stream_next_async(ctx: *mut grail_ctx, ds: *mut grail_dyn_stream, in_dev: *const f32, in_stride: u64,
+        in_len_dev: *const u32, key_dev: *const f32, key_stride: u64, out_dev: *mut f32, out_stride: u64,
+        out_len_dev: *mut u32, nonfinite_dev: *mut u32, min_gain_dev: *mut f64) -> c_int;
+    pub fn grail_dyn_stream_close(ctx: *mut grail_ctx, ds: *mut grail_dyn_stream) -> c_int;
 
     pub fn grail_device_alloc(ctx: *mut grail_ctx, bytes: usize, out: *mut *mut std::ffi::c_void) -> c_int;
     pub fn grail_device_free(ctx: *mut grail_ctx, ptr: *mut std::ffi::c_void) -> c_int;

@@ -794,6 +794,129 @@ impl Gpu {
         Ok(IirStream { gpu: self, is, n_rows, tail, _set: set })
     }
 
+    /// A set of gain curves on this device (`grail_dyn_create`), for [`Gpu::dynamics`] and [`Gpu::dyn_stream`]: one to sixteen
+    /// curves, each a table of [`DYN_POINTS`] gains ([`dyn_design`] makes one), its two alphas ([`dyn_ballistics`]) and its
+    /// detector (`sys::GRAIL_DYN_PEAK` or `sys::GRAIL_DYN_SQUARE`).  Released when dropped.
+    pub fn dyn_set(&self, curves: &[DynCurve]) -> Result<DynSet<'_>, Error> {
+        if curves.iter().any(|c| c.gain.len() != DYN_POINTS) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "dyn_set: a curve has DYN_POINTS gains".to_string() });
+        }
+        let gain: Vec<f64> = curves.iter().flat_map(|c| c.gain.iter().copied()).collect();
+        let alpha: Vec<f64> = curves.iter().flat_map(|c| c.alpha.iter().copied()).collect();
+        let detector: Vec<u32> = curves.iter().map(|c| c.detector as u32).collect();
+        let mut set: *mut sys::grail_dyn = std::ptr::null_mut();
+        check(unsafe { sys::grail_dyn_create(self.ctx, gain.as_ptr(), alpha.as_ptr(), detector.as_ptr(), curves.len() as u32, &mut set) })?;
+        Ok(DynSet { gpu: self, set })
+    }
+
+    /// Rows of samples compressed, expanded or ducked on the device (`grail_dyn_async`; the contract is the header's section
+    /// "levels, continued: dynamics"), row `i` on curve `which[i]` of the set (`None`: curve 0 for every row).  `keys`: `None`,
+    /// and every row follows itself; or the key rows and, per row, the index of the key it follows (ducking: the bed's rows keyed
+    /// by the voice's track).  Returns the rows, per row the count of non-finite input samples (they enter as +0.0) and the
+    /// smallest gain it was given (1.0 for an empty row); a row whose curve or key index is outside comes back empty with a NaN.
+    pub fn dynamics(&self, set: &DynSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, keys: Option<(&[Vec<f32>], &[u32])>)
+                    -> Result<(Vec<Vec<f32>>, Vec<u32>, Vec<f64>), Error> {
+        let n = rows.len();
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut out_lens = vec![0u32; n];
+        let mut bad = vec![0u32; n];
+        let mut min_gain = vec![1f64; n];
+        if n == 0 {
+            return Ok((out, bad, min_gain));
+        }
+        if which.map_or(false, |w| w.len() != n) || keys.map_or(false, |(k, r)| r.len() != n || k.is_empty()) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "dynamics: one curve index and one key index per row".to_string() });
+        }
+        let longest = rows.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = ((longest + 63) / 64 * 64).max(64);
+        let lens: Vec<u32> = rows.iter().map(|r| r.len() as u32).collect();
+        let n_keys = keys.map_or(0, |(k, _)| k.len());
+        let key_stride = keys.map_or(0, |(k, _)| ((k.iter().map(|r| r.len()).max().unwrap_or(0) + 63) / 64 * 64).max(64));
+        let key_lens: Vec<u32> = keys.map_or(Vec::new(), |(k, _)| k.iter().map(|r| r.len() as u32).collect());
+        unsafe {
+            // rows, out, len, out_len, nonfinite, min_gain, curve, key, key_len, key_row
+            let mut d: [*mut std::ffi::c_void; 10] = [std::ptr::null_mut(); 10];
+            let sizes = [n * stride * 4, n * stride * 4, n * 4, n * 4, n * 4, n * 8, n * 4, n_keys * key_stride * 4, n_keys * 4, n * 4];
+            let mut r = Ok(());
+            for k in 0..10 {
+                if r.is_ok() && (k < 6 || (k == 6 && which.is_some()) || (k > 6 && keys.is_some())) {
+                    r = check(sys::grail_device_alloc(self.ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in rows.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if let (true, Some(w)) = (r.is_ok(), which) {
+                r = check(sys::grail_memcpy_h2d(self.ctx, d[6], w.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if let Some((k, key_row)) = keys {
+                for (i, row) in k.iter().enumerate() {
+                    if r.is_ok() && !row.is_empty() {
+                        r = check(sys::grail_memcpy_h2d(self.ctx, (d[7] as *mut f32).add(i * key_stride) as *mut std::ffi::c_void,
+                                                        row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                    }
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, d[8], key_lens.as_ptr() as *const std::ffi::c_void, n_keys * 4));
+                }
+                if r.is_ok() {
+                    r = check(sys::grail_memcpy_h2d(self.ctx, d[9], key_row.as_ptr() as *const std::ffi::c_void, n * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_dyn_async(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
+                                               d[6] as *const u32, d[7] as *const f32, key_stride as u64, d[8] as *const u32,
+                                               n_keys as u32, d[9] as *const u32, d[1] as *mut f32, stride as u64, d[3] as *mut u32,
+                                               d[4] as *mut u32, d[5] as *mut f64));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(self.ctx, min_gain.as_mut_ptr() as *mut std::ffi::c_void, d[5], n * 8));
+            }
+            for i in 0..n {
+                if r.is_ok() && out_lens[i] != 0 && out_lens[i] != LIMIT_REFUSED {
+                    out[i] = vec![0f32; out_lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(self.ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * stride) as *const std::ffi::c_void,
+                                                    out_lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(self.ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad, min_gain))
+    }
+
+    /// A stream of `n_rows` self-keyed rows compressed chunk by chunk (`grail_dyn_stream_open`; the contract is the header's
+    /// section "levels, continued: dynamics of streams"), row `i` bound to curve `which[i]` of the set (`None`: curve 0).  The
+    /// chunks' outputs put end to end are the bits [`Gpu::dynamics`] gives for the whole rows.  Closed when dropped; the borrow
+    /// keeps the set alive for as long.  (Keyed streams are reached through the `-sys` crate.)
+    pub fn dyn_stream<'a>(&'a self, set: &'a DynSet<'a>, n_rows: u32, which: Option<&[u32]>) -> Result<DynStream<'a>, Error> {
+        if which.map_or(false, |w| w.len() != n_rows as usize) {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "dyn_stream: one curve index per row".to_string() });
+        }
+        let mut ds: *mut sys::grail_dyn_stream = std::ptr::null_mut();
+        check(unsafe {
+            sys::grail_dyn_stream_open(self.ctx, set.set, n_rows, which.map_or(std::ptr::null(), |w| w.as_ptr()), 0, std::ptr::null(), &mut ds)
+        })?;
+        Ok(DynStream { gpu: self, ds, n_rows, _set: set })
+    }
+
     /// A stream of `n_rows` rows resampled chunk by chunk from `rate_in` to `rate_out` (`grail_resample_stream_open`; the
     /// contract is the header's section "levels, continued: sample-rate conversion of streams").  The chunks' outputs put
     /// end to end, then the tail of [`ResampleStream::finish`], are the bits [`Gpu::resample`] gives for the whole rows.
@@ -1237,6 +1360,109 @@ impl Drop for IirStream<'_> {
     fn drop(&mut self) {
         unsafe {
             sys::grail_iir_stream_close(self.gpu.ctx, self.is);
+        }
+    }
+}
+
+/// One gain curve of a [`DynSet`]: [`DYN_POINTS`] gains over the levels of the envelope, `[alpha_attack, alpha_release]`, and the
+/// detector (`sys::GRAIL_DYN_PEAK` or `sys::GRAIL_DYN_SQUARE`).
+#[derive(Clone, Debug)]
+pub struct DynCurve {
+    pub gain: Vec<f64>,
+    pub alpha: [f64; 2],
+    pub detector: i32,
+}
+
+/// A set of gain curves resident on a [`Gpu`]'s device ([`Gpu::dyn_set`]); `grail_dyn_free` when dropped.
+pub struct DynSet<'a> {
+    gpu: &'a Gpu,
+    set: *mut sys::grail_dyn,
+}
+
+impl Drop for DynSet<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_dyn_free(self.gpu.ctx, self.set);
+        }
+    }
+}
+
+/// Self-keyed rows compressed chunk by chunk on a [`Gpu`]'s device ([`Gpu::dyn_stream`]), their envelopes resident in HBM
+/// between calls; `grail_dyn_stream_close` when dropped.
+pub struct DynStream<'a> {
+    gpu: &'a Gpu,
+    ds: *mut sys::grail_dyn_stream,
+    n_rows: u32,
+    _set: &'a DynSet<'a>,
+}
+
+impl DynStream<'_> {
+    /// Feeds row `i` the samples `chunks[i]` (an empty chunk: the row pauses) and returns, per row, as many outputs, the count
+    /// of non-finite samples among those fed and the smallest gain of the call (1.0 for an empty chunk)
+    /// (`grail_dyn_stream_next_async`).
+    pub fn next(&mut self, chunks: &[Vec<f32>]) -> Result<(Vec<Vec<f32>>, Vec<u32>, Vec<f64>), Error> {
+        let n = self.n_rows as usize;
+        if chunks.len() != n {
+            return Err(Error { status: sys::GRAIL_ERR_INVALID_ARG, message: "DynStream::next: one chunk per row".to_string() });
+        }
+        let longest = chunks.iter().map(|r| r.len()).max().unwrap_or(0);
+        let stride = (longest + 63) / 64 * 64;
+        let lens: Vec<u32> = chunks.iter().map(|r| r.len() as u32).collect();
+        let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
+        let mut bad = vec![0u32; n];
+        let mut min_gain = vec![1f64; n];
+        let ctx = self.gpu.ctx;
+        unsafe {
+            let mut d: [*mut std::ffi::c_void; 5] = [std::ptr::null_mut(); 5];
+            let sizes = [n * stride.max(1) * 4, n * stride.max(1) * 4, n * 4, n * 4, n * 8];
+            let mut r = Ok(());
+            for k in 0..5 {
+                if r.is_ok() {
+                    r = check(sys::grail_device_alloc(ctx, sizes[k], &mut d[k]));
+                }
+            }
+            for (i, row) in chunks.iter().enumerate() {
+                if r.is_ok() && !row.is_empty() {
+                    r = check(sys::grail_memcpy_h2d(ctx, (d[0] as *mut f32).add(i * stride) as *mut std::ffi::c_void,
+                                                    row.as_ptr() as *const std::ffi::c_void, row.len() * 4));
+                }
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_h2d(ctx, d[2], lens.as_ptr() as *const std::ffi::c_void, n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_dyn_stream_next_async(ctx, self.ds, d[0] as *const f32, stride as u64, d[2] as *const u32,
+                                                           std::ptr::null(), 0, d[1] as *mut f32, stride as u64, std::ptr::null_mut(),
+                                                           d[3] as *mut u32, d[4] as *mut f64));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, bad.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));
+            }
+            if r.is_ok() {
+                r = check(sys::grail_memcpy_d2h(ctx, min_gain.as_mut_ptr() as *mut std::ffi::c_void, d[4], n * 8));
+            }
+            for i in 0..n {
+                if r.is_ok() && lens[i] != 0 {          // (a dynamics stream writes as many outputs as it is fed samples)
+                    out[i] = vec![0f32; lens[i] as usize];
+                    r = check(sys::grail_memcpy_d2h(ctx, out[i].as_mut_ptr() as *mut std::ffi::c_void,
+                                                    (d[1] as *const f32).add(i * stride) as *const std::ffi::c_void, lens[i] as usize * 4));
+                }
+            }
+            for p in d {
+                if !p.is_null() {
+                    sys::grail_device_free(ctx, p);
+                }
+            }
+            r?;
+        }
+        Ok((out, bad, min_gain))
+    }
+}
+
+impl Drop for DynStream<'_> {
+    fn drop(&mut self) {
+        unsafe {
+            sys::grail_dyn_stream_close(self.gpu.ctx, self.ds);
         }
     }
 }
@@ -1699,6 +1925,27 @@ pub fn iir_design(kind: i32, sample_rate: u32, f0_hz: f64, q: f64, gain_db: f64)
     let mut coef = [0f64; 5];
     check(unsafe { sys::grail_iir_design(kind, sample_rate, f0_hz, q, gain_db, coef.as_mut_ptr()) })?;
     Ok(coef)
+}
+
+/// The gains of one curve, and the most curves of a set (`GRAIL_DYN_POINTS`, `GRAIL_DYN_CURVES_MAX`).
+pub const DYN_POINTS: usize = sys::GRAIL_DYN_POINTS as usize;
+pub const DYN_CURVES_MAX: u32 = sys::GRAIL_DYN_CURVES_MAX;
+
+/// The gain curve of a soft-knee compressor (`sys::GRAIL_DYN_COMPRESS`) or of its mirror below the threshold, a downward
+/// expander held at `range_db` (`sys::GRAIL_DYN_EXPAND`), over the levels of `detector`'s envelope: [`DYN_POINTS`] gains
+/// (`grail_dyn_design`; pure host).
+pub fn dyn_design(kind: i32, detector: i32, threshold_db: f64, ratio: f64, knee_db: f64, range_db: f64, makeup_db: f64) -> Result<Vec<f64>, Error> {
+    let mut gain = vec![0f64; DYN_POINTS];
+    check(unsafe { sys::grail_dyn_design(kind, detector, threshold_db, ratio, knee_db, range_db, makeup_db, gain.as_mut_ptr()) })?;
+    Ok(gain)
+}
+
+/// `[alpha_attack, alpha_release]` of an envelope that covers 1 - 1/e of a step in `attack_ms` on the way up and `release_ms`
+/// on the way down, 0.0 for a time of 0 (`grail_dyn_ballistics`; pure host).
+pub fn dyn_ballistics(sample_rate: u32, attack_ms: f64, release_ms: f64) -> Result<[f64; 2], Error> {
+    let mut alpha = [0f64; 2];
+    check(unsafe { sys::grail_dyn_ballistics(sample_rate, attack_ms, release_ms, alpha.as_mut_ptr()) })?;
+    Ok(alpha)
 }
 
 /// The block transition matrix of one filter, `[2 S][2 S]` row-major: state `i` (`s1[0] s2[0] s1[1] ...`) after 1024 steps on

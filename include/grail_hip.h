@@ -1514,6 +1514,150 @@ int grail_iir_stream_finish_async(grail_ctx *ctx, grail_iir_stream *is, const ui
  * grail_iir_free of it returns GRAIL_ERR_INVALID_ARG and frees nothing. */
 int grail_iir_stream_close(grail_ctx *ctx, grail_iir_stream *is);
 
+/* ---- levels, continued: dynamics ---------------------------------------------------------------------------------------------------
+ * Between the equaliser (grail_iir_async) and the limiter (grail_limit_async) a speech chain has a compressor: it evens out
+ * an utterance's syllables, holds a bus together, pushes a bed down under a voice (ducking), closes a gate on the noise
+ * between phrases.  All of them are one thing: an envelope follower with separate attack and release, and a gain read off
+ * a static curve at the envelope's level.  The limiter keeps its hard guarantee; this is the soft stage in front of it.
+ * ARITHMETIC.  All of it IEEE binary64, every operation rounded by itself (no fused multiply-add anywhere), evaluated in
+ * the order written; denormals are not flushed.  The device evaluates no log, exp or pow: the curve is a TABLE made on the
+ * host, the caller's own or grail_dyn_design's, indexed with the exponent and mantissa bits of the envelope and interpolated
+ * linearly.  The numbers are a pure function of the row's samples, its key's samples, its curve, alphas and detector: not
+ * of the strides beyond where they cut, the row's index, the rows around it, the other curves of the set, alignment, the
+ * device or the launch.  No atomics.
+ * CURVE.  LO = GRAIL_DYN_LOG2_LO = -32, HI = GRAIL_DYN_LOG2_HI = 8, 16 = GRAIL_DYN_STEPS_PER_OCTAVE steps an octave,
+ * GRAIL_DYN_POINTS = (HI - LO) * 16 + 1 = 641 points.  A curve is G[641] finite doubles >= 0, the gain at the levels
+ *     lev[k] = 2^(LO + k div 16) * (1 + (k mod 16) / 16),   k = 0 .. 640           (lev[0] = 2^-32, lev[640] = 2^8)
+ * of the envelope e; with it two numbers alpha_attack, alpha_release in [0, 1) and a detector, GRAIL_DYN_PEAK (e follows
+ * |w|, a level in dB is 20 log10 e) or GRAIL_DYN_SQUARE (e follows w*w, a level in dB is 10 log10 e).
+ * LOOKUP  curve(e), for e finite and >= 0:
+ *   - e < 2^LO: G[0].   e >= 2^HI: G[640].
+ *   - otherwise, with E the biased exponent field of e and m its 52 mantissa bits:
+ *         k = (E - (1023 + LO)) * 16 + (m >> 48);   f = (double)(m & (2^48 - 1)) * 2^-48   (exact);
+ *         g = G[k] + f * (G[k+1] - G[k])            (one subtraction, one product, one addition, each rounded)
+ * SET.  1 <= C <= GRAIL_DYN_CURVES_MAX = 16 curves, each with its own alphas and detector.
+ * ROW.  For a row of n = min(len[u], row_stride) samples with curve c = curve_dev[u] (NULL: curve 0 for every row), from
+ * e = +0.0, for t = 0 .. n - 1 in ascending order:
+ *     1. v = (double)x[t]                 (a sample that is not finite is counted once in nonfinite[u], enters as +0.0, and
+ *                                          its output is +0.0)
+ *     2. the key:  self-keyed: w = v.   keyed: w = (double)key[kr][t] for t < min(key_len[kr], key_stride), +0.0 beyond
+ *                                          (a key sample that is not finite enters as +0.0 and is not counted)
+ *     3. a = |w|  (PEAK)   or   a = w * w  (SQUARE)
+ *     4. alpha = (a > e) ? alpha_attack : alpha_release;      e = a + alpha * (e - a)
+ *     5. g = curve(e);      out[t] = (float)(g * v)  for t < n_out = min(n, out_stride): the only rounding to binary32
+ *     6. min_gain[u] = the smallest g over ALL t < n (also where out_stride cut the outputs; the first of equal ones), and
+ *        1.0 for n = 0.  With make-up in the curve it can lie above 1.0.
+ * out between n_out and out_stride is never written; memory between n and row_stride enters nothing.  out_len[u] = n_out.
+ * g is finite and v enters finite, so no NaN is ever produced: every output bit is promised.
+ * REFUSED ROWS.  A row whose curve index is >= C, or (keyed) whose key index is >= n_keys: out_len[u] = GRAIL_LIMIT_REFUSED,
+ * nonfinite[u] = 0, min_gain[u] = NaN (the bits 0x7FF8000000000000), its out row unwritten.
+ * KEYS.  key_dev: device [n_keys][key_stride] floats, NULL = self-keyed (then the key arguments are not read).  key_len_dev:
+ * device [n_keys], NULL = key_stride for every key.  key_row_dev: device [n_rows], NULL = row u listens to key u (then
+ * n_keys >= n_rows).  Ducking: the bed's rows keyed by the voice's track.  The poor man's stereo link: both channels keyed
+ * by one row.  Keyed rows may not overlap out_dev (they may be rows_dev itself).
+ * DESIGN.  grail_dyn_design fills G[k] for k = 0 .. 640.  With T = threshold_db, R = ratio, W = knee_db:
+ *     x = 20 * log10(lev[k])  (PEAK)   or   10 * log10(lev[k])  (SQUARE);     d = x - T;     h = W / 2
+ *     GRAIL_DYN_COMPRESS:   d <= -h:  r = 0.0
+ *                           d >=  h:  r = (T + d / R) - x
+ *                           else:     q = d + h;   r = ((1 / R - 1) * (q * q)) / (2 * W)
+ *     GRAIL_DYN_EXPAND:     d >=  h:  r = 0.0
+ *                           d <= -h:  r = (T + d * R) - x
+ *                           else:     q = d - h;   r = ((1 - R) * (q * q)) / (2 * W)
+ *                           then r = -range_db where r < -range_db        (the reduction is held at the range; a gate is
+ *                                                                          a large R with the range it may close by)
+ *     G[k] = pow(10, (r + makeup_db) / 20)
+ * (r is y - x of the usual soft-knee curve y(x); range_db is read by EXPAND only.)  The bits of log10 and pow are the C
+ * library's: the table as grail_dyn_design returns it is the contract, as with grail_iir_design.
+ * BALLISTICS.  grail_dyn_ballistics: alpha = exp(-1000 / (ms * (double)rate)), and exactly 0.0 for a time of 0 (the envelope
+ * is the detector's value at once); alpha[0] from attack_ms, alpha[1] from release_ms.  After `ms` the envelope has covered
+ * 1 - 1/e of a step.
+ * WHAT THE TABLE PROMISES: between two points the curve is the chord.  Against the ideal formula that is within 0.01 dB
+ * on a segment that holds no corner of the curve and within 0.14 dB on the one segment that holds a hard corner (DESIGN.md
+ * §4.23 derives and measures both).
+ * A LONE LONG ROW is one lane's serial work, as in grail_iir_async, and there is no form parallel in time: the branch on
+ * a > e makes the recurrence non-linear.  NOT here: look-ahead (the limiter is the look-ahead stage), linked groups that take
+ * the maximum over members (a shared key row is what there is), smoothing in the log domain. */
+#define GRAIL_DYN_STEPS_PER_OCTAVE 16
+#define GRAIL_DYN_LOG2_LO (-32)
+#define GRAIL_DYN_LOG2_HI 8
+#define GRAIL_DYN_POINTS 641
+#define GRAIL_DYN_CURVES_MAX 16
+#define GRAIL_DYN_PEAK     0
+#define GRAIL_DYN_SQUARE   1
+#define GRAIL_DYN_COMPRESS 0
+#define GRAIL_DYN_EXPAND   1
+typedef struct grail_dyn grail_dyn; /* a set of gain curves with their ballistics, resident in HBM */
+
+/* Pure host: gain[0 .. 640] = G of DESIGN above.  GRAIL_ERR_INVALID_ARG, nothing written: an unknown kind or detector,
+ * a threshold_db or makeup_db that is not finite, ratio < 1 or not finite, knee_db or range_db below 0 or not finite, gain
+ * NULL, a table whose numbers are not all finite (a make-up of thousands of dB). */
+int grail_dyn_design(int kind, int detector, double threshold_db, double ratio, double knee_db, double range_db,
+                     double makeup_db, double *gain /* [GRAIL_DYN_POINTS] */);
+/* Pure host: alpha[0], alpha[1] of BALLISTICS above.  GRAIL_ERR_INVALID_ARG, nothing written: sample_rate 0, a time that
+ * is negative or not finite, alpha NULL, a time so long that its alpha rounds to 1.0. */
+int grail_dyn_ballistics(uint32_t sample_rate, double attack_ms, double release_ms, double alpha[2]);
+
+/* A set of n_curves curves on ctx's device: gain [n_curves][GRAIL_DYN_POINTS], alpha [n_curves][2] (attack, release),
+ * detector [n_curves].  The set keeps its own copy, uploaded on ctx's stream; the arrays may be reused at once.
+ * GRAIL_ERR_INVALID_ARG, nothing created: a NULL argument, n_curves outside 1 .. 16, a gain that is not finite or is
+ * negative, an alpha outside [0, 1), an unknown detector.  These come first; without a usable device: GRAIL_ERR_NO_DEVICE. */
+int grail_dyn_create(grail_ctx *ctx, const double *gain, const double *alpha, const uint32_t *detector, uint32_t n_curves,
+                     grail_dyn **out);
+/* Releases a set once everything queued on ctx's stream is through; sets still alive at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: a pointer that is not a live set of this context (sets are looked up,
+ * not looked into); a set that still has open streams. */
+int grail_dyn_free(grail_ctx *ctx, grail_dyn *set);
+/* ROW above, queued on ctx's stream like grail_iir_async: rows_dev: device [n_rows][row_stride]; len_dev: device [n_rows];
+ * curve_dev: device [n_rows] or NULL; the keys as in KEYS; out_dev: device [n_rows][out_stride] (out_stride = 0: the
+ * results only).  Results are DEVICE arrays [n_rows], each may be NULL: out_len, nonfinite, min_gain.  out_dev must overlap
+ * neither rows_dev nor the keyed rows.  16-byte loads and stores where every base is 16-byte aligned and every stride a
+ * multiple of 4, 4-byte ones otherwise: same bits.  One lane takes one row, 64 rows to a wavefront.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: set NULL or of another context; a NULL buffer with samples to read or write;
+ * key_dev with n_keys = 0, or with key_row_dev NULL and n_keys < n_rows; overlapping ranges; rows or keys that span more
+ * than 2^60 samples; row_stride and out_stride that both allow a row of 2^32 samples or more.  These come first; without a
+ * usable device: GRAIL_ERR_NO_DEVICE.  n_rows = 0 is a success that queues nothing. */
+int grail_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev, uint64_t row_stride,
+                    const uint32_t *len_dev, uint32_t n_rows, const uint32_t *curve_dev, const float *key_dev,
+                    uint64_t key_stride, const uint32_t *key_len_dev, uint32_t n_keys, const uint32_t *key_row_dev,
+                    float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev,
+                    double *min_gain_dev);
+
+/* ---- levels, continued: dynamics of streams ---------------------------------------------------------------------------------------
+ * A DYNAMICS STREAM: n_rows independent rows, each bound to one curve of a live set (and, keyed, to one key row) when the
+ * stream is opened, their state resident in HBM between calls: N, the samples fed so far (64 bits), and e.
+ * THE CONTRACT.  For any split of a row's samples into calls (calls of no samples included), the outputs of the `next`
+ * calls put end to end are bit for bit what grail_dyn_async writes for the whole row; the sum of the calls' nonfinite
+ * counts is its count; a call's min_gain is that call's own (1.0 for a call that fed the row nothing), and the smallest
+ * over the calls that fed the row something is the whole row's.  A row rings out over nothing: there is no `finish`, and
+ * a row never ends.
+ * KEYS.  A keyed stream (n_keys >= 1 at open) reads the key of row u in a call at key_dev + key_row[u] * key_stride,
+ * samples t < in_len[u]: the key advances with the row it drives. */
+typedef struct grail_dyn_stream grail_dyn_stream;
+
+/* A stream of n_rows rows on the curves of `set`: curve is a HOST array [n_rows] of indices into the set, NULL means
+ * curve 0 for every row.  n_keys = 0: self-keyed (key_row is not read).  n_keys >= 1: key_row is a HOST array [n_rows] of
+ * indices below n_keys, NULL means row u listens to key u (then n_keys >= n_rows).  GRAIL_ERR_INVALID_ARG, nothing
+ * created: ctx or out NULL; a set that is not a live set of this context; n_rows = 0; a curve index >= the set's count; a
+ * key index >= n_keys (checked here: a stream has no refused rows).  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE. */
+int grail_dyn_stream_open(grail_ctx *ctx, const grail_dyn *set, uint32_t n_rows, const uint32_t *curve, uint32_t n_keys,
+                          const uint32_t *key_row, grail_dyn_stream **out);
+/* Feeds every row u its next n = min(in_len_dev[u], in_stride) samples from in_dev + u * in_stride and writes their n
+ * outputs to out_dev + u * out_stride, from index 0; queued on ctx's stream.  key_dev: device [n_keys][key_stride] for a
+ * keyed stream, NULL for a self-keyed one.  Results are DEVICE arrays [n_rows], each may be NULL: out_len[u] = n;
+ * nonfinite[u]; min_gain[u].  n = 0 is legal (a paused row).  out_dev past out_len is never written.
+ * GRAIL_ERR_INVALID_ARG, nothing queued: a stream that is not an open stream of this context (looked up, not looked into);
+ * a NULL buffer with samples to read or write, in_len_dev NULL; out_stride < in_stride; a keyed stream without key_dev, a
+ * self-keyed one with it; key_stride < in_stride; overlapping ranges.  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE. */
+int grail_dyn_stream_next_async(grail_ctx *ctx, grail_dyn_stream *ds, const float *in_dev, uint64_t in_stride,
+                                const uint32_t *in_len_dev, const float *key_dev, uint64_t key_stride, float *out_dev,
+                                uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev, double *min_gain_dev);
+/* Releases a stream once everything queued on ctx's stream is through; streams still open at grail_destroy go with the
+ * context.  NULL is a no-op.  GRAIL_ERR_INVALID_ARG: not an open stream of this context.  While a set has open streams,
+ * grail_dyn_free of it returns GRAIL_ERR_INVALID_ARG and frees nothing. */
+int grail_dyn_stream_close(grail_ctx *ctx, grail_dyn_stream *ds);
+
 /* ---- device memory plumbing ------------------------------------------- */
 int grail_device_alloc(grail_ctx *ctx, size_t bytes, void **out);
 int grail_device_free(grail_ctx *ctx, void *ptr);
