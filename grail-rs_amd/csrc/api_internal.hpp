@@ -221,6 +221,28 @@ private:
     size_t cap_ = 0;           // of what mem_ holds (a moved-from buffer keeps the number and holds nothing)
 };
 
+// max(count, 1) elements for dst, the first `count` of them copied from src (if any) on `stream`
+template <typename Tp>
+hipError_t upload(DeviceBuffer<Tp> &dst, const void *src, size_t count, hipStream_t stream)
+{
+    const hipError_t e = dst.alloc(count);
+    if (e != hipSuccess || !src || !count) return e;
+    return hipMemcpyAsync(dst.get(), src, count * sizeof(Tp), hipMemcpyHostToDevice, stream);
+}
+
+// What a stream bound to a set knows of each row: the row's filter, its curve or its key.  The host copy is kept while the
+// upload may be in flight.  fill: the caller's n_rows indices; where it gave none, 0 for every row (own_row: u for row u).
+struct RowIndex {
+    std::vector<uint32_t> host;
+    DeviceBuffer<uint32_t> dev;         // [n_rows]
+    hipError_t fill(const uint32_t *given, uint32_t n_rows, bool own_row, hipStream_t stream)
+    {
+        host.resize(n_rows);
+        for (uint32_t u = 0; u < n_rows; ++u) host[u] = given ? given[u] : (own_row ? u : 0u);
+        return upload(dev, host.data(), n_rows, stream);
+    }
+};
+
 // One hipHostMalloc allocation of `capacity()` bytes.  Grow-only users ask `capacity() < need` before they alloc.
 class PinnedBuffer {
 public:
@@ -368,8 +390,7 @@ struct ChunkedStream {
 // A stream of rows filtered call by call (fir_kernels.hip): one state word a row.
 struct grail_filter_stream : ChunkedStream {
     const grail_fir *set = nullptr;   // (a set with open streams is not freed); ring_cap is fir_stream_ring_capacity(set->taps_max)
-    std::vector<uint32_t> filter;     // the rows' filters (host copy, kept while the upload may be in flight)
-    grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows]
+    grail::host::RowIndex filter;     // the rows' filters
 };
 
 // A stream of rows resampled call by call (resample_kernels.hip), all on one pair of rates: three state words a row (samples
@@ -418,8 +439,7 @@ struct grail_iir {
 struct grail_iir_stream : ChunkedStream {
     const grail_iir *set = nullptr;   // (a set with open streams is not freed)
     uint32_t tail = 0;                // the outputs a row rings out over at its finish
-    std::vector<uint32_t> filter;     // the rows' filters (host copy, kept while the upload may be in flight)
-    grail::host::DeviceBuffer<uint32_t> d_filter;   // [n_rows]
+    grail::host::RowIndex filter;     // the rows' filters
 };
 
 // A set of gain curves with their ballistics (transforms.cpp; the image is dyn_plan.cpp's): owned by the context's TransformState,
@@ -439,10 +459,8 @@ struct grail_dyn {
 struct grail_dyn_stream : ChunkedStream {
     const grail_dyn *set = nullptr;   // (a set with open streams is not freed)
     uint32_t n_keys = 0;              // 0: self-keyed
-    std::vector<uint32_t> curve;      // the rows' curves and keys (host copies, kept while the upload may be in flight)
-    std::vector<uint32_t> key_row;
-    grail::host::DeviceBuffer<uint32_t> d_curve;    // [n_rows]
-    grail::host::DeviceBuffer<uint32_t> d_key_row;  // [n_rows] (a keyed stream's)
+    grail::host::RowIndex curve;      // the rows' curves
+    grail::host::RowIndex key_row;    // ... and keys (a keyed stream's; empty otherwise)
 };
 
 // What the launch policy reads of a batch, or of a row group of one: host facts only (copyable; grail_plan_ragged_blocks
@@ -524,15 +542,6 @@ int bind(grail_ctx *ctx);
 // ... for the device entry points that say their own name (levels.cpp, transforms.cpp, transform_streams.cpp): without a context, why there is none,
 // GRAIL_ERR_NO_DEVICE on a machine without a GPU
 int bind_device(grail_ctx *ctx, const char *who);
-
-// max(count, 1) elements for dst, the first `count` of them copied from src (if any) on `stream`
-template <typename Tp>
-hipError_t upload(DeviceBuffer<Tp> &dst, const void *src, size_t count, hipStream_t stream)
-{
-    const hipError_t e = dst.alloc(count);
-    if (e != hipSuccess || !src || !count) return e;
-    return hipMemcpyAsync(dst.get(), src, count * sizeof(Tp), hipMemcpyHostToDevice, stream);
-}
 
 // grail_api.cpp
 void name_voices(BatchFacts &b, const uint32_t *voice_ids, uint32_t n_utt);

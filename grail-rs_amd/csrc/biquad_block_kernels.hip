@@ -317,8 +317,7 @@ hipError_t block_launch(const BiquadBlockArgs &a, uint32_t bound, hipStream_t st
     if (workgroups == 0) return hipSuccess;
     if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
     // (the rest pass writes no samples: what it loads decides alone)
-    const bool vec = (reinterpret_cast<uintptr_t>(a.rows) & 15u) == 0 && (a.row_stride & 3u) == 0 &&
-                     (!OUT || ((reinterpret_cast<uintptr_t>(a.out) & 15u) == 0 && (a.out_stride & 3u) == 0));
+    const bool vec = aligned16(a.rows, a.row_stride) && (!OUT || aligned16(a.out, a.out_stride));
     if (bound <= 1u)
         block_launch_vec<1, OUT>(a, vec, (uint32_t)workgroups, stream);
     else if (bound == 2u)

@@ -285,16 +285,13 @@ void dyn_launch_keyed(const DynArgs &a, bool vec, uint32_t groups, hipStream_t s
         dyn_launch_vec<false, STREAM>(a, vec, groups, stream);
 }
 
-bool aligned16(const void *p, uint64_t stride) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0 && (stride & 3u) == 0; }
-
 }  // namespace
 
 hipError_t launch_dyn(const DynArgs &args, hipStream_t stream)
 {
     if (args.n_rows == 0) return hipSuccess;
     const uint32_t groups = (args.n_rows + LOUD_ROWS - 1u) / LOUD_ROWS;
-    const bool vec = aligned16(args.rows, args.row_stride) && aligned16(args.out, args.out_stride) &&
-                     (!args.key || aligned16(args.key, args.key_stride));
+    const bool vec = aligned16(args.rows, args.row_stride, args.out, args.out_stride) && (!args.key || aligned16(args.key, args.key_stride));
     if (args.state)
         dyn_launch_keyed<true>(args, vec, groups, stream);
     else

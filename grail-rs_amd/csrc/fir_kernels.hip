@@ -399,56 +399,44 @@ uint64_t fir_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t tail
     return chunks ? chunks : 1u;
 }
 
-hipError_t launch_fir(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, const uint32_t *filter,
-                      const double *taps, const uint32_t *desc, uint32_t n_filters, uint32_t grid_chunks, float *out,
-                      uint64_t out_stride, uint32_t *cbad, hipStream_t stream)
+hipError_t launch_fir(const FirArgs &a, hipStream_t stream)
 {
-    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
-    if (workgroups == 0) return hipSuccess;
-    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                     ((row_stride | out_stride) & 3u) == 0;
-    launch_either(vec, fir_kernel<true>, fir_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, rows, row_stride,
-                  len, n_rows, filter, taps, desc, n_filters, grid_chunks, out, out_stride, cbad);
+    const uint64_t workgroups = (uint64_t)a.n_rows * a.grid_chunks;
+    hipError_t e;
+    if (!grid_fits(workgroups, &e)) return e;
+    launch_either(aligned16(a.rows, a.row_stride, a.out, a.out_stride), fir_kernel<true>, fir_kernel<false>, dim3((uint32_t)workgroups),
+                  dim3(FIR_THREADS), 0, stream, a.rows, a.row_stride, a.len, a.n_rows, a.filter, a.taps, a.desc, a.n_filters, a.grid_chunks,
+                  a.out, a.out_stride, a.cbad);
     return hipGetLastError();
 }
 
-hipError_t launch_fir_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, const uint32_t *filter, const uint32_t *desc,
-                             uint32_t n_filters, uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                             uint32_t *nonfinite, hipStream_t stream)
+hipError_t launch_fir_totals(const FirArgs &a, hipStream_t stream)
 {
-    if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(fir_totals_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, stream, len, row_stride, n_rows, filter, desc,
-                       n_filters, out_stride, cbad, grid_chunks, out_len, nonfinite);
+    if (a.n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(fir_totals_kernel, dim3((a.n_rows + 255u) / 256u), dim3(256), 0, stream, a.len, a.row_stride, a.n_rows, a.filter,
+                       a.desc, a.n_filters, a.out_stride, a.cbad, a.grid_chunks, a.out_len, a.nonfinite);
     return hipGetLastError();
 }
 
-hipError_t launch_fir_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
-                             const double *taps, const uint32_t *desc, uint32_t n_filters, const uint64_t *state, const float *ring,
-                             uint32_t ring_cap, const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out,
-                             uint64_t out_stride, uint32_t *cbad, hipStream_t stream)
+hipError_t launch_fir_stream(const FirArgs &a, hipStream_t stream)
 {
-    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
-    if (workgroups == 0) return hipSuccess;
-    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                     ((in_stride | out_stride) & 3u) == 0;
-    launch_either(vec, fir_stream_kernel<true>, fir_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, in,
-                  in_stride, in_len, n_rows, filter, taps, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u,
-                  grid_chunks, out, out_stride, cbad);
+    const uint64_t workgroups = (uint64_t)a.n_rows * a.grid_chunks;
+    hipError_t e;
+    if (!grid_fits(workgroups, &e)) return e;
+    launch_either(aligned16(a.rows, a.row_stride, a.out, a.out_stride), fir_stream_kernel<true>, fir_stream_kernel<false>,
+                  dim3((uint32_t)workgroups), dim3(FIR_THREADS), 0, stream, a.rows, a.row_stride, a.len, a.n_rows, a.filter, a.taps,
+                  a.desc, a.n_filters, a.state, a.ring, a.ring_cap, a.mark, a.finishing ? 1u : 0u, a.grid_chunks, a.out, a.out_stride,
+                  a.cbad);
     return hipGetLastError();
 }
 
-hipError_t launch_fir_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
-                                     const uint32_t *desc, uint32_t n_filters, uint64_t *state, float *ring, uint32_t ring_cap,
-                                     const uint8_t *mark, bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                                     uint32_t *nonfinite, hipStream_t stream)
+hipError_t launch_fir_stream_advance(const FirArgs &a, hipStream_t stream)
 {
-    if (n_rows == 0) return hipSuccess;
+    if (a.n_rows == 0) return hipSuccess;
     const uint32_t rows_per_group = FIR_THREADS / 64u;
-    hipLaunchKernelGGL(fir_stream_advance_kernel, dim3(n_rows / rows_per_group + (n_rows % rows_per_group != 0u)), dim3(FIR_THREADS), 0, stream, in,
-                       in_stride, in_len, n_rows, filter, desc, n_filters, state, ring, ring_cap, mark, finishing ? 1u : 0u, cbad,
-                       grid_chunks, out_len, nonfinite);
+    hipLaunchKernelGGL(fir_stream_advance_kernel, dim3(a.n_rows / rows_per_group + (a.n_rows % rows_per_group != 0u)), dim3(FIR_THREADS), 0,
+                       stream, a.rows, a.row_stride, a.len, a.n_rows, a.filter, a.desc, a.n_filters, a.state, a.ring, a.ring_cap, a.mark,
+                       a.finishing ? 1u : 0u, a.cbad, a.grid_chunks, a.out_len, a.nonfinite);
     return hipGetLastError();
 }
 

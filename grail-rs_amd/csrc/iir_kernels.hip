@@ -247,8 +247,7 @@ hipError_t launch_iir(const IirArgs &args, uint32_t bound, hipStream_t stream)
 {
     if (args.n_rows == 0) return hipSuccess;
     const uint32_t groups = (args.n_rows + LOUD_ROWS - 1u) / LOUD_ROWS;
-    const bool vec = (reinterpret_cast<uintptr_t>(args.rows) & 15u) == 0 && (args.row_stride & 3u) == 0 &&
-                     (reinterpret_cast<uintptr_t>(args.out) & 15u) == 0 && (args.out_stride & 3u) == 0;
+    const bool vec = aligned16(args.rows, args.row_stride, args.out, args.out_stride);
     if (args.state)
         iir_launch_bound<true>(args, bound, vec, groups, stream);
     else

@@ -212,134 +212,132 @@ hipError_t launch_true_peak_totals(const uint32_t *len, uint64_t row_stride, uin
                                    const uint32_t *cbad, uint32_t grid_chunks, double *true_peak, uint32_t *nonfinite,
                                    hipStream_t stream);
 
-// limiter (limiter_kernels.hip): one workgroup per (group of `group` consecutive rows, chunk of LIMIT_CHUNK samples),
-// grid_chunks = limit_grid_chunks(row_stride) of them per group; the limited rows go to out, the chunk's numbers
-// (limit_chunk_bytes() each) to cstat[group * grid_chunks + c] (chunks past a group's last and the chunks of a group whose
-// members differ in length are left unwritten, as is out there).  ceiling finite and > 0, lookahead_log2 <= 10.
-constexpr uint32_t LIMIT_CHUNK = 4096;      // == GRAIL_LIMIT_CHUNK (not part of the contract: no number depends on it)
-uint64_t limit_grid_chunks(uint64_t row_stride);
-size_t limit_chunk_bytes();
-hipError_t launch_limit_frames(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_groups, uint32_t group,
-                               float ceiling, uint32_t lookahead_log2, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                               void *cstat, hipStream_t stream);
-// ... and a group's smallest gain, its count of limited samples and of non-finite ones, one lane per group (outputs may
-// be NULL); a refused group reads NaN, 0xFFFFFFFF, 0
-hipError_t launch_limit_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_groups, uint32_t group,
-                               uint32_t lookahead_log2, const void *cstat, uint32_t grid_chunks, float *min_gain,
-                               uint32_t *n_limited, uint32_t *nonfinite, hipStream_t stream);
-
-// sample-rate conversion (resample_kernels.hip): one workgroup per (row, chunk of RESAMPLE_CHUNK outputs), grid_chunks =
-// resample_grid_chunks(row_stride, out_stride, U, D) of them per row; the resampled rows go to out, the count of non-finite
-// input samples a chunk owns to cbad[row * grid_chunks + c] (chunks past a row's last are left unwritten, as is out
-// there).  table: device [U][P] numerators of 2^26 (grail_resample_coefficients).
-constexpr uint32_t RESAMPLE_CHUNK = 1024;   // == GRAIL_RESAMPLE_CHUNK (not part of the contract: no number depends on it)
-uint64_t resample_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t U, uint32_t D);
-hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D,
-                           uint32_t P, const int32_t *table, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                           uint32_t *cbad, hipStream_t stream);
-// ... and a row's out_len = min(ceil(n U / D), out_stride) and count from them, one lane per row (outputs may be NULL)
-hipError_t launch_resample_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t U, uint32_t D,
-                                  uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                                  uint32_t *nonfinite, hipStream_t stream);
-
-// FIR filtering (fir_kernels.hip): one workgroup per (row, chunk of FIR_CHUNK outputs), grid_chunks = fir_grid_chunks(
-// row_stride, out_stride, the set's longest tail) of them per row; the filtered rows go to out, the count of non-finite
-// input samples a chunk owns to cbad[row * grid_chunks + c] (chunks past a row's last are left unwritten, as is out there,
-// and as is everything of a row whose filter index is outside the set).  taps: device, the set's image as binary64, every
-// filter padded with +0.0 to a multiple of 8; desc: device [n_filters][4] = {first tap, padded taps, taps, origin}
-// (fir_plan.h); filter: device [n_rows] or NULL (filter 0 for every row).
-constexpr uint32_t FIR_CHUNK = 2048;   // == GRAIL_FIR_CHUNK (not part of the contract: no number depends on it)
-uint64_t fir_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t tail_max);
-hipError_t launch_fir(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, const uint32_t *filter,
-                      const double *taps, const uint32_t *desc, uint32_t n_filters, uint32_t grid_chunks, float *out,
-                      uint64_t out_stride, uint32_t *cbad, hipStream_t stream);
-// ... and a row's out_len = min(n + K - 1 - o, out_stride) and count from them, one lane per row (outputs may be NULL);
-// a refused row: 0xFFFFFFFF and 0
-hipError_t launch_fir_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, const uint32_t *filter, const uint32_t *desc,
-                             uint32_t n_filters, uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                             uint32_t *nonfinite, hipStream_t stream);
-
+// Row transforms (limiter, resampler, FIR, meter streams): one struct of arguments a kind, taken by every launcher of the kind,
+// one-shot and on streams alike.  A launcher hands its kernel the fields that the kernel's parameters name
+// (tests/test_launch_args_host.py holds them to it).  Every pointer is DEVICE unless it says HOST; every result may be NULL.
 // Streams: rows (the limiter: groups of rows) fed call by call.  What every kind keeps, said once in row_kernel_common.h:
 // the state word (the samples fed so far, bit 63 set once the row has ended), word 0 of a row's state, and a ring of ring_cap
 // samples a row, ring_cap a power of two: sample t of a row at t mod ring_cap, +0.0 where it was not finite.  A call launches
 // a chunk kernel that reads state and ring and writes out and the chunks' numbers (grid_chunks of them a row: enough for the
 // most outputs a row can have in the call, *_plan.cpp), then an advance kernel, the only writer of state and ring.  A row
 // that has ended and is fed is refused: 0xFFFFFFFF where its length would stand, 0 non-finite samples, nothing else.
-// finishing: in and in_len are not read (no samples are fed), the rows with mark[u] != 0 (mark NULL: every row) that have
-// not ended write their tail and end; nonfinite is not written.
-//
-// FIR filtering of streams (fir_kernels.hip): state: device [n_rows], the state word; ring: device [n_rows][ring_cap], at or
-// above the set's longest n_taps - 1.  One workgroup per (row, chunk of FIR_CHUNK of the call's outputs).  filter: device
-// [n_rows], checked by the host.
-hipError_t launch_fir_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
-                             const double *taps, const uint32_t *desc, uint32_t n_filters, const uint64_t *state, const float *ring,
-                             uint32_t ring_cap, const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out,
-                             uint64_t out_stride, uint32_t *cbad, hipStream_t stream);
-// ... and a row's out_len and count from its chunks, its last samples into the ring and its state advanced, one wave per
-// row (outputs may be NULL)
-hipError_t launch_fir_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, const uint32_t *filter,
-                                     const uint32_t *desc, uint32_t n_filters, uint64_t *state, float *ring, uint32_t ring_cap,
-                                     const uint8_t *mark, bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                                     uint32_t *nonfinite, hipStream_t stream);
+struct RowCallArgs {
+    const float *rows;      // [n_rows][row_stride]; row u holds min(len[u], row_stride) samples.  On a stream: the samples the
+    uint64_t row_stride;    // call feeds (the kernels' in, in_stride, in_len)
+    const uint32_t *len;    // [n_rows]
+    uint64_t *state;        // from here on: a call on a stream (a one-shot call leaves the five zero).  [units][the kind's words],
+                            // word 0 the state word; units: the rows, or the limiter's groups
+    float *ring;            // [n_rows][ring_cap]
+    uint32_t ring_cap;
+    const uint8_t *mark;    // [units] or NULL (every unit): whom a finishing call ends
+    bool finishing;         // rows and len are not read (no samples are fed), the marked units that have not ended write their
+                            // tail and end; nonfinite is not written
+};
 
-// sample-rate conversion of streams (resample_kernels.hip): all rows on one pair of rates.  state: device
-// [n_rows][RESAMPLE_STREAM_STATE_WORDS] = {the state word, the input time floor(M D / U) of the row's next output M, the
-// phase M D mod U}; ring: device [n_rows][ring_cap], at or above P - 1.  One workgroup per (row, chunk of
-// RESAMPLE_STREAM_CHUNK of the call's outputs).
+// The two rules every launcher of these kinds follows.  A kernel's VEC instantiation (16-byte accesses) runs where the rows it
+// touches start on 16 bytes and lie a multiple of 4 samples apart, else its 4-byte one: the same bits.
+inline bool aligned16(const void *rows, uint64_t stride) { return (reinterpret_cast<uintptr_t>(rows) & 15u) == 0 && (stride & 3u) == 0; }
+inline bool aligned16(const void *a, uint64_t a_stride, const void *b, uint64_t b_stride) { return aligned16(a, a_stride) && aligned16(b, b_stride); }
+// A grid of `workgroups` is launched (true) unless there are none (*e = hipSuccess) or more than 2^31 - 1 (hipErrorInvalidValue).
+inline bool grid_fits(uint64_t workgroups, hipError_t *e)
+{
+    *e = workgroups > 0x7FFFFFFFull ? hipErrorInvalidValue : hipSuccess;
+    return workgroups != 0 && *e == hipSuccess;
+}
+
+// limiter (limiter_kernels.hip): one workgroup per (group of `group` consecutive rows, chunk of LIMIT_CHUNK samples; a stream:
+// of the call's outputs).  state: [n_groups]; ring: [n_groups * group][at or above 3 * 2^ell + 19]; mark: [n_groups].  A group
+// whose members differ in length (a stream: are fed different n, or that has ended and is fed) is refused: out_len 0xFFFFFFFF,
+// min_gain NaN, n_limited 0xFFFFFFFF (a stream: 0), nonfinite 0, nothing else written.
+constexpr uint32_t LIMIT_CHUNK = 4096;      // == GRAIL_LIMIT_CHUNK (not part of the contract: no number depends on it)
+uint64_t limit_grid_chunks(uint64_t row_stride);
+size_t limit_chunk_bytes();
+struct LimitArgs : RowCallArgs {
+    uint32_t n_groups, group;
+    float ceiling;              // finite and > 0
+    uint32_t ell;               // lookahead_log2, <= 10
+    uint32_t grid_chunks;       // limit_grid_chunks(row_stride) a group; a stream's chunk kernel runs only when != 0
+    float *out;                 // the limited rows (chunks past a group's last are left unwritten)
+    uint64_t out_stride;
+    void *cstat;                // the chunks' numbers, limit_chunk_bytes() each, at [group * grid_chunks + c]
+    uint32_t *out_len, *n_limited, *nonfinite;  // [n_groups] each: a group's outputs of the call (streams only), its limited
+    float *min_gain;                            // and its non-finite samples, its smallest gain
+};
+hipError_t launch_limit_frames(const LimitArgs &a, hipStream_t stream);
+hipError_t launch_limit_totals(const LimitArgs &a, hipStream_t stream);             // one lane per group: the results from cstat
+hipError_t launch_limit_stream(const LimitArgs &a, hipStream_t stream);
+hipError_t launch_limit_stream_advance(const LimitArgs &a, hipStream_t stream);     // one wave per group: results, rings, state
+
+// sample-rate conversion (resample_kernels.hip): one workgroup per (row, chunk of RESAMPLE_CHUNK outputs; a stream: of
+// RESAMPLE_STREAM_CHUNK of the call's outputs), all rows on one pair of rates.  state: [n_rows][RESAMPLE_STREAM_STATE_WORDS] =
+// {the state word, the input time floor(M D / U) of the row's next output M, the phase M D mod U}; ring: [n_rows][at or above P - 1].
+constexpr uint32_t RESAMPLE_CHUNK = 1024;   // == GRAIL_RESAMPLE_CHUNK (not part of the contract: no number depends on it)
 constexpr uint32_t RESAMPLE_STREAM_STATE_WORDS = 3;
-hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D,
-                                  uint32_t P, const int32_t *table, const uint64_t *state, const float *ring, uint32_t ring_cap,
-                                  const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                                  uint32_t *cbad, hipStream_t stream);
-// ... and a row's out_len and count from its chunks, its last samples into the ring and its state advanced, one wave per
-// row (outputs may be NULL)
-hipError_t launch_resample_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U,
-                                          uint32_t D, uint32_t P, uint64_t *state, float *ring, uint32_t ring_cap, const uint8_t *mark,
-                                          bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                                          uint32_t *nonfinite, hipStream_t stream);
+uint64_t resample_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t U, uint32_t D);
+struct ResampleArgs : RowCallArgs {
+    uint32_t n_rows, up, down, taps;    // up, down, taps: grail_resample_ratio's U, D and P (the taps of one phase)
+    const int32_t *table;       // [up][taps] numerators of 2^26 (grail_resample_coefficients)
+    uint32_t grid_chunks;       // resample_grid_chunks(row_stride, out_stride, up, down) a row
+    float *out;                 // the resampled rows (chunks past a row's last are left unwritten)
+    uint64_t out_stride;
+    uint32_t *cbad;             // the non-finite input samples a chunk owns, at [row * grid_chunks + c]
+    uint32_t *out_len, *nonfinite;      // [n_rows]: min(ceil(n U / D), out_stride) (a stream: the call's outputs), and the count
+};
+hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream);
+hipError_t launch_resample_totals(const ResampleArgs &a, hipStream_t stream);           // one lane per row: the results from cbad
+hipError_t launch_resample_stream(const ResampleArgs &a, hipStream_t stream);
+hipError_t launch_resample_stream_advance(const ResampleArgs &a, hipStream_t stream);   // one wave per row: results, ring, state
 
-// the limiter on streams (limiter_kernels.hip): groups of rows, one ceiling and look-ahead for all.  state: device
-// [n_groups], the state word of a group's members; ring: device [n_groups * group][ring_cap], at or above
-// 3 * 2^lookahead_log2 + 19.  The chunk kernel only when grid_chunks != 0: one workgroup per (group, chunk of LIMIT_CHUNK
-// of the call's outputs), the chunk's numbers (limit_chunk_bytes() each) to cstat[group * grid_chunks + c].  mark: device
-// [n_groups].
-hipError_t launch_limit_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups, uint32_t group,
-                               float ceiling, uint32_t lookahead_log2, const uint64_t *state, const float *ring, uint32_t ring_cap,
-                               const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                               void *cstat, hipStream_t stream);
-// ... and a group's out_len and numbers from its chunks, its members' last samples into their rings and its state advanced,
-// one wave per group (outputs may be NULL); a group whose members are fed different n, or that has ended and is fed:
-// 0xFFFFFFFF, NaN, 0, 0, nothing else
-hipError_t launch_limit_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups,
-                                       uint32_t group, uint32_t lookahead_log2, uint64_t *state, float *ring, uint32_t ring_cap,
-                                       const uint8_t *mark, bool finishing, const void *cstat, uint32_t grid_chunks,
-                                       uint32_t *out_len, float *min_gain, uint32_t *n_limited, uint32_t *nonfinite,
-                                       hipStream_t stream);
+// FIR filtering (fir_kernels.hip): one workgroup per (row, chunk of FIR_CHUNK outputs; a stream: of the call's outputs).  state:
+// [n_rows], the state word; ring: [n_rows][at or above the set's longest n_taps - 1].  A row whose filter index is outside the
+// set: 0xFFFFFFFF and 0, nothing of it written (a stream's indices were checked by the host).
+constexpr uint32_t FIR_CHUNK = 2048;   // == GRAIL_FIR_CHUNK (not part of the contract: no number depends on it)
+uint64_t fir_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t tail_max);
+struct FirArgs : RowCallArgs {
+    uint32_t n_rows;
+    const uint32_t *filter;     // [n_rows] or NULL (filter 0 for every row)
+    const double *taps;         // the set's image as binary64, every filter padded with +0.0 to a multiple of 8
+    const uint32_t *desc;       // [n_filters][4] = {first tap, padded taps, taps, origin} (fir_plan.h)
+    uint32_t n_filters;
+    uint32_t grid_chunks;       // fir_grid_chunks(row_stride, out_stride, the set's longest tail) a row
+    float *out;                 // the filtered rows (chunks past a row's last are left unwritten)
+    uint64_t out_stride;
+    uint32_t *cbad;             // the non-finite input samples a chunk owns, at [row * grid_chunks + c]
+    uint32_t *out_len, *nonfinite;      // [n_rows]: min(n + K - 1 - o, out_stride) (a stream: the call's outputs), and the count
+};
+hipError_t launch_fir(const FirArgs &a, hipStream_t stream);
+hipError_t launch_fir_totals(const FirArgs &a, hipStream_t stream);             // one lane per row: the results from cbad
+hipError_t launch_fir_stream(const FirArgs &a, hipStream_t stream);
+hipError_t launch_fir_stream_advance(const FirArgs &a, hipStream_t stream);     // one wave per row: results, ring, state
 
-// meter streams (meter_stream_kernels.hip): rows metered call by call.  state: DEVICE [n_rows][METER_STREAM_STATE_WORDS] (word 0:
-// the state word; 1 .. 5: s1 .. s4 and acc as their bits; 6: the running true peak; 7: the hops completed), ring:
-// DEVICE [n_rows][METER_STREAM_RING], ledger: DEVICE [n_rows][max_hops].  A call is three launches in this order: the hops (one
-// lane per row; a feeding call only), the call's true peak (one wave per row and chunk of METER_STREAM_CHUNK output times,
-// grid_chunks of them a row, the chunk's maximum and non-finite count to cmax / cbad [row * grid_chunks + c]), the advance (one
-// wave per row: the call's results, any of which may be NULL, the ring, N, the running peak, the hop count).  The first two
-// read N and the hop count, only the third writes them.  coef: HOST [10].  A row that has ended and is fed, or that the call
-// would carry past max_hops: 0xFFFFFFFF, NaN, 0, nothing else.
+// meter streams (meter_stream_kernels.hip): rows metered call by call.  A call is three launches in this order: the hops (one
+// lane per row; a feeding call only), the call's true peak (one wave per row and chunk of METER_STREAM_CHUNK output times), the
+// advance (one wave per row: the call's results, the ring, N, the running peak, the hop count).  The first two read N and the
+// hop count, only the third writes them.  state: [n_rows][METER_STREAM_STATE_WORDS] (word 0: the state word; 1 .. 5: s1 .. s4
+// and acc as their bits; 6: the running true peak; 7: the hops completed); ring: [n_rows][METER_STREAM_RING].  A row that has
+// ended and is fed, or that the call would carry past max_hops: 0xFFFFFFFF, NaN, 0, nothing else.
 constexpr uint32_t METER_STREAM_STATE_WORDS = 8;
 constexpr uint32_t METER_STREAM_RING = 16;
 constexpr uint32_t METER_STREAM_CHUNK = 4096;
-hipError_t launch_meter_stream_hops(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
-                                    const double *coef, uint64_t *state, double *ledger, uint64_t max_hops, double *hops_out,
-                                    uint64_t hops_stride, hipStream_t stream);
-hipError_t launch_meter_stream_peak(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
-                                    const uint64_t *state, uint64_t max_hops, const float *ring, const uint8_t *mark, bool finishing,
-                                    uint32_t grid_chunks, double *cmax, uint32_t *cbad, hipStream_t stream);
-hipError_t launch_meter_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
-                                       uint64_t *state, uint64_t max_hops, float *ring, const uint8_t *mark, bool finishing,
-                                       const double *cmax, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *n_hops,
-                                       double *true_peak, uint32_t *nonfinite, hipStream_t stream);
+struct MeterStreamArgs : RowCallArgs {
+    uint32_t n_rows, hop;
+    const double *coef;         // HOST [10], the K-weighting
+    double *ledger;             // [n_rows][max_hops]: every hop sum of a row so far
+    uint64_t max_hops;
+    double *hops_out;           // [n_rows][hops_stride] or NULL: the hop sums this call completes
+    uint64_t hops_stride;
+    uint32_t grid_chunks;       // chunks of output times a row
+    double *cmax;               // a chunk's largest |y| and its non-finite count, each at [row * grid_chunks + c]
+    uint32_t *cbad;
+    uint32_t *n_hops, *nonfinite;       // [n_rows] each: the hops the call completed, its non-finite samples, its true peak
+    double *true_peak;
+};
+hipError_t launch_meter_stream_hops(const MeterStreamArgs &a, hipStream_t stream);
+hipError_t launch_meter_stream_peak(const MeterStreamArgs &a, hipStream_t stream);
+hipError_t launch_meter_stream_advance(const MeterStreamArgs &a, hipStream_t stream);
 // ... and what a meter shows of every row now, one lane per row (outputs may be NULL); changes nothing
 hipError_t launch_meter_stream_read(const uint64_t *state, uint32_t n_rows, uint32_t hop, const double *ledger, uint64_t max_hops,
-                                    double *integrated, double *momentary, double *short_term, double *true_peak, uint64_t *hops,
+                                    double *integrated, double *momentary, double *short_term, double *true_peak, uint64_t *hops_out,
                                     hipStream_t stream);
 
 // recursive filtering (iir_kernels.hip): one lane per row through the S sections of its filter, 64 rows to a wave, the

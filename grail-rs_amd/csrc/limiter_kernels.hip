@@ -681,56 +681,43 @@ uint64_t limit_grid_chunks(uint64_t row_stride) { return (row_stride + LIMIT_CHU
 
 size_t limit_chunk_bytes() { return sizeof(LimitChunk); }
 
-hipError_t launch_limit_frames(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_groups, uint32_t group,
-                               float ceiling, uint32_t lookahead_log2, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                               void *cstat, hipStream_t stream)
+hipError_t launch_limit_frames(const LimitArgs &a, hipStream_t stream)
 {
-    const uint64_t workgroups = (uint64_t)n_groups * grid_chunks;
-    if (workgroups == 0) return hipSuccess;
-    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                     ((row_stride | out_stride) & 3u) == 0;
-    launch_either(vec, limit_frames_kernel<true>, limit_frames_kernel<false>, dim3((uint32_t)workgroups), dim3(256), 0, stream, rows,
-                  row_stride, len, n_groups, group, ceiling, lookahead_log2, grid_chunks, out, out_stride, (LimitChunk *)cstat);
+    const uint64_t workgroups = (uint64_t)a.n_groups * a.grid_chunks;
+    hipError_t e;
+    if (!grid_fits(workgroups, &e)) return e;
+    launch_either(aligned16(a.rows, a.row_stride, a.out, a.out_stride), limit_frames_kernel<true>, limit_frames_kernel<false>,
+                  dim3((uint32_t)workgroups), dim3(256), 0, stream, a.rows, a.row_stride, a.len, a.n_groups, a.group, a.ceiling,
+                  a.ell, a.grid_chunks, a.out, a.out_stride, (LimitChunk *)a.cstat);
     return hipGetLastError();
 }
 
-hipError_t launch_limit_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_groups, uint32_t group,
-                               uint32_t lookahead_log2, const void *cstat, uint32_t grid_chunks, float *min_gain,
-                               uint32_t *n_limited, uint32_t *nonfinite, hipStream_t stream)
+hipError_t launch_limit_totals(const LimitArgs &a, hipStream_t stream)
 {
-    if (n_groups == 0) return hipSuccess;
-    hipLaunchKernelGGL(limit_totals_kernel, dim3((n_groups + 255u) / 256u), dim3(256), 0, stream, len, row_stride, n_groups,
-                       group, lookahead_log2, (const LimitChunk *)cstat, grid_chunks, min_gain, n_limited, nonfinite);
+    if (a.n_groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(limit_totals_kernel, dim3((a.n_groups + 255u) / 256u), dim3(256), 0, stream, a.len, a.row_stride, a.n_groups,
+                       a.group, a.ell, (const LimitChunk *)a.cstat, a.grid_chunks, a.min_gain, a.n_limited, a.nonfinite);
     return hipGetLastError();
 }
 
-hipError_t launch_limit_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups, uint32_t group,
-                               float ceiling, uint32_t lookahead_log2, const uint64_t *state, const float *ring, uint32_t ring_cap,
-                               const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                               void *cstat, hipStream_t stream)
+hipError_t launch_limit_stream(const LimitArgs &a, hipStream_t stream)
 {
-    const uint64_t workgroups = (uint64_t)n_groups * grid_chunks;
-    if (workgroups == 0) return hipSuccess;
-    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                     ((in_stride | out_stride) & 3u) == 0;
-    launch_either(vec, limit_stream_kernel<true>, limit_stream_kernel<false>, dim3((uint32_t)workgroups), dim3(256), 0, stream, in,
-                  in_stride, in_len, n_groups, group, ceiling, lookahead_log2, state, ring, ring_cap, mark, finishing ? 1u : 0u,
-                  grid_chunks, out, out_stride, (LimitChunk *)cstat);
+    const uint64_t workgroups = (uint64_t)a.n_groups * a.grid_chunks;
+    hipError_t e;
+    if (!grid_fits(workgroups, &e)) return e;
+    launch_either(aligned16(a.rows, a.row_stride, a.out, a.out_stride), limit_stream_kernel<true>, limit_stream_kernel<false>,
+                  dim3((uint32_t)workgroups), dim3(256), 0, stream, a.rows, a.row_stride, a.len, a.n_groups, a.group, a.ceiling,
+                  a.ell, a.state, a.ring, a.ring_cap, a.mark, a.finishing ? 1u : 0u, a.grid_chunks, a.out, a.out_stride,
+                  (LimitChunk *)a.cstat);
     return hipGetLastError();
 }
 
-hipError_t launch_limit_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_groups,
-                                       uint32_t group, uint32_t lookahead_log2, uint64_t *state, float *ring, uint32_t ring_cap,
-                                       const uint8_t *mark, bool finishing, const void *cstat, uint32_t grid_chunks,
-                                       uint32_t *out_len, float *min_gain, uint32_t *n_limited, uint32_t *nonfinite,
-                                       hipStream_t stream)
+hipError_t launch_limit_stream_advance(const LimitArgs &a, hipStream_t stream)
 {
-    if (n_groups == 0) return hipSuccess;
-    hipLaunchKernelGGL(limit_stream_advance_kernel, dim3(n_groups / 4u + (n_groups % 4u != 0u)), dim3(256), 0, stream, in, in_stride,
-                       in_len, n_groups, group, lookahead_log2, state, ring, ring_cap, mark, finishing ? 1u : 0u,
-                       (const LimitChunk *)cstat, grid_chunks, out_len, min_gain, n_limited, nonfinite);
+    if (a.n_groups == 0) return hipSuccess;
+    hipLaunchKernelGGL(limit_stream_advance_kernel, dim3(a.n_groups / 4u + (a.n_groups % 4u != 0u)), dim3(256), 0, stream, a.rows,
+                       a.row_stride, a.len, a.n_groups, a.group, a.ell, a.state, a.ring, a.ring_cap, a.mark, a.finishing ? 1u : 0u,
+                       (const LimitChunk *)a.cstat, a.grid_chunks, a.out_len, a.min_gain, a.n_limited, a.nonfinite);
     return hipGetLastError();
 }
 

@@ -441,63 +441,46 @@ __global__ __launch_bounds__(256) void meter_stream_read_kernel(const uint64_t *
     integrated[u] = count ? sum / (double)count : 0.0;
 }
 
-bool meter_vec(const float *in, uint64_t in_stride) { return (reinterpret_cast<uintptr_t>(in) & 15u) == 0 && (in_stride & 3u) == 0; }
-
 }  // namespace
 
-hipError_t launch_meter_stream_hops(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
-                                    const double *coef, uint64_t *state, double *ledger, uint64_t max_hops, double *hops_out,
-                                    uint64_t hops_stride, hipStream_t stream)
+hipError_t launch_meter_stream_hops(const MeterStreamArgs &a, hipStream_t stream)
 {
-    if (n_rows == 0 || in_stride == 0) return hipSuccess;
-    LoudCoef c;
-    for (int i = 0; i < 10; ++i) c.c[i] = coef[i];
-    const uint32_t groups = (n_rows + LOUD_ROWS - 1u) / LOUD_ROWS;
-    if (meter_vec(in, in_stride))
-        hipLaunchKernelGGL(meter_stream_hops_kernel<true>, dim3(groups), dim3(64), 0, stream, in, in_stride, in_len, n_rows, hop, c,
-                           state, ledger, max_hops, hops_out, hops_stride);
-    else
-        hipLaunchKernelGGL(meter_stream_hops_kernel<false>, dim3(groups), dim3(64), 0, stream, in, in_stride, in_len, n_rows, hop, c,
-                           state, ledger, max_hops, hops_out, hops_stride);
+    if (a.n_rows == 0 || a.row_stride == 0) return hipSuccess;
+    LoudCoef coef;
+    for (int i = 0; i < 10; ++i) coef.c[i] = a.coef[i];
+    launch_either(aligned16(a.rows, a.row_stride), meter_stream_hops_kernel<true>, meter_stream_hops_kernel<false>,
+                  dim3((a.n_rows + LOUD_ROWS - 1u) / LOUD_ROWS), dim3(64), 0, stream, a.rows, a.row_stride, a.len, a.n_rows, a.hop, coef,
+                  a.state, a.ledger, a.max_hops, a.hops_out, a.hops_stride);
     return hipGetLastError();
 }
 
-hipError_t launch_meter_stream_peak(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
-                                    const uint64_t *state, uint64_t max_hops, const float *ring, const uint8_t *mark, bool finishing,
-                                    uint32_t grid_chunks, double *cmax, uint32_t *cbad, hipStream_t stream)
+hipError_t launch_meter_stream_peak(const MeterStreamArgs &a, hipStream_t stream)
 {
-    const uint64_t waves = (uint64_t)n_rows * grid_chunks;
-    if (waves == 0) return hipSuccess;
-    const uint64_t groups = (waves + 3u) / 4u;
-    if (groups > 0x7FFFFFFFull) return hipErrorInvalidValue;
-    if (finishing || meter_vec(in, in_stride))
-        hipLaunchKernelGGL(meter_stream_peak_kernel<true>, dim3((uint32_t)groups), dim3(256), 0, stream, in, in_stride, in_len, n_rows,
-                           hop, state, max_hops, ring, mark, finishing ? 1u : 0u, grid_chunks, cmax, cbad);
-    else
-        hipLaunchKernelGGL(meter_stream_peak_kernel<false>, dim3((uint32_t)groups), dim3(256), 0, stream, in, in_stride, in_len, n_rows,
-                           hop, state, max_hops, ring, mark, finishing ? 1u : 0u, grid_chunks, cmax, cbad);
+    const uint64_t groups = ((uint64_t)a.n_rows * a.grid_chunks + 3u) / 4u;        // (four waves, one a (row, chunk), to a workgroup)
+    hipError_t e;
+    if (!grid_fits(groups, &e)) return e;
+    launch_either(a.finishing || aligned16(a.rows, a.row_stride), meter_stream_peak_kernel<true>, meter_stream_peak_kernel<false>,
+                  dim3((uint32_t)groups), dim3(256), 0, stream, a.rows, a.row_stride, a.len, a.n_rows, a.hop, a.state, a.max_hops, a.ring,
+                  a.mark, a.finishing ? 1u : 0u, a.grid_chunks, a.cmax, a.cbad);
     return hipGetLastError();
 }
 
-hipError_t launch_meter_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t hop,
-                                       uint64_t *state, uint64_t max_hops, float *ring, const uint8_t *mark, bool finishing,
-                                       const double *cmax, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *n_hops,
-                                       double *true_peak, uint32_t *nonfinite, hipStream_t stream)
+hipError_t launch_meter_stream_advance(const MeterStreamArgs &a, hipStream_t stream)
 {
-    if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(meter_stream_advance_kernel, dim3(n_rows / 4u + (n_rows % 4u != 0u)), dim3(256), 0, stream, in, in_stride,
-                       in_len, n_rows, hop, state, max_hops, ring, mark, finishing ? 1u : 0u, cmax, cbad, grid_chunks, n_hops,
-                       true_peak, nonfinite);
+    if (a.n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(meter_stream_advance_kernel, dim3(a.n_rows / 4u + (a.n_rows % 4u != 0u)), dim3(256), 0, stream, a.rows,
+                       a.row_stride, a.len, a.n_rows, a.hop, a.state, a.max_hops, a.ring, a.mark, a.finishing ? 1u : 0u, a.cmax, a.cbad,
+                       a.grid_chunks, a.n_hops, a.true_peak, a.nonfinite);
     return hipGetLastError();
 }
 
 hipError_t launch_meter_stream_read(const uint64_t *state, uint32_t n_rows, uint32_t hop, const double *ledger, uint64_t max_hops,
-                                    double *integrated, double *momentary, double *short_term, double *true_peak, uint64_t *hops,
+                                    double *integrated, double *momentary, double *short_term, double *true_peak, uint64_t *hops_out,
                                     hipStream_t stream)
 {
     if (n_rows == 0) return hipSuccess;
     hipLaunchKernelGGL(meter_stream_read_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, stream, state, n_rows, hop, ledger,
-                       max_hops, integrated, momentary, short_term, true_peak, hops);
+                       max_hops, integrated, momentary, short_term, true_peak, hops_out);
     return hipGetLastError();
 }
 

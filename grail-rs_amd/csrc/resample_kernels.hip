@@ -502,13 +502,12 @@ uint64_t resample_grid_chunks(uint64_t row_stride, uint64_t out_stride, uint32_t
     return chunks ? chunks : 1u;
 }
 
-hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_t *len, uint32_t n_rows, uint32_t U, uint32_t D,
-                           uint32_t P, const int32_t *table, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                           uint32_t *cbad, hipStream_t stream)
+hipError_t launch_resample(const ResampleArgs &a, hipStream_t stream)
 {
-    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
-    if (workgroups == 0) return hipSuccess;
-    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t workgroups = (uint64_t)a.n_rows * a.grid_chunks;
+    hipError_t e;
+    if (!grid_fits(workgroups, &e)) return e;
+    const uint32_t U = a.up, D = a.down, P = a.taps;
     // the longest stretch of a chunk: floor((U - 1 + (RESAMPLE_CHUNK - 1) D) / U) + P samples, and the rounding to groups of 4
     const uint64_t stretch = ((uint64_t)(U - 1u) + (uint64_t)(RESAMPLE_CHUNK - 1u) * D) / U + P + RS_STAGE_SLACK;
     const uint64_t staged_bytes = (RESAMPLE_CHUNK + stretch) * 4u, table_bytes = (uint64_t)U * (P + 1u) * 4u;
@@ -516,23 +515,20 @@ hipError_t launch_resample(const float *rows, uint64_t row_stride, const uint32_
     const int tab = U == 1u ? RS_TAB_UNIFORM : (staged && staged_bytes + table_bytes <= RS_LDS_MAX ? RS_TAB_LDS : RS_TAB_GLOBAL);
     const uint32_t stage_words = staged ? (uint32_t)stretch : 0u;
     const uint32_t lds = (uint32_t)((staged ? staged_bytes : RESAMPLE_CHUNK * 4u) + (tab == RS_TAB_LDS ? table_bytes : 0u));
-    const bool vec = ((reinterpret_cast<uintptr_t>(rows) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                     ((row_stride | out_stride) & 3u) == 0;
-    launch_either(vec, staged ? resample_variant<true, true>(tab) : resample_variant<false, true>(tab),
+    launch_either(aligned16(a.rows, a.row_stride, a.out, a.out_stride),
+                  staged ? resample_variant<true, true>(tab) : resample_variant<false, true>(tab),
                   staged ? resample_variant<true, false>(tab) : resample_variant<false, false>(tab), dim3((uint32_t)workgroups),
-                  dim3(RS_THREADS), lds, stream, rows, row_stride, len, n_rows, U, D, P, table, stage_words, grid_chunks, out, out_stride,
-                  cbad);
+                  dim3(RS_THREADS), lds, stream, a.rows, a.row_stride, a.len, a.n_rows, a.up, a.down, a.taps, a.table, stage_words,
+                  a.grid_chunks, a.out, a.out_stride, a.cbad);
     return hipGetLastError();
 }
 
-hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U, uint32_t D,
-                                  uint32_t P, const int32_t *table, const uint64_t *state, const float *ring, uint32_t ring_cap,
-                                  const uint8_t *mark, bool finishing, uint32_t grid_chunks, float *out, uint64_t out_stride,
-                                  uint32_t *cbad, hipStream_t stream)
+hipError_t launch_resample_stream(const ResampleArgs &a, hipStream_t stream)
 {
-    const uint64_t workgroups = (uint64_t)n_rows * grid_chunks;
-    if (workgroups == 0) return hipSuccess;
-    if (workgroups > 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const uint64_t workgroups = (uint64_t)a.n_rows * a.grid_chunks;
+    hipError_t e;
+    if (!grid_fits(workgroups, &e)) return e;
+    const uint32_t U = a.up, D = a.down, P = a.taps;
     // the stretch, the table and the three ways to the coefficients as in launch_resample, for the stream's chunk
     const uint64_t stretch = ((uint64_t)(U - 1u) + (uint64_t)(RESAMPLE_STREAM_CHUNK - 1u) * D) / U + P + RS_STAGE_SLACK;
     const uint64_t staged_bytes = (RESAMPLE_STREAM_CHUNK + stretch) * 4u, table_bytes = (uint64_t)U * (P + 1u) * 4u;
@@ -540,35 +536,30 @@ hipError_t launch_resample_stream(const float *in, uint64_t in_stride, const uin
     const int tab = U == 1u ? RS_TAB_UNIFORM : (staged && staged_bytes + table_bytes <= RS_LDS_MAX ? RS_TAB_LDS : RS_TAB_GLOBAL);
     const uint32_t stage_words = staged ? (uint32_t)stretch : 0u;
     const uint32_t lds = (uint32_t)((staged ? staged_bytes : RESAMPLE_STREAM_CHUNK * 4u) + (tab == RS_TAB_LDS ? table_bytes : 0u));
-    const bool vec = ((reinterpret_cast<uintptr_t>(in) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
-                     ((in_stride | out_stride) & 3u) == 0;
-    launch_either(vec, staged ? resample_stream_variant<true, true>(tab) : resample_stream_variant<false, true>(tab),
+    launch_either(aligned16(a.rows, a.row_stride, a.out, a.out_stride),
+                  staged ? resample_stream_variant<true, true>(tab) : resample_stream_variant<false, true>(tab),
                   staged ? resample_stream_variant<true, false>(tab) : resample_stream_variant<false, false>(tab),
-                  dim3((uint32_t)workgroups), dim3(RS_THREADS), lds, stream, in, in_stride, in_len, n_rows, U, D, P, table, stage_words,
-                  grid_chunks, state, ring, ring_cap, mark, finishing ? 1u : 0u, out, out_stride, cbad);
+                  dim3((uint32_t)workgroups), dim3(RS_THREADS), lds, stream, a.rows, a.row_stride, a.len, a.n_rows, a.up, a.down, a.taps,
+                  a.table, stage_words, a.grid_chunks, a.state, a.ring, a.ring_cap, a.mark, a.finishing ? 1u : 0u, a.out, a.out_stride,
+                  a.cbad);
     return hipGetLastError();
 }
 
-hipError_t launch_resample_stream_advance(const float *in, uint64_t in_stride, const uint32_t *in_len, uint32_t n_rows, uint32_t U,
-                                          uint32_t D, uint32_t P, uint64_t *state, float *ring, uint32_t ring_cap, const uint8_t *mark,
-                                          bool finishing, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                                          uint32_t *nonfinite, hipStream_t stream)
+hipError_t launch_resample_stream_advance(const ResampleArgs &a, hipStream_t stream)
 {
-    if (n_rows == 0) return hipSuccess;
+    if (a.n_rows == 0) return hipSuccess;
     const uint32_t rows_per_group = RS_THREADS / 64u;
-    hipLaunchKernelGGL(resample_stream_advance_kernel, dim3(n_rows / rows_per_group + (n_rows % rows_per_group != 0u)), dim3(RS_THREADS), 0,
-                       stream, in, in_stride, in_len, n_rows, U, D, P, state, ring, ring_cap, mark, finishing ? 1u : 0u, cbad,
-                       grid_chunks, out_len, nonfinite);
+    hipLaunchKernelGGL(resample_stream_advance_kernel, dim3(a.n_rows / rows_per_group + (a.n_rows % rows_per_group != 0u)),
+                       dim3(RS_THREADS), 0, stream, a.rows, a.row_stride, a.len, a.n_rows, a.up, a.down, a.taps, a.state, a.ring,
+                       a.ring_cap, a.mark, a.finishing ? 1u : 0u, a.cbad, a.grid_chunks, a.out_len, a.nonfinite);
     return hipGetLastError();
 }
 
-hipError_t launch_resample_totals(const uint32_t *len, uint64_t row_stride, uint32_t n_rows, uint32_t U, uint32_t D,
-                                  uint64_t out_stride, const uint32_t *cbad, uint32_t grid_chunks, uint32_t *out_len,
-                                  uint32_t *nonfinite, hipStream_t stream)
+hipError_t launch_resample_totals(const ResampleArgs &a, hipStream_t stream)
 {
-    if (n_rows == 0) return hipSuccess;
-    hipLaunchKernelGGL(resample_totals_kernel, dim3((n_rows + 255u) / 256u), dim3(256), 0, stream, len, row_stride, n_rows, U, D,
-                       out_stride, cbad, grid_chunks, out_len, nonfinite);
+    if (a.n_rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(resample_totals_kernel, dim3((a.n_rows + 255u) / 256u), dim3(256), 0, stream, a.len, a.row_stride, a.n_rows, a.up,
+                       a.down, a.out_stride, a.cbad, a.grid_chunks, a.out_len, a.nonfinite);
     return hipGetLastError();
 }
 

@@ -4,8 +4,9 @@
 // §4.18), and filtered recursively chunk by chunk: grail_iir_stream_* (iir_kernels.hip, §4.20; checks iir_plan.cpp; one launch
 // a call, no ring), and compressed chunk by chunk: grail_dyn_stream_* (dyn_kernels.hip, §4.23; checks dyn_plan.cpp; one launch a call,
 // no ring, no finish).  A kind's own are its argument checks (fir_plan.cpp, resample_plan.cpp, limit_plan.cpp, meter_plan.cpp; their common
-// end row_checks.h), what it keeps beside the rings, and its launches (two; the meter's three).  What the kinds do alike stands
-// once, first: telling a stream of the context's, its device state, a finishing call's marks, its close.
+// end row_checks.h), what it keeps beside the rings, and its launches (two; the meter's three), which take one struct of arguments
+// filled once a call (kernels.h).  What the kinds do alike stands once, first: telling a stream of the context's, its device
+// state, a finishing call's marks, its close, and what a call's arguments take from the stream (on_stream).
 #include "transform_state.h"
 
 using namespace grail;
@@ -71,6 +72,14 @@ int marks(grail_ctx *ctx, ChunkedStream &s, const uint8_t *which, const uint8_t 
     return GRAIL_OK;
 }
 
+// What a kind's arguments take from the call's samples and from the stream itself: its state, its ring, the marks.
+void on_stream(RowCallArgs &a, const ChunkedStream &s, const float *in_dev, uint64_t in_stride, const uint32_t *in_len_dev,
+               const uint8_t *mark_dev, bool finishing)
+{
+    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev;
+    a.state = s.d_state.get(), a.ring = s.d_ring.get(), a.ring_cap = s.ring_cap, a.mark = mark_dev, a.finishing = finishing;
+}
+
 // The two kernels of a call on a stream: the outputs (chunks = 0: there are none to write), then the state.  One function a
 // kind, for their launches take what the kind keeps.
 int fir_stream_call(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev, uint64_t in_stride,
@@ -80,18 +89,18 @@ int fir_stream_call(grail_ctx *ctx, grail_filter_stream *fs, const float *in_dev
     TransformState *st;
     int rc = state(ctx, &st);
     if (rc) return rc;
+    if (chunks && (rc = st->d_firbad.reserve(ctx->stream, (size_t)fs->units * (size_t)chunks))) return rc;
     const grail_fir *set = fs->set;
+    FirArgs a = {};
+    on_stream(a, *fs, in_dev, in_stride, in_len_dev, mark_dev, finishing);
+    a.n_rows = fs->n_rows, a.filter = fs->filter.dev.get(), a.taps = set->d_taps.get(), a.desc = set->d_desc.get();
+    a.n_filters = set->n_filters, a.grid_chunks = (uint32_t)chunks, a.out = out_dev, a.out_stride = out_stride;
+    a.cbad = st->d_firbad.get(), a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {
-        if ((rc = st->d_firbad.reserve(ctx->stream, (size_t)fs->units * (size_t)chunks))) return rc;
-        const hipError_t e = launch_fir_stream(in_dev, in_stride, in_len_dev, fs->n_rows, fs->d_filter.get(), set->d_taps.get(),
-                                               set->d_desc.get(), set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap,
-                                               mark_dev, finishing, (uint32_t)chunks, out_dev, out_stride, st->d_firbad.get(),
-                                               ctx->stream);
+        const hipError_t e = launch_fir_stream(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "fir stream kernel launch");
     }
-    const hipError_t e = launch_fir_stream_advance(in_dev, in_stride, in_len_dev, fs->n_rows, fs->d_filter.get(), set->d_desc.get(),
-                                                   set->n_filters, fs->d_state.get(), fs->d_ring.get(), fs->ring_cap, mark_dev, finishing,
-                                                   st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_fir_stream_advance(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "fir stream advance kernel launch");
     return GRAIL_OK;
 }
@@ -103,16 +112,17 @@ int resample_stream_call(grail_ctx *ctx, grail_resample_stream *rs, const float 
     TransformState *st;
     int rc = state(ctx, &st);
     if (rc) return rc;
+    if (chunks && (rc = st->d_rbad.reserve(ctx->stream, (size_t)rs->units * (size_t)chunks))) return rc;
+    ResampleArgs a = {};
+    on_stream(a, *rs, in_dev, in_stride, in_len_dev, mark_dev, finishing);
+    a.n_rows = rs->n_rows, a.up = rs->up, a.down = rs->down, a.taps = rs->taps, a.table = rs->d_table.get();
+    a.grid_chunks = (uint32_t)chunks, a.out = out_dev, a.out_stride = out_stride;
+    a.cbad = st->d_rbad.get(), a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {
-        if ((rc = st->d_rbad.reserve(ctx->stream, (size_t)rs->units * (size_t)chunks))) return rc;
-        const hipError_t e = launch_resample_stream(in_dev, in_stride, in_len_dev, rs->n_rows, rs->up, rs->down, rs->taps,
-                                                    rs->d_table.get(), rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev,
-                                                    finishing, (uint32_t)chunks, out_dev, out_stride, st->d_rbad.get(), ctx->stream);
+        const hipError_t e = launch_resample_stream(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "resample stream kernel launch");
     }
-    const hipError_t e = launch_resample_stream_advance(in_dev, in_stride, in_len_dev, rs->n_rows, rs->up, rs->down, rs->taps,
-                                                        rs->d_state.get(), rs->d_ring.get(), rs->ring_cap, mark_dev, finishing,
-                                                        st->d_rbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_resample_stream_advance(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "resample stream advance kernel launch");
     return GRAIL_OK;
 }
@@ -124,17 +134,17 @@ int limit_stream_call(grail_ctx *ctx, grail_limit_stream *ls, const float *in_de
     TransformState *st;
     int rc = state(ctx, &st);
     if (rc) return rc;
+    if (chunks && (rc = st->d_lstat.reserve(ctx->stream, (size_t)ls->units * (size_t)chunks * limit_chunk_bytes()))) return rc;
+    LimitArgs a = {};
+    on_stream(a, *ls, in_dev, in_stride, in_len_dev, mark_dev, finishing);
+    a.n_groups = ls->units, a.group = ls->group, a.ceiling = ls->ceiling, a.ell = ls->ell;
+    a.grid_chunks = (uint32_t)chunks, a.out = out_dev, a.out_stride = out_stride, a.cstat = st->d_lstat.get();
+    a.out_len = out_len_dev, a.min_gain = min_gain_dev, a.n_limited = n_limited_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {
-        if ((rc = st->d_lstat.reserve(ctx->stream, (size_t)ls->units * (size_t)chunks * limit_chunk_bytes()))) return rc;
-        const hipError_t e = launch_limit_stream(in_dev, in_stride, in_len_dev, ls->units, ls->group, ls->ceiling, ls->ell,
-                                                 ls->d_state.get(), ls->d_ring.get(), ls->ring_cap, mark_dev, finishing,
-                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat.get(), ctx->stream);
+        const hipError_t e = launch_limit_stream(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "limit stream kernel launch");
     }
-    const hipError_t e = launch_limit_stream_advance(in_dev, in_stride, in_len_dev, ls->units, ls->group, ls->ell, ls->d_state.get(),
-                                                     ls->d_ring.get(), ls->ring_cap, mark_dev, finishing, st->d_lstat.get(),
-                                                     (uint32_t)chunks, out_len_dev, min_gain_dev, n_limited_dev, nonfinite_dev,
-                                                     ctx->stream);
+    const hipError_t e = launch_limit_stream_advance(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "limit stream advance kernel launch");
     return GRAIL_OK;
 }
@@ -147,22 +157,22 @@ int meter_stream_call(grail_ctx *ctx, grail_meter_stream *ms, const float *in_de
     TransformState *st;
     int rc = state(ctx, &st);
     if (rc) return rc;
+    if (chunks && (rc = st->d_mpeak.reserve(ctx->stream, (size_t)ms->n_rows * (size_t)chunks))) return rc;
+    if (chunks && (rc = st->d_mbad.reserve(ctx->stream, (size_t)ms->n_rows * (size_t)chunks))) return rc;
+    MeterStreamArgs a = {};
+    on_stream(a, *ms, in_dev, in_stride, in_len_dev, mark_dev, finishing);
+    a.n_rows = ms->n_rows, a.hop = ms->hop, a.coef = ms->coef, a.ledger = ms->d_ledger.get(), a.max_hops = ms->max_hops;
+    a.hops_out = hop_sumsq_dev, a.hops_stride = hops_stride, a.grid_chunks = (uint32_t)chunks;
+    a.cmax = st->d_mpeak.get(), a.cbad = st->d_mbad.get(), a.n_hops = n_hops_dev, a.true_peak = true_peak_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {
-        if ((rc = st->d_mpeak.reserve(ctx->stream, (size_t)ms->n_rows * (size_t)chunks))) return rc;
-        if ((rc = st->d_mbad.reserve(ctx->stream, (size_t)ms->n_rows * (size_t)chunks))) return rc;
         if (!finishing) {
-            const hipError_t e = launch_meter_stream_hops(in_dev, in_stride, in_len_dev, ms->n_rows, ms->hop, ms->coef, ms->d_state.get(),
-                                                          ms->d_ledger.get(), ms->max_hops, hop_sumsq_dev, hops_stride, ctx->stream);
+            const hipError_t e = launch_meter_stream_hops(a, ctx->stream);
             if (e != hipSuccess) return hip_fail(e, "meter stream hops kernel launch");
         }
-        const hipError_t e = launch_meter_stream_peak(in_dev, in_stride, in_len_dev, ms->n_rows, ms->hop, ms->d_state.get(), ms->max_hops,
-                                                      ms->d_ring.get(), mark_dev, finishing, (uint32_t)chunks, st->d_mpeak.get(),
-                                                      st->d_mbad.get(), ctx->stream);
+        const hipError_t e = launch_meter_stream_peak(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "meter stream peak kernel launch");
     }
-    const hipError_t e = launch_meter_stream_advance(in_dev, in_stride, in_len_dev, ms->n_rows, ms->hop, ms->d_state.get(), ms->max_hops,
-                                                     ms->d_ring.get(), mark_dev, finishing, st->d_mpeak.get(), st->d_mbad.get(),
-                                                     (uint32_t)chunks, n_hops_dev, true_peak_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_meter_stream_advance(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "meter stream advance kernel launch");
     return GRAIL_OK;
 }
@@ -174,7 +184,7 @@ int iir_stream_call(grail_ctx *ctx, grail_iir_stream *is, const float *in_dev, u
 {
     const grail_iir *set = is->set;
     IirArgs a = {};
-    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev, a.n_rows = is->n_rows, a.filter = is->d_filter.get();
+    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev, a.n_rows = is->n_rows, a.filter = is->filter.dev.get();
     a.image = set->d_image.get(), a.sections = set->d_sections.get(), a.n_filters = set->n_filters, a.tail = is->tail;
     a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     a.state = is->d_state.get(), a.mark = mark_dev, a.finishing = finishing ? 1u : 0u;
@@ -190,10 +200,10 @@ int dyn_stream_call(grail_ctx *ctx, grail_dyn_stream *ds, const float *in_dev, u
 {
     const grail_dyn *set = ds->set;
     DynArgs a = {};
-    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev, a.n_rows = ds->n_rows, a.curve = ds->d_curve.get();
+    a.rows = in_dev, a.row_stride = in_stride, a.len = in_len_dev, a.n_rows = ds->n_rows, a.curve = ds->curve.dev.get();
     a.image = set->d_image.get(), a.alpha = set->d_alpha.get(), a.detector = set->d_detector.get(), a.n_curves = set->n_curves;
     if (ds->n_keys && in_stride)        // (a call of no samples reads no key and may come without one)
-        a.key = key_dev, a.key_stride = key_stride, a.n_keys = ds->n_keys, a.key_row = ds->d_key_row.get();
+        a.key = key_dev, a.key_stride = key_stride, a.n_keys = ds->n_keys, a.key_row = ds->key_row.dev.get();
     a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev, a.min_gain = min_gain_dev;
     a.state = ds->d_state.get();
     const hipError_t e = launch_dyn(a, ctx->stream);
@@ -220,9 +230,7 @@ int grail_filter_stream_open(grail_ctx *ctx, const grail_fir *set, uint32_t n_ro
     fs->set = set;
     fs->n_rows = fs->units = n_rows;
     fs->ring_cap = fir_stream_ring_capacity(set->taps_max);
-    fs->filter.assign(n_rows, 0u);
-    if (filter) std::copy(filter, filter + n_rows, fs->filter.begin());
-    HIP_TRY(upload(fs->d_filter, fs->filter.data(), n_rows, ctx->stream));
+    HIP_TRY(fs->filter.fill(filter, n_rows, false, ctx->stream));
     if ((rc = alloc_state(ctx, *fs, 1))) return rc;
     *out = peek(ctx)->fir_streams.add(std::move(fs));       // (the set was found: the state is there)
     return GRAIL_OK;
@@ -489,9 +497,7 @@ int grail_iir_stream_open(grail_ctx *ctx, const grail_iir *set, uint32_t n_rows,
     is->tail = tail;
     is->n_rows = is->units = n_rows;
     is->ring_cap = 0;                                       // (no ring: the filter's memory is its state)
-    is->filter.assign(n_rows, 0u);
-    if (filter) std::copy(filter, filter + n_rows, is->filter.begin());
-    HIP_TRY(upload(is->d_filter, is->filter.data(), n_rows, ctx->stream));
+    HIP_TRY(is->filter.fill(filter, n_rows, false, ctx->stream));
     if ((rc = alloc_state(ctx, *is, iir_stream_state_words(set->bound)))) return rc;       // (nothing fed, every state +0.0)
     *out = peek(ctx)->iir_streams.add(std::move(is));       // (the set was found: the state is there)
     return GRAIL_OK;
@@ -544,14 +550,8 @@ int grail_dyn_stream_open(grail_ctx *ctx, const grail_dyn *set, uint32_t n_rows,
     ds->n_keys = n_keys;
     ds->n_rows = ds->units = n_rows;
     ds->ring_cap = 0;                                       // (no ring: the envelope is the row's memory)
-    ds->curve.assign(n_rows, 0u);
-    if (curve) std::copy(curve, curve + n_rows, ds->curve.begin());
-    HIP_TRY(upload(ds->d_curve, ds->curve.data(), n_rows, ctx->stream));
-    if (n_keys) {
-        ds->key_row.resize(n_rows);
-        for (uint32_t u = 0; u < n_rows; ++u) ds->key_row[u] = key_row ? key_row[u] : u;
-        HIP_TRY(upload(ds->d_key_row, ds->key_row.data(), n_rows, ctx->stream));
-    }
+    HIP_TRY(ds->curve.fill(curve, n_rows, false, ctx->stream));
+    if (n_keys) HIP_TRY(ds->key_row.fill(key_row, n_rows, true, ctx->stream));
     if ((rc = alloc_state(ctx, *ds, DYN_STREAM_STATE_WORDS))) return rc;       // (nothing fed, e = +0.0)
     *out = peek(ctx)->dyn_streams.add(std::move(ds));       // (the set was found: the state is there)
     return GRAIL_OK;

@@ -41,6 +41,26 @@ int resample_table(grail_ctx *ctx, TransformState *st, uint32_t rate_in, uint32_
     return GRAIL_OK;
 }
 
+// grail_fir_free, grail_iir_free and grail_dyn_free: a set of the context's `sets` is released unless one of its `streams` is
+// still open on it.  The refusals of the call `who` speak of a `set_noun` set and of `stream_noun` streams.
+template <typename Set, typename Stream>
+int set_free(grail_ctx *ctx, Owned<Set> TransformState::*sets, Owned<Stream> TransformState::*streams, Set *set, const char *who,
+             const char *set_noun, const char *stream_noun)
+{
+    if (!set) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": ctx is NULL");
+    if (!own(ctx, sets, set)) return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": not a " + set_noun + " set of this context");
+    TransformState *st = peek(ctx);
+    if ((st->*streams).any([set](const Stream &s) { return s.set == set; }))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string(who) + ": the set still has open " + stream_noun + " streams");
+    // (a kernel or the upload still queued may be reading it)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    (st->*sets).remove(set);
+    return GRAIL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -70,15 +90,17 @@ int grail_limit_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_stride
     const uint64_t chunks = limit_grid_chunks(row_stride);
     // (the one argument check that comes after the device)
     if ((uint64_t)n_groups * chunks > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_limit_async: more than 2^31 chunks");
+    if (chunks && (rc = st->d_lstat.reserve(ctx->stream, (size_t)n_groups * (size_t)chunks * limit_chunk_bytes()))) return rc;
+    LimitArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_groups = n_groups, a.group = group;
+    a.ceiling = ceiling, a.ell = lookahead_log2, a.grid_chunks = (uint32_t)chunks, a.out = out_dev, a.out_stride = out_stride;
+    a.cstat = st->d_lstat.get(), a.min_gain = min_gain_dev, a.n_limited = n_limited_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {               // (rows of no samples: 1.0f, 0, 0 from the totals alone)
-        if ((rc = st->d_lstat.reserve(ctx->stream, (size_t)n_groups * (size_t)chunks * limit_chunk_bytes()))) return rc;
-        const hipError_t e = launch_limit_frames(rows_dev, row_stride, len_dev, n_groups, group, ceiling, lookahead_log2,
-                                                 (uint32_t)chunks, out_dev, out_stride, st->d_lstat.get(), ctx->stream);
+        const hipError_t e = launch_limit_frames(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "limiter frames kernel launch");
     }
     if (!min_gain_dev && !n_limited_dev && !nonfinite_dev) return GRAIL_OK;
-    const hipError_t e = launch_limit_totals(len_dev, row_stride, n_groups, group, lookahead_log2, st->d_lstat.get(),
-                                             (uint32_t)chunks, min_gain_dev, n_limited_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_limit_totals(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "limiter totals kernel launch");
     return GRAIL_OK;
 }
@@ -104,17 +126,20 @@ int grail_resample_async(grail_ctx *ctx, const float *rows_dev, uint64_t row_str
     const uint64_t chunks = resample_grid_chunks(row_stride, out_stride, U, D);
     // (the one argument check that comes after the device)
     if ((uint64_t)n_rows * chunks > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_resample_async: more than 2^31 chunks");
+    ResampleArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows, a.up = U, a.down = D, a.taps = P;
+    a.grid_chunks = (uint32_t)chunks, a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {               // (rows of no samples: 0, 0 from the totals alone)
-        const int32_t *table = nullptr;
-        if ((rc = resample_table(ctx, st, rate_in, rate_out, U, D, P, &table))) return rc;
+        if ((rc = resample_table(ctx, st, rate_in, rate_out, U, D, P, &a.table))) return rc;
         if ((rc = st->d_rbad.reserve(ctx->stream, (size_t)n_rows * (size_t)chunks))) return rc;
-        const hipError_t e = launch_resample(rows_dev, row_stride, len_dev, n_rows, U, D, P, table, (uint32_t)chunks, out_dev,
-                                             out_stride, st->d_rbad.get(), ctx->stream);
+    }
+    a.cbad = st->d_rbad.get();
+    if (chunks) {
+        const hipError_t e = launch_resample(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "resample kernel launch");
     }
     if (!out_len_dev && !nonfinite_dev) return GRAIL_OK;
-    const hipError_t e = launch_resample_totals(len_dev, row_stride, n_rows, U, D, out_stride, st->d_rbad.get(), (uint32_t)chunks,
-                                                out_len_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_resample_totals(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "resample totals kernel launch");
     return GRAIL_OK;
 }
@@ -142,18 +167,7 @@ int grail_fir_create(grail_ctx *ctx, const float *taps, const uint32_t *n_taps, 
 
 int grail_fir_free(grail_ctx *ctx, grail_fir *set)
 {
-    if (!set) return GRAIL_OK;
-    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_free: ctx is NULL");
-    if (!own(ctx, &TransformState::firs, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_free: not a filter set of this context");
-    TransformState *st = peek(ctx);
-    if (st->fir_streams.any([set](const grail_filter_stream &fs) { return fs.set == set; }))
-        return fail(GRAIL_ERR_INVALID_ARG, "grail_fir_free: the set still has open filter streams");
-    // (a kernel or the upload still queued may be reading it)
-    int rc = bind(ctx);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st->firs.remove(set);
-    return GRAIL_OK;
+    return set_free(ctx, &TransformState::firs, &TransformState::fir_streams, set, "grail_fir_free", "filter", "filter");
 }
 
 int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
@@ -178,15 +192,17 @@ int grail_fir_async(grail_ctx *ctx, const grail_fir *set, const float *rows_dev,
     if (n_rows == 0) return GRAIL_OK;
     TransformState *st;
     if ((rc = state(ctx, &st))) return rc;
+    if (chunks && (rc = st->d_firbad.reserve(ctx->stream, (size_t)n_rows * (size_t)chunks))) return rc;
+    FirArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows, a.filter = filter_dev;
+    a.taps = set->d_taps.get(), a.desc = set->d_desc.get(), a.n_filters = set->n_filters, a.grid_chunks = (uint32_t)chunks;
+    a.out = out_dev, a.out_stride = out_stride, a.cbad = st->d_firbad.get(), a.out_len = out_len_dev, a.nonfinite = nonfinite_dev;
     if (chunks) {               // (rows of no samples: 0, 0 from the totals alone)
-        if ((rc = st->d_firbad.reserve(ctx->stream, (size_t)n_rows * (size_t)chunks))) return rc;
-        const hipError_t e = launch_fir(rows_dev, row_stride, len_dev, n_rows, filter_dev, set->d_taps.get(), set->d_desc.get(),
-                                        set->n_filters, (uint32_t)chunks, out_dev, out_stride, st->d_firbad.get(), ctx->stream);
+        const hipError_t e = launch_fir(a, ctx->stream);
         if (e != hipSuccess) return hip_fail(e, "fir kernel launch");
     }
     if (!out_len_dev && !nonfinite_dev) return GRAIL_OK;
-    const hipError_t e = launch_fir_totals(len_dev, row_stride, n_rows, filter_dev, set->d_desc.get(), set->n_filters, out_stride,
-                                           st->d_firbad.get(), (uint32_t)chunks, out_len_dev, nonfinite_dev, ctx->stream);
+    const hipError_t e = launch_fir_totals(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "fir totals kernel launch");
     return GRAIL_OK;
 }
@@ -212,18 +228,7 @@ int grail_iir_create(grail_ctx *ctx, const double *coef, const uint32_t *n_secti
 
 int grail_iir_free(grail_ctx *ctx, grail_iir *set)
 {
-    if (!set) return GRAIL_OK;
-    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_free: ctx is NULL");
-    if (!own(ctx, &TransformState::iirs, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_free: not a filter set of this context");
-    TransformState *st = peek(ctx);
-    if (st->iir_streams.any([set](const grail_iir_stream &is) { return is.set == set; }))
-        return fail(GRAIL_ERR_INVALID_ARG, "grail_iir_free: the set still has open IIR streams");
-    // (a kernel or the upload still queued may be reading it)
-    int rc = bind(ctx);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st->iirs.remove(set);
-    return GRAIL_OK;
+    return set_free(ctx, &TransformState::iirs, &TransformState::iir_streams, set, "grail_iir_free", "filter", "IIR");
 }
 
 int grail_iir_async(grail_ctx *ctx, const grail_iir *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
@@ -277,18 +282,7 @@ int grail_dyn_create(grail_ctx *ctx, const double *gain, const double *alpha, co
 
 int grail_dyn_free(grail_ctx *ctx, grail_dyn *set)
 {
-    if (!set) return GRAIL_OK;
-    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_free: ctx is NULL");
-    if (!own(ctx, &TransformState::dyns, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_free: not a curve set of this context");
-    TransformState *st = peek(ctx);
-    if (st->dyn_streams.any([set](const grail_dyn_stream &ds) { return ds.set == set; }))
-        return fail(GRAIL_ERR_INVALID_ARG, "grail_dyn_free: the set still has open dynamics streams");
-    // (a kernel or the upload still queued may be reading it)
-    int rc = bind(ctx);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    st->dyns.remove(set);
-    return GRAIL_OK;
+    return set_free(ctx, &TransformState::dyns, &TransformState::dyn_streams, set, "grail_dyn_free", "curve", "dynamics");
 }
 
 int grail_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
