@@ -1,6 +1,6 @@
 // grail_dialogue — two lines of text by two voices, laid one after the other on a timeline (grail_mix_place_sequential),
 // the first voice panned left and the second right, mixed on an MI355X (grail::Gpu::mix) and written as a stereo WAV.
-//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] [--makeup DB]] [--rate R] [--report] "first line" "second line"
+//   usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] [--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] [--makeup DB]] [--compress-tracks] [--rate R] [--report] "first line" "second line"
 // --level DB brings both lines to that RMS level (decibels, 0 dB = an RMS of 1.0) before they are panned: the rows are
 // measured on the device and the gains follow from their levels (grail::Gpu::mix_leveled).  --lufs L brings them to a
 // K-weighted gated loudness of L LUFS instead (GRAIL_LEVEL_LOUDNESS; a line shorter than 400 ms cannot be leveled).
@@ -26,6 +26,8 @@
 // itself): threshold T in dB, ratio R >= 1, a knee of KNEE dB (6 unless given), attack and release in milliseconds (5 and 120
 // unless given).  --makeup DB (with --compress) is built into the curve.  Prints each track's largest gain reduction in dB.  The
 // make-up can lift peaks, so with --ceiling the tracks' true peaks are measured after it.
+// --compress-tracks (with --compress) compresses them with grail_track_dyn_async instead, a workgroup a track, the form that is
+// meant for a few long tracks: the same samples, bit for bit.  The line printed names the call.
 // --rate R resamples the two finished tracks, after the mix and the limiter, from the voices' 44 100 Hz to R Hz on the device
 // (grail::Gpu::resample) and writes the WAV at R; the filter overshoots a little, so the line it prints has the tracks'
 // true peaks at R.
@@ -57,7 +59,7 @@ int main(int argc, char **argv)
     uint32_t band_taps = 255;
     EqOption eq_option;
     bool eq_blocked = false;
-    bool compress = false, bad_compress = false, makeup_given = false;
+    bool compress = false, bad_compress = false, makeup_given = false, compress_by_track = false;
     double comp[5] = {0.0, 1.0, 6.0, 5.0, 120.0}, makeup_db = 0.0;        // T, R, knee, attack ms, release ms
     for (int i = 1; i < argc; ++i) {
         if ((!std::strcmp(argv[i], "-o") || !std::strcmp(argv[i], "--output")) && i + 1 < argc) out_path = argv[++i];
@@ -96,6 +98,7 @@ int main(int argc, char **argv)
             bad_band = bad_band || rest == argv[i] || *rest || argv[i][0] == '-' || k < 3 || k > GRAIL_FIR_TAPS_MAX || k % 2 == 0;
         } else if (!std::strcmp(argv[i], "--eq")) eq_option.take(argc, argv, i);      // (examples/eq_option.h)
         else if (!std::strcmp(argv[i], "--eq-blocked")) eq_blocked = true;
+        else if (!std::strcmp(argv[i], "--compress-tracks")) compress_by_track = true;
         else if (!std::strcmp(argv[i], "--compress")) {
             bad_compress = bad_compress || compress || i + 1 >= argc;      // (named twice, or without a value)
             compress = true;
@@ -133,16 +136,16 @@ int main(int argc, char **argv)
     // (the curve and the alphas of --compress are made here: the designer refuses what it cannot make)
     std::vector<double> comp_gain(GRAIL_DYN_POINTS);
     double comp_alpha[2] = {0.0, 0.0};
-    bad_compress = bad_compress || (makeup_given && !compress) ||
+    bad_compress = bad_compress || (makeup_given && !compress) || (compress_by_track && !compress) ||
                    (compress && (grail_dyn_design(GRAIL_DYN_COMPRESS, GRAIL_DYN_PEAK, comp[0], comp[1], comp[2], 0.0, makeup_db, comp_gain.data()) ||
                                  grail_dyn_ballistics(44100, comp[3], comp[4], comp_alpha)));
     if (lines.size() != 2 || bad_level || bad_ceiling || bad_report || bad_rate || bad_band || bad_eq || bad_compress || (capped && !leveled) || (limit && !capped)) {
         std::fprintf(stderr, "usage: grail_dialogue [-o out.wav] [--level DB | --lufs L] [--ceiling DBTP [--limit]] [--band LO HI [--taps K]] "
-                             "[--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] [--makeup DB]] [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
+                             "[--eq KIND:F0:Q[:GAIN]]... [--eq-blocked] [--compress T:R[:KNEE[:ATTACK_MS:RELEASE_MS]] [--makeup DB]] [--compress-tracks] [--rate R] [--report] \"first line\" \"second line\"\n       (--ceiling needs --level or --lufs, --limit "
                              "needs --ceiling, --band takes 0 <= LO < HI <= 22050 Hz, --taps an odd number from 3 to 4096 and needs "
                              "--band, --eq takes lowpass, highpass, bandpass, notch, peak, lowshelf or highshelf, 0 < F0 < 22050 Hz, Q > 0 and a "
                              "gain in dB, up to eight times, --eq-blocked needs --eq, --compress takes a threshold in dB, a ratio of 1 or more, a knee of 0 dB or more and "
-                             "two times of 0 ms or more, once, --makeup needs --compress, --rate takes a whole number of Hz, --report takes no value)\n");
+                             "two times of 0 ms or more, once, --makeup and --compress-tracks need --compress, --rate takes a whole number of Hz, --report takes no value)\n");
         return 2;
     }
     try {
@@ -216,8 +219,8 @@ int main(int argc, char **argv)
             for (uint32_t t = 0; t < n && !rc; ++t)
                 rc = grail_memcpy_h2d(ctx, (float *)d_rows + t * stride, tracks[t].data(), tracks[t].size() * 4);
             if (!rc) rc = grail_memcpy_h2d(ctx, d_len, track_len.data(), n * 4);
-            if (!rc) rc = grail_dyn_async(ctx, set, (const float *)d_rows, stride, (const uint32_t *)d_len, n, nullptr, nullptr, 0, nullptr, 0, nullptr,
-                                          (float *)d_out, stride, nullptr, nullptr, (double *)d_gain);
+            if (!rc) rc = (compress_by_track ? grail_track_dyn_async : grail_dyn_async)(ctx, set, (const float *)d_rows, stride, (const uint32_t *)d_len, n, nullptr, nullptr, 0, nullptr, 0, nullptr,
+                                                                                      (float *)d_out, stride, nullptr, nullptr, (double *)d_gain);
             for (uint32_t t = 0; t < n && !rc; ++t)
                 rc = grail_memcpy_d2h(ctx, tracks[t].data(), (const float *)d_out + t * stride, tracks[t].size() * 4);
             std::vector<double> min_gain(n, 1.0);
@@ -226,8 +229,8 @@ int main(int argc, char **argv)
                 if (p) grail_device_free(ctx, p);
             const int freed = grail_dyn_free(ctx, set);
             grail::check(rc ? rc : freed);
-            std::printf("Compressed (grail_dyn_async) above %g dB at %g:1, knee %g dB, attack %g ms, release %g ms, make-up %g dB: largest gain reduction",
-                        comp[0], comp[1], comp[2], comp[3], comp[4], makeup_db);
+            std::printf("Compressed (%s) above %g dB at %g:1, knee %g dB, attack %g ms, release %g ms, make-up %g dB: largest gain reduction",
+                        compress_by_track ? "grail_track_dyn_async" : "grail_dyn_async", comp[0], comp[1], comp[2], comp[3], comp[4], makeup_db);
             for (uint32_t t = 0; t < n; ++t)    // (the curve holds the make-up: the reduction is what lies under it)
                 std::printf("%s %.2f dB", t ? " and" : "", makeup_db - 20.0 * std::log10(min_gain[t]));
             std::printf("\n");

@@ -19,6 +19,12 @@ constexpr uint32_t DYN_IMAGE_DOUBLES = 2 * DYN_POINTS;
 constexpr uint32_t DYN_KEY_LO = (uint32_t)(1023 + DYN_LOG2_LO) * DYN_STEPS;
 // a stream's state words a row: N, then e as its bits
 constexpr uint32_t DYN_STREAM_STATE_WORDS = 2;
+// grail_track_dyn_async (track_env_kernels.hip): a workgroup walks its row in tiles of TRACK_TILE samples, a power of two.  Not
+// part of the contract: no number depends on it.  One wave runs the envelope's chain; each of the TRACK_TILE / 4 other lanes
+// takes four samples of a tile on either side of the chain.
+constexpr uint32_t TRACK_TILE = 1024;
+constexpr uint32_t TRACK_WORKERS = TRACK_TILE / 4;
+constexpr uint32_t TRACK_THREADS = 64 + TRACK_WORKERS;
 
 // lev[k] = 2^(LO + k div 16) * (1 + (k mod 16) / 16), exact; k < DYN_POINTS
 double dyn_level(uint32_t k);

@@ -433,5 +433,8 @@ struct DynArgs {
     uint64_t *state;
 };
 hipError_t launch_dyn(const DynArgs &args, hipStream_t stream);
+// the same rows, the same bits, a workgroup a row (track_env_kernels.hip): for the few long tracks of a mix.
+// state is not read (there is no stream form); more than 2^31 - 1 rows: hipErrorInvalidValue.
+hipError_t launch_track_dyn(const DynArgs &args, hipStream_t stream);
 
 }  // namespace grail

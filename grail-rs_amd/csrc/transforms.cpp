@@ -3,7 +3,7 @@
 // _free / _async (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_iir_create / _free / _async
 // (iir_kernels.hip, a set's checks and image iir_plan.cpp, §4.19) and grail_biquad_blocked_async (biquad_block_kernels.hip, its
 // matrices, grid and scratch size iir_plan.cpp, §4.22) and grail_dyn_create / _free / _async (dyn_kernels.hip, a set's checks and
-// image dyn_plan.cpp, §4.23): their checks, their scratch, their launches.
+// image dyn_plan.cpp, §4.23) and grail_track_dyn_async (track_env_kernels.hip, §4.24): their checks, their scratch, their launches.
 // What they check of a pair of rows is row_checks.h.  The same chunk by chunk, on streams, is transform_streams.cpp; what a
 // context keeps for both is transform_state.h.
 #include "row_checks.h"
@@ -306,6 +306,33 @@ int grail_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev,
     a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev, a.min_gain = min_gain_dev;
     const hipError_t e = launch_dyn(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "dyn kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_track_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                          uint32_t n_rows, const uint32_t *curve_dev, const float *key_dev, uint64_t key_stride,
+                          const uint32_t *key_len_dev, uint32_t n_keys, const uint32_t *key_row_dev, float *out_dev, uint64_t out_stride,
+                          uint32_t *out_len_dev, uint32_t *nonfinite_dev, double *min_gain_dev)
+{
+    if (!set) return fail(GRAIL_ERR_INVALID_ARG, "grail_track_dyn_async: set is NULL");
+    // (without a context the set was not looked up and is not looked into: the call ends at bind_device)
+    if (ctx && !own(ctx, &TransformState::dyns, set))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_track_dyn_async: not a curve set of this context");
+    if (const char *why = dyn_call_error(rows_dev, row_stride, len_dev, n_rows, key_dev, key_stride, n_keys, key_row_dev, out_dev, out_stride))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_track_dyn_async: ") + why);
+    // (a workgroup a row)
+    if (n_rows > 0x7FFFFFFFull) return fail(GRAIL_ERR_INVALID_ARG, "grail_track_dyn_async: more than 2^31 workgroups");
+    int rc = bind_device(ctx, "grail_track_dyn_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (row_stride == 0 && !out_len_dev && !nonfinite_dev && !min_gain_dev) return GRAIL_OK;    // (rows of no samples, and nobody asks)
+    DynArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows, a.curve = curve_dev;
+    a.image = set->d_image.get(), a.alpha = set->d_alpha.get(), a.detector = set->d_detector.get(), a.n_curves = set->n_curves;
+    a.key = key_dev, a.key_stride = key_stride, a.key_len = key_len_dev, a.n_keys = n_keys, a.key_row = key_row_dev;
+    a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev, a.min_gain = min_gain_dev;
+    const hipError_t e = launch_track_dyn(a, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "track dyn kernel launch");
     return GRAIL_OK;
 }
 

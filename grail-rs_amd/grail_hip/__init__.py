@@ -95,6 +95,7 @@ EXPORTS = [
     "grail_iir_stream_len", "grail_iir_stream_open", "grail_iir_stream_next_async", "grail_iir_stream_finish_async",
     "grail_iir_stream_close",
     "grail_dyn_design", "grail_dyn_ballistics", "grail_dyn_create", "grail_dyn_free", "grail_dyn_async",
+    "grail_track_dyn_async",
     "grail_dyn_stream_open", "grail_dyn_stream_next_async", "grail_dyn_stream_close",
 ]
 MIX_ACCUMULATE = 1               # GRAIL_MIX_ACCUMULATE
@@ -454,6 +455,7 @@ def load():
     L.grail_dyn_create.argtypes = [vp, vp, vp, vp, C.c_uint32, vp]
     L.grail_dyn_free.argtypes = [vp, vp]
     L.grail_dyn_async.argtypes = [vp, vp, vp, u64, vp, C.c_uint32, vp, vp, u64, vp, C.c_uint32, vp, vp, u64, vp, vp, vp]
+    L.grail_track_dyn_async.argtypes = list(L.grail_dyn_async.argtypes)
     L.grail_dyn_stream_open.argtypes = [vp, vp, C.c_uint32, vp, C.c_uint32, vp, vp]
     L.grail_dyn_stream_next_async.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, u64, vp, vp, vp]
     L.grail_dyn_stream_close.argtypes = [vp, vp]
@@ -1751,6 +1753,23 @@ class Context:
                              lambda *d: self.dyn_async(dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev, out_stride,
                                                        *d, key_dev=key_dev, key_stride=key_stride, key_len_dev=key_len_dev,
                                                        n_keys=n_keys, key_row_dev=key_row_dev))
+
+    def track_dyn_async(self, dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev, out_stride, out_len_dev=None,
+                        nonfinite_dev=None, min_gain_dev=None, key_dev=None, key_stride=0, key_len_dev=None, n_keys=0, key_row_dev=None):
+        """grail_track_dyn_async: dyn_async's arguments, results and bits with a workgroup a row, for the few long tracks of a
+        mix (the header's WHICH CALL FOR WHAT says below how many rows)."""
+        _check(load().grail_track_dyn_async(self.handle, dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, key_dev, key_stride,
+                                            key_len_dev, n_keys, key_row_dev, out_dev, out_stride, out_len_dev, nonfinite_dev,
+                                            min_gain_dev))
+
+    def track_dyn(self, dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev, out_stride, key_dev=None, key_stride=0,
+                  key_len_dev=None, n_keys=0, key_row_dev=None):
+        """track_dyn_async, waited for, the results copied back as dyn does: (out_len uint32, nonfinite uint32, min_gain
+        float64), one per row."""
+        return _waited_sized(self, n_rows, (np.uint32, np.uint32, np.float64),
+                             lambda *d: self.track_dyn_async(dyn_set, rows_dev, row_stride, len_dev, n_rows, curve_dev, out_dev,
+                                                             out_stride, *d, key_dev=key_dev, key_stride=key_stride,
+                                                             key_len_dev=key_len_dev, n_keys=n_keys, key_row_dev=key_row_dev))
 
     def dyn_stream_open(self, dyn_set, n_rows, curves=None, n_keys=0, key_rows=None):
         """grail_dyn_stream_open: a stream of n_rows rows compressed call by call, row u bound to curve curves[u] of the set (a

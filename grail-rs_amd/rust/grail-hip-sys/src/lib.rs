@@ -431,6 +431,10 @@ extern "C" {
         n_rows: u32, curve_dev: *const u32, key_dev: *const f32, key_stride: u64, key_len_dev: *const u32, n_keys: u32,
         key_row_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32, nonfinite_dev: *mut u32,
         min_gain_dev: *mut f64) -> c_int;
+    pub fn grail_track_dyn_async(ctx: *mut grail_ctx, set: *const grail_dyn, rows_dev: *const f32, row_stride: u64, len_dev: *const u32,
+        n_rows: u32, curve_dev: *const u32, key_dev: *const f32, key_stride: u64, key_len_dev: *const u32, n_keys: u32,
+        key_row_dev: *const u32, out_dev: *mut f32, out_stride: u64, out_len_dev: *mut u32, nonfinite_dev: *mut u32,
+        min_gain_dev: *mut f64) -> c_int;
     pub fn grail_dyn_stream_open(ctx: *mut grail_ctx, set: *const grail_dyn, n_rows: u32, curve: *const u32, n_keys: u32,
         key_row: *const u32, out: *mut *mut grail_dyn_stream) -> c_int;
     pub fn grail_dyn_stream_next_async(ctx: *mut grail_ctx, ds: *mut grail_dyn_stream, in_dev: *const f32, in_stride: u64,

@@ -816,6 +816,19 @@ impl Gpu {
     /// smallest gain it was given (1.0 for an empty row); a row whose curve or key index is outside comes back empty with a NaN.
     pub fn dynamics(&self, set: &DynSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, keys: Option<(&[Vec<f32>], &[u32])>)
                     -> Result<(Vec<Vec<f32>>, Vec<u32>, Vec<f64>), Error> {
+        self.dynamics_rows(set, rows, which, keys, false)
+    }
+
+    /// [`Gpu::dynamics`] with a workgroup a row (`grail_track_dyn_async`; the header's section "levels, continued: dynamics, a
+    /// workgroup a row"): the call for the few long tracks of a mix, [`Gpu::dynamics`] the one for many rows.  Bit for bit
+    /// [`Gpu::dynamics`] in every result: only the envelope's chain stays serial, the rest of a sample's work does not.
+    pub fn track_dynamics(&self, set: &DynSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, keys: Option<(&[Vec<f32>], &[u32])>)
+                          -> Result<(Vec<Vec<f32>>, Vec<u32>, Vec<f64>), Error> {
+        self.dynamics_rows(set, rows, which, keys, true)
+    }
+
+    fn dynamics_rows(&self, set: &DynSet<'_>, rows: &[Vec<f32>], which: Option<&[u32]>, keys: Option<(&[Vec<f32>], &[u32])>, tracks: bool)
+                     -> Result<(Vec<Vec<f32>>, Vec<u32>, Vec<f64>), Error> {
         let n = rows.len();
         let mut out: Vec<Vec<f32>> = vec![Vec::new(); n];
         let mut out_lens = vec![0u32; n];
@@ -870,10 +883,11 @@ impl Gpu {
                 }
             }
             if r.is_ok() {
-                r = check(sys::grail_dyn_async(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
-                                               d[6] as *const u32, d[7] as *const f32, key_stride as u64, d[8] as *const u32,
-                                               n_keys as u32, d[9] as *const u32, d[1] as *mut f32, stride as u64, d[3] as *mut u32,
-                                               d[4] as *mut u32, d[5] as *mut f64));
+                let call = if tracks { sys::grail_track_dyn_async } else { sys::grail_dyn_async };
+                r = check(call(self.ctx, set.set, d[0] as *const f32, stride as u64, d[2] as *const u32, n as u32,
+                               d[6] as *const u32, d[7] as *const f32, key_stride as u64, d[8] as *const u32,
+                               n_keys as u32, d[9] as *const u32, d[1] as *mut f32, stride as u64, d[3] as *mut u32,
+                               d[4] as *mut u32, d[5] as *mut f64));
             }
             if r.is_ok() {
                 r = check(sys::grail_memcpy_d2h(self.ctx, out_lens.as_mut_ptr() as *mut std::ffi::c_void, d[3], n * 4));

@@ -1574,9 +1574,11 @@ int grail_iir_stream_close(grail_ctx *ctx, grail_iir_stream *is);
  * WHAT THE TABLE PROMISES: between two points the curve is the chord.  Against the ideal formula that is within 0.01 dB
  * on a segment that holds no corner of the curve and within 0.14 dB on the one segment that holds a hard corner (DESIGN.md
  * §4.23 derives and measures both).
- * A LONE LONG ROW is one lane's serial work, as in grail_iir_async, and there is no form parallel in time: the branch on
- * a > e makes the recurrence non-linear.  NOT here: look-ahead (the limiter is the look-ahead stage), linked groups that take
- * the maximum over members (a shared key row is what there is), smoothing in the log domain. */
+ * A LONE LONG ROW is one lane's serial work here, as in grail_iir_async.  The branch on a > e makes the recurrence
+ * non-linear, so the chain of step 4 stays serial whoever runs it; the rest of a sample's work no longer is: the next
+ * section, grail_track_dyn_async, gives a row a workgroup and writes these very bits.  NOT here: look-ahead (the limiter
+ * is the look-ahead stage), linked groups that take the maximum over members (a shared key row is what there is), smoothing
+ * in the log domain. */
 #define GRAIL_DYN_STEPS_PER_OCTAVE 16
 #define GRAIL_DYN_LOG2_LO (-32)
 #define GRAIL_DYN_LOG2_HI 8
@@ -1621,6 +1623,34 @@ int grail_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev,
                     uint64_t key_stride, const uint32_t *key_len_dev, uint32_t n_keys, const uint32_t *key_row_dev,
                     float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev,
                     double *min_gain_dev);
+
+/* ---- levels, continued: dynamics, a workgroup a row ------------------------------------------------------------------------------
+ * The same call for the few long tracks of a finished mix.  grail_dyn_async gives a row to one lane, which is right for
+ * thousands of utterances and leaves a lone track of minutes to one lane of one wavefront.  grail_track_dyn_async gives a row
+ * a workgroup.  Of a sample's work only step 4 of ROW above, alpha = (a > e) ? alpha_attack : alpha_release and
+ * e = a + alpha * (e - a), needs the sample before it: that chain stays serial, one lane's.  Steps 1 to 3 ahead of it and the
+ * lookup, the product, the rounding to binary32 and the candidate for min_gain behind it are done for 1 024 samples at a
+ * time by the workgroup's other lanes, a tile ahead of the chain and a tile behind it.
+ * THE BITS are those of ROW above, whatever the number of rows: this is no contract of its own.  Every operation is ROW's,
+ * in ROW's order, each rounded by itself; out, out_len, nonfinite and min_gain are bit for bit what grail_dyn_async writes
+ * for the same arguments, min_gain the first in time of equal gains (the sign of a zero gain included), over all t < n.
+ * Sets, keys, curves, refused rows, out_stride = 0, the 16-byte and 4-byte accesses: all as there.  No atomics.
+ * WHICH CALL FOR WHAT.  Both calls write the same bits, so the choice is one of time alone, and the library does not
+ * make it.  Measured on one MI355X (DESIGN.md §4.24, rows of 96 006 samples, call and sync): this call is the faster up to
+ * 512 rows and beyond: 2.1 ms against 11.8 ms for 1 row, 2.9 ms against 13.6 ms for 512 rows; at 4 096 rows the two are level
+ * (14.5 ms against 13.7 ms); at 65 536 rows grail_dyn_async is 14 times the faster (15.9 ms against 220 ms).  A lone row of
+ * 10^7 samples takes 221 ms here, 22 ns a sample, against 1 233 ms there, and eight such rows 238 to 264 ms (a launch's time
+ * moves by a fifth with where its workgroups land).  So: the tracks of a mix, up to a few hundred rows: this call.  The
+ * utterances of a batch, thousands of rows: grail_dyn_async.
+ * Arguments, checks and errors are grail_dyn_async's, in its order, with this call's name in grail_last_error; besides,
+ * GRAIL_ERR_INVALID_ARG for more than 2^31 - 1 rows (a workgroup a row).  These come first; without a usable device:
+ * GRAIL_ERR_NO_DEVICE.  n_rows = 0 is a success that queues nothing, and so is row_stride = 0 with no result asked for.
+ * NOT here: a stream form (grail_dyn_stream_* carries e between calls), a choice between the two calls made by the library. */
+int grail_track_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *rows_dev, uint64_t row_stride,
+                          const uint32_t *len_dev, uint32_t n_rows, const uint32_t *curve_dev, const float *key_dev,
+                          uint64_t key_stride, const uint32_t *key_len_dev, uint32_t n_keys, const uint32_t *key_row_dev,
+                          float *out_dev, uint64_t out_stride, uint32_t *out_len_dev, uint32_t *nonfinite_dev,
+                          double *min_gain_dev);
 
 /* ---- levels, continued: dynamics of streams ---------------------------------------------------------------------------------------
  * A DYNAMICS STREAM: n_rows independent rows, each bound to one curve of a live set (and, keyed, to one key row) when the
