@@ -4,7 +4,7 @@ of every length either side of a tile mixed in one wave, the scalar path against
 above a row, three curves with both detectors in one wave (a compressor, an expander with a range, and the caller's own
 staircase G[k] = k, on which a wrong k or f shows in every bit), refused rows, alphas of 0 and an attack far below the release,
 samples aimed at every edge of the lookup, and keyed calls: keys shorter and longer than their rows, key_len_dev NULL, two rows
-on one key, a key index outside, non-finite key samples, and a bed ducked under voices.  Every output buffer holds a canary
+on one key, a key index outside, non-finite key samples, keys of no samples, and a bed ducked under voices.  Every output buffer holds a canary
 wherever nothing may be written, and is checked there."""
 import ctypes as C
 
@@ -17,6 +17,18 @@ from test_levels_gpu import CANARY, Dev, dev  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
 LENGTHS = [0, 1, 3, 63, 64, 65, 127, 128, 129, 200, 1000]
+# dyn_kernel<VEC, KEYED, STREAM>: the eight that tests/test_dyn_code_objects.py finds in the library
+VARIANTS = [(vec, keyed, stream) for vec in (True, False) for keyed in (False, True) for stream in (False, True)]
+
+
+def variant(in_offset=0, stride=0, out_offset=0, out_stride=0, keyed=False, key_offset=0, key_stride=0, stream=False):
+    """the dyn_kernel<VEC, KEYED, STREAM> that launch_dyn starts: VEC by aligned16 over rows and out and, keyed, over the key
+    (the offsets are floats from a 16-byte aligned base).  keyed: the call brings a key_dev: a keyed stream's call of no
+    samples (in_stride 0) does not, and runs the unkeyed kernel."""
+    vec = in_offset % 4 == 0 and stride % 4 == 0 and out_offset % 4 == 0 and out_stride % 4 == 0
+    if keyed:
+        vec = vec and key_offset % 4 == 0 and key_stride % 4 == 0
+    return (vec, keyed, stream)
 
 
 def staircase():
@@ -55,8 +67,8 @@ def run(ctx, dev, dyn_set, rows, which=None, keys=None, key_row=None, key_lens=N
     d_which = None if which is None else dev.up(np.array(which, np.uint32))
     kw = {}
     if keys is not None:
-        key_stride = key_stride or (max([len(k) for k in keys] + [1]) + 63) // 64 * 64
-        khost = np.full(len(keys) * key_stride + key_offset, np.nan, np.float32)
+        key_stride = (max([len(k) for k in keys] + [1]) + 63) // 64 * 64 if key_stride is None else key_stride
+        khost = np.full(max(len(keys) * key_stride + key_offset, 4), np.nan, np.float32)          # (key_stride 0: keys of no samples)
         for j, k in enumerate(keys):
             khost[key_offset + j * key_stride:key_offset + j * key_stride + len(k)] = k
         kw = dict(key_dev=C.c_void_p(dev.up(khost).value + key_offset * 4), key_stride=key_stride, n_keys=len(keys),
@@ -209,6 +221,14 @@ def edge_samples():
     return x
 
 
+def edge_curves():
+    """the four settings the edge samples go through: the staircase at alpha = 0 on either detector, an expander whose release
+    rides below 2^-32, and the staircase on the square with alphas that are not 0"""
+    gate = G.dyn_design(G.DYN_EXPAND, G.DYN_PEAK, -150.0, 2.0, 10.0, 60.0, 0.0)       # its knee lies on the table's lower end
+    return [(staircase(), (0.0, 0.0), G.DYN_PEAK), (staircase(), (0.0, 0.0), G.DYN_SQUARE), (gate, (0.0, 0.5), G.DYN_PEAK),
+            (staircase(), (0.5, 0.96875), G.DYN_SQUARE)]
+
+
 def test_samples_on_the_lookups_edges(gpu_ctx, dev, sets):
     """every lev[k], the float32 below and above it, the squares' roots and their neighbours, magnitudes below 2^-32 and above
     2^8 (for the square: below 2^-16 and above 16), +-0.0, denormals, NaN and +-Inf: with alpha = 0 the staircase answers k + f
@@ -216,9 +236,7 @@ def test_samples_on_the_lookups_edges(gpu_ctx, dev, sets):
     same samples cross the table's lower end on the way down"""
     x = edge_samples()
     rng = np.random.default_rng(12)
-    gate = G.dyn_design(G.DYN_EXPAND, G.DYN_PEAK, -150.0, 2.0, 10.0, 60.0, 0.0)       # its knee lies on the table's lower end
-    curves = [(staircase(), (0.0, 0.0), G.DYN_PEAK), (staircase(), (0.0, 0.0), G.DYN_SQUARE), (gate, (0.0, 0.5), G.DYN_PEAK),
-              (staircase(), (0.5, 0.96875), G.DYN_SQUARE)]
+    curves = edge_curves()
     rows = [x, x, x, x, rng.permutation(x), rng.permutation(x)]
     which = [0, 1, 2, 3, 0, 1]
     want = M.dyn_model(rows, curves, which)
@@ -274,6 +292,26 @@ def test_a_row_may_be_its_own_key(gpu_ctx, dev, sets):
     want = M.dyn_model(rows, curves, [0, 1, 2])
     same(want, alone, "self-keyed")
     same(want, keyed, "keyed by itself")
+
+
+def test_keys_of_no_samples(gpu_ctx, dev, sets):
+    """key_stride 0 (the header allows it: keys of no samples): no key load is issued (`key_loads` false in the keyed kernel,
+    the key's tile never written), every key sample reads +0.0 and the gain is the curve's at e = +0.0 throughout, on either
+    path.  No other case runs a keyed call without a key load."""
+    rng = np.random.default_rng(16)
+    curves = three_curves()
+    rows = [audio(n, rng) for n in (200, 65, 0, 64, 129)]
+    rows[0][3] = np.nan
+    which = [0, 1, 2, 2, 1]
+    nothing = [np.zeros(0, np.float32)]
+    want = M.dyn_model(rows, curves, which, keys=nothing, key_row=[0] * 5)
+    at_rest = [float(np.asarray(curves[c][0], np.float64)[0]) for c in which]          # (e = +0.0 lies below the table: G[0] itself)
+    assert [w[3] for w in want] == [g if len(x) else 1.0 for g, x in zip(at_rest, rows)]
+    dyn_set = sets(curves)
+    for kw, vec in ((dict(stride=256, out_stride=256), True), (dict(stride=256, out_stride=256, in_offset=1), False),
+                    (dict(stride=256, out_stride=256, key_offset=1), False)):
+        assert variant(kw.get("in_offset", 0), 256, 0, 256, True, kw.get("key_offset", 0), 0) == (vec, True, False)
+        same(want, run(gpu_ctx, dev, dyn_set, rows, which, keys=nothing, key_row=[0] * 5, key_stride=0, **kw), ("no key samples", kw))
 
 
 def test_a_bed_ducks_under_the_voices_that_speak(gpu_ctx, dev, sets):

@@ -3,7 +3,8 @@ tests/iir_blocked_model.py, bit for bit in the filtered samples (NaN positions c
 non-finite counts: rows that end at, before and after a block's edge and the edge of a workgroup's 64 blocks, filters of one,
 three and eight sections in one launch, tails that stay inside a block and that cross one, the scalar path against the
 aligned one, out_stride cutting inside a row, counts without outputs, non-finite samples in several blocks and past a cut,
-refused rows, scratch left by a longer call, and a row of over a thousand blocks.  Against grail_iir_async on the device:
+refused rows, scratch left by a longer call, a row of over a thousand blocks, the section bounds below eight on both paths,
+and a workgroup that starts past its row's stride.  Against grail_iir_async on the device:
 the same bits over rows of one block and over every row's first block, and within the contract's bound elsewhere.  Every
 output buffer holds a canary wherever nothing may be written, and is checked there."""
 import ctypes as C
@@ -19,7 +20,7 @@ import grail_hip as G
 from iir_blocked_model import BLOCK, iir_blocked_model
 from iir_model import REFUSED
 from test_iir_blocked_host import BOUND, butterworth
-from test_iir_gpu import noise, random_filter, same_samples
+from test_iir_gpu import BOUNDS, bound_of, noise, random_filter, same_samples
 from test_levels_gpu import CANARY, Dev, dev  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -76,12 +77,50 @@ def sets(gpu_ctx):
         gpu_ctx.iir_free(s)
 
 
-def edge_rows():
-    rng = np.random.default_rng(41)
-    filters = [random_filter(S, rng, radius=0.999) for S in (1, 3, 8)]
-    rows = [noise(n, rng) for n in LENGTHS]
+# biquad_block_kernel<section bound, VEC, OUT> and biquad_block_propagate_kernel<section bound>: the twenty that
+# tests/test_iir_blocked_code_objects.py finds in the library
+VARIANTS = ([("block", sb, vec, out) for sb in BOUNDS for vec in (True, False) for out in (False, True)] +
+            [("propagate", sb) for sb in BOUNDS])
+# the lower bounds' rows: either side of a block's edge and of two blocks', and one sample into a second workgroup
+BOUND_LENGTHS = [0, 1, 1023, 1024, 1025, 2049, 65537]
+# a tail of 6: the row of one sample is a block of 7 steps and the long row's second workgroup has 7 to do (`extent` below a
+# block, all of it in the one-by-one remainder loop); of 1 030: the row of one sample has a second block of tail alone, the row
+# of 1 023 a third, and the long row's second workgroup a whole block and one more lane
+BOUND_TAILS = (6, 1030)
+BOUND_LAYOUTS = {"aligned": {}, "offset-odd": dict(in_offset=1, stride=65539, out_offset=1, out_stride=66577)}
+NOTCH = (G.IIR_NOTCH, 44100, 50.0, 30.0)       # poles of radius 0.99988 at 50 Hz: a block matrix with entries of very different size
+
+
+def variant(bound, in_offset=0, stride=0, out_offset=0, out_stride=0, tail=0):
+    """the kernels a call on a set of that bound launches (a row_stride above 0): the rest pass, whose VEC is decided by what it
+    loads alone, the output pass (aligned16 over both buffers), and the propagate wherever the grid has two blocks"""
+    vec_in = in_offset % 4 == 0 and stride % 4 == 0
+    vec_out = vec_in and out_offset % 4 == 0 and out_stride % 4 == 0
+    launched = {("block", bound, vec_in, False), ("block", bound, vec_out, True)}
+    if -(-(stride + tail) // BLOCK) >= 2:
+        launched.add(("propagate", bound))
+    return launched
+
+
+def edge_rows(bound=8):
+    """(filters, rows, which) for a set of that section bound: 8 is the rows of every length of LENGTHS on one, three and eight
+    sections; below it the rows of BOUND_LENGTHS on two filters, at bound 1 a one-pole section and a notch close to the circle"""
+    if bound == 8:
+        rng = np.random.default_rng(41)
+        filters = [random_filter(S, rng, radius=0.999) for S in (1, 3, 8)]
+        rows = [noise(n, rng) for n in LENGTHS]
+        rows[4][0] = np.float32(-0.0)
+        which = [0, 1, 2, 2, 1, 0, 2, 1, 2, 0]
+        return filters, rows, which
+    rng = np.random.default_rng(41 + bound)
+    if bound == 1:
+        filters = [np.array([[1.0, -1.0, 0.0, -0.9995, 0.0]]), np.array([G.iir_design(*NOTCH)])]
+    else:
+        filters = [random_filter(S, rng, radius=0.999) for S in {2: (2, 1), 4: (4, 3)}[bound]]
+    rows = [noise(n, rng) for n in BOUND_LENGTHS]
     rows[4][0] = np.float32(-0.0)
-    which = [0, 1, 2, 2, 1, 0, 2, 1, 2, 0]
+    rows[6][[3, 1024, 65536]] = (np.nan, -np.inf, np.inf)              # (the last in the second workgroup's count)
+    which = [0, 1, 1, 0, 1, 0, 1]
     return filters, rows, which
 
 
@@ -116,6 +155,83 @@ def test_the_scalar_path_gives_the_aligned_paths_bits(gpu_ctx, dev, sets, edges)
     for kw in (dict(in_offset=1, stride=70001, out_offset=1, out_stride=70011), dict(in_offset=1), dict(stride=70003),
                dict(out_offset=3), dict(out_stride=70009)):
         same(want(7), launch(gpu_ctx, dev, iir_set, rows, which, tail=7, **kw), kw)
+
+
+# ---- the lower section bounds -----------------------------------------------------------------------------------------------------
+_BOUND_MODEL = {}
+
+
+def bound_model(bound, tail):
+    """the rows of a lower bound and what the model makes of them, computed once"""
+    if (bound, tail) not in _BOUND_MODEL:
+        filters, rows, which = edge_rows(bound)
+        _BOUND_MODEL[bound, tail] = (filters, rows, which, iir_blocked_model(rows, filters, which, tail))
+    return _BOUND_MODEL[bound, tail]
+
+
+@pytest.mark.parametrize("layout", sorted(BOUND_LAYOUTS))
+@pytest.mark.parametrize("bound", [1, 2, 4])
+def test_the_lower_section_bounds_on_both_paths(gpu_ctx, dev, sets, bound, layout):
+    """biquad_block_kernel<bound, VEC, OUT> for both VEC and both passes and biquad_block_propagate_kernel<bound>, bit for bit
+    against the model: rows that end either side of a block's edge, a row one sample into a second workgroup (whose one lane
+    of the rest pass and two of the output pass are the only active ones), blocks of tail alone, rows of fewer blocks than the
+    grid (their second workgroup leaves at once, the row of no samples' first one too).  At bound 1 also against
+    grail_iir_async on the device, as test_against_the_serial_call_on_the_device does: the first block identical, the rest
+    within BOUND of the row's peak and half a unit in the last place of each."""
+    kw = BOUND_LAYOUTS[layout]
+    stride, out_stride = kw.get("stride", 65600), kw.get("out_stride", 66624)
+    offsets = {k: v for k, v in kw.items() if k.endswith("offset")}
+    vec = layout == "aligned"
+    # (the arithmetic of the lines this case is named for in tests/KERNEL_PATHS.md)
+    steps = {tail: [n + tail if n else 0 for n in BOUND_LENGTHS] for tail in BOUND_TAILS}
+    assert [-(-k // BLOCK) for k in steps[6]] == [0, 1, 2, 2, 2, 3, 65] and [-(-k // BLOCK) for k in steps[1030]] == [0, 2, 3, 3, 3, 4, 66]
+    assert steps[6][1] == 7 and steps[6][6] - 64 * BLOCK == 7 and 7 % 4                           # an extent of 7: the remainder loop
+    assert steps[1030][1] > BLOCK >= 1 and steps[1030][2] > 2 * BLOCK >= 1023                      # blocks of tail alone
+    for tail in BOUND_TAILS:
+        filters, rows, which, want = bound_model(bound, tail)
+        assert bound_of(filters) == bound and -(-(stride + tail) // BLOCK) > 64                    # two workgroups a row
+        assert variant(bound, kw.get("in_offset", 0), stride, kw.get("out_offset", 0), out_stride, tail) == \
+            {("block", bound, vec, False), ("block", bound, vec, True), ("propagate", bound)}
+        assert [r[1] for r in want] == steps[tail] and want[6][2] == 3
+        iir_set = sets(filters)
+        blocked = launch(gpu_ctx, dev, iir_set, rows, which, tail=tail, stride=stride, out_stride=out_stride, **offsets)
+        same(want, blocked, (bound, layout, tail))
+        if bound != 1:
+            continue
+        serial = launch(gpu_ctx, dev, iir_set, rows, which, tail=tail, stride=stride, out_stride=out_stride, call="iir", **offsets)
+        assert np.array_equal(serial[1], blocked[1]) and np.array_equal(serial[2], blocked[2])
+        for i in range(len(rows)):
+            n_out = int(serial[1][i])
+            ys, yb = serial[0][i, :n_out], blocked[0][i, :n_out]
+            same_samples(yb[:BLOCK], ys[:BLOCK], (layout, tail, i, "the first block"))
+            if n_out <= BLOCK:
+                continue
+            peak = float(np.max(np.abs(ys)))
+            apart = np.abs(yb.astype(np.float64) - ys.astype(np.float64))
+            allowed = BOUND * peak + 0.5 * (np.spacing(np.abs(ys)).astype(np.float64) + np.spacing(np.abs(yb)).astype(np.float64))
+            worst = int(np.argmax(apart - allowed))
+            print(f"\n{layout} tail {tail} row {i} ({len(rows[i])} samples): the largest |blocked - serial| {apart.max() / peak:.3e} of the peak")
+            assert apart[worst] <= allowed[worst], (layout, tail, i, worst, ys[worst], yb[worst])
+
+
+@pytest.mark.parametrize("bound", BOUNDS)
+def test_a_workgroup_whose_first_step_lies_past_the_stride(gpu_ctx, dev, sets, bound):
+    """a row that fills its stride of 65 536 samples and rings out for 7 more: block 64 is the second workgroup's, it starts at
+    or past the row's last group (sample) of four, so `start_in` is held at row_last and every load of the workgroup reads that
+    one.  No other case has a workgroup start past row_last (the rows of 65 537 and 70 000 samples lie in longer strides)."""
+    filters = edge_rows(bound)[0] if bound != 8 else edge_rows(8)[0][1:]
+    assert bound_of(filters) == bound
+    rng = np.random.default_rng(46 + bound)
+    rows = [noise(65536, rng), noise(1, rng)]
+    rows[0][[65535, 1024]] = (np.nan, np.float32(-0.0))
+    want = iir_blocked_model(rows, filters, [0, 1], 7)
+    assert [w[1:] for w in want] == [(65543, 1), (8, 0)]
+    iir_set = sets(filters)
+    for in_offset, row_last in ((0, 65532), (1, 65535)):
+        assert variant(bound, in_offset, 65536, 0, 65600, 7) == {("block", bound, not in_offset, False), ("block", bound, not in_offset, True),
+                                                              ("propagate", bound)}
+        assert 64 * BLOCK > row_last                                                   # the second workgroup's first step
+        same(want, launch(gpu_ctx, dev, iir_set, rows, [0, 1], tail=7, stride=65536, out_stride=65600, in_offset=in_offset), (bound, in_offset))
 
 
 # ---- cuts, counts, refusals -----------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Recursive filtering on the device (grail_iir_async) against the numpy model of tests/iir_model.py, bit for bit in the
 filtered samples (NaN positions compared as NaN), the lengths and the non-finite counts: partial last waves, rows that end at,
-before and after a tile's edge and all of them in one wave, a len beyond the stride, the scalar path against the aligned one,
+before and after a tile's edge and all of them in one wave, a len beyond the stride, the scalar path against the aligned one
+under every section bound (and strides of 1 and 4, where every load is clamped),
 out_stride cutting inside a row and inside its tail, tails with and without samples before them, a decay through the
 denormals of both formats, filters of one to eight sections in one wave, rows on different filters and on none, non-finite
 samples, a filter that overflows, and a row's bits wherever it lies in the launch.  Every output buffer holds a canary
@@ -19,6 +20,26 @@ pytestmark = pytest.mark.gpu
 TILE = 64                                       # the samples of a row that one pass of the kernel's loop takes
 LENGTHS = [0, 1, 63, 64, 65, 127, 128, 129, 300]
 IDENTITY = [1.0, 0.0, 0.0, 0.0, 0.0]
+# iir_kernel<section bound, VEC, STREAM>: the sixteen that tests/test_iir_code_objects.py finds in the library
+BOUNDS = (1, 2, 4, 8)
+VARIANTS = [(sb, vec, stream) for sb in BOUNDS for vec in (True, False) for stream in (False, True)]
+
+
+def bound_of(filters):
+    """the section bound a set of these filters is launched with: iir_set_image's power of two at or above the largest filter's
+    sections, through iir_launch_bound's dispatch (<= 1, == 2, <= 4, else 8)"""
+    most = max(len(np.asarray(f, np.float64).reshape(-1, 5)) for f in filters)
+    bound = 1
+    while bound < most:
+        bound <<= 1
+    return 1 if bound <= 1 else (2 if bound == 2 else (4 if bound <= 4 else 8))
+
+
+def variant(bound, in_offset=0, stride=0, out_offset=0, out_stride=0, stream=False):
+    """the iir_kernel<SB, VEC, STREAM> that launch_iir starts for a set of that bound: VEC by aligned16 over both buffers (the
+    offsets are floats from a 16-byte aligned base; a finishing call has no input: in_offset = stride = 0)"""
+    vec = in_offset % 4 == 0 and stride % 4 == 0 and out_offset % 4 == 0 and out_stride % 4 == 0
+    return (bound, vec, stream)
 
 
 def random_filter(S, rng, radius=0.95):
@@ -130,21 +151,45 @@ def test_a_wave_of_every_length_and_a_len_beyond_the_stride(gpu_ctx, dev, sets):
     assert [w[1] for w in want] == [137, 109, 137]
 
 
-def test_the_scalar_path_gives_the_aligned_paths_bits(gpu_ctx, dev, sets):
-    """a base 4 bytes off 16-byte alignment and a stride of 301 on either side, and each side alone"""
-    rng = np.random.default_rng(6)
-    filters = [random_filter(S, rng) for S in (2, 5)]
+# the layouts of the scalar-path case: both sides off, then each side's base and each side's stride alone
+SCALAR_LAYOUTS = (dict(in_offset=1, stride=301, out_offset=1, out_stride=321), dict(in_offset=1, stride=304, out_stride=384),
+                  dict(stride=301, out_stride=384), dict(stride=304, out_offset=3, out_stride=384), dict(stride=304, out_stride=322))
+SCALAR_SECTIONS = {1: (1, 1), 2: (2, 1), 4: (4, 3), 8: (8, 5)}             # the two filters of a set, by its largest's sections
+
+
+@pytest.mark.parametrize("most", BOUNDS)
+def test_the_scalar_path_gives_the_aligned_paths_bits(gpu_ctx, dev, sets, most):
+    """a base 4 bytes off 16-byte alignment and a stride of 301 on either side, and each side alone, under every section bound:
+    iir_kernel<most, false, false> by all five layouts, <most, true, false> by the aligned one.  Then the smallest strides
+    there are, 1 (scalar) and 4 (VEC), under rows of 1 and 4 samples that ring out over two tiles: every load of every tile
+    is past the stride or past the launch's last row or both, and reads the row's last sample or group."""
+    rng = np.random.default_rng(6 + most)
+    filters = [random_filter(S, rng) for S in SCALAR_SECTIONS[most]]
+    assert bound_of(filters) == most
     rows = [noise(n, rng) for n in (301, 300, 0, 17, 64, 299, 301)]
     which = [0, 1, 1, 0, 1, 0, 1]
     iir_set = sets(filters)
+    assert variant(most, 0, 304, 0, 384) == (most, True, False)
     aligned = run(gpu_ctx, dev, iir_set, rows, which, tail=20, stride=304, out_stride=384)
     want = same(rows, filters, which, 20, aligned, "aligned")
-    for kw in (dict(in_offset=1, stride=301, out_offset=1, out_stride=321), dict(in_offset=1, stride=304, out_stride=384),
-               dict(stride=301, out_stride=384), dict(stride=304, out_offset=3, out_stride=384), dict(stride=304, out_stride=322)):
+    for kw in SCALAR_LAYOUTS:
+        assert variant(most, kw.get("in_offset", 0), kw["stride"], kw.get("out_offset", 0), kw["out_stride"]) == (most, False, False)
         out, out_len, bad = run(gpu_ctx, dev, iir_set, rows, which, tail=20, **kw)
         same(rows, filters, which, 20, (out, out_len, bad), kw)
         for i, (y, n_out, _) in enumerate(want):
             same_samples(out[i, :n_out], aligned[0][i, :n_out], (kw, i))
+    # strides of 1 and 4: tail 70 makes two tiles (the second one's prefetch lies past the stride as a whole), seven rows
+    # leave 57 lanes of the wave on the clamped last row, and 71 and 74 outputs end in a partial group of four
+    ones = [noise(n, rng) for n in (1, 1, 0, 1, 1, 1, 1)]
+    fours = [noise(n, rng) for n in (4, 1, 0, 4, 3, 4, 1)]
+    ones[1][0] = fours[3][3] = np.nan
+    for short, kw in ((ones, dict(stride=1, out_stride=75)), (ones, dict(stride=1, out_stride=72)), (fours, dict(stride=4, out_stride=76)),
+                      (fours, dict(stride=4, out_stride=75))):
+        vec = kw["stride"] == 4 and kw["out_stride"] % 4 == 0
+        assert variant(most, 0, kw["stride"], 0, kw["out_stride"]) == (most, vec, False)
+        assert 64 < max(len(x) for x in short) + 70 <= 128 and len(short) % 64 != 0
+        got = same(short, filters, which, 70, run(gpu_ctx, dev, iir_set, short, which, tail=70, **kw), kw)
+        assert [w[1] for w in got] == [len(x) + 70 if len(x) else 0 for x in short]
 
 
 def test_out_stride_cuts_inside_the_row_and_inside_the_tail(gpu_ctx, dev, sets):

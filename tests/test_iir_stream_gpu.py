@@ -3,14 +3,15 @@ to end and then the tail are grail_iir_async's row, bit for bit, and the calls' 
 of 300 - 700 samples on filters of one to eight sections, split into calls of 63, 64, 65 samples, of random sizes that
 differ from row to row with empty calls in between, and of 1 sample (seventy such calls, across a tile's edge at 64, then the
 rest of every row in one call: a row of 700 in calls of one would be 700 launches and as many copies); finish with and without a tail, and on some rows while the others go
-on; a row fed after its end; a set that cannot be freed while a stream is open on it.  Every output buffer holds a canary
-wherever nothing may be written."""
+on; every section bound on both paths with rows paused inside a call; a row fed after its end; a set that cannot be freed
+while a stream is open on it.  Every output buffer holds a canary wherever nothing may be written."""
 import numpy as np
 import pytest
 
 import grail_hip as G
 from iir_model import REFUSED, IirStreamModel, iir_model
-from test_iir_gpu import noise, random_filter, same_samples
+from test_iir_gpu import BOUNDS, bound_of, noise, random_filter, same_samples, variant
+from test_iir_host import NEGATIVE_ZEROS
 from test_levels_gpu import CANARY, Dev, dev  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
@@ -233,6 +234,94 @@ def test_a_row_fed_nothing_has_no_tail_and_a_stream_without_a_tail_writes_none(g
                 same_samples(np.concatenate([got[r], tails[r]]), want[r][0], (tail, r))
             gpu_ctx.iir_stream_close(stream)
     finally:
+        gpu_ctx.iir_free(iir_set)
+
+
+# ---- every section bound on both paths ------------------------------------------------------------------------------------------
+BOUND_SECTIONS = {1: (1, 1, 1), 2: (2, 1, 2), 4: (4, 3, 1), 8: (8, 5, 2)}        # a set's filters, by its largest's sections
+BOUND_LAYOUTS = {"aligned": dict(in_stride=208, out_stride=208), "offset-odd": dict(in_stride=201, out_stride=203, in_offset=1, out_offset=3)}
+BOUND_TAIL = 37
+MINUS_ROW = 9                                                                     # bound 1: a row of -0.0 through NEGATIVE_ZEROS
+
+
+def bound_case(most):
+    """(rows, filters, which): 65 rows of 60 - 200 samples (a whole wave and a wave of one row), some samples not finite, on a
+    set whose largest filter has `most` sections; at bound 1 a section that answers silence with -0.0, fed a row of -0.0"""
+    rng = np.random.default_rng(50 + most)
+    filters = [random_filter(S, rng) for S in BOUND_SECTIONS[most]]
+    rows = [noise(int(rng.integers(60, 201)), rng) for _ in range(ROWS)]
+    rows[0], rows[64] = noise(200, rng), noise(60, rng)
+    for x in rows[::6]:
+        x[rng.integers(0, len(x), 4)] = (np.nan, np.inf, -np.inf, np.float32(-0.0))
+    which = [int(f) for f in rng.integers(0, len(filters), ROWS)]
+    which[0] = 0                                                                  # (the largest filter is in use)
+    if most == 1:
+        filters.append(np.array([NEGATIVE_ZEROS]))
+        rows[MINUS_ROW], which[MINUS_ROW] = np.full(70, -0.0, np.float32), len(filters) - 1
+    return rows, filters, which
+
+
+def bound_calls(rows):
+    """[call][row]: 63 samples (every seventh row paused: its lane keeps its state while the wave runs 63 steps), 1 sample, the
+    rest (every fifth row paused while its neighbours run whole tiles), then the rest of those"""
+    left = np.array([len(x) for x in rows])
+    r = np.arange(len(rows))
+    calls = []
+    for n in (np.where(r % 7 == 3, 0, 63), np.full(len(rows), 1), np.where(r % 5 == 2, 0, 1000), np.full(len(rows), 1000)):
+        calls.append(np.minimum(n, left))
+        left = left - calls[-1]
+    assert not left.any() and (calls[2][r % 5 != 2] - 64).max() > 64 and calls[3].max() > 64
+    return calls
+
+
+@pytest.mark.parametrize("layout", sorted(BOUND_LAYOUTS))
+@pytest.mark.parametrize("most", BOUNDS)
+def test_every_section_bound_on_both_paths(gpu_ctx, dev, most, layout):
+    """iir_kernel<most, VEC, true> for both VEC, in `next` and in `finish`: call by call against IirStreamModel, and the calls
+    put end to end against grail_iir_async.  Some rows are finished by marks while the others are not, then the rest."""
+    rows, filters, which = bound_case(most)
+    kw = BOUND_LAYOUTS[layout]
+    vec = layout == "aligned"
+    assert bound_of(filters) == most
+    assert variant(most, kw.get("in_offset", 0), kw["in_stride"], kw.get("out_offset", 0), kw["out_stride"], True) == (most, vec, True)
+    assert variant(most, 0, 0, kw.get("out_offset", 0), kw["out_stride"], True) == (most, vec, True)            # the finishing calls
+    iir_set = gpu_ctx.iir_create(filters)
+    stream = gpu_ctx.iir_stream_open(iir_set, ROWS, which, BOUND_TAIL)
+    model = IirStreamModel(filters, which, BOUND_TAIL)
+    try:
+        whole, whole_bad = one_shot(gpu_ctx, dev, iir_set, rows, which, BOUND_TAIL)
+        feeder = Feeder(gpu_ctx, dev, stream, ROWS, **kw)
+        fed = np.zeros(ROWS, np.int64)
+        pieces, bads = [[] for _ in rows], np.zeros(ROWS, np.int64)
+        for c, n in enumerate(bound_calls(rows)):
+            chunks = [rows[r][fed[r]:fed[r] + n[r]] for r in range(ROWS)]
+            got, out_len, bad = feeder.next(chunks)
+            want = model.next(chunks)
+            for r in range(ROWS):
+                assert (out_len[r], bad[r]) == (want[r][1], want[r][2]) and out_len[r] == n[r], (c, r)
+                same_samples(got[r], want[r][0], (most, layout, c, r, "against the model"))
+                pieces[r].append(got[r])
+            bads += bad
+            fed += n
+        marks = np.arange(ROWS) % 3 == 0
+        for which_rows in (marks.astype(np.uint8), None):
+            tails, tail_len = feeder.finish(which_rows)
+            want_tails = model.finish(None if which_rows is None else marks)
+            takes = marks if which_rows is not None else ~marks
+            assert tail_len.tolist() == [BOUND_TAIL if m else 0 for m in takes]
+            for r in range(ROWS):
+                same_samples(tails[r], want_tails[r], (most, layout, r, "the tail against the model"))
+                pieces[r].append(tails[r])
+        for r in range(ROWS):
+            same_samples(np.concatenate(pieces[r]), whole[r], (most, layout, r, "against grail_iir_async"))
+        assert bads.tolist() == whole_bad.tolist() and bads.sum() > 0
+        if most == 1:
+            # what the row of -0.0 is there for: b0 = -1 answers -0.0 with +0.0, which is what leaves; the sample itself, had
+            # the select kept it, is -0.0 (and the tail, on +0.0, answers +0.0, +0.0, -0.0 in turn, as the rows' call on silence)
+            y = np.concatenate(pieces[MINUS_ROW])
+            assert np.all(y[:70].view(np.uint32) == 0) and np.signbit(y[70:76]).tolist() == [False, False, True] * 2
+    finally:
+        gpu_ctx.iir_stream_close(stream)
         gpu_ctx.iir_free(iir_set)
 
 

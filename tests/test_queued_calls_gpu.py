@@ -1,6 +1,8 @@
 """Post-processing calls queued behind one another with no wait from the host in between: the host-side code that protects a
 kernel still queued (DeviceBuffer::reserve waits before a scratch grows, resample_table before the oldest of its four
-tables goes, grail_fir_free before a set goes; a table's upload from pageable memory) runs with work in the queue.  Every
+tables goes, grail_fir_free, grail_iir_free and grail_dyn_free before a set goes; a table's upload from pageable memory, and
+a filter set's block matrices; the scratch of the blocked recursive filter; the row indices a stream is opened with) runs with
+work in the queue.  Every
 input is uploaded and every buffer allocated before a test's first call, every result goes to a device buffer, the test
 waits once at the end, and what it then downloads is the models' bits.  A context of its own per test: its scratch and its
 table cache start empty."""
@@ -9,10 +11,15 @@ import pytest
 
 import grail_hip as G
 from grail_hip import workload as W
+import dyn_model as M
 from fir_model import fir_model
+from iir_blocked_model import iir_blocked_model
+from iir_model import iir_model
 from resample_model import resample_model
 from test_levels_gpu import CANARY, Dev, _awkward, same_bits
 from test_levels_host import row_model
+from test_dyn_gpu import three_curves
+from test_iir_gpu import random_filter
 from test_limiter_host import limiter_model
 from test_true_peak_host import true_peak_model
 
@@ -306,3 +313,182 @@ def test_lengths_flow_on_the_device_through_five_stages(ctx, dev):
         assert tp[i] == w_tp > 0 and u32(d_tp_bad)[i] == w_tp_bad == 0
         w_sumsq, w_peak, w_lv_bad = row_model(fir[i, :n_fir])
         assert sumsq[i] == w_sumsq > 0 and peak[i] == w_peak and u32(d_lv_bad)[i] == w_lv_bad == 0
+
+
+# ---- e. recursive filters and dynamics ------------------------------------------------------------------------------------------
+def _blocked(ctx, dev, iir_set, rows, tail):
+    """a blocked call's buffers, all made here -> what _blocked_check needs once the queue has drained"""
+    stride = (max(len(x) for x in rows) + 63) // 64 * 64
+    out_stride = stride + (tail + 63) // 64 * 64
+    d_rows, d_len = _up(dev, rows, stride)
+    return (iir_set, d_rows, stride, d_len, len(rows), None, tail, _canary(dev, len(rows), out_stride), out_stride,
+            dev.alloc(len(rows) * 4), dev.alloc(len(rows) * 4))
+
+
+def _blocked_check(dev, call, rows, filters, what):
+    _, _, _, _, n, _, tail, d_out, out_stride, d_out_len, d_bad = call
+    want = iir_blocked_model(rows, filters, None, tail)
+    _rows_equal(dev.down(d_out, (n, out_stride), np.float32), [w[0] for w in want], what)
+    assert np.array_equal(dev.down(d_out_len, n, np.uint32), [w[1] for w in want]), what
+    assert np.array_equal(dev.down(d_bad, n, np.uint32), [w[2] for w in want]), what
+
+
+def test_a_sets_block_matrices_go_up_and_the_blocked_scratch_grows_with_work_queued(ctx, dev):
+    """the context's first blocked call is a new set's first: its block matrices are made on the host and uploaded from there
+    with nothing waited for.  Behind it a call on another set with longer rows and more of them, for which both the block
+    states and the workgroups' counts grow with the first call still queued on them; then the first set again, on a small
+    call.  All three are the model's bits."""
+    rng = np.random.default_rng(51)
+    first, second = [random_filter(2, rng, radius=0.999)], [random_filter(3, rng, radius=0.999)]
+    small, large = [_noise(rng, n) for n in (1500, 0, 1025)], [_noise(rng, n) for n in (70000, 4097, 1, 66000)]
+    a, b = ctx.iir_create(first), ctx.iir_create(second)
+    try:
+        calls = [_blocked(ctx, dev, a, small, 9), _blocked(ctx, dev, b, large, 40), _blocked(ctx, dev, a, small[::-1], 2000)]
+        # (blocks of states and workgroups of counts: the second call needs more of both than the first left)
+        grid = [-(-(c[2] + c[6]) // 1024) for c in calls]
+        assert 4 * grid[1] * 2 * 4 > 3 * grid[0] * 2 * 2 and 4 * -(-grid[1] // 64) > 3 * -(-grid[0] // 64) and grid[2] < grid[1]
+        for c in calls:
+            ctx.iir_blocked_async(*c)
+        ctx.sync()
+    finally:
+        ctx.iir_free(a)
+        ctx.iir_free(b)
+    _blocked_check(dev, calls[0], small, first, "the set's first blocked call")
+    _blocked_check(dev, calls[1], large, second, "the larger call")
+    _blocked_check(dev, calls[2], small[::-1], first, "the small call behind it")
+
+
+def test_an_iir_set_and_a_curve_set_are_freed_with_work_queued_and_others_created(ctx, dev):
+    """grail_iir_free and grail_dyn_free at once behind a call of the set's own (they wait for what is queued), a different set
+    of the same shape created (which may get the freed one's memory) and used: each result is its own set's"""
+    rng = np.random.default_rng(52)
+    filters = [[random_filter(3, rng), random_filter(1, rng)] for _ in range(2)]
+    comp = [G.dyn_design(G.DYN_COMPRESS, G.DYN_PEAK, t, 4.0, 6.0, 0.0, 0.0) for t in (-30.0, -12.0)]
+    curves = [[(comp[k], G.dyn_ballistics(48000, 1.0, 50.0 + 100.0 * k), G.DYN_PEAK), (np.arange(M.POINTS, dtype=np.float64) + k, (0.25, 0.875), G.DYN_SQUARE)]
+              for k in range(2)]
+    rows = [_noise(rng, n) for n in (700, 129, 0, 1000)]
+    which = [0, 1, 1, 0]
+    stride, out_stride, tail = 1024, 1088, 40
+    d_rows, d_len = _up(dev, rows, stride)
+    d_which = dev.up(np.array(which, np.uint32))
+    iir_res = [(_canary(dev, 4, out_stride), dev.alloc(16), dev.alloc(16)) for _ in range(2)]
+    dyn_res = [(_canary(dev, 4, out_stride), dev.alloc(16), dev.alloc(16), dev.alloc(32)) for _ in range(2)]
+    a = ctx.iir_create(filters[0])
+    ctx.iir_async(a, d_rows, stride, d_len, 4, d_which, tail, iir_res[0][0], out_stride, iir_res[0][1], iir_res[0][2])
+    ctx.iir_free(a)
+    b = ctx.iir_create(filters[1])
+    ctx.iir_async(b, d_rows, stride, d_len, 4, d_which, tail, iir_res[1][0], out_stride, iir_res[1][1], iir_res[1][2])
+    c = ctx.dyn_create(curves[0])
+    ctx.dyn_async(c, d_rows, stride, d_len, 4, d_which, dyn_res[0][0], out_stride, *dyn_res[0][1:])
+    ctx.dyn_free(c)
+    d = ctx.dyn_create(curves[1])
+    ctx.dyn_async(d, d_rows, stride, d_len, 4, d_which, dyn_res[1][0], out_stride, *dyn_res[1][1:])
+    ctx.sync()
+    ctx.iir_free(b)
+    ctx.dyn_free(d)
+    outs = []
+    for k in range(2):
+        want = iir_model(rows, filters[k], which, tail)
+        out = dev.down(iir_res[k][0], (4, out_stride), np.float32)
+        _rows_equal(out, [w[0] for w in want], ("iir", k))
+        assert np.array_equal(dev.down(iir_res[k][1], 4, np.uint32), [w[1] for w in want])
+        assert np.array_equal(dev.down(iir_res[k][2], 4, np.uint32), [w[2] for w in want])
+        outs.append(out)
+        want = M.dyn_model(rows, curves[k], which)
+        out = dev.down(dyn_res[k][0], (4, out_stride), np.float32)
+        _rows_equal(out, [w[0] for w in want], ("dyn", k))
+        assert np.array_equal(dev.down(dyn_res[k][1], 4, np.uint32), [w[1] for w in want])
+        assert np.array_equal(dev.down(dyn_res[k][2], 4, np.uint32), [w[2] for w in want])
+        assert same_bits(dev.down(dyn_res[k][3], 4, np.float64), np.array([w[3] for w in want], np.float64))
+        outs.append(out)
+    assert not np.array_equal(outs[0].view(np.uint32), outs[2].view(np.uint32))
+    assert not np.array_equal(outs[1].view(np.uint32), outs[3].view(np.uint32))
+
+
+def test_the_rows_of_a_stream_follow_the_indices_given_at_its_opening(ctx, dev):
+    """an IIR stream and a dynamics stream opened with the caller's filter, curve and key_row arrays, which are written over the
+    moment the open returns, and the streams fed at once: every row runs through what its index said at the opening"""
+    rng = np.random.default_rng(53)
+    n_rows, n, stride = 70, 150, 192
+    filters = [random_filter(S, rng) for S in (1, 2, 3)]
+    curves = three_curves()
+    rows = [_noise(rng, n) for _ in range(n_rows)]
+    keys = [_noise(rng, n) for _ in range(n_rows)]
+    which = rng.integers(0, 3, n_rows).astype(np.uint32)
+    key_row = rng.permutation(n_rows).astype(np.uint32)
+    given = (which.copy(), which.copy(), key_row.copy())
+    d_rows, d_len = _up(dev, rows, stride)
+    d_keys, _ = _up(dev, keys, stride)
+    d_iir, d_dyn = _canary(dev, n_rows, stride), _canary(dev, n_rows, stride)
+    res = [dev.alloc(n_rows * 4) for _ in range(4)] + [dev.alloc(n_rows * 8)]
+    iir_set, dyn_set = ctx.iir_create(filters), ctx.dyn_create(curves)
+    streams = []
+    try:
+        streams.append(("iir", ctx.iir_stream_open(iir_set, n_rows, given[0], 0)))
+        given[0][:] = (given[0] + 1) % 3
+        streams.append(("dyn", ctx.dyn_stream_open(dyn_set, n_rows, given[1], n_rows, given[2])))
+        given[1][:] = (given[1] + 1) % 3
+        given[2][:] = given[2][::-1].copy()
+        ctx.iir_stream_next_async(streams[0][1], d_rows, stride, d_len, d_iir, stride, res[0], res[1])
+        ctx.dyn_stream_next_async(streams[1][1], d_rows, stride, d_len, d_dyn, stride, res[2], res[3], res[4], key_dev=d_keys, key_stride=stride)
+        ctx.sync()
+    finally:
+        for kind, st in streams:
+            (ctx.iir_stream_close if kind == "iir" else ctx.dyn_stream_close)(st)
+        ctx.iir_free(iir_set)
+        ctx.dyn_free(dyn_set)
+    assert not np.array_equal(given[0], which) and not np.array_equal(given[2], key_row)
+    want = iir_model(rows, filters, which.tolist())
+    _rows_equal(dev.down(d_iir, (n_rows, stride), np.float32), [w[0] for w in want], "iir stream")
+    assert np.array_equal(dev.down(res[0], n_rows, np.uint32), [n] * n_rows)
+    assert np.array_equal(dev.down(res[1], n_rows, np.uint32), [w[2] for w in want])
+    want = M.dyn_model(rows, curves, which.tolist(), keys=keys, key_row=key_row.tolist())
+    _rows_equal(dev.down(d_dyn, (n_rows, stride), np.float32), [w[0] for w in want], "dyn stream")
+    assert np.array_equal(dev.down(res[3], n_rows, np.uint32), [w[2] for w in want])
+    assert same_bits(dev.down(res[4], n_rows, np.float64), np.array([w[3] for w in want], np.float64))
+
+
+def test_lengths_flow_on_the_device_through_a_recursive_filter_and_a_compressor(ctx, dev):
+    """rows band-passed, equalised and compressed, twice (once a lane a row, once a workgroup a row): the recursive filter reads
+    the lengths the band-pass wrote on the device and writes its own, with the tail, for both dynamics calls to read; the
+    host sees none of them before the one wait"""
+    rng = np.random.default_rng(54)
+    K, origin, tail, n = 33, 16, 75, 5
+    h = rng.uniform(-1.0, 1.0, K).astype(np.float32)
+    filters, curves = [random_filter(3, rng)], three_curves()
+    rows = [_noise(rng, k) for k in (1200, 64, 0, 777, 1)]
+    stride, fir_stride, iir_stride = 1216, 1280, 1344
+    d_rows, d_len = _up(dev, rows, stride)
+    d_fir, d_iir, d_dyn, d_track = (_canary(dev, n, s) for s in (fir_stride, iir_stride, iir_stride, iir_stride))
+    d_fir_len, d_iir_len, d_dyn_len, d_track_len = (dev.alloc(n * 4) for _ in range(4))
+    d_bad = [dev.alloc(n * 4) for _ in range(4)]
+    d_gain = [dev.alloc(n * 8) for _ in range(2)]
+    fir_set, iir_set, dyn_set = ctx.fir_create([(h, origin)]), ctx.iir_create(filters), ctx.dyn_create(curves)
+    try:
+        ctx.fir_async(fir_set, d_rows, stride, d_len, n, None, d_fir, fir_stride, d_fir_len, d_bad[0])
+        ctx.iir_async(iir_set, d_fir, fir_stride, d_fir_len, n, None, tail, d_iir, iir_stride, d_iir_len, d_bad[1])
+        ctx.dyn_async(dyn_set, d_iir, iir_stride, d_iir_len, n, None, d_dyn, iir_stride, d_dyn_len, d_bad[2], d_gain[0])
+        ctx.track_dyn_async(dyn_set, d_iir, iir_stride, d_iir_len, n, None, d_track, iir_stride, d_track_len, d_bad[3], d_gain[1])
+        ctx.sync()
+    finally:
+        ctx.fir_free(fir_set)
+        ctx.iir_free(iir_set)
+        ctx.dyn_free(dyn_set)
+    u32 = lambda p: dev.down(p, n, np.uint32)
+    fir, iir = dev.down(d_fir, (n, fir_stride), np.float32), dev.down(d_iir, (n, iir_stride), np.float32)
+    fir_len, iir_len = u32(d_fir_len), u32(d_iir_len)
+    want = [fir_model(x, h, origin) for x in rows]
+    _rows_equal(fir, [w[0] for w in want], "fir")
+    assert np.array_equal(fir_len, [w[1] for w in want]) and np.array_equal(u32(d_bad[0]), [w[2] for w in want])
+    assert fir_len.max() > 1200 and 0 in fir_len
+    filtered = [fir[i, :fir_len[i]] for i in range(n)]
+    want = iir_model(filtered, filters, None, tail)
+    _rows_equal(iir, [w[0] for w in want], "iir")
+    assert np.array_equal(iir_len, [w[1] for w in want]) and np.array_equal(u32(d_bad[1]), [0] * n)
+    assert iir_len.tolist() == [k + tail if k else 0 for k in fir_len]
+    equalised = [iir[i, :iir_len[i]] for i in range(n)]
+    want = M.dyn_model(equalised, curves)
+    for d_out, d_out_len, d_b, d_g, what in ((d_dyn, d_dyn_len, d_bad[2], d_gain[0], "dyn"), (d_track, d_track_len, d_bad[3], d_gain[1], "track dyn")):
+        _rows_equal(dev.down(d_out, (n, iir_stride), np.float32), [w[0] for w in want], what)
+        assert np.array_equal(u32(d_out_len), iir_len) and np.array_equal(u32(d_b), [0] * n), what
+        assert same_bits(dev.down(d_g, n, np.float64), np.array([w[3] for w in want], np.float64)), what

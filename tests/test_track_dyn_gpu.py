@@ -4,7 +4,7 @@ contract of its own.  The shapes are the new kernel's: with T = TRACK_TILE read 
 side of one, two, three and five tiles (the three-stage pipeline fills, runs full and drains) in calls of 1, 2, 13 and 70 rows;
 non-finite samples at a tile's first sample, its last, in between and in the last, partial tile; outputs cut inside a tile and
 exactly on a tile's edge with the row's smallest gain behind the cut; the 4-byte path against the 16-byte one; keys that end
-inside a tile and keys longer than their rows; refused rows; gains that compare equal with different sign bits in different
+inside a tile and keys longer than their rows; keys of no samples; refused rows; gains that compare equal with different sign bits in different
 lanes and tiles; a row of 300 001 samples against grail_dyn_async on the same buffers; the calls that queue nothing; and the
 dialogue example with --compress-tracks.  Every output buffer holds a canary wherever nothing may be written."""
 import ctypes as C
@@ -18,12 +18,20 @@ import pytest
 import dyn_model as M
 import grail_hip as G
 from test_dyn_gpu import audio, edge_samples, same, same_bits, sets, staircase, three_curves  # noqa: F401  (sets is a fixture)
+from test_dyn_gpu import variant as dyn_variant
 from test_levels_gpu import CANARY, Dev, dev  # noqa: F401  (dev is a fixture)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 T = int(re.search(r"constexpr uint32_t TRACK_TILE = (\d+);", open(os.path.join(ROOT, "grail-rs_amd", "csrc", "dyn_plan.h")).read()).group(1))
 LENGTHS = [0, 1, 63, 64, 65, T - 1, T, T + 1, 2 * T - 1, 2 * T, 2 * T + 1, 3 * T + 5, 5 * T + 1]
+# track_env_kernel<VEC, KEYED>: the four that tests/test_track_dyn_code_objects.py finds in the library
+VARIANTS = [(vec, keyed) for vec in (True, False) for keyed in (False, True)]
+
+
+def variant(in_offset=0, stride=0, out_offset=0, out_stride=0, keyed=False, key_offset=0, key_stride=0):
+    """the track_env_kernel<VEC, KEYED> that launch_track_dyn starts: test_dyn_gpu.variant's rule without the streams"""
+    return dyn_variant(in_offset, stride, out_offset, out_stride, keyed, key_offset, key_stride)[:2]
 
 
 def pad64(n):
@@ -50,8 +58,8 @@ def run(ctx, dev, dyn_set, rows, which=None, keys=None, key_row=None, key_lens=N
     if self_key:
         kw = dict(key_dev=d_in, key_stride=stride, n_keys=len(rows), key_len_dev=d_len, key_row_dev=None)
     elif keys is not None:
-        key_stride = key_stride or pad64(max([len(k) for k in keys] + [1]))
-        khost = np.full(len(keys) * key_stride + key_offset, np.nan, np.float32)
+        key_stride = pad64(max([len(k) for k in keys] + [1])) if key_stride is None else key_stride
+        khost = np.full(max(len(keys) * key_stride + key_offset, 4), np.nan, np.float32)          # (key_stride 0: keys of no samples)
         for j, k in enumerate(keys):
             khost[key_offset + j * key_stride:key_offset + j * key_stride + len(k)] = k
         kw = dict(key_dev=C.c_void_p(dev.up(khost).value + key_offset * 4), key_stride=key_stride, n_keys=len(keys),
@@ -241,6 +249,26 @@ def test_a_row_may_be_its_own_key(gpu_ctx, dev, sets):
     want = M.dyn_model(rows, curves, [0, 1, 2])
     same(want, run(gpu_ctx, dev, dyn_set, rows, [0, 1, 2]), "self-keyed")
     same(want, run(gpu_ctx, dev, dyn_set, rows, [0, 1, 2], self_key=True), "keyed by rows_dev")
+
+
+def test_keys_of_no_samples(gpu_ctx, dev, sets):
+    """key_stride 0 (keys of no samples): `key_loads` is false, no worker loads a key sample, every one reads +0.0 and the gain
+    is the curve's at e = +0.0 over one tile, two and a partial third, on either path.  No other case runs the keyed kernel
+    without a key load."""
+    rng = np.random.default_rng(16)
+    curves = three_curves()
+    rows = [audio(n, rng) for n in (2 * T + 77, T, 0, 65)]
+    rows[0][T] = np.nan
+    which = [0, 1, 2, 2]
+    nothing = [np.zeros(0, np.float32)]
+    want = M.dyn_model(rows, curves, which, keys=nothing, key_row=[0] * 4)
+    at_rest = [float(np.asarray(curves[c][0], np.float64)[0]) for c in which]          # (e = +0.0 lies below the table: G[0] itself)
+    assert [w[3] for w in want] == [g if len(x) else 1.0 for g, x in zip(at_rest, rows)]
+    dyn_set = sets(curves)
+    wide = 2 * T + 128
+    for kw, vec in ((dict(stride=wide, out_stride=wide), True), (dict(stride=wide, out_stride=wide, out_offset=1), False)):
+        assert variant(0, wide, kw.get("out_offset", 0), wide, True, 0, 0) == (vec, True)
+        same(want, run(gpu_ctx, dev, dyn_set, rows, which, keys=nothing, key_row=[0] * 4, key_stride=0, **kw), ("no key samples", kw))
 
 
 # ---- gains that compare equal ------------------------------------------------------------------------------------------------
