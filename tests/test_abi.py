@@ -304,6 +304,49 @@ def test_the_signature_check_catches_a_swapped_width_a_dropped_parameter_and_a_l
         assert len(diffs) == 1 and diffs[0].startswith(where), (where, diffs)
 
 
+# ---- the ctypes signatures against the header -------------------------------------------------------------------------
+# Both sides are brought to classes of kind and width: "ptr", "void", u32 / u64 / i32 / i64 / f32 / f64.  ctypes types are
+# classed by their type code and sizeof, never by identity: c_size_t, c_uint64 and c_ulong are one class object here.
+def _header_class(ty):
+    if ty is None:
+        return "void"
+    base, levels = ty
+    return "ptr" if levels else {"c_int": "i32", "usize": "u64"}.get(base, base)
+
+
+def _ctypes_class(t):
+    if t is None:
+        return "void"
+    code = getattr(t, "_type_", None)
+    if not isinstance(code, str) or code in "Pz":               # POINTER(...) and arrays; c_void_p, c_char_p
+        return "ptr"
+    kind = "f" if code in "fd" else "i" if code in "bhilq" else "u" if code in "BHILQ" else code
+    return f"{kind}{8 * C.sizeof(t)}"
+
+
+def binding_differences(lib):
+    """`name: header [...] binding [...]` for every function whose restype and argtypes, as load() set them, are not the
+    header's prototype class by class (the return class first)."""
+    assert C.sizeof(C.c_size_t) == 8                            # what lets size_t pass for u64 above
+    c_funcs, _ = c_header_model()
+    assert sorted(c_funcs) == header_functions() == sorted(G.EXPORTS), "a prototype the parser skipped, or a row missing"
+    diffs = []
+    for name, (ret, params) in sorted(c_funcs.items()):
+        fn = getattr(lib, name)
+        header = [_header_class(ret)] + [_header_class(p) for p in params]
+        binding = [_ctypes_class(fn.restype)] + ["unset"] * (fn.argtypes is None) + [_ctypes_class(t) for t in fn.argtypes or []]
+        if header != binding:
+            diffs.append(f"{name}: header {header} binding {binding}")
+    return diffs
+
+
+def test_ctypes_signatures_match_the_header(built):
+    """Every function's restype and argtypes agree with its prototype in include/grail_hip.h: the parameter count, and
+    pointer / integer / float and width of each parameter and of the return value."""
+    diffs = binding_differences(G.load())
+    assert not diffs, "\n".join(diffs)
+
+
 def test_rust_struct_size_asserts_hold_for_the_header(tmp_path):
     """The crate's `const _: () = assert!(size_of::<T>() == N)` literals against what the C compiler gives the header's
     structs (and against the ctypes mirrors the GPU tests call through)."""
