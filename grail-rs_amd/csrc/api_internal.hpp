@@ -41,6 +41,7 @@
 #include "limit_plan.h"
 #include "meter_plan.h"
 #include "resample_plan.h"
+#include "spectrum_plan.h"
 
 // (the opaque types of the C ABI are global; everything else the units share lives in grail::host)
 
@@ -452,6 +453,20 @@ struct grail_dyn {
     grail::host::DeviceBuffer<double> d_image;        // [n_curves][DYN_IMAGE_DOUBLES]
     grail::host::DeviceBuffer<double> d_alpha;        // [n_curves][2]
     grail::host::DeviceBuffer<uint32_t> d_detector;   // [n_curves]
+};
+
+// A set for short-time spectra (transforms.cpp; the checks and the image are spectrum_plan.cpp's): owned by the context's
+// TransformState, released by grail_spectrum_free or with the context.  No stream is ever open on one.
+struct grail_spectrum {
+    grail::SpectrumFacts facts;
+    std::vector<float> window;        // (host copies, kept while the upload may be in flight)
+    std::vector<double> twiddles;
+    std::vector<uint32_t> desc;
+    std::vector<float> weights;
+    grail::host::DeviceBuffer<float> d_window;        // [n_window]
+    grail::host::DeviceBuffer<double> d_twiddles;     // [N/2] pairs (re, im)
+    grail::host::DeviceBuffer<uint32_t> d_desc;       // [max(n_bands, 1)][SPECTRUM_BAND_WORDS]
+    grail::host::DeviceBuffer<float> d_weights;       // the bands' weights one after another
 };
 
 // A stream of rows compressed call by call (dyn_kernels.hip): DYN_STREAM_STATE_WORDS state words a row (samples fed, then the

@@ -437,4 +437,34 @@ hipError_t launch_dyn(const DynArgs &args, hipStream_t stream);
 // state is not read (there is no stream form); more than 2^31 - 1 rows: hipErrorInvalidValue.
 hipError_t launch_track_dyn(const DynArgs &args, hipStream_t stream);
 
+// short-time spectra (spectrum_kernels.hip; the contract is grail_spectrum.h's "levels, continued: short-time spectra", DESIGN.md
+// §4.25): one workgroup per (row, chunk of SPECTRUM_CHUNK_FRAMES frames), grid_chunks = spectrum_grid_chunks(row_stride, hop)
+// of them a row (spectrum_plan.h).  log2n .. n_bands: the set's facts; window: DEVICE [n_window]; twiddles: DEVICE [N/2]
+// pairs (re, im); band_desc: DEVICE [n_bands][4] = {first bin, count, first weight, 0}; band_weights: DEVICE, the bands'
+// weights one after another.  power: [n_rows][frames_stride][N/2 + 1] or NULL; bands: [n_rows][frames_stride][n_bands] or NULL;
+// frames past a row's last are left unwritten.  cbad: the non-finite samples a chunk owns (those of its frames' hops), at
+// [row * grid_chunks + c], or NULL when nobody asks for the count (chunks past a row's last are left unwritten).
+struct SpectrumArgs {
+    const float *rows;
+    uint64_t row_stride;
+    const uint32_t *len;
+    uint32_t n_rows;
+    uint32_t log2n, n_window, hop, pad, n_bands;
+    const float *window;
+    const double *twiddles;
+    const uint32_t *band_desc;
+    const float *band_weights;
+    float *power;
+    float *bands;
+    uint64_t frames_stride;
+    uint32_t grid_chunks;
+    uint32_t *cbad;
+    uint32_t *n_frames;
+    uint32_t *nonfinite;
+};
+// n_rows * grid_chunks is at most 2^31 - 1 (the host has checked)
+hipError_t launch_spectrum(const SpectrumArgs &args, hipStream_t stream);
+// ... and a row's n_frames and count from cbad, one lane per row (outputs may be NULL)
+hipError_t launch_spectrum_totals(const SpectrumArgs &args, hipStream_t stream);
+
 }  // namespace grail

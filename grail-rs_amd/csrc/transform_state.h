@@ -43,7 +43,8 @@ struct ResampleTable {
 // chunks' non-finite counts that a resampling call folds (4 B per chunk of 1024 outputs), the resampler's tables of the
 // last few pairs of rates, the same counts of a filtering call (4 B per chunk of 2048 outputs), the filter sets the caller
 // has created, the block states (16 B per section of the set's bound and block of 1024 steps) and counts of a blocked
-// recursive-filtering call, the curve sets the caller has created, and the streams open (each with its rows' state: api_internal.hpp, ChunkedStream).  A stream's calls use the
+// recursive-filtering call, the curve sets the caller has created, the non-finite counts of a spectrum
+// call (4 B per row and chunk of 8 frames), the spectrum sets the caller has created, and the streams open (each with its rows' state: api_internal.hpp, ChunkedStream).  A stream's calls use the
 // chunk scratch of their kind.
 struct TransformState : CtxPart {
     DeviceBuffer<unsigned char> d_lstat;    // limiter chunks
@@ -64,6 +65,8 @@ struct TransformState : CtxPart {
     Owned<grail_iir_stream> iir_streams;    // ... and, after them (they die first), the IIR streams open on them
     Owned<grail_dyn> dyns;                  // the curve sets alive
     Owned<grail_dyn_stream> dyn_streams;    // ... and, after them (they die first), the dynamics streams open on them
+    DeviceBuffer<uint32_t> d_specbad;       // spectrum chunks (8 frames each): non-finite counts
+    Owned<grail_spectrum> spectra;          // the spectrum sets alive
 };
 
 // what the context has, made by nobody: NULL before the first call that needed it

@@ -3,7 +3,9 @@
 // _free / _async (fir_kernels.hip, a set's checks and image fir_plan.cpp, §4.14) and grail_iir_create / _free / _async
 // (iir_kernels.hip, a set's checks and image iir_plan.cpp, §4.19) and grail_biquad_blocked_async (biquad_block_kernels.hip, its
 // matrices, grid and scratch size iir_plan.cpp, §4.22) and grail_dyn_create / _free / _async (dyn_kernels.hip, a set's checks and
-// image dyn_plan.cpp, §4.23) and grail_track_dyn_async (track_env_kernels.hip, §4.24): their checks, their scratch, their launches.
+// image dyn_plan.cpp, §4.23) and grail_track_dyn_async (track_env_kernels.hip, §4.24) and grail_spectrum_create / _free / _async
+// (spectrum_kernels.hip, a set's checks and image and the call's checks spectrum_plan.cpp, §4.25): their checks, their scratch,
+// their launches.
 // What they check of a pair of rows is row_checks.h.  The same chunk by chunk, on streams, is transform_streams.cpp; what a
 // context keeps for both is transform_state.h.
 #include "row_checks.h"
@@ -333,6 +335,82 @@ int grail_track_dyn_async(grail_ctx *ctx, const grail_dyn *set, const float *row
     a.out = out_dev, a.out_stride = out_stride, a.out_len = out_len_dev, a.nonfinite = nonfinite_dev, a.min_gain = min_gain_dev;
     const hipError_t e = launch_track_dyn(a, ctx->stream);
     if (e != hipSuccess) return hip_fail(e, "track dyn kernel launch");
+    return GRAIL_OK;
+}
+
+int grail_spectrum_create(grail_ctx *ctx, uint32_t log2n, const float *window, uint32_t n_window, uint32_t hop, uint32_t pad,
+                          uint32_t n_bands, const uint32_t *band_first, const uint32_t *band_count, const float *band_weights,
+                          grail_spectrum **out)
+{
+    if (!out) return fail(GRAIL_ERR_INVALID_ARG, "grail_spectrum_create: NULL argument");
+    if (const char *why = spectrum_set_error(log2n, window, n_window, hop, pad, n_bands, band_first, band_count, band_weights))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_spectrum_create: ") + why);
+    int rc = bind_device(ctx, "grail_spectrum_create");
+    if (rc) return rc;
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    std::unique_ptr<grail_spectrum> set(new (std::nothrow) grail_spectrum());
+    if (!set) return fail(GRAIL_ERR_OUT_OF_MEMORY, "spectrum set");
+    set->facts.log2n = log2n, set->facts.n_window = n_window, set->facts.hop = hop, set->facts.pad = pad, set->facts.n_bands = n_bands;
+    set->window.assign(window, window + n_window);
+    spectrum_set_image(log2n, n_bands, band_first, band_count, band_weights, set->twiddles, set->desc, set->weights);
+    HIP_TRY(upload(set->d_window, set->window.data(), set->window.size(), ctx->stream));
+    HIP_TRY(upload(set->d_twiddles, set->twiddles.data(), set->twiddles.size(), ctx->stream));
+    HIP_TRY(upload(set->d_desc, set->desc.data(), set->desc.size(), ctx->stream));
+    HIP_TRY(upload(set->d_weights, set->weights.data(), set->weights.size(), ctx->stream));
+    *out = st->spectra.add(std::move(set));
+    return GRAIL_OK;
+}
+
+// (set_free without its streams: no stream is ever open on a spectrum set)
+int grail_spectrum_free(grail_ctx *ctx, grail_spectrum *set)
+{
+    if (!set) return GRAIL_OK;
+    if (!ctx) return fail(GRAIL_ERR_INVALID_ARG, "grail_spectrum_free: ctx is NULL");
+    if (!own(ctx, &TransformState::spectra, set)) return fail(GRAIL_ERR_INVALID_ARG, "grail_spectrum_free: not a spectrum set of this context");
+    // (a kernel or the upload still queued may be reading it)
+    int rc = bind(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    peek(ctx)->spectra.remove(set);
+    return GRAIL_OK;
+}
+
+int grail_spectrum_async(grail_ctx *ctx, const grail_spectrum *set, const float *rows_dev, uint64_t row_stride, const uint32_t *len_dev,
+                         uint32_t n_rows, float *power_dev, float *bands_dev, uint64_t frames_stride, uint32_t *n_frames_dev,
+                         uint32_t *nonfinite_dev)
+{
+    if (!set) return fail(GRAIL_ERR_INVALID_ARG, "grail_spectrum_async: set is NULL");
+    if (ctx && !own(ctx, &TransformState::spectra, set))
+        return fail(GRAIL_ERR_INVALID_ARG, "grail_spectrum_async: not a spectrum set of this context");
+    // (without a context the set was not looked up and is not looked into: the checks that need its facts are left out, and
+    // the call ends at bind_device)
+    if (const char *why = spectrum_call_error(ctx ? &set->facts : nullptr, rows_dev, row_stride, len_dev, n_rows, power_dev, bands_dev,
+                                              frames_stride))
+        return fail(GRAIL_ERR_INVALID_ARG, std::string("grail_spectrum_async: ") + why);
+    int rc = bind_device(ctx, "grail_spectrum_async");
+    if (rc) return rc;
+    if (n_rows == 0) return GRAIL_OK;
+    if (row_stride == 0 && !n_frames_dev && !nonfinite_dev) return GRAIL_OK;    // (rows of no samples, and nobody asks)
+    TransformState *st;
+    if ((rc = state(ctx, &st))) return rc;
+    const SpectrumFacts &f = set->facts;
+    const uint64_t chunks = spectrum_grid_chunks(row_stride, f.hop);
+    if (chunks && nonfinite_dev && (rc = st->d_specbad.reserve(ctx->stream, (size_t)n_rows * (size_t)chunks))) return rc;
+    SpectrumArgs a = {};
+    a.rows = rows_dev, a.row_stride = row_stride, a.len = len_dev, a.n_rows = n_rows;
+    a.log2n = f.log2n, a.n_window = f.n_window, a.hop = f.hop, a.pad = f.pad, a.n_bands = f.n_bands;
+    a.window = set->d_window.get(), a.twiddles = set->d_twiddles.get(), a.band_desc = set->d_desc.get();
+    a.band_weights = set->d_weights.get(), a.power = power_dev, a.bands = bands_dev, a.frames_stride = frames_stride;
+    a.grid_chunks = (uint32_t)chunks, a.cbad = chunks && nonfinite_dev ? st->d_specbad.get() : nullptr;
+    a.n_frames = n_frames_dev, a.nonfinite = nonfinite_dev;
+    if (chunks) {               // (rows of no samples: 0, 0 from the totals alone)
+        const hipError_t e = launch_spectrum(a, ctx->stream);
+        if (e != hipSuccess) return hip_fail(e, "spectrum kernel launch");
+    }
+    if (!n_frames_dev && !nonfinite_dev) return GRAIL_OK;
+    const hipError_t e = launch_spectrum_totals(a, ctx->stream);
+    if (e != hipSuccess) return hip_fail(e, "spectrum totals kernel launch");
     return GRAIL_OK;
 }
 

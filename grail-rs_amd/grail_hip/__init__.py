@@ -27,6 +27,8 @@ from .host import *                                                         # no
 from .host import _mix_items                                                # noqa: F401
 from .device import *                                                       # noqa: F401,F403
 from .device import _BorrowedContext, _coef10, _marks, _per, _waited        # noqa: F401
+# include/grail_spectrum.h (short-time spectra) is the submodule grail_hip.spectrum and adds no name here: see its docstring
+from . import spectrum                                                      # noqa: F401
 
 
 def __getattr__(name):

@@ -367,6 +367,10 @@ def _signatures():
 _SIGNATURES = _signatures()
 EXPORTS = list(_SIGNATURES)
 
+# ... and of every symbol a header declares that grail_hip.h includes (include/grail_spectrum.h: grail_hip.spectrum brings its table
+# with _also_declares when it is imported, which the package does); load() sets these the same way, so there is one path
+_INCLUDED_SIGNATURES = {}
+
 _lib = None
 
 
@@ -376,8 +380,17 @@ def lib_exists():
 
 def _declare(L, name):
     fn = getattr(L, name)
-    fn.restype, fn.argtypes = _SIGNATURES[name]
+    fn.restype, fn.argtypes = _SIGNATURES[name] if name in _SIGNATURES else _INCLUDED_SIGNATURES[name]
     return fn
+
+
+def _also_declares(table):
+    """a module's own signature table joins what load() declares (on the library at once, if it is loaded already)"""
+    assert not set(table) & set(_SIGNATURES)
+    _INCLUDED_SIGNATURES.update(table)
+    if _lib is not None:
+        for name in table:
+            _declare(_lib, name)
 
 
 def load():
@@ -393,7 +406,7 @@ def load():
     if version != ABI_VERSION:
         raise GrailError(ERR_INVALID_ARG, f"{LIB_PATH} has ABI version {version}, this binding "
                                           f"mirrors version {ABI_VERSION} of include/grail_hip.h: rebuild the library")
-    for name in _SIGNATURES:
+    for name in list(_SIGNATURES) + list(_INCLUDED_SIGNATURES):
         _declare(L, name)
     _lib = L
     return L

@@ -5,6 +5,9 @@
 #![allow(non_camel_case_types)]
 use std::os::raw::{c_char, c_int};
 
+/// `include/grail_spectrum.h`, which `grail_hip.h` includes at its end: short-time spectra of rows.
+pub mod spectrum;
+
 pub const GRAIL_NUM_FORMANTS: usize = 8;
 pub const GRAIL_NUM_VOICED: usize = 2;
 pub const GRAIL_UNIQUE_ID_BYTES: usize = 128;

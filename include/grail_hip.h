@@ -1801,4 +1801,8 @@ int grail_node_host_free(grail_node *node, void *ptr);
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- levels, continued: short-time spectra (STFT power and mel bands of rows): a header of its own, a part of this one --- */
+#include "grail_spectrum.h"
+
 #endif /* GRAIL_HIP_H */
